@@ -17,6 +17,9 @@ The JSON line also carries
                   against the 8 TB/s HBM3E peak;
   cpu_baseline -- the reference-structured CPU oracle (kind "port", 1 thread) timed on this box's host
                   cores on a bounded sample (rank 0, N = 1 only).
+
+`--dump-outputs DIR` writes what the last timed step computed to DIR/*.npy (dump_outputs) for output-for-output
+comparison of two builds; the inputs depend on the arguments only (committed fixture, seeded device generator).
 """
 import argparse
 import importlib
@@ -35,6 +38,8 @@ FLOP_PER_SITE = 176          # 8 nc^2 * 5 + 8 nc, nc = 2
 BYTES_PER_SITE = 384         # 5 nc^2 c + 2 nc c, c = 16 B
 HBM_PEAK_GBS = 8000.0        # MI355X_MICROARCH.md: 8.0 TB/s spec (6.29 TB/s measured copy)
 MASS = -0.07                 # beta = 6.0, m_crit ~ -0.0706
+DUMP_BUDGET_BYTES = 64 * 10**6  # --dump-outputs: every file of one run together
+DUMP_SEED = 4242             # positions of the fixed sample of an output too large to write whole
 
 
 def site_index_grid(Lx, Ly):
@@ -189,6 +194,32 @@ def timed(qmg, wl, steps, warmup, barrier):
     barrier()
     wall = time.perf_counter() - t0
     return wall, ev_ms / steps
+
+
+def dump_outputs(out_dir, arrays, rank, world):
+    """`--dump-outputs DIR`: what the timed path left in its last step, one DIR/<name>.npy per output in float64 (a complex
+    array as [n, 2] = re, im), so that two builds run with the same arguments can be compared element for element.  The
+    budget of 64 * 10^6 bytes is shared by all outputs of all ranks; an output larger than its share is written as a fixed
+    sample: the same seeded positions in every run, ascending, stored beside it as DIR/<name>_index.npy (float64, exact
+    below 2^53).  With more than one rank every file name carries _rank<r>.  Returns what was written, for the JSON line."""
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // (world * len(arrays)) - 4096      # 4 KiB per output for the two .npy headers
+    suffix = "_rank%d" % rank if world > 1 else ""
+    written = {}
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a).reshape(-1)
+        vals = a.astype(np.complex128).view(np.float64).reshape(-1, 2) if np.iscomplexobj(a) else a.astype(np.float64)
+        entry = {"file": name + suffix + ".npy", "elements": int(a.size)}
+        if vals.nbytes > share:
+            per = vals.itemsize * (2 if vals.ndim == 2 else 1) + 8     # values + index of one element
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(a.size, size=share // per, replace=False))
+            vals = vals[idx]
+            np.save(os.path.join(out_dir, name + suffix + "_index.npy"), idx.astype(np.float64))
+            entry["sample"] = int(idx.size)
+            entry["index_file"] = name + suffix + "_index.npy"
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), vals)
+        written[name] = entry
+    return {"dir": out_dir, "outputs": written}
 
 
 def cpu_baseline(fixture, budget_s=12.0):
@@ -716,17 +747,25 @@ def self_launch(n, argv):
     for r in range(n):
         env = dict(base, RANK=str(r), LOCAL_RANK=str(r), GROUP_RANK="0", LOCAL_WORLD_SIZE=str(n))
         procs.append(subprocess.Popen([sys.executable, os.path.abspath(__file__)] + argv, env=env, stdout=subprocess.PIPE if r == 0 else subprocess.DEVNULL, text=True))
-    out0 = ""
+    import threading
+    chunks = []
+    reader = threading.Thread(target=lambda: chunks.append(procs[0].stdout.read()), daemon=True)
+    reader.start()
     rc = 0
     try:
-        out0, _ = procs[0].communicate()
-        for pr in procs:
-            pr.wait()
+        # watch every child, not only rank 0: the others may be waiting in the rendezvous for the one that died
+        while True:
+            codes = [pr.poll() for pr in procs]
+            if all(c is not None for c in codes) or any(codes):
+                break
+            time.sleep(0.1)
     finally:
         for pr in procs:
             if pr.poll() is None:
                 pr.kill()
-                pr.wait()
+            pr.wait()
+        reader.join()
+    out0 = "".join(chunks)
     for pr in procs:
         if pr.returncode != 0:
             rc = pr.returncode if pr.returncode > 0 else 1
@@ -737,11 +776,12 @@ def self_launch(n, argv):
 
 def launch_check(rank, world):
     """Smallest end-to-end exercise of the launch path: every rank joins the process group the launcher's environment describes
-    (RCCL when a GPU is visible, gloo otherwise), ONE sum all-reduce of a one per rank, rank 0 prints what the collective saw.
-    `collective_ranks` == n_gpus proves that `world` ranks took part in a real collective.  CPU test: tests/test_distributed_cpu.py."""
+    (RCCL when there is a GPU for every rank, gloo otherwise), ONE sum all-reduce of a one per rank, rank 0 prints what the
+    collective saw.  `collective_ranks` == n_gpus proves that `world` ranks took part in a real collective.  CPU test:
+    tests/test_distributed_cpu.py."""
     import torch
     import torch.distributed as dist
-    on_gpu = torch.cuda.is_available()
+    on_gpu = torch.cuda.is_available() and torch.cuda.device_count() >= world
     if on_gpu:
         torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", "0")))
         dist.init_process_group("nccl", device_id=torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0"))))
@@ -771,7 +811,13 @@ def main():
     ap.add_argument("--nrhs", type=int, default=8)
     ap.add_argument("--cpu-worker", nargs=2, metavar=("L", "BUDGET_S"), help="internal: one CPU-oracle apply loop (cpu_baseline_all_cores)")
     ap.add_argument("--launch-check", action="store_true", help="only the launch path: N ranks join one process group (RCCL on GPUs, gloo on a CPU box), one all-reduce, one JSON line")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last timed step computed as DIR/<name>.npy "
+                                                          "(float64, at most 64 MB in all; a fixed seeded sample of a larger output)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.workload == "kcycle":
+        ap.error("--dump-outputs: the kcycle workload solves in a driver process that returns no arrays to bench.py")
     if args.cpu_worker:
         cpu_worker(int(args.cpu_worker[0]), float(args.cpu_worker[1]))
         return
@@ -851,6 +897,7 @@ def main():
         wl = StaggeredMultiRHS(qmg, L, fixture, 1337 + rank, args.nrhs, rank, world, dist, torch)
         gate_err = wl.parity_gate(fixture)
         wall, kern_ms = timed(qmg, wl, args.steps, args.warmup, barrier)
+        dumped = dump_outputs(args.dump_outputs, {"lhs": wl.lhs.to_host(), "norms": wl.norms.cpu().numpy()}, rank, world) if args.dump_outputs else None
         wall = sharding.max_over_ranks(wall, dist, "cuda")
         sites_rhs = L * L * args.nrhs
         out = {"metric": "staggered multi-RHS Dslash throughput", "value": world * sites_rhs * wl.FLOP_PER_SITE_RHS * args.steps / wall / 1e9,
@@ -863,6 +910,8 @@ def main():
                             "kernel": "k_stencil_pair<double,1,2,NORM,PF> (nrhs loop, fused norms) + k_apply_norm_final",
                             "note": "whole step in one pass: apply with fused per-RHS norms, 64/nrhs + 32 B/site/rhs (a separate norm2sq would re-read 16)"},
                "parity_gate_rel_l2": gate_err}
+        if dumped:
+            out["dump_outputs"] = dumped
         if rank == 0:
             print(json.dumps(out), flush=True)
         if dist is not None:
@@ -872,6 +921,7 @@ def main():
     wl = Workload(qmg, L, fixture, seed=1337 + rank)
     gate_err = wl.parity_gate(fixture)
     wall, kern_ms = timed(qmg, wl, args.steps, args.warmup, barrier)
+    dumped = dump_outputs(args.dump_outputs, {"lhs": wl.lhs.to_host()}, rank, world) if args.dump_outputs else None
 
     wall = sharding.max_over_ranks(wall, dist, "cuda")
     sites = L * L
@@ -890,6 +940,8 @@ def main():
         "hbm_gb_per_s_aggregate": world * BYTES_PER_SITE * sites * args.steps / wall / 1e9,
         "parity_gate_rel_l2": gate_err,
     }
+    if dumped:
+        out["dump_outputs"] = dumped
     # HBM traffic per launch from the committed rocprofv3 PMC passes of this same command (profiles/), collected separately
     # because counters cannot be read from inside the timed run -- and only if they belong to the kernel source in use
     out["roofline"]["traffic"], out["roofline"]["traffic_source"] = pmc_traffic(L)
