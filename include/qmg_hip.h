@@ -438,38 +438,24 @@ int qmg_wilson_hops_direct(int dtype, const qmg_stencil_desc* d, const void* gau
 
 /* ---------------- tuning hooks (not part of the reference surface) ---------------- */
 /* Dispatch / codegen knobs, all with the defaults the measurements in profiles/ chose; results never depend on them
- * beyond summation order.  Unknown keys return QMG_ERR_INVALID.
- *   "stencil_nt"    bit 0: non-temporal loads of the stencil matrices, bit 1: non-temporal stores, nc <= 4 kernels (3)
- *   "stencil_pair"  0: one site per lane group (kernel A); 1 / 2: both parities of a column on 1 / 2 rows per lane group (2)
+ * beyond summation order.  Unknown keys, and values a key does not take, return QMG_ERR_INVALID.
+ *   "stencil_pair"  0: one site per lane group (kernel A); 2: fp64, both parities of a column on 2 rows per lane group (1 row where
+ *                   Ly is odd) (2)
  *   "pair_prefetch" 1: fp64 batches with nc = 1 request system k+1's right-hand side ahead of system k's arithmetic (1)
  *   "blas_nt_mb"    BLAS-1 kernels read their read-only operands non-temporally from vectors of this many MiB upwards, 0 = never (256)
- *   "stencil_rows"  cap on gridDim.y of the stencil kernels, 0 = one block row per lattice row (0)
  *   "stencil_mfma"  1: multi-rhs coarse applies (nc in 8,12,16,24,32; >= 4-5 systems) on the f64 matrix cores, 2-MFMA
  *                   packing for <= 8 systems; 2: plain 4-MFMA products; 0: vector-FMA kernel B only (1)
- *   "gen_sites"     cap on sites per block of kernel B, 0 = register-limited maximum (0)
- *   "gen32"         fp32-stored matrices, even nc: 1 = fp32 tile end to end (kernel B32), 2 = same with 2-site tiles,
- *                   0 = kernel B with widening loads (1)
  *   "stencil_site"  nc = 2 through the site kernel (csrc/qmg_site.hip): bit 0 fp64 where it is the faster one (hops-only,
  *                   one system), bit 1 fp32, bit 2 fp64 always (A/B measurements) (3)
- *   "site_block"    threads per block of the site kernel: 64, 128 or 256 (256); "site_gy": cap on its grid.y, 0 = rows (0);
- *                   "site_generic": 1 = its run-time-flag variant instead of the compile-time piece shapes (0)
- *   "mfma_vl"       kernel C: right-hand sides through an LDS slice (coalesced loads / stores) (1)
- *   "mfma_pair8"    kernel C at nc = 8 with 5-8 systems: a wavefront owns two adjacent sites (block-diagonal 16 x 16 tile) (1)
  *   "wilson_pair"   the full Wilson operator from the links: 0 = one site per lane group (kernel W), 1 = both parities of a column
  *                   (kernel W2), 2 = W2 on two rows per lane group for one system on an even run of rows, else as 1 (2)
- *   "xfer_pack"     1: complex<float> single-system restrict / prolong move two elements per lane (16-byte accesses) (1)
- *   "xfer_tile"     1: batched restrict / prolong as LDS-tiled kernels; 0: the one-system kernels, system by system (1)
- *   "xfer_mfma"     batched restrict / prolong (2-16 systems) as contractions on the f64 matrix cores (even block width, <= 32 null vectors, a
- *                   chunk of the tile within 60 KB of LDS): 1 = where that is the faster kernel (the complex<float> restrict), 2 = every served
- *                   shape, 0 = never (1)
  *   "setup_fused"   1: block-local setup kernels (block orthonormalisation in LDS, Galerkin build as per-block products);
  *                   0: the full-lattice restrict / prolong / probe passes of the reference's formulation (1)
  *   "malloc_poison" 1: qmg_malloc fills every allocation with 0xFF bytes (NaNs in every storage precision): a buffer read before
  *                   it is written then shows deterministically (0)
  *   "reduce_spin"   1: the host picks the results of the batch reductions (qmg_batch_reduce*, qmg_batch_multidot*) up by polling a sequence
  *                   number the final stage's last block publishes in coherent host memory behind them; the stream is NOT synchronised by
- *                   these calls then (later launches are ordered behind the kernel anyway).  0: hipStreamSynchronize, as before (1)
- * (The ablation switch of tools/variants.py exists only in the tools build, `make DIAG=1`; this library has no such key.) */
+ *                   these calls then (later launches are ordered behind the kernel anyway).  0: hipStreamSynchronize, as before (1) */
 /* (QMG_TUNING="key=value,key=value" in the environment applies the same settings inside qmg_init -- for A/B runs of programs that do not call this.) */
 int qmg_set_tuning(const char* key, int value);
 

@@ -266,12 +266,8 @@ void release_blas_workspace();
 void release_batch_workspace();
 void release_stencil_workspace();
 extern int g_setup_fused; // qmg_setup.hip; "setup_fused"
-extern int g_wilson_pair;
-extern long g_blas_nt_bytes;   // qmg_blas.hip; "blas_nt_mb"   // qmg_wilson.hip; "wilson_pair"
-extern int g_xfer_mfma;   // qmg_transfer_mfma.hip; "xfer_mfma"
-extern int g_xfer_pack;   // qmg_transfer.hip; "xfer_pack"
-extern int g_xfer_tile;   // qmg_transfer.hip; set through qmg_set_tuning("xfer_tile", v)
-extern int g_site_block, g_site_gy, g_site_generic;   // qmg_site.hip; "site_block", "site_gy", "site_generic"
+extern int g_wilson_pair;      // qmg_wilson.hip; "wilson_pair"
+extern long g_blas_nt_bytes;   // qmg_blas.hip; "blas_nt_mb"
 
 // Memory-bound 1-D launches.  One 16-byte element per thread up to 2^18 blocks, grid-stride beyond: on this part a
 // streaming copy reaches 6.2 TB/s at 262 144 blocks but only 5.4 TB/s at 8 192 (profiles/r01_membw_ceiling.txt).

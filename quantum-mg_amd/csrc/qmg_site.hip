@@ -228,12 +228,8 @@ __global__ __launch_bounds__(BLOCK) void k_from_half(void* __restrict__ dst, con
   }
 }
 
-int g_site_block = BLOCK, g_site_gy = 0;
-int g_site_generic = 0;   // "site_generic": 1 forces the run-time-flag kernel (SHAPE 0)
-
 template <int ST, bool BATCH>
 static void launch_site_b(const SiteArgs& a, int shape, bool zero, dim3 grid, hipStream_t st) {
-  const int BLOCK = g_site_block;
   if (shape == 1) { if (zero) k_stencil_site<ST, 1, true, BATCH><<<grid, BLOCK, 0, st>>>(a); else k_stencil_site<ST, 1, false, BATCH><<<grid, BLOCK, 0, st>>>(a); }
   else if (shape == 2) { if (zero) k_stencil_site<ST, 2, true, BATCH><<<grid, BLOCK, 0, st>>>(a); else k_stencil_site<ST, 2, false, BATCH><<<grid, BLOCK, 0, st>>>(a); }
   else k_stencil_site<ST, 0, false, BATCH><<<grid, BLOCK, 0, st>>>(a);
@@ -287,12 +283,10 @@ int site_kernel_apply(int storage, const qmg_stencil_desc* d, void* lhs, const v
   }
   int shape = (a.par_count == 2 && sh[0] != sh[1]) ? 0 : sh[0];
   if (only_where_faster && storage == 2 && !(n == 1 && shape == 2)) return SITE_DECLINED;
-  if (g_site_generic) shape = 0;
   const int lps = storage == 0 ? 1 : storage == 1 ? 2 : 4;
   const long lanes = (long)a.hr * lps;
   unsigned gy = a.nrows > 65535 ? 65535u : (unsigned)a.nrows;
-  if (g_site_gy > 0 && gy > (unsigned)g_site_gy) gy = (unsigned)g_site_gy;
-  dim3 grid((unsigned)((lanes + g_site_block - 1) / g_site_block), gy);
+  dim3 grid((unsigned)((lanes + BLOCK - 1) / BLOCK), gy);
   if (storage == 0) launch_site<0>(a, shape, zero, grid, st);
   else if (storage == 1) launch_site<1>(a, shape, zero, grid, st);
   else launch_site<2>(a, shape, zero, grid, st);

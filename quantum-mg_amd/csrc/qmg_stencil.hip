@@ -60,18 +60,7 @@ struct StencilArgs {
   double* norm_part;
   // apply epilogue (kernels B / B32, one system per launch): out = other_scale other + acc_scale acc, MR dots of out (qmg_common.h)
   Epilogue epi;
-#ifdef QMG_DIAGNOSTICS
-  int ablate;        // tools-only build (make DIAG=1; tools/variants.py): 1 = neighbours := own site, 2 = no store, 4 = no rhs loads
-#endif
 };
-
-// Ablation switches exist only in the tools build (-DQMG_DIAGNOSTICS, `make DIAG=1`, never shipped): in libqmg_hip.so the
-// test is the constant 0 and every ablated path is dead code.
-#ifdef QMG_DIAGNOSTICS
-#define QMG_ABLATE(a, bits) ((a).ablate & (bits))
-#else
-#define QMG_ABLATE(a, bits) 0
-#endif
 
 // The system a launch's k-th right-hand side belongs to (masked batches process a subset: a.ridx), WITHOUT touching memory: a.ridx[k] with a
 // run-time k -- divergent or uniform -- is a vector load from the kernel-argument segment, and the `s_waitcnt vmcnt(0)` in front of its use also
@@ -348,9 +337,8 @@ __global__ __launch_bounds__(BLOCK) void k_stencil_elem(const StencilArgs a) {
       Frag xv[5];
 #pragma unroll
       for (int d = 0; d < 4; d++)
-        xv[d] = ((hop_mask >> d) & 1u) ? ld_frag<T, NC, false>(x, (QMG_ABLATE(a, 1) ? site : nb[d]) * VPS + vf) : zero_frag<T, NC>();
+        xv[d] = ((hop_mask >> d) & 1u) ? ld_frag<T, NC, false>(x, nb[d] * VPS + vf) : zero_frag<T, NC>();
       xv[4] = need_own ? ld_frag<T, NC, false>(x, site * VPS + vf) : zero_frag<T, NC>();
-      if (QMG_ABLATE(a, 4)) { for (int d = 0; d < 5; d++) for (int w = 0; w < CW; w++) { xv[d].v[w].x = (T)(1.0 + c0 + w); xv[d].v[w].y = (T)0.5; } }
 
       ct acc = czero<T>();
       fmac<T, NC>(acc, m[4], xv[4]);                       // clover first, as the reference does
@@ -359,7 +347,6 @@ __global__ __launch_bounds__(BLOCK) void k_stencil_elem(const StencilArgs a) {
       fmac<T, NC>(acc, sh, xv[4]);
       row_sum<T, NC>(acc);
 
-      if (QMG_ABLATE(a, 2) && acc.x != (T)1.2345e30) continue;
       if (c0 == 0) {
         if (!do_zero) { const ct o = out[site * NC + r]; acc.x += o.x; acc.y += o.y; }
         st_elem<T, NTS>(out, site * NC + r, acc);
@@ -645,13 +632,6 @@ __global__ __launch_bounds__(BLOCK) void k_stencil_gen(const StencilArgs a, cons
       auto prefetch = [&](int piece) {
         const cplx* mbase = (piece == 4) ? a.clover : a.hopping;                 // (element offsets, so that the same
         long moff = (piece == 4) ? site0 * nc2 : (long)piece * a.size_cm + site0 * nc2;   //  code serves both matrix widths)
-        if (QMG_ABLATE(a, 16) && (piece == 2 || piece == 3)) {
-          // diagnostic (wrong arithmetic, right access pattern): what the backward hops would cost if they re-read the
-          // neighbour's FORWARD link (gamma5-hermitian link compression) instead of streaming their own array
-          long nsite0 = (piece == 2) ? opp + (long)y * a.hr + (j0 + s - 1 < 0 ? 0 : j0 + s - 1) : opp + (long)ym * a.hr + j0;
-          if (nsite0 + nsite > 2 * a.half_vol) nsite0 = 2 * a.half_vol - nsite;
-          moff = (long)(piece - 2) * a.size_cm + nsite0 * nc2;
-        }
         const int lim = nsite * (int)nc2;
         if (pairs) {
 #pragma unroll
@@ -732,7 +712,7 @@ __global__ __launch_bounds__(BLOCK) void k_stencil_gen(const StencilArgs a, cons
         while (oi < 5 && !((piece_mask >> order[oi]) & 1u)) oi++;
         if (oi < 5) { nxt = order[oi]; prefetch(nxt); }
         __syncthreads();
-        if (worker && s_of < nsite && !QMG_ABLATE(a, 32)) {
+        if (worker && s_of < nsite) {
           const cplx* mrow = mlds + (size_t)sr * L.rs;
           const cplx* xs = xlds + s_of * nc;
           for (int cc = c0; cc < c1; cc++) {
@@ -741,7 +721,6 @@ __global__ __launch_bounds__(BLOCK) void k_stencil_gen(const StencilArgs a, cons
             for (int kk = 0; kk < KR; kk++) cmac(acc[kk], m, xs[kk * rows + cc]);
           }
         }
-        if (QMG_ABLATE(a, 32)) acc[0] = cadd(acc[0], widen_mraw<M32>(stage[0]));   // diagnostic: no LDS reads / FMAs, loads kept alive
         cur = nxt;
       }
 
@@ -913,7 +892,7 @@ __global__ __launch_bounds__(BLOCK) void k_stencil_gen32(const StencilArgs a, co
         // issue the global loads of the piece PF ahead (into the set just parked) before computing on this one
         if (nextp >= 0) prefetch(nextp, f);
         __syncthreads();
-        if (worker && s_of < nsite && !QMG_ABLATE(a, 32)) {
+        if (worker && s_of < nsite) {
           const float2* mrow = mlds + (size_t)sr * rs32;
           const cplx* xs = xlds + s_of * nc;
           for (int cc = c0; cc < c1; cc++) {
@@ -923,7 +902,6 @@ __global__ __launch_bounds__(BLOCK) void k_stencil_gen32(const StencilArgs a, co
             for (int kk = 0; kk < KR; kk++) cmac(acc[kk], m, xs[kk * rows + cc]);
           }
         }
-        if (QMG_ABLATE(a, 32)) acc[0] = cadd(acc[0], stage[f][0]);   // diagnostic: no LDS reads / FMAs, loads kept alive (raw bits)
       };
       if constexpr (PF == 1 && PP > 4) {
         // one piece ahead, large tiles (nc = 24: six staged pairs per thread): a plain loop.  Unrolled over the five pieces -- which is what the
@@ -1452,19 +1430,10 @@ __global__ __launch_bounds__(BLOCK, (QMG_KC_F32_PF2 && MODE == 1 && M32 && V32 &
   }
 }
 
-static int g_stencil_nt = 3;     // tuning knob: bit0 non-temporal matrix loads, bit1 non-temporal stores (kernel A)
-#ifdef QMG_DIAGNOSTICS
-static int g_stencil_ablate = 0;
-#endif
 static int g_stencil_site = 3;    // tuning knob: nc 2 through the site kernel (qmg_site.hip): bit 0 fp64 where it is faster, bit 1 fp32, bit 2 fp64 always
-static int g_stencil_pair = 2;    // tuning knob: 0 = one site per lane group (kernel A), 1/2 = paired parities x 1/2 rows (kernel A2)
+static int g_stencil_pair = 2;    // tuning knob: 0 = one site per lane group (kernel A), 2 = fp64 paired parities x 2 rows where Ly is even (kernel A2)
 static int g_pair_prefetch = 1;   // tuning knob: 1 = kernel A2 prefetches the next system's right-hand side in fp64 batches
-static int g_stencil_rows = 0;   // tuning knob: cap on gridDim.y (0 = one block row per lattice row)
 static int g_stencil_mfma = 1;   // tuning knob: 1 = multi-rhs applies with nc in {8,12,16,24,32} run on the f64 matrix cores (kernel C); 2 = same, plain 4-MFMA products; 0 = off
-static int g_mfma_pair8 = 1;     // tuning knob: 1 = kernel C at nc = 8 with up to 8 systems owns two sites per wavefront, 0 = one
-static int g_mfma_vl = 1;        // tuning knob: 1 = kernel C loads / stores the right-hand sides coalesced through an LDS slice, 0 = operand-layout global accesses
-static int g_gen32 = 1;          // tuning knob: fp32-stored matrices, even nc: 1 = kernel B32 (fp32 tile end to end), 2 = same with 2-site tiles, 0 = kernel B with widening loads
-static int g_gen_sites = 0;      // tuning knob: cap on sites per block in kernel B (0 = register-limited maximum)
 
 static GenLayout make_gen_layout(int nc, int hr, int mat32, int site_cap = 0) {
   GenLayout L;
@@ -1475,7 +1444,6 @@ static GenLayout make_gen_layout(int nc, int hr, int mat32, int site_cap = 0) {
   // fp32-stored matrices: the kernel is bound by bytes in flight per CU (one piece per resident block), not by HBM; with
   // half the bytes per piece, smaller tiles (more resident blocks) pay: 512^2, nc = 24: S = 5 1.81 ms, S = 2 1.59 ms
   if (mat32 && nc >= 16 && S > 2) S = 2;
-  if (g_gen_sites > 0 && S > g_gen_sites) S = g_gen_sites;
   if (site_cap > 0 && S > site_cap) S = site_cap;
   if (S < 1) S = 1;
   L.S = S;
@@ -1495,28 +1463,13 @@ using namespace qmg;
 
 extern "C" int qmg_set_tuning(const char* key, int value) {
   if (!key) return QMG_ERR_INVALID;
-  if (!strcmp(key, "stencil_nt")) { g_stencil_nt = value; return QMG_SUCCESS; }
-#ifdef QMG_DIAGNOSTICS
-  if (!strcmp(key, "stencil_ablate")) { g_stencil_ablate = value; return QMG_SUCCESS; }
-#endif
-  if (!strcmp(key, "stencil_pair")) { g_stencil_pair = value; return QMG_SUCCESS; }
+  if (!strcmp(key, "stencil_pair")) { if (value != 0 && value != 2) return QMG_ERR_INVALID; g_stencil_pair = value; return QMG_SUCCESS; }
   if (!strcmp(key, "blas_nt_mb")) { g_blas_nt_bytes = (long)value << 20; return QMG_SUCCESS; }
   if (!strcmp(key, "pair_prefetch")) { g_pair_prefetch = value; return QMG_SUCCESS; }
   if (!strcmp(key, "stencil_site")) { g_stencil_site = value; return QMG_SUCCESS; }
-  if (!strcmp(key, "site_block")) { if (value != 64 && value != 128 && value != 256) return QMG_ERR_INVALID; g_site_block = value; return QMG_SUCCESS; }
-  if (!strcmp(key, "site_gy")) { g_site_gy = value; return QMG_SUCCESS; }
-  if (!strcmp(key, "site_generic")) { g_site_generic = value ? 1 : 0; return QMG_SUCCESS; }
-  if (!strcmp(key, "stencil_rows")) { g_stencil_rows = value; return QMG_SUCCESS; }
-  if (!strcmp(key, "gen_sites")) { g_gen_sites = value; return QMG_SUCCESS; }
-  if (!strcmp(key, "gen32")) { g_gen32 = value; return QMG_SUCCESS; }
   if (!strcmp(key, "stencil_mfma")) { g_stencil_mfma = value; return QMG_SUCCESS; }
-  if (!strcmp(key, "mfma_vl")) { g_mfma_vl = value; return QMG_SUCCESS; }
-  if (!strcmp(key, "mfma_pair8")) { g_mfma_pair8 = value; return QMG_SUCCESS; }
-  if (!strcmp(key, "xfer_tile")) { g_xfer_tile = value; return QMG_SUCCESS; }
-  if (!strcmp(key, "xfer_pack")) { g_xfer_pack = value; return QMG_SUCCESS; }
   if (!strcmp(key, "wilson_pair")) { g_wilson_pair = value; return QMG_SUCCESS; }
   if (!strcmp(key, "setup_fused")) { g_setup_fused = value; return QMG_SUCCESS; }
-  if (!strcmp(key, "xfer_mfma")) { g_xfer_mfma = value; return QMG_SUCCESS; }
   if (!strcmp(key, "reduce_spin")) { g_reduce_spin = value; return QMG_SUCCESS; }
   if (!strcmp(key, "malloc_poison")) { g_malloc_poison = value ? 1 : 0; return QMG_SUCCESS; }
   return QMG_ERR_INVALID;
@@ -1750,9 +1703,6 @@ static int stencil_apply_impl(const qmg_stencil_desc* d, void* lhs, const void* 
   a.norm_part = nullptr;
   a.epi = no_epilogue();
   for (int k = 0; k < 16; k++) a.ridx[k] = ridx ? ridx[k < nrhs ? k : 0] : (unsigned char)k;
-#ifdef QMG_DIAGNOSTICS
-  a.ablate = g_stencil_ablate;
-#endif
   for (int i = 0; i < 2; i++) { a.shift[i] = d->shift[i]; a.eo_shift[i] = d->eo_shift[i]; a.dof_shift[i] = d->dof_shift[i]; }
 
   // which parity halves have any work
@@ -1764,7 +1714,6 @@ static int stencil_apply_impl(const qmg_stencil_desc* d, void* lhs, const void* 
   a.par_count = (ev && od) ? 2 : 1;
   a.nrows = d->Ly * a.par_count;
   unsigned gy = a.nrows > 65535 ? 65535u : (unsigned)a.nrows;
-  if (g_stencil_rows > 0 && gy > (unsigned)g_stencil_rows) gy = (unsigned)g_stencil_rows;
   hipStream_t st = as_stream(stream);
 
   if (norms_dev) {
@@ -1820,35 +1769,25 @@ static int stencil_apply_impl(const qmg_stencil_desc* d, void* lhs, const void* 
 
   // fp32: the one-site-per-lane-group kernel is the faster one (4096^2 Wilson: 0.573 ms against 0.592 ms for the paired
   // kernel, profiles/r02_kernel_rooflines.json: half the bytes per site leave the paired kernel's longer dependent chain
-  // exposed), so the paired kernel serves fp64 only unless "stencil_pair" asks for it explicitly (>= 8)
-  const bool use_pair = vec32 ? (g_stencil_pair >= 8) : (g_stencil_pair > 0);
-  if ((nc == 1 || nc == 2 || nc == 4) && a.par_count == 2 && use_pair && lhs != rhs && !slab) {
-    const int E = (vec32 && nc % 2 == 0) ? nc * nc / 2 : nc * nc;   // lanes per site (KA<T, NC>::E)
-    const int rows = ((g_stencil_pair & 7) >= 4 && d->Ly % 4 == 0) ? 4 : ((g_stencil_pair & 7) >= 2 && d->Ly % 2 == 0) ? 2 : 1;
+  // exposed), so the paired kernel serves fp64 only
+  if ((nc == 1 || nc == 2 || nc == 4) && a.par_count == 2 && g_stencil_pair && !vec32 && lhs != rhs && !slab) {
+    const int E = nc * nc;   // lanes per site (KA<double, NC>::E)
+    const int rows = (d->Ly % 2 == 0) ? 2 : 1;
     const unsigned gx = (unsigned)((a.hr + BLOCK / E - 1) / (BLOCK / E));
     unsigned gyp = (unsigned)(d->Ly / rows);
     if (gyp > 65535u) gyp = 65535u;
-    if (g_stencil_rows > 0 && gyp > (unsigned)g_stencil_rows) gyp = (unsigned)g_stencil_rows;
     dim3 grid(gx, gyp), block(BLOCK);
-#define QMG_PAIR_LAUNCH_T(T, NC, ROWS)                                                        \
-    switch (g_stencil_nt & 3) {                                                               \
-      case 0: k_stencil_pair<T, NC, ROWS, false, false><<<grid, block, 0, st>>>(a); break;    \
-      case 1: k_stencil_pair<T, NC, ROWS, true, false><<<grid, block, 0, st>>>(a); break;     \
-      case 2: k_stencil_pair<T, NC, ROWS, false, true><<<grid, block, 0, st>>>(a); break;     \
-      default: k_stencil_pair<T, NC, ROWS, true, true><<<grid, block, 0, st>>>(a); break;     \
-    }
-    // staggered-type batches (nc = 1, fp64, default non-temporal policy): the variant that requests system k+1 ahead of system
-    // k's arithmetic -- 4096^2, 8 systems: 1.04 -> 0.90 ms; at nc = 2 it loses 3 % (tools/apply_norm_ab.py), so not there
-    const bool pf = nc == 1 && !vec32 && a.nrhs > 1 && g_pair_prefetch && (g_stencil_nt & 3) == 3;
-#define QMG_PAIR_LAUNCH(NC, ROWS) if (vec32) { QMG_PAIR_LAUNCH_T(float, NC, ROWS) } else { QMG_PAIR_LAUNCH_T(double, NC, ROWS) }
+    // staggered-type batches (nc = 1): the variant that requests system k+1 ahead of system k's arithmetic -- 4096^2, 8 systems:
+    // 1.04 -> 0.90 ms; at nc = 2 it loses 3 % (tools/apply_norm_ab.py), so not there
+    const bool pf = nc == 1 && a.nrhs > 1 && g_pair_prefetch;
+#define QMG_PAIR_LAUNCH(NC, ROWS) k_stencil_pair<double, NC, ROWS, true, true><<<grid, block, 0, st>>>(a);
 #define QMG_PAIR_LAUNCH_PF(ROWS) k_stencil_pair<double, 1, ROWS, true, true, false, true><<<grid, block, 0, st>>>(a);
-    if (pf) { if (rows == 4) { QMG_PAIR_LAUNCH_PF(4) } else if (rows == 2) { QMG_PAIR_LAUNCH_PF(2) } else { QMG_PAIR_LAUNCH_PF(1) } }
-    else if (nc == 1) { if (rows == 4) { QMG_PAIR_LAUNCH(1, 4) } else if (rows == 2) { QMG_PAIR_LAUNCH(1, 2) } else { QMG_PAIR_LAUNCH(1, 1) } }
-    if (nc == 2) { if (rows == 4) { QMG_PAIR_LAUNCH(2, 4) } else if (rows == 2) { QMG_PAIR_LAUNCH(2, 2) } else { QMG_PAIR_LAUNCH(2, 1) } }
-    if (nc == 4) { if (rows >= 2) { QMG_PAIR_LAUNCH(4, 2) } else { QMG_PAIR_LAUNCH(4, 1) } }
+    if (pf) { if (rows == 2) { QMG_PAIR_LAUNCH_PF(2) } else { QMG_PAIR_LAUNCH_PF(1) } }
+    else if (nc == 1) { if (rows == 2) { QMG_PAIR_LAUNCH(1, 2) } else { QMG_PAIR_LAUNCH(1, 1) } }
+    if (nc == 2) { if (rows == 2) { QMG_PAIR_LAUNCH(2, 2) } else { QMG_PAIR_LAUNCH(2, 1) } }
+    if (nc == 4) { if (rows == 2) { QMG_PAIR_LAUNCH(4, 2) } else { QMG_PAIR_LAUNCH(4, 1) } }
 #undef QMG_PAIR_LAUNCH
 #undef QMG_PAIR_LAUNCH_PF
-#undef QMG_PAIR_LAUNCH_T
     QMG_LAUNCH_CHECK();
     return QMG_SUCCESS;
   }
@@ -1857,19 +1796,11 @@ static int stencil_apply_impl(const qmg_stencil_desc* d, void* lhs, const void* 
     const int E = (vec32 && nc % 2 == 0) ? nc * nc / 2 : nc * nc;
     const unsigned gx = (unsigned)((a.hr + BLOCK / E - 1) / (BLOCK / E));
     dim3 grid(gx, gy), block(BLOCK);
-#define QMG_ELEM_LAUNCH_T(T, NC)                                                              \
-    switch (g_stencil_nt & 3) {                                                               \
-      case 0: k_stencil_elem<T, NC, false, false><<<grid, block, 0, st>>>(a); break;          \
-      case 1: k_stencil_elem<T, NC, true, false><<<grid, block, 0, st>>>(a); break;           \
-      case 2: k_stencil_elem<T, NC, false, true><<<grid, block, 0, st>>>(a); break;           \
-      default: k_stencil_elem<T, NC, true, true><<<grid, block, 0, st>>>(a); break;           \
-    }
-#define QMG_ELEM_LAUNCH(NC) if (vec32) { QMG_ELEM_LAUNCH_T(float, NC) } else { QMG_ELEM_LAUNCH_T(double, NC) }
+#define QMG_ELEM_LAUNCH(NC) if (vec32) { k_stencil_elem<float, NC, true, true><<<grid, block, 0, st>>>(a); } else { k_stencil_elem<double, NC, true, true><<<grid, block, 0, st>>>(a); }
     if (nc == 1) { QMG_ELEM_LAUNCH(1) }
     if (nc == 2) { QMG_ELEM_LAUNCH(2) }
     if (nc == 4) { QMG_ELEM_LAUNCH(4) }
 #undef QMG_ELEM_LAUNCH
-#undef QMG_ELEM_LAUNCH_T
     QMG_LAUNCH_CHECK();
     return QMG_SUCCESS;
   }
@@ -1891,8 +1822,8 @@ static int stencil_apply_impl(const qmg_stencil_desc* d, void* lhs, const void* 
       size_t smem = a.mat32 ? sizeof(float2) * (size_t)(BLOCK / WAVE) * nc * (nc + 2) : sizeof(cplx) * (size_t)(BLOCK / WAVE) * nc * (nc + 1);
       int mode = (g_stencil_mfma == 2 || nk > 8) ? 0 : 1;
       // 9-16 systems in fp64: the real-form tiles where they save MFMAs (nc = 24: 36 instead of 48 per piece; nc = 8: 4 instead of 8)
-      if (mode == 0 && g_stencil_mfma == 1 && g_mfma_vl && !a.mat32 && !a.vec32 && (nc == 24 || nc == 8)) mode = 2;
-      const bool vl_slices = a.mat16 ? (mode == 1) : (g_mfma_vl && !(mode == 0 && a.mat32));   // (the 16-bit instantiations: VL with MODE 1, not with MODE 0)
+      if (mode == 0 && g_stencil_mfma == 1 && !a.mat32 && !a.vec32 && (nc == 24 || nc == 8)) mode = 2;
+      const bool vl_slices = a.mat16 ? (mode == 1) : !(mode == 0 && a.mat32);   // (the 16-bit instantiations: VL with MODE 1, not with MODE 0)
       if (vl_slices) smem += sizeof(cplx) * (size_t)(BLOCK / WAVE) * (mode == 1 ? 8 : 16) * (nc + 1);   // the wavefronts' vector slices
 #define QMG_MFMA_LAUNCH0(NC, MODE, M32, V32, VL)                                                              \
       {                                                                                                         \
@@ -1900,7 +1831,7 @@ static int stencil_apply_impl(const qmg_stencil_desc* d, void* lhs, const void* 
           QMG_HIP_CHECK(hipFuncSetAttribute((const void*)k_stencil_mfma<NC, MODE, M32, V32, VL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem)); \
         k_stencil_mfma<NC, MODE, M32, V32, VL><<<grid, block, smem, st>>>(b, nk);                             \
       }
-#define QMG_MFMA_LAUNCH1(NC, MODE, M32, V32) { if (g_mfma_vl && !(MODE == 0 && M32)) QMG_MFMA_LAUNCH0(NC, MODE, M32, V32, true) else QMG_MFMA_LAUNCH0(NC, MODE, M32, V32, false) }
+#define QMG_MFMA_LAUNCH1(NC, MODE, M32, V32) QMG_MFMA_LAUNCH0(NC, MODE, M32, V32, !(MODE == 0 && M32))
 #define QMG_MFMA_LAUNCH16(NC, MODE, V32)                                                                        \
       {                                                                                                         \
         if (smem > 64 * 1024)                                                                                   \
@@ -1912,8 +1843,8 @@ static int stencil_apply_impl(const qmg_stencil_desc* d, void* lhs, const void* 
         else if (a.vec32) QMG_MFMA_LAUNCH1(NC, MODE, true, true) else if (a.mat32) QMG_MFMA_LAUNCH1(NC, MODE, true, false) else QMG_MFMA_LAUNCH1(NC, MODE, false, false) }
 #define QMG_MFMA_LAUNCH(NC)                                                                                     \
       if (mode == 2) QMG_MFMA_LAUNCH0(NC, 2, false, false, true) else if (mode == 0) QMG_MFMA_LAUNCH2(NC, 0) else QMG_MFMA_LAUNCH2(NC, 1)
-      // nc = 8, up to 8 systems, whole lattice: two sites per wavefront (PAIR; "mfma_pair8" = 0 keeps one)
-      if (nc == 8 && mode == 1 && g_mfma_pair8 && !slab && (a.hr % 2 == 0)) {
+      // nc = 8, up to 8 systems, whole lattice: two sites per wavefront (PAIR)
+      if (nc == 8 && mode == 1 && !slab && (a.hr % 2 == 0)) {
         const unsigned gxp = (unsigned)((a.hr / 2 + BLOCK / WAVE - 1) / (BLOCK / WAVE));
         dim3 gridp(gxp, gy);
         const size_t smemp = (a.mat32 ? sizeof(float2) * (size_t)(BLOCK / WAVE) * 16 * 18 : sizeof(cplx) * (size_t)(BLOCK / WAVE) * 16 * 17) +
@@ -1943,9 +1874,9 @@ static int stencil_apply_impl(const qmg_stencil_desc* d, void* lhs, const void* 
   }
 
   if (nc > BLOCK) return QMG_ERR_UNSUPPORTED;
-  if (a.mat32 && !(nc & 1) && g_gen32 && !(slab && nc <= 4)) {   // (a slab's fp32 applies at nc = 4 keep kernel B's widening loads)
+  if (a.mat32 && !(nc & 1) && !(slab && nc <= 4)) {   // (a slab's fp32 applies at nc = 4 keep kernel B's widening loads)
     // kernel B32: fp32 tile end to end (even nc)
-    const GenLayout L = make_gen_layout(nc, a.hr, g_gen32 == 2 ? 1 : 0);
+    const GenLayout L = make_gen_layout(nc, a.hr, 0);
     if (a.mat16 && (nc & 3)) return QMG_ERR_UNSUPPORTED;
     const int pp = a.mat16 ? (L.mat_elems / 4 + BLOCK - 1) / BLOCK : (L.mat_elems / 2 + BLOCK - 1) / BLOCK;
     if (pp >= 1 && pp <= (a.mat16 ? 3 : 6)) {

@@ -530,14 +530,14 @@ __global__ __launch_bounds__(BLOCK) void k_brestrict_small(const void* __restric
 
 // two complex<float> per lane (16-byte accesses): even fnc (a pack stays inside one site), 16-byte aligned arrays
 template <typename T>
-static bool xfer_pack2(const XferGeom& g, const void* nullvecs, const void* fine) {
-  return sizeof(T) == sizeof(float) && g_xfer_pack && !(g.fnc & 1) && !(g.fsize & 1) && aligned16(nullvecs) && aligned16(fine);
+static bool pack2_ok(const XferGeom& g, const void* nullvecs, const void* fine) {
+  return sizeof(T) == sizeof(float) && !(g.fnc & 1) && !(g.fsize & 1) && aligned16(nullvecs) && aligned16(fine);
 }
 
 template <typename T>
 static int launch_restrict(const void* nullvecs, int nvec, const void* fine, void* coarse, const XferGeom& g, hipStream_t st) {
   if ((g.bx & 1) == 0) {
-    const bool pack2 = xfer_pack2<T>(g, nullvecs, fine);
+    const bool pack2 = pack2_ok<T>(g, nullvecs, fine);
     const int G = (g.bx / 2) * g.fnc / (pack2 ? 2 : 1);
     int NG = BLOCK / G;
     if (NG < 1) NG = 1;
@@ -556,7 +556,7 @@ static int launch_restrict(const void* nullvecs, int nvec, const void* fine, voi
 
 template <typename T>
 static int launch_prolong(const void* nullvecs, int nvec, const void* coarse, void* fine, const XferGeom& g, hipStream_t st) {
-  const bool pack2 = xfer_pack2<T>(g, nullvecs, fine);
+  const bool pack2 = pack2_ok<T>(g, nullvecs, fine);
   const long row_packs = (long)g.fhr * g.fnc / (pack2 ? 2 : 1);
   unsigned gx = (unsigned)((row_packs + BLOCK - 1) / BLOCK);
   if (gx > 1024) gx = 1024;
@@ -595,14 +595,9 @@ static int launch_prolong_nv32(const void* null32, int nvec, const void* coarse,
   return QMG_SUCCESS;
 }
 
-// qmg_transfer_mfma.hip: the batched transfers as contractions on the matrix cores (SITE_DECLINED: shapes not served there)
+// qmg_transfer_mfma.hip: the batched restrict as a contraction on the matrix cores (SITE_DECLINED: shapes not served there)
 int restrict_batch_mfma(int f32, const void* nullvecs, int nvec, const void* fine, void* coarse, int fhr, int fLy, int fnc, int chr, int cLy, int cnc, int bx, int by,
                         long fhalf_vol, long fsize, const int* ids8, int n, long cstride, long fstride, hipStream_t st);
-int prolong_batch_mfma(int f32, const void* nullvecs, int nvec, const void* coarse, void* fine, int fhr, int fLy, int fnc, int chr, int cLy, int cnc, int bx, int by,
-                       long fhalf_vol, long fsize, const int* ids8, int n, long cstride, long fstride, hipStream_t st);
-
-int g_xfer_pack = 1;   // tuning knob "xfer_pack": complex<float> transfer kernels move two elements per lane (16-byte accesses)
-int g_xfer_tile = 1;   // tuning knob "xfer_tile": 1 = batched transfer as LDS-tiled kernels, 0 = system by system
 
 // sites per prolong tile: a fine half-row segment of at least 512 bytes where the lattice allows, LDS <= 48 KB
 static int prolong_tile_sites(const XferGeom& g, int nvec, int KB) {
@@ -618,7 +613,7 @@ template <typename T>
 static int prolong_batch_impl(const void* nullvecs, int nvec, const void* coarse, void* fine, const XferGeom& g, const BatchIdx& bi, size_t cstride,
                               size_t fstride, hipStream_t st) {
   typedef typename CStore<T>::type ct;
-  if (bi.n == 1 || !g_xfer_tile || (g.bx & 1)) {   // one system (or an odd block width): the single-vector kernel, system by system
+  if (bi.n == 1 || (g.bx & 1)) {   // one system (or an odd block width): the single-vector kernel, system by system
     for (int s = 0; s < bi.n; s++) {
       const int rc = launch_prolong<T>(nullvecs, nvec, (const ct*)coarse + (size_t)bi.id[s] * cstride, (ct*)fine + (size_t)bi.id[s] * fstride, g, st);
       if (rc) return rc;
@@ -627,12 +622,6 @@ static int prolong_batch_impl(const void* nullvecs, int nvec, const void* coarse
   }
   for (int s0 = 0; s0 < bi.n; s0 += 8) {
     const int left = bi.n - s0;
-    {
-      const PassIds pi = make_pass(bi, s0);
-      const int rc = prolong_batch_mfma(sizeof(T) == 4, nullvecs, nvec, coarse, fine, g.fhr, g.fLy, g.fnc, g.chr, g.cLy, g.cnc, g.bx, g.by, g.fhalf_vol, g.fsize, pi.id, pi.n,
-                                        (long)cstride, (long)fstride, st);
-      if (rc != SITE_DECLINED) { if (rc) return rc; continue; }
-    }
     const int KB = left > 4 ? 8 : left > 2 ? 4 : 2;
     const int SX = prolong_tile_sites(g, nvec, KB);
     const size_t smem = (size_t)SX * (nvec * KB + 1) * sizeof(ct);
@@ -651,7 +640,7 @@ template <typename T>
 static int restrict_batch_impl(const void* nullvecs, int nvec, const void* fine, void* coarse, const XferGeom& g, const BatchIdx& bi, size_t fstride,
                                size_t cstride, hipStream_t st) {
   typedef typename CStore<T>::type ct;
-  if (bi.n == 1 || !g_xfer_tile || (g.bx & 1)) {
+  if (bi.n == 1 || (g.bx & 1)) {
     for (int s = 0; s < bi.n; s++) {
       const int rc = launch_restrict<T>(nullvecs, nvec, (const ct*)fine + (size_t)bi.id[s] * fstride, (ct*)coarse + (size_t)bi.id[s] * cstride, g, st);
       if (rc) return rc;
@@ -671,7 +660,7 @@ static int restrict_batch_impl(const void* nullvecs, int nvec, const void* fine,
       if (rc != SITE_DECLINED) { if (rc) return rc; continue; }
     }
     const int KB = left > 4 ? 8 : left > 2 ? 4 : 2;
-    if (nel <= 32 && nvec <= 24 && g_xfer_tile != 2) {   // one element per lane, every load of a site in flight at once
+    if (nel <= 32 && nvec <= 24) {   // one element per lane, every load of a site in flight at once
 #define QMG_RS(KBV, NVTV) k_brestrict_small<T, KBV, NVTV><<<gx, BLOCK, 0, st>>>(nullvecs, nvec, fine, coarse, g, make_pass(bi, s0), (long)cstride, (long)fstride)
 #define QMG_RS_KB(KBV) { if (nvec <= 8) QMG_RS(KBV, 8); else if (nvec <= 16) QMG_RS(KBV, 16); else QMG_RS(KBV, 24); }
       if (KB == 8) QMG_RS_KB(8) else if (KB == 4) QMG_RS_KB(4) else QMG_RS_KB(2)

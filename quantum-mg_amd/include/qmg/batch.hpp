@@ -38,13 +38,6 @@ namespace qmg {
 
 const int BATCH_MAX = 16;
 
-// The K-cycle's fixed-count smoothers with their scalars on the device (bmr_fixed_zero_guess).  QMG_KCYCLE_DEVICE_SCALARS=0 restores
-// the host-scalar loops (bminv_vector_minres_zero_guess: one host round trip per MR iteration, residual recomputed): A/B runs.
-inline bool kcycle_device_scalars() {
-  static const bool on = !(getenv("QMG_KCYCLE_DEVICE_SCALARS") && atoi(getenv("QMG_KCYCLE_DEVICE_SCALARS")) == 0);
-  return on;
-}
-
 template <typename T> struct dtype_of;
 template <> struct dtype_of<double> { enum { value = QMG_C64 }; };
 template <> struct dtype_of<float> { enum { value = QMG_C32 }; };
@@ -481,10 +474,6 @@ inline std::vector<inversion_info> bminv_vector_minres_zero_guess(qmg::BatchT<T>
 // ---------------------------------------------------------------------------------------------
 namespace qmg {
 inline bool mr_tolerance_unreachable(double eps) { return eps <= 1e-14; }
-// bgcr_core: the iteration's dots in one pass / one host round trip (see there).  QMG_GCR_FUSED=0 restores the three-pass form.
-inline bool gcr_fused_dots() { static const bool on = !(getenv("QMG_GCR_FUSED") && atoi(getenv("QMG_GCR_FUSED")) == 0); return on; }
-// ... and its vector updates in one pass (qmg_batch_gcr_update_t).  QMG_GCR_FUSED_UPDATE=0: the separate multi-axpy / axpy / copy passes.
-inline bool gcr_fused_update() { static const bool on = !(getenv("QMG_GCR_FUSED_UPDATE") && atoi(getenv("QMG_GCR_FUSED_UPDATE")) == 0); return on; }
 }  // namespace qmg
 template <typename T>
 inline int bmr_fixed_zero_guess(qmg::BatchT<T> x, qmg::BatchT<T> b, qmg::BatchT<T>* r_out, int size, int iters, double omega,
@@ -704,42 +693,30 @@ inline std::vector<inversion_info> bgcr_core(qmg::BatchT<T> phi, qmg::BatchT<T> 
     else if (!z_ready) qmg::bcopy(z, r, size, act);   // (z_ready: the previous iteration's update pass wrote z = r already)
     z_ready = false;
     matrix_vector(w, z, act, extra_info);
-    // ONE reduction pass and one host round trip per iteration (qmg::gcr_fused_dots(); QMG_GCR_FUSED=0: the three-pass form): the Gram-Schmidt
+    // ONE reduction pass and one host round trip per iteration: the Gram-Schmidt
     // coefficients c_i = <W_i, w>, <r, w> and <w, w> come from the same pass over the RAW w; for the orthogonalised w' = w - sum_i (c_i / N_i) W_i
     //   <w', w'> = <w, w> - sum_i |c_i|^2 / N_i          (the W_i are orthogonal)
     //   <r,  w'> = <r, w>                                (r is orthogonal to every W_i of the cycle: each step removed that component)
     // A system whose w' keeps less than 1e-6 of |w|^2 (w almost inside the span: the subtraction has lost its digits) takes the explicit dots.
     std::vector<qmg::cvec> d2(nrhs, qmg::cvec(2, 0.0));
-    unsigned explicit_dots = act;
-    // With the dots of the fused form alpha is known BEFORE w is orthogonalised, so the Gram-Schmidt update of w, the residual update and (without a
-    // preconditioner) the copy z_next = r go through ONE pass (qmg_batch_gcr_update_t: the same bits as the three separate passes).
-    bool deferred = false;
-    std::vector<qmg::cvec> cdef;
-    if (qmg::gcr_fused_dots()) {
-      std::vector<qmg::BatchT<T> > basis(W.begin(), W.begin() + kb);
-      basis.push_back(r); basis.push_back(w);
-      std::vector<qmg::cvec> c = qmg::bmultidot(basis, kb + 2, w, size, act);
-      explicit_dots = 0;
-      for (int k = 0; k < nrhs; k++) {
-        if (!qmg::is_active(act, k)) continue;
-        double ww = c[k][kb + 1].real();
-        const double ww_raw = ww;
-        for (int i = 0; i < kb; i++) { ww -= std::norm(c[k][i]) / Wnorm2[i][k]; c[k][i] = -c[k][i] / Wnorm2[i][k]; }
-        d2[k][0] = c[k][kb]; d2[k][1] = ww;
-        if (!(ww > 1e-6 * ww_raw)) explicit_dots |= 1u << k;
-        c[k].resize(kb);
-        C[k][kb] = c[k];
-      }
-      if (explicit_dots == 0 && qmg::gcr_fused_update()) { deferred = true; cdef = c; }
-      else if (kb > 0) qmg::bmulti_caxpy(c, W, kb, w, size, act);
-    } else if (kb > 0) {
-      std::vector<qmg::cvec> c = qmg::bmultidot(W, kb, w, size, act);
-      for (int k = 0; k < nrhs; k++)
-        if (qmg::is_active(act, k))
-          for (int i = 0; i < kb; i++) c[k][i] = -c[k][i] / Wnorm2[i][k];
-      qmg::bmulti_caxpy(c, W, kb, w, size, act);
-      for (int k = 0; k < nrhs; k++) if (qmg::is_active(act, k)) C[k][kb] = c[k];
+    std::vector<qmg::BatchT<T> > basis(W.begin(), W.begin() + kb);
+    basis.push_back(r); basis.push_back(w);
+    std::vector<qmg::cvec> c = qmg::bmultidot(basis, kb + 2, w, size, act);
+    unsigned explicit_dots = 0;
+    for (int k = 0; k < nrhs; k++) {
+      if (!qmg::is_active(act, k)) continue;
+      double ww = c[k][kb + 1].real();
+      const double ww_raw = ww;
+      for (int i = 0; i < kb; i++) { ww -= std::norm(c[k][i]) / Wnorm2[i][k]; c[k][i] = -c[k][i] / Wnorm2[i][k]; }
+      d2[k][0] = c[k][kb]; d2[k][1] = ww;
+      if (!(ww > 1e-6 * ww_raw)) explicit_dots |= 1u << k;
+      c[k].resize(kb);
+      C[k][kb] = c[k];
     }
+    // With these dots alpha is known BEFORE w is orthogonalised, so the Gram-Schmidt update of w, the residual update and (without a
+    // preconditioner) the copy z_next = r go through ONE pass (qmg_batch_gcr_update_t: the same bits as the three separate passes).
+    const bool deferred = explicit_dots == 0;
+    if (!deferred && kb > 0) qmg::bmulti_caxpy(c, W, kb, w, size, act);
     if (explicit_dots) {
       rw[0] = r; rw[1] = w;
       const std::vector<qmg::cvec> e2 = qmg::bmultidot(rw, 2, w, size, explicit_dots);
@@ -747,9 +724,7 @@ inline std::vector<inversion_info> bgcr_core(qmg::BatchT<T> phi, qmg::BatchT<T> 
     }
     qmg::cvec alpha(nrhs, 0.0), malpha(nrhs, 0.0);
     unsigned upd = 0, renorm = 0;
-    // the true norm re-anchors the recurrence when it has lost digits and CONFIRMS a convergence the recurrence announces (fused form; the
-    // three-pass form keeps its wider band of 4 eps)
-    const double band = qmg::gcr_fused_dots() ? 1.0 : 4.0;
+    // the true norm re-anchors the recurrence when it has lost digits and CONFIRMS a convergence the recurrence announces
     for (int k = 0; k < nrhs; k++) {
       if (!qmg::is_active(act, k)) continue;
       ops[k]++;
@@ -762,7 +737,7 @@ inline std::vector<inversion_info> bgcr_core(qmg::BatchT<T> phi, qmg::BatchT<T> 
       used[k] = kb + 1;
       upd |= 1u << k;
       rsq[k] = rsq[k] - std::norm(wr) / ww;
-      if (!(rsq[k] > 1e-8 * rsq_ref[k]) || std::sqrt(rsq[k]) < band * epsv[k] * bnorm[k]) renorm |= 1u << k;
+      if (!(rsq[k] > 1e-8 * rsq_ref[k]) || std::sqrt(rsq[k]) < epsv[k] * bnorm[k]) renorm |= 1u << k;
     }
     if (deferred) {
       qmg::BatchT<T> z_next;
@@ -770,7 +745,7 @@ inline std::vector<inversion_info> bgcr_core(qmg::BatchT<T> phi, qmg::BatchT<T> 
         if (kb + 1 == (int)Z.size()) { Z.push_back(pool.get()); W.push_back(pool.get()); Wnorm2.push_back(std::vector<double>(nrhs, 0.0)); }
         z_next = Z[kb + 1];
       }
-      qmg::bgcr_update(cdef, W, kb, w, malpha, r, z_next, size, upd);
+      qmg::bgcr_update(c, W, kb, w, malpha, r, z_next, size, upd);
       z_ready = z_next.p != 0;
     } else qmg::bcaxpy(malpha, w, r, size, upd);
     if (renorm) {
@@ -1005,7 +980,7 @@ inline void mg_preconditioner_batch(qmg::BatchT<T> lhs, qmg::BatchT<T> rhs, int 
     qmg::BatchT<T> y = ne ? fpool.get() : x;
     if (!y.p) { std::cout << "[QMG-ERROR]: out of device memory for the CGNE smoother's iterate\n"; return false; }
     bool have_r = false;
-    if (qmg::mr_tolerance_unreachable(tol) && qmg::kcycle_device_scalars()) {
+    if (qmg::mr_tolerance_unreachable(tol)) {
       const int nops = bmr_fixed_zero_guess<T>(y, b, r_out, (int)fine_size_solve, iters, 0.85, apply_stencil_typed_batch<T>, (void*)op, mask, op);
       mg->add_tracker_count(type, (ne ? 2 : 1) * nops * nact, level);
       have_r = r_out != 0;

@@ -198,8 +198,6 @@ struct Stencil2D {
   }
   void *slab_comm_stream, *slab_ev_rhs, *slab_ev_halo;
   bool slab_overlap_ready() {
-    static const bool wanted = !(getenv("QMG_SLAB_OVERLAP") && atoi(getenv("QMG_SLAB_OVERLAP")) == 0);
-    if (!wanted) return false;
     if (!slab_comm_stream) {
       if (qmg_stream_create(&slab_comm_stream) != QMG_SUCCESS || qmg_event_create(&slab_ev_rhs) != QMG_SUCCESS || qmg_event_create(&slab_ev_halo) != QMG_SUCCESS) {
         slab_comm_stream = 0;

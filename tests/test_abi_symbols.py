@@ -38,6 +38,24 @@ def test_status_strings_and_version(so):
     assert so.qmg_status_string(3) == b"unsupported"
 
 
+def test_tuning_keys_retained_and_retired(so):
+    """qmg_set_tuning only sets host globals: every kept key takes its default, the retired A/B keys are unknown keys."""
+    success, invalid = 0, 1
+    defaults = {"stencil_pair": 2, "pair_prefetch": 1, "stencil_site": 3, "stencil_mfma": 1, "blas_nt_mb": 256,
+                "wilson_pair": 2, "setup_fused": 1, "reduce_spin": 1, "malloc_poison": 0}
+    for key, value in defaults.items():
+        assert so.qmg_set_tuning(key.encode(), value) == success, key
+    retired = ("stencil_nt", "stencil_ablate", "stencil_rows", "gen_sites", "gen32", "mfma_vl", "mfma_pair8",
+               "site_block", "site_gy", "site_generic", "xfer_tile", "xfer_pack", "xfer_mfma")
+    for key in retired:
+        for value in (0, 1, 2):
+            assert so.qmg_set_tuning(key.encode(), value) == invalid, (key, value)
+    for value in (-1, 1, 3, 4, 8, 10):
+        assert so.qmg_set_tuning(b"stencil_pair", value) == invalid, value
+    assert so.qmg_set_tuning(b"stencil_pair", 0) == success
+    assert so.qmg_set_tuning(b"stencil_pair", 2) == success
+
+
 def test_desc_struct_layout_matches_header():
     # int Lx,Ly,nc (+pad) ; 2 pointers ; 6 doubles
     assert ctypes.sizeof(qmg.StencilDesc) == 16 + 16 + 48

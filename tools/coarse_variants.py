@@ -1,5 +1,5 @@
 """A/B timing of the generic-nc (coarse) stencil kernel's tuning knobs at the K-cycle's coarse sizes, interleaved rounds
-in one process.  usage: coarse_variants.py L nc '[{"gen_sites":0},{"gen_sites":2}]'"""
+in one process.  usage: coarse_variants.py L nc '[{"stencil_mfma":1},{"stencil_mfma":0},{"mat32":1}]' [nrhs]"""
 import importlib, json, os, sys
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -7,7 +7,6 @@ sys.path.insert(0, ROOT)
 import torch  # noqa: F401  (before libqmg_hip)
 qmg = importlib.import_module("quantum-mg_amd")
 qmg.init(0)
-qmg.set_tuning("stencil_nt", 3)
 L = int(sys.argv[1]); nc = int(sys.argv[2])
 variants = json.loads(sys.argv[3])
 nrhs = int(sys.argv[4]) if len(sys.argv) > 4 else 1
@@ -41,7 +40,7 @@ for rnd in range(6):
         qmg.sync(); timer.start()
         for _ in range(20): apply(v)
         res[i].append(timer.stop_ms() / 20)
-        if rnd == 0 and not v.get('stencil_ablate') and not v.get('mat32'):
+        if rnd == 0 and not v.get('mat32'):
             h = y.to_host()
             if ref is None: ref = h
             else: assert np.linalg.norm(h - ref) <= 1e-13 * np.linalg.norm(ref), "variant changed the result"

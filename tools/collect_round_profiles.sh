@@ -13,7 +13,7 @@ rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/prof_write -- python3 bench
 echo pmc done
 python tools/summarize_profiles.py $TAG > $O/summarize.log 2>&1
 cp profiles/${TAG}_summary.md profiles/${TAG}_pmc_traffic.json profiles/${TAG}_kernel_stats.csv $O/
-python tools/bench_r02.py > $O/${TAG}_kernel_rooflines.json 2> $O/bench_r02.err
+python tools/bench_kernels.py > $O/${TAG}_kernel_rooflines.json 2> $O/bench_kernels.err
 echo kernels done
 python tools/site_kernel_ab.py > $O/${TAG}_site_kernel_ab.txt 2>&1
 python tools/apply_norm_ab.py > $O/${TAG}_apply_norm_ab.txt 2>&1
@@ -36,7 +36,7 @@ for v in "" f32; do
   rm -rf $O/prof_m
 done
 echo mrhs done
-python tools/xfer_bench.py > $O/${TAG}_xfer_mfma.txt 2>&1
+python tools/xfer_bench.py > $O/${TAG}_xfer_bench.txt 2>&1
 python tools/kernelc_bench.py > $O/${TAG}_kernelC_multi_rhs.txt 2>&1
 echo xfer done
 python bench.py > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err

@@ -38,10 +38,8 @@ for site in (0, 1):
     run(lambda: qmg.stencil_apply_t(qmg.C32, d32, l, r, FULL), 192 * vol, "fp32 full  site=%d" % site)
     run(lambda: qmg.stencil_apply_t(qmg.C32, d32, l, r, DEO), (128 + 32) * vol / 2, "fp32 D_eo  site=%d" % site)
 d16 = qmg.make_desc(L, L, 2, c16, h16, -0.07)
-for gen in (0, 1):
-    qmg.set_tuning("site_generic", gen)
-    run(lambda: qmg.stencil_apply_h16(d16, l, r, FULL), 112 * vol, "16-bit matrices full  generic=%d" % gen)
-    run(lambda: qmg.stencil_apply_h16(d16, l, r, DEO), (64 + 32) * vol / 2, "16-bit matrices D_eo  generic=%d" % gen)
+run(lambda: qmg.stencil_apply_h16(d16, l, r, FULL), 112 * vol, "16-bit matrices full")
+run(lambda: qmg.stencil_apply_h16(d16, l, r, DEO), (64 + 32) * vol / 2, "16-bit matrices D_eo")
 
 # batches of 8 right-hand sides at 2048^2: matrices once per site (320 + 64 n B/site in fp64)
 del r, l, c32, h32, c16, h16
