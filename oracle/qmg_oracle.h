@@ -129,7 +129,26 @@ int qo_coarse_build(double* cclover, double* chopping, const qo_stencil_desc* fi
                     int cLx, int cLy, int cnc);
 
 /* ---- K-cycle (oracle/qmg_oracle_kcycle.cpp): multigrid/stateful_multigrid.h:734-1060 driven as
- *      tests/n13_wilson_kcycle/wilson_kcycle.cpp:86-122,459-471.  Krylov drivers: parity unpinned. ---- */
+ *      tests/n13_wilson_kcycle/wilson_kcycle.cpp:86-122,459-471 and tests/n19_wilson_kcycle_precond.  Krylov drivers: parity unpinned. ---- */
+/* operator types, stencil/stencil_2d.h QMGStencilType */
+enum { QO_MATVEC_ORIGINAL = 0, QO_MATVEC_DAGGER = 1, QO_MATVEC_RIGHT_JACOBI = 2, QO_MATVEC_RIGHT_SCHUR = 3, QO_MATVEC_M_MDAGGER = 4,
+       QO_MATVEC_MDAGGER_M = 5, QO_MATVEC_RBJ_DAGGER = 6, QO_MATVEC_RBJ_M_MDAGGER = 7, QO_MATVEC_RBJ_MDAGGER_M = 8 };
+typedef struct {
+  int L; double mass; int n_refine, coarse_dof;   /* L x L Wilson, n_refine 4x4 coarsenings to coarse_dof colours */
+  double tol; int max_iter, restart;              /* outer flexible GCR */
+  double inner_tol, coarsest_tol; int n_smooth;   /* intermediate / coarsest tolerances (1000 iterations, restart 32); MR steps */
+  int level_type;      /* ORIGINAL (n13 hierarchy), RIGHT_JACOBI or RIGHT_SCHUR (n19: Galerkin from the rbjacobi stencil): outer solve and every level */
+  int coarsest_type;   /* level_type (restarted GCR), or one of the normal forms of that hierarchy (restarted CG) */
+  int cgne;            /* CGNE smoothers (ignored on RIGHT_SCHUR levels) */
+  double normal_shift; /* added to a normal coarsest operator */
+} qo_kcycle_params;
+/* gauge: nc=1 LatticeGauge; nullvecs[l]: coarse_dof vectors of level-l size, NOT yet block-orthonormalised; b: right-hand side of the
+ * ORIGINAL system, x_out its reconstructed solution.  Returns outer iterations (negative: not converged; < -100000: bad input);
+ * fills true_res (ORIGINAL operator), ops[level], its[level]; hist / chist (may be NULL) receive the outer relative residual per
+ * iteration and the iteration count of every coarsest solve (negative: hit its cap), *nhist_out / *nchist_out their lengths. */
+int qo_kcycle(const qo_kcycle_params* p, const double* gauge, const double* const* nullvecs, const double* b, double* x_out, double* true_res,
+              long* ops, long* its, double* hist, int nhist, int* nhist_out, long* chist, int nchist, int* nchist_out);
+/* the n13 shape (ORIGINAL, MR, GCR coarsest solve) */
 int qo_wilson_kcycle(int L, double mass, int n_refine, int coarse_dof, const double* gauge, const double* const* nullvecs, const double* b,
                      double tol, int max_iter, int restart, double inner_tol, double coarsest_tol, int n_smooth, double* x_out,
                      double* true_res, long* ops, long* its);

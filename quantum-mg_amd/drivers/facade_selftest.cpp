@@ -312,7 +312,7 @@ int main(int argc, char** argv) {
           check(all_ok && worst_it <= 1 && worst_x < 1e-7, rf == -1 ? "bcg_core == minv_vector_cg per system (M^dag M, Galerkin nc = 8, 3 systems)" : "bcg_core == minv_vector_cg_restart(16) per system", worst_x);
         }
       }
-      // a normal operator with CoarsestSolveMG::normal_shift (shift_function, stateful_multigrid.h:724-729)
+      // a normal operator with CoarsestSolveMG::normal_shift (stateful_multigrid.h:724-729)
       BatchOp sh(st, QMG_MATVEC_RBJ_MDAGGER_M);
       sh.normal_shift = complex<double>(0.37, 0.0); sh.shift_length = n;
       apply_stencil_typed_batch<double>(out, in, all, (void*)&sh);

@@ -60,6 +60,7 @@ static int run(int rank, int world, int device, bool slab_mode, int argc, char**
   const QMGStencilType coarsest_type = (coarsest_env == "rbj_mmd") ? QMG_MATVEC_RBJ_M_MDAGGER : (coarsest_env == "rbj_mdm") ? QMG_MATVEC_RBJ_MDAGGER_M : solve_type;
   const bool want_rbj_dagger = cgne || coarsest_type != solve_type;
   unsigned long long seed = 1337ull;
+  const char* dump_dir = slab_mode ? 0 : getenv("QMG_DUMP_DIR");   // test hook: null vectors, b and the reconstructed solution
 
   inversion_info invif;
   inversion_verbose_struct verb;
@@ -128,6 +129,14 @@ static int run(int rank, int world, int device, bool slab_mode, int argc, char**
       normalize(null_vectors[j], fsize);
       normalize(null_vectors[j + lats[i]->get_nc() / 2], fsize);
     }
+    if (dump_dir) {   // raw complex128, coarse_dof vectors back to back (pre block-ortho), for the oracle tests
+      FILE* f = fopen((string(dump_dir) + "/nullvecs_level" + to_string(i - 1) + ".bin").c_str(), "wb");
+      for (int j = 0; j < coarse_dof && f; j++) {
+        const std::vector<complex<double>> h = qmg::to_host(null_vectors[j], (size_t)fsize);
+        fwrite(h.data(), sizeof(complex<double>), h.size(), f);
+      }
+      if (f) fclose(f);
+    }
     transfer_objs[i - 1] = new TransferMG(lats[i - 1], lats[i], null_vectors, true, false, QMG_DOUBLE_PROJECTION);
     level_solve_objs[i - 1] = new StatefulMultigridMG::LevelSolveMG;
     level_solve_objs[i - 1]->fine_stencil_app = solve_type;
@@ -179,10 +188,13 @@ static int run(int rank, int world, int device, bool slab_mode, int argc, char**
   mg_object->apply_stencil(Ax, x_reconstruct, 0);   // the ORIGINAL operator
   const double true_res = sqrt(diffnorm2sq(b, Ax, lats[0]->get_size_cv_l())) / bnorm;
   cout << "Check tolerance " << true_res << "\n";
-  if (!slab_mode && getenv("QMG_DUMP_DIR")) {   // test hook: the reconstructed solution as raw complex128
-    const std::vector<complex<double>> hx = qmg::to_host(x_reconstruct, (size_t)lats[0]->get_size_cv_l());
-    FILE* f = fopen((string(getenv("QMG_DUMP_DIR")) + "/x.bin").c_str(), "wb");
-    if (f) { fwrite(hx.data(), sizeof(complex<double>), hx.size(), f); fclose(f); }
+  if (dump_dir) {   // b and the reconstructed solution as raw complex128
+    const size_t n = (size_t)lats[0]->get_size_cv_l();
+    const std::vector<complex<double>> hb = qmg::to_host(b, n), hx = qmg::to_host(x_reconstruct, n);
+    FILE* f = fopen((string(dump_dir) + "/b.bin").c_str(), "wb");
+    if (f) { fwrite(hb.data(), sizeof(complex<double>), n, f); fclose(f); }
+    f = fopen((string(dump_dir) + "/x.bin").c_str(), "wb");
+    if (f) { fwrite(hx.data(), sizeof(complex<double>), n, f); fclose(f); }
   }
   if (slab_mode) { const double xn = norm2sq(x_reconstruct, lats[0]->get_size_cv_l()); cout << setprecision(15) << "[QMG-SLAB]: world " << world << " ; |b| " << bnorm << " ; |x|^2 " << xn << "\n" << setprecision(20); }
   cout << setprecision(6) << "[QMG-TIMING]: solve " << solve_s << " s ; outer iterations/s " << invif.iter / solve_s << "\n";

@@ -9,7 +9,7 @@
 // Semantics: each system sees exactly the iteration it would see alone.  Every scalar (alpha, residual norm, Gram-
 // Schmidt coefficient, restart decision, inner tolerance) is per system; a system that converges inside a solve is
 // FROZEN (its bit leaves the active mask: no kernel reads or writes it) while the rest continue.  The per-system
-// arithmetic is that of krylov.hpp / multigrid.hpp line by line -- element-wise kernels and reductions are
+// arithmetic is that of krylov.hpp / stateful_multigrid.h line by line -- element-wise kernels and reductions are
 // bit-identical to the single-vector ones, the MFMA apply and the blocked transfer differ in summation order only
 // (1e-13), so a batched solve reproduces the single solves to solver tolerance with the same iteration counts (+-1).
 //
@@ -197,7 +197,7 @@ inline void apply_stencil_2D_M_batch(qmg::Batch lhs, qmg::Batch rhs, unsigned ma
 struct BatchOp {
   Stencil2D* st;
   QMGStencilType type;
-  complex<double> normal_shift;   // CoarsestSolveMG::normal_shift: added to a normal operator (shift_function, stateful_multigrid.h:724-729)
+  complex<double> normal_shift;   // CoarsestSolveMG::normal_shift: added to a normal operator (stateful_multigrid.h:724-729)
   size_t shift_length;
   BatchOp(Stencil2D* st_, QMGStencilType type_) : st(st_), type(type_), normal_shift(0.0), shift_length(0) {}
   // operator of a K-cycle level (smoothed with MR / CGNE, solved with flexible GCR)
@@ -624,7 +624,7 @@ inline std::vector<inversion_info> bminv_vector_bicgstab_l_zero_guess(qmg::Batch
 // ---------------------------------------------------------------------------------------------
 // Flexible GCR with restarts for a batch: qmg_gcr_core of krylov.hpp per system, in lock step.  All systems start
 // together, so the basis index kb (and with it the restart points) is common; everything else is per system.
-// zero_guess: the caller has zeroed phi, r0 = b (krylov.hpp ZeroGuess).
+// zero_guess: the caller has zeroed phi, r0 = b.
 // ---------------------------------------------------------------------------------------------
 template <typename T>
 inline std::vector<inversion_info> bgcr_core(qmg::BatchT<T> phi, qmg::BatchT<T> phi0, int size, int max_iter, double eps, int restart_freq,
@@ -888,8 +888,8 @@ inline std::vector<inversion_info> bcg_core(qmg::BatchT<T> phi, qmg::BatchT<T> p
 }
 
 // ---------------------------------------------------------------------------------------------
-// One K-cycle application for the active systems of a batch: StatefulMultigridMG::mg_preconditioner
-// (multigrid.hpp; stateful_multigrid.h:734-1060) step for step.  extra_data is a BatchKcycle.
+// One K-cycle application for the active systems of a batch: stateful_multigrid.h:734-1060 step for step.
+// extra_data is a BatchKcycle.  StatefulMultigridMG::mg_preconditioner runs it on a batch of one system.
 // ---------------------------------------------------------------------------------------------
 struct BatchKcycle {
   StatefulMultigridMG* mg;
@@ -1049,7 +1049,7 @@ inline void mg_preconditioner_batch(qmg::BatchT<T> lhs, qmg::BatchT<T> rhs, int 
   qmg::BatchT<T> z2 = r1;   // r1 is free again
   qmg::bzero(z2, fine_size, mask);
   transfer->prolong_c2f_precond_t<T>(e_rec.p, e_rec.stride, z2.p, z2.stride, nrhs, mask);
-  if (coarse_type == QMG_MATVEC_RIGHT_SCHUR) qmg::bzero(batch_odd_half(z2, fine_size / 2), fine_size - fine_size / 2, mask);   // as multigrid.hpp
+  if (coarse_type == QMG_MATVEC_RIGHT_SCHUR) qmg::bzero(batch_odd_half(z2, fine_size / 2), fine_size - fine_size / 2, mask);   // (:1018)
   qmg::bcxpyz(z1, z2, lhs, fine_size_solve, mask);
 
   // ---- 4. post-smooth on r2 = rhs - A lhs
@@ -1075,22 +1075,6 @@ inline bool qmg_reserve_kcycle_scratch(StatefulMultigridMG* mg, size_t outer_siz
   return good;
 }
 
-// StatefulMultigridMG::mg_preconditioner for one system through this engine (declared in multigrid.hpp).  QMG_KCYCLE_ENGINE=single
-// keeps the single-vector implementation of multigrid.hpp (A/B runs, and the reference-shaped code path for the parity tests).
-inline bool qmg_kcycle_via_batch(StatefulMultigridMG* mg, complex<double>* lhs, complex<double>* rhs, int size, inversion_verbose_struct* verb) {
-  static const bool on = !(getenv("QMG_KCYCLE_ENGINE") && std::string(getenv("QMG_KCYCLE_ENGINE")) == "single");
-  // y-slabs take this engine too: launch_set_batch exchanges the batch's halo rows and every reduction is completed across the ranks (C3 shape on one
-  // slab / two thread-emulated slabs: 1.43 / 1.71 s against 1.71 / 2.24 s through the single-vector code).  QMG_KCYCLE_SLAB_ENGINE=single keeps slabs on
-  // the single-vector code, whose nc = 2 applies overlap their halo exchange with the interior rows -- the choice to re-measure on real xGMI links.
-  static const bool slab_on = !(getenv("QMG_KCYCLE_SLAB_ENGINE") && std::string(getenv("QMG_KCYCLE_SLAB_ENGINE")) == "single");
-  if (!on || (qmg::slab().on && !slab_on)) return false;
-  BatchKcycle bk(mg, 1);
-  if (!bk.supported()) return false;
-  const size_t stride = (size_t)mg->get_lattice(mg->get_multigrid_level())->get_size_cv_l();
-  mg_preconditioner_batch<double>(qmg::Batch(lhs, stride, 1), qmg::Batch(rhs, stride, 1), size, 1u, (void*)&bk, verb);
-  return true;
-}
-
 // The fp32 K-cycle as the preconditioner of an fp64 flexible outer solve (BASELINE configs[4] "fp32"): the residual of
 // the active systems is rounded to complex<float>, ONE K-cycle runs entirely on the fp32 shadow hierarchy
 // (BatchKcycle::enable_f32_hierarchy), and the correction is widened back.  The outer VPGCR orthogonalises and
@@ -1107,6 +1091,24 @@ inline void mg_preconditioner_batch_mixed(qmg::Batch lhs, qmg::Batch rhs, int si
   qmg::bzero(z32, n, mask);
   mg_preconditioner_batch<float>(z32, r32, size, mask, extra_data, verb);
   qmg::bconvert(lhs, z32, (size_t)size, mask);
+}
+
+// StatefulMultigridMG::mg_preconditioner (declared in multigrid.hpp): one system is a batch of one.  A hierarchy this engine does not
+// implement (a level names a variant stencil that was never built) is an error: the preconditioner then returns its input.
+inline void StatefulMultigridMG::mg_preconditioner(complex<double>* lhs, complex<double>* rhs, int size, void* extra_data, inversion_verbose_struct* verb) {
+  StatefulMultigridMG* mg = (StatefulMultigridMG*)extra_data;
+  const int level = mg->get_multigrid_level();
+  const int total_num_levels = mg->get_num_levels();
+  if (total_num_levels > 1 && mg->get_level_solve() == 0) { std::cout << "[QMG-MG-SOLVE-ERROR]: Level solve for level " << level << " does not exist.\n"; return; }
+  const long fine_size = mg->get_lattice(level)->get_size_cv_l();
+  if (total_num_levels == 1) { copy_vector(lhs, rhs, fine_size); return; }   // :803-807
+  BatchKcycle bk(mg, 1);
+  if (!bk.supported()) {
+    std::cout << "[QMG-ERROR]: the K-cycle does not implement this hierarchy's level / coarsest operator types (or a variant stencil they name is not built).\n";
+    copy_vector(lhs, rhs, size);
+    return;
+  }
+  mg_preconditioner_batch<double>(qmg::Batch(lhs, fine_size, 1), qmg::Batch(rhs, fine_size, 1), size, 1u, (void*)&bk, verb);
 }
 
 #endif

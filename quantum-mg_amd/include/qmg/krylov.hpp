@@ -148,17 +148,6 @@ inline std::vector<complex<double>> gcr_direction_weights(const std::vector<comp
 // MinRes / MR with relaxation omega (minv_vector_minres(x, b, n, iters, tol, omega, op, opdata)).
 //   r = b - A x ; repeat: p = A r ; alpha = <p,r>/<p,p> ; x += omega alpha r ; r -= omega alpha p
 // ---------------------------------------------------------------------------------------------
-// Zero-initial-guess hint.  Every K-cycle smoother and coarse solve starts from a vector the caller has just zeroed
-// (stateful_multigrid.h:848, :958, :1010), so r0 = b exactly and the reference's opening A*x0 is an apply of zeros.  A
-// caller that KNOWS x0 == 0 constructs a qmg::ZeroGuess right before the solver call; the solver consumes the hint at
-// entry (nested preconditioner solves never see it), skips that apply and its two vector passes, and does not count it
-// in ops_count.  Results are bit-identical to the unhinted path.
-namespace qmg {
-inline bool& zero_guess_flag() { static thread_local bool f = false; return f; }
-inline bool take_zero_guess() { bool f = zero_guess_flag(); zero_guess_flag() = false; return f; }
-struct ZeroGuess { ZeroGuess() { zero_guess_flag() = true; } ~ZeroGuess() { zero_guess_flag() = false; } };
-}  // namespace qmg
-
 inline inversion_info minv_vector_minres(complex<double>* phi, complex<double>* phi0, int size, int max_iter, double eps, double omega,
                                          matrix_op_cplx matrix_vector, void* extra_info, inversion_verbose_struct* verb = 0) {
   inversion_info invif;
@@ -169,13 +158,9 @@ inline inversion_info minv_vector_minres(complex<double>* phi, complex<double>* 
   const double bsq = norm2sq(phi0, size);
   const double bnorm = std::sqrt(bsq);
   int ops = 0;
-  double rsq;
-  if (qmg::take_zero_guess()) { copy_vector(r, phi0, size); rsq = bsq; }   // x0 == 0: r = b
-  else {
-    matrix_vector(p, phi, extra_info); ops++;
-    caxpbyz(1.0, phi0, -1.0, p, r, size);
-    rsq = norm2sq(r, size);
-  }
+  matrix_vector(p, phi, extra_info); ops++;
+  caxpbyz(1.0, phi0, -1.0, p, r, size);
+  double rsq = norm2sq(r, size);
   double rsq_ref = rsq;
   int k = 0;
   bool conv = (bnorm == 0.0) || (std::sqrt(rsq) < eps * bnorm);
@@ -220,8 +205,8 @@ inline inversion_info minv_vector_cg(complex<double>* phi, complex<double>* phi0
   complex<double>*r = pool.get(), *p = pool.get(), *Ap = pool.get();
   const double bnorm = std::sqrt(norm2sq(phi0, size));
   int ops = 0;
-  if (qmg::take_zero_guess()) copy_vector(r, phi0, size);
-  else { matrix_vector(Ap, phi, extra_info); ops++; caxpbyz(1.0, phi0, -1.0, Ap, r, size); }
+  matrix_vector(Ap, phi, extra_info); ops++;
+  caxpbyz(1.0, phi0, -1.0, Ap, r, size);
   copy_vector(p, r, size);
   double rsq = norm2sq(r, size);
   int k = 0;
@@ -295,13 +280,9 @@ inline inversion_info qmg_gcr_core(complex<double>* phi, complex<double>* phi0, 
   const double bsq = norm2sq(phi0, size);
   const double bnorm = std::sqrt(bsq);
   int ops = 0;
-  double rsq;
-  if (qmg::take_zero_guess()) { copy_vector(r, phi0, size); rsq = bsq; }   // x0 == 0: r = b
-  else {
-    matrix_vector(tmp, phi, extra_info); ops++;
-    caxpbyz(1.0, phi0, -1.0, tmp, r, size);
-    rsq = norm2sq(r, size);
-  }
+  matrix_vector(tmp, phi, extra_info); ops++;
+  caxpbyz(1.0, phi0, -1.0, tmp, r, size);
+  double rsq = norm2sq(r, size);
   double rsq_ref = rsq;
   bool conv = (bnorm == 0.0) || (std::sqrt(rsq) < eps * bnorm);
   int k = 0, kb = 0;   // total iterations, index within the current basis
@@ -387,8 +368,8 @@ inline inversion_info minv_vector_bicgstab_l(complex<double>* phi, complex<doubl
   complex<double>* rt = pool.get();
   const double bnorm = std::sqrt(norm2sq(phi0, size));
   int ops = 0;
-  if (qmg::take_zero_guess()) copy_vector(r[0], phi0, size);
-  else { matrix_vector(u[0], phi, extra_info); ops++; caxpbyz(1.0, phi0, -1.0, u[0], r[0], size); }
+  matrix_vector(u[0], phi, extra_info); ops++;
+  caxpbyz(1.0, phi0, -1.0, u[0], r[0], size);
   copy_vector(rt, r[0], size);
   zero_vector(u[0], size);
   complex<double> rho0 = 1.0, alpha = 0.0, omega = 1.0;
@@ -468,7 +449,6 @@ inline inversion_info minv_vector_richardson(complex<double>* phi, complex<doubl
   int ops = 0, k = 0;
   double rsq = 0.0;
   bool conv = false;
-  qmg::take_zero_guess();   // no saving taken here: the first sweep's A*x0 is folded into the loop
   while (k < max_iter) {
     matrix_vector(Ax, phi, extra_info); ops++;
     caxpbyz(1.0, phi0, -1.0, Ax, r, size);

@@ -246,9 +246,6 @@ class MultigridMG {
 };
 
 // ---------------- solve state + K-cycle (stateful_multigrid.h) ----------------
-class StatefulMultigridMG;
-// batch.hpp: the K-cycle engine every supported configuration runs on (one system = a batch of one); false = not served there
-inline bool qmg_kcycle_via_batch(StatefulMultigridMG* mg, complex<double>* lhs, complex<double>* rhs, int size, inversion_verbose_struct* verb);
 enum QMGDslashType { QMG_DSLASH_TYPE_NULLVEC = 0, QMG_DSLASH_TYPE_KRYLOV = 1, QMG_DSLASH_TYPE_PRESMOOTH = 2, QMG_DSLASH_TYPE_POSTSMOOTH = 3 };
 
 class StatefulMultigridMG : public MultigridMG {
@@ -383,188 +380,9 @@ class StatefulMultigridMG : public MultigridMG {
     else if (in_range(i, "reset tracker")) dslash_tracker_list[i]->reset_tracker();
   }
 
- protected:
-  struct ShiftedFunctionStruct { matrix_op_cplx function; void* extra_data; complex<double> extra_shift; int length; };
-  static void shift_function(complex<double>* out, complex<double>* in, void* data) {   // :724-729
-    ShiftedFunctionStruct* s = (ShiftedFunctionStruct*)data;
-    s->function(out, in, s->extra_data);
-    caxpy(s->extra_shift, in, out, s->length);
-  }
-
- public:
-  // One K-cycle application, lhs ~= A^-1 rhs (stateful_multigrid.h:734-1060), every step a device kernel.
-  static void mg_preconditioner(complex<double>* lhs, complex<double>* rhs, int size, void* extra_data, inversion_verbose_struct* verb) {
-    StatefulMultigridMG* mg = (StatefulMultigridMG*)extra_data;
-    const int level = mg->get_multigrid_level();
-    Stencil2D* fine_stencil = mg->get_stencil(level);
-    const int total_num_levels = mg->get_num_levels();
-
-    LevelSolveMG* level_solve = (total_num_levels > 1) ? mg->get_level_solve() : 0;
-    if (total_num_levels > 1 && level_solve == 0) { std::cout << "[QMG-MG-SOLVE-ERROR]: Level solve for level " << level << " does not exist.\n"; return; }
-    const long fine_size = mg->get_lattice(level)->get_size_cv_l();
-    if (total_num_levels == 1) { copy_vector(lhs, rhs, fine_size); return; }   // :803-807
-    // ONE engine: every configuration runs in the lock-step batch engine as a batch of one system (batch.hpp: same algorithm step for
-    // step, the fixed-count smoothers' scalars on the device, apply epilogues).  What continues below is the reference-shaped
-    // single-vector code: QMG_KCYCLE_ENGINE=single (A/B runs, the digit-for-digit slab comparisons of the tests), QMG_KCYCLE_SLAB_ENGINE=single,
-    // and a hierarchy whose level types name a variant stencil that was not built (it warns exactly as the reference does).
-    if (qmg_kcycle_via_batch(mg, lhs, rhs, size, verb)) return;
-
-    Stencil2D* coarse_stencil = mg->get_stencil(level + 1);
-    TransferMG* transfer = mg->get_transfer(level);
-    ArrayStorageMG<complex<double>>* fine_storage = mg->get_storage(level);
-    ArrayStorageMG<complex<double>>* coarse_storage = mg->get_storage(level + 1);
-    const long coarse_size = mg->get_lattice(level + 1)->get_size_cv_l();
-
-    inversion_info invif;
-    inversion_verbose_struct verb2(VERB_SUMMARY, std::string(" "));
-    if (verb == 0 || verb->verbosity == VERB_NONE) { verb2.verbosity = VERB_NONE; verb2.precond_verbosity = VERB_NONE; }
-    else verb2.precond_verbosity = VERB_SUMMARY;
-    verb2.verb_prefix = "  ";
-    for (int i = 1; i < level + 1; i++) verb2.verb_prefix += "  ";
-    verb2.verb_prefix += "[QMG-MG-SOLVE-INFO]: Level " + to_string(level + 1) + " ";
-
-    const int n_pre_smooth = level_solve->pre_iters, n_post_smooth = level_solve->post_iters;
-    const double pre_smooth_tol = level_solve->pre_tol, post_smooth_tol = level_solve->post_tol;
-    const bool pre_cgne = level_solve->pre_cgne, post_cgne = level_solve->post_cgne;
-    const QMGStencilType fine_type = level_solve->fine_stencil_app;
-    matrix_op_cplx apply_fine_M = Stencil2D::get_apply_function(fine_type);
-    long fine_size_solve = fine_size;
-    if (fine_type == QMG_MATVEC_RIGHT_SCHUR) fine_size_solve /= 2;
-
-    int coarse_max_iter, coarse_restart;
-    double coarse_tol;
-    QMGStencilType coarse_type;
-    if (level < total_num_levels - 2) {
-      LevelSolveMG* cs = mg->get_level_solve(level + 1);
-      coarse_type = cs->fine_stencil_app; coarse_max_iter = cs->intermediate_iters; coarse_tol = cs->intermediate_tol; coarse_restart = cs->intermediate_restart_freq;
-    } else {
-      CoarsestSolveMG* cs = mg->get_coarsest_solve();
-      coarse_type = cs->coarsest_stencil_app; coarse_max_iter = cs->coarsest_iters; coarse_tol = cs->coarsest_tol; coarse_restart = cs->coarsest_restart_freq;
-    }
-    matrix_op_cplx apply_coarse_M = Stencil2D::get_apply_function(coarse_type);
-    long coarse_size_solve = coarse_size;
-    if (coarse_type == QMG_MATVEC_RIGHT_SCHUR) coarse_size_solve /= 2;
-
-    complex<double>* Atmp = fine_storage->check_out();
-    complex<double>* z1 = fine_storage->check_out();
-    zero_vector(z1, fine_size);
-    complex<double>* r1 = fine_storage->check_out();
-
-    // ---- 1. pre-smooth: A z1 ~ rhs, r1 = rhs - A z1 (:845-873)
-    if (n_pre_smooth > 0) {
-      if (pre_cgne && (fine_type == QMG_MATVEC_ORIGINAL || fine_type == QMG_MATVEC_RIGHT_JACOBI)) {
-        complex<double>* z1_prec = fine_storage->check_out();
-        zero_vector(z1_prec, fine_size);
-        qmg::zero_guess_flag() = true;   // the iterate was zeroed just above: r0 = rhs, no A*0 (krylov.hpp)
-        invif = minv_vector_minres(z1_prec, rhs, (int)fine_size_solve, n_pre_smooth, pre_smooth_tol, 0.85,
-                                   Stencil2D::get_apply_function(fine_type == QMG_MATVEC_ORIGINAL ? QMG_MATVEC_M_MDAGGER : QMG_MATVEC_RBJ_M_MDAGGER), (void*)fine_stencil);
-        fine_stencil->apply_M(z1, z1_prec, fine_type == QMG_MATVEC_ORIGINAL ? QMG_MATVEC_DAGGER : QMG_MATVEC_RBJ_DAGGER);
-        mg->add_tracker_count(QMG_DSLASH_TYPE_PRESMOOTH, 2 * invif.ops_count + 1, level);
-        fine_storage->check_in(z1_prec);
-      } else {
-        qmg::zero_guess_flag() = true;   // the iterate was zeroed just above: r0 = rhs, no A*0 (krylov.hpp)
-        invif = minv_vector_minres(z1, rhs, (int)fine_size_solve, n_pre_smooth, pre_smooth_tol, 0.85, apply_fine_M, (void*)fine_stencil);
-        mg->add_tracker_count(QMG_DSLASH_TYPE_PRESMOOTH, invif.ops_count, level);
-      }
-      apply_fine_M(Atmp, z1, (void*)fine_stencil);   // = zero_vector + apply_M(.., fine_type), one launch for ORIGINAL
-      mg->add_tracker_count(QMG_DSLASH_TYPE_PRESMOOTH, 1, level);
-      caxpbyz(1.0, rhs, -1.0, Atmp, r1, fine_size_solve);
-    } else {
-      zero_vector(Atmp, fine_size_solve);
-      copy_vector(r1, rhs, fine_size_solve);
-      copy_vector(z1, rhs, fine_size_solve);
-    }
-    // (Schur: the odd half of r1 must not leak stale pool data into the restriction)
-    if (fine_type == QMG_MATVEC_RIGHT_SCHUR) zero_vector(r1 + fine_size_solve, fine_size - fine_size_solve);
-
-    // ---- 2. restrict, prepare, coarse solve (recursion = the "K"), reconstruct (:875-1002)
-    complex<double>* r_coarse = coarse_storage->check_out();
-    zero_vector(r_coarse, coarse_size);
-    transfer->restrict_f2c(r1, r_coarse);
-    fine_storage->check_in(r1);
-    const double rnorm = std::sqrt(norm2sq(r_coarse, coarse_size));
-    complex<double>* r_coarse_prep = coarse_storage->check_out();
-    zero_vector(r_coarse_prep, coarse_size);
-    coarse_stencil->prepare_M(r_coarse_prep, r_coarse, coarse_type);
-    const double rnorm_prep = std::sqrt(norm2sq(r_coarse_prep, coarse_size));
-    complex<double>* e_coarse = coarse_storage->check_out();
-    zero_vector(e_coarse, coarse_size);
-    const double inner_tol = (rnorm_prep > 0.0) ? coarse_tol * rnorm / rnorm_prep : coarse_tol;
-    qmg::zero_guess_flag() = true;   // e_coarse was zeroed just above; consumed by whichever solver runs next
-    if (level == total_num_levels - 2) {
-      const bool coarsest_normal = (coarse_type == QMG_MATVEC_M_MDAGGER || coarse_type == QMG_MATVEC_MDAGGER_M ||
-                                    coarse_type == QMG_MATVEC_RBJ_M_MDAGGER || coarse_type == QMG_MATVEC_RBJ_MDAGGER_M);
-      ShiftedFunctionStruct shift_struct;
-      matrix_op_cplx op = apply_coarse_M;
-      void* opdata = (void*)coarse_stencil;
-      if (coarsest_normal && mg->get_coarsest_solve()->normal_shift != 0.0) {
-        shift_struct.function = apply_coarse_M; shift_struct.extra_data = (void*)coarse_stencil;
-        shift_struct.extra_shift = mg->get_coarsest_solve()->normal_shift; shift_struct.length = (int)coarse_size_solve;
-        op = shift_function; opdata = (void*)&shift_struct;
-      }
-      if (coarse_restart == -1) {
-        if (!coarsest_normal) invif = minv_vector_gcr(e_coarse, r_coarse_prep, (int)coarse_size_solve, coarse_max_iter, inner_tol, op, opdata, &verb2);
-        else invif = minv_vector_cg(e_coarse, r_coarse_prep, (int)coarse_size_solve, coarse_max_iter, inner_tol, op, opdata, &verb2);
-      } else {
-        if (!coarsest_normal) invif = minv_vector_gcr_restart(e_coarse, r_coarse_prep, (int)coarse_size_solve, coarse_max_iter, inner_tol, coarse_restart, op, opdata, &verb2);
-        else invif = minv_vector_cg_restart(e_coarse, r_coarse_prep, (int)coarse_size_solve, coarse_max_iter, inner_tol, coarse_restart, op, opdata, &verb2);
-      }
-    } else {
-      mg->go_coarser();
-      if (coarse_restart == -1)
-        invif = minv_vector_gcr_var_precond(e_coarse, r_coarse_prep, (int)coarse_size_solve, coarse_max_iter, inner_tol, apply_coarse_M, (void*)coarse_stencil,
-                                            mg_preconditioner, (void*)mg, &verb2);
-      else
-        invif = minv_vector_gcr_var_precond_restart(e_coarse, r_coarse_prep, (int)coarse_size_solve, coarse_max_iter, inner_tol, coarse_restart, apply_coarse_M,
-                                                    (void*)coarse_stencil, mg_preconditioner, (void*)mg, &verb2);
-      mg->go_finer();
-    }
-    mg->add_tracker_count(QMG_DSLASH_TYPE_KRYLOV, invif.ops_count, level + 1);
-    mg->add_iterations_count(invif.iter, level + 1);
-    coarse_storage->check_in(r_coarse_prep);
-    complex<double>* e_coarse_reconstruct = coarse_storage->check_out();
-    zero_vector(e_coarse_reconstruct, coarse_size);
-    coarse_stencil->reconstruct_M(e_coarse_reconstruct, e_coarse, r_coarse, coarse_type);
-    coarse_storage->check_in(r_coarse);
-    coarse_storage->check_in(e_coarse);
-
-    // ---- 3. prolong and correct (:1013-1021)
-    complex<double>* z2 = fine_storage->check_out();
-    zero_vector(z2, fine_size);
-    transfer->prolong_c2f(e_coarse_reconstruct, z2);
-    if (coarse_type == QMG_MATVEC_RIGHT_SCHUR) zero_vector(z2 + fine_size / 2, fine_size / 2);
-    coarse_storage->check_in(e_coarse_reconstruct);
-    cxpyz(z1, z2, lhs, fine_size_solve);
-    fine_storage->check_in(z1);
-    fine_storage->check_in(z2);
-
-    // ---- 4. post-smooth on r2 = rhs - A lhs (:1023-1056)
-    if (n_post_smooth > 0) {
-      apply_fine_M(Atmp, lhs, (void*)fine_stencil);
-      complex<double>* r2 = fine_storage->check_out();
-      caxpbyz(1.0, rhs, -1.0, Atmp, r2, fine_size_solve);
-      complex<double>* z3 = fine_storage->check_out();
-      zero_vector(z3, fine_size);
-      if (post_cgne && (fine_type == QMG_MATVEC_ORIGINAL || fine_type == QMG_MATVEC_RIGHT_JACOBI)) {
-        complex<double>* z3_prec = fine_storage->check_out();
-        zero_vector(z3_prec, fine_size);
-        qmg::zero_guess_flag() = true;   // the iterate was zeroed just above: r0 = rhs, no A*0 (krylov.hpp)
-        invif = minv_vector_minres(z3_prec, r2, (int)fine_size_solve, n_post_smooth, post_smooth_tol, 0.85,
-                                   Stencil2D::get_apply_function(fine_type == QMG_MATVEC_ORIGINAL ? QMG_MATVEC_M_MDAGGER : QMG_MATVEC_RBJ_M_MDAGGER), (void*)fine_stencil);
-        fine_stencil->apply_M(z3, z3_prec, fine_type == QMG_MATVEC_ORIGINAL ? QMG_MATVEC_DAGGER : QMG_MATVEC_RBJ_DAGGER);
-        mg->add_tracker_count(QMG_DSLASH_TYPE_POSTSMOOTH, 2 * invif.ops_count + 1, level);
-        fine_storage->check_in(z3_prec);
-      } else {
-        qmg::zero_guess_flag() = true;   // the iterate was zeroed just above: r0 = rhs, no A*0 (krylov.hpp)
-        invif = minv_vector_minres(z3, r2, (int)fine_size_solve, n_post_smooth, post_smooth_tol, 0.85, apply_fine_M, (void*)fine_stencil);
-        mg->add_tracker_count(QMG_DSLASH_TYPE_POSTSMOOTH, invif.ops_count, level);
-      }
-      cxpy(z3, lhs, fine_size_solve);
-      fine_storage->check_in(r2);
-      fine_storage->check_in(z3);
-    }
-    fine_storage->check_in(Atmp);
-  }
+  // One K-cycle application, lhs ~= A^-1 rhs (stateful_multigrid.h:734-1060): mg_preconditioner_batch on a batch of one system,
+  // defined at the end of batch.hpp.
+  static void mg_preconditioner(complex<double>* lhs, complex<double>* rhs, int size, void* extra_data, inversion_verbose_struct* verb);
 };
 
 #endif

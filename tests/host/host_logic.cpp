@@ -1,8 +1,7 @@
 // Host-only checks of the facade's solver bookkeeping (no GPU call is made; links libqmg_hip.so for the symbols only).
 //   1. qmg::gcr_direction_weights: GCR with RAW search directions + back-substitution == GCR with explicitly
 //      orthogonalised directions (krylov.hpp), on a small dense host problem.
-//   2. qmg::ZeroGuess / take_zero_guess: the hint is consumed exactly once and cleared on scope exit.
-//   3. batch masks and views (batch.hpp).
+//   2. batch masks and views (batch.hpp).
 #include <complex>
 #include <cstdio>
 #include <random>
@@ -62,13 +61,7 @@ int main() {
   for (int i = 0; i < n; i++) { rr += std::norm(b[i] - res[i]); bb += std::norm(b[i]); }
   if (!(rr < 1e-6 * bb)) { printf("FAIL gcr residual %.3e\n", std::sqrt(rr / bb)); fails++; }
 
-  // ---- 2. zero-guess hint
-  if (qmg::take_zero_guess()) { printf("FAIL hint set by default\n"); fails++; }
-  { qmg::ZeroGuess zg; if (!qmg::take_zero_guess()) { printf("FAIL hint not delivered\n"); fails++; } if (qmg::take_zero_guess()) { printf("FAIL hint delivered twice\n"); fails++; } }
-  { qmg::ZeroGuess zg; }
-  if (qmg::take_zero_guess()) { printf("FAIL hint leaked out of scope\n"); fails++; }
-
-  // ---- 3. batch views and masks
+  // ---- 2. batch views and masks
   if (qmg::full_mask(5) != 0x1Fu || qmg::full_mask(16) != 0xFFFFu) { printf("FAIL full_mask\n"); fails++; }
   if (!qmg::is_active(0b0100u, 2) || qmg::is_active(0b0100u, 1)) { printf("FAIL is_active\n"); fails++; }
   cd* base = reinterpret_cast<cd*>(0x1000);

@@ -295,6 +295,35 @@ def wilson_kcycle_history(L, mass, n_refine, coarse_dof, gauge, nullvecs, b, tol
     return it, x, true_res.value, list(ops), list(its), hist[:nho.value].copy(), chist[:ncho.value].copy()
 
 
+# operator types (oracle/qmg_oracle.h QO_MATVEC_*, stencil_2d.h QMGStencilType)
+(MATVEC_ORIGINAL, MATVEC_DAGGER, MATVEC_RIGHT_JACOBI, MATVEC_RIGHT_SCHUR, MATVEC_M_MDAGGER, MATVEC_MDAGGER_M, MATVEC_RBJ_DAGGER,
+ MATVEC_RBJ_M_MDAGGER, MATVEC_RBJ_MDAGGER_M) = range(9)
+
+
+class KcycleParams(C.Structure):
+    _fields_ = [("L", C.c_int), ("mass", C.c_double), ("n_refine", C.c_int), ("coarse_dof", C.c_int),
+                ("tol", C.c_double), ("max_iter", C.c_int), ("restart", C.c_int),
+                ("inner_tol", C.c_double), ("coarsest_tol", C.c_double), ("n_smooth", C.c_int),
+                ("level_type", C.c_int), ("coarsest_type", C.c_int), ("cgne", C.c_int), ("normal_shift", C.c_double)]
+
+
+def kcycle(L, mass, n_refine, coarse_dof, gauge, nullvecs, b, level_type=MATVEC_ORIGINAL, coarsest_type=None, cgne=False, normal_shift=0.0,
+           tol=1e-10, max_iter=1000, restart=32, inner_tol=0.2, coarsest_tol=0.2, n_smooth=2):
+    """CPU K-cycle solve of the ORIGINAL system b with every branch the oracle restates (oracle/qmg_oracle_kcycle.cpp qo_kcycle):
+    level_type ORIGINAL (n13 hierarchy) or RIGHT_JACOBI / RIGHT_SCHUR (n19 hierarchy), coarsest_type None (= level_type, GCR) or a
+    normal form (CG, + normal_shift), CGNE smoothers.  Returns (outer iterations, reconstructed x, true residual, ops, its)."""
+    q = KcycleParams(L, mass, n_refine, coarse_dof, tol, max_iter, restart, inner_tol, coarsest_tol, n_smooth, level_type,
+                     level_type if coarsest_type is None else coarsest_type, int(cgne), normal_shift)
+    ptrs = (C.c_void_p * n_refine)(*[nv.ctypes.data for nv in nullvecs])
+    x = cvec(L * L * 2)
+    true_res = C.c_double()
+    ops = (C.c_long * (n_refine + 1))()
+    its = (C.c_long * (n_refine + 1))()
+    it = lib().qo_kcycle(C.byref(q), _p(gauge), ptrs, _p(b), _p(x), C.byref(true_res), ops, its, None, 0, None, None, 0, None)
+    assert it > -100000, it
+    return it, x, true_res.value, list(ops), list(its)
+
+
 KRYLOV_CG, KRYLOV_BICGSTAB_L, KRYLOV_RICHARDSON, KRYLOV_MR, KRYLOV_GCR = range(5)
 
 

@@ -109,7 +109,7 @@ def test_wilson_kcycle_matches_oracle(golden_dir, L, n_refine, coarse_dof, mass)
     d = ol.make_desc(L, L, 2, clover, hopping, mass)
     assert cs.rel_l2(ol.stencil_apply(d, x_gpu), b) <= 1.1e-10
     # Dslash counts per level as tracked by the facade (stateful_multigrid.h:854-865).  The facade skips the smoothers'
-    # opening A*0 (zero initial guess, krylov.hpp ZeroGuess), takes the pre-smoother's recursive residual instead of
+    # opening A*0 (zero initial guess, batch.hpp *_zero_guess), takes the pre-smoother's recursive residual instead of
     # recomputing rhs - A z1 (batch.hpp bmr_fixed_zero_guess), and counts the applies it really performs:
     # pre = n_pre, post = n_post per outer iteration (the reference's accounting: n_pre + 2 and n_post + 1).
     m = re.search(r"Level 0 NullVec 0 PreSmooth (\d+) Krylov 0 PostSmooth (\d+)", out.stdout)
@@ -227,38 +227,31 @@ def test_schur_kcycle_with_narrow_stored_rbjacobi_operators(golden_dir):
     assert abs(its["f32"] - its["f64"]) <= 1 and abs(its["f16"] - its["f64"]) <= 1, its
 
 
-def test_cgne_smoothers_in_both_engines(golden_dir):
+def test_cgne_smoothers_match_the_oracle(golden_dir):
     """LevelSolveMG::pre_cgne / post_cgne (stateful_multigrid.h:847-857, 1032-1042: MR on M M^dagger, then M^dagger; no reference test sets the flags, the
     driver takes QMG_SMOOTHER=cgne).  The lock-step batch engine (dagger stencil by name, the MR dots riding on the second apply, fixed-count
-    device-scalar form) against the reference-shaped single-vector code of multigrid.hpp (perform_swap_dagger, minv_vector_minres on
-    apply_M_M_dagger): same outer iteration count, the same solution, true residual <= 1e-10; the trackers count what each engine performs
-    (per level visit 2 (2 x 2 + 1) smoother applies, plus the two residual applies the single-vector engine spends and the batch engine saves
-    one of).  Then three systems in lock step, fp64 and with the K-cycle in complex<float> (the dagger stencil's fp32 shadow)."""
+    device-scalar form) against the CPU oracle's K-cycle with CGNE smoothers on the same dumped null vectors and right-hand side: the same outer
+    iteration count, the same solution, true residual <= 1e-10; the trackers count what the engine performs (per level visit 2 x 2 + 1 smoother
+    applies, the pre-smoother handing back its recursive residual).  Then three systems in lock step, fp64 and with the K-cycle in complex<float>
+    (the dagger stencil's fp32 shadow)."""
     gauge_file = os.path.join(golden_dir, "l64t64b60_heatbath.dat")
+    args = ["128", "-0.07", "6.0", "2", "8", gauge_file, "64"]
     res = {}
-    for tag, extra in (("batch", {}), ("single", {"QMG_KCYCLE_ENGINE": "single"}), ("mr", {"QMG_SMOOTHER": "mr"})):
-        with tempfile.TemporaryDirectory() as d:
-            env = dict(os.environ, QMG_QUIET="1", QMG_SMOOTHER="cgne", QMG_DUMP_DIR=d)
-            env.update(extra)
-            out = subprocess.run([os.path.join(DRIVERS, "n13_wilson_kcycle"), "128", "-0.07", "6.0", "2", "8", gauge_file, "64"], cwd=DRIVERS, env=env,
-                                 capture_output=True, text=True, timeout=150)
-            assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-2000:]
-            assert "[QMG-ERROR]" not in out.stdout and "[QMG-WARNING]" not in out.stdout
-            assert ("CGNE smoothers" in out.stdout) == (tag != "mr")
-            it = int(re.search(r"Multigrid converged in (\d+) iterations", out.stdout).group(1))
-            chk = float(re.search(r"Check tolerance ([-\d.e+]+)", out.stdout).group(1))
-            m = re.search(r"Level 0 NullVec 0 PreSmooth (\d+) Krylov 0 PostSmooth (\d+)", out.stdout)
-            x = np.fromfile(os.path.join(d, "x.bin"), dtype=np.complex128)
-            res[tag] = (it, chk, int(m.group(1)), int(m.group(2)), x)
+    for tag, extra in (("batch", {}), ("mr", {"QMG_SMOOTHER": "mr"})):
+        it, chk, x, out, nullvecs, b = _kcycle_run("n13_wilson_kcycle", args, dict({"QMG_SMOOTHER": "cgne"}, **extra), n_refine=2)
+        assert ("CGNE smoothers" in out) == (tag != "mr")
+        m = re.search(r"Level 0 NullVec 0 PreSmooth (\d+) Krylov 0 PostSmooth (\d+)", out)
+        res[tag] = (it, chk, int(m.group(1)), int(m.group(2)), x, nullvecs, b)
     for tag in res:
         assert res[tag][1] <= 1.05e-10, (tag, res[tag][:4])
-    assert res["batch"][0] == res["single"][0], (res["batch"][:4], res["single"][:4])
-    rel = np.linalg.norm(res["batch"][4] - res["single"][4]) / np.linalg.norm(res["single"][4])
-    assert rel < 1e-8, rel
     it = res["batch"][0]
+    o_it, x_cpu, o_res, _, _ = ol.kcycle(128, -0.07, 2, 8, _tiled_gauge(gauge_file, 128), res["batch"][5], res["batch"][6], cgne=True)
+    assert o_it > 0 and o_res <= 1.05e-10
+    assert it == o_it, (res["batch"][:4], o_it)
+    rel = np.linalg.norm(res["batch"][4] - x_cpu) / np.linalg.norm(x_cpu)
+    assert rel < 1e-8, rel
     # level-0 visits = outer iterations; smoother applies per visit: MR on M M^dagger costs 2 per step, + the closing M^dagger
     assert res["batch"][2] == it * 5 and res["batch"][3] == it * 5, res["batch"][:4]
-    assert res["single"][2] == it * 6 and res["single"][3] == it * 5, res["single"][:4]
     assert res["mr"][2] == res["mr"][0] * 2                                                                # (plain MR: 2 applies per visit)
     for extra in ([], ["f32"]):
         out = subprocess.run([os.path.join(DRIVERS, "n13_wilson_kcycle_mrhs"), "128", "-0.07", "6.0", "2", "8", gauge_file, "64", "3", "verify"] + extra, cwd=DRIVERS,
@@ -337,7 +330,15 @@ def test_rbjacobi_hops_from_the_links_reproduce_the_stored_stencil_solve(golden_
             assert abs(int(a[1]) - int(b[1])) <= 1 and float(a[3]) <= 1.05e-10
 
 
-def _kcycle_run(driver, args, env_extra, timeout=200):
+def _tiled_gauge(gauge_file, L):
+    """the drivers' read_gauge_u1_tiled: the fixture's phases (file order x, y, mu) repeated over an L x L lattice"""
+    ph = np.loadtxt(gauge_file)
+    t = int(round((ph.size // 2) ** 0.5))
+    return ol.phases_to_gauge_u1(np.tile(ph.reshape(t, t, 2), (L // t, L // t, 1)).reshape(-1), L, L)
+
+
+def _kcycle_run(driver, args, env_extra, n_refine, timeout=200):
+    """one driver run under QMG_DUMP_DIR: outer iterations, check tolerance, x, stdout, and the dumped null vectors and right-hand side"""
     with tempfile.TemporaryDirectory() as d:
         env = dict(os.environ, QMG_QUIET="1", QMG_DUMP_DIR=d)
         env.update(env_extra)
@@ -346,8 +347,10 @@ def _kcycle_run(driver, args, env_extra, timeout=200):
         assert "[QMG-ERROR]" not in out.stdout and "[QMG-WARNING]" not in out.stdout, out.stdout[-3000:]
         it = int(re.search(r"Multigrid converged in (\d+) iterations", out.stdout).group(1))
         chk = float(re.search(r"Check tolerance ([-\d.e+]+)", out.stdout).group(1))
-        x = np.fromfile(os.path.join(d, "x.bin"), dtype=np.complex128)
-    return it, chk, x, out.stdout
+        load = lambda name: np.fromfile(os.path.join(d, name), dtype=np.complex128)
+        x, b = load("x.bin"), load("b.bin")
+        nullvecs = [load("nullvecs_level%d.bin" % l) for l in range(n_refine)]
+    return it, chk, x, out.stdout, nullvecs, b
 
 
 @pytest.mark.parametrize("hooks", [
@@ -357,36 +360,39 @@ def _kcycle_run(driver, args, env_extra, timeout=200):
     {"QMG_SOLVE_TYPE": "jacobi", "QMG_COARSEST_TYPE": "rbj_mdm", "QMG_NORMAL_SHIFT": "0.01"},
     {"QMG_COARSEST_TYPE": "rbj_mdm"},
 ], ids=["jacobi", "jacobi-cgne", "jacobi-coarsest-MMdag", "jacobi-coarsest-MdagM-shifted", "schur-coarsest-MdagM"])
-def test_right_jacobi_levels_and_normal_coarsest_solves_in_both_engines(golden_dir, hooks):
+def test_right_jacobi_levels_and_normal_coarsest_solves_match_the_oracle(golden_dir, hooks):
     """The branches of StatefulMultigridMG::mg_preconditioner no reference driver selects (stateful_multigrid.h:845-857 CGNE on a RIGHT_JACOBI level, :930-960 the
     coarsest solve by CG on a normal-equation operator with normal_shift; stencil_2d.h:2418-2527 apply / prepare / reconstruct by type), reached through the n19
     counterpart's environment hooks.  The lock-step batch engine (operators by name: right-block-Jacobi hops + unit shift, its dagger stencil, batched CG) against
-    the reference-shaped single-vector code of multigrid.hpp (perform_swap_*, minv_vector_cg): the same outer iteration count, the same reconstructed solution,
-    true residual against the ORIGINAL operator <= 1e-7 (tol 1e-8 on the preconditioned system).  Parity here is engine against engine: the reference holds no
-    output for these branches."""
+    the CPU oracle's K-cycle on the same dumped null vectors and right-hand side (n19 hierarchy: Galerkin from the right-block-Jacobi stencil): the same outer
+    iteration count (+-1), the same reconstructed solution, true residual against the ORIGINAL operator <= 1e-7 (tol 1e-8 on the preconditioned system)."""
     gauge_file = os.path.join(golden_dir, "l64t64b60_heatbath.dat")
-    args = ["128", "2", gauge_file, "64"]
-    b = _kcycle_run("n19_wilson_kcycle_precond", args, hooks)
-    s = _kcycle_run("n19_wilson_kcycle_precond", args, dict(hooks, QMG_KCYCLE_ENGINE="single"))
-    assert "solve type" in b[3]
-    assert b[1] <= 1e-7 and s[1] <= 1e-7, (b[:2], s[:2])
-    assert abs(b[0] - s[0]) <= 1, (b[:2], s[:2])
-    rel = np.linalg.norm(b[2] - s[2]) / np.linalg.norm(s[2])
+    it, chk, x, out, nullvecs, b = _kcycle_run("n19_wilson_kcycle_precond", ["128", "2", gauge_file, "64"], hooks, n_refine=2)
+    assert "solve type" in out
+    level_type = ol.MATVEC_RIGHT_JACOBI if hooks.get("QMG_SOLVE_TYPE") == "jacobi" else ol.MATVEC_RIGHT_SCHUR
+    coarsest = {"rbj_mmd": ol.MATVEC_RBJ_M_MDAGGER, "rbj_mdm": ol.MATVEC_RBJ_MDAGGER_M}.get(hooks.get("QMG_COARSEST_TYPE"))
+    o_it, x_cpu, o_res, _, _ = ol.kcycle(128, -0.07, 2, 8, _tiled_gauge(gauge_file, 128), nullvecs, b, level_type=level_type, coarsest_type=coarsest,
+                                         cgne=hooks.get("QMG_SMOOTHER") == "cgne", normal_shift=float(hooks.get("QMG_NORMAL_SHIFT", 0.0)), tol=1e-8)
+    assert chk <= 1e-7 and 0 < o_it and o_res <= 1e-7, (it, chk, o_it, o_res)
+    assert abs(it - o_it) <= 1, (it, o_it)
+    rel = np.linalg.norm(x - x_cpu) / np.linalg.norm(x_cpu)
     assert rel < 1e-6, rel
 
 
 @pytest.mark.parametrize("ctype", ["mmd", "mdm"])
-def test_coarsest_cg_on_the_original_hierarchy_in_both_engines(golden_dir, ctype):
+def test_coarsest_cg_on_the_original_hierarchy_matches_the_oracle(golden_dir, ctype):
     """n13's hierarchy with the coarsest solve by CG on M M^dagger / M^dagger M (CoarsestSolveMG::coarsest_stencil_app, stateful_multigrid.h:930-960; prepare_M /
-    reconstruct_M of those types, stencil_2d.h:1413-1446): batch engine (bcg_core, the dagger stencil by name) against the single-vector engine
-    (minv_vector_cg_restart, perform_swap_dagger) -- same outer iterations, same solution, true residual <= 1e-10; then three systems in lock step."""
+    reconstruct_M of those types, stencil_2d.h:1413-1446): batch engine (bcg_core, the dagger stencil by name) against the CPU oracle's K-cycle (restarted CG on
+    the same normal operator) on the same dumped null vectors and right-hand side -- same outer iterations (+-1), same solution, true residual <= 1e-10; then
+    three systems in lock step."""
     gauge_file = os.path.join(golden_dir, "l64t64b60_heatbath.dat")
     args = ["128", "-0.07", "6.0", "2", "8", gauge_file, "64"]
-    b = _kcycle_run("n13_wilson_kcycle", args, {"QMG_COARSEST_TYPE": ctype})
-    s = _kcycle_run("n13_wilson_kcycle", args, {"QMG_COARSEST_TYPE": ctype, "QMG_KCYCLE_ENGINE": "single"})
-    assert b[1] <= 1.05e-10 and s[1] <= 1.05e-10, (b[:2], s[:2])
-    assert abs(b[0] - s[0]) <= 1, (b[:2], s[:2])
-    rel = np.linalg.norm(b[2] - s[2]) / np.linalg.norm(s[2])
+    it, chk, x, _, nullvecs, b = _kcycle_run("n13_wilson_kcycle", args, {"QMG_COARSEST_TYPE": ctype}, n_refine=2)
+    o_it, x_cpu, o_res, _, _ = ol.kcycle(128, -0.07, 2, 8, _tiled_gauge(gauge_file, 128), nullvecs, b,
+                                         coarsest_type=ol.MATVEC_M_MDAGGER if ctype == "mmd" else ol.MATVEC_MDAGGER_M)
+    assert chk <= 1.05e-10 and 0 < o_it and o_res <= 1.05e-10, (it, chk, o_it, o_res)
+    assert abs(it - o_it) <= 1, (it, o_it)
+    rel = np.linalg.norm(x - x_cpu) / np.linalg.norm(x_cpu)
     assert rel < 1e-7, rel
     out = subprocess.run([os.path.join(DRIVERS, "n13_wilson_kcycle_mrhs"), "128", "-0.07", "6.0", "2", "8", gauge_file, "64", "3", "verify"], cwd=DRIVERS,
                          env=dict(os.environ, QMG_QUIET="1", QMG_COARSEST_TYPE=ctype), capture_output=True, text=True, timeout=200)

@@ -33,10 +33,9 @@ def _fp64_coarse_storage(monkeypatch):
     streams the fp64 arrays (multigrid.hpp: coarse_f32_wanted).  These tests compare the two runs digit by digit, so the children
     of this module run with fp64 coarse storage on both sides."""
     monkeypatch.setenv("QMG_COARSE_F32", "0")
-    # ... and with the same arithmetic on both sides: a slab run keeps the single-vector K-cycle of multigrid.hpp (its exchanges overlap the
-    # interior) and the separate BLAS-1 passes, while the single-domain default is the batch engine with apply epilogues -- the same numbers
-    # summed in a different order.  The digit-for-digit comparisons of this module are about the DECOMPOSITION, so both sides run the former.
-    monkeypatch.setenv("QMG_KCYCLE_ENGINE", "single")
+    # ... and with the same arithmetic on both sides: a slab run takes the separate BLAS-1 passes, while the single-domain default fuses
+    # some of them into apply epilogues -- the same numbers summed in a different order.  The digit-for-digit comparisons of this module are
+    # about the DECOMPOSITION, so both sides run the former.
     monkeypatch.setenv("QMG_APPLY_EPILOGUE", "0")
 
 
@@ -699,16 +698,16 @@ def test_narrow_stored_matrices_on_slabs(nc, nrhs, mask, bits, f32):
             assert np.array_equal(got[k * nl:(k + 1) * nl], rows(want[k * n:(k + 1) * n], Ly, row, y0, Ll)), (nc, r, k)
 
 
-@pytest.mark.parametrize("R,extra", [(2, {}), (4, {"QMG_COARSE_BITS": "16"}), (2, {"QMG_KCYCLE_SLAB_ENGINE": "single"})])
+@pytest.mark.parametrize("R,extra", [(2, {}), (4, {"QMG_COARSE_BITS": "16"})])
 def test_kcycle_on_slabs_with_the_default_engine_and_storage(R, extra, monkeypatch):
-    """What a slab run does when nothing is switched off (this module's other tests pin fp64 coarse storage and the single-vector engine to compare digit by digit):
-    the lock-step batch engine as a batch of one system (qmg_kcycle_via_batch; QMG_KCYCLE_SLAB_ENGINE=single: the single-vector code) streaming the complex<float>
+    """What a slab run does when nothing is switched off (this module's other tests pin fp64 coarse storage and separate BLAS-1 passes to compare digit by digit):
+    the lock-step batch engine as a batch of one system (StatefulMultigridMG::mg_preconditioner) streaming the complex<float>
     (QMG_COARSE_BITS=16: complex<half>) copies of the Galerkin matrices through the slab kernels.  One slab: the plain driver's outer iteration count; R thread-emulated
     slabs: the same count (+-1), true residual < 1e-9, the same solution norm to 1e-9."""
     import os
     import re
     import subprocess
-    for k in ("QMG_COARSE_F32", "QMG_KCYCLE_ENGINE", "QMG_APPLY_EPILOGUE"):
+    for k in ("QMG_COARSE_F32", "QMG_APPLY_EPILOGUE"):
         monkeypatch.delenv(k, raising=False)
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     drivers = os.path.join(root, "quantum-mg_amd", "drivers")
@@ -741,13 +740,13 @@ def test_red_black_kcycle_on_slabs_with_the_default_engine_and_storage(R, hooks,
     import os
     import re
     import subprocess
-    for k in ("QMG_COARSE_F32", "QMG_KCYCLE_ENGINE", "QMG_APPLY_EPILOGUE"):
+    for k in ("QMG_COARSE_F32", "QMG_APPLY_EPILOGUE"):
         monkeypatch.delenv(k, raising=False)
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     drivers = os.path.join(root, "quantum-mg_amd", "drivers")
     subprocess.check_call(["make", "-C", drivers, "-j4"], stdout=subprocess.DEVNULL)
-    # (the 64^2 fixture tiled to 128^2, as in test_gpu_kcycle: on the 128^2 fixture the restarted CG on M_rbj^dagger M_rbj stalls the outer solve at 1e-2 in BOTH
-    # engines -- identical residual histories -- which is the algorithm's business, not a test of the decomposition)
+    # (the 64^2 fixture tiled to 128^2, as in test_gpu_kcycle: on the 128^2 fixture the restarted CG on M_rbj^dagger M_rbj stalls the outer solve at 1e-2,
+    # which is the algorithm's business, not a test of the decomposition)
     gauge = os.path.join(root, "tests", "golden", "l64t64b60_heatbath.dat")
     args = [os.path.join(drivers, "n19_wilson_kcycle_precond"), "128", "2", gauge, "64"]
     env = dict(os.environ, QMG_QUIET="1")

@@ -1,5 +1,5 @@
 """CPU-side checks of the C++ facade's solver bookkeeping (tests/host/host_logic.cpp): the raw-direction GCR
-back-substitution, the zero-guess hint, batch masks / views.  Compiled with g++ against the headers; libqmg_hip.so is
+back-substitution, batch masks / views.  Compiled with g++ against the headers; libqmg_hip.so is
 linked for its symbols only -- no GPU call is made."""
 import importlib
 import os
