@@ -523,6 +523,9 @@ int qmg_batch_multi_caxpy_t(int dtype, const double* coeffs, const void* const* 
   if (!valid_dtype(dtype) || nrhs < 1 || nrhs > BATCH_MAX || nj < 0 || (nj > 0 && (!coeffs || !xs)) || (!y && n)) return QMG_ERR_INVALID;
   BatchIdx bi = expand_mask(mask, nrhs);
   if (bi.n == 0 || n == 0 || nj == 0) return QMG_SUCCESS;
+  // one fp64 system of 16 MB and more (a single outer solve on the fine lattice): the single-vector kernel, which takes up to 32 vector sets per
+  // pass over y instead of 8 -- the same sums in the same order
+  if (dtype == QMG_C64 && nrhs == 1 && n * 16 >= ((size_t)16 << 20)) return qmg_multi_caxpy(coeffs, xs, nj, y, n, stream);
   bi.nt = batch_nt(bi, n, dtype);
   int W = pack_width(dtype, n, stride, nrhs, {y});
   for (int j = 0; j < nj; j++) if (!xs[j]) return QMG_ERR_INVALID; else if (dtype == QMG_C32 && !aligned16(xs[j])) W = 1;

@@ -6,6 +6,7 @@
 // Systems: Wilson (nc = 2) at `mass` on the L x L gauge file for BiCGStab-L (L = 1, 6: n13:359 uses 6), Richardson (n22:289
 // parameters), MR(0.85) (the K-cycle smoother), restarted GCR(8) and unrestarted GCR, CG on M^dagger M (the coarsest
 // normal-equation solve, stateful_multigrid.h:915-969); gauged Laplace (nc = 1, m^2 = 0.01) for plain CG (n02 / n03).
+// The `*_x0` runs repeat BiCGStab-6, MR, GCR(8) and CG from a gaussian initial guess (dumped as x0_wilson / x0_laplace).
 // The last case drives CG from HOST vectors through apply_stencil_2D_host_thunk, the host-pointer compatibility thunk
 // with the reference's exact matrix_op_cplx signature (stencil_2d.h:15-19): an unmodified CPU solver
 // calling the GPU operator.
@@ -83,6 +84,12 @@ int main(int argc, char** argv) {
   zero_vector(x, nw); inv = minv_vector_minres(x, b, nw, 6, 1e-30, 0.85, apply_stencil_2D_M, (void*)&wilson); report("mr", inv, bn); dump(dir, "x_mr", x, nw);
   zero_vector(x, nw); inv = minv_vector_gcr_restart(x, b, nw, 400, 1e-9, 8, apply_stencil_2D_M, (void*)&wilson); report("gcr8", inv, bn); dump(dir, "x_gcr8", x, nw);
   zero_vector(x, nw); inv = minv_vector_gcr(x, b, nw, 60, 1e-9, apply_stencil_2D_M, (void*)&wilson); report("gcr", inv, bn); dump(dir, "x_gcr", x, nw);
+  complex<double>* x0 = allocate_vector<complex<double>>(nw);
+  gaussian(x0, nw, 4444ull);
+  dump(dir, "x0_wilson", x0, nw);
+  copy_vector(x, x0, nw); inv = minv_vector_bicgstab_l(x, b, nw, 500, 5e-5, 6, apply_stencil_2D_M, (void*)&wilson); report("bicgstab6_x0", inv, bn); dump(dir, "x_bicgstab6_x0", x, nw);
+  copy_vector(x, x0, nw); inv = minv_vector_minres(x, b, nw, 6, 1e-30, 0.85, apply_stencil_2D_M, (void*)&wilson); report("mr_x0", inv, bn); dump(dir, "x_mr_x0", x, nw);
+  copy_vector(x, x0, nw); inv = minv_vector_gcr_restart(x, b, nw, 400, 1e-9, 8, apply_stencil_2D_M, (void*)&wilson); report("gcr8_x0", inv, bn); dump(dir, "x_gcr8_x0", x, nw);
   // CG on the normal operator, right-hand side M^dag b
   complex<double>* bnrm = allocate_vector<complex<double>>(nw);
   zero_vector(bnrm, nw);
@@ -96,6 +103,9 @@ int main(int argc, char** argv) {
   gaussian(bl, nl, 4343ull);
   dump(dir, "b_laplace", bl, nl);
   zero_vector(xl, nl); inv = minv_vector_cg(xl, bl, nl, 2000, 1e-10, apply_stencil_2D_M, (void*)&laplace); report("cg_laplace", inv, sqrt(norm2sq(bl, nl))); dump(dir, "x_cg_laplace", xl, nl);
+  gaussian(xl, nl, 4545ull);
+  dump(dir, "x0_laplace", xl, nl);
+  inv = minv_vector_cg(xl, bl, nl, 2000, 1e-10, apply_stencil_2D_M, (void*)&laplace); report("cg_laplace_x0", inv, sqrt(norm2sq(bl, nl))); dump(dir, "x_cg_laplace_x0", xl, nl);
 
   // the same system from HOST vectors through the host-pointer thunk: a CPU CG that only knows matrix_op_cplx
   {
@@ -111,7 +121,7 @@ int main(int argc, char** argv) {
     fclose(f);
     deallocate_vector(&dl); deallocate_vector(&dr);
   }
-  deallocate_vector(&bl); deallocate_vector(&xl); deallocate_vector(&bnrm); deallocate_vector(&b); deallocate_vector(&x); deallocate_vector(&gauge);
+  deallocate_vector(&bl); deallocate_vector(&xl); deallocate_vector(&bnrm); deallocate_vector(&b); deallocate_vector(&x); deallocate_vector(&x0); deallocate_vector(&gauge);
   qmg::VecPool::release_all();
   return qmg_driver::leave(0);
 }

@@ -1,7 +1,7 @@
 // mrhs_solve.hpp -- the batched outer solve shared by n13_wilson_kcycle_mrhs and n22_wilson_kcycle_adaptive (nrhs=K):
 // nrhs gaussian right-hand sides (seeds seed, seed+1, ...), solved in lock-step batches (include/qmg/batch.hpp) sized to
 // the HBM that is free (qmg::batch_systems_that_fit), per-system report, and optionally the same systems re-solved alone
-// by the single-vector path.
+// one at a time, each as a batch of one (the single path: minv_vector_gcr_var_precond_restart).
 #ifndef MRHS_SOLVE_HPP
 #define MRHS_SOLVE_HPP
 #include <chrono>
@@ -110,7 +110,7 @@ inline bool mrhs_solve_and_report(StatefulMultigridMG* mg, Lattice2D* lat0, int 
         ok_ = ok_ && inv[k].success && true_res < 20 * tol;
         total_iters += inv[k].iter;
       }
-      if (verify_mode != 0) {   // the same systems, alone, through the single-vector path
+      if (verify_mode != 0) {   // the same systems, alone: each one a batch of one
         inversion_verbose_struct vq(VERB_NONE, "");
         complex<double>* x1 = mg->check_out(0);
         for (int k = 0; k < nb; k++) {

@@ -45,7 +45,7 @@ inline bool relax_null_vectors_batched(Stencil2D* st, complex<double>** null_vec
     const qmg::cvec mone(nb, -1.0);
     qmg::bblas<T>(QMG_BOP_CAX, &mone, 0, 0, 0, B, (size_t)fsize, mask);
     qmg::bzero(X, (size_t)fsize, mask);
-    bminv_vector_bicgstab_l_zero_guess<T>(X, B, (int)fsize, 500, 5e-5, 6, apply_stencil_typed_batch<T>, (void*)&op, mask);
+    bbicgstab_l_core<T>(X, B, (int)fsize, 500, 5e-5, 6, apply_stencil_typed_batch<T>, (void*)&op, mask, true);
     qmg::bcxpy(G, X, (size_t)fsize, mask);
     for (int k = 0; k < nb; k++) {
       complex<double>* v = null_vectors[j0 + k];

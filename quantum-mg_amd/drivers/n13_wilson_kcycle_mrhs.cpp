@@ -7,7 +7,7 @@
 // iteration together: every coarse operator and null vector is streamed once per step for the whole batch and the
 // coarse applies run on the f64 matrix cores.
 // Under a one-process-per-GPU launcher (RANK / WORLD_SIZE / LOCAL_RANK) each rank solves its own nrhs systems.
-// With `verify`, every system is then solved again ALONE by the single-vector path (krylov.hpp / multigrid.hpp) and the
+// With `verify`, every system is then solved again ALONE, as a batch of one (minv_vector_gcr_var_precond_restart), and the
 // two solutions, iteration counts and wall times are compared.
 #include "n13_setup.hpp"
 #include "mrhs_solve.hpp"

@@ -1,17 +1,18 @@
 // batch.hpp -- the K-cycle for a LOCK-STEP BATCH of independent right-hand sides (BASELINE configs[3]/[4]:
-// "independent right-hand sides", several per GPU).
+// "independent right-hand sides", several per GPU), and the stencil operators of a batch it runs on.
 //
 // The reference solves one system at a time (tests/n13_wilson_kcycle/wilson_kcycle.cpp:459-466), so k systems stream
 // every coarse operator and every null vector k times.  Here up to 16 systems advance through the SAME iteration of the
-// SAME solver together: one launch per step for the whole batch, the matrices / null vectors read once, and the coarse
-// applies run as (nc x nc).(nc x k) contractions on the f64 matrix cores (qmg_stencil.hip kernel C).
+// SAME solver together (the batch Krylov cores of krylov.hpp): one launch per step for the whole batch, the matrices /
+// null vectors read once, and the coarse applies run as (nc x nc).(nc x k) contractions on the f64 matrix cores
+// (qmg_stencil.hip kernel C).  StatefulMultigridMG::mg_preconditioner is this K-cycle on a batch of one.
 //
 // Semantics: each system sees exactly the iteration it would see alone.  Every scalar (alpha, residual norm, Gram-
 // Schmidt coefficient, restart decision, inner tolerance) is per system; a system that converges inside a solve is
 // FROZEN (its bit leaves the active mask: no kernel reads or writes it) while the rest continue.  The per-system
-// arithmetic is that of krylov.hpp / stateful_multigrid.h line by line -- element-wise kernels and reductions are
-// bit-identical to the single-vector ones, the MFMA apply and the blocked transfer differ in summation order only
-// (1e-13), so a batched solve reproduces the single solves to solver tolerance with the same iteration counts (+-1).
+// arithmetic is that of stateful_multigrid.h line by line -- element-wise kernels and reductions of a batch give every
+// system the bits it gets alone, the MFMA apply and the blocked transfer differ in summation order only (1e-13), so a
+// batched solve reproduces the systems solved alone to solver tolerance with the same iteration counts (+-1).
 //
 // Scope: every configuration of stateful_multigrid.h:734-1060 -- fine_stencil_app in {ORIGINAL, RIGHT_JACOBI, RIGHT_SCHUR} with MR or CGNE
 // smoothers and flexible-GCR intermediate solves; coarsest_stencil_app one of those (GCR) or one of the four normal-equation operators
@@ -38,127 +39,6 @@ namespace qmg {
 
 const int BATCH_MAX = 16;
 
-template <typename T> struct dtype_of;
-template <> struct dtype_of<double> { enum { value = QMG_C64 }; };
-template <> struct dtype_of<float> { enum { value = QMG_C32 }; };
-
-// nrhs vectors, `stride` complex elements apart
-template <typename T>
-struct BatchT {
-  complex<T>* p;
-  size_t stride;
-  int nrhs;
-  BatchT() : p(0), stride(0), nrhs(0) {}
-  BatchT(complex<T>* p_, size_t stride_, int nrhs_) : p(p_), stride(stride_), nrhs(nrhs_) {}
-  complex<T>* vec(int k) const { return p + (size_t)k * stride; }
-};
-typedef BatchT<double> Batch;
-
-inline unsigned full_mask(int nrhs) { return (nrhs >= 32) ? 0xFFFFFFFFu : ((1u << nrhs) - 1u); }
-inline bool is_active(unsigned mask, int k) { return (mask >> k) & 1u; }
-
-// batch scratch, recycled like VecPool (whose unit is one complex<double>: an fp32 batch takes half as many units)
-template <typename T>
-struct BatchPoolT {
-  VecPool pool;
-  size_t stride;
-  int nrhs;
-  BatchPoolT(size_t n, int nrhs_) : pool((n * (size_t)nrhs_ * sizeof(complex<T>) + sizeof(complex<double>) - 1) / sizeof(complex<double>)), stride(n), nrhs(nrhs_) {}
-  BatchT<T> get() { return BatchT<T>(reinterpret_cast<complex<T>*>(pool.get()), stride, nrhs); }
-};
-typedef BatchPoolT<double> BatchPool;
-
-typedef std::vector<complex<double>> cvec;
-
-template <typename T>
-inline void bblas(int op, const cvec* a, const cvec* b, const BatchT<T>* x, const BatchT<T>* y, BatchT<T> z, size_t n, unsigned mask) {
-  std::vector<double> fa, fb;
-  if (a) { fa.resize(2 * z.nrhs); for (int k = 0; k < z.nrhs; k++) { fa[2 * k] = (*a)[k].real(); fa[2 * k + 1] = (*a)[k].imag(); } }
-  if (b) { fb.resize(2 * z.nrhs); for (int k = 0; k < z.nrhs; k++) { fb[2 * k] = (*b)[k].real(); fb[2 * k + 1] = (*b)[k].imag(); } }
-  ok(qmg_batch_blas_t(dtype_of<T>::value, op, a ? fa.data() : 0, b ? fb.data() : 0, x ? x->p : 0, y ? y->p : 0, z.p, n, z.nrhs, z.stride, mask, current_stream()), "qmg_batch_blas");
-}
-template <typename T> inline void bzero(BatchT<T> z, size_t n, unsigned mask) { bblas<T>(QMG_BOP_ZERO, 0, 0, 0, 0, z, n, mask); }
-template <typename T> inline void bcopy(BatchT<T> z, BatchT<T> x, size_t n, unsigned mask) { bblas<T>(QMG_BOP_COPY, 0, 0, &x, 0, z, n, mask); }
-template <typename T> inline void bcaxpy(const cvec& a, BatchT<T> x, BatchT<T> y, size_t n, unsigned mask) { bblas<T>(QMG_BOP_CAXPY, &a, 0, &x, 0, y, n, mask); }   // y += a x
-template <typename T> inline void bcxpy(BatchT<T> x, BatchT<T> y, size_t n, unsigned mask) { bblas<T>(QMG_BOP_CXPY, 0, 0, &x, 0, y, n, mask); }                   // y += x
-template <typename T> inline void bcaxpbyz(const cvec& a, BatchT<T> x, const cvec& b, BatchT<T> y, BatchT<T> z, size_t n, unsigned mask) { bblas<T>(QMG_BOP_CAXPBYZ, &a, &b, &x, &y, z, n, mask); }
-template <typename T> inline void bxmyz(BatchT<T> x, BatchT<T> y, BatchT<T> z, size_t n, unsigned mask) {   // z = x - y
-  const cvec one(z.nrhs, 1.0), mone(z.nrhs, -1.0);
-  bcaxpbyz(one, x, mone, y, z, n, mask);
-}
-template <typename T> inline void bcxpyz(BatchT<T> x, BatchT<T> y, BatchT<T> z, size_t n, unsigned mask) {   // z = x + y
-  const cvec one(z.nrhs, 1.0);
-  bcaxpbyz(one, x, one, y, z, n, mask);
-}
-
-// per-system |x_k|^2; entries of frozen systems keep `fill`
-template <typename T>
-inline std::vector<double> bnorm2sq(BatchT<T> x, size_t n, unsigned mask, double fill = 0.0) {
-  std::vector<double> raw(2 * x.nrhs, 0.0), out(x.nrhs, fill);
-  ok(qmg_batch_reduce_t(dtype_of<T>::value, QMG_BRED_NORM2, x.p, 0, n, x.nrhs, x.stride, mask, raw.data(), current_stream()), "qmg_batch_reduce");
-  for (int k = 0; k < x.nrhs; k++) if (is_active(mask, k)) out[k] = raw[2 * k];
-  return out;
-}
-template <typename T>
-inline std::vector<double> bdiffnorm2sq(BatchT<T> x, BatchT<T> y, size_t n, unsigned mask) {
-  std::vector<double> raw(2 * x.nrhs, 0.0), out(x.nrhs, 0.0);
-  ok(qmg_batch_reduce_t(dtype_of<T>::value, QMG_BRED_DIFFNORM2, x.p, y.p, n, x.nrhs, x.stride, mask, raw.data(), current_stream()), "qmg_batch_reduce");
-  for (int k = 0; k < x.nrhs; k++) if (is_active(mask, k)) out[k] = raw[2 * k];
-  return out;
-}
-// d[k][j] = <xs[j]_k, y_k>
-template <typename T>
-inline std::vector<cvec> bmultidot(const std::vector<BatchT<T> >& xs, int nj, BatchT<T> y, size_t n, unsigned mask) {
-  std::vector<cvec> out(y.nrhs, cvec(nj, 0.0));
-  int done = 0;
-  while (done < nj) {   // the ABI takes up to 32 vector sets per call
-    const int jj = (nj - done > 32) ? 32 : nj - done;
-    std::vector<const void*> ptrs(jj);
-    for (int j = 0; j < jj; j++) ptrs[j] = xs[done + j].p;
-    std::vector<double> raw((size_t)2 * y.nrhs * jj, 0.0);
-    ok(qmg_batch_multidot_t(dtype_of<T>::value, ptrs.data(), jj, y.p, n, y.nrhs, y.stride, mask, raw.data(), current_stream()), "qmg_batch_multidot");
-    for (int k = 0; k < y.nrhs; k++)
-      if (is_active(mask, k))
-        for (int j = 0; j < jj; j++) out[k][done + j] = complex<double>(raw[((size_t)k * jj + j) * 2], raw[((size_t)k * jj + j) * 2 + 1]);
-    done += jj;
-  }
-  return out;
-}
-// y_k += sum_j c[k][j] xs[j]_k
-template <typename T>
-inline void bmulti_caxpy(const std::vector<cvec>& c, const std::vector<BatchT<T> >& xs, int nj, BatchT<T> y, size_t n, unsigned mask) {
-  if (nj <= 0) return;
-  std::vector<double> cf((size_t)2 * nj * y.nrhs, 0.0);
-  std::vector<const void*> ptrs(nj);
-  for (int j = 0; j < nj; j++) {
-    ptrs[j] = xs[j].p;
-    for (int k = 0; k < y.nrhs; k++) { cf[((size_t)j * y.nrhs + k) * 2] = c[k][j].real(); cf[((size_t)j * y.nrhs + k) * 2 + 1] = c[k][j].imag(); }
-  }
-  ok(qmg_batch_multi_caxpy_t(dtype_of<T>::value, cf.data(), ptrs.data(), nj, y.p, n, y.nrhs, y.stride, mask, current_stream()), "qmg_batch_multi_caxpy");
-}
-// one flexible-GCR iteration's vector updates in one pass: w_k += sum_j c[k][j] Ws[j]_k ; r_k += a[k] w_k ; z_next_k = r_k (z_next.p != 0)
-template <typename T>
-inline void bgcr_update(const std::vector<cvec>& c, const std::vector<BatchT<T> >& Ws, int nj, BatchT<T> w, const cvec& a, BatchT<T> r, BatchT<T> z_next, size_t n, unsigned mask) {
-  std::vector<double> cf((size_t)2 * (nj > 0 ? nj : 1) * w.nrhs, 0.0), af((size_t)2 * w.nrhs, 0.0);
-  std::vector<const void*> ptrs(nj > 0 ? nj : 1, (const void*)0);
-  for (int j = 0; j < nj; j++) {
-    ptrs[j] = Ws[j].p;
-    for (int k = 0; k < w.nrhs; k++) { cf[((size_t)j * w.nrhs + k) * 2] = c[k][j].real(); cf[((size_t)j * w.nrhs + k) * 2 + 1] = c[k][j].imag(); }
-  }
-  for (int k = 0; k < w.nrhs; k++) { af[2 * k] = a[k].real(); af[2 * k + 1] = a[k].imag(); }
-  ok(qmg_batch_gcr_update_t(dtype_of<T>::value, nj > 0 ? cf.data() : 0, nj > 0 ? ptrs.data() : 0, nj, w.p, af.data(), r.p, z_next.p, n, w.nrhs, w.stride, mask, current_stream()),
-     "qmg_batch_gcr_update");
-}
-// z_k = x_k across storage precisions (round / widen), active systems only
-template <typename TD, typename TS>
-inline void bconvert(BatchT<TD> z, BatchT<TS> x, size_t n, unsigned mask) {
-  for (int k = 0; k < z.nrhs; k++)
-    if (is_active(mask, k)) ok(qmg_convert(z.vec(k), dtype_of<TD>::value, x.vec(k), dtype_of<TS>::value, n, current_stream()), "qmg_convert");
-}
-
-}  // namespace qmg
-
-namespace qmg {
 // How many systems of a K-cycle solve fit in the HBM that is free right now.  Per system the outer flexible GCR keeps
 // 2 (restart or expected iterations) + ~8 vectors of level 0, every intermediate GCR 2 restart + ~12 of its level, and
 // the coarsest GCR 2 restart + 4; 15 % head-room.  (4096^2 Wilson, restart 64: ~75 GB per system -- 3 per 288 GB GPU.)
@@ -182,11 +62,6 @@ inline int batch_systems_that_fit(StatefulMultigridMG* mg, int outer_basis, int 
 }
 }  // namespace qmg
 
-// lhs_k = A rhs_k for the active systems
-template <typename T> using batch_matrix_op_t = void (*)(qmg::BatchT<T> lhs, qmg::BatchT<T> rhs, unsigned mask, void* extra_data);
-template <typename T> using batch_precond_op_t = void (*)(qmg::BatchT<T> lhs, qmg::BatchT<T> rhs, int size, unsigned mask, void* extra_data, inversion_verbose_struct* verb);
-typedef batch_matrix_op_t<double> batch_matrix_op;
-typedef batch_precond_op_t<double> batch_precond_op;
 
 inline void apply_stencil_2D_M_batch(qmg::Batch lhs, qmg::Batch rhs, unsigned mask, void* extra_data) {
   ((Stencil2D*)extra_data)->apply_M_overwrite_batch(lhs.p, rhs.p, lhs.nrhs, lhs.stride, mask);
@@ -400,73 +275,11 @@ inline void reconstruct_M_batch(Stencil2D* st, QMGStencilType type, qmg::BatchT<
 }
 
 // ---------------------------------------------------------------------------------------------
-// MR(omega) for a batch: minv_vector_minres of krylov.hpp per system, in lock step.  x0 = 0 is REQUIRED (every use in the
-// K-cycle; the caller has zeroed phi): r0 = b.
-// ---------------------------------------------------------------------------------------------
-template <typename T>
-inline std::vector<inversion_info> bminv_vector_minres_zero_guess(qmg::BatchT<T> phi, qmg::BatchT<T> phi0, int size, int max_iter, double eps, double omega,
-                                                                   batch_matrix_op_t<T> matrix_vector, void* extra_info, unsigned mask) {
-  const int nrhs = phi.nrhs;
-  std::vector<inversion_info> inv(nrhs);
-  qmg::BatchPoolT<T> pool(phi.stride, nrhs);
-  qmg::BatchT<T> r = pool.get(), p = pool.get();
-  const std::vector<double> bsq = qmg::bnorm2sq(phi0, size, mask);
-  qmg::bcopy(r, phi0, size, mask);
-  std::vector<double> rsq = bsq, rsq_ref = bsq, bnorm(nrhs);
-  std::vector<int> its(nrhs, 0), ops(nrhs, 0);
-  std::vector<bool> conv(nrhs, false);
-  unsigned act = 0;
-  for (int k = 0; k < nrhs; k++) {
-    bnorm[k] = std::sqrt(bsq[k]);
-    if (!qmg::is_active(mask, k)) continue;
-    conv[k] = (bnorm[k] == 0.0) || (std::sqrt(rsq[k]) < eps * bnorm[k]);
-    if (!conv[k] && max_iter > 0) act |= 1u << k;
-  }
-  std::vector<qmg::BatchT<T> > rp(2);
-  rp[0] = r; rp[1] = p;
-  while (act) {
-    matrix_vector(p, r, act, extra_info);
-    const std::vector<qmg::cvec> d2 = qmg::bmultidot(rp, 2, p, size, act);
-    qmg::cvec alpha(nrhs, 0.0), malpha(nrhs, 0.0);
-    unsigned upd = 0, renorm = 0;
-    for (int k = 0; k < nrhs; k++) {
-      if (!qmg::is_active(act, k)) continue;
-      ops[k]++;
-      const complex<double> pr = std::conj(d2[k][0]);
-      const double pp = d2[k][1].real();
-      if (pp == 0.0) { act &= ~(1u << k); continue; }   // breakdown: this system stops (krylov.hpp `break`)
-      alpha[k] = omega * pr / pp; malpha[k] = -alpha[k];
-      upd |= 1u << k;
-      rsq[k] = rsq[k] - (2.0 * omega - omega * omega) * std::norm(pr) / pp;
-      if (!(rsq[k] > 1e-8 * rsq_ref[k]) || std::sqrt(rsq[k]) < 4.0 * eps * bnorm[k]) renorm |= 1u << k;
-    }
-    qmg::bcaxpy(alpha, r, phi, size, upd);
-    // r is only needed by a further iteration or by a true-norm re-anchoring: the residual update of a system's LAST
-    // iteration is skipped (the K-cycle recomputes b - A x itself); x and the returned analytic |r|^2 are unaffected
-    unsigned need_r = renorm;
-    for (int k = 0; k < nrhs; k++) if (qmg::is_active(upd, k) && its[k] + 1 < max_iter) need_r |= 1u << k;
-    qmg::bcaxpy(malpha, p, r, size, upd & need_r);
-    if (renorm) {
-      const std::vector<double> t = qmg::bnorm2sq(r, size, renorm);
-      for (int k = 0; k < nrhs; k++) if (qmg::is_active(renorm, k)) { rsq[k] = t[k]; rsq_ref[k] = t[k]; }
-    }
-    for (int k = 0; k < nrhs; k++) {
-      if (!qmg::is_active(upd, k)) continue;
-      its[k]++;
-      if (std::sqrt(rsq[k]) < eps * bnorm[k]) { conv[k] = true; act &= ~(1u << k); }
-      else if (its[k] >= max_iter) act &= ~(1u << k);
-    }
-  }
-  for (int k = 0; k < nrhs; k++) { inv[k].success = conv[k]; inv[k].iter = its[k]; inv[k].resSq = rsq[k]; inv[k].ops_count = ops[k]; inv[k].name = "MinRes (batch)"; }
-  return inv;
-}
-
-// ---------------------------------------------------------------------------------------------
 // MR(omega) with a FIXED iteration count and every scalar on the device (qmg_batch_mr_dots_t / qmg_batch_mr_update_t): the form the
 // K-cycle's smoothers take.  Their tolerance (1e-15 in n13 / n19 / n22, 1e-20 in LevelSolveMG's defaults) is below what the
-// recursive residual of a few MR steps can reach in fp64, so minv_vector_minres always runs its `max_iter` iterations and NO host
+// recursive residual of a few MR steps can reach in fp64, so bmr_core always runs its `max_iter` iterations and NO host
 // decision depends on <p,r> / <p,p>: alpha is formed on the device and the per-iteration host round trip disappears.  The
-// arithmetic is that of bminv_vector_minres_zero_guess, operation for operation (same reduction order, same alpha = (omega <p,r>) / <p,p>).
+// arithmetic is that of bmr_core (krylov.hpp), operation for operation (same reduction order, same alpha = (omega <p,r>) / <p,p>).
 //   x0 = 0 is implied: x is WRITTEN by the first step (x = alpha b; no zero fill, no read) -- with iters == 0, x = 0.
 //   r_out (optional): the recursive residual b - A x after the last step (the K-cycle's pre-smoother wants it: it IS the residual the
 //   reference recomputes with one more apply, stateful_multigrid.h:863-866, up to rounding); without it the last residual update is skipped.
@@ -493,398 +306,6 @@ inline int bmr_fixed_zero_guess(qmg::BatchT<T> x, qmg::BatchT<T> b, qmg::BatchT<
     qmg::ok(qmg_batch_mr_update_t(dt, omega, x.p, rin.p, want_r ? r.p : 0, p.p, it == 0, (size_t)size, x.nrhs, x.stride, mask, qmg::current_stream()), "qmg_batch_mr_update");
   }
   return iters;
-}
-
-// ---------------------------------------------------------------------------------------------
-// BiCGStab(L) for a batch: minv_vector_bicgstab_l of krylov.hpp per system, in lock step (the null-vector relaxation of
-// tests/n13_wilson_kcycle/wilson_kcycle.cpp:359, several null vectors at a time).  x0 = 0 is REQUIRED (the caller has
-// zeroed phi): r0 = b.  `iter` counts BiCG steps per system; a system that converges, breaks down or reaches max_iter is
-// frozen at the end of its L-block.  The closing updates of a block go through one multi-vector pass each.
-// ---------------------------------------------------------------------------------------------
-template <typename T>
-inline std::vector<inversion_info> bminv_vector_bicgstab_l_zero_guess(qmg::BatchT<T> phi, qmg::BatchT<T> phi0, int size, int max_iter, double eps, int L,
-                                                                      batch_matrix_op_t<T> matrix_vector, void* extra_info, unsigned mask) {
-  const int nrhs = phi.nrhs;
-  std::vector<inversion_info> inv(nrhs);
-  qmg::BatchPoolT<T> pool(phi.stride, nrhs);
-  std::vector<qmg::BatchT<T> > r(L + 1), u(L + 1);
-  for (int i = 0; i <= L; i++) { r[i] = pool.get(); u[i] = pool.get(); }
-  qmg::BatchT<T> rt = pool.get();
-  const std::vector<double> bsq = qmg::bnorm2sq(phi0, size, mask);
-  qmg::bcopy(r[0], phi0, size, mask);
-  qmg::bcopy(rt, phi0, size, mask);
-  qmg::bzero(u[0], size, mask);
-  std::vector<double> rsq = bsq, bnorm(nrhs, 0.0);
-  std::vector<int> its(nrhs, 0), ops(nrhs, 0);
-  std::vector<bool> conv(nrhs, false);
-  qmg::cvec rho0(nrhs, 1.0), alpha(nrhs, 0.0), omega(nrhs, 1.0);
-  unsigned act = 0;
-  for (int k = 0; k < nrhs; k++) {
-    bnorm[k] = std::sqrt(bsq[k]);
-    if (!qmg::is_active(mask, k)) continue;
-    conv[k] = (bnorm[k] == 0.0) || (std::sqrt(rsq[k]) < eps * bnorm[k]);
-    if (!conv[k] && max_iter > 0) act |= 1u << k;
-  }
-  const qmg::cvec one(nrhs, 1.0);
-  std::vector<qmg::BatchT<T> > single(1);
-  auto bdot1 = [&](qmg::BatchT<T> a, qmg::BatchT<T> b, unsigned m) {   // <a_k, b_k> per system
-    single[0] = a;
-    const std::vector<qmg::cvec> d = qmg::bmultidot(single, 1, b, size, m);
-    qmg::cvec out(nrhs, 0.0);
-    for (int k = 0; k < nrhs; k++) out[k] = d[k][0];
-    return out;
-  };
-  std::vector<qmg::cvec> tau(nrhs, qmg::cvec((L + 1) * (L + 1), 0.0)), gamma(nrhs, qmg::cvec(L + 1, 0.0)), gammap(nrhs, qmg::cvec(L + 1, 0.0)),
-      gammapp(nrhs, qmg::cvec(L + 1, 0.0));
-  std::vector<std::vector<double> > sigma(nrhs, std::vector<double>(L + 1, 0.0));
-  while (act) {
-    for (int k = 0; k < nrhs; k++) if (qmg::is_active(act, k)) rho0[k] = -omega[k] * rho0[k];
-    for (int j = 0; j < L && act; j++) {   // BiCG part
-      const qmg::cvec rho1 = bdot1(rt, r[j], act);
-      qmg::cvec mbeta(nrhs, 0.0);
-      for (int k = 0; k < nrhs; k++) {
-        if (!qmg::is_active(act, k)) continue;
-        if (rho0[k] == 0.0) { act &= ~(1u << k); continue; }                 // breakdown: this system stops
-        mbeta[k] = -(alpha[k] * rho1[k] / rho0[k]);
-        rho0[k] = rho1[k];
-      }
-      if (!act) break;
-      for (int i = 0; i <= j; i++) qmg::bcaxpbyz(one, r[i], mbeta, u[i], u[i], size, act);   // u_i = r_i - beta u_i
-      matrix_vector(u[j + 1], u[j], act, extra_info);
-      const qmg::cvec gam = bdot1(rt, u[j + 1], act);
-      qmg::cvec malpha(nrhs, 0.0);
-      for (int k = 0; k < nrhs; k++) {
-        if (!qmg::is_active(act, k)) continue;
-        ops[k]++;
-        if (gam[k] == 0.0) { act &= ~(1u << k); continue; }
-        alpha[k] = rho0[k] / gam[k];
-        malpha[k] = -alpha[k];
-      }
-      if (!act) break;
-      for (int i = 0; i <= j; i++) qmg::bcaxpy(malpha, u[i + 1], r[i], size, act);
-      matrix_vector(r[j + 1], r[j], act, extra_info);
-      qmg::bcaxpy(alpha, u[0], phi, size, act);
-      for (int k = 0; k < nrhs; k++) if (qmg::is_active(act, k)) { ops[k]++; its[k]++; }
-    }
-    if (!act) break;
-    for (int j = 1; j <= L && act; j++) {   // MR part: modified Gram-Schmidt on r_1..r_L
-      for (int i = 1; i < j; i++) {
-        const qmg::cvec d = bdot1(r[i], r[j], act);
-        qmg::cvec mt(nrhs, 0.0);
-        for (int k = 0; k < nrhs; k++) if (qmg::is_active(act, k)) { tau[k][i * (L + 1) + j] = d[k] / sigma[k][i]; mt[k] = -tau[k][i * (L + 1) + j]; }
-        qmg::bcaxpy(mt, r[i], r[j], size, act);
-      }
-      std::vector<qmg::BatchT<T> > two(2);
-      two[0] = r[j]; two[1] = r[0];
-      // <r_j, r_j> and <r_j, r_0> in one pass over r_j: d[k][0] = <r_j, r_j>, d[k][1] = <r_0, r_j> = conj <r_j, r_0>
-      const std::vector<qmg::cvec> d = qmg::bmultidot(two, 2, r[j], size, act);
-      for (int k = 0; k < nrhs; k++) {
-        if (!qmg::is_active(act, k)) continue;
-        sigma[k][j] = d[k][0].real();
-        if (sigma[k][j] == 0.0) { act &= ~(1u << k); continue; }
-        gammap[k][j] = std::conj(d[k][1]) / sigma[k][j];
-      }
-    }
-    if (!act) break;
-    std::vector<qmg::cvec> cx(nrhs, qmg::cvec(L, 0.0)), cr(nrhs, qmg::cvec(L, 0.0)), cu(nrhs, qmg::cvec(L, 0.0));
-    for (int k = 0; k < nrhs; k++) {
-      if (!qmg::is_active(act, k)) continue;
-      qmg::cvec &g = gamma[k], &gp = gammap[k], &gpp = gammapp[k], &t = tau[k];
-      g[L] = gp[L];
-      omega[k] = g[L];
-      for (int j = L - 1; j >= 1; j--) {
-        g[j] = gp[j];
-        for (int i = j + 1; i <= L; i++) g[j] -= t[j * (L + 1) + i] * g[i];
-      }
-      for (int j = 1; j < L; j++) {
-        gpp[j] = g[j + 1];
-        for (int i = j + 1; i < L; i++) gpp[j] += t[j * (L + 1) + i] * g[i + 1];
-      }
-      // x += gamma_1 r_0 + sum_{j<L} gamma''_j r_j ; r_0 -= sum_{j<=L} gamma'_j r_j ; u_0 -= sum_{j<=L} gamma_j u_j
-      cx[k][0] = g[1];
-      for (int j = 1; j < L; j++) cx[k][j] = gpp[j];
-      for (int j = 1; j <= L; j++) { cr[k][j - 1] = -gp[j]; cu[k][j - 1] = -g[j]; }
-    }
-    std::vector<qmg::BatchT<T> > r0L(r.begin(), r.begin() + L), r1L(r.begin() + 1, r.end()), u1L(u.begin() + 1, u.end());
-    qmg::bmulti_caxpy(cx, r0L, L, phi, size, act);     // reads r_0 before it changes
-    qmg::bmulti_caxpy(cr, r1L, L, r[0], size, act);
-    qmg::bmulti_caxpy(cu, u1L, L, u[0], size, act);
-    const std::vector<double> t2 = qmg::bnorm2sq(r[0], size, act);
-    for (int k = 0; k < nrhs; k++) {
-      if (!qmg::is_active(act, k)) continue;
-      rsq[k] = t2[k];
-      if (std::sqrt(rsq[k]) < eps * bnorm[k]) { conv[k] = true; act &= ~(1u << k); }
-      else if (its[k] >= max_iter) act &= ~(1u << k);
-    }
-  }
-  for (int k = 0; k < nrhs; k++) { inv[k].success = conv[k]; inv[k].iter = its[k]; inv[k].resSq = rsq[k]; inv[k].ops_count = ops[k]; inv[k].name = "BiCGStab-L (batch)"; }
-  return inv;
-}
-
-// ---------------------------------------------------------------------------------------------
-// Flexible GCR with restarts for a batch: qmg_gcr_core of krylov.hpp per system, in lock step.  All systems start
-// together, so the basis index kb (and with it the restart points) is common; everything else is per system.
-// zero_guess: the caller has zeroed phi, r0 = b.
-// ---------------------------------------------------------------------------------------------
-template <typename T>
-inline std::vector<inversion_info> bgcr_core(qmg::BatchT<T> phi, qmg::BatchT<T> phi0, int size, int max_iter, double eps, int restart_freq,
-                                             batch_matrix_op_t<T> matrix_vector, void* extra_info, batch_precond_op_t<T> precond, void* precond_info,
-                                             unsigned mask, bool zero_guess, inversion_verbose_struct* verb, const char* name,
-                                             const std::vector<double>* eps_per_system = 0) {
-  const int nrhs = phi.nrhs;
-  std::vector<inversion_info> inv(nrhs);
-  std::vector<double> epsv(nrhs, eps);   // relative tolerance per system (the K-cycle's inner tolerance depends on the system)
-  if (eps_per_system) epsv = *eps_per_system;
-  const int basis_max = (restart_freq > 0) ? restart_freq : max_iter;
-  qmg::BatchPoolT<T> pool(phi.stride, nrhs);
-  qmg::BatchT<T> r = pool.get(), tmp = pool.get();
-  std::vector<qmg::BatchT<T> > Z, W;        // raw search directions and orthogonalised images (krylov.hpp: z is not orthogonalised)
-  std::vector<std::vector<double> > Wnorm2;   // [basis index][system]
-  std::vector<std::vector<qmg::cvec> > C(nrhs);   // C[system][k][i]: Gram-Schmidt coefficients of this cycle
-  std::vector<qmg::cvec> alphas(nrhs);           // alphas[system][k]
-  std::vector<int> used(nrhs, 0);                // directions system k has taken in this cycle
-  auto flush_x = [&]() {                         // x_k += sum_j y_kj z_j for every system with pending directions
-    int K = 0;
-    unsigned m = 0;
-    for (int k = 0; k < nrhs; k++) if (used[k] > 0) { m |= 1u << k; if (used[k] > K) K = used[k]; }
-    if (!m) return;
-    std::vector<qmg::cvec> y(nrhs, qmg::cvec(K, 0.0));
-    for (int k = 0; k < nrhs; k++) {
-      if (used[k] <= 0) continue;
-      const qmg::cvec yk = qmg::gcr_direction_weights(alphas[k], C[k], used[k]);
-      for (int j = 0; j < used[k]; j++) y[k][j] = yk[j];
-      used[k] = 0;
-    }
-    qmg::bmulti_caxpy(y, Z, K, phi, size, m);
-  };
-  const std::vector<double> bsq = qmg::bnorm2sq(phi0, size, mask);
-  std::vector<double> rsq(nrhs, 0.0), rsq_ref(nrhs, 0.0), bnorm(nrhs, 0.0);
-  std::vector<int> its(nrhs, 0), ops(nrhs, 0);
-  std::vector<bool> conv(nrhs, false);
-  if (zero_guess) { qmg::bcopy(r, phi0, size, mask); rsq = bsq; }
-  else {
-    matrix_vector(tmp, phi, mask, extra_info);
-    for (int k = 0; k < nrhs; k++) if (qmg::is_active(mask, k)) ops[k]++;
-    qmg::bxmyz(phi0, tmp, r, size, mask);
-    rsq = qmg::bnorm2sq(r, size, mask);
-  }
-  unsigned act = 0;
-  for (int k = 0; k < nrhs; k++) {
-    bnorm[k] = std::sqrt(bsq[k]);
-    rsq_ref[k] = rsq[k];
-    if (!qmg::is_active(mask, k)) continue;
-    conv[k] = (bnorm[k] == 0.0) || (std::sqrt(rsq[k]) < epsv[k] * bnorm[k]);
-    if (!conv[k] && max_iter > 0) act |= 1u << k;
-  }
-  int kb = 0;
-  bool z_ready = false;
-  inversion_verbose_struct pverb(verb ? verb->precond_verbosity : VERB_NONE, verb ? verb->precond_verb_prefix : std::string(""));
-  if (verb) { pverb.precond_verbosity = verb->precond_verbosity; pverb.precond_verb_prefix = verb->precond_verb_prefix; }
-  std::vector<qmg::BatchT<T> > rw(2);
-  while (act) {
-    if (kb == (int)Z.size()) { Z.push_back(pool.get()); W.push_back(pool.get()); Wnorm2.push_back(std::vector<double>(nrhs, 0.0)); }
-    for (int k = 0; k < nrhs; k++) { if ((int)C[k].size() <= kb) { C[k].push_back(qmg::cvec()); alphas[k].push_back(0.0); } }
-    qmg::BatchT<T> z = Z[kb], w = W[kb];
-    if (z.p == 0 || w.p == 0 || r.p == 0 || tmp.p == 0) {   // out of HBM: stop, report every active system as not converged
-      std::cout << "[QMG-ERROR]: " << name << ": could not allocate basis vector " << kb << " for a batch of " << nrhs << " systems; size the batch with qmg::batch_systems_that_fit.\n";
-      break;
-    }
-    if (precond) { qmg::bzero(z, size, act); precond(z, r, size, act, precond_info, &pverb); }
-    else if (!z_ready) qmg::bcopy(z, r, size, act);   // (z_ready: the previous iteration's update pass wrote z = r already)
-    z_ready = false;
-    matrix_vector(w, z, act, extra_info);
-    // ONE reduction pass and one host round trip per iteration: the Gram-Schmidt
-    // coefficients c_i = <W_i, w>, <r, w> and <w, w> come from the same pass over the RAW w; for the orthogonalised w' = w - sum_i (c_i / N_i) W_i
-    //   <w', w'> = <w, w> - sum_i |c_i|^2 / N_i          (the W_i are orthogonal)
-    //   <r,  w'> = <r, w>                                (r is orthogonal to every W_i of the cycle: each step removed that component)
-    // A system whose w' keeps less than 1e-6 of |w|^2 (w almost inside the span: the subtraction has lost its digits) takes the explicit dots.
-    std::vector<qmg::cvec> d2(nrhs, qmg::cvec(2, 0.0));
-    std::vector<qmg::BatchT<T> > basis(W.begin(), W.begin() + kb);
-    basis.push_back(r); basis.push_back(w);
-    std::vector<qmg::cvec> c = qmg::bmultidot(basis, kb + 2, w, size, act);
-    unsigned explicit_dots = 0;
-    for (int k = 0; k < nrhs; k++) {
-      if (!qmg::is_active(act, k)) continue;
-      double ww = c[k][kb + 1].real();
-      const double ww_raw = ww;
-      for (int i = 0; i < kb; i++) { ww -= std::norm(c[k][i]) / Wnorm2[i][k]; c[k][i] = -c[k][i] / Wnorm2[i][k]; }
-      d2[k][0] = c[k][kb]; d2[k][1] = ww;
-      if (!(ww > 1e-6 * ww_raw)) explicit_dots |= 1u << k;
-      c[k].resize(kb);
-      C[k][kb] = c[k];
-    }
-    // With these dots alpha is known BEFORE w is orthogonalised, so the Gram-Schmidt update of w, the residual update and (without a
-    // preconditioner) the copy z_next = r go through ONE pass (qmg_batch_gcr_update_t: the same bits as the three separate passes).
-    const bool deferred = explicit_dots == 0;
-    if (!deferred && kb > 0) qmg::bmulti_caxpy(c, W, kb, w, size, act);
-    if (explicit_dots) {
-      rw[0] = r; rw[1] = w;
-      const std::vector<qmg::cvec> e2 = qmg::bmultidot(rw, 2, w, size, explicit_dots);
-      for (int k = 0; k < nrhs; k++) if (qmg::is_active(explicit_dots, k)) d2[k] = e2[k];
-    }
-    qmg::cvec alpha(nrhs, 0.0), malpha(nrhs, 0.0);
-    unsigned upd = 0, renorm = 0;
-    // the true norm re-anchors the recurrence when it has lost digits and CONFIRMS a convergence the recurrence announces
-    for (int k = 0; k < nrhs; k++) {
-      if (!qmg::is_active(act, k)) continue;
-      ops[k]++;
-      const double ww = d2[k][1].real();
-      if (ww == 0.0) { act &= ~(1u << k); continue; }
-      Wnorm2[kb][k] = ww;
-      const complex<double> wr = std::conj(d2[k][0]);
-      alpha[k] = wr / ww; malpha[k] = -alpha[k];
-      alphas[k][kb] = alpha[k];
-      used[k] = kb + 1;
-      upd |= 1u << k;
-      rsq[k] = rsq[k] - std::norm(wr) / ww;
-      if (!(rsq[k] > 1e-8 * rsq_ref[k]) || std::sqrt(rsq[k]) < epsv[k] * bnorm[k]) renorm |= 1u << k;
-    }
-    if (deferred) {
-      qmg::BatchT<T> z_next;
-      if (!precond && kb + 1 < basis_max) {
-        if (kb + 1 == (int)Z.size()) { Z.push_back(pool.get()); W.push_back(pool.get()); Wnorm2.push_back(std::vector<double>(nrhs, 0.0)); }
-        z_next = Z[kb + 1];
-      }
-      qmg::bgcr_update(c, W, kb, w, malpha, r, z_next, size, upd);
-      z_ready = z_next.p != 0;
-    } else qmg::bcaxpy(malpha, w, r, size, upd);
-    if (renorm) {
-      const std::vector<double> t = qmg::bnorm2sq(r, size, renorm);
-      for (int k = 0; k < nrhs; k++) if (qmg::is_active(renorm, k)) { rsq[k] = t[k]; rsq_ref[k] = t[k]; }
-    }
-    kb++;
-    for (int k = 0; k < nrhs; k++) {
-      if (!qmg::is_active(upd, k)) continue;
-      its[k]++;
-      if (verb && verb->verbosity == VERB_DETAIL) { std::cout << verb->verb_prefix << name; if (nrhs > 1) std::cout << " rhs " << k; std::cout << " Iter " << its[k] << " RelTol " << std::sqrt(rsq[k]) / bnorm[k] << "\n"; }
-      if (std::sqrt(rsq[k]) < epsv[k] * bnorm[k]) { conv[k] = true; act &= ~(1u << k); }
-    }
-    if (kb == basis_max) flush_x();   // the basis is about to be reused: bring every pending x up to date (frozen systems too)
-    if (act && kb == basis_max) {   // restart: true residual, drop the basis (before the iteration cap, as in krylov.hpp)
-      matrix_vector(tmp, phi, act, extra_info);
-      qmg::bxmyz(phi0, tmp, r, size, act);
-      const std::vector<double> t = qmg::bnorm2sq(r, size, act);
-      kb = 0;
-      z_ready = false;
-      for (int k = 0; k < nrhs; k++) {
-        if (!qmg::is_active(act, k)) continue;
-        ops[k]++;
-        rsq[k] = t[k]; rsq_ref[k] = t[k];
-        if (std::sqrt(rsq[k]) < epsv[k] * bnorm[k]) { conv[k] = true; act &= ~(1u << k); }
-      }
-    }
-    for (int k = 0; k < nrhs; k++) if (qmg::is_active(act, k) && its[k] >= max_iter) act &= ~(1u << k);
-  }
-  flush_x();
-  for (int k = 0; k < nrhs; k++) {
-    inv[k].success = conv[k]; inv[k].iter = its[k]; inv[k].resSq = rsq[k]; inv[k].ops_count = ops[k]; inv[k].name = name;
-    if (verb && verb->verbosity != VERB_NONE && qmg::is_active(mask, k)) {   // (one system: krylov.hpp's line, word for word)
-      std::cout << verb->verb_prefix << name;
-      if (nrhs > 1) std::cout << " rhs " << k;
-      std::cout << (conv[k] ? " Success " : " Fail ") << "Iter " << its[k] << " RelTol " << (bnorm[k] > 0 ? std::sqrt(rsq[k]) / bnorm[k] : 0.0) << "\n";
-    }
-  }
-  return inv;
-}
-
-// ---------------------------------------------------------------------------------------------
-// CG with restarts for a batch: minv_vector_cg / minv_vector_cg_restart of krylov.hpp per system, in lock step (the coarsest solve on a
-// normal-equation operator, stateful_multigrid.h:930-960).  Every active system starts each restart cycle together; a system that converges,
-// breaks down (<p, A p> == 0) or reaches max_iter is frozen.  restart_freq <= 0: one cycle of max_iter iterations.
-// zero_guess: the caller has zeroed phi, the first cycle's r0 = b.
-// ---------------------------------------------------------------------------------------------
-template <typename T>
-inline std::vector<inversion_info> bcg_core(qmg::BatchT<T> phi, qmg::BatchT<T> phi0, int size, int max_iter, double eps, int restart_freq,
-                                            batch_matrix_op_t<T> matrix_vector, void* extra_info, unsigned mask, bool zero_guess,
-                                            inversion_verbose_struct* verb, const char* name, const std::vector<double>* eps_per_system = 0) {
-  const int nrhs = phi.nrhs;
-  std::vector<inversion_info> inv(nrhs);
-  std::vector<double> epsv(nrhs, eps);
-  if (eps_per_system) epsv = *eps_per_system;
-  qmg::BatchPoolT<T> pool(phi.stride, nrhs);
-  qmg::BatchT<T> r = pool.get(), p = pool.get(), Ap = pool.get();
-  const std::vector<double> bsq = qmg::bnorm2sq(phi0, size, mask);
-  std::vector<double> rsq(nrhs, 0.0), bnorm(nrhs, 0.0);
-  std::vector<int> its(nrhs, 0), ops(nrhs, 0);
-  std::vector<bool> conv(nrhs, false);
-  for (int k = 0; k < nrhs; k++) bnorm[k] = std::sqrt(bsq[k]);
-  const qmg::cvec one(nrhs, 1.0);
-  std::vector<qmg::BatchT<T> > pv(1);
-  unsigned live = (r.p && p.p && Ap.p) ? mask : 0u;   // systems that may still start a cycle
-  if (!live && mask) std::cout << "[QMG-ERROR]: " << name << ": out of device memory for the CG work vectors\n";
-  bool first = true;
-  while (live) {
-    // ---- one cycle (minv_vector_cg with at most `chunk` iterations per system)
-    std::vector<int> chunk(nrhs, 0), done_in_cycle(nrhs, 0);
-    unsigned act = 0;
-    for (int k = 0; k < nrhs; k++) {
-      if (!qmg::is_active(live, k)) continue;
-      const int left = max_iter - its[k];
-      chunk[k] = (restart_freq > 0 && left > restart_freq) ? restart_freq : left;
-    }
-    if (first && zero_guess) { qmg::bcopy(r, phi0, size, live); rsq = bsq; }
-    else {
-      matrix_vector(Ap, phi, live, extra_info);
-      for (int k = 0; k < nrhs; k++) if (qmg::is_active(live, k)) ops[k]++;
-      qmg::bxmyz(phi0, Ap, r, size, live);
-      const std::vector<double> t = qmg::bnorm2sq(r, size, live);
-      for (int k = 0; k < nrhs; k++) if (qmg::is_active(live, k)) rsq[k] = t[k];
-    }
-    first = false;
-    qmg::bcopy(p, r, size, live);
-    for (int k = 0; k < nrhs; k++) {
-      if (!qmg::is_active(live, k)) continue;
-      conv[k] = (bnorm[k] == 0.0) || (std::sqrt(rsq[k]) < epsv[k] * bnorm[k]);
-      if (!conv[k] && chunk[k] > 0) act |= 1u << k;
-    }
-    while (act) {
-      matrix_vector(Ap, p, act, extra_info);
-      pv[0] = p;
-      const std::vector<qmg::cvec> d = qmg::bmultidot(pv, 1, Ap, size, act);   // <p, A p>
-      qmg::cvec alpha(nrhs, 0.0), malpha(nrhs, 0.0);
-      unsigned upd = 0;
-      for (int k = 0; k < nrhs; k++) {
-        if (!qmg::is_active(act, k)) continue;
-        ops[k]++;
-        const double pAp = d[k][0].real();
-        if (pAp == 0.0) { act &= ~(1u << k); continue; }   // breakdown: this system's cycle ends (krylov.hpp `break`)
-        alpha[k] = rsq[k] / pAp; malpha[k] = -alpha[k];
-        upd |= 1u << k;
-      }
-      qmg::bcaxpy(alpha, p, phi, size, upd);
-      qmg::bcaxpy(malpha, Ap, r, size, upd);
-      const std::vector<double> rn = qmg::bnorm2sq(r, size, upd);
-      qmg::cvec beta(nrhs, 0.0);
-      unsigned go_on = 0;
-      for (int k = 0; k < nrhs; k++) {
-        if (!qmg::is_active(upd, k)) continue;
-        its[k]++; done_in_cycle[k]++;
-        if (verb && verb->verbosity == VERB_DETAIL) { std::cout << verb->verb_prefix << "CG"; if (nrhs > 1) std::cout << " rhs " << k; std::cout << " Iter " << its[k] << " RelTol " << std::sqrt(rn[k]) / bnorm[k] << "\n"; }
-        if (std::sqrt(rn[k]) < epsv[k] * bnorm[k]) { rsq[k] = rn[k]; conv[k] = true; act &= ~(1u << k); continue; }
-        beta[k] = rn[k] / rsq[k];
-        rsq[k] = rn[k];
-        if (done_in_cycle[k] >= chunk[k]) act &= ~(1u << k);
-        else go_on |= 1u << k;
-      }
-      qmg::bcaxpbyz(one, r, beta, p, p, size, go_on);   // p = r + beta p
-    }
-    // ---- which systems start another cycle (minv_vector_cg_restart: stop on success, on a cycle without an iteration, at max_iter)
-    unsigned next = 0;
-    for (int k = 0; k < nrhs; k++) {
-      if (!qmg::is_active(live, k)) continue;
-      if (restart_freq > 0 && !conv[k] && done_in_cycle[k] > 0 && its[k] < max_iter) next |= 1u << k;
-    }
-    live = next;
-  }
-  for (int k = 0; k < nrhs; k++) {
-    inv[k].success = conv[k]; inv[k].iter = its[k]; inv[k].resSq = rsq[k]; inv[k].ops_count = ops[k]; inv[k].name = name;
-    if (verb && verb->verbosity != VERB_NONE && qmg::is_active(mask, k)) {   // (one system: krylov.hpp's line, word for word)
-      std::cout << verb->verb_prefix << name;
-      if (nrhs > 1) std::cout << " rhs " << k;
-      std::cout << (conv[k] ? " Success " : " Fail ") << "Iter " << its[k] << " RelTol " << (bnorm[k] > 0 ? std::sqrt(rsq[k]) / bnorm[k] : 0.0) << "\n";
-    }
-  }
-  return inv;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -986,7 +407,7 @@ inline void mg_preconditioner_batch(qmg::BatchT<T> lhs, qmg::BatchT<T> rhs, int 
       have_r = r_out != 0;
     } else {
       qmg::bzero(y, fine_size, mask);
-      std::vector<inversion_info> inv = bminv_vector_minres_zero_guess<T>(y, b, (int)fine_size_solve, iters, tol, 0.85, apply_stencil_typed_batch<T>, (void*)op, mask);
+      std::vector<inversion_info> inv = bmr_core<T>(y, b, (int)fine_size_solve, iters, tol, 0.85, apply_stencil_typed_batch<T>, (void*)op, mask, true);
       for (int k = 0; k < nrhs; k++) if (qmg::is_active(mask, k)) mg->add_tracker_count(type, (ne ? 2 : 1) * inv[k].ops_count, level);
     }
     if (ne) {

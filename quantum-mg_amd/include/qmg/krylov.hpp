@@ -1,4 +1,4 @@
-// krylov.hpp -- the Krylov drivers the K-cycle calls, on device-resident vectors.
+// krylov.hpp -- the Krylov solvers, on device-resident vectors: MR(omega), CG (restarted or not), flexible GCR and BiCGStab(L).
 //
 // The reference takes these from quantum-linalg (`inverters/generic_*.h`, absent; only the call sites
 // are known: stateful_multigrid.h:851-990,1037-1046, tests/n13_wilson_kcycle/wilson_kcycle.cpp:459-466,
@@ -9,8 +9,15 @@
 //   * resSq is the (recursive) residual norm squared at exit; iter counts iterations; ops_count counts
 //     operator applications (used by DslashTrackerMG, stateful_multigrid.h:854-865)
 // All vectors are device pointers; every reduction is a two-stage device reduction whose result comes back
-// to the host because the control flow depends on it.  GCR-type orthogonalisation uses one fused
-// multi-dot pass (qmg_multidot) instead of k separate dot kernels.
+// to the host because the control flow depends on it.
+//
+// Each method has ONE implementation, for a LOCK-STEP BATCH of up to 16 independent systems (bmr_core, bcg_core, bgcr_core,
+// bbicgstab_l_core): one launch per step for the whole batch, every scalar and every decision per system, and a system that
+// converges is FROZEN (its bit leaves the active mask: no kernel reads or writes it) while the rest continue.  The reference-
+// named single-vector entry points (minv_vector_minres, minv_vector_cg, ..., minv_vector_bicgstab_l) run these cores on a
+// batch of one; only Richardson is single-vector code.  Every type and function of the batch layer is a template on the
+// storage scalar T of the vectors (double | float); all scalars, inner products and convergence decisions stay fp64.
+// The operators, the K-cycle and the mixed-precision preconditioner of a batch are in batch.hpp.
 #ifndef QMG_KRYLOV_HPP
 #define QMG_KRYLOV_HPP
 
@@ -100,38 +107,18 @@ struct VecPool {
   }
 };
 
-inline void report(inversion_verbose_struct* verb, const char* name, int iter, double rel, bool summary_only = false) {
-  if (!verb) return;
-  if (verb->verbosity == VERB_DETAIL && !summary_only)
-    std::cout << verb->verb_prefix << name << " Iter " << iter << " RelTol " << rel << "\n";
+// a solver's per-iteration (VERB_DETAIL) and closing lines for system k; in a batch of several the system's index follows the name
+inline void report(inversion_verbose_struct* verb, const char* name, int nrhs, int k, int iter, double rel) {
+  if (!verb || verb->verbosity != VERB_DETAIL) return;
+  std::cout << verb->verb_prefix << name;
+  if (nrhs > 1) std::cout << " rhs " << k;
+  std::cout << " Iter " << iter << " RelTol " << rel << "\n";
 }
-inline void summary(inversion_verbose_struct* verb, const char* name, bool ok_, int iter, double rel) {
+inline void summary(inversion_verbose_struct* verb, const char* name, int nrhs, int k, bool ok_, int iter, double rel) {
   if (!verb || verb->verbosity == VERB_NONE) return;
-  std::cout << verb->verb_prefix << name << (ok_ ? " Success " : " Fail ") << "Iter " << iter << " RelTol " << rel << "\n";
-}
-
-inline std::vector<complex<double>> multidot(const std::vector<complex<double>*>& xs, int k, const complex<double>* y, size_t n) {
-  std::vector<complex<double>> out(k);
-  int done = 0;
-  while (done < k) {   // the ABI takes up to 64 vectors per call
-    const int kk = (k - done > 64) ? 64 : k - done;
-    std::vector<const void*> ptrs(kk);
-    for (int i = 0; i < kk; i++) ptrs[i] = xs[done + i];
-    std::vector<double> r(2 * kk);
-    ok(qmg_multidot(ptrs.data(), kk, y, n, nullptr, r.data(), current_stream()), "qmg_multidot");
-    for (int i = 0; i < kk; i++) out[done + i] = complex<double>(r[2 * i], r[2 * i + 1]);
-    done += kk;
-  }
-  return out;
-}
-
-// y += sum_i a_i x_i, i < k, in one pass (qmg_multi_caxpy)
-inline void multi_caxpy(const std::vector<complex<double>>& a, const std::vector<complex<double>*>& xs, int k, complex<double>* y, size_t n) {
-  if (k <= 0) return;
-  std::vector<double> cf(2 * k);
-  std::vector<const void*> ptrs(k);
-  for (int i = 0; i < k; i++) { cf[2 * i] = a[i].real(); cf[2 * i + 1] = a[i].imag(); ptrs[i] = xs[i]; }
-  ok(qmg_multi_caxpy(cf.data(), ptrs.data(), k, y, n, current_stream()), "qmg_multi_caxpy");
+  std::cout << verb->verb_prefix << name;
+  if (nrhs > 1) std::cout << " rhs " << k;
+  std::cout << (ok_ ? " Success " : " Fail ") << "Iter " << iter << " RelTol " << rel << "\n";
 }
 
 // GCR with raw search directions: y_j such that sum_k alpha_k z'_k = sum_j y_j z_j, z'_k = z_k + sum_{i<k} c[k][i] z'_i
@@ -142,296 +129,673 @@ inline std::vector<complex<double>> gcr_direction_weights(const std::vector<comp
   return beta;
 }
 
+template <typename T> struct dtype_of;
+template <> struct dtype_of<double> { enum { value = QMG_C64 }; };
+template <> struct dtype_of<float> { enum { value = QMG_C32 }; };
+
+// nrhs vectors, `stride` complex elements apart
+template <typename T>
+struct BatchT {
+  complex<T>* p;
+  size_t stride;
+  int nrhs;
+  BatchT() : p(0), stride(0), nrhs(0) {}
+  BatchT(complex<T>* p_, size_t stride_, int nrhs_) : p(p_), stride(stride_), nrhs(nrhs_) {}
+  complex<T>* vec(int k) const { return p + (size_t)k * stride; }
+};
+typedef BatchT<double> Batch;
+
+inline unsigned full_mask(int nrhs) { return (nrhs >= 32) ? 0xFFFFFFFFu : ((1u << nrhs) - 1u); }
+inline bool is_active(unsigned mask, int k) { return (mask >> k) & 1u; }
+
+// batch scratch, recycled like VecPool (whose unit is one complex<double>: an fp32 batch takes half as many units)
+template <typename T>
+struct BatchPoolT {
+  VecPool pool;
+  size_t stride;
+  int nrhs;
+  BatchPoolT(size_t n, int nrhs_) : pool((n * (size_t)nrhs_ * sizeof(complex<T>) + sizeof(complex<double>) - 1) / sizeof(complex<double>)), stride(n), nrhs(nrhs_) {}
+  BatchT<T> get() { return BatchT<T>(reinterpret_cast<complex<T>*>(pool.get()), stride, nrhs); }
+};
+typedef BatchPoolT<double> BatchPool;
+
+typedef std::vector<complex<double>> cvec;
+
+template <typename T>
+inline void bblas(int op, const cvec* a, const cvec* b, const BatchT<T>* x, const BatchT<T>* y, BatchT<T> z, size_t n, unsigned mask) {
+  std::vector<double> fa, fb;
+  if (a) { fa.resize(2 * z.nrhs); for (int k = 0; k < z.nrhs; k++) { fa[2 * k] = (*a)[k].real(); fa[2 * k + 1] = (*a)[k].imag(); } }
+  if (b) { fb.resize(2 * z.nrhs); for (int k = 0; k < z.nrhs; k++) { fb[2 * k] = (*b)[k].real(); fb[2 * k + 1] = (*b)[k].imag(); } }
+  ok(qmg_batch_blas_t(dtype_of<T>::value, op, a ? fa.data() : 0, b ? fb.data() : 0, x ? x->p : 0, y ? y->p : 0, z.p, n, z.nrhs, z.stride, mask, current_stream()), "qmg_batch_blas");
+}
+template <typename T> inline void bzero(BatchT<T> z, size_t n, unsigned mask) { bblas<T>(QMG_BOP_ZERO, 0, 0, 0, 0, z, n, mask); }
+template <typename T> inline void bcopy(BatchT<T> z, BatchT<T> x, size_t n, unsigned mask) { bblas<T>(QMG_BOP_COPY, 0, 0, &x, 0, z, n, mask); }
+template <typename T> inline void bcaxpy(const cvec& a, BatchT<T> x, BatchT<T> y, size_t n, unsigned mask) { bblas<T>(QMG_BOP_CAXPY, &a, 0, &x, 0, y, n, mask); }   // y += a x
+template <typename T> inline void bcxpy(BatchT<T> x, BatchT<T> y, size_t n, unsigned mask) { bblas<T>(QMG_BOP_CXPY, 0, 0, &x, 0, y, n, mask); }                   // y += x
+template <typename T> inline void bcaxpbyz(const cvec& a, BatchT<T> x, const cvec& b, BatchT<T> y, BatchT<T> z, size_t n, unsigned mask) { bblas<T>(QMG_BOP_CAXPBYZ, &a, &b, &x, &y, z, n, mask); }
+template <typename T> inline void bxmyz(BatchT<T> x, BatchT<T> y, BatchT<T> z, size_t n, unsigned mask) {   // z = x - y
+  const cvec one(z.nrhs, 1.0), mone(z.nrhs, -1.0);
+  bcaxpbyz(one, x, mone, y, z, n, mask);
+}
+template <typename T> inline void bcxpyz(BatchT<T> x, BatchT<T> y, BatchT<T> z, size_t n, unsigned mask) {   // z = x + y
+  const cvec one(z.nrhs, 1.0);
+  bcaxpbyz(one, x, one, y, z, n, mask);
+}
+
+// per-system |x_k|^2; entries of frozen systems keep `fill`
+template <typename T>
+inline std::vector<double> bnorm2sq(BatchT<T> x, size_t n, unsigned mask, double fill = 0.0) {
+  std::vector<double> raw(2 * x.nrhs, 0.0), out(x.nrhs, fill);
+  ok(qmg_batch_reduce_t(dtype_of<T>::value, QMG_BRED_NORM2, x.p, 0, n, x.nrhs, x.stride, mask, raw.data(), current_stream()), "qmg_batch_reduce");
+  for (int k = 0; k < x.nrhs; k++) if (is_active(mask, k)) out[k] = raw[2 * k];
+  return out;
+}
+template <typename T>
+inline std::vector<double> bdiffnorm2sq(BatchT<T> x, BatchT<T> y, size_t n, unsigned mask) {
+  std::vector<double> raw(2 * x.nrhs, 0.0), out(x.nrhs, 0.0);
+  ok(qmg_batch_reduce_t(dtype_of<T>::value, QMG_BRED_DIFFNORM2, x.p, y.p, n, x.nrhs, x.stride, mask, raw.data(), current_stream()), "qmg_batch_reduce");
+  for (int k = 0; k < x.nrhs; k++) if (is_active(mask, k)) out[k] = raw[2 * k];
+  return out;
+}
+// d[k][j] = <xs[j]_k, y_k>
+template <typename T>
+inline std::vector<cvec> bmultidot(const std::vector<BatchT<T> >& xs, int nj, BatchT<T> y, size_t n, unsigned mask) {
+  std::vector<cvec> out(y.nrhs, cvec(nj, 0.0));
+  int done = 0;
+  while (done < nj) {   // the ABI takes up to 32 vector sets per call
+    const int jj = (nj - done > 32) ? 32 : nj - done;
+    std::vector<const void*> ptrs(jj);
+    for (int j = 0; j < jj; j++) ptrs[j] = xs[done + j].p;
+    std::vector<double> raw((size_t)2 * y.nrhs * jj, 0.0);
+    ok(qmg_batch_multidot_t(dtype_of<T>::value, ptrs.data(), jj, y.p, n, y.nrhs, y.stride, mask, raw.data(), current_stream()), "qmg_batch_multidot");
+    for (int k = 0; k < y.nrhs; k++)
+      if (is_active(mask, k))
+        for (int j = 0; j < jj; j++) out[k][done + j] = complex<double>(raw[((size_t)k * jj + j) * 2], raw[((size_t)k * jj + j) * 2 + 1]);
+    done += jj;
+  }
+  return out;
+}
+// y_k += sum_j c[k][j] xs[j]_k
+template <typename T>
+inline void bmulti_caxpy(const std::vector<cvec>& c, const std::vector<BatchT<T> >& xs, int nj, BatchT<T> y, size_t n, unsigned mask) {
+  if (nj <= 0) return;
+  std::vector<double> cf((size_t)2 * nj * y.nrhs, 0.0);
+  std::vector<const void*> ptrs(nj);
+  for (int j = 0; j < nj; j++) {
+    ptrs[j] = xs[j].p;
+    for (int k = 0; k < y.nrhs; k++) { cf[((size_t)j * y.nrhs + k) * 2] = c[k][j].real(); cf[((size_t)j * y.nrhs + k) * 2 + 1] = c[k][j].imag(); }
+  }
+  ok(qmg_batch_multi_caxpy_t(dtype_of<T>::value, cf.data(), ptrs.data(), nj, y.p, n, y.nrhs, y.stride, mask, current_stream()), "qmg_batch_multi_caxpy");
+}
+// one flexible-GCR iteration's vector updates in one pass: w_k += sum_j c[k][j] Ws[j]_k ; r_k += a[k] w_k ; z_next_k = r_k (z_next.p != 0)
+template <typename T>
+inline void bgcr_update(const std::vector<cvec>& c, const std::vector<BatchT<T> >& Ws, int nj, BatchT<T> w, const cvec& a, BatchT<T> r, BatchT<T> z_next, size_t n, unsigned mask) {
+  std::vector<double> cf((size_t)2 * (nj > 0 ? nj : 1) * w.nrhs, 0.0), af((size_t)2 * w.nrhs, 0.0);
+  std::vector<const void*> ptrs(nj > 0 ? nj : 1, (const void*)0);
+  for (int j = 0; j < nj; j++) {
+    ptrs[j] = Ws[j].p;
+    for (int k = 0; k < w.nrhs; k++) { cf[((size_t)j * w.nrhs + k) * 2] = c[k][j].real(); cf[((size_t)j * w.nrhs + k) * 2 + 1] = c[k][j].imag(); }
+  }
+  for (int k = 0; k < w.nrhs; k++) { af[2 * k] = a[k].real(); af[2 * k + 1] = a[k].imag(); }
+  ok(qmg_batch_gcr_update_t(dtype_of<T>::value, nj > 0 ? cf.data() : 0, nj > 0 ? ptrs.data() : 0, nj, w.p, af.data(), r.p, z_next.p, n, w.nrhs, w.stride, mask, current_stream()),
+     "qmg_batch_gcr_update");
+}
+// z_k = x_k across storage precisions (round / widen), active systems only
+template <typename TD, typename TS>
+inline void bconvert(BatchT<TD> z, BatchT<TS> x, size_t n, unsigned mask) {
+  for (int k = 0; k < z.nrhs; k++)
+    if (is_active(mask, k)) ok(qmg_convert(z.vec(k), dtype_of<TD>::value, x.vec(k), dtype_of<TS>::value, n, current_stream()), "qmg_convert");
+}
+
+}  // namespace qmg
+
+// lhs_k = A rhs_k for the active systems
+template <typename T> using batch_matrix_op_t = void (*)(qmg::BatchT<T> lhs, qmg::BatchT<T> rhs, unsigned mask, void* extra_data);
+template <typename T> using batch_precond_op_t = void (*)(qmg::BatchT<T> lhs, qmg::BatchT<T> rhs, int size, unsigned mask, void* extra_data, inversion_verbose_struct* verb);
+typedef batch_matrix_op_t<double> batch_matrix_op;
+typedef batch_precond_op_t<double> batch_precond_op;
+
+namespace qmg {
+// r = b - A x for the active systems (tmp: scratch for A x), one counted operator application each; returns |r_k|^2
+template <typename T>
+inline std::vector<double> bresidual(BatchT<T> r, BatchT<T> x, BatchT<T> b, BatchT<T> tmp, int size, batch_matrix_op_t<T> matrix_vector, void* extra_info,
+                                     unsigned mask, std::vector<int>& ops) {
+  matrix_vector(tmp, x, mask, extra_info);
+  for (int k = 0; k < x.nrhs; k++) if (is_active(mask, k)) ops[k]++;
+  bxmyz(b, tmp, r, size, mask);
+  return bnorm2sq(r, size, mask);
+}
+
+// a single-vector operator / preconditioner (the reference's callback types) as the operator of a batch of one system
+struct MatrixOp1 { matrix_op_cplx f; void* data; };
+struct PrecondOp1 { precond_op_cplx f; void* data; };
+inline void matrix_op1(Batch lhs, Batch rhs, unsigned mask, void* op) {
+  if (mask) ((MatrixOp1*)op)->f(lhs.p, rhs.p, ((MatrixOp1*)op)->data);
+}
+inline void precond_op1(Batch lhs, Batch rhs, int size, unsigned mask, void* op, inversion_verbose_struct* verb) {
+  if (mask) ((PrecondOp1*)op)->f(lhs.p, rhs.p, size, ((PrecondOp1*)op)->data, verb);
+}
+inline inversion_info renamed(inversion_info inv, const std::string& name) { inv.name = name; return inv; }
 }  // namespace qmg
 
 // ---------------------------------------------------------------------------------------------
-// MinRes / MR with relaxation omega (minv_vector_minres(x, b, n, iters, tol, omega, op, opdata)).
-//   r = b - A x ; repeat: p = A r ; alpha = <p,r>/<p,p> ; x += omega alpha r ; r -= omega alpha p
+// MR(omega) (minv_vector_minres):  r = b - A x ; repeat: p = A r ; alpha = omega <p,r>/<p,p> ; x += alpha r ; r -= alpha p.
+// zero_guess: the caller has zeroed phi, r0 = b (no apply).  `name` labels the printed lines (and inversion_info::name).
 // ---------------------------------------------------------------------------------------------
-inline inversion_info minv_vector_minres(complex<double>* phi, complex<double>* phi0, int size, int max_iter, double eps, double omega,
-                                         matrix_op_cplx matrix_vector, void* extra_info, inversion_verbose_struct* verb = 0) {
-  inversion_info invif;
-  invif.name = "MinRes (relaxation parameter " + std::to_string(omega) + ")";
-  qmg::VecPool pool(size);
-  complex<double>* r = pool.get();
-  complex<double>* p = pool.get();
-  const double bsq = norm2sq(phi0, size);
-  const double bnorm = std::sqrt(bsq);
-  int ops = 0;
-  matrix_vector(p, phi, extra_info); ops++;
-  caxpbyz(1.0, phi0, -1.0, p, r, size);
-  double rsq = norm2sq(r, size);
-  double rsq_ref = rsq;
-  int k = 0;
-  bool conv = (bnorm == 0.0) || (std::sqrt(rsq) < eps * bnorm);
-  while (!conv && k < max_iter) {
-    matrix_vector(p, r, extra_info); ops++;
+template <typename T>
+inline std::vector<inversion_info> bmr_core(qmg::BatchT<T> phi, qmg::BatchT<T> phi0, int size, int max_iter, double eps, double omega,
+                                            batch_matrix_op_t<T> matrix_vector, void* extra_info, unsigned mask, bool zero_guess,
+                                            inversion_verbose_struct* verb = 0, const char* name = "MinRes") {
+  const int nrhs = phi.nrhs;
+  std::vector<inversion_info> inv(nrhs);
+  qmg::BatchPoolT<T> pool(phi.stride, nrhs);
+  qmg::BatchT<T> r = pool.get(), p = pool.get();
+  const std::vector<double> bsq = qmg::bnorm2sq(phi0, size, mask);
+  std::vector<int> its(nrhs, 0), ops(nrhs, 0);
+  std::vector<double> rsq = bsq;
+  if (zero_guess) qmg::bcopy(r, phi0, size, mask);
+  else rsq = qmg::bresidual(r, phi, phi0, p, size, matrix_vector, extra_info, mask, ops);
+  std::vector<double> rsq_ref = rsq, bnorm(nrhs);
+  std::vector<bool> conv(nrhs, false);
+  unsigned act = 0;
+  for (int k = 0; k < nrhs; k++) {
+    bnorm[k] = std::sqrt(bsq[k]);
+    if (!qmg::is_active(mask, k)) continue;
+    conv[k] = (bnorm[k] == 0.0) || (std::sqrt(rsq[k]) < eps * bnorm[k]);
+    if (!conv[k] && max_iter > 0) act |= 1u << k;
+  }
+  std::vector<qmg::BatchT<T> > rp(2);
+  rp[0] = r; rp[1] = p;
+  while (act) {
+    matrix_vector(p, r, act, extra_info);
     // <r,p> and <p,p> in one pass over p; the new residual norm follows analytically:
     // |r - a p|^2 = |r|^2 - (2 omega - omega^2) |<p,r>|^2 / <p,p>   for a = omega <p,r>/<p,p>
-    std::vector<complex<double>*> rp = {r, p};
-    std::vector<complex<double>> d2 = qmg::multidot(rp, 2, p, size);
-    const complex<double> pr = std::conj(d2[0]);
-    const double pp = d2[1].real();
-    if (pp == 0.0) break;
-    const complex<double> alpha = omega * pr / pp;
-    caxpy(alpha, r, phi, size);
-    // (the subtraction loses absolute accuracy ~1e-16 * rsq_ref: re-anchor with a true norm after every 8 orders of magnitude)
-    rsq = rsq - (2.0 * omega - omega * omega) * std::norm(pr) / pp;
-    const bool renorm = !(rsq > 1e-8 * rsq_ref) || std::sqrt(rsq) < 4.0 * eps * bnorm;
-    // r is only needed by a further iteration or by the re-anchoring: the residual update of the LAST iteration is skipped
-    // (callers that want the residual recompute b - A x, as the K-cycle does); x and the returned |r|^2 are unaffected
-    if (renorm || k + 1 < max_iter) caxpy(-alpha, p, r, size);
-    if (renorm) { rsq = norm2sq(r, size); rsq_ref = rsq; }
-    k++;
-    qmg::report(verb, "MinRes", k, std::sqrt(rsq) / bnorm);
-    if (std::sqrt(rsq) < eps * bnorm) conv = true;
+    const std::vector<qmg::cvec> d2 = qmg::bmultidot(rp, 2, p, size, act);
+    qmg::cvec alpha(nrhs, 0.0), malpha(nrhs, 0.0);
+    unsigned upd = 0, renorm = 0;
+    for (int k = 0; k < nrhs; k++) {
+      if (!qmg::is_active(act, k)) continue;
+      ops[k]++;
+      const complex<double> pr = std::conj(d2[k][0]);
+      const double pp = d2[k][1].real();
+      if (pp == 0.0) { act &= ~(1u << k); continue; }   // breakdown: this system stops
+      alpha[k] = omega * pr / pp; malpha[k] = -alpha[k];
+      upd |= 1u << k;
+      // (the subtraction loses absolute accuracy ~1e-16 * rsq_ref: re-anchor with a true norm after every 8 orders of magnitude)
+      rsq[k] = rsq[k] - (2.0 * omega - omega * omega) * std::norm(pr) / pp;
+      if (!(rsq[k] > 1e-8 * rsq_ref[k]) || std::sqrt(rsq[k]) < 4.0 * eps * bnorm[k]) renorm |= 1u << k;
+    }
+    qmg::bcaxpy(alpha, r, phi, size, upd);
+    // r is only needed by a further iteration or by a true-norm re-anchoring: the residual update of a system's LAST
+    // iteration is skipped (callers that want the residual recompute b - A x, as the K-cycle does); x and the returned |r|^2 are unaffected
+    unsigned need_r = renorm;
+    for (int k = 0; k < nrhs; k++) if (qmg::is_active(upd, k) && its[k] + 1 < max_iter) need_r |= 1u << k;
+    qmg::bcaxpy(malpha, p, r, size, upd & need_r);
+    if (renorm) {
+      const std::vector<double> t = qmg::bnorm2sq(r, size, renorm);
+      for (int k = 0; k < nrhs; k++) if (qmg::is_active(renorm, k)) { rsq[k] = t[k]; rsq_ref[k] = t[k]; }
+    }
+    for (int k = 0; k < nrhs; k++) {
+      if (!qmg::is_active(upd, k)) continue;
+      its[k]++;
+      qmg::report(verb, name, nrhs, k, its[k], std::sqrt(rsq[k]) / bnorm[k]);
+      if (std::sqrt(rsq[k]) < eps * bnorm[k]) { conv[k] = true; act &= ~(1u << k); }
+      else if (its[k] >= max_iter) act &= ~(1u << k);
+    }
   }
-  invif.success = conv;
-  invif.iter = k;
-  invif.resSq = rsq;
-  invif.ops_count = ops;
-  qmg::summary(verb, "MinRes", conv, k, bnorm > 0 ? std::sqrt(rsq) / bnorm : 0.0);
-  return invif;
+  for (int k = 0; k < nrhs; k++) {
+    inv[k].success = conv[k]; inv[k].iter = its[k]; inv[k].resSq = rsq[k]; inv[k].ops_count = ops[k]; inv[k].name = name;
+    if (qmg::is_active(mask, k)) qmg::summary(verb, name, nrhs, k, conv[k], its[k], bnorm[k] > 0 ? std::sqrt(rsq[k]) / bnorm[k] : 0.0);
+  }
+  return inv;
 }
 
 // ---------------------------------------------------------------------------------------------
-// CG (Hermitian positive definite op): minv_vector_cg(x, b, n, max_iter, tol, op, opdata, verb)
+// BiCGStab(L) (Sleijpen & Fokkema 1993; minv_vector_bicgstab_l): the null-vector relaxation of tests/n13_wilson_kcycle/wilson_kcycle.cpp:359
+// and the fine-level solver of the slab drivers.  `iter` counts BiCG steps per system; a system that converges, breaks down or
+// reaches max_iter is frozen at the end of its L-block.  The closing updates of a block go through one multi-vector pass each.
+// zero_guess: the caller has zeroed phi, r0 = b (no apply).
 // ---------------------------------------------------------------------------------------------
-inline inversion_info minv_vector_cg(complex<double>* phi, complex<double>* phi0, int size, int max_iter, double eps, matrix_op_cplx matrix_vector,
-                                     void* extra_info, inversion_verbose_struct* verb = 0) {
-  inversion_info invif;
-  invif.name = "CG";
-  qmg::VecPool pool(size);
-  complex<double>*r = pool.get(), *p = pool.get(), *Ap = pool.get();
-  const double bnorm = std::sqrt(norm2sq(phi0, size));
-  int ops = 0;
-  matrix_vector(Ap, phi, extra_info); ops++;
-  caxpbyz(1.0, phi0, -1.0, Ap, r, size);
-  copy_vector(p, r, size);
-  double rsq = norm2sq(r, size);
-  int k = 0;
-  bool conv = (bnorm == 0.0) || (std::sqrt(rsq) < eps * bnorm);
-  while (!conv && k < max_iter) {
-    matrix_vector(Ap, p, extra_info); ops++;
-    const double pAp = dot(p, Ap, size).real();
-    if (pAp == 0.0) break;
-    const double alpha = rsq / pAp;
-    caxpy(alpha, p, phi, size);
-    caxpy(-alpha, Ap, r, size);
-    const double rsq_new = norm2sq(r, size);
-    k++;
-    qmg::report(verb, "CG", k, std::sqrt(rsq_new) / bnorm);
-    if (std::sqrt(rsq_new) < eps * bnorm) { rsq = rsq_new; conv = true; break; }
-    const double beta = rsq_new / rsq;
-    rsq = rsq_new;
-    cxpay(r, beta, p, size);   // p = r + beta p
+template <typename T>
+inline std::vector<inversion_info> bbicgstab_l_core(qmg::BatchT<T> phi, qmg::BatchT<T> phi0, int size, int max_iter, double eps, int L,
+                                                    batch_matrix_op_t<T> matrix_vector, void* extra_info, unsigned mask, bool zero_guess,
+                                                    inversion_verbose_struct* verb = 0, const char* name = "BiCGStab-L") {
+  const int nrhs = phi.nrhs;
+  std::vector<inversion_info> inv(nrhs);
+  qmg::BatchPoolT<T> pool(phi.stride, nrhs);
+  std::vector<qmg::BatchT<T> > r(L + 1), u(L + 1);
+  for (int i = 0; i <= L; i++) { r[i] = pool.get(); u[i] = pool.get(); }
+  qmg::BatchT<T> rt = pool.get();
+  const std::vector<double> bsq = qmg::bnorm2sq(phi0, size, mask);
+  std::vector<int> its(nrhs, 0), ops(nrhs, 0);
+  std::vector<double> rsq = bsq, bnorm(nrhs, 0.0);
+  if (zero_guess) qmg::bcopy(r[0], phi0, size, mask);
+  else rsq = qmg::bresidual(r[0], phi, phi0, u[0], size, matrix_vector, extra_info, mask, ops);
+  qmg::bcopy(rt, r[0], size, mask);
+  qmg::bzero(u[0], size, mask);
+  std::vector<bool> conv(nrhs, false);
+  qmg::cvec rho0(nrhs, 1.0), alpha(nrhs, 0.0), omega(nrhs, 1.0);
+  unsigned act = 0;
+  for (int k = 0; k < nrhs; k++) {
+    bnorm[k] = std::sqrt(bsq[k]);
+    if (!qmg::is_active(mask, k)) continue;
+    conv[k] = (bnorm[k] == 0.0) || (std::sqrt(rsq[k]) < eps * bnorm[k]);
+    if (!conv[k] && max_iter > 0) act |= 1u << k;
   }
-  invif.success = conv; invif.iter = k; invif.resSq = rsq; invif.ops_count = ops;
-  qmg::summary(verb, "CG", conv, k, bnorm > 0 ? std::sqrt(rsq) / bnorm : 0.0);
-  return invif;
+  const qmg::cvec one(nrhs, 1.0);
+  std::vector<qmg::BatchT<T> > single(1);
+  auto bdot1 = [&](qmg::BatchT<T> a, qmg::BatchT<T> b, unsigned m) {   // <a_k, b_k> per system
+    single[0] = a;
+    const std::vector<qmg::cvec> d = qmg::bmultidot(single, 1, b, size, m);
+    qmg::cvec out(nrhs, 0.0);
+    for (int k = 0; k < nrhs; k++) out[k] = d[k][0];
+    return out;
+  };
+  std::vector<qmg::cvec> tau(nrhs, qmg::cvec((L + 1) * (L + 1), 0.0)), gamma(nrhs, qmg::cvec(L + 1, 0.0)), gammap(nrhs, qmg::cvec(L + 1, 0.0)),
+      gammapp(nrhs, qmg::cvec(L + 1, 0.0));
+  std::vector<std::vector<double> > sigma(nrhs, std::vector<double>(L + 1, 0.0));
+  while (act) {
+    for (int k = 0; k < nrhs; k++) if (qmg::is_active(act, k)) rho0[k] = -omega[k] * rho0[k];
+    for (int j = 0; j < L && act; j++) {   // BiCG part
+      const qmg::cvec rho1 = bdot1(rt, r[j], act);
+      qmg::cvec mbeta(nrhs, 0.0);
+      for (int k = 0; k < nrhs; k++) {
+        if (!qmg::is_active(act, k)) continue;
+        if (rho0[k] == 0.0) { act &= ~(1u << k); continue; }                 // breakdown: this system stops
+        mbeta[k] = -(alpha[k] * rho1[k] / rho0[k]);
+        rho0[k] = rho1[k];
+      }
+      if (!act) break;
+      for (int i = 0; i <= j; i++) qmg::bcaxpbyz(one, r[i], mbeta, u[i], u[i], size, act);   // u_i = r_i - beta u_i
+      matrix_vector(u[j + 1], u[j], act, extra_info);
+      const qmg::cvec gam = bdot1(rt, u[j + 1], act);
+      qmg::cvec malpha(nrhs, 0.0);
+      for (int k = 0; k < nrhs; k++) {
+        if (!qmg::is_active(act, k)) continue;
+        ops[k]++;
+        if (gam[k] == 0.0) { act &= ~(1u << k); continue; }
+        alpha[k] = rho0[k] / gam[k];
+        malpha[k] = -alpha[k];
+      }
+      if (!act) break;
+      for (int i = 0; i <= j; i++) qmg::bcaxpy(malpha, u[i + 1], r[i], size, act);
+      matrix_vector(r[j + 1], r[j], act, extra_info);
+      qmg::bcaxpy(alpha, u[0], phi, size, act);
+      for (int k = 0; k < nrhs; k++) if (qmg::is_active(act, k)) { ops[k]++; its[k]++; }
+    }
+    if (!act) break;
+    for (int j = 1; j <= L && act; j++) {   // MR part: modified Gram-Schmidt on r_1..r_L
+      for (int i = 1; i < j; i++) {
+        const qmg::cvec d = bdot1(r[i], r[j], act);
+        qmg::cvec mt(nrhs, 0.0);
+        for (int k = 0; k < nrhs; k++) if (qmg::is_active(act, k)) { tau[k][i * (L + 1) + j] = d[k] / sigma[k][i]; mt[k] = -tau[k][i * (L + 1) + j]; }
+        qmg::bcaxpy(mt, r[i], r[j], size, act);
+      }
+      std::vector<qmg::BatchT<T> > two(2);
+      two[0] = r[j]; two[1] = r[0];
+      // <r_j, r_j> and <r_j, r_0> in one pass over r_j: d[k][0] = <r_j, r_j>, d[k][1] = <r_0, r_j> = conj <r_j, r_0>
+      const std::vector<qmg::cvec> d = qmg::bmultidot(two, 2, r[j], size, act);
+      for (int k = 0; k < nrhs; k++) {
+        if (!qmg::is_active(act, k)) continue;
+        sigma[k][j] = d[k][0].real();
+        if (sigma[k][j] == 0.0) { act &= ~(1u << k); continue; }
+        gammap[k][j] = std::conj(d[k][1]) / sigma[k][j];
+      }
+    }
+    if (!act) break;
+    std::vector<qmg::cvec> cx(nrhs, qmg::cvec(L, 0.0)), cr(nrhs, qmg::cvec(L, 0.0)), cu(nrhs, qmg::cvec(L, 0.0));
+    for (int k = 0; k < nrhs; k++) {
+      if (!qmg::is_active(act, k)) continue;
+      qmg::cvec &g = gamma[k], &gp = gammap[k], &gpp = gammapp[k], &t = tau[k];
+      g[L] = gp[L];
+      omega[k] = g[L];
+      for (int j = L - 1; j >= 1; j--) {
+        g[j] = gp[j];
+        for (int i = j + 1; i <= L; i++) g[j] -= t[j * (L + 1) + i] * g[i];
+      }
+      for (int j = 1; j < L; j++) {
+        gpp[j] = g[j + 1];
+        for (int i = j + 1; i < L; i++) gpp[j] += t[j * (L + 1) + i] * g[i + 1];
+      }
+      // x += gamma_1 r_0 + sum_{j<L} gamma''_j r_j ; r_0 -= sum_{j<=L} gamma'_j r_j ; u_0 -= sum_{j<=L} gamma_j u_j
+      cx[k][0] = g[1];
+      for (int j = 1; j < L; j++) cx[k][j] = gpp[j];
+      for (int j = 1; j <= L; j++) { cr[k][j - 1] = -gp[j]; cu[k][j - 1] = -g[j]; }
+    }
+    std::vector<qmg::BatchT<T> > r0L(r.begin(), r.begin() + L), r1L(r.begin() + 1, r.end()), u1L(u.begin() + 1, u.end());
+    qmg::bmulti_caxpy(cx, r0L, L, phi, size, act);     // reads r_0 before it changes
+    qmg::bmulti_caxpy(cr, r1L, L, r[0], size, act);
+    qmg::bmulti_caxpy(cu, u1L, L, u[0], size, act);
+    const std::vector<double> t2 = qmg::bnorm2sq(r[0], size, act);
+    for (int k = 0; k < nrhs; k++) {
+      if (!qmg::is_active(act, k)) continue;
+      rsq[k] = t2[k];
+      qmg::report(verb, name, nrhs, k, its[k], std::sqrt(rsq[k]) / bnorm[k]);
+      if (std::sqrt(rsq[k]) < eps * bnorm[k]) { conv[k] = true; act &= ~(1u << k); }
+      else if (its[k] >= max_iter) act &= ~(1u << k);
+    }
+  }
+  for (int k = 0; k < nrhs; k++) {
+    inv[k].success = conv[k]; inv[k].iter = its[k]; inv[k].resSq = rsq[k]; inv[k].ops_count = ops[k]; inv[k].name = name;
+    if (qmg::is_active(mask, k)) qmg::summary(verb, name, nrhs, k, conv[k], its[k], bnorm[k] > 0 ? std::sqrt(rsq[k]) / bnorm[k] : 0.0);
+  }
+  return inv;
 }
 
-inline inversion_info minv_vector_cg_restart(complex<double>* phi, complex<double>* phi0, int size, int max_iter, double eps, int restart_freq,
-                                             matrix_op_cplx matrix_vector, void* extra_info, inversion_verbose_struct* verb = 0) {
-  inversion_info total;
-  total.name = "Restarted CG(" + std::to_string(restart_freq) + ")";
-  const double bnorm = std::sqrt(norm2sq(phi0, size));
-  while (total.iter < max_iter) {
-    const int chunk = (max_iter - total.iter < restart_freq) ? max_iter - total.iter : restart_freq;
-    inversion_info one = minv_vector_cg(phi, phi0, size, chunk, eps, matrix_vector, extra_info, 0);
-    total.iter += one.iter; total.ops_count += one.ops_count; total.resSq = one.resSq; total.success = one.success;
-    if (one.success || one.iter == 0) break;
-  }
-  qmg::summary(verb, "CG-restart", total.success, total.iter, bnorm > 0 ? std::sqrt(total.resSq) / bnorm : 0.0);
-  return total;
-}
 
 // ---------------------------------------------------------------------------------------------
-// Flexible (variable-preconditioned) GCR with optional restarts -- the K-cycle's Krylov wrapper.
+// Flexible (variable-preconditioned) GCR with optional restarts (minv_vector_gcr*) -- the K-cycle's Krylov solver.
 //   r = b - A x
 //   loop:  z_k = M^-1 r (preconditioner; identity when precond == 0)
-//          w_k = A z_k ; orthogonalise w_k against w_0..w_{k-1} (and carry z_k along)
-//          alpha = <w_k, r>/<w_k,w_k> ; x += alpha z_k ; r -= alpha w_k
+//          w_k = A z_k ; orthogonalise w_k against w_0..w_{k-1}
+//          alpha = <w_k, r>/<w_k,w_k> ; x += alpha z'_k ; r -= alpha w_k
 //   restart_freq > 0: the basis is dropped every restart_freq directions.
 // The z_k are NOT orthogonalised explicitly.  With c_ik the Gram-Schmidt coefficients of w_k, the conjugate
 // directions are z'_k = z_k + sum_{i<k} c_ik z'_i and x = x0 + sum_k alpha_k z'_k = x0 + sum_j y_j z_j, where y
-// follows from alpha and c by a k x k back-substitution on the host (qmg::gcr_direction_weights).  x is only needed
-// at a restart and at exit, so the k-vector pass "z_k -= sum c_ik Z_i" of every iteration (a third of GCR's BLAS-1
-// traffic) becomes ONE multi-axpy per restart cycle.  w_k, r and every scalar -- hence every convergence decision --
-// are computed exactly as before; x differs by rounding only.
+// follows from alpha and c by a k x k back-substitution on the host (qmg::gcr_direction_weights): x is only brought
+// up to date at a restart and at exit, by ONE multi-axpy.  All systems of a batch start together, so the basis index kb
+// (and with it the restart points) is common; everything else is per system.
+// zero_guess: the caller has zeroed phi, r0 = b (no apply).
 // ---------------------------------------------------------------------------------------------
-inline inversion_info qmg_gcr_core(complex<double>* phi, complex<double>* phi0, int size, int max_iter, double eps, int restart_freq,
-                                   matrix_op_cplx matrix_vector, void* extra_info, precond_op_cplx precond, void* precond_info,
-                                   inversion_verbose_struct* verb, const char* name) {
-  inversion_info invif;
-  invif.name = name;
+template <typename T>
+inline std::vector<inversion_info> bgcr_core(qmg::BatchT<T> phi, qmg::BatchT<T> phi0, int size, int max_iter, double eps, int restart_freq,
+                                             batch_matrix_op_t<T> matrix_vector, void* extra_info, batch_precond_op_t<T> precond, void* precond_info,
+                                             unsigned mask, bool zero_guess, inversion_verbose_struct* verb, const char* name,
+                                             const std::vector<double>* eps_per_system = 0) {
+  const int nrhs = phi.nrhs;
+  std::vector<inversion_info> inv(nrhs);
+  std::vector<double> epsv(nrhs, eps);   // relative tolerance per system (the K-cycle's inner tolerance depends on the system)
+  if (eps_per_system) epsv = *eps_per_system;
   const int basis_max = (restart_freq > 0) ? restart_freq : max_iter;
-  qmg::VecPool pool(size);
-  complex<double>* r = pool.get();
-  complex<double>* tmp = pool.get();
-  std::vector<complex<double>*> Z, W;     // raw search directions z_k and orthogonalised images w'_k, allocated on demand
-  std::vector<double> Wnorm2;
-  std::vector<std::vector<complex<double>>> C;   // C[k][i] = Gram-Schmidt coefficient of w_k against w'_i (i < k), this cycle
-  std::vector<complex<double>> alphas;           // alpha_k of this cycle
-  auto flush_x = [&](int K) {                    // x += sum_k alpha_k z'_k for the K directions of this cycle
-    if (K <= 0) return;
-    qmg::multi_caxpy(qmg::gcr_direction_weights(alphas, C, K), Z, K, phi, size);
+  qmg::BatchPoolT<T> pool(phi.stride, nrhs);
+  qmg::BatchT<T> r = pool.get(), tmp = pool.get();
+  std::vector<qmg::BatchT<T> > Z, W;        // raw search directions and orthogonalised images
+  std::vector<std::vector<double> > Wnorm2;   // [basis index][system]
+  std::vector<std::vector<qmg::cvec> > C(nrhs);   // C[system][k][i]: Gram-Schmidt coefficients of this cycle
+  std::vector<qmg::cvec> alphas(nrhs);           // alphas[system][k]
+  std::vector<int> used(nrhs, 0);                // directions system k has taken in this cycle
+  auto flush_x = [&]() {                         // x_k += sum_j y_kj z_j for every system with pending directions
+    int K = 0;
+    unsigned m = 0;
+    for (int k = 0; k < nrhs; k++) if (used[k] > 0) { m |= 1u << k; if (used[k] > K) K = used[k]; }
+    if (!m) return;
+    std::vector<qmg::cvec> y(nrhs, qmg::cvec(K, 0.0));
+    for (int k = 0; k < nrhs; k++) {
+      if (used[k] <= 0) continue;
+      const qmg::cvec yk = qmg::gcr_direction_weights(alphas[k], C[k], used[k]);
+      for (int j = 0; j < used[k]; j++) y[k][j] = yk[j];
+      used[k] = 0;
+    }
+    qmg::bmulti_caxpy(y, Z, K, phi, size, m);
   };
-  const double bsq = norm2sq(phi0, size);
-  const double bnorm = std::sqrt(bsq);
-  int ops = 0;
-  matrix_vector(tmp, phi, extra_info); ops++;
-  caxpbyz(1.0, phi0, -1.0, tmp, r, size);
-  double rsq = norm2sq(r, size);
-  double rsq_ref = rsq;
-  bool conv = (bnorm == 0.0) || (std::sqrt(rsq) < eps * bnorm);
-  int k = 0, kb = 0;   // total iterations, index within the current basis
+  const std::vector<double> bsq = qmg::bnorm2sq(phi0, size, mask);
+  std::vector<double> rsq(nrhs, 0.0), rsq_ref(nrhs, 0.0), bnorm(nrhs, 0.0);
+  std::vector<int> its(nrhs, 0), ops(nrhs, 0);
+  std::vector<bool> conv(nrhs, false);
+  if (zero_guess) { qmg::bcopy(r, phi0, size, mask); rsq = bsq; }
+  else rsq = qmg::bresidual(r, phi, phi0, tmp, size, matrix_vector, extra_info, mask, ops);
+  unsigned act = 0;
+  for (int k = 0; k < nrhs; k++) {
+    bnorm[k] = std::sqrt(bsq[k]);
+    rsq_ref[k] = rsq[k];
+    if (!qmg::is_active(mask, k)) continue;
+    conv[k] = (bnorm[k] == 0.0) || (std::sqrt(rsq[k]) < epsv[k] * bnorm[k]);
+    if (!conv[k] && max_iter > 0) act |= 1u << k;
+  }
+  int kb = 0;
+  bool z_ready = false;
   inversion_verbose_struct pverb(verb ? verb->precond_verbosity : VERB_NONE, verb ? verb->precond_verb_prefix : std::string(""));
   if (verb) { pverb.precond_verbosity = verb->precond_verbosity; pverb.precond_verb_prefix = verb->precond_verb_prefix; }
-  while (!conv && k < max_iter) {
-    if (kb == (int)Z.size()) { Z.push_back(pool.get()); W.push_back(pool.get()); Wnorm2.push_back(0.0); C.push_back(std::vector<complex<double>>()); alphas.push_back(0.0); }
-    complex<double>* z = Z[kb];
-    complex<double>* w = W[kb];
-    if (precond) { zero_vector(z, size); precond(z, r, size, precond_info, &pverb); }
-    else copy_vector(z, r, size);
-    matrix_vector(w, z, extra_info); ops++;
-    C[kb].clear();
-    if (kb > 0) {   // Gram-Schmidt of w against the current basis: ONE multi-dot pass, ONE fused multi-axpy pass
-      std::vector<complex<double>> c = qmg::multidot(W, kb, w, size);
-      for (int i = 0; i < kb; i++) c[i] = -c[i] / Wnorm2[i];
-      qmg::multi_caxpy(c, W, kb, w, size);
-      C[kb] = c;
+  std::vector<qmg::BatchT<T> > rw(2);
+  while (act) {
+    if (kb == (int)Z.size()) { Z.push_back(pool.get()); W.push_back(pool.get()); Wnorm2.push_back(std::vector<double>(nrhs, 0.0)); }
+    for (int k = 0; k < nrhs; k++) { if ((int)C[k].size() <= kb) { C[k].push_back(qmg::cvec()); alphas[k].push_back(0.0); } }
+    qmg::BatchT<T> z = Z[kb], w = W[kb];
+    if (z.p == 0 || w.p == 0 || r.p == 0 || tmp.p == 0) {   // out of HBM: stop, report every active system as not converged
+      std::cout << "[QMG-ERROR]: " << name << ": could not allocate basis vector " << kb << " for a batch of " << nrhs << " systems; size the batch with qmg::batch_systems_that_fit.\n";
+      break;
     }
-    // <r,w> and <w,w> in one pass over w
-    std::vector<complex<double>*> rw = {r, w};
-    std::vector<complex<double>> d2 = qmg::multidot(rw, 2, w, size);
-    const double ww = d2[1].real();
-    if (ww == 0.0) break;
-    Wnorm2[kb] = ww;
-    const complex<double> wr = std::conj(d2[0]);   // <w,r>
-    const complex<double> alpha = wr / ww;
-    alphas[kb] = alpha;
-    caxpy(-alpha, w, r, size);
-    // |r - alpha w|^2 = |r|^2 - |<w,r>|^2 / <w,w>: no extra reduction; confirmed by a true norm near convergence
-    // (the subtraction loses absolute accuracy ~1e-16 * rsq_ref: re-anchor with a true norm after every 8 orders of magnitude)
-    rsq = rsq - std::norm(wr) / ww;
-    if (!(rsq > 1e-8 * rsq_ref) || std::sqrt(rsq) < 4.0 * eps * bnorm) { rsq = norm2sq(r, size); rsq_ref = rsq; }
-    k++; kb++;
-    qmg::report(verb, name, k, std::sqrt(rsq) / bnorm);
-    if (std::sqrt(rsq) < eps * bnorm) { conv = true; break; }
-    if (kb == basis_max) {   // restart: bring x up to date, recompute the true residual, drop the basis
-      flush_x(kb);
-      matrix_vector(tmp, phi, extra_info); ops++;
-      caxpbyz(1.0, phi0, -1.0, tmp, r, size);
-      rsq = norm2sq(r, size);
-      rsq_ref = rsq;
+    if (precond) { qmg::bzero(z, size, act); precond(z, r, size, act, precond_info, &pverb); }
+    else if (!z_ready) qmg::bcopy(z, r, size, act);   // (z_ready: the previous iteration's update pass wrote z = r already)
+    z_ready = false;
+    matrix_vector(w, z, act, extra_info);
+    // ONE reduction pass and one host round trip per iteration: the Gram-Schmidt
+    // coefficients c_i = <W_i, w>, <r, w> and <w, w> come from the same pass over the RAW w; for the orthogonalised w' = w - sum_i (c_i / N_i) W_i
+    //   <w', w'> = <w, w> - sum_i |c_i|^2 / N_i          (the W_i are orthogonal)
+    //   <r,  w'> = <r, w>                                (r is orthogonal to every W_i of the cycle: each step removed that component)
+    // A system whose w' keeps less than 1e-6 of |w|^2 (w almost inside the span: the subtraction has lost its digits) takes the explicit dots.
+    std::vector<qmg::cvec> d2(nrhs, qmg::cvec(2, 0.0));
+    std::vector<qmg::BatchT<T> > basis(W.begin(), W.begin() + kb);
+    basis.push_back(r); basis.push_back(w);
+    std::vector<qmg::cvec> c = qmg::bmultidot(basis, kb + 2, w, size, act);
+    unsigned explicit_dots = 0;
+    for (int k = 0; k < nrhs; k++) {
+      if (!qmg::is_active(act, k)) continue;
+      double ww = c[k][kb + 1].real();
+      const double ww_raw = ww;
+      for (int i = 0; i < kb; i++) { ww -= std::norm(c[k][i]) / Wnorm2[i][k]; c[k][i] = -c[k][i] / Wnorm2[i][k]; }
+      d2[k][0] = c[k][kb]; d2[k][1] = ww;
+      if (!(ww > 1e-6 * ww_raw)) explicit_dots |= 1u << k;
+      c[k].resize(kb);
+      C[k][kb] = c[k];
+    }
+    // With these dots alpha is known BEFORE w is orthogonalised, so the Gram-Schmidt update of w, the residual update and (without a
+    // preconditioner) the copy z_next = r go through ONE pass (qmg_batch_gcr_update_t: the same bits as the three separate passes).
+    const bool deferred = explicit_dots == 0;
+    if (!deferred && kb > 0) qmg::bmulti_caxpy(c, W, kb, w, size, act);
+    if (explicit_dots) {
+      rw[0] = r; rw[1] = w;
+      const std::vector<qmg::cvec> e2 = qmg::bmultidot(rw, 2, w, size, explicit_dots);
+      for (int k = 0; k < nrhs; k++) if (qmg::is_active(explicit_dots, k)) d2[k] = e2[k];
+    }
+    qmg::cvec alpha(nrhs, 0.0), malpha(nrhs, 0.0);
+    unsigned upd = 0, renorm = 0;
+    // the true norm re-anchors the recurrence when it has lost digits and CONFIRMS a convergence the recurrence announces
+    for (int k = 0; k < nrhs; k++) {
+      if (!qmg::is_active(act, k)) continue;
+      ops[k]++;
+      const double ww = d2[k][1].real();
+      if (ww == 0.0) { act &= ~(1u << k); continue; }
+      Wnorm2[kb][k] = ww;
+      const complex<double> wr = std::conj(d2[k][0]);
+      alpha[k] = wr / ww; malpha[k] = -alpha[k];
+      alphas[k][kb] = alpha[k];
+      used[k] = kb + 1;
+      upd |= 1u << k;
+      rsq[k] = rsq[k] - std::norm(wr) / ww;
+      if (!(rsq[k] > 1e-8 * rsq_ref[k]) || std::sqrt(rsq[k]) < epsv[k] * bnorm[k]) renorm |= 1u << k;
+    }
+    if (deferred) {
+      qmg::BatchT<T> z_next;
+      if (!precond && kb + 1 < basis_max) {
+        if (kb + 1 == (int)Z.size()) { Z.push_back(pool.get()); W.push_back(pool.get()); Wnorm2.push_back(std::vector<double>(nrhs, 0.0)); }
+        z_next = Z[kb + 1];
+      }
+      qmg::bgcr_update(c, W, kb, w, malpha, r, z_next, size, upd);
+      z_ready = z_next.p != 0;
+    } else qmg::bcaxpy(malpha, w, r, size, upd);
+    if (renorm) {
+      const std::vector<double> t = qmg::bnorm2sq(r, size, renorm);
+      for (int k = 0; k < nrhs; k++) if (qmg::is_active(renorm, k)) { rsq[k] = t[k]; rsq_ref[k] = t[k]; }
+    }
+    kb++;
+    for (int k = 0; k < nrhs; k++) {
+      if (!qmg::is_active(upd, k)) continue;
+      its[k]++;
+      qmg::report(verb, name, nrhs, k, its[k], std::sqrt(rsq[k]) / bnorm[k]);
+      if (std::sqrt(rsq[k]) < epsv[k] * bnorm[k]) { conv[k] = true; act &= ~(1u << k); }
+    }
+    if (kb == basis_max) flush_x();   // the basis is about to be reused: bring every pending x up to date (frozen systems too)
+    if (act && kb == basis_max) {   // restart: true residual, drop the basis (before the iteration cap)
+      const std::vector<double> t = qmg::bresidual(r, phi, phi0, tmp, size, matrix_vector, extra_info, act, ops);
       kb = 0;
-      if (verb && verb->verbosity >= VERB_RESTART_DETAIL) std::cout << verb->verb_prefix << name << " restart at iter " << k << " RelTol " << std::sqrt(rsq) / bnorm << "\n";
-      if (std::sqrt(rsq) < eps * bnorm) { conv = true; break; }
+      z_ready = false;
+      for (int k = 0; k < nrhs; k++) {
+        if (!qmg::is_active(act, k)) continue;
+        rsq[k] = t[k]; rsq_ref[k] = t[k];
+        if (verb && verb->verbosity >= VERB_RESTART_DETAIL) {
+          std::cout << verb->verb_prefix << name;
+          if (nrhs > 1) std::cout << " rhs " << k;
+          std::cout << " restart at iter " << its[k] << " RelTol " << std::sqrt(rsq[k]) / bnorm[k] << "\n";
+        }
+        if (std::sqrt(rsq[k]) < epsv[k] * bnorm[k]) { conv[k] = true; act &= ~(1u << k); }
+      }
     }
+    for (int k = 0; k < nrhs; k++) if (qmg::is_active(act, k) && its[k] >= max_iter) act &= ~(1u << k);
   }
-  flush_x(kb);   // (kb == 0 right after a restart: nothing pending)
-  invif.success = conv; invif.iter = k; invif.resSq = rsq; invif.ops_count = ops;
-  qmg::summary(verb, name, conv, k, bnorm > 0 ? std::sqrt(rsq) / bnorm : 0.0);
-  return invif;
+  flush_x();
+  for (int k = 0; k < nrhs; k++) {
+    inv[k].success = conv[k]; inv[k].iter = its[k]; inv[k].resSq = rsq[k]; inv[k].ops_count = ops[k]; inv[k].name = name;
+    if (qmg::is_active(mask, k)) qmg::summary(verb, name, nrhs, k, conv[k], its[k], bnorm[k] > 0 ? std::sqrt(rsq[k]) / bnorm[k] : 0.0);
+  }
+  return inv;
 }
 
+// ---------------------------------------------------------------------------------------------
+// CG with restarts (minv_vector_cg, minv_vector_cg_restart; Hermitian positive definite operators: the coarsest solve on a
+// normal-equation operator, stateful_multigrid.h:930-960).  Each cycle starts from the true residual of the current x and runs
+// at most restart_freq iterations; every active system starts each cycle together; a system that converges, breaks down
+// (<p, A p> == 0), completes a cycle without an iteration or reaches max_iter is frozen.  restart_freq <= 0: one cycle of
+// max_iter iterations.  zero_guess: the caller has zeroed phi, the first cycle's r0 = b (no apply).
+// ---------------------------------------------------------------------------------------------
+template <typename T>
+inline std::vector<inversion_info> bcg_core(qmg::BatchT<T> phi, qmg::BatchT<T> phi0, int size, int max_iter, double eps, int restart_freq,
+                                            batch_matrix_op_t<T> matrix_vector, void* extra_info, unsigned mask, bool zero_guess,
+                                            inversion_verbose_struct* verb, const char* name, const std::vector<double>* eps_per_system = 0) {
+  const int nrhs = phi.nrhs;
+  std::vector<inversion_info> inv(nrhs);
+  std::vector<double> epsv(nrhs, eps);
+  if (eps_per_system) epsv = *eps_per_system;
+  qmg::BatchPoolT<T> pool(phi.stride, nrhs);
+  qmg::BatchT<T> r = pool.get(), p = pool.get(), Ap = pool.get();
+  const std::vector<double> bsq = qmg::bnorm2sq(phi0, size, mask);
+  std::vector<double> rsq(nrhs, 0.0), bnorm(nrhs, 0.0);
+  std::vector<int> its(nrhs, 0), ops(nrhs, 0);
+  std::vector<bool> conv(nrhs, false);
+  for (int k = 0; k < nrhs; k++) bnorm[k] = std::sqrt(bsq[k]);
+  const qmg::cvec one(nrhs, 1.0);
+  std::vector<qmg::BatchT<T> > pv(1);
+  unsigned live = (r.p && p.p && Ap.p) ? mask : 0u;   // systems that may still start a cycle
+  if (!live && mask) std::cout << "[QMG-ERROR]: " << name << ": out of device memory for the CG work vectors\n";
+  bool first = true;
+  while (live) {
+    // ---- one cycle: at most `chunk` iterations per system
+    std::vector<int> chunk(nrhs, 0), done_in_cycle(nrhs, 0);
+    unsigned act = 0;
+    for (int k = 0; k < nrhs; k++) {
+      if (!qmg::is_active(live, k)) continue;
+      const int left = max_iter - its[k];
+      chunk[k] = (restart_freq > 0 && left > restart_freq) ? restart_freq : left;
+    }
+    if (first && zero_guess) { qmg::bcopy(r, phi0, size, live); rsq = bsq; }
+    else {
+      const std::vector<double> t = qmg::bresidual(r, phi, phi0, Ap, size, matrix_vector, extra_info, live, ops);
+      for (int k = 0; k < nrhs; k++) if (qmg::is_active(live, k)) rsq[k] = t[k];
+    }
+    first = false;
+    qmg::bcopy(p, r, size, live);
+    for (int k = 0; k < nrhs; k++) {
+      if (!qmg::is_active(live, k)) continue;
+      conv[k] = (bnorm[k] == 0.0) || (std::sqrt(rsq[k]) < epsv[k] * bnorm[k]);
+      if (!conv[k] && chunk[k] > 0) act |= 1u << k;
+    }
+    while (act) {
+      matrix_vector(Ap, p, act, extra_info);
+      pv[0] = p;
+      const std::vector<qmg::cvec> d = qmg::bmultidot(pv, 1, Ap, size, act);   // <p, A p>
+      qmg::cvec alpha(nrhs, 0.0), malpha(nrhs, 0.0);
+      unsigned upd = 0;
+      for (int k = 0; k < nrhs; k++) {
+        if (!qmg::is_active(act, k)) continue;
+        ops[k]++;
+        const double pAp = d[k][0].real();
+        if (pAp == 0.0) { act &= ~(1u << k); continue; }   // breakdown: this system's cycle ends
+        alpha[k] = rsq[k] / pAp; malpha[k] = -alpha[k];
+        upd |= 1u << k;
+      }
+      qmg::bcaxpy(alpha, p, phi, size, upd);
+      qmg::bcaxpy(malpha, Ap, r, size, upd);
+      const std::vector<double> rn = qmg::bnorm2sq(r, size, upd);
+      qmg::cvec beta(nrhs, 0.0);
+      unsigned go_on = 0;
+      for (int k = 0; k < nrhs; k++) {
+        if (!qmg::is_active(upd, k)) continue;
+        its[k]++; done_in_cycle[k]++;
+        qmg::report(verb, "CG", nrhs, k, its[k], std::sqrt(rn[k]) / bnorm[k]);
+        if (std::sqrt(rn[k]) < epsv[k] * bnorm[k]) { rsq[k] = rn[k]; conv[k] = true; act &= ~(1u << k); continue; }
+        beta[k] = rn[k] / rsq[k];
+        rsq[k] = rn[k];
+        if (done_in_cycle[k] >= chunk[k]) act &= ~(1u << k);
+        else go_on |= 1u << k;
+      }
+      qmg::bcaxpbyz(one, r, beta, p, p, size, go_on);   // p = r + beta p
+    }
+    // ---- which systems start another cycle: none on success, after a cycle without an iteration, at max_iter
+    unsigned next = 0;
+    for (int k = 0; k < nrhs; k++) {
+      if (!qmg::is_active(live, k)) continue;
+      if (restart_freq > 0 && !conv[k] && done_in_cycle[k] > 0 && its[k] < max_iter) next |= 1u << k;
+    }
+    live = next;
+  }
+  for (int k = 0; k < nrhs; k++) {
+    inv[k].success = conv[k]; inv[k].iter = its[k]; inv[k].resSq = rsq[k]; inv[k].ops_count = ops[k]; inv[k].name = name;
+    if (qmg::is_active(mask, k)) qmg::summary(verb, name, nrhs, k, conv[k], its[k], bnorm[k] > 0 ? std::sqrt(rsq[k]) / bnorm[k] : 0.0);
+  }
+  return inv;
+}
+
+// ---------------------------------------------------------------------------------------------
+// The reference-named single-vector entry points: the cores above on a batch of one system, from the
+// initial guess in phi.  The opening r = b - A x0 counts in ops_count; the printed lines carry no system index.
+// ---------------------------------------------------------------------------------------------
+inline inversion_info minv_vector_minres(complex<double>* phi, complex<double>* phi0, int size, int max_iter, double eps, double omega,
+                                         matrix_op_cplx matrix_vector, void* extra_info, inversion_verbose_struct* verb = 0) {
+  qmg::MatrixOp1 a = {matrix_vector, extra_info};
+  return qmg::renamed(bmr_core<double>(qmg::Batch(phi, size, 1), qmg::Batch(phi0, size, 1), size, max_iter, eps, omega, qmg::matrix_op1, &a, 1u, false, verb)[0],
+                      "MinRes (relaxation parameter " + std::to_string(omega) + ")");
+}
+inline inversion_info minv_vector_cg(complex<double>* phi, complex<double>* phi0, int size, int max_iter, double eps, matrix_op_cplx matrix_vector,
+                                     void* extra_info, inversion_verbose_struct* verb = 0) {
+  qmg::MatrixOp1 a = {matrix_vector, extra_info};
+  return bcg_core<double>(qmg::Batch(phi, size, 1), qmg::Batch(phi0, size, 1), size, max_iter, eps, -1, qmg::matrix_op1, &a, 1u, false, verb, "CG")[0];
+}
+inline inversion_info minv_vector_cg_restart(complex<double>* phi, complex<double>* phi0, int size, int max_iter, double eps, int restart_freq,
+                                             matrix_op_cplx matrix_vector, void* extra_info, inversion_verbose_struct* verb = 0) {
+  qmg::MatrixOp1 a = {matrix_vector, extra_info};
+  return qmg::renamed(bcg_core<double>(qmg::Batch(phi, size, 1), qmg::Batch(phi0, size, 1), size, max_iter, eps, restart_freq, qmg::matrix_op1, &a, 1u, false, verb, "CG-restart")[0],
+                      "Restarted CG(" + std::to_string(restart_freq) + ")");
+}
 inline inversion_info minv_vector_gcr(complex<double>* phi, complex<double>* phi0, int size, int max_iter, double eps, matrix_op_cplx op, void* opd,
                                       inversion_verbose_struct* verb = 0) {
-  return qmg_gcr_core(phi, phi0, size, max_iter, eps, -1, op, opd, 0, 0, verb, "GCR");
+  qmg::MatrixOp1 a = {op, opd};
+  return bgcr_core<double>(qmg::Batch(phi, size, 1), qmg::Batch(phi0, size, 1), size, max_iter, eps, -1, qmg::matrix_op1, &a, 0, 0, 1u, false, verb, "GCR")[0];
 }
 inline inversion_info minv_vector_gcr_restart(complex<double>* phi, complex<double>* phi0, int size, int max_iter, double eps, int restart_freq,
                                               matrix_op_cplx op, void* opd, inversion_verbose_struct* verb = 0) {
-  return qmg_gcr_core(phi, phi0, size, max_iter, eps, restart_freq, op, opd, 0, 0, verb, "GCR-restart");
+  qmg::MatrixOp1 a = {op, opd};
+  return bgcr_core<double>(qmg::Batch(phi, size, 1), qmg::Batch(phi0, size, 1), size, max_iter, eps, restart_freq, qmg::matrix_op1, &a, 0, 0, 1u, false, verb, "GCR-restart")[0];
 }
 inline inversion_info minv_vector_gcr_var_precond(complex<double>* phi, complex<double>* phi0, int size, int max_iter, double eps, matrix_op_cplx op,
                                                   void* opd, precond_op_cplx precond, void* precd, inversion_verbose_struct* verb = 0) {
-  return qmg_gcr_core(phi, phi0, size, max_iter, eps, -1, op, opd, precond, precd, verb, "VPGCR");
+  qmg::MatrixOp1 a = {op, opd};
+  qmg::PrecondOp1 m = {precond, precd};
+  return bgcr_core<double>(qmg::Batch(phi, size, 1), qmg::Batch(phi0, size, 1), size, max_iter, eps, -1, qmg::matrix_op1, &a, precond ? qmg::precond_op1 : 0, &m, 1u, false, verb, "VPGCR")[0];
 }
 inline inversion_info minv_vector_gcr_var_precond_restart(complex<double>* phi, complex<double>* phi0, int size, int max_iter, double eps,
                                                           int restart_freq, matrix_op_cplx op, void* opd, precond_op_cplx precond, void* precd,
                                                           inversion_verbose_struct* verb = 0) {
-  return qmg_gcr_core(phi, phi0, size, max_iter, eps, restart_freq, op, opd, precond, precd, verb, "VPGCR-restart");
+  qmg::MatrixOp1 a = {op, opd};
+  qmg::PrecondOp1 m = {precond, precd};
+  return bgcr_core<double>(qmg::Batch(phi, size, 1), qmg::Batch(phi0, size, 1), size, max_iter, eps, restart_freq, qmg::matrix_op1, &a, precond ? qmg::precond_op1 : 0, &m, 1u, false, verb,
+                           "VPGCR-restart")[0];
 }
-
-// ---------------------------------------------------------------------------------------------
-// BiCGStab(L) (Sleijpen & Fokkema 1993): minv_vector_bicgstab_l(x, b, n, max_iter, tol, L, op, opdata, verb)
-// -- the null-vector relaxation of tests/n13_wilson_kcycle/wilson_kcycle.cpp:359.  `iter` counts BiCG steps.
-// ---------------------------------------------------------------------------------------------
+// `iter` counts BiCG steps
 inline inversion_info minv_vector_bicgstab_l(complex<double>* phi, complex<double>* phi0, int size, int max_iter, double eps, int L,
                                              matrix_op_cplx matrix_vector, void* extra_info, inversion_verbose_struct* verb = 0) {
-  inversion_info invif;
-  invif.name = "BiCGStab-" + std::to_string(L);
-  qmg::VecPool pool(size);
-  std::vector<complex<double>*> r(L + 1), u(L + 1);
-  for (int i = 0; i <= L; i++) { r[i] = pool.get(); u[i] = pool.get(); }
-  complex<double>* rt = pool.get();
-  const double bnorm = std::sqrt(norm2sq(phi0, size));
-  int ops = 0;
-  matrix_vector(u[0], phi, extra_info); ops++;
-  caxpbyz(1.0, phi0, -1.0, u[0], r[0], size);
-  copy_vector(rt, r[0], size);
-  zero_vector(u[0], size);
-  complex<double> rho0 = 1.0, alpha = 0.0, omega = 1.0;
-  double rsq = norm2sq(r[0], size);
-  bool conv = (bnorm == 0.0) || (std::sqrt(rsq) < eps * bnorm);
-  int k = 0;
-  std::vector<complex<double>> tau((L + 1) * (L + 1)), gamma(L + 1), gammap(L + 1), gammapp(L + 1);
-  std::vector<double> sigma(L + 1);
-  bool breakdown = false;
-  while (!conv && k < max_iter && !breakdown) {
-    rho0 = -omega * rho0;
-    for (int j = 0; j < L && !breakdown; j++) {   // BiCG part
-      const complex<double> rho1 = dot(rt, r[j], size);
-      if (rho0 == 0.0) { breakdown = true; break; }
-      const complex<double> beta = alpha * rho1 / rho0;
-      rho0 = rho1;
-      for (int i = 0; i <= j; i++) cxpay(r[i], -beta, u[i], size);   // u_i = r_i - beta u_i
-      matrix_vector(u[j + 1], u[j], extra_info); ops++;
-      const complex<double> gam = dot(rt, u[j + 1], size);
-      if (gam == 0.0) { breakdown = true; break; }
-      alpha = rho0 / gam;
-      for (int i = 0; i <= j; i++) caxpy(-alpha, u[i + 1], r[i], size);
-      matrix_vector(r[j + 1], r[j], extra_info); ops++;
-      caxpy(alpha, u[0], phi, size);
-      k++;
-    }
-    if (breakdown) break;
-    for (int j = 1; j <= L; j++) {   // MR part: modified Gram-Schmidt on r_1..r_L
-      for (int i = 1; i < j; i++) {
-        tau[i * (L + 1) + j] = dot(r[i], r[j], size) / sigma[i];
-        caxpy(-tau[i * (L + 1) + j], r[i], r[j], size);
-      }
-      sigma[j] = norm2sq(r[j], size);
-      if (sigma[j] == 0.0) { breakdown = true; break; }
-      gammap[j] = dot(r[j], r[0], size) / sigma[j];
-    }
-    if (breakdown) break;
-    gamma[L] = gammap[L];
-    omega = gamma[L];
-    for (int j = L - 1; j >= 1; j--) {
-      gamma[j] = gammap[j];
-      for (int i = j + 1; i <= L; i++) gamma[j] -= tau[j * (L + 1) + i] * gamma[i];
-    }
-    for (int j = 1; j < L; j++) {
-      gammapp[j] = gamma[j + 1];
-      for (int i = j + 1; i < L; i++) gammapp[j] += tau[j * (L + 1) + i] * gamma[i + 1];
-    }
-    caxpy(gamma[1], r[0], phi, size);
-    caxpy(-gammap[L], r[L], r[0], size);
-    caxpy(-gamma[L], u[L], u[0], size);
-    for (int j = 1; j < L; j++) {
-      caxpy(-gamma[j], u[j], u[0], size);
-      caxpy(gammapp[j], r[j], phi, size);
-      caxpy(-gammap[j], r[j], r[0], size);
-    }
-    rsq = norm2sq(r[0], size);
-    qmg::report(verb, "BiCGStab-L", k, std::sqrt(rsq) / bnorm);
-    if (std::sqrt(rsq) < eps * bnorm) conv = true;
-  }
-  invif.success = conv; invif.iter = k; invif.resSq = rsq; invif.ops_count = ops;
-  qmg::summary(verb, "BiCGStab-L", conv, k, bnorm > 0 ? std::sqrt(rsq) / bnorm : 0.0);
-  return invif;
+  qmg::MatrixOp1 a = {matrix_vector, extra_info};
+  return qmg::renamed(bbicgstab_l_core<double>(qmg::Batch(phi, size, 1), qmg::Batch(phi0, size, 1), size, max_iter, eps, L, qmg::matrix_op1, &a, 1u, false, verb)[0],
+                      "BiCGStab-" + std::to_string(L));
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -465,7 +829,7 @@ inline inversion_info minv_vector_richardson(complex<double>* phi, complex<doubl
     conv = (bnorm == 0.0) || (std::sqrt(rsq) < eps * bnorm);
   }
   invif.success = conv; invif.iter = k; invif.resSq = rsq; invif.ops_count = ops;
-  qmg::summary(verb, "Richardson", conv, k, bnorm > 0 ? std::sqrt(rsq) / bnorm : 0.0);
+  qmg::summary(verb, "Richardson", 1, 0, conv, k, bnorm > 0 ? std::sqrt(rsq) / bnorm : 0.0);
   return invif;
 }
 

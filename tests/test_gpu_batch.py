@@ -299,7 +299,7 @@ def test_batch_non_temporal_reads_change_no_bit(dtype):
 @pytest.mark.parametrize("dtype", ["c64", "c32"])
 def test_mr_step_with_device_scalars_is_the_host_scalar_step(nrhs, mask, dtype):
     """qmg_batch_mr_dots_t + qmg_batch_mr_update_t (the K-cycle's fixed-count smoother, scalars never leave the device) against the
-    host-scalar step of bminv_vector_minres_zero_guess built from the existing entry points: multidot of {r, p} against p, alpha =
+    host-scalar step of bmr_core (krylov.hpp) built from the existing entry points: multidot of {r, p} against p, alpha =
     omega conj(<r,p>) / <p,p> on the host, two caxpy.  Same reduction order and the same (omega pr) / pp: x and r BIT FOR BIT, in both
     storage precisions; the dots in the device slot equal the multidot's; frozen systems untouched; the x_set form (x = alpha r) equals
     the accumulate form on x = 0; <p,p> = 0 leaves a system as it is."""

@@ -47,7 +47,7 @@ def test_c2_wilson_apply_2048_and_4096_fp64_and_fp32(golden_dir):
 
 def test_c3_wilson_kcycle_2048_three_levels_nc24(golden_dir):
     """configs[2]: n13 K-cycle, 2048^2 -> 512^2 -> 128^2, coarse nc = 24.  Four systems in lock step; system 0 is then
-    re-solved alone by the single-vector path: converged, every true residual <= 1e-10, iterations batched = single +-1,
+    re-solved alone as a batch of one (the single path): converged, every true residual <= 1e-10, iterations batched = single +-1,
     solutions equal to solver accuracy."""
     fixture = os.path.join(golden_dir, "l64t64b60_heatbath.dat")
     out = subprocess.run([os.path.join(DRIVERS, "n13_wilson_kcycle_mrhs"), "2048", "-0.07", "6.0", "2", "24", fixture, "64", "4", "verify0"], cwd=DRIVERS,
@@ -119,7 +119,7 @@ def test_c4_staggered_4096_eight_rhs_norms_and_allreduce(golden_dir, monkeypatch
 
 def test_c5_adaptive_schur_4096_fp64_and_fp32_kcycle(golden_dir):
     """configs[4] on one GPU: adaptive n22 setup (one pass), 4096^2 -> 1024^2 -> 256^2 -> 64^2, nc = 8, solved in the red-black
-    (right-block-Jacobi Schur) form of n19 -- (i) all fp64 through the single-vector path, (ii) one more system through the
+    (right-block-Jacobi Schur) form of n19 -- (i) all fp64 through the reference-named entry point (a batch of one), (ii) one more system through the
     batch engine with the K-cycle preconditioner in fp32.  Both: true residual of the ORIGINAL system <= 1e-10."""
     fixture = os.path.join(golden_dir, "l64t64b60_heatbath.dat")
     out = subprocess.run([os.path.join(DRIVERS, "n22_wilson_kcycle_adaptive"), "4096", "-0.07", "6.0", "3", "1", fixture, "64", "schur", "nrhs=1", "f32"], cwd=DRIVERS,

@@ -109,7 +109,7 @@ def test_wilson_kcycle_matches_oracle(golden_dir, L, n_refine, coarse_dof, mass)
     d = ol.make_desc(L, L, 2, clover, hopping, mass)
     assert cs.rel_l2(ol.stencil_apply(d, x_gpu), b) <= 1.1e-10
     # Dslash counts per level as tracked by the facade (stateful_multigrid.h:854-865).  The facade skips the smoothers'
-    # opening A*0 (zero initial guess, batch.hpp *_zero_guess), takes the pre-smoother's recursive residual instead of
+    # opening A*0 (zero initial guess: the zero_guess argument of the krylov.hpp cores), takes the pre-smoother's recursive residual instead of
     # recomputing rhs - A z1 (batch.hpp bmr_fixed_zero_guess), and counts the applies it really performs:
     # pre = n_pre, post = n_post per outer iteration (the reference's accounting: n_pre + 2 and n_post + 1).
     m = re.search(r"Level 0 NullVec 0 PreSmooth (\d+) Krylov 0 PostSmooth (\d+)", out.stdout)
@@ -148,8 +148,8 @@ def test_n13_128_nc12_stagnation_is_a_property_of_the_configuration(golden_dir):
                                                                   (64, 1, 24, 2, True, "-0.07"), (128, 1, 12, 4, False, "-0.06"), (128, 2, 8, 3, True, "-0.06")])
 def test_batched_kcycle_reproduces_the_single_solves(golden_dir, L, n_refine, coarse_dof, nrhs, point, mass):
     """include/qmg/batch.hpp: up to 16 systems advance through one K-cycle iteration together (coarse applies on the
-    f64 matrix cores, null vectors streamed once per step).  `verify` re-solves every system alone through the
-    single-vector path: iteration counts equal (+-1), solutions equal to solver accuracy, every true residual <= 1e-10.
+    f64 matrix cores, null vectors streamed once per step).  `verify` re-solves every system alone, as a batch of one
+    (the single path, minv_vector_gcr_var_precond_restart): iteration counts equal (+-1), solutions equal to solver accuracy, every true residual <= 1e-10.
     With `point`, system 1 is a point source and converges on its own schedule, so the outer-level freeze masks are
     exercised as well as the inner ones (coarse solves converge per system all the time).  The 128^2 fixture runs at mass
     -0.06: at -0.07 it is past critical (test_n13_128_nc12_stagnation_is_a_property_of_the_configuration)."""
@@ -269,7 +269,7 @@ def test_cgne_smoothers_match_the_oracle(golden_dir):
 def test_batched_schur_kcycle_reproduces_the_single_solves(golden_dir):
     """n19 configuration (even-odd Schur complement of the right-block-Jacobi operator on every level, four levels
     128 -> 32 -> 8 -> 2) for a lock-step batch: prepare / Schur solve / reconstruct per system, inner tolerances per
-    system (coarse_tol |r| / |r_prep|), verified against the single-vector path system by system."""
+    system (coarse_tol |r| / |r_prep|), verified system by system against the same system solved alone as a batch of one."""
     gauge_file = os.path.join(golden_dir, "l128t128b60_heatbath.dat")
     out = subprocess.run([os.path.join(DRIVERS, "n19_wilson_kcycle_precond"), "128", "3", gauge_file, "128", "nrhs=3"], cwd=DRIVERS,
                          env=dict(os.environ, QMG_QUIET="1", QMG_MRHS_VERIFY="1"), capture_output=True, text=True, timeout=150)
@@ -405,7 +405,7 @@ def test_coarsest_cg_on_the_original_hierarchy_matches_the_oracle(golden_dir, ct
 def test_batched_right_jacobi_solves_follow_the_single_solves(golden_dir):
     """Three systems in lock step with the outer solve, every level and the coarsest solve on the RIGHT_JACOBI operator and CGNE smoothers (n19 counterpart,
     QMG_SOLVE_TYPE=jacobi, nrhs=3): each system converges, is reconstructed (x = C^-1 y) to a true residual <= 1e-7 against the ORIGINAL operator, and matches its
-    single-vector solve (QMG_MRHS_VERIFY: iteration counts within 1, solutions to 1e-6)."""
+    solve alone as a batch of one (QMG_MRHS_VERIFY: iteration counts within 1, solutions to 1e-6)."""
     gauge_file = os.path.join(golden_dir, "l64t64b60_heatbath.dat")
     out = subprocess.run([os.path.join(DRIVERS, "n19_wilson_kcycle_precond"), "128", "2", gauge_file, "64", "nrhs=3"], cwd=DRIVERS,
                          env=dict(os.environ, QMG_QUIET="1", QMG_SOLVE_TYPE="jacobi", QMG_SMOOTHER="cgne", QMG_MRHS_VERIFY="1"), capture_output=True, text=True, timeout=300)

@@ -5,6 +5,8 @@ these drivers stay PARITY UNPINNED (quantum-linalg stores no outputs).
 
 Bar: iteration counts equal +-1 (bit-different reductions can move a stopping decision by one step; BiCGStab-L: one sweep of
 L), solutions equal to 1e-7 relative (both solve to <= 1e-9), fixed-iteration runs (MR, Richardson) equal to 1e-12.
+Every driver but Richardson is a batch of one through the batch cores of krylov.hpp; the `*_x0` cases start BiCGStab-6, MR,
+GCR(8) and CG from a gaussian initial guess (r0 = b - A x0, that apply counted) and are held to the same bars.
 Also: CG driven from HOST vectors through apply_stencil_2D_host_thunk (the reference's matrix_op_cplx signature)."""
 import os
 import re
@@ -49,11 +51,18 @@ CASES = [  # name, oracle kind, operator, rhs file, max_iter, tol, param_i, para
 ]
 
 
-@pytest.mark.parametrize("name,kind,op,bfile,max_iter,tol,pi,pd,slack", CASES)
-def test_converging_drivers_match_the_oracle_twins(run, name, kind, op, bfile, max_iter, tol, pi, pd, slack):
+CASES_X0 = [  # name, oracle kind, operator, rhs file, initial-guess file, max_iter, tol, param_i, param_d, iteration slack
+    ("bicgstab6_x0", ol.KRYLOV_BICGSTAB_L, "wilson", "b_wilson", "x0_wilson", 500, 5e-5, 6, 0.0, 6),
+    ("gcr8_x0", ol.KRYLOV_GCR, "wilson", "b_wilson", "x0_wilson", 400, 1e-9, 8, 0.0, 1),
+    ("cg_laplace_x0", ol.KRYLOV_CG, "laplace", "b_laplace", "x0_laplace", 2000, 1e-10, 0, 0.0, 1),
+]
+
+
+def check_converging(run, name, kind, op, bfile, max_iter, tol, pi, pd, slack, x0file=None):
     rows, load, ops = run
     b = load(bfile)
-    conv, it, x, rsq, _ = ol.krylov_solve(kind, ops[op], b, max_iter, tol, param_i=pi, param_d=pd)
+    x0 = load(x0file) if x0file else None
+    conv, it, x, rsq, _ = ol.krylov_solve(kind, ops[op], b, max_iter, tol, param_i=pi, param_d=pd, x0=x0)
     g_ok, g_it, g_ops, g_rel = rows[name]
     assert bool(g_ok) == conv
     assert abs(g_it - it) <= slack, (name, g_it, it)
@@ -61,6 +70,16 @@ def test_converging_drivers_match_the_oracle_twins(run, name, kind, op, bfile, m
     true = np.linalg.norm(b - ol.stencil_apply(ops[op], xg)) / np.linalg.norm(b)    # the GPU solution against the ORACLE's operator
     assert true <= 1.5 * max(tol, 1e-12) or not conv
     assert cs.rel_l2(xg, x) < (1e-3 if tol > 1e-6 else 1e-7), (name, cs.rel_l2(xg, x))
+
+
+@pytest.mark.parametrize("name,kind,op,bfile,max_iter,tol,pi,pd,slack", CASES)
+def test_converging_drivers_match_the_oracle_twins(run, name, kind, op, bfile, max_iter, tol, pi, pd, slack):
+    check_converging(run, name, kind, op, bfile, max_iter, tol, pi, pd, slack)
+
+
+@pytest.mark.parametrize("name,kind,op,bfile,x0file,max_iter,tol,pi,pd,slack", CASES_X0)
+def test_converging_drivers_from_an_initial_guess_match_the_oracle_twins(run, name, kind, op, bfile, x0file, max_iter, tol, pi, pd, slack):
+    check_converging(run, name, kind, op, bfile, max_iter, tol, pi, pd, slack, x0file)
 
 
 def test_fixed_iteration_drivers_match_exactly(run):
@@ -72,6 +91,15 @@ def test_fixed_iteration_drivers_match_exactly(run):
     _, it, x, rsq, _ = ol.krylov_solve(ol.KRYLOV_RICHARDSON, ops["wilson"], b, 10, 1e-10, param_i=250, param_d=0.33)
     assert rows["richardson"][1] == it == 10 and rows["richardson"][0] == 0 and cs.rel_l2(load("x_richardson"), x) < 1e-12
     assert abs(rows["richardson"][3] - np.sqrt(rsq) / np.linalg.norm(b)) < 1e-10
+
+
+def test_mr_from_an_initial_guess_matches_exactly(run):
+    rows, load, ops = run
+    b = load("b_wilson")
+    _, it, x, rsq, _ = ol.krylov_solve(ol.KRYLOV_MR, ops["wilson"], b, 6, 1e-30, param_d=0.85, x0=load("x0_wilson"))
+    assert rows["mr_x0"][1] == it == 6 and cs.rel_l2(load("x_mr_x0"), x) < 1e-12
+    assert abs(rows["mr_x0"][3] - np.sqrt(rsq) / np.linalg.norm(b)) < 1e-10
+    assert rows["mr_x0"][2] == 1 + it                                                      # the opening A x0 counts
 
 
 def test_cg_on_the_normal_operator_matches(run):
