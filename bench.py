@@ -4,19 +4,24 @@
 A "step" is one pass of the hot path over one synthetic right-hand side:
     apply_stencil_2D_M  (stencil/stencil_2d.h:2571-2576)  ==  lhs = (clover + hopping + shift) rhs
 on the L x L even-odd lattice, Wilson nc = 2 (2 spin components over a U(1) gauge field), fp64.
-Default workload: L = 4096 (the north-star target); the 2048^2 configuration is timed as well and
-reported under "also".  Inputs are resident in HBM before the timed region.
+Default workload: L = 4096 (the north-star target).  Inputs are resident in HBM before the timed region.
 
 Multi-GPU: independent right-hand sides, one per rank, every rank holding a replica of the stencil
 (SURVEY 8e).  The apply has no exchange step, so there is no data-path collective: weak scaling,
 `value` = (sites processed by all ranks) * 176 flop / max-over-ranks time.
 
-The JSON line also carries
+A plain run does only what the headline needs: set up, warm up, time the steps, write the outputs
+(`--dump-outputs`), print the JSON line.  Besides the headline that line carries
   roofline     -- ALGORITHMIC bytes per launch (384 B/site: five 2x2 matrices + rhs + lhs)
                   / average launch duration measured live with HIP events on the launch stream,
-                  against the 8 TB/s HBM3E peak;
+                  against the 8 TB/s HBM3E peak (from the timed steps themselves).
+`--full` adds everything that takes runs of its own (`--no-also`, `--no-kcycle`, `--no-cpu-baseline` trim it):
+  parity_gate_rel_l2 -- the workload at full size against the CPU oracle (through periodicity);
+  also*        -- the 2048^2 configuration, fp32 / 16-bit matrices / from the links, staggered 8 rhs,
+                  the K-cycle drivers, the y-slab solves; with N > 1 the RCCL collective proof and the
+                  staggered all-reduce step;
   cpu_baseline -- the reference-structured CPU oracle (kind "port", 1 thread) timed on this box's host
-                  cores on a bounded sample (rank 0, N = 1 only).
+                  cores on a bounded sample (rank 0, N = 1 only), and on all of them.
 
 `--dump-outputs DIR` writes what the last timed step computed to DIR/*.npy (dump_outputs) for output-for-output
 comparison of two builds; the inputs depend on the arguments only (committed fixture, seeded device generator).
@@ -802,9 +807,11 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--L", type=int, default=4096)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-also", action="store_true")
-    ap.add_argument("--no-kcycle", action="store_true")
+    ap.add_argument("--full", action="store_true", help="beyond the headline: parity gates against the CPU oracle, the other sizes, precisions "
+                                                       "and configurations (also*), the K-cycle and slab drivers, the CPU baselines")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
+    ap.add_argument("--no-also", action="store_true", help="--full without the also* legs")
+    ap.add_argument("--no-kcycle", action="store_true", help="--full without the K-cycle drivers")
     ap.add_argument("--workload", choices=["wilson", "staggered", "kcycle"], default="wilson",
                     help="wilson: the headline fine Wilson apply (default); staggered: BASELINE configs[3], 8 rhs per GPU + one all-reduce per step; "
                          "kcycle: BASELINE configs[2] K-cycle, --nrhs independent systems per GPU in lock step, right-hand sides sharded over ranks (no collective)")
@@ -854,6 +861,17 @@ def main():
     fixture = os.path.join(ROOT, "tests", "golden", "l64t64b60_heatbath.dat")
     L = args.L
     sharding = importlib.import_module("quantum-mg_amd.sharding")
+
+    def gate_or_first_launch(wl):
+        """--full: the parity gate, which launches the step once on its probe vector.  Otherwise that one untimed launch on
+        the workload's own inputs (it loads the step's code object), so that the warm-up and timed steps start as they do in
+        a --full run.  Returns the gate's error, or None."""
+        if args.full:
+            return wl.parity_gate(fixture)
+        wl.step()
+        qmg.sync()
+        return None
+
     if args.workload == "kcycle":
         # every rank runs the batched n13 driver on its own GPU (the child takes LOCAL_RANK for the device and RANK for its
         # share of the right-hand sides); one step = one complete solve of the rank's batch; setup is outside the rate
@@ -895,7 +913,7 @@ def main():
         return
     if args.workload == "staggered":
         wl = StaggeredMultiRHS(qmg, L, fixture, 1337 + rank, args.nrhs, rank, world, dist, torch)
-        gate_err = wl.parity_gate(fixture)
+        gate_err = gate_or_first_launch(wl)
         wall, kern_ms = timed(qmg, wl, args.steps, args.warmup, barrier)
         dumped = dump_outputs(args.dump_outputs, {"lhs": wl.lhs.to_host(), "norms": wl.norms.cpu().numpy()}, rank, world) if args.dump_outputs else None
         wall = sharding.max_over_ranks(wall, dist, "cuda")
@@ -908,8 +926,9 @@ def main():
                "roofline": {"bound": "hbm", "achieved": wl.bytes_per_site_rhs * sites_rhs / (kern_ms * 1e-3) / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                             "frac": wl.bytes_per_site_rhs * sites_rhs / (kern_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, "traffic": None,
                             "kernel": "k_stencil_pair<double,1,2,NORM,PF> (nrhs loop, fused norms) + k_apply_norm_final",
-                            "note": "whole step in one pass: apply with fused per-RHS norms, 64/nrhs + 32 B/site/rhs (a separate norm2sq would re-read 16)"},
-               "parity_gate_rel_l2": gate_err}
+                            "note": "whole step in one pass: apply with fused per-RHS norms, 64/nrhs + 32 B/site/rhs (a separate norm2sq would re-read 16)"}}
+        if gate_err is not None:
+            out["parity_gate_rel_l2"] = gate_err
         if dumped:
             out["dump_outputs"] = dumped
         if rank == 0:
@@ -919,7 +938,7 @@ def main():
             dist.destroy_process_group()
         return
     wl = Workload(qmg, L, fixture, seed=1337 + rank)
-    gate_err = wl.parity_gate(fixture)
+    gate_err = gate_or_first_launch(wl)
     wall, kern_ms = timed(qmg, wl, args.steps, args.warmup, barrier)
     dumped = dump_outputs(args.dump_outputs, {"lhs": wl.lhs.to_host()}, rank, world) if args.dump_outputs else None
 
@@ -938,8 +957,9 @@ def main():
                      "traffic": None, "kernel": "k_stencil_pair<double,2,2>", "algorithmic_bytes_per_launch": BYTES_PER_SITE * sites,
                      "avg_launch_ms": kern_ms},
         "hbm_gb_per_s_aggregate": world * BYTES_PER_SITE * sites * args.steps / wall / 1e9,
-        "parity_gate_rel_l2": gate_err,
     }
+    if gate_err is not None:
+        out["parity_gate_rel_l2"] = gate_err
     if dumped:
         out["dump_outputs"] = dumped
     # HBM traffic per launch from the committed rocprofv3 PMC passes of this same command (profiles/), collected separately
@@ -947,14 +967,15 @@ def main():
     out["roofline"]["traffic"], out["roofline"]["traffic_source"] = pmc_traffic(L)
     wl.free()
 
-    if world > 1 and dist is not None:
+    also = args.full and not args.no_also
+    if args.full and world > 1 and dist is not None:
         # (i) proof that `world` ranks met in a real RCCL collective; (ii) BASELINE configs[3]'s step on every rank: 8 right-hand sides
         # per GPU, per-RHS norms from the apply pass, ONE all-reduce of world x 8 doubles per step (north_star: "a single RCCL all-reduce
         # per global reduction over xGMI") -- the default workload above has no collective by construction
         ones = torch.ones(1, dtype=torch.float64, device="cuda")
         dist.all_reduce(ones)
         out["collective"] = {"backend": dist.get_backend(), "is_rccl": True, "group_world_size": dist.get_world_size(), "ranks_seen_by_allreduce": int(ones.item())}
-        if not args.no_also:
+        if also:
             swl = StaggeredMultiRHS(qmg, 4096, fixture, 1337 + rank, 8, rank, world, dist, torch)
             sgate = swl.parity_gate(fixture)
             ssteps = max(10, args.steps // 4)
@@ -970,7 +991,7 @@ def main():
                 "every_rank_sees_every_norm": bool((norms_host > 0).all()) and len(norms_host) == 8 * world}
             swl.free()
 
-    if rank == 0 and world == 1 and not args.no_also and L != 2048:
+    if rank == 0 and world == 1 and also and L != 2048:
         wl2 = Workload(qmg, 2048, fixture, seed=1337)
         e2 = wl2.parity_gate(fixture)
         # one discarded pass first (the first pass after freeing the 4096^2 workload's 6.5 GB occasionally carries a one-off
@@ -984,12 +1005,12 @@ def main():
                        "note": "working set 1.6 GB; the 128 MiB vectors partly live in the 256 MiB Infinity Cache"}
         wl2.free()
 
-    if rank == 0 and world == 1 and not args.no_also:
+    if rank == 0 and world == 1 and also:
         out["also_f32"] = f32_fine_apply(qmg, L, fixture, args.steps, args.warmup, barrier)
         out["also_wilson_from_links"] = wilson_from_links(qmg, L, fixture, args.steps, args.warmup, barrier)
         out["also_staggered_8rhs"] = staggered_8rhs(qmg, 4096, fixture, max(10, args.steps // 4), args.warmup, barrier, torch)
 
-    if rank == 0 and world == 1 and not args.no_also and not args.no_kcycle:
+    if rank == 0 and world == 1 and also and not args.no_kcycle:
         out["also_kcycle"] = kcycle_c3()
         out["also_kcycle"]["cpu_reference_same_system"] = kcycle_cpu_reference()
         out["also_kcycle_c5_schur"] = kcycle_c5_schur_and_f32()
@@ -1009,7 +1030,7 @@ def main():
         out["also_kcycle"]["fp32_kcycle_16bit_storage"] = h1
         out["also_kcycle_c5_shape"] = kcycle_c5_shape()
 
-    if not args.no_also:   # every rank takes part: the slabs of one lattice
+    if also:   # every rank takes part: the slabs of one lattice
         def everyone_ok(res):   # a leg that failed on ANY rank ends the slab legs for all ranks (the next leg's children would only wait for each other)
             good = 1.0 if (res is not None and "error" not in res) else 0.0
             if dist is not None:
@@ -1038,7 +1059,7 @@ def main():
             if not go_on:
                 out["also_slab_note"] = "a slab leg failed on some rank; the remaining slab legs were skipped"
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(fixture)
         out["cpu_baseline_all_cores"] = cpu_baseline_all_cores()
 

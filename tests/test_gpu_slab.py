@@ -6,7 +6,7 @@ single-domain apply BIT FOR BIT (the per-site arithmetic is the same code).  One
 these tests live in one process and the "exchange" between different slabs is done by the test; the library's own exchange
 is exercised on one rank (device copies = the periodic wrap) and through a real one-rank RCCL communicator
 (QMG_COMM_FORCE_RCCL: ncclSend / ncclRecv to self inside a group, and the all-reduce of the distributed reductions).
-More ranks need more GPUs: the driver's multi-GPU bench runs `also_slab_solve` (bench.py) on them."""
+More ranks need more GPUs: the driver's multi-GPU bench runs `also_slab_solve` (bench.py --full) on them."""
 import importlib
 
 import numpy as np

@@ -39,7 +39,7 @@ echo mrhs done
 python tools/xfer_bench.py > $O/${TAG}_xfer_bench.txt 2>&1
 python tools/kernelc_bench.py > $O/${TAG}_kernelC_multi_rhs.txt 2>&1
 echo xfer done
-python bench.py > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err
+python bench.py --full > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err
 echo bench done
 python -c "
 import json
