@@ -332,6 +332,22 @@ int qmg_batch_mr_dots_t(int dtype, const void* r, const void* p, size_t n, int n
 int qmg_batch_mr_update_t(int dtype, double omega, void* x, const void* r_in, void* r_out, const void* p, int x_set, size_t n, int nrhs,
                           size_t stride, unsigned mask, void* stream);
 int qmg_batch_mr_read_dots(double* out_host, int nrhs, void* stream);
+/* ONE basis V shared by every system of a batch (coarsest-level deflation and its Lanczos eigensolver, include/qmg/eigen.hpp):
+ * nv <= 128 vectors of n elements, vector j at V + j * ldv (ldv >= n), storage dtype as V's and B's; systems as in the batch entry
+ * points (nrhs <= 16, stride, mask).  Coefficient arrays are indexed [(k * nv + j) * 2 + {0,1}] (system k, basis vector j).
+ * Every call reads each element of V once and each element of B once; fp64 accumulation for both storage types.  Under
+ * distributed reductions (y-slabs) the entry points return QMG_ERR_UNSUPPORTED.
+ *   qmg_basis_dot_t      C[k][j] = <v_j, b_k> for the active systems (deterministic two-stage reduction: the same bits run to run);
+ *                        out_on_device: `out` is device memory and the call does not synchronise, else host memory (returns with them there).
+ *   qmg_basis_update_t   b_k += sum_j C[k][j] v_j; coeffs in device memory (coeffs_on_device) or host memory.
+ *   qmg_batch_deflate_t  e_k = sum_j v_j <v_j, b_k> inv_lambda[j] (e overwritten; inv_lambda: nv doubles in device memory): the dot,
+ *                        a device-side final reduce-and-scale and the update in stream order; nothing synchronises. */
+int qmg_basis_dot_t(int dtype, const void* V, int nv, size_t ldv, const void* B, size_t n, int nrhs, size_t stride, unsigned mask,
+                    double* out, int out_on_device, void* stream);
+int qmg_basis_update_t(int dtype, const double* coeffs, int coeffs_on_device, const void* V, int nv, size_t ldv, void* B, size_t n,
+                       int nrhs, size_t stride, unsigned mask, void* stream);
+int qmg_batch_deflate_t(int dtype, const void* V, int nv, size_t ldv, const double* inv_lambda, const void* B, void* E, size_t n,
+                        int nrhs, size_t stride, unsigned mask, void* stream);
 int qmg_prolong_batch_t(int dtype, const void* nullvecs, int nvec, const void* coarse, void* fine, int fLx, int fLy, int fnc,
                         int cLx, int cLy, int cnc, int nrhs, size_t cstride, size_t fstride, unsigned mask, void* stream);
 int qmg_restrict_batch_t(int dtype, const void* nullvecs, int nvec, const void* fine, void* coarse, int fLx, int fLy, int fnc,

@@ -49,6 +49,7 @@ ABI_SYMBOLS = [
     "qmg_convert_to_c16", "qmg_convert_from_c16", "qmg_stencil_apply_h16", "qmg_stencil_apply_mat16_t", "qmg_stencil_apply_norm2",
     "qmg_wilson_apply_direct", "qmg_wilson_hops_direct", "qmg_halo_exchange", "qmg_halo_exchange_parity", "qmg_stencil_apply_slab", "qmg_wilson_fill_slab", "qmg_comm_set_distributed_reductions", "qmg_coarse_build_slab", "qmg_gaussian_slab", "qmg_rb_hopping_slab", "qmg_build_dagger_slab", "qmg_staggered_fill_slab", "qmg_laplace_fill_slab", "qmg_comm_emulate_begin", "qmg_comm_emulate_attach", "qmg_comm_emulate_end",
     "qmg_stencil_apply_epi_t", "qmg_wilson_apply_direct_epi", "qmg_wilson_hops_direct_epi", "qmg_batch_mr_dots_t", "qmg_batch_mr_update_t", "qmg_batch_mr_read_dots",
+    "qmg_basis_dot_t", "qmg_basis_update_t", "qmg_batch_deflate_t",
     "qmg_u1_heatbath_noncompact", "qmg_u1_phase_to_gauge", "qmg_u1_gauge_to_phase", "qmg_u1_plaquette", "qmg_u1_noncompact_action",
 ]
 
@@ -568,6 +569,36 @@ def batch_multidot_t(dtype, xs, y, n, nrhs, stride, mask):
     check(lib().qmg_batch_multidot_t(dtype, ptrs, nj, _vp(y), C.c_size_t(n), nrhs, C.c_size_t(stride), C.c_uint(mask), out.ctypes.data_as(C.POINTER(C.c_double)), None),
           "qmg_batch_multidot_t")
     return (out[0::2] + 1j * out[1::2]).reshape(nrhs, nj)
+
+
+def basis_dot_t(dtype, V, nv, ldv, B, n, nrhs, stride, mask, out_dev=None):
+    """C[k][j] = <v_j, b_k> for one basis V shared by the batch (qmg_basis_dot_t); (nrhs, nv) complex array, NaN for inactive systems.
+    out_dev: a DeviceArray of nrhs * nv complex128 to receive them on the device instead (returns None)."""
+    if out_dev is not None:
+        check(lib().qmg_basis_dot_t(dtype, _vp(V), nv, C.c_size_t(ldv), _vp(B), C.c_size_t(n), nrhs, C.c_size_t(stride), C.c_uint(mask),
+                                    C.cast(C.c_void_p(out_dev.ptr), C.POINTER(C.c_double)), 1, None), "qmg_basis_dot_t")
+        return None
+    out = np.full(2 * nrhs * nv, np.nan)
+    check(lib().qmg_basis_dot_t(dtype, _vp(V), nv, C.c_size_t(ldv), _vp(B), C.c_size_t(n), nrhs, C.c_size_t(stride), C.c_uint(mask),
+                                out.ctypes.data_as(C.POINTER(C.c_double)), 0, None), "qmg_basis_dot_t")
+    return (out[0::2] + 1j * out[1::2]).reshape(nrhs, nv)
+
+
+def basis_update_t(dtype, coeffs, V, nv, ldv, B, n, nrhs, stride, mask):
+    """b_k += sum_j C[k][j] v_j (qmg_basis_update_t); coeffs: (nrhs, nv) complex on the host, or a DeviceArray of them"""
+    if isinstance(coeffs, DeviceArray):
+        cp, dev = C.cast(C.c_void_p(coeffs.ptr), C.POINTER(C.c_double)), 1
+    else:
+        cf = np.ascontiguousarray(np.asarray(coeffs, dtype=np.complex128).reshape(nrhs, nv)).view(np.float64)
+        cp, dev = cf.ctypes.data_as(C.POINTER(C.c_double)), 0
+    check(lib().qmg_basis_update_t(dtype, cp, dev, _vp(V), nv, C.c_size_t(ldv), _vp(B), C.c_size_t(n), nrhs, C.c_size_t(stride), C.c_uint(mask), None),
+          "qmg_basis_update_t")
+
+
+def batch_deflate_t(dtype, V, nv, ldv, inv_lambda_dev, B, E, n, nrhs, stride, mask):
+    """e_k = sum_j v_j <v_j, b_k> inv_lambda[j] (qmg_batch_deflate_t); inv_lambda_dev: a DeviceArray of nv float64"""
+    check(lib().qmg_batch_deflate_t(dtype, _vp(V), nv, C.c_size_t(ldv), C.cast(C.c_void_p(inv_lambda_dev.ptr), C.POINTER(C.c_double)), _vp(B), _vp(E),
+                                    C.c_size_t(n), nrhs, C.c_size_t(stride), C.c_uint(mask), None), "qmg_batch_deflate_t")
 
 
 def prolong_batch_t(dtype, nullvecs, nvec, coarse, fine, fdims, cdims, nrhs, cstride, fstride, mask):

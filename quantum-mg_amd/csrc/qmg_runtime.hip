@@ -91,6 +91,7 @@ int qmg_shutdown(void) {
   release_blas_workspace();
   release_batch_workspace();
   release_stencil_workspace();
+  release_deflate_workspace();
   QMG_HIP_CHECK(hipDeviceSynchronize());
   return QMG_SUCCESS;
 }

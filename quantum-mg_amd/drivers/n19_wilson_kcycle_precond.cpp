@@ -23,6 +23,7 @@
 #include "../include/qmg/qmg.hpp"
 #include "driver_common.hpp"
 #include "mrhs_solve.hpp"
+#include "deflate_hook.hpp"
 
 using namespace std;
 
@@ -155,6 +156,8 @@ static int run(int rank, int world, int device, bool slab_mode, int argc, char**
     cout << "[QMG-SETUP]: level " << i << " = " << curr_x_len << "x" << curr_y_len << " nc " << coarse_dof << " built from the rbjacobi stencil\n";
   }
 
+  deflate_from_env(mg_object, dump_dir, root);   // QMG_DEFLATE (deflate_hook.hpp)
+
   matrix_op_cplx apply_stencil_op = Stencil2D::get_apply_function(solve_type);
   const int solve_size = (solve_type == QMG_MATVEC_RIGHT_SCHUR) ? lats[0]->get_size_cv() / 2 : lats[0]->get_size_cv();   // n19:300
   if (solve_type != QMG_MATVEC_RIGHT_SCHUR || coarsest_type != solve_type || cgne)
@@ -197,6 +200,11 @@ static int run(int rank, int world, int device, bool slab_mode, int argc, char**
     if (f) { fwrite(hx.data(), sizeof(complex<double>), n, f); fclose(f); }
   }
   if (slab_mode) { const double xn = norm2sq(x_reconstruct, lats[0]->get_size_cv_l()); cout << setprecision(15) << "[QMG-SLAB]: world " << world << " ; |b| " << bnorm << " ; |x|^2 " << xn << "\n" << setprecision(20); }
+  if (deflate_hook_on() && root)   // (the coarsest solve's applies per level: only with the deflation hook, whose effect they show)
+    for (int i = 0; i <= n_refine; i++)
+      cout << "[QMG-OPS-STATS]: Level " << i << " NullVec " << mg_object->get_tracker_count(QMG_DSLASH_TYPE_NULLVEC, i) << " PreSmooth "
+           << mg_object->get_tracker_count(QMG_DSLASH_TYPE_PRESMOOTH, i) << " Krylov " << mg_object->get_tracker_count(QMG_DSLASH_TYPE_KRYLOV, i)
+           << " PostSmooth " << mg_object->get_tracker_count(QMG_DSLASH_TYPE_POSTSMOOTH, i) << " Total " << mg_object->get_total_count(i) << "\n";
   cout << setprecision(6) << "[QMG-TIMING]: solve " << solve_s << " s ; outer iterations/s " << invif.iter / solve_s << "\n";
   mg_object->check_in(b_prep, 0); mg_object->check_in(x_reconstruct, 0); mg_object->check_in(Ax, 0); mg_object->check_in(x, 0); mg_object->check_in(b, 0);
 

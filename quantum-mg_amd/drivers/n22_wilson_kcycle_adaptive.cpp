@@ -38,6 +38,7 @@
 #include "../include/qmg/qmg.hpp"
 #include "driver_common.hpp"
 #include "mrhs_solve.hpp"
+#include "deflate_hook.hpp"
 
 #include <vector>
 
@@ -327,6 +328,7 @@ static int run(int proc_rank, int proc_world, int local_rank, bool slab_mode, in
     level_solve_objs[i]->intermediate_iters = inner_max_iter;
     level_solve_objs[i]->intermediate_restart_freq = inner_restart_freq;
   }
+  deflate_from_env(mg_object, getenv("QMG_DUMP_DIR"), t_root);   // QMG_DEFLATE (deflate_hook.hpp): part of the setup
   qmg_stream_sync(qmg::current_stream());
   const double setup_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_setup0).count();
   if (mg_object->any_coarse_f16()) cout << "[QMG-INFO]: Galerkin matrices (and right-block-Jacobi hops) of the preconditioner levels are stored as complex<half> (QMG_COARSE_BITS=16; default 32, 64: fp64)\n";

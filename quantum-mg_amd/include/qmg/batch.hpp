@@ -16,7 +16,7 @@
 //
 // Scope: every configuration of stateful_multigrid.h:734-1060 -- fine_stencil_app in {ORIGINAL, RIGHT_JACOBI, RIGHT_SCHUR} with MR or CGNE
 // smoothers and flexible-GCR intermediate solves; coarsest_stencil_app one of those (GCR) or one of the four normal-equation operators
-// (CG, normal_shift).  A hierarchy whose types name a variant stencil that is not built is rejected loudly (BatchKcycle::supported), not emulated.
+// (CG, normal_shift, the deflated initial guess).  A hierarchy whose types name a variant stencil that is not built is rejected loudly (BatchKcycle::supported), not emulated.
 //
 // Storage precision: every type and function here is a template on the storage scalar T of the batch vectors (double |
 // float).  T = double is the engine described above.  T = float is the fp32 instantiation of the path (BASELINE
@@ -341,6 +341,7 @@ struct BatchKcycle {
     const int nl = mg->get_num_levels();
     for (int i = 0; i < nl; i++) if (!mg->get_stencil(i) || !mg->get_stencil(i)->enable_f32_shadow(i == 0 ? half_fine : half_coarse)) return false;
     for (int i = 0; i < nl - 1; i++) if (!mg->get_transfer(i)->enable_f32_shadow()) return false;
+    if (mg->get_coarsest_deflated() > 0 && !mg->deflation_basis_f32()) return false;   // the deflated guess of the coarsest solve
     return true;
   }
 };
@@ -451,8 +452,14 @@ inline void mg_preconditioner_batch(qmg::BatchT<T> lhs, qmg::BatchT<T> rhs, int 
   std::vector<inversion_info> cinv;
   if (level == total_num_levels - 2 && BatchOp::is_normal(coarse_type)) {   // CG on a normal-equation operator, shifted by normal_shift (:930-960)
     coarse_op.normal_shift = mg->get_coarsest_solve()->normal_shift; coarse_op.shift_length = coarse_size_solve;
+    // deflated initial guess e = sum_i v_i <v_i, b> / lambda_i (:893-907), formed on the device; CG then starts from it, and its opening
+    // r = b - A e is one more counted apply, as in the reference's minv_vector_cg with a nonzero guess
+    const void* basis = (mg->get_coarsest_solve()->deflate && mg->get_coarsest_deflated() > 0) ? (sizeof(T) == sizeof(float) ? mg->deflation_basis_f32() : mg->deflation_basis()) : 0;
+    if (basis)
+      qmg::ok(qmg_batch_deflate_t(qmg::dtype_of<T>::value, basis, (int)mg->get_coarsest_deflated(), coarse_size, mg->deflation_inv_lambda(), r_coarse_prep.p, e_coarse.p,
+                                  coarse_size_solve, nrhs, e_coarse.stride, mask, qmg::current_stream()), "qmg_batch_deflate");
     cinv = bcg_core<T>(e_coarse, r_coarse_prep, (int)coarse_size_solve, coarse_max_iter, coarse_tol, coarse_restart, apply_stencil_typed_batch<T>, (void*)&coarse_op,
-                       mask, true, &verb2, coarse_restart == -1 ? "CG" : "CG-restart", &inner_tol);
+                       mask, basis == 0, &verb2, coarse_restart == -1 ? "CG" : "CG-restart", &inner_tol);
   } else if (level == total_num_levels - 2) {
     cinv = bgcr_core<T>(e_coarse, r_coarse_prep, (int)coarse_size_solve, coarse_max_iter, coarse_tol, coarse_restart, apply_stencil_typed_batch<T>, (void*)&coarse_op,
                         (batch_precond_op_t<T>)0, 0, mask, true, &verb2, coarse_restart == -1 ? "GCR" : "GCR-restart", &inner_tol);

@@ -1,7 +1,7 @@
 // multigrid.hpp -- ArrayStorageMG, MultigridMG and StatefulMultigridMG (with the K-cycle
 // `mg_preconditioner`) on device vectors.  Reference: storage/array_storage.h:23-155,
-// multigrid/multigrid.h:54-600, multigrid/stateful_multigrid.h:43-1062.  ARPACK deflation
-// (stateful_multigrid.h:611-712) is out of scope (no ARPACK; the reference guards it with NO_ARPACK).
+// multigrid/multigrid.h:54-600, multigrid/stateful_multigrid.h:43-1062.  Coarsest-level deflation (stateful_multigrid.h:611-712,
+// 893-907) takes its eigenpairs from the GPU thick-restart Lanczos of eigen.hpp, not ARPACK (deflate_coarsest is defined there).
 #ifndef QMG_MULTIGRID_HPP
 #define QMG_MULTIGRID_HPP
 
@@ -285,17 +285,34 @@ class StatefulMultigridMG : public MultigridMG {
     }
   };
 
-  struct CoarsestSolveMG {   // :204-241 (the `deflate` member exists only with ARPACK)
+  struct CoarsestSolveMG {   // :204-241
     QMGStencilType coarsest_stencil_app;
     double coarsest_tol; int coarsest_iters; int coarsest_restart_freq;
+    bool deflate;   // deflate a normal-equation coarsest solve once deflate_coarsest has computed eigenpairs; ignored otherwise
     double normal_shift;
-    CoarsestSolveMG() : coarsest_stencil_app(QMG_MATVEC_ORIGINAL), coarsest_tol(1e-20), coarsest_iters(100000000), coarsest_restart_freq(32), normal_shift(0.0) {}
+    CoarsestSolveMG() : coarsest_stencil_app(QMG_MATVEC_ORIGINAL), coarsest_tol(1e-20), coarsest_iters(100000000), coarsest_restart_freq(32), deflate(true), normal_shift(0.0) {}
   };
 
  protected:
   vector<LevelSolveMG*> level_solve_list;
   vector<DslashTrackerMG*> dslash_tracker_list;
   CoarsestSolveMG* coarsest_solve;
+  // coarsest-level deflation (deflate_coarsest): nev eigenpairs of the coarsest normal operator; the eigenvectors are one contiguous
+  // device block (coarsest_evecs points into it), with 1 / lambda on the device and, for the fp32 K-cycle, a complex<float> copy
+  unsigned int coarsest_deflated;
+  complex<double>* coarsest_evals;
+  complex<double>** coarsest_evecs;
+  complex<double>* evec_block;
+  complex<float>* evec_block32;
+  double* inv_lambda_dev;
+  int deflate_restarts, deflate_applies;
+  void free_coarsest_deflation(const char* why) {
+    if (coarsest_deflated == 0 && coarsest_evals == 0 && coarsest_evecs == 0) return;
+    if (why) std::cout << "[QMG-INFO]: coarsest-level eigenpairs freed (" << why << ")\n";
+    delete[] coarsest_evals; delete[] coarsest_evecs;
+    deallocate_vector(&evec_block); deallocate_vector(&evec_block32); deallocate_vector(&inv_lambda_dev);
+    coarsest_evals = 0; coarsest_evecs = 0; coarsest_deflated = 0;
+  }
 
   static bool valid_fine_app(LevelSolveMG* s) {
     return s->fine_stencil_app == QMG_MATVEC_ORIGINAL || s->fine_stencil_app == QMG_MATVEC_RIGHT_JACOBI || s->fine_stencil_app == QMG_MATVEC_RIGHT_SCHUR;
@@ -303,10 +320,11 @@ class StatefulMultigridMG : public MultigridMG {
 
  public:
   StatefulMultigridMG(Lattice2D* in_lat, Stencil2D* in_stencil, CoarsestSolveMG* in_coarsest_solve)
-      : MultigridMG(in_lat, in_stencil), current_level(0), coarsest_solve(in_coarsest_solve) {
+      : MultigridMG(in_lat, in_stencil), current_level(0), coarsest_solve(in_coarsest_solve), coarsest_deflated(0), coarsest_evals(0), coarsest_evecs(0),
+        evec_block(0), evec_block32(0), inv_lambda_dev(0), deflate_restarts(0), deflate_applies(0) {
     dslash_tracker_list.push_back(new DslashTrackerMG());
   }
-  ~StatefulMultigridMG() { for (size_t i = 0; i < dslash_tracker_list.size(); i++) delete dslash_tracker_list[i]; }
+  ~StatefulMultigridMG() { free_coarsest_deflation(0); for (size_t i = 0; i < dslash_tracker_list.size(); i++) delete dslash_tracker_list[i]; }
   virtual bool coarse_f32_default() const { return true; }   // this hierarchy is a preconditioner (mg_preconditioner)
 
   void set_multigrid_level(int level) {
@@ -347,6 +365,7 @@ class StatefulMultigridMG : public MultigridMG {
     push_level(l, t, in_solve, false, false, QMG_MULTIGRID_PRECOND_ORIGINAL, CoarseOperator2D::QMG_COARSE_BUILD_ORIGINAL, nvecs);
   }
   void pop_level() {
+    free_coarsest_deflation("the coarsest level was popped");
     level_solve_list.pop_back();
     delete dslash_tracker_list.back();
     dslash_tracker_list.pop_back();
@@ -354,6 +373,7 @@ class StatefulMultigridMG : public MultigridMG {
   }
   void update_level(int level, Lattice2D* l, TransferMG* t, LevelSolveMG* in_solve, bool build_stencil, bool is_chiral, QMGMultigridPrecondStencil from, CoarseOperator2D::QMGCoarseBuildStencil extra, complex<double>** nvecs = 0) {
     if (!valid_fine_app(in_solve)) { std::cout << "[QMG-ERROR]: In StatefulMultigridMG:;update_level, LevelSolveMG::fine_stencil_app should only be original, right jacobi, or schur.\n"; return; }
+    free_coarsest_deflation("a level was updated: the coarsest operator changes");
     MultigridMG::update_level(level, l, t, build_stencil, is_chiral, from, extra, nvecs);
     level_solve_list[level - 1] = in_solve;
   }
@@ -379,6 +399,19 @@ class StatefulMultigridMG : public MultigridMG {
     if (i == -1) { for (int j = 0; j < num_levels; j++) dslash_tracker_list[j]->reset_tracker(); }
     else if (in_range(i, "reset tracker")) dslash_tracker_list[i]->reset_tracker();
   }
+
+  // coarsest-level deflation (:611-712): the num_low lowest and num_high highest eigenpairs of the coarsest normal operator, by the
+  // thick-restart Lanczos of eigen.hpp (defined there); print_evals prints them as [QMG-COARSEST-EVALS] lines
+  void deflate_coarsest(int num_low, int num_high, bool print_evals = false);
+  unsigned int get_coarsest_deflated() { return coarsest_deflated; }
+  complex<double>* get_coarsest_evals() { return coarsest_evals; }
+  complex<double>** get_coarsest_evecs() { return coarsest_evecs; }
+  // not in the reference: what the K-cycle's deflated guess streams (qmg_batch_deflate_t) and what the eigensolver cost
+  const void* deflation_basis() { return evec_block; }
+  const void* deflation_basis_f32();
+  const double* deflation_inv_lambda() { return inv_lambda_dev; }
+  int get_deflation_restarts() { return deflate_restarts; }
+  int get_deflation_applies() { return deflate_applies; }
 
   // One K-cycle application, lhs ~= A^-1 rhs (stateful_multigrid.h:734-1060): mg_preconditioner_batch on a batch of one system,
   // defined at the end of batch.hpp.

@@ -11,6 +11,7 @@
 #include "krylov.hpp"
 #include "multigrid.hpp"
 #include "batch.hpp"
+#include "eigen.hpp"
 #include "u1.hpp"
 #include "reductions.hpp"
 #endif
