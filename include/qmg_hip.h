@@ -292,6 +292,18 @@ int qmg_batch_multi_caxpy_t(int dtype, const double* coeffs, const void* const* 
  * bit for bit qmg_batch_multi_caxpy_t, qmg_batch_blas_t(QMG_BOP_CAXPY), qmg_batch_blas_t(QMG_BOP_COPY) in that order.  w, r, z_next distinct. */
 int qmg_batch_gcr_update_t(int dtype, const double* coeffs, const void* const* ws, int nj, void* w, const double* a, void* r, void* z_next,
                            size_t n, int nrhs, size_t stride, unsigned mask, void* stream);
+/* The vector updates of one multi-shift CG iteration (quantum-linalg's minv_vector_cg_m; qmg/krylov.hpp: bcg_m_core) in ONE pass, for
+ * every shift s < ns (1 <= ns <= 16) and every system k of mask & shift_masks[s]:
+ *   x[s]_k += a[s][k] p[s]_k
+ *   p[s]_k  = z[s][k] r_k + c[s][k] p[s]_k
+ * xs, ps: tables of ns batch base pointers (as xs of qmg_batch_multi_caxpy_t); a, z, c: REAL coefficients, [s * nrhs + k] (CG on a
+ * Hermitian operator has no others).  shift_masks[s]: the systems that still iterate shift s; a (system, shift) pair outside it is
+ * neither read nor written, and a shift whose mask is 0 costs nothing.  r is read once per element for all shifts (once per 8 shifts
+ * when ns > 8): 1 + 2 ns vector reads and 2 ns writes per system instead of the 4 ns reads and 2 ns writes of the separate passes.
+ * bit for bit qmg_batch_blas_t(QMG_BOP_CAXPY) with (a, 0) on x[s], then qmg_batch_blas_t(QMG_BOP_CAXPBYZ) with (z, 0), (c, 0) on
+ * r, p[s] -> p[s].  The 2 ns vectors and r are distinct. */
+int qmg_batch_cgm_update_t(int dtype, const void* const* xs, const void* const* ps, int ns, const double* a, const double* z, const double* c,
+                           const unsigned* shift_masks, const void* r, size_t n, int nrhs, size_t stride, unsigned mask, void* stream);
 int qmg_batch_reduce_t(int dtype, int op, const void* x, const void* y, size_t n, int nrhs, size_t stride, unsigned mask,
                        double* out_host, void* stream);
 int qmg_batch_multidot_t(int dtype, const void* const* xs, int nj, const void* y, size_t n, int nrhs, size_t stride, unsigned mask,

@@ -179,6 +179,71 @@ __global__ __launch_bounds__(BLOCK) void k_bgcr_update(void* __restrict__ w_, co
   }
 }
 
+// Multi-shift CG's vector updates of one iteration in ONE pass (bcg_m_core): for every shift s that system k still iterates,
+//   x[s] += a[s] p[s] ;  p[s] = z[s] r + c[s] p[s]        (a, z, c real: the coefficients of CG on a Hermitian operator)
+// r is read once per element and serves every shift: 1 + 2 S reads and 2 S writes where the k_bblas passes (CAXPY on x[s], CAXPBYZ on r, p[s]) make
+// 4 S reads and 2 S writes.  Operation for operation those two passes with coefficients (a, 0), (z, 0), (c, 0) -- cmac / cmul with the zero imaginary
+// part kept, because dropping it changes the sign of a zero result -- so the same bits; the kernel is bound by its loads (64 bytes per shift and
+// element against 12 FMAs).  A (system, shift) pair that has converged is not in the system's list: neither read nor written.  Shifts are
+// taken CGM_CHUNK at a time, all 2 CGM_CHUNK loads of a chunk requested in storage form before the first is used (as bmulti_caxpy_run: 8 loads in flight).
+constexpr int CGM_J = 8;        // shifts per launch (the coefficient tables travel as kernel arguments)
+constexpr int CGM_CHUNK = 4;    // shifts per staged chunk
+struct BatchCgm {
+  void* x[CGM_J];
+  void* p[CGM_J];
+  double a[CGM_J][BATCH_MAX], z[CGM_J][BATCH_MAX], c[CGM_J][BATCH_MAX];
+  unsigned char na[BATCH_MAX];            // per system: how many of the launch's shifts it still iterates
+  unsigned char idx[BATCH_MAX][CGM_J];    // ... and which (slots of x / p / a / z / c)
+};
+template <typename T, int W, int NJ>
+__device__ __forceinline__ void bcgm_chunk(const BatchCgm& m, int k, int j0, long off, long i, const cplx (&rr)[W]) {
+  typedef typename CStore<T>::type ct;
+  typedef typename RawP<T, W>::type raw;
+  raw xr[NJ], pr[NJ];
+  int s[NJ];
+#pragma unroll
+  for (int j = 0; j < NJ; j++) {
+    s[j] = m.idx[k][j0 + j];
+    xr[j] = ld_rawp<T, W>(reinterpret_cast<const ct*>(m.x[s[j]]) + off, i);
+    pr[j] = ld_rawp<T, W>(reinterpret_cast<const ct*>(m.p[s[j]]) + off, i);
+  }
+#pragma unroll
+  for (int j = 0; j < NJ; j++) {
+    const cplx a = cmake(m.a[s[j]][k], 0.0), z = cmake(m.z[s[j]][k], 0.0), c = cmake(m.c[s[j]][k], 0.0);
+    cplx xv[W], pv[W], pn[W];
+    widen_rawp<T, W>(xr[j], xv);
+    widen_rawp<T, W>(pr[j], pv);
+#pragma unroll
+    for (int w = 0; w < W; w++) {
+      cmac(xv[w], a, pv[w]);                          // k_bblas<CAXPY>
+      pn[w] = cmul(z, rr[w]); cmac(pn[w], c, pv[w]);  // k_bblas<CAXPBYZ>
+    }
+    stc_pack<T, W>(reinterpret_cast<ct*>(m.x[s[j]]) + off, i, xv);
+    stc_pack<T, W>(reinterpret_cast<ct*>(m.p[s[j]]) + off, i, pn);
+  }
+}
+template <typename T, int W>
+__global__ __launch_bounds__(BLOCK) void k_bcgm_update(const BatchCgm m, const void* __restrict__ r_, const BatchIdx bi, long n, long stride) {
+  typedef typename CStore<T>::type ct;
+  const int k = bi.id[blockIdx.y];
+  const int na = m.na[k];
+  const long off = (long)k * stride;
+  const ct* rv = reinterpret_cast<const ct*>(r_) + off;
+  const long np = n / W;
+  for (long i = (long)blockIdx.x * BLOCK + threadIdx.x; i < np; i += (long)gridDim.x * BLOCK) {
+    cplx rr[W];
+    ldb<T, W>(rv, i, rr, bi.nt);
+    int j0 = 0;
+    for (; j0 + CGM_CHUNK <= na; j0 += CGM_CHUNK) bcgm_chunk<T, W, CGM_CHUNK>(m, k, j0, off, i, rr);
+    switch (na - j0) {
+      case 1: bcgm_chunk<T, W, 1>(m, k, j0, off, i, rr); break;
+      case 2: bcgm_chunk<T, W, 2>(m, k, j0, off, i, rr); break;
+      case 3: bcgm_chunk<T, W, 3>(m, k, j0, off, i, rr); break;
+      default: break;
+    }
+  }
+}
+
 // ---------------- reductions (two-stage, deterministic; fp64: partition identical to qmg_blas.hip) ----------------
 template <int NV>
 __device__ __forceinline__ void bblock_reduce_store(double* v, double* partial_out) {
@@ -584,6 +649,45 @@ int qmg_batch_gcr_update_t(int dtype, const double* coeffs, const void* const* w
   QMG_DISPATCH_TW(dtype, W, QMG_K);
 #undef QMG_K
   QMG_LAUNCH_CHECK();
+  return QMG_SUCCESS;
+}
+
+// x[s]_k += a[s][k] p[s]_k ; p[s]_k = z[s][k] r_k + c[s][k] p[s]_k for every shift s < ns and every system k of mask & shift_masks[s]: see k_bcgm_update.
+// a, z, c: [s * nrhs + k], real.  More than 8 shifts take one launch per 8 (r is read once per launch).
+int qmg_batch_cgm_update_t(int dtype, const void* const* xs, const void* const* ps, int ns, const double* a, const double* z, const double* c,
+                           const unsigned* shift_masks, const void* r, size_t n, int nrhs, size_t stride, unsigned mask, void* stream) {
+  if (!valid_dtype(dtype) || nrhs < 1 || nrhs > BATCH_MAX || ns < 1 || ns > BATCH_MAX || !xs || !ps || !a || !z || !c || !shift_masks || (!r && n)) return QMG_ERR_INVALID;
+  for (int s = 0; s < ns; s++) {
+    if (n && (!xs[s] || !ps[s] || xs[s] == r || ps[s] == r || xs[s] == ps[s])) return QMG_ERR_INVALID;
+    for (int t = 0; t < s; t++) if (n && (xs[s] == xs[t] || ps[s] == ps[t] || xs[s] == ps[t] || ps[s] == xs[t])) return QMG_ERR_INVALID;
+  }
+  if (n == 0) return QMG_SUCCESS;
+  int W = pack_width(dtype, n, stride, nrhs, {r});
+  for (int s = 0; s < ns; s++) if (dtype == QMG_C32 && (!aligned16(xs[s]) || !aligned16(ps[s]))) W = 1;
+  for (int s0 = 0; s0 < ns; s0 += CGM_J) {
+    const int sj = (ns - s0 < CGM_J) ? ns - s0 : CGM_J;
+    BatchCgm m;
+    memset(&m, 0, sizeof(m));
+    unsigned any = 0;
+    for (int j = 0; j < sj; j++) {
+      m.x[j] = const_cast<void*>(xs[s0 + j]);
+      m.p[j] = const_cast<void*>(ps[s0 + j]);
+      const unsigned act = mask & shift_masks[s0 + j];
+      any |= act;
+      for (int k = 0; k < nrhs; k++) {
+        m.a[j][k] = a[(size_t)(s0 + j) * nrhs + k]; m.z[j][k] = z[(size_t)(s0 + j) * nrhs + k]; m.c[j][k] = c[(size_t)(s0 + j) * nrhs + k];
+        if ((act >> k) & 1u) m.idx[k][m.na[k]++] = (unsigned char)j;
+      }
+    }
+    BatchIdx bi = expand_mask(any, nrhs);   // a system none of whose shifts is iterated any more launches no block
+    if (bi.n == 0) continue;
+    bi.nt = batch_nt(bi, n, dtype);
+    dim3 grid(grid_1d(n / W), (unsigned)bi.n);
+#define QMG_K(T, WW) k_bcgm_update<T, WW><<<grid, BLOCK, 0, as_stream(stream)>>>(m, r, bi, (long)n, (long)stride)
+    QMG_DISPATCH_TW(dtype, W, QMG_K);
+#undef QMG_K
+    QMG_LAUNCH_CHECK();
+  }
   return QMG_SUCCESS;
 }
 

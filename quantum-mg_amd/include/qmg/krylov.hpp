@@ -1,4 +1,4 @@
-// krylov.hpp -- the Krylov solvers, on device-resident vectors: MR(omega), CG (restarted or not), flexible GCR and BiCGStab(L).
+// krylov.hpp -- the Krylov solvers, on device-resident vectors: MR(omega), CG (restarted or not), multi-shift CG, flexible GCR and BiCGStab(L).
 //
 // The reference takes these from quantum-linalg (`inverters/generic_*.h`, absent; only the call sites
 // are known: stateful_multigrid.h:851-990,1037-1046, tests/n13_wilson_kcycle/wilson_kcycle.cpp:459-466,
@@ -11,8 +11,8 @@
 // All vectors are device pointers; every reduction is a two-stage device reduction whose result comes back
 // to the host because the control flow depends on it.
 //
-// Each method has ONE implementation, for a LOCK-STEP BATCH of up to 16 independent systems (bmr_core, bcg_core, bgcr_core,
-// bbicgstab_l_core): one launch per step for the whole batch, every scalar and every decision per system, and a system that
+// Each method has ONE implementation, for a LOCK-STEP BATCH of up to 16 independent systems (bmr_core, bcg_core, bcg_m_core,
+// bgcr_core, bbicgstab_l_core): one launch per step for the whole batch, every scalar and every decision per system, and a system that
 // converges is FROZEN (its bit leaves the active mask: no kernel reads or writes it) while the rest continue.  The reference-
 // named single-vector entry points (minv_vector_minres, minv_vector_cg, ..., minv_vector_bicgstab_l) run these cores on a
 // batch of one; only Richardson is single-vector code.  Every type and function of the batch layer is a template on the
@@ -22,6 +22,43 @@
 #define QMG_KRYLOV_HPP
 
 #include <cmath>
+
+namespace qmg {
+
+// ---------------------------------------------------------------------------------------------
+// The scalar recurrence of multi-shift CG (B. Jegerlehner, hep-lat/9612014), in CG's own notation.  CG on the base system
+// A0 = A + sigma_0 takes, in iteration n,  alpha_n = |r_n|^2 / <p_n, A0 p_n>,  x += alpha_n p_n,  r_{n+1} = r_n - alpha_n A0 p_n,
+// beta_n = |r_{n+1}|^2 / |r_n|^2,  p_{n+1} = r_{n+1} + beta_n p_n.  The residual of the system shifted by dsigma_s = sigma_s - sigma_0
+// stays collinear with the base residual, r^s_n = zeta^s_n r_n, as long as every x^s starts from zero, with
+//   zeta_{n+1} = zeta_n zeta_{n-1} alpha_{n-1} / ( alpha_n beta_{n-1} (zeta_{n-1} - zeta_n) + zeta_{n-1} alpha_{n-1} (1 + dsigma alpha_n) )
+//   alpha^s_n  = alpha_n zeta_{n+1} / zeta_n ,      beta^s_n = beta_n (zeta_{n+1} / zeta_n)^2
+// from zeta_{-1} = zeta_0 = 1, alpha_{-1} = 1, beta_{-1} = 0 (so zeta_1 = 1 / (1 + dsigma alpha_0), and the base shift keeps zeta = 1).
+// One call advances every shift of `active` (bit s) by one iteration and hands back the three coefficients of the fused vector update
+//   x^s += a[s] p^s ;  p^s = z[s] r_{n+1} + c[s] p^s        (a = alpha^s_n, z = zeta_{n+1}, c = beta^s_n)
+// zeta[s] / zeta_prev[s] hold zeta_n / zeta_{n-1} on entry and zeta_{n+1} / zeta_n on return.  A shift outside `active` is left alone:
+// its zeta keeps the value it froze at and its coefficients come back 0.  dsigma >= 0 makes 0 < zeta_{n+1} <= zeta_n: zeta only decays,
+// the faster the larger the shift, which is why a converged shift has to be frozen instead of iterated into underflow.
+// Host arithmetic only (tests/host/multishift_host.cpp compiles this header with QMG_KRYLOV_HOST_ONLY and no device code).
+// ---------------------------------------------------------------------------------------------
+inline void cgm_coefficients(int ns, const double* dsigma, unsigned active, double alpha, double beta, double alpha_prev, double beta_prev,
+                             double* zeta, double* zeta_prev, double* a, double* z, double* c) {
+  for (int s = 0; s < ns; s++) {
+    a[s] = z[s] = c[s] = 0.0;
+    if (!((active >> s) & 1u)) continue;
+    const double zn = zeta[s], zo = zeta_prev[s];
+    const double ratio = zo * alpha_prev / (alpha * beta_prev * (zo - zn) + zo * alpha_prev * (1.0 + dsigma[s] * alpha));   // zeta_{n+1} / zeta_n
+    zeta_prev[s] = zn;
+    zeta[s] = zn * ratio;
+    a[s] = alpha * ratio;
+    z[s] = zeta[s];
+    c[s] = beta * ratio * ratio;
+  }
+}
+
+}  // namespace qmg
+
+#ifndef QMG_KRYLOV_HOST_ONLY
+#include <algorithm>
 #include <iostream>
 #include <map>
 #include <string>
@@ -746,6 +783,134 @@ inline std::vector<inversion_info> bcg_core(qmg::BatchT<T> phi, qmg::BatchT<T> p
 }
 
 // ---------------------------------------------------------------------------------------------
+// Multi-shift CG (quantum-linalg's minv_vector_cg_m): (A + sigma_s) x[s]_k = b_k for every active system k and every shift s < S <= 16,
+// A Hermitian positive definite, sigma_s >= 0 in any order, from ZERO initial guesses (the shifted residuals must stay collinear;
+// a non-zero phi[s] is refused).  All S solutions are built in the Krylov space of the smallest shift sigma_0, on which the CG
+// recurrence is anchored: one apply of A per iteration on the active systems, <p, A p> and <p, p> from one multidot (A0 = A +
+// sigma_0 is never formed: <p, A0 p> = <p, A p> + sigma_0 <p, p>, and r -= alpha (A p + sigma_0 p) is one two-vector axpy), |r|^2,
+// the scalars of every shift from cgm_coefficients, and ONE qmg_batch_cgm_update_t for the 2 S vector updates.
+// Shift s of system k is frozen (leaves shift_masks[s]: neither read nor written again) when zeta_s |r_k| < eps |b_k|; that is the
+// recurrence residual of the shifted system, known from host scalars, so every shift is checked every iteration.  A system leaves
+// the mask when its smallest shift has converged (the larger ones have by then: zeta_s <= 1), at breakdown (<p, A0 p> == 0) or at
+// max_iter.  Returns inv[k * S + s]: iter = the iteration at which the shift froze, ops_count = the system's applies so far,
+// resSq = zeta_s^2 |r_k|^2.  phi[s]: the batch of solutions of shift s.
+// ---------------------------------------------------------------------------------------------
+template <typename T>
+inline std::vector<inversion_info> bcg_m_core(const std::vector<qmg::BatchT<T> >& phi, qmg::BatchT<T> phi0, int size, int max_iter, double eps,
+                                              const std::vector<double>& shifts, batch_matrix_op_t<T> matrix_vector, void* extra_info, unsigned mask,
+                                              inversion_verbose_struct* verb, const char* name = "CG-M") {
+  const int nrhs = phi0.nrhs, S = (int)shifts.size();
+  std::vector<inversion_info> inv((size_t)nrhs * (S > 0 ? S : 0));
+  for (auto& i : inv) i.name = name;
+  if (S < 1 || S > 16 || (int)phi.size() != S) { std::cout << "[QMG-ERROR]: " << name << ": takes 1 to 16 shifts and one solution batch per shift\n"; return inv; }
+  for (int s = 0; s < S; s++)
+    if (!phi[s].p || phi[s].stride != phi0.stride || phi[s].nrhs != nrhs) { std::cout << "[QMG-ERROR]: " << name << ": solution batch " << s << " does not have the layout of the right-hand sides\n"; return inv; }
+  int base = 0;
+  for (int s = 1; s < S; s++) if (shifts[s] < shifts[base]) base = s;
+  std::vector<double> dsigma(S);
+  for (int s = 0; s < S; s++) dsigma[s] = shifts[s] - shifts[base];
+  const double sigma0 = shifts[base];
+  if (sigma0 < 0.0) { std::cout << "[QMG-ERROR]: " << name << ": negative shift " << sigma0 << "\n"; return inv; }
+  for (int s = 0; s < S; s++) {
+    const std::vector<double> g = qmg::bnorm2sq(phi[s], size, mask);
+    for (int k = 0; k < nrhs; k++)
+      if (qmg::is_active(mask, k) && g[k] != 0.0) {
+        std::cout << "[QMG-ERROR]: " << name << ": non-zero initial guess (shift " << s << ", rhs " << k << "): multi-shift CG starts from zero\n";
+        return inv;
+      }
+  }
+  qmg::BatchPoolT<T> pool(phi0.stride, nrhs);
+  qmg::BatchT<T> r = pool.get(), Ap = pool.get();
+  std::vector<qmg::BatchT<T> > ps(S);
+  bool have = r.p && Ap.p;
+  for (int s = 0; s < S; s++) { ps[s] = pool.get(); have = have && ps[s].p; }
+  const std::vector<double> bsq = qmg::bnorm2sq(phi0, size, mask);
+  std::vector<double> rsq(bsq), bnorm(nrhs, 0.0), alpha_prev(nrhs, 1.0), beta_prev(nrhs, 0.0);
+  std::vector<std::vector<double> > zeta(nrhs, std::vector<double>(S, 1.0)), zeta_prev(zeta);
+  std::vector<int> its(nrhs, 0), ops(nrhs, 0);
+  std::vector<unsigned> live(nrhs, 0u);            // per system: the shifts it still iterates
+  std::vector<unsigned> shift_masks(S, 0u);        // per shift: the systems that still iterate it (the kernel's view of `live`)
+  unsigned act = 0;
+  if (!have && mask) std::cout << "[QMG-ERROR]: " << name << ": out of device memory for the CG work vectors\n";
+  for (int k = 0; k < nrhs; k++) {
+    if (!qmg::is_active(mask, k)) continue;
+    bnorm[k] = std::sqrt(bsq[k]);
+    for (int s = 0; s < S; s++) { inv[(size_t)k * S + s].success = (bnorm[k] == 0.0); inv[(size_t)k * S + s].resSq = bsq[k]; }
+    if (have && bnorm[k] > 0.0 && max_iter > 0) { act |= 1u << k; live[k] = qmg::full_mask(S); }
+  }
+  if (act) {
+    qmg::bcopy(r, phi0, size, act);
+    for (int s = 0; s < S; s++) qmg::bcopy(ps[s], phi0, size, act);
+  }
+  std::vector<qmg::BatchT<T> > dotv(2), axv(2);
+  std::vector<const void*> xtab(S), ptab(S);
+  for (int s = 0; s < S; s++) { xtab[s] = phi[s].p; ptab[s] = ps[s].p; }
+  std::vector<double> a((size_t)S * nrhs), z((size_t)S * nrhs), c((size_t)S * nrhs), as(S), zs(S), cs(S);
+  while (act) {
+    matrix_vector(Ap, ps[base], act, extra_info);
+    dotv[0] = Ap; dotv[1] = ps[base];
+    const std::vector<qmg::cvec> d = qmg::bmultidot(dotv, sigma0 != 0.0 ? 2 : 1, ps[base], size, act);   // <A p, p> (, <p, p>)
+    std::vector<double> alpha(nrhs, 0.0);
+    std::vector<qmg::cvec> rc(nrhs, qmg::cvec(2, 0.0));
+    unsigned upd = 0;
+    for (int k = 0; k < nrhs; k++) {
+      if (!qmg::is_active(act, k)) continue;
+      ops[k]++;
+      const double pAp = d[k][0].real() + (sigma0 != 0.0 ? sigma0 * d[k][1].real() : 0.0);
+      if (pAp == 0.0) { act &= ~(1u << k); continue; }   // breakdown: the system stops where it is
+      alpha[k] = rsq[k] / pAp;
+      rc[k][0] = -alpha[k]; rc[k][1] = -alpha[k] * sigma0;
+      upd |= 1u << k;
+    }
+    axv[0] = Ap; axv[1] = ps[base];
+    qmg::bmulti_caxpy(rc, axv, sigma0 != 0.0 ? 2 : 1, r, size, upd);   // r -= alpha (A p + sigma_0 p)
+    const std::vector<double> rn = qmg::bnorm2sq(r, size, upd);
+    std::fill(a.begin(), a.end(), 0.0); std::fill(z.begin(), z.end(), 0.0); std::fill(c.begin(), c.end(), 0.0);
+    std::fill(shift_masks.begin(), shift_masks.end(), 0u);
+    for (int k = 0; k < nrhs; k++) {
+      if (!qmg::is_active(upd, k)) continue;
+      const double beta = rn[k] / rsq[k];
+      qmg::cgm_coefficients(S, dsigma.data(), live[k], alpha[k], beta, alpha_prev[k], beta_prev[k], zeta[k].data(), zeta_prev[k].data(), as.data(), zs.data(), cs.data());
+      for (int s = 0; s < S; s++) {
+        if (!((live[k] >> s) & 1u)) continue;
+        a[(size_t)s * nrhs + k] = as[s]; z[(size_t)s * nrhs + k] = zs[s]; c[(size_t)s * nrhs + k] = cs[s];
+        shift_masks[s] |= 1u << k;
+      }
+      alpha_prev[k] = alpha[k]; beta_prev[k] = beta; rsq[k] = rn[k];
+    }
+    if (upd)
+      qmg::ok(qmg_batch_cgm_update_t(qmg::dtype_of<T>::value, xtab.data(), ptab.data(), S, a.data(), z.data(), c.data(), shift_masks.data(), r.p, size, nrhs,
+                                     r.stride, upd, qmg::current_stream()), "qmg_batch_cgm_update");
+    for (int k = 0; k < nrhs; k++) {
+      if (!qmg::is_active(upd, k)) continue;
+      its[k]++;
+      const double rnorm = std::sqrt(rsq[k]);
+      qmg::report(verb, name, nrhs, k, its[k], rnorm / bnorm[k]);
+      for (int s = 0; s < S; s++) {
+        if (!((live[k] >> s) & 1u)) continue;
+        inversion_info& o = inv[(size_t)k * S + s];
+        o.iter = its[k]; o.resSq = zeta[k][s] * zeta[k][s] * rsq[k];
+        if (std::fabs(zeta[k][s]) * rnorm < eps * bnorm[k]) { o.success = true; live[k] &= ~(1u << s); }
+      }
+      if (!((live[k] >> base) & 1u) || its[k] >= max_iter) act &= ~(1u << k);
+    }
+  }
+  for (int k = 0; k < nrhs; k++) {
+    if (!qmg::is_active(mask, k)) continue;
+    for (int s = 0; s < S; s++) {
+      inversion_info& o = inv[(size_t)k * S + s];
+      o.ops_count = ops[k];
+      if (verb && verb->verbosity != VERB_NONE) {
+        std::cout << verb->verb_prefix << name;
+        if (nrhs > 1) std::cout << " rhs " << k;
+        std::cout << " shift " << s << (o.success ? " Success " : " Fail ") << "Iter " << o.iter << " RelTol " << (bnorm[k] > 0 ? std::sqrt(o.resSq) / bnorm[k] : 0.0) << "\n";
+      }
+    }
+  }
+  return inv;
+}
+
+// ---------------------------------------------------------------------------------------------
 // The reference-named single-vector entry points: the cores above on a batch of one system, from the
 // initial guess in phi.  The opening r = b - A x0 counts in ops_count; the printed lines carry no system index.
 // ---------------------------------------------------------------------------------------------
@@ -790,6 +955,19 @@ inline inversion_info minv_vector_gcr_var_precond_restart(complex<double>* phi, 
   return bgcr_core<double>(qmg::Batch(phi, size, 1), qmg::Batch(phi0, size, 1), size, max_iter, eps, restart_freq, qmg::matrix_op1, &a, precond ? qmg::precond_op1 : 0, &m, 1u, false, verb,
                            "VPGCR-restart")[0];
 }
+// Multi-shift CG on one right-hand side: phi[s] = (A + shifts[s])^-1 phi0 for s < n_shift, every phi[s] zero on entry.  Argument order as
+// quantum-linalg's minv_vector_cg_m is recalled (PARITY UNPINNED like the rest: neither the library nor a call site is in the reference tree).
+// resid_freq_check and worst_first have no effect here: every shift's recurrence residual is checked in every iteration (host
+// scalars only), and the recurrence is always anchored on the smallest shift.  Returns one inversion_info per shift.
+inline std::vector<inversion_info> minv_vector_cg_m(complex<double>** phi, complex<double>* phi0, int n_shift, int size, int resid_freq_check, int max_iter,
+                                                    double eps, double* shifts, matrix_op_cplx matrix_vector, void* extra_info, bool worst_first = false,
+                                                    inversion_verbose_struct* verb = 0) {
+  (void)resid_freq_check; (void)worst_first;
+  qmg::MatrixOp1 a = {matrix_vector, extra_info};
+  std::vector<qmg::Batch> x;
+  for (int s = 0; s < n_shift; s++) x.push_back(qmg::Batch(phi[s], size, 1));
+  return bcg_m_core<double>(x, qmg::Batch(phi0, size, 1), size, max_iter, eps, std::vector<double>(shifts, shifts + (n_shift > 0 ? n_shift : 0)), qmg::matrix_op1, &a, 1u, verb);
+}
 // `iter` counts BiCG steps
 inline inversion_info minv_vector_bicgstab_l(complex<double>* phi, complex<double>* phi0, int size, int max_iter, double eps, int L,
                                              matrix_op_cplx matrix_vector, void* extra_info, inversion_verbose_struct* verb = 0) {
@@ -833,4 +1011,5 @@ inline inversion_info minv_vector_richardson(complex<double>* phi, complex<doubl
   return invif;
 }
 
+#endif  // QMG_KRYLOV_HOST_ONLY
 #endif

@@ -5,6 +5,7 @@
 #ifndef QMG_OPERATORS_HPP
 #define QMG_OPERATORS_HPP
 
+#include "krylov.hpp"
 #include "stencil2d.hpp"
 
 namespace qmg {
@@ -138,6 +139,36 @@ struct Staggered2D : public EoPrecNc1 {
   void prepare_b(complex<double>* b_new, complex<double>* b) { prepare_b_impl(b_new, b, shift); }                 // :190-202
   void apply_eo_prec_M(complex<double>* lhs, complex<double>* rhs) { apply_eo_prec_impl(lhs, rhs, shift); }       // m^2 - D_eo D_oe (:206-224)
   void reconstruct_x(complex<double>* x, complex<double>* b) { reconstruct_x_impl(x, b, shift); }                 // :228-240
+
+  // Every mass of a scan at once (not in the reference, whose drivers solve mass by mass): xs[i] = D(masses[i])^-1 b on the full lattice,
+  // b general (both parities).  With H = D(0), the anti-Hermitian hopping part, D(m)^-1 = (m - H) (m^2 - H^2)^-1 and -H^2 is Hermitian
+  // positive semi-definite and independent of the mass (block diagonal in parity: -D_eo D_oe on the even sites, -D_oe D_eo on the odd
+  // ones, the operator of apply_eo_prec_M for both parities).  So ONE multi-shift CG (minv_vector_cg_m) on A = -H^2 with the shifts
+  // m_i^2 gives every y_i = (m_i^2 - H^2)^-1 b for the operator applies of the lightest mass, and x_i = m_i y_i - H y_i costs one
+  // more hopping apply per mass.  Real masses > 0; xs[i] distinct device vectors, overwritten.  The object's shift, its built
+  // variants and every other method are untouched.  Returns one inversion_info per mass (iter: when that mass froze).
+  std::vector<inversion_info> solve_masses(complex<double>** xs, complex<double>* b, const double* masses, int n_mass, int max_iter, double eps,
+                                           inversion_verbose_struct* verb = 0) {
+    if (qmg::slab().on) { std::cout << "[QMG-ERROR]: Staggered2D::solve_masses does not run on y-slabs.\n"; return std::vector<inversion_info>((size_t)(n_mass > 0 ? n_mass : 0)); }
+    const long cv = lat->get_size_cv_l();
+    std::vector<double> sigma((size_t)(n_mass > 0 ? n_mass : 0));
+    for (int i = 0; i < n_mass; i++) { sigma[i] = masses[i] * masses[i]; zero_vector(xs[i], cv); }
+    std::vector<inversion_info> inv = minv_vector_cg_m(xs, b, n_mass, (int)cv, 1, max_iter, eps, sigma.data(), apply_minus_hop_sq, (void*)this, false, verb);
+    for (int i = 0; i < n_mass && i < (int)inv.size(); i++) {
+      if (!tmp_eo_space) tmp_eo_space = allocate_vector<complex<double>>(cv);
+      launch(QMG_P_HOPPING | QMG_P_ZERO, tmp_eo_space, xs[i], 0, hopping, 0.0, 0.0, 0.0);
+      caxpby(-1.0, tmp_eo_space, masses[i], xs[i], cv);
+    }
+    return inv;
+  }
+  static void apply_minus_hop_sq(complex<double>* lhs, complex<double>* rhs, void* self) {   // lhs = -H^2 rhs
+    Staggered2D* st = (Staggered2D*)self;
+    const long cv = st->lat->get_size_cv_l();
+    if (!st->tmp_eo_space) st->tmp_eo_space = allocate_vector<complex<double>>(cv);
+    st->launch(QMG_P_HOPPING | QMG_P_ZERO, st->tmp_eo_space, rhs, 0, st->hopping, 0.0, 0.0, 0.0);
+    st->launch(QMG_P_HOPPING | QMG_P_ZERO, lhs, st->tmp_eo_space, 0, st->hopping, 0.0, 0.0, 0.0);
+    cax(-1.0, lhs, cv);
+  }
 };
 inline void apply_eo_staggered_2D_M(complex<double>* lhs, complex<double>* rhs, void* extra_data) { ((Staggered2D*)extra_data)->apply_eo_prec_M(lhs, rhs); }
 
@@ -165,6 +196,22 @@ struct GaugedLaplace2D : public EoPrecNc1 {
   void prepare_b(complex<double>* b_new, complex<double>* b) { prepare_b_impl(b_new, b, 4.0 + shift); }             // :154-166
   void apply_eo_prec_M(complex<double>* lhs, complex<double>* rhs) { apply_eo_prec_impl(lhs, rhs, 4.0 + shift); }   // :170-188
   void reconstruct_x(complex<double>* x, complex<double>* b) { reconstruct_x_impl(x, b, 4.0 + shift); }             // :192-204
+
+  // Every m^2 of a scan at once: xs[i] = (Laplace + mass_sqs[i])^-1 b from ONE multi-shift CG (minv_vector_cg_m).  The operator at m^2 = 0
+  // is Hermitian positive (semi-)definite and m^2 is a multiple of the identity, so nothing is reconstructed.  mass_sqs[i] > 0, real.
+  // The object's shift, its built variants and every other method are untouched.
+  std::vector<inversion_info> solve_masses(complex<double>** xs, complex<double>* b, const double* mass_sqs, int n_mass, int max_iter, double eps,
+                                           inversion_verbose_struct* verb = 0) {
+    if (qmg::slab().on) { std::cout << "[QMG-ERROR]: GaugedLaplace2D::solve_masses does not run on y-slabs.\n"; return std::vector<inversion_info>((size_t)(n_mass > 0 ? n_mass : 0)); }
+    const long cv = lat->get_size_cv_l();
+    std::vector<double> sigma(mass_sqs, mass_sqs + (n_mass > 0 ? n_mass : 0));
+    for (int i = 0; i < n_mass; i++) zero_vector(xs[i], cv);
+    return minv_vector_cg_m(xs, b, n_mass, (int)cv, 1, max_iter, eps, sigma.data(), apply_massless, (void*)this, false, verb);
+  }
+  static void apply_massless(complex<double>* lhs, complex<double>* rhs, void* self) {   // lhs = (4 + hopping) rhs: the operator at m^2 = 0
+    GaugedLaplace2D* gl = (GaugedLaplace2D*)self;
+    gl->launch(QMG_P_CLOVER | QMG_P_HOPPING | QMG_P_ZERO, lhs, rhs, gl->clover, gl->hopping, 0.0, 0.0, 0.0);
+  }
 };
 inline void apply_eo_gauge_laplace_2D_M(complex<double>* lhs, complex<double>* rhs, void* extra_data) { ((GaugedLaplace2D*)extra_data)->apply_eo_prec_M(lhs, rhs); }
 
