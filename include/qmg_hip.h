@@ -166,6 +166,21 @@ int qmg_u1_gauge_to_phase(double* phase, const void* gauge, size_t n, void* stre
 /* out_host[0..1] = average plaquette (get_plaquette_u1, :424-462), out_host[2] = topological charge (get_topo_u1, :465-508) */
 int qmg_u1_plaquette(const void* gauge, int Lx, int Ly, double* out_host, void* stream);
 int qmg_u1_noncompact_action(const double* phase, int Lx, int Ly, double beta, double* out_host, void* stream);   /* :386-421 */
+/* Field tools (u1_utils.h:183-383, 545-603).  gauge: DEVICE complex<double>[2 Lx Ly] as above; trans: a DEVICE complex<double>[Lx Ly]
+ * nc = 1 colour vector; all asynchronous on `stream`.  The three random fills draw from the counter-based generator of the heatbath,
+ * keyed by (seed, mu, site): the result depends on neither launch geometry nor call order, and reproduces the DISTRIBUTION of the
+ * reference's fields, not its std::mt19937 stream.  (lorentz_gauge_fix_u1, :511-542, is an unfinished stub there and is not offered.) */
+int qmg_u1_hot_gauge(void* gauge, int Lx, int Ly, unsigned long long seed, void* stream);                  /* rand_gauge_u1: phases uniform in (-pi, pi) */
+int qmg_u1_gauss_gauge(void* gauge, int Lx, int Ly, double beta, unsigned long long seed, void* stream);   /* gauss_gauge_u1: N(0, 1/|beta|); beta == 0: hot */
+int qmg_u1_random_trans(void* trans, int Lx, int Ly, unsigned long long seed, void* stream);               /* rand_trans_u1 */
+/* apply_gauge_trans_u1: U_mu(x) <- g(x) U_mu(x) conj g(x + mu), in place, one pass */
+int qmg_u1_gauge_transform(void* gauge, const void* trans, int Lx, int Ly, void* stream);
+/* apply_ape_smear_u1: n_iter times U_mu <- P[U_mu + alpha (upper staple + lower staple)], P[z] = z / |z|, P[0] = 1 (no (1 - alpha) factor,
+ * as in the reference); both directions from the previous iterate, one launch per iteration.  smeared == gauge is allowed; n_iter == 0 copies. */
+int qmg_u1_ape_smear(void* smeared, const void* gauge, int Lx, int Ly, double alpha, int n_iter, void* stream);
+/* create_instanton_u1 / create_noncompact_instanton_u1, in place, with the reference's centring arithmetic */
+int qmg_u1_instanton(void* gauge, int Lx, int Ly, double Q, int x0, int y0, void* stream);
+int qmg_u1_noncompact_instanton(double* phase, int Lx, int Ly, double Q, void* stream);
 
 /* ---------------- stencil variants (device side) ---------------- */
 /* build_dagger_stencil (stencil_2d.h:1080-1139); also serves build_rbj_dagger_stencil (:1989-2060). */

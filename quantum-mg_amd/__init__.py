@@ -51,6 +51,7 @@ ABI_SYMBOLS = [
     "qmg_stencil_apply_epi_t", "qmg_wilson_apply_direct_epi", "qmg_wilson_hops_direct_epi", "qmg_batch_mr_dots_t", "qmg_batch_mr_update_t", "qmg_batch_mr_read_dots",
     "qmg_basis_dot_t", "qmg_basis_update_t", "qmg_batch_deflate_t",
     "qmg_u1_heatbath_noncompact", "qmg_u1_phase_to_gauge", "qmg_u1_gauge_to_phase", "qmg_u1_plaquette", "qmg_u1_noncompact_action",
+    "qmg_u1_hot_gauge", "qmg_u1_gauss_gauge", "qmg_u1_random_trans", "qmg_u1_gauge_transform", "qmg_u1_ape_smear", "qmg_u1_instanton", "qmg_u1_noncompact_instanton",
 ]
 
 
@@ -723,6 +724,34 @@ def u1_noncompact_action(phase, Lx, Ly, beta):
     out = C.c_double()
     check(lib().qmg_u1_noncompact_action(_vp(phase), Lx, Ly, C.c_double(beta), C.byref(out), None), "qmg_u1_noncompact_action")
     return out.value
+
+
+def u1_hot_gauge(gauge, Lx, Ly, seed, stream=None):
+    check(lib().qmg_u1_hot_gauge(_vp(gauge), Lx, Ly, C.c_ulonglong(seed), C.c_void_p(stream)), "qmg_u1_hot_gauge")
+
+
+def u1_gauss_gauge(gauge, Lx, Ly, beta, seed, stream=None):
+    check(lib().qmg_u1_gauss_gauge(_vp(gauge), Lx, Ly, C.c_double(beta), C.c_ulonglong(seed), C.c_void_p(stream)), "qmg_u1_gauss_gauge")
+
+
+def u1_random_trans(trans, Lx, Ly, seed, stream=None):
+    check(lib().qmg_u1_random_trans(_vp(trans), Lx, Ly, C.c_ulonglong(seed), C.c_void_p(stream)), "qmg_u1_random_trans")
+
+
+def u1_gauge_transform(gauge, trans, Lx, Ly, stream=None):
+    check(lib().qmg_u1_gauge_transform(_vp(gauge), _vp(trans), Lx, Ly, C.c_void_p(stream)), "qmg_u1_gauge_transform")
+
+
+def u1_ape_smear(smeared, gauge, Lx, Ly, alpha, n_iter, stream=None):
+    check(lib().qmg_u1_ape_smear(_vp(smeared), _vp(gauge), Lx, Ly, C.c_double(alpha), n_iter, C.c_void_p(stream)), "qmg_u1_ape_smear")
+
+
+def u1_instanton(gauge, Lx, Ly, Q, x0, y0, stream=None):
+    check(lib().qmg_u1_instanton(_vp(gauge), Lx, Ly, C.c_double(Q), x0, y0, C.c_void_p(stream)), "qmg_u1_instanton")
+
+
+def u1_noncompact_instanton(phase, Lx, Ly, Q, stream=None):
+    check(lib().qmg_u1_noncompact_instanton(_vp(phase), Lx, Ly, C.c_double(Q), C.c_void_p(stream)), "qmg_u1_noncompact_instanton")
 
 
 def set_tuning(key, value):

@@ -92,6 +92,7 @@ int qmg_shutdown(void) {
   release_batch_workspace();
   release_stencil_workspace();
   release_deflate_workspace();
+  release_u1_workspace();
   QMG_HIP_CHECK(hipDeviceSynchronize());
   return QMG_SUCCESS;
 }

@@ -14,6 +14,12 @@
 //
 // Layout: phase field = two real nc=1 lattice fields (mu = 0, 1), phase[mu*V + site], site = even-odd index
 // (lattice.h:75-81), as `gauge_coord_to_index` gives it; compact links U = exp(i A) in the same order (complex).
+//
+// Field tools (u1_utils.h:183-383, 545-603): hot / Gaussian fields and random gauge transforms, the gauge transform itself,
+// APE smearing and the two instantons.  All are site-local or nearest-neighbour.  The random ones draw from the counter-based
+// generator below, keyed by (seed, mu, site): the field depends on neither the launch geometry nor the call order, and -- as
+// with the heatbath -- it is the DISTRIBUTION of the reference that is reproduced, not its std::mt19937 stream.
+// lorentz_gauge_fix_u1 (:511-542) is an unfinished stub in the reference (its loop has no body and never ends): not here.
 #include <string.h>
 
 #include "qmg_common.h"
@@ -80,6 +86,123 @@ __global__ __launch_bounds__(BLOCK) void k_gauge_to_phase(double* __restrict__ p
   for (long i = (long)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (long)gridDim.x * BLOCK) phase[i] = atan2(gauge[i].y, gauge[i].x);
 }
 
+// one uniform draw in (-pi, pi) keyed by (seed, counter); 53 bits, centred so that neither end point is reached
+__device__ __forceinline__ double uniform_phase_draw(unsigned long long seed, unsigned long long counter) {
+  const unsigned long long h = mix64(mix64(seed * 0xD1342543DE82EF95ull + 2ull * counter) + 2ull * counter + 1ull);
+  const double u = ((double)(h >> 11) + 0.5) * (1.0 / 9007199254740992.0);   // (0,1)
+  return 3.14159265358979323846 * (2.0 * u - 1.0);
+}
+
+// rand_gauge_u1 / rand_trans_u1 (u1_utils.h:185-237; width < 0: uniform phases) and gauss_gauge_u1 (:200-223; N(0, width^2) phases),
+// then U = exp(i A).  Element i = mu * V + site is draw number i of `seed`.
+__global__ __launch_bounds__(BLOCK) void k_random_u1(cplx* __restrict__ out, long n, double width, unsigned long long seed) {
+  for (long i = (long)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (long)gridDim.x * BLOCK) {
+    const double a = (width < 0.0) ? uniform_phase_draw(seed, (unsigned long long)i) : width * gaussian_draw(seed, (unsigned long long)i);
+    double s, c;
+    sincos(a, &s, &c);
+    out[i] = cmake(c, s);
+  }
+}
+
+// apply_gauge_trans_u1 (u1_utils.h:241-272): U_mu(x) <- g(x) U_mu(x) conj g(x + mu), both directions in one pass
+__global__ __launch_bounds__(BLOCK) void k_gauge_transform(cplx* __restrict__ gauge, const cplx* __restrict__ trans, int Lx, int Ly) {
+  const long V = (long)Lx * Ly;
+  for (long t = (long)blockIdx.x * BLOCK + threadIdx.x; t < V; t += (long)gridDim.x * BLOCK) {
+    const int x = (int)(t % Lx), y = (int)(t / Lx);
+    const int xp = (x + 1 == Lx) ? 0 : x + 1, yp = (y + 1 == Ly) ? 0 : y + 1;
+    const long s = eo_index(x, y, Lx, Ly);
+    const cplx g = trans[s];
+    gauge[s] = cmul(cmul(g, gauge[s]), cconj(trans[eo_index(xp, y, Lx, Ly)]));
+    gauge[V + s] = cmul(cmul(g, gauge[V + s]), cconj(trans[eo_index(x, yp, Lx, Ly)]));
+  }
+}
+
+// P[z] = exp(i arg z), P[0] = 1 (arg_vector + polar, u1_utils.h:371-372).  z / |z| costs one rsqrt and two multiplies per link
+// where atan2 + sincos cost a few hundred fp64 operations -- comparable to the time the link's 64 bytes take from HBM
+// (profiles/u1_smear_bench.txt has both).  -DQMG_U1_APE_TRIG builds the trigonometric form for that comparison only.
+__device__ __forceinline__ cplx project_u1(cplx z) {
+#ifdef QMG_U1_APE_TRIG
+  double s, c;
+  sincos(atan2(z.y, z.x), &s, &c);
+  return cmake(c, s);
+#else
+  const double n2 = fma(z.x, z.x, z.y * z.y);
+  if (!(n2 > 0.0)) return cmake(1.0, 0.0);
+  const double r = rsqrt(n2);
+  return cmake(z.x * r, z.y * r);
+#endif
+}
+
+// One APE iteration (u1_utils.h:292-375), out != in.  A thread owns the two sites (2 xh, y) and (2 xh + 1, y) -- one of each
+// parity, at the same offset xh of their rows in the even-odd layout, so every load and store of a wave is one contiguous
+// run -- and writes all four of their links from 15 loaded links (the pair shares five of the 20 a site-per-thread kernel
+// would load).  Rows: site (x, r) lives at ((r + p Ly) Lx/2 + x/2), p = (x + r) & 1.
+//   U'_x(s) = P[ U_x(s) + alpha ( U_y(s) U_x(s+y) conj U_y(s+x) + conj U_y(s-y) U_x(s-y) U_y(s+x-y) ) ]
+//   U'_y(s) = P[ U_y(s) + alpha ( U_x(s) U_y(s+x) conj U_x(s+y) + conj U_x(s-x) U_y(s-x) U_x(s-x+y) ) ]
+__global__ __launch_bounds__(BLOCK) void k_ape_smear(cplx* __restrict__ out, const cplx* __restrict__ in, int Lx, int Ly, double alpha) {
+  const long V = (long)Lx * Ly;
+  const int h = Lx >> 1;
+  const long npairs = V / 2;
+  const cplx* __restrict__ Ux = in;
+  const cplx* __restrict__ Uy = in + V;
+  for (long t = (long)blockIdx.x * BLOCK + threadIdx.x; t < npairs; t += (long)gridDim.x * BLOCK) {
+    const int xh = (int)(t % h), y = (int)(t / h);
+    const int yp = (y + 1 == Ly) ? 0 : y + 1, ym = (y == 0) ? Ly - 1 : y - 1;
+    const int xl = (xh == 0) ? h - 1 : xh - 1, xr = (xh + 1 == h) ? 0 : xh + 1;
+    // a: the even-x site of the pair, b: the odd-x one; l: the odd-x site left of a, r: the even-x site right of b
+    const int q = y & 1, qp = yp & 1, qm = ym & 1;
+    const long ra = (long)(y + q * Ly) * h, rb = (long)(y + (1 - q) * Ly) * h;          // rows of even-x / odd-x sites at y
+    const long rap = (long)(yp + qp * Ly) * h, rbp = (long)(yp + (1 - qp) * Ly) * h;    // at y + 1
+    const long ram = (long)(ym + qm * Ly) * h, rbm = (long)(ym + (1 - qm) * Ly) * h;    // at y - 1
+    const cplx ax = Ux[ra + xh], ay = Uy[ra + xh], bx = Ux[rb + xh], by = Uy[rb + xh];
+    const cplx apx = Ux[rap + xh], bpx = Ux[rbp + xh];
+    const cplx amx = Ux[ram + xh], amy = Uy[ram + xh], bmx = Ux[rbm + xh], bmy = Uy[rbm + xh];
+    const cplx lx = Ux[rb + xl], ly = Uy[rb + xl], lpx = Ux[rbp + xl];
+    const cplx ry = Uy[ra + xr], rmy = Uy[ram + xr];
+
+    cplx st;
+    // site a: x + xhat = b, x - xhat = l
+    st = cadd(cmul(cmul(ay, apx), cconj(by)), cmul(cmul(cconj(amy), amx), bmy));
+    out[ra + xh] = project_u1(cmake(fma(alpha, st.x, ax.x), fma(alpha, st.y, ax.y)));
+    st = cadd(cmul(cmul(ax, by), cconj(apx)), cmul(cmul(cconj(lx), ly), lpx));
+    out[V + ra + xh] = project_u1(cmake(fma(alpha, st.x, ay.x), fma(alpha, st.y, ay.y)));
+    // site b: x + xhat = r, x - xhat = a
+    st = cadd(cmul(cmul(by, bpx), cconj(ry)), cmul(cmul(cconj(bmy), bmx), rmy));
+    out[rb + xh] = project_u1(cmake(fma(alpha, st.x, bx.x), fma(alpha, st.y, bx.y)));
+    st = cadd(cmul(cmul(bx, ry), cconj(bpx)), cmul(cmul(cconj(ax), ay), apx));
+    out[V + rb + xh] = project_u1(cmake(fma(alpha, st.x, by.x), fma(alpha, st.y, by.y)));
+  }
+}
+
+// create_instanton_u1 (u1_utils.h:545-572): the site (x, y) of the reference's loop, displaced by r = (x - Lx/2 + 1/2, y - Ly/2 + 1/2)
+// from the centre, lands on ((x - Lx/2 + x0 + 3 Lx) % Lx, (y - Ly/2 + y0 + 3 Ly) % Ly); U_x *= exp(i Q r_y / r^2), U_y *= exp(-i Q r_x / r^2).
+// The map (x, y) -> target is a bijection for every x0, y0 that keeps the reference's % arguments non-negative.
+__global__ __launch_bounds__(BLOCK) void k_instanton(cplx* __restrict__ gauge, int Lx, int Ly, double Q, int x0, int y0) {
+  const long V = (long)Lx * Ly;
+  for (long t = (long)blockIdx.x * BLOCK + threadIdx.x; t < V; t += (long)gridDim.x * BLOCK) {
+    const int x = (int)(t % Lx), y = (int)(t / Lx);
+    const double rx = x - Lx / 2 + 0.5, ry = y - Ly / 2 + 0.5;
+    const double r2 = rx * rx + ry * ry;
+    const long s = eo_index((x - Lx / 2 + x0 + 3 * Lx) % Lx, (y - Ly / 2 + y0 + 3 * Ly) % Ly, Lx, Ly);
+    double sn, cs;
+    sincos(Q * ry / r2, &sn, &cs);
+    gauge[s] = cmul(gauge[s], cmake(cs, sn));
+    sincos(-Q * rx / r2, &sn, &cs);
+    gauge[V + s] = cmul(gauge[V + s], cmake(cs, sn));
+  }
+}
+
+// create_noncompact_instanton_u1 (u1_utils.h:575-603), with the reference's ten-digit literal for pi
+__global__ __launch_bounds__(BLOCK) void k_noncompact_instanton(double* __restrict__ phase, int Lx, int Ly, double Q) {
+  const long V = (long)Lx * Ly;
+  for (long t = (long)blockIdx.x * BLOCK + threadIdx.x; t < V; t += (long)gridDim.x * BLOCK) {
+    const int x = (int)(t % Lx), y = (int)(t / Lx);
+    const long s = eo_index(x, y, Lx, Ly);
+    phase[s] += -Q * 3.1415926535 * y / (double)V;
+    if (y == Ly - 1) phase[V + s] += Q * 3.1415926535 * x / Lx;
+  }
+}
+
 // Per-block partial sums of: plaquette (re, im), topological charge density arg(P)/2pi, and -- from a phase field --
 // the non-compact plaquette angle squared.  MODE 0: compact links; MODE 1: phases.
 template <int MODE>
@@ -142,6 +265,29 @@ static int plaquette_sums(const void* gauge, const double* phase, int Lx, int Ly
   return QMG_SUCCESS;
 }
 
+// the calling thread's scratch field of qmg_u1_ape_smear
+struct SmearScratch { cplx* buf = nullptr; size_t bytes = 0; int device = -1; };
+static thread_local SmearScratch g_smear;
+
+static int smear_scratch(size_t bytes, cplx** out) {
+  int dev = 0;
+  QMG_HIP_CHECK(hipGetDevice(&dev));
+  if (g_smear.device != dev || g_smear.bytes < bytes) {
+    if (g_smear.buf && g_smear.device == dev) QMG_HIP_CHECK(hipFree(g_smear.buf));   // waits for the device: nothing still reads it
+    g_smear = SmearScratch();
+    QMG_HIP_CHECK(hipMalloc((void**)&g_smear.buf, bytes));
+    g_smear.bytes = bytes;
+    g_smear.device = dev;
+  }
+  *out = g_smear.buf;
+  return QMG_SUCCESS;
+}
+
+void release_u1_workspace() {   // qmg_shutdown (qmg_runtime.hip)
+  if (g_smear.buf) hipFree(g_smear.buf);
+  g_smear = SmearScratch();
+}
+
 }  // namespace qmg
 
 using namespace qmg;
@@ -202,6 +348,87 @@ int qmg_u1_noncompact_action(const double* phase, int Lx, int Ly, double beta, d
   const int rc = plaquette_sums(nullptr, phase, Lx, Ly, s, stream, 1);
   if (rc) return rc;
   *out_host = 0.5 * beta * s[0];
+  return QMG_SUCCESS;
+}
+
+// rand_gauge_u1 (u1_utils.h:185-195): hot start, phases uniform in (-pi, pi).  gauge: DEVICE complex<double>[2 Lx Ly].
+int qmg_u1_hot_gauge(void* gauge, int Lx, int Ly, unsigned long long seed, void* stream) {
+  if (!gauge || !valid_lattice(Lx, Ly)) return QMG_ERR_INVALID;
+  const long n = 2L * Lx * Ly;
+  k_random_u1<<<grid_1d((size_t)n), BLOCK, 0, as_stream(stream)>>>((cplx*)gauge, n, -1.0, seed);
+  QMG_LAUNCH_CHECK();
+  return QMG_SUCCESS;
+}
+// gauss_gauge_u1 (:200-223): phases N(0, 1/|beta|); beta == 0 is the hot start
+int qmg_u1_gauss_gauge(void* gauge, int Lx, int Ly, double beta, unsigned long long seed, void* stream) {
+  if (!gauge || !valid_lattice(Lx, Ly) || beta != beta) return QMG_ERR_INVALID;
+  if (beta == 0.0) return qmg_u1_hot_gauge(gauge, Lx, Ly, seed, stream);
+  const long n = 2L * Lx * Ly;
+  k_random_u1<<<grid_1d((size_t)n), BLOCK, 0, as_stream(stream)>>>((cplx*)gauge, n, 1.0 / sqrt(fabs(beta)), seed);
+  QMG_LAUNCH_CHECK();
+  return QMG_SUCCESS;
+}
+// rand_trans_u1 (:227-237): trans: DEVICE complex<double>[Lx Ly], phases uniform in (-pi, pi)
+int qmg_u1_random_trans(void* trans, int Lx, int Ly, unsigned long long seed, void* stream) {
+  if (!trans || !valid_lattice(Lx, Ly)) return QMG_ERR_INVALID;
+  const long n = (long)Lx * Ly;
+  k_random_u1<<<grid_1d((size_t)n), BLOCK, 0, as_stream(stream)>>>((cplx*)trans, n, -1.0, seed);
+  QMG_LAUNCH_CHECK();
+  return QMG_SUCCESS;
+}
+
+// apply_gauge_trans_u1 (:241-272), in place
+int qmg_u1_gauge_transform(void* gauge, const void* trans, int Lx, int Ly, void* stream) {
+  if (!gauge || !trans || !valid_lattice(Lx, Ly)) return QMG_ERR_INVALID;
+  k_gauge_transform<<<grid_1d((size_t)Lx * Ly), BLOCK, 0, as_stream(stream)>>>((cplx*)gauge, (const cplx*)trans, Lx, Ly);
+  QMG_LAUNCH_CHECK();
+  return QMG_SUCCESS;
+}
+
+// apply_ape_smear_u1 (:276-383): n_iter iterations of one launch each, ping-ponging between `smeared` and the calling thread's scratch
+// field so that the last one lands in `smeared`.  smeared == gauge is allowed (the reference copies first); n_iter == 0 is a copy.
+// The scratch field grows on demand (the only synchronous step, and only when it grows) and is held until qmg_shutdown, like the
+// reduction workspaces; calls of one host thread on different streams share it and must not overlap.
+int qmg_u1_ape_smear(void* smeared, const void* gauge, int Lx, int Ly, double alpha, int n_iter, void* stream) {
+  if (!smeared || !gauge || !valid_lattice(Lx, Ly) || n_iter < 0 || alpha != alpha) return QMG_ERR_INVALID;
+  const size_t n = 2 * (size_t)Lx * Ly, bytes = sizeof(cplx) * n;
+  const bool in_place = (smeared == gauge);
+  if (!in_place && ((const char*)smeared < (const char*)gauge + bytes && (const char*)gauge < (const char*)smeared + bytes)) return QMG_ERR_INVALID;   // partial overlap
+  if (n_iter == 0) return in_place ? QMG_SUCCESS : qmg_copy_vector(smeared, gauge, n, stream);
+  cplx* tmp = nullptr;
+  if (in_place || n_iter > 1) {
+    const int rc = smear_scratch(bytes, &tmp);
+    if (rc) return rc;
+  }
+  // targets alternate and end on `smeared`; in place with an odd count the roles swap (the first target cannot be the
+  // source) and the result is copied over from the scratch field
+  const bool swapped = in_place && (n_iter & 1);
+  cplx* ends[2] = {swapped ? tmp : (cplx*)smeared, swapped ? (cplx*)smeared : tmp};
+  const unsigned g = grid_1d((size_t)Lx * Ly / 2);
+  const cplx* src = (const cplx*)gauge;
+  for (int i = 0; i < n_iter; i++) {
+    cplx* dst = ends[(n_iter - 1 - i) & 1];
+    k_ape_smear<<<g, BLOCK, 0, as_stream(stream)>>>(dst, src, Lx, Ly, alpha);
+    src = dst;
+  }
+  QMG_LAUNCH_CHECK();
+  return swapped ? qmg_copy_vector(smeared, tmp, n, stream) : QMG_SUCCESS;
+}
+
+// create_instanton_u1 (:545-572), in place: charge Q centred between the sites around (x0, y0)
+int qmg_u1_instanton(void* gauge, int Lx, int Ly, double Q, int x0, int y0, void* stream) {
+  if (!gauge || !valid_lattice(Lx, Ly)) return QMG_ERR_INVALID;
+  // the reference's (x - Lx/2 + x0 + 3 Lx) % Lx needs a non-negative argument (and no int overflow) to be a lattice coordinate
+  if (x0 < -2 * (long)Lx - Lx / 2 || y0 < -2 * (long)Ly - Ly / 2 || x0 > (1 << 30) || y0 > (1 << 30)) return QMG_ERR_INVALID;
+  k_instanton<<<grid_1d((size_t)Lx * Ly), BLOCK, 0, as_stream(stream)>>>((cplx*)gauge, Lx, Ly, Q, x0, y0);
+  QMG_LAUNCH_CHECK();
+  return QMG_SUCCESS;
+}
+// create_noncompact_instanton_u1 (:575-603), in place on a phase field
+int qmg_u1_noncompact_instanton(double* phase, int Lx, int Ly, double Q, void* stream) {
+  if (!phase || !valid_lattice(Lx, Ly)) return QMG_ERR_INVALID;
+  k_noncompact_instanton<<<grid_1d((size_t)Lx * Ly), BLOCK, 0, as_stream(stream)>>>(phase, Lx, Ly, Q);
+  QMG_LAUNCH_CHECK();
   return QMG_SUCCESS;
 }
 

@@ -1,7 +1,9 @@
 // u1.hpp -- U(1) gauge utilities on device fields (reference: u1/u1_utils.h): text I/O in the reference's format
 // (read_gauge_u1 :38-67, write_gauge_u1 :105-168), unit field (:172-181), polar_vector, non-compact heatbath (:607-757; here
 // a four-colour parallel heatbath on the device, csrc/qmg_u1.hip), plaquette / topology / non-compact action (:386-508).
-// Smearing, gauge transforms and instantons stay out of scope (input preparation no BASELINE config uses).
+// Field preparation on the device as well: hot and Gaussian starts and random gauge transforms (:183-237), apply_gauge_trans_u1
+// (:241-272), APE smearing (:276-383) and the two instantons (:545-603); read_phase_u1 (:70-102) is host text I/O like read_gauge_u1.
+// lorentz_gauge_fix_u1 (:511-542) is an unfinished stub in the reference (its loop never ends) and has no counterpart.
 // `gauge_field` is a DEVICE nc=1 LatticeGauge (mu, eo, y, x) of complex links; `phases` a DEVICE double field in the same order.
 #ifndef QMG_U1_HPP
 #define QMG_U1_HPP
@@ -92,13 +94,71 @@ inline void write_gauge_u1(double* phase_field, Lattice2D* lat, std::string outp
 inline void polar_vector(double* phases, complex<double>* gauge_field, size_t n) { qmg::ok(qmg_u1_phase_to_gauge(gauge_field, phases, n, qmg::current_stream()), "qmg_u1_phase_to_gauge"); }
 
 // Non-compact heatbath (u1_utils.h:607-757).  The reference threads a std::mt19937 through; here the generator state is a
-// (seed, sweeps done) pair so that successive calls continue one stream.
-struct HeatbathRng { unsigned long long seed, sweeps_done; explicit HeatbathRng(unsigned long long s = 1337ull) : seed(s), sweeps_done(0) {} };
+// (seed, sweeps done) pair so that successive calls continue one stream (and a count of the random fields drawn, see rand_gauge_u1).
+struct HeatbathRng { unsigned long long seed, sweeps_done, fields_drawn; explicit HeatbathRng(unsigned long long s = 1337ull) : seed(s), sweeps_done(0), fields_drawn(0) {} };
 inline void heatbath_noncompact_update(double* phase_field, Lattice2D* lat, double beta, int n_update, HeatbathRng& generator) {
   if (lat->get_nc() != 1) { std::cout << "[QMG-ERROR]: U1 gauge functions require Nc = 1 lattice.\n"; return; }
   qmg::ok(qmg_u1_heatbath_noncompact(phase_field, lat->get_dim_mu(0), lat->get_dim_mu(1), beta, n_update, generator.seed, generator.sweeps_done, qmg::current_stream()),
           "qmg_u1_heatbath_noncompact");
   generator.sweeps_done += (unsigned long long)n_update;
+}
+
+// Just the phases, not compactified (u1_utils.h:70-99): `phase_field` a DEVICE double field, same file order as read_gauge_u1
+inline bool read_phase_u1(double* phase_field, Lattice2D* lat, std::string input_file) {
+  if (lat->get_nc() != 1) { std::cout << "[QMG-ERROR]: U1 gauge functions require Nc = 1 lattice.\n"; return false; }
+  const int x_len = lat->get_dim_mu(0), y_len = lat->get_dim_mu(1);
+  std::FILE* f = std::fopen(input_file.c_str(), "r");
+  if (!f) { std::cout << "[QMG-ERROR]: cannot open gauge file " << input_file << "\n"; return false; }
+  std::vector<double> host((size_t)lat->get_size_gauge());
+  bool good = true;
+  for (int x = 0; x < x_len && good; x++)
+    for (int y = 0; y < y_len && good; y++)
+      for (int mu = 0; mu < 2; mu++)
+        if (std::fscanf(f, "%lf", &host[lat->gauge_coord_to_index(x, y, 0, 0, mu)]) != 1) { good = false; break; }
+  std::fclose(f);
+  if (!good) { std::cout << "[QMG-ERROR]: gauge file " << input_file << " is too short for this lattice.\n"; return false; }
+  qmg::upload(phase_field, host.data(), host.size());
+  return true;
+}
+
+// Random fields (u1_utils.h:183-237).  Where the reference threads a std::mt19937 through, the HeatbathRng stands in: every call
+// draws its field from a seed derived from (seed, calls made) and counts itself, so consecutive calls give different fields and a
+// program that makes the same calls in the same order gets the same fields.  The distributions are the reference's, the streams not.
+inline unsigned long long u1_next_field_seed(HeatbathRng& generator) {
+  return generator.seed * 0x9E3779B97F4A7C15ull + 0xD1B54A32D192ED03ull * (++generator.fields_drawn);
+}
+inline void rand_gauge_u1(complex<double>* gauge_field, Lattice2D* lat, HeatbathRng& generator) {   // :185-195
+  if (lat->get_nc() != 1) { std::cout << "[QMG-ERROR]: U1 gauge functions require Nc = 1 lattice.\n"; return; }
+  qmg::ok(qmg_u1_hot_gauge(gauge_field, lat->get_dim_mu(0), lat->get_dim_mu(1), u1_next_field_seed(generator), qmg::current_stream()), "qmg_u1_hot_gauge");
+}
+inline void gauss_gauge_u1(complex<double>* gauge_field, Lattice2D* lat, HeatbathRng& generator, double beta) {   // :200-223
+  if (lat->get_nc() != 1) { std::cout << "[QMG-ERROR]: U1 gauge functions require Nc = 1 lattice.\n"; return; }
+  qmg::ok(qmg_u1_gauss_gauge(gauge_field, lat->get_dim_mu(0), lat->get_dim_mu(1), beta, u1_next_field_seed(generator), qmg::current_stream()), "qmg_u1_gauss_gauge");
+}
+inline void rand_trans_u1(complex<double>* gauge_trans, Lattice2D* lat, HeatbathRng& generator) {   // :227-237
+  if (lat->get_nc() != 1) { std::cout << "[QMG-ERROR]: U1 gauge functions require Nc = 1 lattice.\n"; return; }
+  qmg::ok(qmg_u1_random_trans(gauge_trans, lat->get_dim_mu(0), lat->get_dim_mu(1), u1_next_field_seed(generator), qmg::current_stream()), "qmg_u1_random_trans");
+}
+
+// u_i(x) = g(x) u_i(x) g^dag(x + i) (:241-272); `gauge_trans` a DEVICE nc = 1 colour vector
+inline void apply_gauge_trans_u1(complex<double>* gauge_field, complex<double>* gauge_trans, Lattice2D* lat) {
+  if (lat->get_nc() != 1) { std::cout << "[QMG-ERROR]: U1 gauge functions require Nc = 1 lattice.\n"; return; }
+  qmg::ok(qmg_u1_gauge_transform(gauge_field, gauge_trans, lat->get_dim_mu(0), lat->get_dim_mu(1), qmg::current_stream()), "qmg_u1_gauge_transform");
+}
+
+// APE smearing with parameter alpha, n_iter times (:276-383); smeared_field == gauge_field is allowed
+inline void apply_ape_smear_u1(complex<double>* smeared_field, complex<double>* gauge_field, Lattice2D* lat, double alpha, int n_iter) {
+  if (lat->get_nc() != 1) { std::cout << "[QMG-ERROR]: U1 gauge functions require Nc = 1 lattice.\n"; return; }
+  qmg::ok(qmg_u1_ape_smear(smeared_field, gauge_field, lat->get_dim_mu(0), lat->get_dim_mu(1), alpha, n_iter, qmg::current_stream()), "qmg_u1_ape_smear");
+}
+
+inline void create_instanton_u1(complex<double>* gauge_field, Lattice2D* lat, double Q, const int x0, const int y0) {   // :545-572
+  if (lat->get_nc() != 1) { std::cout << "[QMG-ERROR]: U1 gauge functions require Nc = 1 lattice.\n"; return; }
+  qmg::ok(qmg_u1_instanton(gauge_field, lat->get_dim_mu(0), lat->get_dim_mu(1), Q, x0, y0, qmg::current_stream()), "qmg_u1_instanton");
+}
+inline void create_noncompact_instanton_u1(double* phase_field, Lattice2D* lat, double Q) {   // :575-603
+  if (lat->get_nc() != 1) { std::cout << "[QMG-ERROR]: U1 gauge functions require Nc = 1 lattice.\n"; return; }
+  qmg::ok(qmg_u1_noncompact_instanton(phase_field, lat->get_dim_mu(0), lat->get_dim_mu(1), Q, qmg::current_stream()), "qmg_u1_noncompact_instanton");
 }
 
 inline complex<double> get_plaquette_u1(complex<double>* gauge_field, Lattice2D* lat) {   // :424-462

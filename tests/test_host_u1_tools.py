@@ -1,0 +1,89 @@
+"""CPU side of the U(1) field tools: (i) the numpy twin tests/u1_numpy.py is pinned by the identities the tools must obey -- gauge
+invariance of plaquette and topology, smearing commuting with a gauge transform, smearing raising the plaquette, the unit charge of an
+instanton on the unit field, the uniform flux of the non-compact instanton -- before it judges the device in test_gpu_u1_tools.py;
+(ii) the drop-in boundary: every new entry point is exported by libqmg_hip.so, declared in include/qmg_hip.h and bound in Python."""
+import importlib
+import os
+import re
+
+import numpy as np
+import pytest
+
+import u1_numpy as un
+
+qmg = importlib.import_module("quantum-mg_amd")
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+FIELDS = [(16, 100.0), (16, 6.0), (16, 1.0), (64, 100.0), (64, 6.0), (64, 1.0)]
+
+
+@pytest.mark.parametrize("L,beta", FIELDS)
+def test_gauge_transform_leaves_plaquette_and_topology(L, beta):
+    Ux, Uy = un.gaussian_links(L, beta, 7)
+    Tx, Ty = un.gauge_transform(Ux, Uy, un.random_transform(L, L, 8))
+    (p0, q0), (p1, q1) = un.plaquette(Ux, Uy), un.plaquette(Tx, Ty)
+    # a plaquette is a product of four unit numbers, each multiplied by two more: a few roundings of 1.1e-16 per plaquette, averaging down
+    # in the mean; the charge sums V angles, each carrying such a rounding
+    assert abs(p1 - p0) < 1e-14 and abs(q1 - q0) < 1e-11
+    assert np.allclose(np.abs(Tx), 1.0, atol=1e-15) and np.allclose(np.abs(Ty), 1.0, atol=1e-15)
+
+
+@pytest.mark.parametrize("L,beta", [f for f in FIELDS if f[1] >= 6.0])
+def test_smearing_commutes_with_a_gauge_transform(L, beta):
+    Ux, Uy = un.gaussian_links(L, beta, 9)
+    g = un.random_transform(L, L, 10)
+    a = un.gauge_transform(*un.ape_smear(Ux, Uy, 0.5, 5), g)
+    b = un.ape_smear(*un.gauge_transform(Ux, Uy, g), 0.5, 5)
+    assert max(np.abs(a[0] - b[0]).max(), np.abs(a[1] - b[1]).max()) < 1e-12
+
+
+@pytest.mark.parametrize("L,beta", FIELDS)
+def test_one_iteration_raises_the_plaquette_and_stays_on_the_circle(L, beta):
+    Ux, Uy = un.gaussian_links(L, beta, 11)
+    Sx, Sy = un.ape_iteration(Ux, Uy, 0.5)
+    assert un.plaquette(Sx, Sy)[0].real > un.plaquette(Ux, Uy)[0].real
+    assert np.allclose(np.abs(Sx), 1.0, atol=1e-15) and np.allclose(np.abs(Sy), 1.0, atol=1e-15)
+    Zx, Zy = un.ape_smear(Ux, Uy, 0.0, 3)                            # alpha = 0: the projection of a unit number is itself
+    assert np.abs(Zx - Ux).max() < 1e-15 and np.abs(Zy - Uy).max() < 1e-15
+    assert un.project(np.zeros(3, dtype=complex)).tolist() == [1.0, 1.0, 1.0]
+
+
+def test_smearing_statement_is_the_symmetric_one():
+    """Exchanging the roles of x and y (transpose the grids, swap the links) must exchange the two outputs."""
+    Ux, Uy = un.gaussian_links(12, 6.0, 12, Ly=8)
+    Sx, Sy = un.ape_iteration(Ux, Uy, 0.3)
+    Ty, Tx = un.ape_iteration(Uy.T.copy(), Ux.T.copy(), 0.3)
+    assert np.abs(Tx.T - Sx).max() < 1e-15 and np.abs(Ty.T - Sy).max() < 1e-15
+
+
+@pytest.mark.parametrize("x0,y0", [(8, 8), (0, 0)])
+def test_instanton_on_the_unit_field_has_charge_one(x0, y0):
+    one = np.ones((16, 16), dtype=complex)
+    Ux, Uy = un.instanton(one, one, 1.0, x0, y0)
+    p, q = un.plaquette(Ux, Uy)
+    assert abs(q - 1.0) < 1e-9
+    assert np.allclose(np.abs(Ux), 1.0, atol=1e-15)
+    # moving the centre moves the field: (x0, y0) against the middle is a roll
+    Mx, My = un.instanton(one, one, 1.0, 8, 8)
+    assert np.array_equal(np.roll(Mx, (x0 - 8, y0 - 8), axis=(0, 1)), Ux) and np.array_equal(np.roll(My, (x0 - 8, y0 - 8), axis=(0, 1)), Uy)
+
+
+def test_noncompact_instanton_is_a_uniform_flux():
+    Lx, Ly, Q = 12, 8, 2.0
+    Ax, Ay = un.noncompact_instanton(np.zeros((Lx, Ly)), np.zeros((Lx, Ly)), Q)
+    theta = Ax + np.roll(Ay, -1, axis=0) - np.roll(Ax, -1, axis=1) - Ay
+    want = np.full((Lx, Ly), Q * 3.1415926535 / (Lx * Ly))
+    want[Lx - 1, Ly - 1] -= Q * 3.1415926535                        # the one plaquette that closes the torus
+    assert np.abs(theta - want).max() < 1e-14
+
+
+def test_new_entry_points_are_exported_declared_and_bound():
+    qmg.build()
+    lib = qmg.lib()
+    header = open(os.path.join(ROOT, "include", "qmg_hip.h")).read()
+    header = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
+    for name in un.NEW_SYMBOLS:
+        assert hasattr(lib, name), "libqmg_hip.so does not export %s" % name
+        assert re.search(r"\bint\s+%s\s*\(" % name, header), "include/qmg_hip.h does not declare %s" % name
+        assert name in qmg.ABI_SYMBOLS
+    for name in un.NEW_BINDINGS:
+        assert callable(getattr(qmg, name, None)), "the Python module does not bind %s" % name
