@@ -182,6 +182,19 @@ int qmg_u1_ape_smear(void* smeared, const void* gauge, int Lx, int Ly, double al
 int qmg_u1_instanton(void* gauge, int Lx, int Ly, double Q, int x0, int y0, void* stream);
 int qmg_u1_noncompact_instanton(double* phase, int Lx, int Ly, double Q, void* stream);
 
+/* ---- molecular dynamics of two-flavour Wilson HMC for compact U(1) (csrc/qmg_hmc.hip; not in the reference); fp64 only ----
+ * H = 1/2 sum pi^2 + beta sum_x (1 - cos P(x)) + phi^dag (D^dag D)^-1 phi, D the Wilson operator with wilson_coeff 1.
+ * theta, pi: DEVICE double[2 Lx Ly] in the (mu, eo, y, x) order; gauge: the links exp(i theta), DEVICE complex<double>[2 Lx Ly]. */
+enum { QMG_HMC_GAUGE_ONLY = 1u };   /* flags of qmg_hmc_momentum_update: no fermion force, X and Y may be null */
+/* pi -= dt (dS_g/dtheta + dS_f/dtheta) in one pass; X = (D^dag D)^-1 phi, Y = D X: DEVICE complex<double>[2 Lx Ly] */
+int qmg_hmc_momentum_update(double* pi, const void* gauge, const void* X, const void* Y, int Lx, int Ly, double beta, double dt, unsigned flags, void* stream);
+/* theta += dt pi ; gauge = exp(i theta) in one pass over n = 2 Lx Ly links */
+int qmg_hmc_link_update(double* theta, void* gauge, const double* pi, size_t n, double dt, void* stream);
+/* pi ~ N(0, 1) per link from the counter-based generator, a function of (seed, trajectory) alone; n even */
+int qmg_hmc_momentum_refresh(double* pi, size_t n, unsigned long long seed, unsigned long long trajectory, void* stream);
+/* the generator seed of random field `field` (0 momenta, 1 pseudofermion noise, 2 Metropolis number) of a trajectory */
+unsigned long long qmg_hmc_stream_seed(unsigned long long seed, unsigned long long trajectory, int field);
+
 /* ---------------- stencil variants (device side) ---------------- */
 /* build_dagger_stencil (stencil_2d.h:1080-1139); also serves build_rbj_dagger_stencil (:1989-2060). */
 int qmg_build_dagger(void* dagger_clover, void* dagger_hopping, const void* clover, const void* hopping,

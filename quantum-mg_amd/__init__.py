@@ -52,6 +52,7 @@ ABI_SYMBOLS = [
     "qmg_basis_dot_t", "qmg_basis_update_t", "qmg_batch_deflate_t",
     "qmg_u1_heatbath_noncompact", "qmg_u1_phase_to_gauge", "qmg_u1_gauge_to_phase", "qmg_u1_plaquette", "qmg_u1_noncompact_action",
     "qmg_u1_hot_gauge", "qmg_u1_gauss_gauge", "qmg_u1_random_trans", "qmg_u1_gauge_transform", "qmg_u1_ape_smear", "qmg_u1_instanton", "qmg_u1_noncompact_instanton",
+    "qmg_hmc_momentum_update", "qmg_hmc_link_update", "qmg_hmc_momentum_refresh", "qmg_hmc_stream_seed",
 ]
 
 
@@ -752,6 +753,30 @@ def u1_instanton(gauge, Lx, Ly, Q, x0, y0, stream=None):
 
 def u1_noncompact_instanton(phase, Lx, Ly, Q, stream=None):
     check(lib().qmg_u1_noncompact_instanton(_vp(phase), Lx, Ly, C.c_double(Q), C.c_void_p(stream)), "qmg_u1_noncompact_instanton")
+
+
+HMC_GAUGE_ONLY = 1   # flags of hmc_momentum_update
+
+
+def hmc_momentum_update(pi, gauge, X, Y, Lx, Ly, beta, dt, flags=0, stream=None):
+    """pi -= dt (gauge force + two-flavour Wilson force); flags = HMC_GAUGE_ONLY drops the fermions (X, Y may be None)"""
+    check(lib().qmg_hmc_momentum_update(_vp(pi), _vp(gauge), _vp(X), _vp(Y), Lx, Ly, C.c_double(beta), C.c_double(dt), C.c_uint(flags), C.c_void_p(stream)),
+          "qmg_hmc_momentum_update")
+
+
+def hmc_link_update(theta, gauge, pi, n, dt, stream=None):
+    """theta += dt pi ; gauge = exp(i theta)"""
+    check(lib().qmg_hmc_link_update(_vp(theta), _vp(gauge), _vp(pi), C.c_size_t(n), C.c_double(dt), C.c_void_p(stream)), "qmg_hmc_link_update")
+
+
+def hmc_momentum_refresh(pi, n, seed, trajectory, stream=None):
+    check(lib().qmg_hmc_momentum_refresh(_vp(pi), C.c_size_t(n), C.c_ulonglong(seed), C.c_ulonglong(trajectory), C.c_void_p(stream)), "qmg_hmc_momentum_refresh")
+
+
+def hmc_stream_seed(seed, trajectory, field):
+    f = lib().qmg_hmc_stream_seed
+    f.restype = C.c_ulonglong
+    return f(C.c_ulonglong(seed), C.c_ulonglong(trajectory), field)
 
 
 def set_tuning(key, value):

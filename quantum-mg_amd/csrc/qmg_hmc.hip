@@ -1,0 +1,162 @@
+// qmg_hmc.hip -- molecular dynamics of two-flavour Wilson HMC for compact U(1) in two dimensions (the Schwinger model); fp64 only.
+// Not in the reference, which has no HMC: the driver is include/qmg/hmc.hpp (SchwingerHMC), the independent statement tests/hmc_numpy.py.
+//
+//   H = 1/2 sum pi^2 + S_g + S_f,   S_g = beta sum_x (1 - cos P(x)),   S_f = phi^dag (D^dag D)^-1 phi,   U_mu(x) = exp(i theta_mu(x))
+//   P(x) = theta_x(x) + theta_y(x+xhat) - theta_x(x+yhat) - theta_y(x),   D: Wilson2D (wilson_coeff 1; tests/coordspace.py::wilson_apply)
+//
+// Forces F = dS/dtheta, with X = (D^dag D)^-1 phi, Y = D X, Hp_mu = (-1 + sigma_mu)/2, Hm_mu = (-1 - sigma_mu)/2:
+//   Fg_x(x) = beta [ sin P(x) - sin P(x-yhat) ]          Fg_y(x) = beta [ -sin P(x) + sin P(x-xhat) ]
+//   Ff_mu(x) = 2 Im[ U_mu(x) Y(x)^dag Hp_mu X(x+mu)  -  conj(U_mu(x)) Y(x+mu)^dag Hm_mu X(x) ]
+// sin P is the imaginary part of the plaquette of the complex links, so the force kernel needs no trigonometry.
+//
+// Layouts (lattice.h:75-81): site (x, y) has index (y + p Ly) Lx/2 + x/2, p = (x + y) & 1; phases, momenta and links are [mu][site],
+// spinors [site][2].
+#include "qmg_common.h"
+
+namespace qmg {
+
+// Y^dag Hp_x X etc. without the factor 1/2 of the projectors (it cancels the 2 of 2 Im[...]).
+//   Hp_x v = (-v0 + v1, v0 - v1)/2      Hm_x v = -(v0 + v1, v0 + v1)/2
+//   Hp_y v = (-v0 - i v1, i v0 - v1)/2  Hm_y v = (-v0 + i v1, -i v0 - v1)/2
+__device__ __forceinline__ cplx ydag_hx(cplx y0, cplx y1, cplx x0, cplx x1, double sgn) {   // sgn = +1: 2 Hp_x, -1: 2 Hm_x
+  const cplx d = cmake(fma(sgn, x1.x, -x0.x), fma(sgn, x1.y, -x0.y));    // -x0 + sgn x1
+  const cplx e = cmake(fma(sgn, x0.x, -x1.x), fma(sgn, x0.y, -x1.y));    // sgn x0 - x1
+  cplx acc = cmake(0.0, 0.0);
+  cmac_conj(acc, y0, d);
+  cmac_conj(acc, y1, e);
+  return acc;
+}
+__device__ __forceinline__ cplx ydag_hy(cplx y0, cplx y1, cplx x0, cplx x1, double sgn) {   // sgn = +1: 2 Hp_y, -1: 2 Hm_y
+  const cplx d = cmake(fma(sgn, x1.y, -x0.x), fma(-sgn, x1.x, -x0.y));   // -x0 - sgn i x1
+  const cplx e = cmake(fma(-sgn, x0.y, -x1.x), fma(sgn, x0.x, -x1.y));   // sgn i x0 - x1
+  cplx acc = cmake(0.0, 0.0);
+  cmac_conj(acc, y0, d);
+  cmac_conj(acc, y1, e);
+  return acc;
+}
+// Im[ U p - conj(U) m ]
+__device__ __forceinline__ double link_force(cplx u, cplx p, cplx m) {
+  return fma(u.x, p.y, u.y * p.x) - fma(u.x, m.y, -u.y * m.x);
+}
+__device__ __forceinline__ double im_plaq(cplx a, cplx b, cplx c, cplx d) {   // Im[ a b conj(c) conj(d) ]
+  const cplx ab = cmul(a, b), cd = cmul(c, d);
+  return fma(ab.y, cd.x, -ab.x * cd.y);
+}
+
+// pi -= dt (Fg + Ff), every link in one pass.  The thread mapping of k_ape_smear (qmg_u1.hip): a thread owns the two sites (2 xh, y) and
+// (2 xh + 1, y) -- one of each parity, at the same offset xh of their rows, so every load and store of a wave is one contiguous run -- and
+// updates all four of their momenta.  It loads 15 links (the five plaquettes P(a), P(b), P(a-y), P(b-y), P(a-x); P(b-x) = P(a)) and, with
+// fermions, X and Y at five sites (a, b, the site right of b and the two above).  All loads are unconditional and sit in front of the
+// arithmetic; every index is a wrapped lattice coordinate, so nothing is read or written outside the fields.
+// Byte model: 128 B/site -- pi read and written (32), two links (32), X and Y (64); the neighbours are expected from cache.
+template <bool FERMIONS>
+__global__ __launch_bounds__(BLOCK) void k_hmc_momentum_update(double* __restrict__ pi, const cplx* __restrict__ gauge, const cplx* __restrict__ X,
+                                                               const cplx* __restrict__ Y, int Lx, int Ly, double beta, double dt) {
+  const long V = (long)Lx * Ly;
+  const int h = Lx >> 1;
+  const long npairs = V / 2;
+  const cplx* __restrict__ Ux = gauge;
+  const cplx* __restrict__ Uy = gauge + V;
+  for (long t = (long)blockIdx.x * BLOCK + threadIdx.x; t < npairs; t += (long)gridDim.x * BLOCK) {
+    const int xh = (int)(t % h), y = (int)(t / h);
+    const int yp = (y + 1 == Ly) ? 0 : y + 1, ym = (y == 0) ? Ly - 1 : y - 1;
+    const int xl = (xh == 0) ? h - 1 : xh - 1, xr = (xh + 1 == h) ? 0 : xh + 1;
+    // a: the even-x site of the pair, b: the odd-x one; l: the odd-x site left of a, r: the even-x site right of b
+    const int q = y & 1, qp = yp & 1, qm = ym & 1;
+    const long ra = (long)(y + q * Ly) * h, rb = (long)(y + (1 - q) * Ly) * h;          // rows of even-x / odd-x sites at y
+    const long rap = (long)(yp + qp * Ly) * h, rbp = (long)(yp + (1 - qp) * Ly) * h;    // at y + 1
+    const long ram = (long)(ym + qm * Ly) * h, rbm = (long)(ym + (1 - qm) * Ly) * h;    // at y - 1
+    const long sa = ra + xh, sb = rb + xh;
+    const double pax = pi[sa], pay = pi[V + sa], pbx = pi[sb], pby = pi[V + sb];
+    const cplx ax = Ux[sa], ay = Uy[sa], bx = Ux[sb], by = Uy[sb];
+    const cplx apx = Ux[rap + xh], bpx = Ux[rbp + xh];
+    const cplx amx = Ux[ram + xh], amy = Uy[ram + xh], bmx = Ux[rbm + xh], bmy = Uy[rbm + xh];
+    const cplx lx = Ux[rb + xl], ly = Uy[rb + xl], lpx = Ux[rbp + xl];
+    const cplx ry = Uy[ra + xr], rmy = Uy[ram + xr];
+    cplx xa0, xa1, ya0, ya1, xb0, xb1, yb0, yb1, xr0, xr1, yr0, yr1, xap0, xap1, yap0, yap1, xbp0, xbp1, ybp0, ybp1;
+    if (FERMIONS) {
+      const long sr = ra + xr, sap = rap + xh, sbp = rbp + xh;
+      xa0 = X[2 * sa]; xa1 = X[2 * sa + 1]; ya0 = Y[2 * sa]; ya1 = Y[2 * sa + 1];
+      xb0 = X[2 * sb]; xb1 = X[2 * sb + 1]; yb0 = Y[2 * sb]; yb1 = Y[2 * sb + 1];
+      xr0 = X[2 * sr]; xr1 = X[2 * sr + 1]; yr0 = Y[2 * sr]; yr1 = Y[2 * sr + 1];
+      xap0 = X[2 * sap]; xap1 = X[2 * sap + 1]; yap0 = Y[2 * sap]; yap1 = Y[2 * sap + 1];
+      xbp0 = X[2 * sbp]; xbp1 = X[2 * sbp + 1]; ybp0 = Y[2 * sbp]; ybp1 = Y[2 * sbp + 1];
+    }
+
+    // sin P: a + x = b, a + y = ap, b + x = r, (a-y) + x = b-y, (a-y) + y = a, l + x = a
+    const double sPa = im_plaq(ax, by, apx, ay), sPb = im_plaq(bx, ry, bpx, by);
+    const double sPam = im_plaq(amx, bmy, ax, amy), sPbm = im_plaq(bmx, rmy, bx, bmy);
+    const double sPl = im_plaq(lx, ay, lpx, ly);
+    double fax = beta * (sPa - sPam), fay = beta * (sPl - sPa);
+    double fbx = beta * (sPb - sPbm), fby = beta * (sPa - sPb);
+    if (FERMIONS) {
+      fax += link_force(ax, ydag_hx(ya0, ya1, xb0, xb1, 1.0), ydag_hx(yb0, yb1, xa0, xa1, -1.0));
+      fay += link_force(ay, ydag_hy(ya0, ya1, xap0, xap1, 1.0), ydag_hy(yap0, yap1, xa0, xa1, -1.0));
+      fbx += link_force(bx, ydag_hx(yb0, yb1, xr0, xr1, 1.0), ydag_hx(yr0, yr1, xb0, xb1, -1.0));
+      fby += link_force(by, ydag_hy(yb0, yb1, xbp0, xbp1, 1.0), ydag_hy(ybp0, ybp1, xb0, xb1, -1.0));
+    }
+    pi[sa] = fma(-dt, fax, pax);
+    pi[V + sa] = fma(-dt, fay, pay);
+    pi[sb] = fma(-dt, fbx, pbx);
+    pi[V + sb] = fma(-dt, fby, pby);
+  }
+}
+
+// theta += dt pi ; U = exp(i theta), one pass over the 2 V links.  One fma: the phases are within one rounding of a host `theta + dt * pi`.
+__global__ __launch_bounds__(BLOCK) void k_hmc_link_update(double* __restrict__ theta, cplx* __restrict__ gauge, const double* __restrict__ pi, long n, double dt) {
+  for (long i = (long)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (long)gridDim.x * BLOCK) {
+    const double th = fma(dt, pi[i], theta[i]);
+    double s, c;
+    sincos(th, &s, &c);
+    theta[i] = th;
+    gauge[i] = cmake(c, s);
+  }
+}
+
+}  // namespace qmg
+
+using namespace qmg;
+
+extern "C" {
+
+// pi -= dt (Fg + Ff).  pi: DEVICE double[2 Lx Ly]; gauge: DEVICE complex<double>[2 Lx Ly], the links exp(i theta) that qmg_hmc_link_update
+// keeps beside the phases; X = (D^dag D)^-1 phi and Y = D X: DEVICE complex<double>[2 Lx Ly] spinors.  flags & QMG_HMC_GAUGE_ONLY drops
+// the fermion force (X and Y are not read and may be null).  pi must not overlap the other fields.
+int qmg_hmc_momentum_update(double* pi, const void* gauge, const void* X, const void* Y, int Lx, int Ly, double beta, double dt, unsigned flags, void* stream) {
+  if (!pi || !gauge || !valid_lattice(Lx, Ly) || beta != beta || dt != dt || (flags & ~(unsigned)QMG_HMC_GAUGE_ONLY)) return QMG_ERR_INVALID;
+  const bool fermions = !(flags & QMG_HMC_GAUGE_ONLY);
+  if (fermions && (!X || !Y)) return QMG_ERR_INVALID;
+  const unsigned g = grid_1d((size_t)Lx * Ly / 2);
+  if (fermions) k_hmc_momentum_update<true><<<g, BLOCK, 0, as_stream(stream)>>>(pi, (const cplx*)gauge, (const cplx*)X, (const cplx*)Y, Lx, Ly, beta, dt);
+  else k_hmc_momentum_update<false><<<g, BLOCK, 0, as_stream(stream)>>>(pi, (const cplx*)gauge, nullptr, nullptr, Lx, Ly, beta, dt);
+  QMG_LAUNCH_CHECK();
+  return QMG_SUCCESS;
+}
+
+// theta += dt pi ; gauge = exp(i theta).  theta, pi: DEVICE double[n]; gauge: DEVICE complex<double>[n]; n = 2 Lx Ly links.
+int qmg_hmc_link_update(double* theta, void* gauge, const double* pi, size_t n, double dt, void* stream) {
+  if ((!theta || !gauge || !pi) && n) return QMG_ERR_INVALID;
+  if (dt != dt) return QMG_ERR_INVALID;
+  if (n == 0) return QMG_SUCCESS;
+  k_hmc_link_update<<<grid_1d(n), BLOCK, 0, as_stream(stream)>>>(theta, (cplx*)gauge, pi, (long)n, dt);
+  QMG_LAUNCH_CHECK();
+  return QMG_SUCCESS;
+}
+
+// Momentum refresh: pi ~ N(0, 1) per link, a function of (seed, trajectory) alone.  The n doubles are filled as n/2 complex numbers by
+// qmg_gaussian, whose Box-Muller pair has unit variance in EACH real component; n must be even (it is 2 Lx Ly).
+int qmg_hmc_momentum_refresh(double* pi, size_t n, unsigned long long seed, unsigned long long trajectory, void* stream) {
+  if ((!pi && n) || (n & 1)) return QMG_ERR_INVALID;
+  return qmg_gaussian(pi, n / 2, qmg_hmc_stream_seed(seed, trajectory, 0), stream);
+}
+
+// The seed of random field number `field` of trajectory `trajectory` (0: momenta, 1: pseudofermion noise, 2: Metropolis number): an
+// injective-looking 64-bit mix of the three, so that neither trajectories nor the fields of one trajectory share a stream.
+unsigned long long qmg_hmc_stream_seed(unsigned long long seed, unsigned long long trajectory, int field) {
+  unsigned long long z = seed * 0x9E3779B97F4A7C15ull + (3ull * trajectory + (unsigned long long)field + 1ull) * 0xD1B54A32D192ED03ull;
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+
+}  // extern "C"

@@ -1,0 +1,73 @@
+// hmc_parity -- the deterministic part of SchwingerHMC (include/qmg/hmc.hpp) on fields the caller supplies, for tests/test_gpu_hmc.py:
+//   ./hmc_parity L gauge_file dir beta mass n_flavours tau n_steps cg_eps
+// gauge_file: phases in the reference's text format (read_phase_u1).  dir/pi.bin: 2 L^2 doubles, dir/phi.bin: 2 L^2 complex<double>, both in
+// the device layout.  Runs md_evolve forward, dumps dir/theta_fwd.bin and dir/pi_fwd.bin, negates the momenta, runs md_evolve again and dumps
+// dir/theta_back.bin and dir/pi_back.bin.  Prints
+//   [MD] forward dH <dH> cg <iterations> converged <0|1> plaq <plaquette>
+//   [MD] back    dH <dH> cg <iterations> converged <0|1> plaq <plaquette>
+#include <cstdio>
+#include <iomanip>
+#include <iostream>
+#include <string>
+#include <vector>
+
+#include "../include/qmg/qmg.hpp"
+#include "driver_common.hpp"
+
+using namespace std;
+
+template <typename T> static bool load(const string& path, T* dev, size_t n) {
+  vector<T> h(n);
+  FILE* f = fopen(path.c_str(), "rb");
+  if (!f) { cout << "[QMG-ERROR]: cannot open " << path << "\n"; return false; }
+  const size_t got = fread(h.data(), sizeof(T), n, f);
+  fclose(f);
+  if (got != n) { cout << "[QMG-ERROR]: " << path << " is too short\n"; return false; }
+  qmg::upload(dev, h.data(), n);
+  return true;
+}
+template <typename T> static void dump(const string& path, const T* dev, size_t n) {
+  vector<T> h = qmg::to_host(dev, n);
+  FILE* f = fopen(path.c_str(), "wb");
+  if (!f) { cout << "[QMG-ERROR]: cannot open " << path << " for writing\n"; return; }
+  fwrite(h.data(), sizeof(T), n, f);
+  fclose(f);
+}
+
+int main(int argc, char** argv) {
+  qmg_driver::Guard guard;
+  if (argc < 10) { cout << "usage: ./hmc_parity L gauge_file dir beta mass n_flavours tau n_steps cg_eps\n"; return -1; }
+  if (!qmg::ok(qmg_init(0), "qmg_init")) return 2;
+  const int L = stoi(argv[1]);
+  const string gauge_file = argv[2], dir = argv[3];
+  const double beta = stod(argv[4]), mass = stod(argv[5]);
+  const int n_flavours = stoi(argv[6]);
+  const double tau = stod(argv[7]);
+  const int n_steps = stoi(argv[8]);
+  const double cg_eps = stod(argv[9]);
+
+  Lattice2D lat_gauge(L, L, 1);
+  const size_t n_links = (size_t)lat_gauge.get_size_gauge(), cv = 2 * (size_t)L * L;
+  double* phases = allocate_vector<double>(n_links);
+  double* pi = allocate_vector<double>(n_links);
+  complex<double>* phi = allocate_vector<complex<double>>(cv);
+  int rc = 0;
+  if (!read_phase_u1(phases, &lat_gauge, gauge_file) || !load(dir + "/pi.bin", pi, n_links) || (n_flavours && !load(dir + "/phi.bin", phi, cv))) rc = 3;
+  if (!rc) {
+    HeatbathRng generator(1);
+    SchwingerHMC hmc(phases, L, L, beta, mass, n_flavours, tau, n_steps, cg_eps, 20000, generator);
+    if (!hmc.ok()) rc = 4;
+    cout << setprecision(17);
+    for (int leg = 0; leg < 2 && !rc; leg++) {
+      const HmcResult r = hmc.md_evolve(pi, phi);
+      cout << "[MD] " << (leg ? "back" : "forward") << " dH " << r.dH << " cg " << r.cg_iterations << " converged " << (r.cg_converged ? 1 : 0) << " plaq " << r.plaquette << "\n";
+      dump(dir + (leg ? "/theta_back.bin" : "/theta_fwd.bin"), phases, n_links);
+      dump(dir + (leg ? "/pi_back.bin" : "/pi_fwd.bin"), pi, n_links);
+      if (!r.cg_converged) rc = 1;
+      cax(-1.0, (complex<double>*)pi, n_links / 2);   // flip the momenta
+    }
+  }
+  deallocate_vector(&phases); deallocate_vector(&pi); deallocate_vector(&phi);
+  qmg::VecPool::release_all();
+  return qmg_driver::leave(rc);
+}

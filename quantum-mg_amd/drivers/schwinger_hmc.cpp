@@ -1,0 +1,81 @@
+// schwinger_hmc -- dynamical Schwinger-model ensembles: compact U(1) with two degenerate Wilson flavours (or none) by hybrid Monte Carlo
+// (include/qmg/hmc.hpp: leapfrog over tau = 1, Metropolis test, everything on the device).
+//   ./schwinger_hmc L beta mass n_flavours n_traj n_therm n_steps seed [out.dat [cold|heatbath]]
+// n_therm trajectories of thermalisation, then n_traj measured ones.  The start is a non-compact heatbath field at the same beta (100 sweeps)
+// unless `cold` is given.  One line per trajectory:
+//   [HMC] <index> dH <dH> acc <0|1> plaq <plaquette> Q <topological charge> cg <CG iterations of the trajectory>
+// and at the end the acceptance rate and <exp(-dH)> (which is 1 in equilibrium) with its jackknife error over the measured trajectories:
+//   [HMC-FINAL] trajectories <n> acceptance <rate> exp_mdH <mean> +/- <error> plaq <mean> +/- <error> unconverged <count>
+// out.dat receives the last configuration through write_gauge_u1 (the text format the n13 / n15 / n19 / n22 drivers read) and is read back
+// through read_gauge_u1: [HMC-READBACK] plaq <plaquette> Q <charge>.
+// Exit status 1 if any CG did not converge.
+#include <cmath>
+#include <iomanip>
+#include <iostream>
+#include <string>
+#include <vector>
+
+#include "../include/qmg/qmg.hpp"
+#include "driver_common.hpp"
+
+using namespace std;
+
+int main(int argc, char** argv) {
+  qmg_driver::Guard guard;
+  if (argc < 9) { cout << "usage: ./schwinger_hmc L beta mass n_flavours n_traj n_therm n_steps seed [out.dat [cold|heatbath]]\n"; return -1; }
+  if (!qmg::ok(qmg_init(0), "qmg_init")) return 2;
+  const int L = stoi(argv[1]);
+  const double beta = stod(argv[2]), mass = stod(argv[3]);
+  const int n_flavours = stoi(argv[4]), n_traj = stoi(argv[5]), n_therm = stoi(argv[6]), n_steps = stoi(argv[7]);
+  HeatbathRng generator(stoull(argv[8]));
+  const string out_cfg = (argc > 9) ? argv[9] : "";
+  const bool cold = (argc > 10) && string(argv[10]) == "cold";
+  const double tau = 1.0, cg_eps = 1e-10;
+  const int cg_max_iter = 20000;
+
+  Lattice2D lat_gauge(L, L, 1);
+  const size_t n_links = (size_t)lat_gauge.get_size_gauge();
+  double* phases = allocate_vector<double>(n_links);
+  qmg::ok(qmg_memset_zero(phases, sizeof(double) * n_links, qmg::current_stream()), "qmg_memset_zero");
+  if (!cold) heatbath_noncompact_update(phases, &lat_gauge, beta, 100, generator);
+
+  int unconverged = 0, accepted = 0;
+  vector<double> w, plaq;
+  {
+    SchwingerHMC hmc(phases, L, L, beta, mass, n_flavours, tau, n_steps, cg_eps, cg_max_iter, generator);
+    if (!hmc.ok()) return qmg_driver::leave(3);
+    cout << setprecision(10);
+    for (int i = 0; i < n_therm + n_traj; i++) {
+      const HmcResult r = hmc.trajectory();
+      cout << "[HMC] " << i << " dH " << r.dH << " acc " << (r.accepted ? 1 : 0) << " plaq " << r.plaquette << " Q " << r.topo << " cg " << r.cg_iterations << "\n";
+      if (!r.cg_converged) unconverged++;
+      if (i >= n_therm) { accepted += r.accepted ? 1 : 0; w.push_back(exp(-r.dH)); plaq.push_back(r.plaquette); }
+    }
+    // jackknife over single trajectories (for a plain mean: the standard error)
+    auto mean_err = [](const vector<double>& v, double& m, double& e) {
+      const size_t n = v.size();
+      m = 0.0; e = 0.0;
+      if (!n) return;
+      for (double x : v) m += x;
+      m /= (double)n;
+      if (n < 2) return;
+      double s = 0.0;
+      for (double x : v) { const double jk = (m * (double)n - x) / (double)(n - 1); s += (jk - m) * (jk - m); }
+      e = sqrt(s * (double)(n - 1) / (double)n);
+    };
+    double wm, we, pm, pe;
+    mean_err(w, wm, we);
+    mean_err(plaq, pm, pe);
+    cout << "[HMC-FINAL] trajectories " << n_traj << " acceptance " << (n_traj ? (double)accepted / n_traj : 0.0) << " exp_mdH " << wm << " +/- " << we << " plaq " << pm << " +/- " << pe
+         << " unconverged " << unconverged << "\n";
+    if (!out_cfg.empty()) {   // written, and read back the way the other drivers will read it
+      write_gauge_u1(hmc.links(), &lat_gauge, out_cfg);
+      complex<double>* check = allocate_vector<complex<double>>(n_links);
+      if (read_gauge_u1(check, &lat_gauge, out_cfg)) cout << "[HMC-READBACK] plaq " << std::real(get_plaquette_u1(check, &lat_gauge)) << " Q " << get_topo_u1(check, &lat_gauge) << "\n";
+      deallocate_vector(&check);
+    }
+  }
+  deallocate_vector(&phases);
+  qmg::VecPool::release_all();
+  return qmg_driver::leave(unconverged == 0 ? 0 : 1);
+}

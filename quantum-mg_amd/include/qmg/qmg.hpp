@@ -14,4 +14,5 @@
 #include "eigen.hpp"
 #include "u1.hpp"
 #include "reductions.hpp"
+#include "hmc.hpp"
 #endif
