@@ -195,6 +195,20 @@ int qmg_hmc_momentum_refresh(double* pi, size_t n, unsigned long long seed, unsi
 /* the generator seed of random field `field` (0 momenta, 1 pseudofermion noise, 2 Metropolis number) of a trajectory */
 unsigned long long qmg_hmc_stream_seed(unsigned long long seed, unsigned long long trajectory, int field);
 
+/* ---- gradient (Wilson) flow and Wilson / Polyakov loops for compact U(1) (csrc/qmg_flow.hip; not in the reference); fp64, single domain ----
+ * d theta / dt = -dS_w/dtheta, S_w = sum_x (1 - cos P(x)): the gauge force of qmg_hmc_momentum_update at beta = 1.  Luescher's third-order
+ * Runge-Kutta step in two registers, Z = -eps dS_w/dtheta:  A = Z, theta += A/4;  A = 8/9 Z - 17/36 A, theta += A;  A = 3/4 Z - A, theta += A.
+ * theta, acc: DEVICE double[2 Lx Ly] in the (mu, eo, y, x) order; gauge*: the links exp(i theta), DEVICE complex<double>[2 Lx Ly]. */
+/* one stage (1, 2, 3), one launch: Z from gauge_in, acc and theta updated in place, gauge_out = exp(i theta); gauge_out != gauge_in */
+int qmg_u1_flow_stage(double* theta, double* acc, void* gauge_out, const void* gauge_in, int Lx, int Ly, double eps, int stage, void* stream);
+/* n_steps full steps; gauge = exp(i theta) on entry and on return.  n_steps == 0 or eps == 0 leave both fields bit for bit. */
+int qmg_u1_flow(double* theta, void* gauge, int Lx, int Ly, double eps, int n_steps, void* stream);
+/* lattice averages of the planar R x T loops, 1 <= R <= r_max <= Lx/2, 1 <= T <= t_max <= Ly/2, from running line products (two passes
+ * over the lattice per pair): out_host[2 ((R-1) t_max + (T-1))] = real part, [.. + 1] = imaginary part.  Synchronous. */
+int qmg_u1_wilson_loops(const void* gauge, int Lx, int Ly, int r_max, int t_max, double* out_host, void* stream);
+/* Polyakov loops: out_host[0..1] = average over y of prod_x U_x(x, y), out_host[2..3] = average over x of prod_y U_y(x, y).  Synchronous. */
+int qmg_u1_polyakov(const void* gauge, int Lx, int Ly, double* out_host, void* stream);
+
 /* ---------------- stencil variants (device side) ---------------- */
 /* build_dagger_stencil (stencil_2d.h:1080-1139); also serves build_rbj_dagger_stencil (:1989-2060). */
 int qmg_build_dagger(void* dagger_clover, void* dagger_hopping, const void* clover, const void* hopping,

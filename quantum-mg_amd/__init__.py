@@ -53,6 +53,7 @@ ABI_SYMBOLS = [
     "qmg_u1_heatbath_noncompact", "qmg_u1_phase_to_gauge", "qmg_u1_gauge_to_phase", "qmg_u1_plaquette", "qmg_u1_noncompact_action",
     "qmg_u1_hot_gauge", "qmg_u1_gauss_gauge", "qmg_u1_random_trans", "qmg_u1_gauge_transform", "qmg_u1_ape_smear", "qmg_u1_instanton", "qmg_u1_noncompact_instanton",
     "qmg_hmc_momentum_update", "qmg_hmc_link_update", "qmg_hmc_momentum_refresh", "qmg_hmc_stream_seed",
+    "qmg_u1_flow_stage", "qmg_u1_flow", "qmg_u1_wilson_loops", "qmg_u1_polyakov",
 ]
 
 
@@ -777,6 +778,30 @@ def hmc_stream_seed(seed, trajectory, field):
     f = lib().qmg_hmc_stream_seed
     f.restype = C.c_ulonglong
     return f(C.c_ulonglong(seed), C.c_ulonglong(trajectory), field)
+
+
+def u1_flow_stage(theta, acc, gauge_out, gauge_in, Lx, Ly, eps, stage, stream=None):
+    """one Runge-Kutta stage (1, 2, 3) of the Wilson flow: acc and theta in place, gauge_out = exp(i theta); neighbours from gauge_in"""
+    check(lib().qmg_u1_flow_stage(_vp(theta), _vp(acc), _vp(gauge_out), _vp(gauge_in), Lx, Ly, C.c_double(eps), stage, C.c_void_p(stream)), "qmg_u1_flow_stage")
+
+
+def u1_flow(theta, gauge, Lx, Ly, eps, n_steps, stream=None):
+    """n_steps third-order Runge-Kutta steps of the Wilson flow; gauge = exp(i theta) on entry and on return"""
+    check(lib().qmg_u1_flow(_vp(theta), _vp(gauge), Lx, Ly, C.c_double(eps), n_steps, C.c_void_p(stream)), "qmg_u1_flow")
+
+
+def u1_wilson_loops(gauge, Lx, Ly, r_max, t_max, stream=None):
+    """W[R - 1, T - 1]: the lattice average of the R x T Wilson loop, a complex (r_max, t_max) array"""
+    out = np.full(2 * r_max * t_max, np.nan)
+    check(lib().qmg_u1_wilson_loops(_vp(gauge), Lx, Ly, r_max, t_max, out.ctypes.data_as(C.POINTER(C.c_double)), C.c_void_p(stream)), "qmg_u1_wilson_loops")
+    return (out[0::2] + 1j * out[1::2]).reshape(r_max, t_max)
+
+
+def u1_polyakov(gauge, Lx, Ly, stream=None):
+    """(Polyakov loop in x averaged over y, Polyakov loop in y averaged over x)"""
+    out = (C.c_double * 4)()
+    check(lib().qmg_u1_polyakov(_vp(gauge), Lx, Ly, out, C.c_void_p(stream)), "qmg_u1_polyakov")
+    return complex(out[0], out[1]), complex(out[2], out[3])
 
 
 def set_tuning(key, value):

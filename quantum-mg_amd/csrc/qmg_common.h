@@ -267,6 +267,7 @@ void release_batch_workspace();
 void release_stencil_workspace();
 void release_deflate_workspace();   // qmg_deflate.hip
 void release_u1_workspace();        // qmg_u1.hip
+void release_flow_workspace();      // qmg_flow.hip
 extern int g_setup_fused; // qmg_setup.hip; "setup_fused"
 extern int g_wilson_pair;      // qmg_wilson.hip; "wilson_pair"
 extern long g_blas_nt_bytes;   // qmg_blas.hip; "blas_nt_mb"

@@ -93,6 +93,7 @@ int qmg_shutdown(void) {
   release_stencil_workspace();
   release_deflate_workspace();
   release_u1_workspace();
+  release_flow_workspace();
   QMG_HIP_CHECK(hipDeviceSynchronize());
   return QMG_SUCCESS;
 }

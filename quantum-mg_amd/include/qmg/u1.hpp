@@ -180,4 +180,64 @@ inline double get_noncompact_action_u1(double* phase_field, double beta, Lattice
   return o;
 }
 
+// ---- Wilson flow and Wilson / Polyakov loops (csrc/qmg_flow.hip; not in the reference).  fp64, single domain: y-slabs are refused. ----
+inline bool u1_flow_refused(Lattice2D* lat, const char* who) {
+  if (lat->get_nc() != 1) { std::cout << "[QMG-ERROR]: U1 gauge functions require Nc = 1 lattice.\n"; return true; }
+  if (qmg::slab().on) { std::cout << "[QMG-ERROR]: " << who << " does not run on y-slabs.\n"; return true; }
+  return false;
+}
+
+// Flows a link field and keeps the phases theta (U = exp(i theta)) across calls, so that "flow k steps, measure, flow k steps, ..." never
+// goes back through arg.  `gauge_field` is the caller's and is flowed in place; t is the flow time reached.
+class WilsonFlowU1 {
+  WilsonFlowU1(WilsonFlowU1 const&);
+  WilsonFlowU1& operator=(WilsonFlowU1 const&);
+  Lattice2D* lat;
+  complex<double>* gauge;
+  double* theta;
+  double t;
+
+ public:
+  WilsonFlowU1(complex<double>* gauge_field, Lattice2D* lattice) : lat(lattice), gauge(gauge_field), theta(0), t(0.0) {
+    if (u1_flow_refused(lat, "WilsonFlowU1")) return;
+    theta = allocate_vector<double>((size_t)lat->get_size_gauge());
+    if (!theta) { std::cout << "[QMG-ERROR]: WilsonFlowU1: out of device memory.\n"; return; }
+    reset();
+  }
+  ~WilsonFlowU1() { deallocate_vector(&theta); }
+  bool ok() const { return theta != 0; }
+  // take the phases from the links again (after the caller changed them) and restart the clock
+  void reset() {
+    if (!theta) return;
+    qmg::ok(qmg_u1_gauge_to_phase(theta, gauge, (size_t)lat->get_size_gauge(), qmg::current_stream()), "qmg_u1_gauge_to_phase");
+    t = 0.0;
+  }
+  // n_steps third-order Runge-Kutta steps of size eps
+  void flow(double eps, int n_steps) {
+    if (!theta) { std::cout << "[QMG-ERROR]: WilsonFlowU1::flow called on an object that was refused.\n"; return; }
+    if (qmg::ok(qmg_u1_flow(theta, gauge, lat->get_dim_mu(0), lat->get_dim_mu(1), eps, n_steps, qmg::current_stream()), "qmg_u1_flow")) t += eps * n_steps;
+  }
+  double time() const { return t; }
+  double* phases() { return theta; }
+  complex<double>* links() { return gauge; }
+  double energy() { return 1.0 - std::real(get_plaquette_u1(gauge, lat)); }   // E(t) = S_w / V
+};
+
+// n_steps steps of size eps on a link field, in place
+inline void wilson_flow_u1(complex<double>* gauge_field, Lattice2D* lat, double eps, int n_steps) {
+  WilsonFlowU1 f(gauge_field, lat);
+  if (f.ok()) f.flow(eps, n_steps);
+}
+
+// out[(R - 1) t_max + (T - 1)] = lattice average of the R x T Wilson loop in the x-y plane, 1 <= R <= r_max <= Lx/2, 1 <= T <= t_max <= Ly/2; `out` is a HOST array
+inline bool get_wilson_loops_u1(complex<double>* gauge_field, Lattice2D* lat, int r_max, int t_max, complex<double>* out) {
+  if (u1_flow_refused(lat, "get_wilson_loops_u1")) return false;
+  return qmg::ok(qmg_u1_wilson_loops(gauge_field, lat->get_dim_mu(0), lat->get_dim_mu(1), r_max, t_max, reinterpret_cast<double*>(out), qmg::current_stream()), "qmg_u1_wilson_loops");
+}
+// out[0]: the Polyakov loop in x averaged over y, out[1]: in y averaged over x; `out` is a HOST array
+inline bool get_polyakov_u1(complex<double>* gauge_field, Lattice2D* lat, complex<double>* out) {
+  if (u1_flow_refused(lat, "get_polyakov_u1")) return false;
+  return qmg::ok(qmg_u1_polyakov(gauge_field, lat->get_dim_mu(0), lat->get_dim_mu(1), reinterpret_cast<double*>(out), qmg::current_stream()), "qmg_u1_polyakov");
+}
+
 #endif
