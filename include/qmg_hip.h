@@ -188,6 +188,12 @@ int qmg_u1_noncompact_instanton(double* phase, int Lx, int Ly, double Q, void* s
 enum { QMG_HMC_GAUGE_ONLY = 1u };   /* flags of qmg_hmc_momentum_update: no fermion force, X and Y may be null */
 /* pi -= dt (dS_g/dtheta + dS_f/dtheta) in one pass; X = (D^dag D)^-1 phi, Y = D X: DEVICE complex<double>[2 Lx Ly] */
 int qmg_hmc_momentum_update(double* pi, const void* gauge, const void* X, const void* Y, int Lx, int Ly, double beta, double dt, unsigned flags, void* stream);
+/* pi -= dt (dS_g/dtheta + sum_j weights[j] Ff(X[j], Y[j])) in one pass: the kick of a rational (one-flavour RHMC) pseudofermion action, Ff the
+ * bilinear of the two-flavour force.  X, Y: HOST arrays of n_poles DEVICE spinors, X[j] = (D^dag D + mu_j^2)^-1 phi, Y[j] = D X[j]; weights: HOST
+ * double[n_poles].  16 poles per launch, further poles in further launches.  n_poles = 0 or QMG_HMC_GAUGE_ONLY: the pure-gauge kick (X, Y,
+ * weights may be null).  n_poles = 1 with weight 1 gives the bits of the two-flavour entry above. */
+int qmg_hmc_momentum_update_poles(double* pi, const void* gauge, const void* const* X, const void* const* Y, const double* weights, int n_poles, int Lx, int Ly,
+                                  double beta, double dt, unsigned flags, void* stream);
 /* theta += dt pi ; gauge = exp(i theta) in one pass over n = 2 Lx Ly links */
 int qmg_hmc_link_update(double* theta, void* gauge, const double* pi, size_t n, double dt, void* stream);
 /* pi ~ N(0, 1) per link from the counter-based generator, a function of (seed, trajectory) alone; n even */

@@ -52,7 +52,7 @@ ABI_SYMBOLS = [
     "qmg_basis_dot_t", "qmg_basis_update_t", "qmg_batch_deflate_t",
     "qmg_u1_heatbath_noncompact", "qmg_u1_phase_to_gauge", "qmg_u1_gauge_to_phase", "qmg_u1_plaquette", "qmg_u1_noncompact_action",
     "qmg_u1_hot_gauge", "qmg_u1_gauss_gauge", "qmg_u1_random_trans", "qmg_u1_gauge_transform", "qmg_u1_ape_smear", "qmg_u1_instanton", "qmg_u1_noncompact_instanton",
-    "qmg_hmc_momentum_update", "qmg_hmc_link_update", "qmg_hmc_momentum_refresh", "qmg_hmc_stream_seed",
+    "qmg_hmc_momentum_update", "qmg_hmc_momentum_update_poles", "qmg_hmc_link_update", "qmg_hmc_momentum_refresh", "qmg_hmc_stream_seed",
     "qmg_u1_flow_stage", "qmg_u1_flow", "qmg_u1_wilson_loops", "qmg_u1_polyakov",
 ]
 
@@ -763,6 +763,16 @@ def hmc_momentum_update(pi, gauge, X, Y, Lx, Ly, beta, dt, flags=0, stream=None)
     """pi -= dt (gauge force + two-flavour Wilson force); flags = HMC_GAUGE_ONLY drops the fermions (X, Y may be None)"""
     check(lib().qmg_hmc_momentum_update(_vp(pi), _vp(gauge), _vp(X), _vp(Y), Lx, Ly, C.c_double(beta), C.c_double(dt), C.c_uint(flags), C.c_void_p(stream)),
           "qmg_hmc_momentum_update")
+
+
+def hmc_momentum_update_poles(pi, gauge, X, Y, weights, Lx, Ly, beta, dt, flags=0, stream=None, n_poles=None):
+    """pi -= dt (gauge force + sum_j weights[j] Ff(X[j], Y[j])) in one pass; X, Y: sequences of device spinors, weights: floats (None: null)"""
+    n = n_poles if n_poles is not None else (len(weights) if weights is not None else 0)
+    xs = (C.c_void_p * max(len(X), 1))(*[_vp(x).value for x in X]) if X is not None else None
+    ys = (C.c_void_p * max(len(Y), 1))(*[_vp(y).value for y in Y]) if Y is not None else None
+    ws = (C.c_double * max(len(weights), 1))(*[float(w) for w in weights]) if weights is not None else None
+    check(lib().qmg_hmc_momentum_update_poles(_vp(pi), _vp(gauge), xs, ys, ws, n, Lx, Ly, C.c_double(beta), C.c_double(dt), C.c_uint(flags), C.c_void_p(stream)),
+          "qmg_hmc_momentum_update_poles")
 
 
 def hmc_link_update(theta, gauge, pi, n, dt, stream=None):

@@ -102,6 +102,82 @@ __global__ __launch_bounds__(BLOCK) void k_hmc_momentum_update(double* __restric
   }
 }
 
+// The pole list of one launch of k_hmc_momentum_update_poles: device pointers and weights travel as kernel arguments (the way BatchCgm
+// of qmg_batch.hip carries its shift lists), so a launch needs no table in device memory.
+#define HMC_POLES_J 16
+struct HmcPoles {
+  const cplx* X[HMC_POLES_J];
+  const cplx* Y[HMC_POLES_J];
+  double w[HMC_POLES_J];
+};
+
+// pi -= dt (Fg + sum_j w_j Ff(X_j, Y_j)), every link in one pass: the kick of a rational pseudofermion action
+//   S = c0 phi^dag (1 + sum_j rho_j (D^dag D + mu_j^2)^-1) phi,   X_j = (D^dag D + mu_j^2)^-1 phi,  Y_j = D X_j,  w_j = c0 rho_j.
+// Thread mapping, index wrapping and the expressions of k_hmc_momentum_update, so that one pole of weight 1 gives its bits: the gauge part
+// first, from its 15 links, of which only the pair's four own links live on into the pole loop; then, pole by pole, the 20 spinor loads in
+// front of that pole's arithmetic and four fused multiply-adds onto the pole sum, to which the gauge part is added last.
+// GAUGE = false (the launches after the first when there are more than HMC_POLES_J poles) loads the four own links alone.
+// Byte model: 64 + 64 n B/site -- pi read and written (32), two links (32), per pole X_j and Y_j (64).
+template <bool GAUGE>
+__global__ __launch_bounds__(BLOCK) void k_hmc_momentum_update_poles(double* __restrict__ pi, const cplx* __restrict__ gauge, const HmcPoles poles, int n_poles,
+                                                                     int Lx, int Ly, double beta, double dt) {
+  const long V = (long)Lx * Ly;
+  const int h = Lx >> 1;
+  const long npairs = V / 2;
+  const cplx* __restrict__ Ux = gauge;
+  const cplx* __restrict__ Uy = gauge + V;
+  for (long t = (long)blockIdx.x * BLOCK + threadIdx.x; t < npairs; t += (long)gridDim.x * BLOCK) {
+    const int xh = (int)(t % h), y = (int)(t / h);
+    const int yp = (y + 1 == Ly) ? 0 : y + 1, ym = (y == 0) ? Ly - 1 : y - 1;
+    const int xl = (xh == 0) ? h - 1 : xh - 1, xr = (xh + 1 == h) ? 0 : xh + 1;
+    const int q = y & 1, qp = yp & 1, qm = ym & 1;
+    const long ra = (long)(y + q * Ly) * h, rb = (long)(y + (1 - q) * Ly) * h;
+    const long rap = (long)(yp + qp * Ly) * h, rbp = (long)(yp + (1 - qp) * Ly) * h;
+    const long sa = ra + xh, sb = rb + xh;
+    const double pax = pi[sa], pay = pi[V + sa], pbx = pi[sb], pby = pi[V + sb];
+    const cplx ax = Ux[sa], ay = Uy[sa], bx = Ux[sb], by = Uy[sb];
+    double gax = 0.0, gay = 0.0, gbx = 0.0, gby = 0.0;   // the differences of sin P of the gauge force
+    if (GAUGE) {
+      const long ram = (long)(ym + qm * Ly) * h, rbm = (long)(ym + (1 - qm) * Ly) * h;
+      const cplx apx = Ux[rap + xh], bpx = Ux[rbp + xh];
+      const cplx amx = Ux[ram + xh], amy = Uy[ram + xh], bmx = Ux[rbm + xh], bmy = Uy[rbm + xh];
+      const cplx lx = Ux[rb + xl], ly = Uy[rb + xl], lpx = Ux[rbp + xl];
+      const cplx ry = Uy[ra + xr], rmy = Uy[ram + xr];
+      const double sPa = im_plaq(ax, by, apx, ay), sPb = im_plaq(bx, ry, bpx, by);
+      const double sPam = im_plaq(amx, bmy, ax, amy), sPbm = im_plaq(bmx, rmy, bx, bmy);
+      const double sPl = im_plaq(lx, ay, lpx, ly);
+      gax = sPa - sPam; gay = sPl - sPa;
+      gbx = sPb - sPbm; gby = sPa - sPb;
+      // Pin the four numbers here: they are used after the pole loop only, and left alone the compiler sinks the plaquettes below the loop
+      // and carries the 15 links through it (212 VGPRs, 2 waves per SIMD instead of 4).
+      asm volatile("" : "+v"(gax), "+v"(gay), "+v"(gbx), "+v"(gby));
+    }
+    // The pole sum starts from -0.0, the one number that fma(w, f, .) leaves every w f at, signed zeros included.
+    double fax = -0.0, fay = -0.0, fbx = -0.0, fby = -0.0;
+    const long sr = ra + xr, sap = rap + xh, sbp = rbp + xh;
+    for (int j = 0; j < n_poles; j++) {
+      const cplx* __restrict__ X = poles.X[j];
+      const cplx* __restrict__ Y = poles.Y[j];
+      const double w = poles.w[j];
+      const cplx xa0 = X[2 * sa], xa1 = X[2 * sa + 1], ya0 = Y[2 * sa], ya1 = Y[2 * sa + 1];
+      const cplx xb0 = X[2 * sb], xb1 = X[2 * sb + 1], yb0 = Y[2 * sb], yb1 = Y[2 * sb + 1];
+      const cplx xr0 = X[2 * sr], xr1 = X[2 * sr + 1], yr0 = Y[2 * sr], yr1 = Y[2 * sr + 1];
+      const cplx xap0 = X[2 * sap], xap1 = X[2 * sap + 1], yap0 = Y[2 * sap], yap1 = Y[2 * sap + 1];
+      const cplx xbp0 = X[2 * sbp], xbp1 = X[2 * sbp + 1], ybp0 = Y[2 * sbp], ybp1 = Y[2 * sbp + 1];
+      fax = fma(w, link_force(ax, ydag_hx(ya0, ya1, xb0, xb1, 1.0), ydag_hx(yb0, yb1, xa0, xa1, -1.0)), fax);
+      fay = fma(w, link_force(ay, ydag_hy(ya0, ya1, xap0, xap1, 1.0), ydag_hy(yap0, yap1, xa0, xa1, -1.0)), fay);
+      fbx = fma(w, link_force(bx, ydag_hx(yb0, yb1, xr0, xr1, 1.0), ydag_hx(yr0, yr1, xb0, xb1, -1.0)), fbx);
+      fby = fma(w, link_force(by, ydag_hy(yb0, yb1, xbp0, xbp1, 1.0), ydag_hy(ybp0, ybp1, xb0, xb1, -1.0)), fby);
+    }
+    // k_hmc_momentum_update's `beta * (...) + Ff` is contracted into one fma by the compiler; written out here so that the bits agree
+    if (GAUGE) { fax = fma(beta, gax, fax); fay = fma(beta, gay, fay); fbx = fma(beta, gbx, fbx); fby = fma(beta, gby, fby); }
+    pi[sa] = fma(-dt, fax, pax);
+    pi[V + sa] = fma(-dt, fay, pay);
+    pi[sb] = fma(-dt, fbx, pbx);
+    pi[V + sb] = fma(-dt, fby, pby);
+  }
+}
+
 // theta += dt pi ; U = exp(i theta), one pass over the 2 V links.  One fma: the phases are within one rounding of a host `theta + dt * pi`.
 __global__ __launch_bounds__(BLOCK) void k_hmc_link_update(double* __restrict__ theta, cplx* __restrict__ gauge, const double* __restrict__ pi, long n, double dt) {
   for (long i = (long)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (long)gridDim.x * BLOCK) {
@@ -130,6 +206,33 @@ int qmg_hmc_momentum_update(double* pi, const void* gauge, const void* X, const 
   if (fermions) k_hmc_momentum_update<true><<<g, BLOCK, 0, as_stream(stream)>>>(pi, (const cplx*)gauge, (const cplx*)X, (const cplx*)Y, Lx, Ly, beta, dt);
   else k_hmc_momentum_update<false><<<g, BLOCK, 0, as_stream(stream)>>>(pi, (const cplx*)gauge, nullptr, nullptr, Lx, Ly, beta, dt);
   QMG_LAUNCH_CHECK();
+  return QMG_SUCCESS;
+}
+
+// pi -= dt (Fg + sum_j weights[j] Ff(X[j], Y[j])) in one pass over the momenta and links.  X, Y: HOST arrays of n_poles DEVICE spinors
+// (X[j] = (D^dag D + mu_j^2)^-1 phi, Y[j] = D X[j]); weights: HOST double[n_poles].  Up to 16 poles go in one launch; further poles take
+// further launches without the gauge force.  n_poles = 0 or flags & QMG_HMC_GAUGE_ONLY is the pure-gauge kick (X, Y, weights are not read
+// and may be null).  One pole of weight 1 gives the bits of qmg_hmc_momentum_update.  pi must not overlap the other fields.
+int qmg_hmc_momentum_update_poles(double* pi, const void* gauge, const void* const* X, const void* const* Y, const double* weights, int n_poles, int Lx, int Ly,
+                                  double beta, double dt, unsigned flags, void* stream) {
+  if (!pi || !gauge || !valid_lattice(Lx, Ly) || beta != beta || dt != dt || n_poles < 0 || (flags & ~(unsigned)QMG_HMC_GAUGE_ONLY)) return QMG_ERR_INVALID;
+  if ((flags & QMG_HMC_GAUGE_ONLY) || n_poles == 0) return qmg_hmc_momentum_update(pi, gauge, nullptr, nullptr, Lx, Ly, beta, dt, QMG_HMC_GAUGE_ONLY, stream);
+  if (!X || !Y || !weights) return QMG_ERR_INVALID;
+  for (int j = 0; j < n_poles; j++)
+    if (!X[j] || !Y[j] || weights[j] != weights[j]) return QMG_ERR_INVALID;
+  const unsigned g = grid_1d((size_t)Lx * Ly / 2);
+  for (int j0 = 0; j0 < n_poles; j0 += HMC_POLES_J) {
+    const int nj = n_poles - j0 < HMC_POLES_J ? n_poles - j0 : HMC_POLES_J;
+    HmcPoles p;
+    for (int j = 0; j < HMC_POLES_J; j++) {
+      p.X[j] = j < nj ? (const cplx*)X[j0 + j] : nullptr;
+      p.Y[j] = j < nj ? (const cplx*)Y[j0 + j] : nullptr;
+      p.w[j] = j < nj ? weights[j0 + j] : 0.0;
+    }
+    if (j0 == 0) k_hmc_momentum_update_poles<true><<<g, BLOCK, 0, as_stream(stream)>>>(pi, (const cplx*)gauge, p, nj, Lx, Ly, beta, dt);
+    else k_hmc_momentum_update_poles<false><<<g, BLOCK, 0, as_stream(stream)>>>(pi, (const cplx*)gauge, p, nj, Lx, Ly, beta, dt);
+    QMG_LAUNCH_CHECK();
+  }
   return QMG_SUCCESS;
 }
 

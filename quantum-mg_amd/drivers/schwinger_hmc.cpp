@@ -9,6 +9,17 @@
 // out.dat receives the last configuration through write_gauge_u1 (the text format the n13 / n15 / n19 / n22 drivers read) and is read back
 // through read_gauge_u1: [HMC-READBACK] plaq <plaquette> Q <charge>.
 // Exit status 1 if any CG did not converge.
+// n_flavours = 1 is RHMC (include/qmg/hmc.hpp) and takes the degree of the rational function and the interval [lo, hi] of the spectrum of
+// (D^dag D)^(1/2) from three more arguments, or from QMG_RHMC_DEGREE (default 8) and QMG_RHMC_LO (required one way or the other); hi = 0 or
+// absent is |2 + mass| + 2:
+//   ./schwinger_hmc L beta mass 1 n_traj n_therm n_steps seed out.dat cold|heatbath [degree lo [hi]]
+// It prints, before the trajectories,
+//   [RHMC] n <degree> ra <lo> rb <hi> delta <delta> det_bound <(1 + delta)^(2 L^2) - 1>
+// (the sampled weight det r(Q^2)^-1 is within that relative distance of det D while the spectrum stays inside the interval) and, after the
+// thermalisation and at the end, SchwingerHMC::range_check on the current field:
+//   [RHMC-CHECK] ratio <|xi^dag (r Q^2 r - 1) xi| / xi^dag xi> bound <2 delta + delta^2> ok <0|1>
+// ok 0 proves that the spectrum has left the interval; the exit status is then 1 as well.
+#include <cstdlib>
 #include <cmath>
 #include <iomanip>
 #include <iostream>
@@ -32,6 +43,15 @@ int main(int argc, char** argv) {
   const bool cold = (argc > 10) && string(argv[10]) == "cold";
   const double tau = 1.0, cg_eps = 1e-10;
   const int cg_max_iter = 20000;
+  int rhmc_degree = 8;
+  double rhmc_lo = 0.0, rhmc_hi = 0.0;
+  if (n_flavours == 1) {
+    if (getenv("QMG_RHMC_DEGREE")) rhmc_degree = atoi(getenv("QMG_RHMC_DEGREE"));
+    if (getenv("QMG_RHMC_LO")) rhmc_lo = atof(getenv("QMG_RHMC_LO"));
+    if (argc > 11) rhmc_degree = stoi(argv[11]);
+    if (argc > 12) rhmc_lo = stod(argv[12]);
+    if (argc > 13) rhmc_hi = stod(argv[13]);
+  }
 
   Lattice2D lat_gauge(L, L, 1);
   const size_t n_links = (size_t)lat_gauge.get_size_gauge();
@@ -39,13 +59,23 @@ int main(int argc, char** argv) {
   qmg::ok(qmg_memset_zero(phases, sizeof(double) * n_links, qmg::current_stream()), "qmg_memset_zero");
   if (!cold) heatbath_noncompact_update(phases, &lat_gauge, beta, 100, generator);
 
-  int unconverged = 0, accepted = 0;
+  int unconverged = 0, accepted = 0, range_failures = 0;
   vector<double> w, plaq;
   {
-    SchwingerHMC hmc(phases, L, L, beta, mass, n_flavours, tau, n_steps, cg_eps, cg_max_iter, generator);
+    SchwingerHMC hmc(phases, L, L, beta, mass, n_flavours, tau, n_steps, cg_eps, cg_max_iter, generator, rhmc_degree, rhmc_lo, rhmc_hi);
     if (!hmc.ok()) return qmg_driver::leave(3);
     cout << setprecision(10);
+    auto rhmc_check = [&]() {
+      const RhmcRangeCheck c = hmc.range_check();
+      cout << "[RHMC-CHECK] ratio " << c.ratio << " bound " << c.bound << " ok " << (c.ok ? 1 : 0) << "\n";
+      if (!c.ok) range_failures++;
+    };
+    if (n_flavours == 1) {
+      const qmg::ZolotarevInvSqrt& z = hmc.rational();
+      cout << "[RHMC] n " << z.n << " ra " << z.ra << " rb " << z.rb << " delta " << z.delta << " det_bound " << expm1(2.0 * L * L * log1p(z.delta)) << "\n";
+    }
     for (int i = 0; i < n_therm + n_traj; i++) {
+      if (n_flavours == 1 && i == n_therm && n_therm > 0) rhmc_check();
       const HmcResult r = hmc.trajectory();
       cout << "[HMC] " << i << " dH " << r.dH << " acc " << (r.accepted ? 1 : 0) << " plaq " << r.plaquette << " Q " << r.topo << " cg " << r.cg_iterations << "\n";
       if (!r.cg_converged) unconverged++;
@@ -68,6 +98,7 @@ int main(int argc, char** argv) {
     mean_err(plaq, pm, pe);
     cout << "[HMC-FINAL] trajectories " << n_traj << " acceptance " << (n_traj ? (double)accepted / n_traj : 0.0) << " exp_mdH " << wm << " +/- " << we << " plaq " << pm << " +/- " << pe
          << " unconverged " << unconverged << "\n";
+    if (n_flavours == 1) rhmc_check();
     if (!out_cfg.empty()) {   // written, and read back the way the other drivers will read it
       write_gauge_u1(hmc.links(), &lat_gauge, out_cfg);
       complex<double>* check = allocate_vector<complex<double>>(n_links);
@@ -77,5 +108,5 @@ int main(int argc, char** argv) {
   }
   deallocate_vector(&phases);
   qmg::VecPool::release_all();
-  return qmg_driver::leave(unconverged == 0 ? 0 : 1);
+  return qmg_driver::leave(unconverged == 0 && range_failures == 0 ? 0 : 1);
 }
