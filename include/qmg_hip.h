@@ -194,6 +194,13 @@ int qmg_hmc_momentum_update(double* pi, const void* gauge, const void* X, const 
  * weights may be null).  n_poles = 1 with weight 1 gives the bits of the two-flavour entry above. */
 int qmg_hmc_momentum_update_poles(double* pi, const void* gauge, const void* const* X, const void* const* Y, const double* weights, int n_poles, int Lx, int Ly,
                                   double beta, double dt, unsigned flags, void* stream);
+/* pi -= dt (dS_g/dtheta + sum_j weights[j] Fs(W[j])) in one pass: the kick of staggered pseudofermions on the even sites, two tastes (one pole
+ * of weight 1) or rooted (one-taste RHMC).  With D = m + H, A = m^2 - H^2: W[j] = X_j (+) (H X_j)_o, X_j = (A_ee + mu_j^2)^-1 phi_e, and
+ * Fs_mu(x) = eta_mu(x) eps(x) Im[U_mu(x) conj(W(x)) W(x+mu)].  W: HOST array of n_poles DEVICE complex<double>[Lx Ly] vectors (nc = 1, even-odd
+ * layout); weights: HOST double[n_poles].  16 poles per launch, further poles in further launches.  n_poles = 0 or QMG_HMC_GAUGE_ONLY: the
+ * pure-gauge kick of qmg_hmc_momentum_update (W, weights may be null). */
+int qmg_hmc_momentum_update_staggered(double* pi, const void* gauge, const void* const* W, const double* weights, int n_poles, int Lx, int Ly, double beta, double dt,
+                                      unsigned flags, void* stream);
 /* theta += dt pi ; gauge = exp(i theta) in one pass over n = 2 Lx Ly links */
 int qmg_hmc_link_update(double* theta, void* gauge, const double* pi, size_t n, double dt, void* stream);
 /* pi ~ N(0, 1) per link from the counter-based generator, a function of (seed, trajectory) alone; n even */

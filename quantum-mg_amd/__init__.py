@@ -52,7 +52,7 @@ ABI_SYMBOLS = [
     "qmg_basis_dot_t", "qmg_basis_update_t", "qmg_batch_deflate_t",
     "qmg_u1_heatbath_noncompact", "qmg_u1_phase_to_gauge", "qmg_u1_gauge_to_phase", "qmg_u1_plaquette", "qmg_u1_noncompact_action",
     "qmg_u1_hot_gauge", "qmg_u1_gauss_gauge", "qmg_u1_random_trans", "qmg_u1_gauge_transform", "qmg_u1_ape_smear", "qmg_u1_instanton", "qmg_u1_noncompact_instanton",
-    "qmg_hmc_momentum_update", "qmg_hmc_momentum_update_poles", "qmg_hmc_link_update", "qmg_hmc_momentum_refresh", "qmg_hmc_stream_seed",
+    "qmg_hmc_momentum_update", "qmg_hmc_momentum_update_poles", "qmg_hmc_momentum_update_staggered", "qmg_hmc_link_update", "qmg_hmc_momentum_refresh", "qmg_hmc_stream_seed",
     "qmg_u1_flow_stage", "qmg_u1_flow", "qmg_u1_wilson_loops", "qmg_u1_polyakov",
 ]
 
@@ -773,6 +773,15 @@ def hmc_momentum_update_poles(pi, gauge, X, Y, weights, Lx, Ly, beta, dt, flags=
     ws = (C.c_double * max(len(weights), 1))(*[float(w) for w in weights]) if weights is not None else None
     check(lib().qmg_hmc_momentum_update_poles(_vp(pi), _vp(gauge), xs, ys, ws, n, Lx, Ly, C.c_double(beta), C.c_double(dt), C.c_uint(flags), C.c_void_p(stream)),
           "qmg_hmc_momentum_update_poles")
+
+
+def hmc_momentum_update_staggered(pi, gauge, W, weights, Lx, Ly, beta, dt, flags=0, stream=None, n_poles=None):
+    """pi -= dt (gauge force + sum_j weights[j] Fs(W[j])), Fs the staggered force; W: a sequence of device nc = 1 vectors, weights: floats (None: null)"""
+    n = n_poles if n_poles is not None else (len(weights) if weights is not None else 0)
+    ws_ = (C.c_void_p * max(len(W), 1))(*[_vp(w).value for w in W]) if W is not None else None
+    ws = (C.c_double * max(len(weights), 1))(*[float(w) for w in weights]) if weights is not None else None
+    check(lib().qmg_hmc_momentum_update_staggered(_vp(pi), _vp(gauge), ws_, ws, n, Lx, Ly, C.c_double(beta), C.c_double(dt), C.c_uint(flags), C.c_void_p(stream)),
+          "qmg_hmc_momentum_update_staggered")
 
 
 def hmc_link_update(theta, gauge, pi, n, dt, stream=None):

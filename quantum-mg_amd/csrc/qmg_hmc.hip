@@ -178,6 +178,90 @@ __global__ __launch_bounds__(BLOCK) void k_hmc_momentum_update_poles(double* __r
   }
 }
 
+// ---- staggered fermions (include/qmg/hmc_staggered.hpp; the independent statement is tests/stag_hmc_numpy.py) ----
+// D = m + H, H psi(x) = -1/2 sum_mu eta_mu(x) [U_mu(x) psi(x+mu) - conj(U_mu(x-mu)) psi(x-mu)] (qmg_staggered_fill: eta_x = 1, eta_y = (-1)^x),
+// A = m^2 - H^2, S_f = phi_e^dag (A_ee + sigma)^-1 phi_e.  With W = X_e (+) (H X_e)_o, X_e = (A_ee + sigma)^-1 phi_e and eps(x) = (-1)^(x+y):
+//   Fs_mu(x) = dS_f/dtheta_mu(x) = eta_mu(x) eps(x) Im[ U_mu(x) conj(W(x)) W(x+mu) ]
+// one complex number per site, two sites per link.
+// The gauge force of a pair of sites without its factor beta: the differences of sin P behind the pair's four momenta, from the pair's own
+// four links (which the caller has loaded) and the eleven around them: the loads and expressions of k_hmc_momentum_update_poles, on the im_plaq
+// both share.  (That kernel keeps its own copy: calling this from it changed its instruction schedule.)
+__device__ __forceinline__ void gauge_force_diffs(const cplx* Ux, const cplx* Uy, long ra, long rb, long rap, long rbp, long ram, long rbm,
+                                                  int xh, int xl, int xr, cplx ax, cplx ay, cplx bx, cplx by, double& gax, double& gay, double& gbx, double& gby) {
+  const cplx apx = Ux[rap + xh], bpx = Ux[rbp + xh];
+  const cplx amx = Ux[ram + xh], amy = Uy[ram + xh], bmx = Ux[rbm + xh], bmy = Uy[rbm + xh];
+  const cplx lx = Ux[rb + xl], ly = Uy[rb + xl], lpx = Ux[rbp + xl];
+  const cplx ry = Uy[ra + xr], rmy = Uy[ram + xr];
+  const double sPa = im_plaq(ax, by, apx, ay), sPb = im_plaq(bx, ry, bpx, by);
+  const double sPam = im_plaq(amx, bmy, ax, amy), sPbm = im_plaq(bmx, rmy, bx, bmy);
+  const double sPl = im_plaq(lx, ay, lpx, ly);
+  gax = sPa - sPam; gay = sPl - sPa;
+  gbx = sPb - sPbm; gby = sPa - sPb;
+}
+
+#define HMC_STAG_J 16
+struct HmcStagPoles {
+  const cplx* W[HMC_STAG_J];
+  double w[HMC_STAG_J];
+};
+// Im[ u conj(a) b ]
+__device__ __forceinline__ double im_u_adag_b(cplx u, cplx a, cplx b) {
+  cplx c = cmake(0.0, 0.0);
+  cmac_conj(c, a, b);
+  return fma(u.x, c.y, u.y * c.x);
+}
+
+// pi -= dt (Fg + sum_j w_j Fs(W_j)), every link in one pass: the kick of two staggered tastes (one pole of weight 1) and of the rooted action
+//   S = c0 phi_e^dag (1 + sum_j rho_j (A_ee + mu_j^2)^-1) phi_e,   w_j = c0 rho_j.
+// Thread mapping and index wrapping of k_hmc_momentum_update_poles: the pair a = (2 xh, y), b = (2 xh + 1, y), so eta_y is +1 on a and -1 on b and
+// eps(a) = (-1)^y = -eps(b).  The gauge part comes first (gauge_force_diffs, pinned as there); then, pole by pole, five loads of W (a, b, the
+// site right of b, the two above) in front of that pole's arithmetic and four fused multiply-adds onto the pole sum.  Every
+// index is a wrapped lattice coordinate.  GAUGE = false (the launches after the first when there are more than HMC_STAG_J poles) loads the
+// four own links alone.  Byte model: 64 + 16 n B/site -- pi read and written (32), two links (32), per pole W_j (16).
+template <bool GAUGE>
+__global__ __launch_bounds__(BLOCK) void k_hmc_momentum_update_staggered(double* __restrict__ pi, const cplx* __restrict__ gauge, const HmcStagPoles poles, int n_poles,
+                                                                         int Lx, int Ly, double beta, double dt) {
+  const long V = (long)Lx * Ly;
+  const int h = Lx >> 1;
+  const long npairs = V / 2;
+  const cplx* __restrict__ Ux = gauge;
+  const cplx* __restrict__ Uy = gauge + V;
+  for (long t = (long)blockIdx.x * BLOCK + threadIdx.x; t < npairs; t += (long)gridDim.x * BLOCK) {
+    const int xh = (int)(t % h), y = (int)(t / h);
+    const int yp = (y + 1 == Ly) ? 0 : y + 1, ym = (y == 0) ? Ly - 1 : y - 1;
+    const int xl = (xh == 0) ? h - 1 : xh - 1, xr = (xh + 1 == h) ? 0 : xh + 1;
+    const int q = y & 1, qp = yp & 1, qm = ym & 1;
+    const long ra = (long)(y + q * Ly) * h, rb = (long)(y + (1 - q) * Ly) * h;
+    const long rap = (long)(yp + qp * Ly) * h, rbp = (long)(yp + (1 - qp) * Ly) * h;
+    const long sa = ra + xh, sb = rb + xh;
+    const double pax = pi[sa], pay = pi[V + sa], pbx = pi[sb], pby = pi[V + sb];
+    const cplx ax = Ux[sa], ay = Uy[sa], bx = Ux[sb], by = Uy[sb];
+    double gax = 0.0, gay = 0.0, gbx = 0.0, gby = 0.0;
+    if (GAUGE) {
+      const long ram = (long)(ym + qm * Ly) * h, rbm = (long)(ym + (1 - qm) * Ly) * h;
+      gauge_force_diffs(Ux, Uy, ra, rb, rap, rbp, ram, rbm, xh, xl, xr, ax, ay, bx, by, gax, gay, gbx, gby);
+      asm volatile("" : "+v"(gax), "+v"(gay), "+v"(gbx), "+v"(gby));   // keep the 15 links out of the pole loop, as in k_hmc_momentum_update_poles
+    }
+    const double ea = q ? -1.0 : 1.0;   // eps(a); eta_x eps = ea, -ea on (a, b); eta_y eps = ea on both
+    double fax = -0.0, fay = -0.0, fbx = -0.0, fby = -0.0;
+    const long sr = ra + xr, sap = rap + xh, sbp = rbp + xh;
+    for (int j = 0; j < n_poles; j++) {
+      const cplx* __restrict__ W = poles.W[j];
+      const double wa = ea * poles.w[j];
+      const cplx a = W[sa], b = W[sb], r = W[sr], ap = W[sap], bp = W[sbp];
+      fax = fma(wa, im_u_adag_b(ax, a, b), fax);
+      fay = fma(wa, im_u_adag_b(ay, a, ap), fay);
+      fbx = fma(-wa, im_u_adag_b(bx, b, r), fbx);
+      fby = fma(wa, im_u_adag_b(by, b, bp), fby);
+    }
+    if (GAUGE) { fax = fma(beta, gax, fax); fay = fma(beta, gay, fay); fbx = fma(beta, gbx, fbx); fby = fma(beta, gby, fby); }
+    pi[sa] = fma(-dt, fax, pax);
+    pi[V + sa] = fma(-dt, fay, pay);
+    pi[sb] = fma(-dt, fbx, pbx);
+    pi[V + sb] = fma(-dt, fby, pby);
+  }
+}
+
 // theta += dt pi ; U = exp(i theta), one pass over the 2 V links.  One fma: the phases are within one rounding of a host `theta + dt * pi`.
 __global__ __launch_bounds__(BLOCK) void k_hmc_link_update(double* __restrict__ theta, cplx* __restrict__ gauge, const double* __restrict__ pi, long n, double dt) {
   for (long i = (long)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (long)gridDim.x * BLOCK) {
@@ -231,6 +315,33 @@ int qmg_hmc_momentum_update_poles(double* pi, const void* gauge, const void* con
     }
     if (j0 == 0) k_hmc_momentum_update_poles<true><<<g, BLOCK, 0, as_stream(stream)>>>(pi, (const cplx*)gauge, p, nj, Lx, Ly, beta, dt);
     else k_hmc_momentum_update_poles<false><<<g, BLOCK, 0, as_stream(stream)>>>(pi, (const cplx*)gauge, p, nj, Lx, Ly, beta, dt);
+    QMG_LAUNCH_CHECK();
+  }
+  return QMG_SUCCESS;
+}
+
+// pi -= dt (Fg + sum_j weights[j] Fs(W[j])) in one pass over the momenta and links, Fs the staggered force above.  W: HOST array of n_poles
+// DEVICE complex<double>[Lx Ly] vectors (nc = 1, even-odd layout; even half (A_ee + mu_j^2)^-1 phi_e, odd half its hopping apply); weights:
+// HOST double[n_poles].  Up to 16 poles go in one launch; further poles take further launches without the gauge force.  n_poles = 0 or
+// flags & QMG_HMC_GAUGE_ONLY is the pure-gauge kick of qmg_hmc_momentum_update (W, weights are not read and may be null).  pi must not
+// overlap the other fields.
+int qmg_hmc_momentum_update_staggered(double* pi, const void* gauge, const void* const* W, const double* weights, int n_poles, int Lx, int Ly, double beta, double dt,
+                                      unsigned flags, void* stream) {
+  if (!pi || !gauge || !valid_lattice(Lx, Ly) || beta != beta || dt != dt || n_poles < 0 || (flags & ~(unsigned)QMG_HMC_GAUGE_ONLY)) return QMG_ERR_INVALID;
+  if ((flags & QMG_HMC_GAUGE_ONLY) || n_poles == 0) return qmg_hmc_momentum_update(pi, gauge, nullptr, nullptr, Lx, Ly, beta, dt, QMG_HMC_GAUGE_ONLY, stream);
+  if (!W || !weights) return QMG_ERR_INVALID;
+  for (int j = 0; j < n_poles; j++)
+    if (!W[j] || weights[j] != weights[j]) return QMG_ERR_INVALID;
+  const unsigned g = grid_1d((size_t)Lx * Ly / 2);
+  for (int j0 = 0; j0 < n_poles; j0 += HMC_STAG_J) {
+    const int nj = n_poles - j0 < HMC_STAG_J ? n_poles - j0 : HMC_STAG_J;
+    HmcStagPoles p;
+    for (int j = 0; j < HMC_STAG_J; j++) {
+      p.W[j] = j < nj ? (const cplx*)W[j0 + j] : nullptr;
+      p.w[j] = j < nj ? weights[j0 + j] : 0.0;
+    }
+    if (j0 == 0) k_hmc_momentum_update_staggered<true><<<g, BLOCK, 0, as_stream(stream)>>>(pi, (const cplx*)gauge, p, nj, Lx, Ly, beta, dt);
+    else k_hmc_momentum_update_staggered<false><<<g, BLOCK, 0, as_stream(stream)>>>(pi, (const cplx*)gauge, p, nj, Lx, Ly, beta, dt);
     QMG_LAUNCH_CHECK();
   }
   return QMG_SUCCESS;

@@ -161,6 +161,9 @@ struct Staggered2D : public EoPrecNc1 {
     }
     return inv;
   }
+  // H = D(0), the hopping part alone, for the staggered molecular dynamics (hmc_staggered.hpp):
+  void apply_hopping(complex<double>* lhs, complex<double>* rhs) { launch(QMG_P_HOPPING | QMG_P_ZERO, lhs, rhs, 0, hopping, 0.0, 0.0, 0.0); }   // lhs = H rhs, lhs != rhs
+  void hop_even_to_odd(complex<double>* w) { launch(QMG_P_OE | QMG_P_ZERO_O, w, w, 0, hopping, 0.0, 0.0, 0.0); }   // w_o = (H w_e)_o in place, w_e kept
   static void apply_minus_hop_sq(complex<double>* lhs, complex<double>* rhs, void* self) {   // lhs = -H^2 rhs
     Staggered2D* st = (Staggered2D*)self;
     const long cv = st->lat->get_size_cv_l();

@@ -15,4 +15,5 @@
 #include "u1.hpp"
 #include "reductions.hpp"
 #include "hmc.hpp"
+#include "hmc_staggered.hpp"
 #endif
