@@ -199,10 +199,9 @@ __device__ __forceinline__ void gauge_force_diffs(const cplx* Ux, const cplx* Uy
   gbx = sPb - sPbm; gby = sPa - sPb;
 }
 
-#define HMC_STAG_J 16
-struct HmcStagPoles {
-  const cplx* W[HMC_STAG_J];
-  double w[HMC_STAG_J];
+struct HmcStagPoles {   // the pole list of one launch of k_hmc_momentum_update_staggered, as HmcPoles
+  const cplx* W[HMC_POLES_J];
+  double w[HMC_POLES_J];
 };
 // Im[ u conj(a) b ]
 __device__ __forceinline__ double im_u_adag_b(cplx u, cplx a, cplx b) {
@@ -216,7 +215,7 @@ __device__ __forceinline__ double im_u_adag_b(cplx u, cplx a, cplx b) {
 // Thread mapping and index wrapping of k_hmc_momentum_update_poles: the pair a = (2 xh, y), b = (2 xh + 1, y), so eta_y is +1 on a and -1 on b and
 // eps(a) = (-1)^y = -eps(b).  The gauge part comes first (gauge_force_diffs, pinned as there); then, pole by pole, five loads of W (a, b, the
 // site right of b, the two above) in front of that pole's arithmetic and four fused multiply-adds onto the pole sum.  Every
-// index is a wrapped lattice coordinate.  GAUGE = false (the launches after the first when there are more than HMC_STAG_J poles) loads the
+// index is a wrapped lattice coordinate.  GAUGE = false (the launches after the first when there are more than HMC_POLES_J poles) loads the
 // four own links alone.  Byte model: 64 + 16 n B/site -- pi read and written (32), two links (32), per pole W_j (16).
 template <bool GAUGE>
 __global__ __launch_bounds__(BLOCK) void k_hmc_momentum_update_staggered(double* __restrict__ pi, const cplx* __restrict__ gauge, const HmcStagPoles poles, int n_poles,
@@ -277,6 +276,27 @@ __global__ __launch_bounds__(BLOCK) void k_hmc_link_update(double* __restrict__ 
 
 using namespace qmg;
 
+// What the two pole kicks (qmg_hmc_momentum_update_poles, _staggered) check first, and the pole lists they check after the pure-gauge case has left: every vector present (B is the
+// second list of vectors, or A again) and no weight a NaN.
+static bool pole_kick_args_valid(const double* pi, const void* gauge, int Lx, int Ly, double beta, double dt, int n_poles, unsigned flags) {
+  return pi && gauge && valid_lattice(Lx, Ly) && beta == beta && dt == dt && n_poles >= 0 && !(flags & ~(unsigned)QMG_HMC_GAUGE_ONLY);
+}
+static bool pole_lists_valid(const void* const* A, const void* const* B, const double* weights, int n_poles) {
+  if (!A || !B || !weights) return false;
+  for (int j = 0; j < n_poles; j++)
+    if (!A[j] || !B[j] || weights[j] != weights[j]) return false;
+  return true;
+}
+// Poles in chunks of HMC_POLES_J: launch(j0, nj, first) fills the list of poles j0 .. j0 + nj - 1 and launches its kernel, with the gauge
+// force if `first` and without it after.
+template <class Launch> static int launch_pole_chunks(int n_poles, Launch launch) {
+  for (int j0 = 0; j0 < n_poles; j0 += HMC_POLES_J) {
+    launch(j0, n_poles - j0 < HMC_POLES_J ? n_poles - j0 : HMC_POLES_J, j0 == 0);
+    QMG_LAUNCH_CHECK();
+  }
+  return QMG_SUCCESS;
+}
+
 extern "C" {
 
 // pi -= dt (Fg + Ff).  pi: DEVICE double[2 Lx Ly]; gauge: DEVICE complex<double>[2 Lx Ly], the links exp(i theta) that qmg_hmc_link_update
@@ -299,25 +319,20 @@ int qmg_hmc_momentum_update(double* pi, const void* gauge, const void* X, const 
 // and may be null).  One pole of weight 1 gives the bits of qmg_hmc_momentum_update.  pi must not overlap the other fields.
 int qmg_hmc_momentum_update_poles(double* pi, const void* gauge, const void* const* X, const void* const* Y, const double* weights, int n_poles, int Lx, int Ly,
                                   double beta, double dt, unsigned flags, void* stream) {
-  if (!pi || !gauge || !valid_lattice(Lx, Ly) || beta != beta || dt != dt || n_poles < 0 || (flags & ~(unsigned)QMG_HMC_GAUGE_ONLY)) return QMG_ERR_INVALID;
+  if (!pole_kick_args_valid(pi, gauge, Lx, Ly, beta, dt, n_poles, flags)) return QMG_ERR_INVALID;
   if ((flags & QMG_HMC_GAUGE_ONLY) || n_poles == 0) return qmg_hmc_momentum_update(pi, gauge, nullptr, nullptr, Lx, Ly, beta, dt, QMG_HMC_GAUGE_ONLY, stream);
-  if (!X || !Y || !weights) return QMG_ERR_INVALID;
-  for (int j = 0; j < n_poles; j++)
-    if (!X[j] || !Y[j] || weights[j] != weights[j]) return QMG_ERR_INVALID;
+  if (!pole_lists_valid(X, Y, weights, n_poles)) return QMG_ERR_INVALID;
   const unsigned g = grid_1d((size_t)Lx * Ly / 2);
-  for (int j0 = 0; j0 < n_poles; j0 += HMC_POLES_J) {
-    const int nj = n_poles - j0 < HMC_POLES_J ? n_poles - j0 : HMC_POLES_J;
+  return launch_pole_chunks(n_poles, [&](int j0, int nj, bool first) {
     HmcPoles p;
     for (int j = 0; j < HMC_POLES_J; j++) {
       p.X[j] = j < nj ? (const cplx*)X[j0 + j] : nullptr;
       p.Y[j] = j < nj ? (const cplx*)Y[j0 + j] : nullptr;
       p.w[j] = j < nj ? weights[j0 + j] : 0.0;
     }
-    if (j0 == 0) k_hmc_momentum_update_poles<true><<<g, BLOCK, 0, as_stream(stream)>>>(pi, (const cplx*)gauge, p, nj, Lx, Ly, beta, dt);
+    if (first) k_hmc_momentum_update_poles<true><<<g, BLOCK, 0, as_stream(stream)>>>(pi, (const cplx*)gauge, p, nj, Lx, Ly, beta, dt);
     else k_hmc_momentum_update_poles<false><<<g, BLOCK, 0, as_stream(stream)>>>(pi, (const cplx*)gauge, p, nj, Lx, Ly, beta, dt);
-    QMG_LAUNCH_CHECK();
-  }
-  return QMG_SUCCESS;
+  });
 }
 
 // pi -= dt (Fg + sum_j weights[j] Fs(W[j])) in one pass over the momenta and links, Fs the staggered force above.  W: HOST array of n_poles
@@ -327,24 +342,19 @@ int qmg_hmc_momentum_update_poles(double* pi, const void* gauge, const void* con
 // overlap the other fields.
 int qmg_hmc_momentum_update_staggered(double* pi, const void* gauge, const void* const* W, const double* weights, int n_poles, int Lx, int Ly, double beta, double dt,
                                       unsigned flags, void* stream) {
-  if (!pi || !gauge || !valid_lattice(Lx, Ly) || beta != beta || dt != dt || n_poles < 0 || (flags & ~(unsigned)QMG_HMC_GAUGE_ONLY)) return QMG_ERR_INVALID;
+  if (!pole_kick_args_valid(pi, gauge, Lx, Ly, beta, dt, n_poles, flags)) return QMG_ERR_INVALID;
   if ((flags & QMG_HMC_GAUGE_ONLY) || n_poles == 0) return qmg_hmc_momentum_update(pi, gauge, nullptr, nullptr, Lx, Ly, beta, dt, QMG_HMC_GAUGE_ONLY, stream);
-  if (!W || !weights) return QMG_ERR_INVALID;
-  for (int j = 0; j < n_poles; j++)
-    if (!W[j] || weights[j] != weights[j]) return QMG_ERR_INVALID;
+  if (!pole_lists_valid(W, W, weights, n_poles)) return QMG_ERR_INVALID;
   const unsigned g = grid_1d((size_t)Lx * Ly / 2);
-  for (int j0 = 0; j0 < n_poles; j0 += HMC_STAG_J) {
-    const int nj = n_poles - j0 < HMC_STAG_J ? n_poles - j0 : HMC_STAG_J;
+  return launch_pole_chunks(n_poles, [&](int j0, int nj, bool first) {
     HmcStagPoles p;
-    for (int j = 0; j < HMC_STAG_J; j++) {
+    for (int j = 0; j < HMC_POLES_J; j++) {
       p.W[j] = j < nj ? (const cplx*)W[j0 + j] : nullptr;
       p.w[j] = j < nj ? weights[j0 + j] : 0.0;
     }
-    if (j0 == 0) k_hmc_momentum_update_staggered<true><<<g, BLOCK, 0, as_stream(stream)>>>(pi, (const cplx*)gauge, p, nj, Lx, Ly, beta, dt);
+    if (first) k_hmc_momentum_update_staggered<true><<<g, BLOCK, 0, as_stream(stream)>>>(pi, (const cplx*)gauge, p, nj, Lx, Ly, beta, dt);
     else k_hmc_momentum_update_staggered<false><<<g, BLOCK, 0, as_stream(stream)>>>(pi, (const cplx*)gauge, p, nj, Lx, Ly, beta, dt);
-    QMG_LAUNCH_CHECK();
-  }
-  return QMG_SUCCESS;
+  });
 }
 
 // theta += dt pi ; gauge = exp(i theta).  theta, pi: DEVICE double[n]; gauge: DEVICE complex<double>[n]; n = 2 Lx Ly links.

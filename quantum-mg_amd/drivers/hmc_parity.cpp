@@ -5,34 +5,10 @@
 // dir/theta_back.bin and dir/pi_back.bin.  Prints
 //   [MD] forward dH <dH> cg <iterations> converged <0|1> plaq <plaquette>
 //   [MD] back    dH <dH> cg <iterations> converged <0|1> plaq <plaquette>
-#include <cstdio>
-#include <iomanip>
-#include <iostream>
-#include <string>
-#include <vector>
-
-#include "../include/qmg/qmg.hpp"
-#include "driver_common.hpp"
+#include "hmc_parity_common.hpp"
 
 using namespace std;
-
-template <typename T> static bool load(const string& path, T* dev, size_t n) {
-  vector<T> h(n);
-  FILE* f = fopen(path.c_str(), "rb");
-  if (!f) { cout << "[QMG-ERROR]: cannot open " << path << "\n"; return false; }
-  const size_t got = fread(h.data(), sizeof(T), n, f);
-  fclose(f);
-  if (got != n) { cout << "[QMG-ERROR]: " << path << " is too short\n"; return false; }
-  qmg::upload(dev, h.data(), n);
-  return true;
-}
-template <typename T> static void dump(const string& path, const T* dev, size_t n) {
-  vector<T> h = qmg::to_host(dev, n);
-  FILE* f = fopen(path.c_str(), "wb");
-  if (!f) { cout << "[QMG-ERROR]: cannot open " << path << " for writing\n"; return; }
-  fwrite(h.data(), sizeof(T), n, f);
-  fclose(f);
-}
+using namespace hmc_parity;
 
 int main(int argc, char** argv) {
   qmg_driver::Guard guard;
@@ -56,16 +32,8 @@ int main(int argc, char** argv) {
   if (!rc) {
     HeatbathRng generator(1);
     SchwingerHMC hmc(phases, L, L, beta, mass, n_flavours, tau, n_steps, cg_eps, 20000, generator);
-    if (!hmc.ok()) rc = 4;
     cout << setprecision(17);
-    for (int leg = 0; leg < 2 && !rc; leg++) {
-      const HmcResult r = hmc.md_evolve(pi, phi);
-      cout << "[MD] " << (leg ? "back" : "forward") << " dH " << r.dH << " cg " << r.cg_iterations << " converged " << (r.cg_converged ? 1 : 0) << " plaq " << r.plaquette << "\n";
-      dump(dir + (leg ? "/theta_back.bin" : "/theta_fwd.bin"), phases, n_links);
-      dump(dir + (leg ? "/pi_back.bin" : "/pi_fwd.bin"), pi, n_links);
-      if (!r.cg_converged) rc = 1;
-      cax(-1.0, (complex<double>*)pi, n_links / 2);   // flip the momenta
-    }
+    rc = hmc.ok() ? md_legs(hmc, dir, phases, pi, phi, n_links) : 4;
   }
   deallocate_vector(&phases); deallocate_vector(&pi); deallocate_vector(&phi);
   qmg::VecPool::release_all();

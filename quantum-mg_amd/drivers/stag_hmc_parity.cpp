@@ -9,34 +9,10 @@
 // mode heatbath:  reads eta.bin (full lattice); phi_e to phi.bin;  [HB] eta2 <eta^dag eta> spf <S_pf(phi_e)> cg <iterations> converged <0|1>
 // mode rational:  one taste; reads v.bin; r(A_ee) v to rv.bin and r(A_ee) r(A_ee) v to rrv.bin;  [RAT] cg <iterations> converged <0|1>
 // Exit status 1 if a solve did not converge.
-#include <cstdio>
-#include <iomanip>
-#include <iostream>
-#include <string>
-#include <vector>
-
-#include "../include/qmg/qmg.hpp"
-#include "driver_common.hpp"
+#include "hmc_parity_common.hpp"
 
 using namespace std;
-
-template <typename T> static bool load(const string& path, T* dev, size_t n) {
-  vector<T> h(n);
-  FILE* f = fopen(path.c_str(), "rb");
-  if (!f) { cout << "[QMG-ERROR]: cannot open " << path << "\n"; return false; }
-  const size_t got = fread(h.data(), sizeof(T), n, f);
-  fclose(f);
-  if (got != n) { cout << "[QMG-ERROR]: " << path << " is too short\n"; return false; }
-  qmg::upload(dev, h.data(), n);
-  return true;
-}
-template <typename T> static void dump(const string& path, const T* dev, size_t n) {
-  vector<T> h = qmg::to_host(dev, n);
-  FILE* f = fopen(path.c_str(), "wb");
-  if (!f) { cout << "[QMG-ERROR]: cannot open " << path << " for writing\n"; return; }
-  fwrite(h.data(), sizeof(T), n, f);
-  fclose(f);
-}
+using namespace hmc_parity;
 
 int main(int argc, char** argv) {
   qmg_driver::Guard guard;
@@ -62,45 +38,18 @@ int main(int argc, char** argv) {
   if (!rc) {
     HeatbathRng generator(1);
     StaggeredSchwingerHMC hmc(phases, L, L, beta, mass, n_tastes, tau, n_steps, cg_eps, 20000, generator, degree);
-    if (!hmc.ok()) rc = 4;
     cout << setprecision(17);
-    if (!rc && n_tastes == 1) {
-      const qmg::ZolotarevInvSqrt& z = hmc.rational();
-      cout << "[RHMC] n " << z.n << " ra " << z.ra << " rb " << z.rb << " c0 " << z.c0 << " delta " << z.delta << "\n";
-    }
-    if (!rc && mode == "md") {
-      if (!load(dir + "/pi.bin", pi, n_links) || !load(dir + "/phi.bin", a, half)) rc = 3;
-      for (int leg = 0; leg < 2 && !rc; leg++) {
-        const HmcResult r = hmc.md_evolve(pi, a);
-        cout << "[MD] " << (leg ? "back" : "forward") << " dH " << r.dH << " cg " << r.cg_iterations << " converged " << (r.cg_converged ? 1 : 0) << " plaq " << r.plaquette << "\n";
-        dump(dir + (leg ? "/theta_back.bin" : "/theta_fwd.bin"), phases, n_links);
-        dump(dir + (leg ? "/pi_back.bin" : "/pi_fwd.bin"), pi, n_links);
-        if (!r.cg_converged) rc = 1;
-        cax(-1.0, (complex<double>*)pi, n_links / 2);   // flip the momenta
-      }
-    } else if (!rc && mode == "heatbath") {
-      if (!load(dir + "/eta.bin", a, cv)) rc = 3;
-      if (!rc) {
-        HmcResult r = hmc.heatbath(b, a);
-        const double spf = hmc.pseudofermion_action(b, r);
-        cout << "[HB] eta2 " << norm2sq(a, cv) << " spf " << spf << " cg " << r.cg_iterations << " converged " << (r.cg_converged ? 1 : 0) << "\n";
-        dump(dir + "/phi.bin", b, half);
-        if (!r.cg_converged) rc = 1;
-      }
-    } else if (!rc && mode == "rational") {
-      if (!load(dir + "/v.bin", a, half)) rc = 3;
-      if (!rc) {
-        HmcResult r = hmc.apply_rational(b, a);
-        dump(dir + "/rv.bin", b, half);
-        const HmcResult r2 = hmc.apply_rational(a, b);
-        dump(dir + "/rrv.bin", a, half);
-        const bool conv = r.cg_converged && r2.cg_converged;
-        cout << "[RAT] cg " << r.cg_iterations + r2.cg_iterations << " converged " << (conv ? 1 : 0) << "\n";
-        if (!conv) rc = 1;
-      }
-    } else if (!rc) {
-      cout << "[QMG-ERROR]: unknown mode " << mode << "\n";
-      rc = 5;
+    if (!hmc.ok()) rc = 4;
+    if (!rc && n_tastes == 1) rhmc_line(hmc);
+    if (rc) {   // refused
+    } else if (mode == "md") {
+      rc = load(dir + "/pi.bin", pi, n_links) && load(dir + "/phi.bin", a, half) ? md_legs(hmc, dir, phases, pi, a, n_links) : 3;
+    } else if (mode == "heatbath") {
+      rc = heatbath_mode(hmc, dir, a, b, cv, half);
+    } else if (mode == "rational") {
+      rc = rational_mode(hmc, dir, a, b, half);
+    } else {
+      rc = unknown_mode(mode);
     }
   }
   deallocate_vector(&phases); deallocate_vector(&pi); deallocate_vector(&a); deallocate_vector(&b);

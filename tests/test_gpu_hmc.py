@@ -243,3 +243,30 @@ def test_two_flavour_run_through_the_driver(tmp_path):
     assert abs(un.plaquette(Ux, Uy)[0].real - rows[-1][3]) < 1e-9
     back = re.search(r"\[HMC-READBACK\] plaq (\S+)", out.stdout)
     assert back and abs(float(back.group(1)) - rows[-1][3]) < 1e-9
+
+
+# 8^2, beta 4, 4 steps, 3 trajectories from a heatbath start: Wilson 0, 2 and 1 flavours (degree 8 on [0.1, default]), staggered 2 and 1 tastes
+SEEDED_LEGS = {
+    "wilson-0": [0.1, 0, 3, 0, 4, "SEED", "CFG", "heatbath"],
+    "wilson-2": [0.1, 2, 3, 0, 4, "SEED", "CFG", "heatbath"],
+    "wilson-1": [0.1, 1, 3, 0, 4, "SEED", "CFG", "heatbath", 8, 0.1],
+    "staggered-2": [0.2, 2, 3, 0, 4, "SEED", "CFG", "heatbath", "staggered"],
+    "staggered-1": [0.2, 1, 3, 0, 4, "SEED", "CFG", "heatbath", 8, "staggered"],
+}
+
+
+@pytest.mark.parametrize("leg", sorted(SEEDED_LEGS))
+def test_trajectories_are_a_function_of_the_seed(tmp_path, leg):
+    """The shared trajectory() (hmc_core.hpp) draws every random field from (seed, trajectory, field) alone and starts every solve from zero:
+    two runs with one seed print the same [HMC] lines to the last digit, another seed prints others."""
+    def lines(seed, name):
+        args = [8, 4.0] + [seed if a == "SEED" else (tmp_path / name if a == "CFG" else a) for a in SEEDED_LEGS[leg]]
+        out, rows = run_driver(args, 120)
+        assert out.returncode == 0, out.stdout[-2000:] + out.stderr
+        assert len(rows) == 3
+        return re.findall(r"^\[HMC\] .*$", out.stdout, re.M)
+    first, again, other = lines(99, "a.dat"), lines(99, "b.dat"), lines(100, "c.dat")
+    print("\n".join(first))
+    assert len(first) == 3 and first == again
+    assert first != other
+    assert (tmp_path / "a.dat").read_bytes() == (tmp_path / "b.dat").read_bytes()
