@@ -3,7 +3,7 @@
 //
 // Why: every coarse-level kernel of the K-cycle streams the SAME matrices (stencil) or the SAME null vectors (transfer)
 // for every right-hand side.  Solving k systems one after the other reads them k times; solving them in lock step reads
-// them once and turns the coarse apply into an (nc x nc).(nc x k) contraction (kernel C of qmg_stencil.hip, f64 MFMA).
+// them once and turns the coarse apply into an (nc x nc).(nc x k) contraction (kernel C of qmg_stencil_mfma.hip, f64 MFMA).
 //
 // Layout: a batch vector is `nrhs` vectors of `n` complex128 at a common `stride` (complex elements).  Every entry point
 // takes a bit mask of ACTIVE systems: a system that has converged inside an inner solve is frozen -- neither read nor

@@ -45,7 +45,7 @@ struct SlabHalo { const void* lo; const void* hi; long stride; int rows; };   //
 int site_kernel_apply(int storage, const qmg_stencil_desc* d, void* lhs, const void* rhs, unsigned pieces, int n, long vec_stride,
                       const unsigned char* ridx, hipStream_t st, bool only_where_faster, const struct SlabHalo* slab);
 int generic_slab_apply(const qmg_stencil_desc* d, void* lhs, const void* rhs, unsigned pieces, int n, long vec_stride, const unsigned char* ridx,
-                       hipStream_t st, const SlabHalo* slab, int mat32, int vec32);   // qmg_stencil.hip: kernel B with halos (any nc; f32: complex<float> matrices and vectors)
+                       hipStream_t st, const SlabHalo* slab, int mat32, int vec32);   // qmg_stencil_apply.hip: kernels B / B32 / C with halos (any nc; f32: complex<float> matrices and vectors)
 constexpr int SITE_DECLINED = 1000;   // not an error: the caller's own kernel is the better one for this launch
 
 // qmg_comm.hip: reductions of y-slab vectors are summed over the ranks (qmg_comm_set_distributed_reductions)
@@ -270,6 +270,10 @@ void release_u1_workspace();        // qmg_u1.hip
 void release_flow_workspace();      // qmg_flow.hip
 extern int g_setup_fused; // qmg_setup.hip; "setup_fused"
 extern int g_wilson_pair;      // qmg_wilson.hip; "wilson_pair"
+extern int g_stencil_site;     // qmg_stencil_apply.hip; "stencil_site"
+extern int g_stencil_pair;     // qmg_stencil_apply.hip; "stencil_pair"
+extern int g_pair_prefetch;    // qmg_stencil.hip; "pair_prefetch"
+extern int g_stencil_mfma;     // qmg_stencil_mfma.hip; "stencil_mfma"
 extern long g_blas_nt_bytes;   // qmg_blas.hip; "blas_nt_mb"
 
 // Memory-bound 1-D launches.  One 16-byte element per thread up to 2^18 blocks, grid-stride beyond: on this part a

@@ -1,4 +1,4 @@
-// qmg_runtime.hip -- device/runtime plumbing of the C-ABI (no compute).
+// qmg_runtime.hip -- device/runtime plumbing of the C-ABI and the tuning knobs (no compute).
 #include <stdio.h>
 #include <string.h>
 
@@ -31,6 +31,21 @@ const char* qmg_status_string(int s) {
     case QMG_ERR_NO_DEVICE: return "no GPU device";
     default: return "unknown status";
   }
+}
+
+// Tuning knobs by name; each global is defined in the unit that reads it (qmg_common.h).
+int qmg_set_tuning(const char* key, int value) {
+  if (!key) return QMG_ERR_INVALID;
+  if (!strcmp(key, "stencil_pair")) { if (value != 0 && value != 2) return QMG_ERR_INVALID; g_stencil_pair = value; return QMG_SUCCESS; }
+  if (!strcmp(key, "blas_nt_mb")) { g_blas_nt_bytes = (long)value << 20; return QMG_SUCCESS; }
+  if (!strcmp(key, "pair_prefetch")) { g_pair_prefetch = value; return QMG_SUCCESS; }
+  if (!strcmp(key, "stencil_site")) { g_stencil_site = value; return QMG_SUCCESS; }
+  if (!strcmp(key, "stencil_mfma")) { g_stencil_mfma = value; return QMG_SUCCESS; }
+  if (!strcmp(key, "wilson_pair")) { g_wilson_pair = value; return QMG_SUCCESS; }
+  if (!strcmp(key, "setup_fused")) { g_setup_fused = value; return QMG_SUCCESS; }
+  if (!strcmp(key, "reduce_spin")) { g_reduce_spin = value; return QMG_SUCCESS; }
+  if (!strcmp(key, "malloc_poison")) { g_malloc_poison = value ? 1 : 0; return QMG_SUCCESS; }
+  return QMG_ERR_INVALID;
 }
 
 int qmg_device_count(int* n) {

@@ -18,7 +18,7 @@
 // of a coarse row, whose fine elements on one fine half-row are CONTIGUOUS (SX G elements, G = (bx/2) nc_f): the workgroup stages a chunk
 // of the null vectors [nvec][rows of the chunk][SX G] and of the fine vectors in LDS with whole-line coalesced loads and the wavefronts
 // pull their MFMA operands from there (row strides odd in 8-byte words: the 16 lanes of an operand column hit 16 different LDS words).
-// Operand maps (as kernel C of qmg_stencil.hip): lane = 16 lq + lr; A (16 x 4): row lr, k lq; B (4 x 16): k lq, column lr;
+// Operand maps (as kernel C of qmg_stencil_mfma.hip): lane = 16 lq + lr; A (16 x 4): row lr, k lq; B (4 x 16): k lq, column lr;
 // C (16 x 16): column lr, row 4 i + lq in accumulator register i.
 #include "qmg_common.h"
 
