@@ -108,6 +108,33 @@ __device__ __forceinline__ double wave_max(double v) {
   return v;
 }
 
+// Two-stage sum of N numbers per thread in a FIXED order, so that the result is deterministic.  First stage, at the end of a kernel of BLOCK
+// threads: the block's N sums go to partials[blockIdx.x * N + q]; `sm` is the kernel's own __shared__ array.
+template <int N>
+__device__ __forceinline__ void block_partials(const double (&v)[N], double (&sm)[N][BLOCK / WAVE], double* __restrict__ partials) {
+  const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
+#pragma unroll
+  for (int q = 0; q < N; q++) {
+    const double w = wave_sum(v[q]);
+    if (lane == 0) sm[q][wv] = w;
+  }
+  __syncthreads();
+  if (threadIdx.x < N) {
+    double t = 0.0;
+    for (int w = 0; w < BLOCK / WAVE; w++) t += sm[threadIdx.x][w];
+    partials[(long)blockIdx.x * N + threadIdx.x] = t;
+  }
+}
+// second stage, one block: out[q] = scale * sum over the blocks in index order
+template <int N>
+__global__ void k_sum_partials(const double* __restrict__ partials, int nparts, double scale, double* __restrict__ out) {
+  if (threadIdx.x < N) {
+    double t = 0.0;
+    for (int i = 0; i < nparts; i++) t += partials[(long)i * N + threadIdx.x];
+    out[threadIdx.x] = t * scale;
+  }
+}
+
 // ---------------- storage precision (qmg_dtype) ----------------
 // Vectors and matrices are STORED as complex<double> (QMG_C64) or complex<float> (QMG_C32).  Except in the fine-stencil
 // kernel A (which computes in the storage type), arithmetic and every reduction accumulate in fp64 registers: an element
@@ -275,6 +302,34 @@ extern int g_stencil_pair;     // qmg_stencil_apply.hip; "stencil_pair"
 extern int g_pair_prefetch;    // qmg_stencil.hip; "pair_prefetch"
 extern int g_stencil_mfma;     // qmg_stencil_mfma.hip; "stencil_mfma"
 extern long g_blas_nt_bytes;   // qmg_blas.hip; "blas_nt_mb"
+
+// A device scratch buffer of the calling thread (declare it thread_local), grown on demand -- the only synchronous step of its users, and only
+// when it grows -- and held until qmg_shutdown.  Calls of one host thread on different streams share it and must not overlap.
+struct ThreadScratch {
+  void* buf = nullptr;
+  size_t bytes = 0;
+  int device = -1;
+  template <class T> int grow(size_t need, T** out) {
+    int dev = 0;
+    QMG_HIP_CHECK(hipGetDevice(&dev));
+    if (device != dev || bytes < need) {
+      if (buf && device == dev) QMG_HIP_CHECK(hipFree(buf));   // waits for the device: nothing still reads it
+      *this = ThreadScratch();
+      QMG_HIP_CHECK(hipMalloc(&buf, need));
+      bytes = need;
+      device = dev;
+    }
+    *out = (T*)buf;
+    return QMG_SUCCESS;
+  }
+  void release() {
+    if (buf) hipFree(buf);
+    *this = ThreadScratch();
+  }
+};
+inline bool fields_overlap(const void* a, size_t abytes, const void* b, size_t bbytes) {
+  return (const char*)a < (const char*)b + bbytes && (const char*)b < (const char*)a + abytes;
+}
 
 // Memory-bound 1-D launches.  One 16-byte element per thread up to 2^18 blocks, grid-stride beyond: on this part a
 // streaming copy reaches 6.2 TB/s at 262 144 blocks but only 5.4 TB/s at 8 192 (profiles/r01_membw_ceiling.txt).

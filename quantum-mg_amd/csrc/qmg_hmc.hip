@@ -11,7 +11,7 @@
 //
 // Layouts (lattice.h:75-81): site (x, y) has index (y + p Ly) Lx/2 + x/2, p = (x + y) & 1; phases, momenta and links are [mu][site],
 // spinors [site][2].
-#include "qmg_common.h"
+#include "qmg_u1_pair.h"
 
 namespace qmg {
 
@@ -38,16 +38,9 @@ __device__ __forceinline__ cplx ydag_hy(cplx y0, cplx y1, cplx x0, cplx x1, doub
 __device__ __forceinline__ double link_force(cplx u, cplx p, cplx m) {
   return fma(u.x, p.y, u.y * p.x) - fma(u.x, m.y, -u.y * m.x);
 }
-__device__ __forceinline__ double im_plaq(cplx a, cplx b, cplx c, cplx d) {   // Im[ a b conj(c) conj(d) ]
-  const cplx ab = cmul(a, b), cd = cmul(c, d);
-  return fma(ab.y, cd.x, -ab.x * cd.y);
-}
 
-// pi -= dt (Fg + Ff), every link in one pass.  The thread mapping of k_ape_smear (qmg_u1.hip): a thread owns the two sites (2 xh, y) and
-// (2 xh + 1, y) -- one of each parity, at the same offset xh of their rows, so every load and store of a wave is one contiguous run -- and
-// updates all four of their momenta.  It loads 15 links (the five plaquettes P(a), P(b), P(a-y), P(b-y), P(a-x); P(b-x) = P(a)) and, with
-// fermions, X and Y at five sites (a, b, the site right of b and the two above).  All loads are unconditional and sit in front of the
-// arithmetic; every index is a wrapped lattice coordinate, so nothing is read or written outside the fields.
+// pi -= dt (Fg + Ff), every link in one pass, on the site pairs of qmg_u1_pair.h (its geometry; the loads are the kernel's own, see below): a
+// thread updates the four momenta of its pair from the pair's 15 links and, with fermions, X and Y at five sites (a, b, the site right of b and the two above), all loaded in front of the arithmetic.
 // Byte model: 128 B/site -- pi read and written (32), two links (32), X and Y (64); the neighbours are expected from cache.
 template <bool FERMIONS>
 __global__ __launch_bounds__(BLOCK) void k_hmc_momentum_update(double* __restrict__ pi, const cplx* __restrict__ gauge, const cplx* __restrict__ X,
@@ -58,16 +51,14 @@ __global__ __launch_bounds__(BLOCK) void k_hmc_momentum_update(double* __restric
   const cplx* __restrict__ Ux = gauge;
   const cplx* __restrict__ Uy = gauge + V;
   for (long t = (long)blockIdx.x * BLOCK + threadIdx.x; t < npairs; t += (long)gridDim.x * BLOCK) {
-    const int xh = (int)(t % h), y = (int)(t / h);
-    const int yp = (y + 1 == Ly) ? 0 : y + 1, ym = (y == 0) ? Ly - 1 : y - 1;
-    const int xl = (xh == 0) ? h - 1 : xh - 1, xr = (xh + 1 == h) ? 0 : xh + 1;
-    // a: the even-x site of the pair, b: the odd-x one; l: the odd-x site left of a, r: the even-x site right of b
-    const int q = y & 1, qp = yp & 1, qm = ym & 1;
-    const long ra = (long)(y + q * Ly) * h, rb = (long)(y + (1 - q) * Ly) * h;          // rows of even-x / odd-x sites at y
-    const long rap = (long)(yp + qp * Ly) * h, rbp = (long)(yp + (1 - qp) * Ly) * h;    // at y + 1
-    const long ram = (long)(ym + qm * Ly) * h, rbm = (long)(ym + (1 - qm) * Ly) * h;    // at y - 1
-    const long sa = ra + xh, sb = rb + xh;
+    const PairGeom g = pair_geom(t, h, Ly);
+    const long sa = g.sa, sb = g.sb;
     const double pax = pi[sa], pay = pi[V + sa], pbx = pi[sb], pby = pi[V + sb];
+    const int xh = g.xh, xl = g.xl, xr = g.xr;
+    const long ra = g.ra, rb = g.rb, rap = g.rap, rbp = g.rbp, ram = g.ram, rbm = g.rbm;
+    // pair_links and pair_sin_diffs, written out: through the helpers the two-flavour kernel kept its registers and occupancy but grew from 599
+    // to 617 instructions (more 64-bit address arithmetic, three more s_waitcnt), and n of its launches back to back at 2048^2 took 1 to 2 %
+    // longer than the parent's in every session measured (profiles/u1_pair_refactor.txt).  Written out, its device code is the parent's text.
     const cplx ax = Ux[sa], ay = Uy[sa], bx = Ux[sb], by = Uy[sb];
     const cplx apx = Ux[rap + xh], bpx = Ux[rbp + xh];
     const cplx amx = Ux[ram + xh], amy = Uy[ram + xh], bmx = Ux[rbm + xh], bmy = Uy[rbm + xh];
@@ -113,7 +104,7 @@ struct HmcPoles {
 
 // pi -= dt (Fg + sum_j w_j Ff(X_j, Y_j)), every link in one pass: the kick of a rational pseudofermion action
 //   S = c0 phi^dag (1 + sum_j rho_j (D^dag D + mu_j^2)^-1) phi,   X_j = (D^dag D + mu_j^2)^-1 phi,  Y_j = D X_j,  w_j = c0 rho_j.
-// Thread mapping, index wrapping and the expressions of k_hmc_momentum_update, so that one pole of weight 1 gives its bits: the gauge part
+// The site pairs (qmg_u1_pair.h) and the expressions of k_hmc_momentum_update, so that one pole of weight 1 gives its bits: the gauge part
 // first, from its 15 links, of which only the pair's four own links live on into the pole loop; then, pole by pole, the 20 spinor loads in
 // front of that pole's arithmetic and four fused multiply-adds onto the pole sum, to which the gauge part is added last.
 // GAUGE = false (the launches after the first when there are more than HMC_POLES_J poles) loads the four own links alone.
@@ -127,34 +118,20 @@ __global__ __launch_bounds__(BLOCK) void k_hmc_momentum_update_poles(double* __r
   const cplx* __restrict__ Ux = gauge;
   const cplx* __restrict__ Uy = gauge + V;
   for (long t = (long)blockIdx.x * BLOCK + threadIdx.x; t < npairs; t += (long)gridDim.x * BLOCK) {
-    const int xh = (int)(t % h), y = (int)(t / h);
-    const int yp = (y + 1 == Ly) ? 0 : y + 1, ym = (y == 0) ? Ly - 1 : y - 1;
-    const int xl = (xh == 0) ? h - 1 : xh - 1, xr = (xh + 1 == h) ? 0 : xh + 1;
-    const int q = y & 1, qp = yp & 1, qm = ym & 1;
-    const long ra = (long)(y + q * Ly) * h, rb = (long)(y + (1 - q) * Ly) * h;
-    const long rap = (long)(yp + qp * Ly) * h, rbp = (long)(yp + (1 - qp) * Ly) * h;
-    const long sa = ra + xh, sb = rb + xh;
+    const PairGeom g = pair_geom(t, h, Ly);
+    const long sa = g.sa, sb = g.sb;
     const double pax = pi[sa], pay = pi[V + sa], pbx = pi[sb], pby = pi[V + sb];
-    const cplx ax = Ux[sa], ay = Uy[sa], bx = Ux[sb], by = Uy[sb];
-    double gax = 0.0, gay = 0.0, gbx = 0.0, gby = 0.0;   // the differences of sin P of the gauge force
+    const PairOwn o = pair_own_links(Ux, Uy, g);
+    PairForce d = {0.0, 0.0, 0.0, 0.0};   // the differences of sin P of the gauge force
     if (GAUGE) {
-      const long ram = (long)(ym + qm * Ly) * h, rbm = (long)(ym + (1 - qm) * Ly) * h;
-      const cplx apx = Ux[rap + xh], bpx = Ux[rbp + xh];
-      const cplx amx = Ux[ram + xh], amy = Uy[ram + xh], bmx = Ux[rbm + xh], bmy = Uy[rbm + xh];
-      const cplx lx = Ux[rb + xl], ly = Uy[rb + xl], lpx = Ux[rbp + xl];
-      const cplx ry = Uy[ra + xr], rmy = Uy[ram + xr];
-      const double sPa = im_plaq(ax, by, apx, ay), sPb = im_plaq(bx, ry, bpx, by);
-      const double sPam = im_plaq(amx, bmy, ax, amy), sPbm = im_plaq(bmx, rmy, bx, bmy);
-      const double sPl = im_plaq(lx, ay, lpx, ly);
-      gax = sPa - sPam; gay = sPl - sPa;
-      gbx = sPb - sPbm; gby = sPa - sPb;
+      d = pair_sin_diffs(pair_links(Ux, Uy, g, o));
       // Pin the four numbers here: they are used after the pole loop only, and left alone the compiler sinks the plaquettes below the loop
       // and carries the 15 links through it (212 VGPRs, 2 waves per SIMD instead of 4).
-      asm volatile("" : "+v"(gax), "+v"(gay), "+v"(gbx), "+v"(gby));
+      asm volatile("" : "+v"(d.ax), "+v"(d.ay), "+v"(d.bx), "+v"(d.by));
     }
     // The pole sum starts from -0.0, the one number that fma(w, f, .) leaves every w f at, signed zeros included.
     double fax = -0.0, fay = -0.0, fbx = -0.0, fby = -0.0;
-    const long sr = ra + xr, sap = rap + xh, sbp = rbp + xh;
+    const long sr = g.ra + g.xr, sap = g.rap + g.xh, sbp = g.rbp + g.xh;
     for (int j = 0; j < n_poles; j++) {
       const cplx* __restrict__ X = poles.X[j];
       const cplx* __restrict__ Y = poles.Y[j];
@@ -164,13 +141,13 @@ __global__ __launch_bounds__(BLOCK) void k_hmc_momentum_update_poles(double* __r
       const cplx xr0 = X[2 * sr], xr1 = X[2 * sr + 1], yr0 = Y[2 * sr], yr1 = Y[2 * sr + 1];
       const cplx xap0 = X[2 * sap], xap1 = X[2 * sap + 1], yap0 = Y[2 * sap], yap1 = Y[2 * sap + 1];
       const cplx xbp0 = X[2 * sbp], xbp1 = X[2 * sbp + 1], ybp0 = Y[2 * sbp], ybp1 = Y[2 * sbp + 1];
-      fax = fma(w, link_force(ax, ydag_hx(ya0, ya1, xb0, xb1, 1.0), ydag_hx(yb0, yb1, xa0, xa1, -1.0)), fax);
-      fay = fma(w, link_force(ay, ydag_hy(ya0, ya1, xap0, xap1, 1.0), ydag_hy(yap0, yap1, xa0, xa1, -1.0)), fay);
-      fbx = fma(w, link_force(bx, ydag_hx(yb0, yb1, xr0, xr1, 1.0), ydag_hx(yr0, yr1, xb0, xb1, -1.0)), fbx);
-      fby = fma(w, link_force(by, ydag_hy(yb0, yb1, xbp0, xbp1, 1.0), ydag_hy(ybp0, ybp1, xb0, xb1, -1.0)), fby);
+      fax = fma(w, link_force(o.ax, ydag_hx(ya0, ya1, xb0, xb1, 1.0), ydag_hx(yb0, yb1, xa0, xa1, -1.0)), fax);
+      fay = fma(w, link_force(o.ay, ydag_hy(ya0, ya1, xap0, xap1, 1.0), ydag_hy(yap0, yap1, xa0, xa1, -1.0)), fay);
+      fbx = fma(w, link_force(o.bx, ydag_hx(yb0, yb1, xr0, xr1, 1.0), ydag_hx(yr0, yr1, xb0, xb1, -1.0)), fbx);
+      fby = fma(w, link_force(o.by, ydag_hy(yb0, yb1, xbp0, xbp1, 1.0), ydag_hy(ybp0, ybp1, xb0, xb1, -1.0)), fby);
     }
     // k_hmc_momentum_update's `beta * (...) + Ff` is contracted into one fma by the compiler; written out here so that the bits agree
-    if (GAUGE) { fax = fma(beta, gax, fax); fay = fma(beta, gay, fay); fbx = fma(beta, gbx, fbx); fby = fma(beta, gby, fby); }
+    if (GAUGE) { fax = fma(beta, d.ax, fax); fay = fma(beta, d.ay, fay); fbx = fma(beta, d.bx, fbx); fby = fma(beta, d.by, fby); }
     pi[sa] = fma(-dt, fax, pax);
     pi[V + sa] = fma(-dt, fay, pay);
     pi[sb] = fma(-dt, fbx, pbx);
@@ -183,22 +160,6 @@ __global__ __launch_bounds__(BLOCK) void k_hmc_momentum_update_poles(double* __r
 // A = m^2 - H^2, S_f = phi_e^dag (A_ee + sigma)^-1 phi_e.  With W = X_e (+) (H X_e)_o, X_e = (A_ee + sigma)^-1 phi_e and eps(x) = (-1)^(x+y):
 //   Fs_mu(x) = dS_f/dtheta_mu(x) = eta_mu(x) eps(x) Im[ U_mu(x) conj(W(x)) W(x+mu) ]
 // one complex number per site, two sites per link.
-// The gauge force of a pair of sites without its factor beta: the differences of sin P behind the pair's four momenta, from the pair's own
-// four links (which the caller has loaded) and the eleven around them: the loads and expressions of k_hmc_momentum_update_poles, on the im_plaq
-// both share.  (That kernel keeps its own copy: calling this from it changed its instruction schedule.)
-__device__ __forceinline__ void gauge_force_diffs(const cplx* Ux, const cplx* Uy, long ra, long rb, long rap, long rbp, long ram, long rbm,
-                                                  int xh, int xl, int xr, cplx ax, cplx ay, cplx bx, cplx by, double& gax, double& gay, double& gbx, double& gby) {
-  const cplx apx = Ux[rap + xh], bpx = Ux[rbp + xh];
-  const cplx amx = Ux[ram + xh], amy = Uy[ram + xh], bmx = Ux[rbm + xh], bmy = Uy[rbm + xh];
-  const cplx lx = Ux[rb + xl], ly = Uy[rb + xl], lpx = Ux[rbp + xl];
-  const cplx ry = Uy[ra + xr], rmy = Uy[ram + xr];
-  const double sPa = im_plaq(ax, by, apx, ay), sPb = im_plaq(bx, ry, bpx, by);
-  const double sPam = im_plaq(amx, bmy, ax, amy), sPbm = im_plaq(bmx, rmy, bx, bmy);
-  const double sPl = im_plaq(lx, ay, lpx, ly);
-  gax = sPa - sPam; gay = sPl - sPa;
-  gbx = sPb - sPbm; gby = sPa - sPb;
-}
-
 struct HmcStagPoles {   // the pole list of one launch of k_hmc_momentum_update_staggered, as HmcPoles
   const cplx* W[HMC_POLES_J];
   double w[HMC_POLES_J];
@@ -212,11 +173,11 @@ __device__ __forceinline__ double im_u_adag_b(cplx u, cplx a, cplx b) {
 
 // pi -= dt (Fg + sum_j w_j Fs(W_j)), every link in one pass: the kick of two staggered tastes (one pole of weight 1) and of the rooted action
 //   S = c0 phi_e^dag (1 + sum_j rho_j (A_ee + mu_j^2)^-1) phi_e,   w_j = c0 rho_j.
-// Thread mapping and index wrapping of k_hmc_momentum_update_poles: the pair a = (2 xh, y), b = (2 xh + 1, y), so eta_y is +1 on a and -1 on b and
-// eps(a) = (-1)^y = -eps(b).  The gauge part comes first (gauge_force_diffs, pinned as there); then, pole by pole, five loads of W (a, b, the
-// site right of b, the two above) in front of that pole's arithmetic and four fused multiply-adds onto the pole sum.  Every
-// index is a wrapped lattice coordinate.  GAUGE = false (the launches after the first when there are more than HMC_POLES_J poles) loads the
-// four own links alone.  Byte model: 64 + 16 n B/site -- pi read and written (32), two links (32), per pole W_j (16).
+// The site pairs of qmg_u1_pair.h: a = (2 xh, y), b = (2 xh + 1, y), so eta_y is +1 on a and -1 on b and eps(a) = (-1)^y = -eps(b).  The gauge
+// part comes first (pinned as in k_hmc_momentum_update_poles); then, pole by pole, five loads of W (a, b, the site right of b, the two above)
+// in front of that pole's arithmetic and four fused multiply-adds onto the pole sum.  GAUGE = false (the launches after the
+// first when there are more than HMC_POLES_J poles) loads the four own links alone.
+// Byte model: 64 + 16 n B/site -- pi read and written (32), two links (32), per pole W_j (16).
 template <bool GAUGE>
 __global__ __launch_bounds__(BLOCK) void k_hmc_momentum_update_staggered(double* __restrict__ pi, const cplx* __restrict__ gauge, const HmcStagPoles poles, int n_poles,
                                                                          int Lx, int Ly, double beta, double dt) {
@@ -226,34 +187,28 @@ __global__ __launch_bounds__(BLOCK) void k_hmc_momentum_update_staggered(double*
   const cplx* __restrict__ Ux = gauge;
   const cplx* __restrict__ Uy = gauge + V;
   for (long t = (long)blockIdx.x * BLOCK + threadIdx.x; t < npairs; t += (long)gridDim.x * BLOCK) {
-    const int xh = (int)(t % h), y = (int)(t / h);
-    const int yp = (y + 1 == Ly) ? 0 : y + 1, ym = (y == 0) ? Ly - 1 : y - 1;
-    const int xl = (xh == 0) ? h - 1 : xh - 1, xr = (xh + 1 == h) ? 0 : xh + 1;
-    const int q = y & 1, qp = yp & 1, qm = ym & 1;
-    const long ra = (long)(y + q * Ly) * h, rb = (long)(y + (1 - q) * Ly) * h;
-    const long rap = (long)(yp + qp * Ly) * h, rbp = (long)(yp + (1 - qp) * Ly) * h;
-    const long sa = ra + xh, sb = rb + xh;
+    const PairGeom g = pair_geom(t, h, Ly);
+    const long sa = g.sa, sb = g.sb;
     const double pax = pi[sa], pay = pi[V + sa], pbx = pi[sb], pby = pi[V + sb];
-    const cplx ax = Ux[sa], ay = Uy[sa], bx = Ux[sb], by = Uy[sb];
-    double gax = 0.0, gay = 0.0, gbx = 0.0, gby = 0.0;
+    const PairOwn o = pair_own_links(Ux, Uy, g);
+    PairForce d = {0.0, 0.0, 0.0, 0.0};   // the differences of sin P of the gauge force
     if (GAUGE) {
-      const long ram = (long)(ym + qm * Ly) * h, rbm = (long)(ym + (1 - qm) * Ly) * h;
-      gauge_force_diffs(Ux, Uy, ra, rb, rap, rbp, ram, rbm, xh, xl, xr, ax, ay, bx, by, gax, gay, gbx, gby);
-      asm volatile("" : "+v"(gax), "+v"(gay), "+v"(gbx), "+v"(gby));   // keep the 15 links out of the pole loop, as in k_hmc_momentum_update_poles
+      d = pair_sin_diffs(pair_links(Ux, Uy, g, o));
+      asm volatile("" : "+v"(d.ax), "+v"(d.ay), "+v"(d.bx), "+v"(d.by));   // keep the 15 links out of the pole loop, as in k_hmc_momentum_update_poles
     }
-    const double ea = q ? -1.0 : 1.0;   // eps(a); eta_x eps = ea, -ea on (a, b); eta_y eps = ea on both
+    const double ea = g.q ? -1.0 : 1.0;   // eps(a); eta_x eps = ea, -ea on (a, b); eta_y eps = ea on both
     double fax = -0.0, fay = -0.0, fbx = -0.0, fby = -0.0;
-    const long sr = ra + xr, sap = rap + xh, sbp = rbp + xh;
+    const long sr = g.ra + g.xr, sap = g.rap + g.xh, sbp = g.rbp + g.xh;
     for (int j = 0; j < n_poles; j++) {
       const cplx* __restrict__ W = poles.W[j];
       const double wa = ea * poles.w[j];
       const cplx a = W[sa], b = W[sb], r = W[sr], ap = W[sap], bp = W[sbp];
-      fax = fma(wa, im_u_adag_b(ax, a, b), fax);
-      fay = fma(wa, im_u_adag_b(ay, a, ap), fay);
-      fbx = fma(-wa, im_u_adag_b(bx, b, r), fbx);
-      fby = fma(wa, im_u_adag_b(by, b, bp), fby);
+      fax = fma(wa, im_u_adag_b(o.ax, a, b), fax);
+      fay = fma(wa, im_u_adag_b(o.ay, a, ap), fay);
+      fbx = fma(-wa, im_u_adag_b(o.bx, b, r), fbx);
+      fby = fma(wa, im_u_adag_b(o.by, b, bp), fby);
     }
-    if (GAUGE) { fax = fma(beta, gax, fax); fay = fma(beta, gay, fay); fbx = fma(beta, gbx, fbx); fby = fma(beta, gby, fby); }
+    if (GAUGE) { fax = fma(beta, d.ax, fax); fay = fma(beta, d.ay, fay); fbx = fma(beta, d.bx, fbx); fby = fma(beta, d.by, fby); }
     pi[sa] = fma(-dt, fax, pax);
     pi[V + sa] = fma(-dt, fay, pay);
     pi[sb] = fma(-dt, fbx, pbx);

@@ -22,14 +22,9 @@
 // lorentz_gauge_fix_u1 (:511-542) is an unfinished stub in the reference (its loop has no body and never ends): not here.
 #include <string.h>
 
-#include "qmg_common.h"
+#include "qmg_u1_pair.h"
 
 namespace qmg {
-
-__device__ __forceinline__ long eo_index(int x, int y, int Lx, int Ly) {
-  const int p = (x + y) & 1;
-  return (long)(y + p * Ly) * (Lx >> 1) + (x >> 1);
-}
 
 __device__ __forceinline__ unsigned long long mix64(unsigned long long z) {
   z += 0x9E3779B97F4A7C15ull;
@@ -133,10 +128,7 @@ __device__ __forceinline__ cplx project_u1(cplx z) {
 #endif
 }
 
-// One APE iteration (u1_utils.h:292-375), out != in.  A thread owns the two sites (2 xh, y) and (2 xh + 1, y) -- one of each
-// parity, at the same offset xh of their rows in the even-odd layout, so every load and store of a wave is one contiguous
-// run -- and writes all four of their links from 15 loaded links (the pair shares five of the 20 a site-per-thread kernel
-// would load).  Rows: site (x, r) lives at ((r + p Ly) Lx/2 + x/2), p = (x + r) & 1.
+// One APE iteration (u1_utils.h:292-375), out != in, on the site pairs of qmg_u1_pair.h: all four links of a pair from its 15.
 //   U'_x(s) = P[ U_x(s) + alpha ( U_y(s) U_x(s+y) conj U_y(s+x) + conj U_y(s-y) U_x(s-y) U_y(s+x-y) ) ]
 //   U'_y(s) = P[ U_y(s) + alpha ( U_x(s) U_y(s+x) conj U_x(s+y) + conj U_x(s-x) U_y(s-x) U_x(s-x+y) ) ]
 __global__ __launch_bounds__(BLOCK) void k_ape_smear(cplx* __restrict__ out, const cplx* __restrict__ in, int Lx, int Ly, double alpha) {
@@ -146,14 +138,11 @@ __global__ __launch_bounds__(BLOCK) void k_ape_smear(cplx* __restrict__ out, con
   const cplx* __restrict__ Ux = in;
   const cplx* __restrict__ Uy = in + V;
   for (long t = (long)blockIdx.x * BLOCK + threadIdx.x; t < npairs; t += (long)gridDim.x * BLOCK) {
-    const int xh = (int)(t % h), y = (int)(t / h);
-    const int yp = (y + 1 == Ly) ? 0 : y + 1, ym = (y == 0) ? Ly - 1 : y - 1;
-    const int xl = (xh == 0) ? h - 1 : xh - 1, xr = (xh + 1 == h) ? 0 : xh + 1;
-    // a: the even-x site of the pair, b: the odd-x one; l: the odd-x site left of a, r: the even-x site right of b
-    const int q = y & 1, qp = yp & 1, qm = ym & 1;
-    const long ra = (long)(y + q * Ly) * h, rb = (long)(y + (1 - q) * Ly) * h;          // rows of even-x / odd-x sites at y
-    const long rap = (long)(yp + qp * Ly) * h, rbp = (long)(yp + (1 - qp) * Ly) * h;    // at y + 1
-    const long ram = (long)(ym + qm * Ly) * h, rbm = (long)(ym + (1 - qm) * Ly) * h;    // at y - 1
+    const PairGeom g = pair_geom(t, h, Ly);
+    const int xh = g.xh, xl = g.xl, xr = g.xr;
+    const long ra = g.ra, rb = g.rb, rap = g.rap, rbp = g.rbp, ram = g.ram, rbm = g.rbm;
+    // pair_links(Ux, Uy, g), written out: through the helper's struct the kernel kept its occupancy (92 VGPRs for 96) but got another schedule,
+    // and an iteration at 4096^2 took 0.2255 ms for the parent's 0.2108 (profiles/u1_pair_refactor.txt)
     const cplx ax = Ux[ra + xh], ay = Uy[ra + xh], bx = Ux[rb + xh], by = Uy[rb + xh];
     const cplx apx = Ux[rap + xh], bpx = Ux[rbp + xh];
     const cplx amx = Ux[ram + xh], amy = Uy[ram + xh], bmx = Ux[rbm + xh], bmy = Uy[rbm + xh];
@@ -225,25 +214,7 @@ __global__ __launch_bounds__(BLOCK) void k_plaquette(const cplx* __restrict__ ga
     }
   }
   __shared__ double sm[3][BLOCK / WAVE];
-  const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
-#pragma unroll
-  for (int q = 0; q < 3; q++) {
-    const double w = wave_sum(v[q]);
-    if (lane == 0) sm[q][wv] = w;
-  }
-  __syncthreads();
-  if (threadIdx.x < 3) {
-    double t = 0.0;
-    for (int w = 0; w < BLOCK / WAVE; w++) t += sm[threadIdx.x][w];
-    partials[(long)blockIdx.x * 3 + threadIdx.x] = t;
-  }
-}
-__global__ void k_sum3(const double* __restrict__ partials, int nparts, double* __restrict__ out) {
-  if (threadIdx.x < 3) {
-    double t = 0.0;
-    for (int i = 0; i < nparts; i++) t += partials[(long)i * 3 + threadIdx.x];   // fixed order: deterministic
-    out[threadIdx.x] = t;
-  }
+  block_partials<3>(v, sm, partials);
 }
 
 static int plaquette_sums(const void* gauge, const double* phase, int Lx, int Ly, double out[3], void* stream, int mode) {
@@ -256,7 +227,7 @@ static int plaquette_sums(const void* gauge, const double* phase, int Lx, int Ly
   QMG_HIP_CHECK(hipMalloc((void**)&buf, sizeof(double) * (3 * nb + 3)));
   if (mode == 0) k_plaquette<0><<<(unsigned)nb, BLOCK, 0, st>>>((const cplx*)gauge, nullptr, Lx, Ly, buf);
   else k_plaquette<1><<<(unsigned)nb, BLOCK, 0, st>>>(nullptr, phase, Lx, Ly, buf);
-  k_sum3<<<1, 64, 0, st>>>(buf, (int)nb, buf + 3 * nb);
+  k_sum_partials<3><<<1, 64, 0, st>>>(buf, (int)nb, 1.0, buf + 3 * nb);
   hipError_t e = hipMemcpyAsync(out, buf + 3 * nb, sizeof(double) * 3, hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);
   hipFree(buf);
@@ -265,28 +236,9 @@ static int plaquette_sums(const void* gauge, const double* phase, int Lx, int Ly
   return QMG_SUCCESS;
 }
 
-// the calling thread's scratch field of qmg_u1_ape_smear
-struct SmearScratch { cplx* buf = nullptr; size_t bytes = 0; int device = -1; };
-static thread_local SmearScratch g_smear;
+static thread_local ThreadScratch g_smear;   // the calling thread's scratch field of qmg_u1_ape_smear
 
-static int smear_scratch(size_t bytes, cplx** out) {
-  int dev = 0;
-  QMG_HIP_CHECK(hipGetDevice(&dev));
-  if (g_smear.device != dev || g_smear.bytes < bytes) {
-    if (g_smear.buf && g_smear.device == dev) QMG_HIP_CHECK(hipFree(g_smear.buf));   // waits for the device: nothing still reads it
-    g_smear = SmearScratch();
-    QMG_HIP_CHECK(hipMalloc((void**)&g_smear.buf, bytes));
-    g_smear.bytes = bytes;
-    g_smear.device = dev;
-  }
-  *out = g_smear.buf;
-  return QMG_SUCCESS;
-}
-
-void release_u1_workspace() {   // qmg_shutdown (qmg_runtime.hip)
-  if (g_smear.buf) hipFree(g_smear.buf);
-  g_smear = SmearScratch();
-}
+void release_u1_workspace() { g_smear.release(); }   // qmg_shutdown (qmg_runtime.hip)
 
 }  // namespace qmg
 
@@ -393,11 +345,11 @@ int qmg_u1_ape_smear(void* smeared, const void* gauge, int Lx, int Ly, double al
   if (!smeared || !gauge || !valid_lattice(Lx, Ly) || n_iter < 0 || alpha != alpha) return QMG_ERR_INVALID;
   const size_t n = 2 * (size_t)Lx * Ly, bytes = sizeof(cplx) * n;
   const bool in_place = (smeared == gauge);
-  if (!in_place && ((const char*)smeared < (const char*)gauge + bytes && (const char*)gauge < (const char*)smeared + bytes)) return QMG_ERR_INVALID;   // partial overlap
+  if (!in_place && fields_overlap(smeared, bytes, gauge, bytes)) return QMG_ERR_INVALID;   // partial overlap
   if (n_iter == 0) return in_place ? QMG_SUCCESS : qmg_copy_vector(smeared, gauge, n, stream);
   cplx* tmp = nullptr;
   if (in_place || n_iter > 1) {
-    const int rc = smear_scratch(bytes, &tmp);
+    const int rc = g_smear.grow(bytes, &tmp);
     if (rc) return rc;
   }
   // targets alternate and end on `smeared`; in place with an odd count the roles swap (the first target cannot be the

@@ -42,9 +42,9 @@ def _device():
 
 
 def fields(golden_dir):
-    """(name, Lx, Ly, (thx, thy)): the three stored configurations and Gaussian beta = 6 phases on 2 x 2, 6 x 4 and 34 x 10"""
+    """(name, Lx, Ly, (thx, thy)): the three stored configurations and Gaussian beta = 6 phases on 2 x 2, 2 x 6, 6 x 2, 6 x 4 and 34 x 10"""
     out = [(name, L, L, fn.file_phases(os.path.join(golden_dir, name + "_heatbath.dat"), L, L)) for name, L in STORED]
-    for Lx, Ly in ((2, 2), (6, 4), (34, 10)):
+    for Lx, Ly in ((2, 2), (2, 6), (6, 2), (6, 4), (34, 10)):
         out.append(("%dx%d" % (Lx, Ly), Lx, Ly, gaussian_phases(Lx, Ly, 6.0, 100 + Lx)))
     return out
 

@@ -25,7 +25,7 @@ qmg = importlib.import_module("quantum-mg_amd")
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DRIVERS = os.path.join(ROOT, "quantum-mg_amd", "drivers")
-SIZES = [(2, 2), (6, 4), (34, 10), (64, 64)]
+SIZES = [(2, 2), (2, 6), (6, 2), (6, 4), (34, 10), (64, 64)]   # (2, 6): xl == xr == xh with distinct rows; (6, 2): yp == ym with distinct columns
 POLES = [1, 3, 16, 17]
 BETA = 3.0
 FIX = "l32t32b60_heatbath.dat"

@@ -39,12 +39,12 @@ def _device():
 
 
 def fields(golden_dir):
-    """(name, Lx, Ly, Ux, Uy): the three stored configurations and two rectangular Gaussian fields at beta = 6"""
+    """(name, Lx, Ly, Ux, Uy): the three stored configurations and Gaussian fields at beta = 6 on the thinnest lattices (2 x 2, 2 x 6, 6 x 2) and two rectangles"""
     out = []
     for name, L in STORED:
         Ux, Uy = cs.phases_to_links(np.loadtxt(os.path.join(golden_dir, name + "_heatbath.dat")), L, L)
         out.append((name, L, L, Ux, Uy))
-    for Lx, Ly in ((6, 4), (34, 10)):
+    for Lx, Ly in ((2, 2), (2, 6), (6, 2), (6, 4), (34, 10)):
         Ux, Uy = un.gaussian_links(Lx, 6.0, 100 + Lx, Ly=Ly)
         out.append(("%dx%d" % (Lx, Ly), Lx, Ly, Ux, Uy))
     return out

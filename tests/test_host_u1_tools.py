@@ -55,6 +55,23 @@ def test_smearing_statement_is_the_symmetric_one():
     assert np.abs(Tx.T - Sx).max() < 1e-15 and np.abs(Ty.T - Sy).max() < 1e-15
 
 
+THIN = [(2, 2), (2, 6), (6, 2)]   # every x-neighbour is the same site (Lx = 2), every y-neighbour is (Ly = 2)
+
+
+@pytest.mark.parametrize("Lx,Ly", THIN)
+def test_smearing_statement_is_the_per_link_loop_on_the_thinnest_lattices(Lx, Ly):
+    """np.roll makes no assumption about the extent, but the device is judged by the twin at these shapes (test_gpu_u1_tools.py), so the
+    twin is first held to u1_utils.h:292-375 written out link by link with % arithmetic.  Same products in the same order: 1e-15."""
+    Ux, Uy = un.gaussian_links(Lx, 6.0, 100 + Lx, Ly=Ly)
+    Sx, Sy = un.ape_iteration(Ux, Uy, 0.5)
+    for x in range(Lx):
+        for y in range(Ly):
+            xp, xm, yp, ym = (x + 1) % Lx, (x - 1) % Lx, (y + 1) % Ly, (y - 1) % Ly
+            zx = Ux[x, y] + 0.5 * (Uy[x, y] * Ux[x, yp] * np.conj(Uy[xp, y]) + np.conj(Uy[x, ym]) * Ux[x, ym] * Uy[xp, ym])
+            zy = Uy[x, y] + 0.5 * (Ux[x, y] * Uy[xp, y] * np.conj(Ux[x, yp]) + np.conj(Ux[xm, y]) * Uy[xm, y] * Ux[xm, yp])
+            assert abs(Sx[x, y] - zx / abs(zx)) < 1e-15 and abs(Sy[x, y] - zy / abs(zy)) < 1e-15, (x, y)
+
+
 @pytest.mark.parametrize("x0,y0", [(8, 8), (0, 0)])
 def test_instanton_on_the_unit_field_has_charge_one(x0, y0):
     one = np.ones((16, 16), dtype=complex)
