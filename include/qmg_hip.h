@@ -427,6 +427,20 @@ int qmg_prolong_batch_nv32(const void* nullvecs_c32, int nvec, const void* coars
                            int cLx, int cLy, int cnc, int nrhs, size_t cstride, size_t fstride, unsigned mask, void* stream);
 int qmg_restrict_batch_nv32(const void* nullvecs_c32, int nvec, const void* fine, void* coarse, int fLx, int fLy, int fnc,
                             int cLx, int cLy, int cnc, int nrhs, size_t fstride, size_t cstride, unsigned mask, void* stream);
+/* Which kernel serves a restrict (op = 0) or prolong (op = 1) request: the answer of the one host function every transfer launch above
+ * switches on.  Host only, no HIP call.  dtype: the vectors' storage; null32 = 1: the _nv32 entry points (dtype QMG_C64); n_active: the
+ * number of active systems of the call (1..16); aligned16: whether the null vectors and (one-system kernels) the fine vector are 16-byte
+ * aligned.  Writes 8 ints per pass of up to 8 systems (one pass where the systems are served one by one) and -1 into the rest of plan_out:
+ *   family  0 unsupported (the call returns QMG_ERR_UNSUPPORTED), 1 k_restrict, 2 k_restrict_generic, 3 k_prolong, 4 k_brestrict_mfma,
+ *           5 k_brestrict_small, 6 k_brestrict_tile, 7 k_bprolong_tile, 8 / 9 k_restrict / k_prolong with complex<float> null vectors
+ *   KB      systems the kernel is instantiated for (1: system by system)
+ *   NV      NVT of k_brestrict_small, NVB of k_bprolong_tile
+ *   MT, CR, nchunk, small  k_brestrict_mfma: row tiles, fine half-rows per chunk, chunks, and whether a full workgroup stages fewer
+ *           positions than it has threads
+ *   W       elements per lane of the one-system kernels
+ * (a member the family does not use is 0).  QMG_ERR_INVALID: a request the entry points reject, or plan_len too short. */
+int qmg_transfer_plan(int op, int dtype, int null32, int nvec, int fLx, int fLy, int fnc, int cLx, int cLy, int cnc, int n_active,
+                      int aligned16, int* plan_out, int plan_len);
 
 /* 16-bit storage of the fine operator (SURVEY 8f-4 "16-bit-storage smoother"; nc = 2 only): d->clover / d->hopping point to
  * complex<half> copies (qmg_convert_to_c16), vectors are complex<float>, arithmetic fp32: 112 B/site instead of 192.  The

@@ -45,7 +45,7 @@ ABI_SYMBOLS = [
     "qmg_batch_blas", "qmg_batch_multi_caxpy", "qmg_batch_reduce", "qmg_batch_multidot", "qmg_prolong_batch", "qmg_restrict_batch",
     "qmg_comm_get_unique_id", "qmg_comm_init", "qmg_comm_init_env", "qmg_comm_rendezvous", "qmg_comm_all_ok", "qmg_comm_world", "qmg_allreduce_sum_f64", "qmg_comm_finalize",
     "qmg_convert", "qmg_stencil_apply_t", "qmg_batch_blas_t", "qmg_batch_multi_caxpy_t", "qmg_batch_gcr_update_t", "qmg_batch_cgm_update_t", "qmg_prolong_batch_nv32", "qmg_restrict_batch_nv32", "qmg_batch_reduce_t", "qmg_batch_multidot_t",
-    "qmg_prolong_batch_t", "qmg_restrict_batch_t",
+    "qmg_prolong_batch_t", "qmg_restrict_batch_t", "qmg_transfer_plan",
     "qmg_convert_to_c16", "qmg_convert_from_c16", "qmg_stencil_apply_h16", "qmg_stencil_apply_mat16_t", "qmg_stencil_apply_norm2",
     "qmg_wilson_apply_direct", "qmg_wilson_hops_direct", "qmg_halo_exchange", "qmg_halo_exchange_parity", "qmg_stencil_apply_slab", "qmg_wilson_fill_slab", "qmg_comm_set_distributed_reductions", "qmg_coarse_build_slab", "qmg_gaussian_slab", "qmg_rb_hopping_slab", "qmg_build_dagger_slab", "qmg_staggered_fill_slab", "qmg_laplace_fill_slab", "qmg_comm_emulate_begin", "qmg_comm_emulate_attach", "qmg_comm_emulate_end",
     "qmg_stencil_apply_epi_t", "qmg_wilson_apply_direct_epi", "qmg_wilson_hops_direct_epi", "qmg_batch_mr_dots_t", "qmg_batch_mr_update_t", "qmg_batch_mr_read_dots",
@@ -634,6 +634,20 @@ def prolong_batch_t(dtype, nullvecs, nvec, coarse, fine, fdims, cdims, nrhs, cst
 def restrict_batch_t(dtype, nullvecs, nvec, fine, coarse, fdims, cdims, nrhs, fstride, cstride, mask):
     check(lib().qmg_restrict_batch_t(dtype, _vp(nullvecs), nvec, _vp(fine), _vp(coarse), *fdims, *cdims, nrhs, C.c_size_t(fstride), C.c_size_t(cstride), C.c_uint(mask), None),
           "qmg_restrict_batch_t")
+
+
+XFER_RESTRICT, XFER_PROLONG = 0, 1
+# kernel families of qmg_transfer_plan (include/qmg_hip.h)
+XF_UNSUPPORTED, XF_RESTRICT, XF_RESTRICT_GENERIC, XF_PROLONG, XF_BRESTRICT_MFMA, XF_BRESTRICT_SMALL, XF_BRESTRICT_TILE, XF_BPROLONG_TILE = range(8)
+XF_RESTRICT_NV32, XF_PROLONG_NV32 = 8, 9
+
+
+def transfer_plan(op, dtype, null32, nvec, fdims, cdims, n_active, aligned16=True):
+    """The kernel plan of a restrict / prolong request (qmg_transfer_plan; host only): a list with one tuple
+    (family, KB, NV, MT, CR, nchunk, small, W) per pass of up to 8 systems."""
+    out = (C.c_int * 16)()
+    check(lib().qmg_transfer_plan(op, dtype, int(null32), nvec, *fdims, *cdims, n_active, int(aligned16), out, 16), "qmg_transfer_plan")
+    return [tuple(out[8 * p:8 * p + 8]) for p in range(2) if out[8 * p] >= 0]
 
 
 def prolong_batch_nv32(null32, nvec, coarse, fine, fdims, cdims, nrhs, cstride, fstride, mask):

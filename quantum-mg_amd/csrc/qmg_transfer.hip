@@ -11,6 +11,7 @@
 #include <string.h>
 
 #include "qmg_common.h"
+#include "qmg_transfer_plan.h"
 
 namespace qmg {
 
@@ -528,92 +529,167 @@ __global__ __launch_bounds__(BLOCK) void k_brestrict_small(const void* __restric
   }
 }
 
-// two complex<float> per lane (16-byte accesses): even fnc (a pack stays inside one site), 16-byte aligned arrays
-template <typename T>
-static bool pack2_ok(const XferGeom& g, const void* nullvecs, const void* fine) {
-  return sizeof(T) == sizeof(float) && !(g.fnc & 1) && !(g.fsize & 1) && aligned16(nullvecs) && aligned16(fine);
+// sites per prolong tile: a fine half-row segment of at least 512 bytes where the lattice allows, LDS <= 48 KB
+static int prolong_tile_sites(int bx, int fnc, int cLx, int nvec, int KB) {
+  const int G = (bx / 2) * fnc;
+  int SX = (32 + G - 1) / G;
+  if (SX < 1) SX = 1;
+  if (SX > cLx) SX = cLx;
+  while (SX > 1 && (size_t)SX * (nvec * KB + 1) * sizeof(cplx) > 48 * 1024) SX--;   // (sized for complex<double> entries; complex<float> tiles use half of it)
+  return SX;
 }
 
-template <typename T>
-static int launch_restrict(const void* nullvecs, int nvec, const void* fine, void* coarse, const XferGeom& g, hipStream_t st) {
-  if ((g.bx & 1) == 0) {
-    const bool pack2 = pack2_ok<T>(g, nullvecs, fine);
-    const int G = (g.bx / 2) * g.fnc / (pack2 ? 2 : 1);
-    int NG = BLOCK / G;
+// The kernel choice of every restrict / prolong launch of this file (qmg_transfer_plan.h).  No HIP call.
+// Single-system kernels: two complex<float> per lane (16-byte accesses) with an even fnc (a pack stays inside one site) and 16-byte aligned
+// arrays.  complex<double> vectors with complex<float> null vectors (null32: a preconditioner level's narrow copy,
+// TransferMG::enable_f32_shadow): two elements per lane, so that a lane's null-vector load stays 16 bytes -- even fnc, even block width
+// (restrict), 16-byte aligned null vectors.
+// The matrix cores (qmg_transfer_mfma.hip) take the complex<float> restrict of 5-8 systems with fnc <= 2 and >= 16 null vectors where
+// make_mfma_tile finds a tile.
+XferPlan transfer_plan(int op, int f32, int null32, int nvec, int fLx, int fLy, int fnc, int cLx, int cLy, int n_total, int left, bool aligned) {
+  XferPlan pl;
+  memset(&pl, 0, sizeof(pl));
+  pl.family = XF_UNSUPPORTED;
+  const int bx = fLx / cLx, by = fLy / cLy;
+  const long fsize = (long)fLx * fLy * fnc;
+  if (null32) {
+    if ((op == XFER_OP_RESTRICT && (bx & 1)) || (fnc & 1) || (fsize & 1) || !aligned) return pl;
+    pl.family = (op == XFER_OP_RESTRICT) ? XF_RESTRICT_NV32 : XF_PROLONG_NV32;
+    pl.KB = 1;
+    pl.W = 2;
+    if (op == XFER_OP_RESTRICT) pl.smem = sizeof(cplx) * BLOCK * XFER_DC;
+    return pl;
+  }
+  if (n_total == 1 || (bx & 1)) {   // one system (or an odd block width): the single-vector kernel, system by system
+    pl.KB = 1;
+    pl.W = (f32 && !(fnc & 1) && !(fsize & 1) && aligned) ? 2 : 1;
+    if (op == XFER_OP_PROLONG) pl.family = XF_PROLONG;
+    else if ((bx & 1) == 0) { pl.family = XF_RESTRICT; pl.smem = sizeof(cplx) * BLOCK * XFER_DC; }
+    else { pl.family = XF_RESTRICT_GENERIC; pl.W = 1; }
+    return pl;
+  }
+  const int n = left < 8 ? left : 8;
+  pl.KB = left > 4 ? 8 : left > 2 ? 4 : 2;
+  if (op == XFER_OP_PROLONG) {
+    pl.NV = (pl.KB == 8 && f32 && nvec >= BPROLONG_NVB_F32) ? BPROLONG_NVB_F32 : 4;
+    pl.SX = prolong_tile_sites(bx, fnc, cLx, nvec, pl.KB);
+    pl.smem = (size_t)pl.SX * (nvec * pl.KB + 1) * (f32 ? sizeof(float2) : sizeof(cplx));
+    if (pl.smem > 64 * 1024) return pl;
+    pl.family = XF_BPROLONG_TILE;
+    return pl;
+  }
+  if (f32 && n >= 5 && fnc <= 2 && nvec >= 16) {
+    const MfmaTile L = make_mfma_tile(bx, by, fnc, nvec, sizeof(float2));
+    if (L.SX) {
+      pl.family = XF_BRESTRICT_MFMA;
+      pl.KB = 8;
+      pl.MT = (nvec <= 16) ? 1 : 2;
+      pl.CR = L.CR;
+      pl.nchunk = L.nchunk;
+      pl.small_pairs = L.CR * (L.SX < cLx ? L.SX : cLx) * L.G < BLOCK;
+      pl.SX = L.SX;
+      pl.tile = L;
+      pl.smem = ((size_t)nvec * L.Dstride + (size_t)8 * L.Fstride) * sizeof(float2);
+      return pl;
+    }
+  }
+  const int nel = bx * by * fnc;
+  if (nel <= 32 && nvec <= 24) {   // one element per lane, every load of a site in flight at once
+    pl.family = XF_BRESTRICT_SMALL;
+    pl.NV = nvec <= 8 ? 8 : nvec <= 16 ? 16 : 24;
+    return pl;
+  }
+  pl.family = XF_BRESTRICT_TILE;
+  return pl;
+}
+
+static XferPlan plan_for(int op, int f32, int null32, int nvec, const XferGeom& g, int n_total, int left, bool aligned) {
+  return transfer_plan(op, f32, null32, nvec, 2 * g.fhr, g.fLy, g.fnc, 2 * g.chr, g.cLy, n_total, left, aligned);
+}
+
+// one system through k_restrict / k_restrict_generic (T: the vectors' storage scalar; NS: the null vectors')
+template <typename T, typename NS>
+static int launch_restrict_plan(const XferPlan& pl, const void* nullvecs, int nvec, const void* fine, void* coarse, const XferGeom& g, hipStream_t st) {
+  if (pl.family == XF_RESTRICT_GENERIC) {
+    if constexpr (sizeof(T) == sizeof(NS))
+      k_restrict_generic<T><<<grid_1d((size_t)4 * g.chalf_vol * nvec / 2), BLOCK, 0, st>>>(nullvecs, nvec, fine, coarse, g);
+    else return QMG_ERR_INVALID;
+  } else if (pl.family == XF_RESTRICT || pl.family == XF_RESTRICT_NV32) {
+    const int G = (g.bx / 2) * g.fnc / pl.W;
+    int NG = BLOCK / (G > 0 ? G : 1);
     if (NG < 1) NG = 1;
     const int cLx = 2 * g.chr;
     if (NG > cLx) NG = cLx;
     const int TPG = BLOCK / NG;
     dim3 grid((unsigned)((cLx + NG - 1) / NG), g.cLy > 65535 ? 65535 : g.cLy);
-    if (pack2) k_restrict<T, 2><<<grid, BLOCK, sizeof(cplx) * BLOCK * XFER_DC, st>>>(nullvecs, nvec, fine, coarse, g, NG, TPG);
-    else k_restrict<T, 1><<<grid, BLOCK, sizeof(cplx) * BLOCK * XFER_DC, st>>>(nullvecs, nvec, fine, coarse, g, NG, TPG);
+    if constexpr (sizeof(T) != sizeof(NS)) {
+      if (pl.W != 2) return QMG_ERR_INVALID;
+      k_restrict<T, 2, NS><<<grid, BLOCK, pl.smem, st>>>(nullvecs, nvec, fine, coarse, g, NG, TPG);
+    } else {
+      if (pl.W == 2) {
+        if constexpr (sizeof(T) == sizeof(float)) k_restrict<T, 2><<<grid, BLOCK, pl.smem, st>>>(nullvecs, nvec, fine, coarse, g, NG, TPG);
+        else return QMG_ERR_INVALID;
+      } else k_restrict<T, 1><<<grid, BLOCK, pl.smem, st>>>(nullvecs, nvec, fine, coarse, g, NG, TPG);
+    }
   } else {
-    k_restrict_generic<T><<<grid_1d((size_t)4 * g.chalf_vol * nvec / 2), BLOCK, 0, st>>>(nullvecs, nvec, fine, coarse, g);
+    return pl.family == XF_UNSUPPORTED ? QMG_ERR_UNSUPPORTED : QMG_ERR_INVALID;
+  }
+  QMG_LAUNCH_CHECK();
+  return QMG_SUCCESS;
+}
+
+template <typename T, typename NS>
+static int launch_prolong_plan(const XferPlan& pl, const void* nullvecs, int nvec, const void* coarse, void* fine, const XferGeom& g, hipStream_t st) {
+  if (pl.family != XF_PROLONG && pl.family != XF_PROLONG_NV32) return pl.family == XF_UNSUPPORTED ? QMG_ERR_UNSUPPORTED : QMG_ERR_INVALID;
+  const long row_packs = (long)g.fhr * g.fnc / pl.W;
+  unsigned gx = (unsigned)((row_packs + BLOCK - 1) / BLOCK);
+  if (gx > 1024) gx = 1024;
+  const int nrows = 2 * g.fLy;
+  dim3 grid(gx, nrows > 65535 ? 65535 : nrows);
+  if constexpr (sizeof(T) != sizeof(NS)) {
+    if (pl.W != 2) return QMG_ERR_INVALID;
+    k_prolong<T, 2, NS><<<grid, BLOCK, 0, st>>>(nullvecs, nvec, coarse, fine, g);
+  } else {
+    if (pl.W == 2) {
+      if constexpr (sizeof(T) == sizeof(float)) k_prolong<T, 2><<<grid, BLOCK, 0, st>>>(nullvecs, nvec, coarse, fine, g);
+      else return QMG_ERR_INVALID;
+    } else k_prolong<T, 1><<<grid, BLOCK, 0, st>>>(nullvecs, nvec, coarse, fine, g);
   }
   QMG_LAUNCH_CHECK();
   return QMG_SUCCESS;
 }
 
 template <typename T>
-static int launch_prolong(const void* nullvecs, int nvec, const void* coarse, void* fine, const XferGeom& g, hipStream_t st) {
-  const bool pack2 = pack2_ok<T>(g, nullvecs, fine);
-  const long row_packs = (long)g.fhr * g.fnc / (pack2 ? 2 : 1);
-  unsigned gx = (unsigned)((row_packs + BLOCK - 1) / BLOCK);
-  if (gx > 1024) gx = 1024;
-  const int nrows = 2 * g.fLy;
-  dim3 grid(gx, nrows > 65535 ? 65535 : nrows);
-  if (pack2) k_prolong<T, 2><<<grid, BLOCK, 0, st>>>(nullvecs, nvec, coarse, fine, g);
-  else k_prolong<T, 1><<<grid, BLOCK, 0, st>>>(nullvecs, nvec, coarse, fine, g);
-  QMG_LAUNCH_CHECK();
-  return QMG_SUCCESS;
+static int launch_restrict(const void* nullvecs, int nvec, const void* fine, void* coarse, const XferGeom& g, hipStream_t st) {
+  const XferPlan pl = plan_for(XFER_OP_RESTRICT, sizeof(T) == sizeof(float), 0, nvec, g, 1, 1, aligned16(nullvecs) && aligned16(fine));
+  return launch_restrict_plan<T, T>(pl, nullvecs, nvec, fine, coarse, g, st);
 }
 
-// complex<double> vectors with complex<float> null vectors (a preconditioner level's narrow copy, TransferMG::enable_f32_shadow): two elements per lane,
-// so that a lane's null-vector load stays 16 bytes.  Even fnc, even block width, 16-byte aligned null vectors.
+template <typename T>
+static int launch_prolong(const void* nullvecs, int nvec, const void* coarse, void* fine, const XferGeom& g, hipStream_t st) {
+  const XferPlan pl = plan_for(XFER_OP_PROLONG, sizeof(T) == sizeof(float), 0, nvec, g, 1, 1, aligned16(nullvecs) && aligned16(fine));
+  return launch_prolong_plan<T, T>(pl, nullvecs, nvec, coarse, fine, g, st);
+}
+
 static int launch_restrict_nv32(const void* null32, int nvec, const void* fine, void* coarse, const XferGeom& g, hipStream_t st) {
-  if ((g.bx & 1) || (g.fnc & 1) || (g.fsize & 1) || !aligned16(null32)) return QMG_ERR_UNSUPPORTED;
-  const int G = (g.bx / 2) * g.fnc / 2;
-  int NG = BLOCK / (G > 0 ? G : 1);
-  if (NG < 1) NG = 1;
-  const int cLx = 2 * g.chr;
-  if (NG > cLx) NG = cLx;
-  const int TPG = BLOCK / NG;
-  dim3 grid((unsigned)((cLx + NG - 1) / NG), g.cLy > 65535 ? 65535 : g.cLy);
-  k_restrict<double, 2, float><<<grid, BLOCK, sizeof(cplx) * BLOCK * XFER_DC, st>>>(null32, nvec, fine, coarse, g, NG, TPG);
-  QMG_LAUNCH_CHECK();
-  return QMG_SUCCESS;
+  const XferPlan pl = plan_for(XFER_OP_RESTRICT, 0, 1, nvec, g, 1, 1, aligned16(null32));
+  return launch_restrict_plan<double, float>(pl, null32, nvec, fine, coarse, g, st);
 }
 static int launch_prolong_nv32(const void* null32, int nvec, const void* coarse, void* fine, const XferGeom& g, hipStream_t st) {
-  if ((g.fnc & 1) || (g.fsize & 1) || !aligned16(null32)) return QMG_ERR_UNSUPPORTED;
-  const long row_packs = (long)g.fhr * g.fnc / 2;
-  unsigned gx = (unsigned)((row_packs + BLOCK - 1) / BLOCK);
-  if (gx > 1024) gx = 1024;
-  const int nrows = 2 * g.fLy;
-  dim3 grid(gx, nrows > 65535 ? 65535 : nrows);
-  k_prolong<double, 2, float><<<grid, BLOCK, 0, st>>>(null32, nvec, coarse, fine, g);
-  QMG_LAUNCH_CHECK();
-  return QMG_SUCCESS;
+  const XferPlan pl = plan_for(XFER_OP_PROLONG, 0, 1, nvec, g, 1, 1, aligned16(null32));
+  return launch_prolong_plan<double, float>(pl, null32, nvec, coarse, fine, g, st);
 }
 
-// qmg_transfer_mfma.hip: the batched restrict as a contraction on the matrix cores (SITE_DECLINED: shapes not served there)
-int restrict_batch_mfma(int f32, const void* nullvecs, int nvec, const void* fine, void* coarse, int fhr, int fLy, int fnc, int chr, int cLy, int cnc, int bx, int by,
+// qmg_transfer_mfma.hip: the batched restrict as a contraction on the matrix cores, for a pass planned as XF_BRESTRICT_MFMA
+int restrict_batch_mfma(const XferPlan& pl, const void* nullvecs, int nvec, const void* fine, void* coarse, int fhr, int fLy, int fnc, int chr, int cLy, int cnc, int bx, int by,
                         long fhalf_vol, long fsize, const int* ids8, int n, long cstride, long fstride, hipStream_t st);
-
-// sites per prolong tile: a fine half-row segment of at least 512 bytes where the lattice allows, LDS <= 48 KB
-static int prolong_tile_sites(const XferGeom& g, int nvec, int KB) {
-  const int G = (g.bx / 2) * g.fnc;
-  int SX = (32 + G - 1) / G;
-  if (SX < 1) SX = 1;
-  if (SX > 2 * g.chr) SX = 2 * g.chr;
-  while (SX > 1 && (size_t)SX * (nvec * KB + 1) * sizeof(cplx) > 48 * 1024) SX--;   // (sized for complex<double> entries; complex<float> tiles use half of it)
-  return SX;
-}
 
 template <typename T>
 static int prolong_batch_impl(const void* nullvecs, int nvec, const void* coarse, void* fine, const XferGeom& g, const BatchIdx& bi, size_t cstride,
                               size_t fstride, hipStream_t st) {
   typedef typename CStore<T>::type ct;
-  if (bi.n == 1 || (g.bx & 1)) {   // one system (or an odd block width): the single-vector kernel, system by system
+  constexpr int f32 = sizeof(T) == sizeof(float);
+  if (plan_for(XFER_OP_PROLONG, f32, 0, nvec, g, bi.n, bi.n, true).family == XF_PROLONG) {   // system by system
     for (int s = 0; s < bi.n; s++) {
       const int rc = launch_prolong<T>(nullvecs, nvec, (const ct*)coarse + (size_t)bi.id[s] * cstride, (ct*)fine + (size_t)bi.id[s] * fstride, g, st);
       if (rc) return rc;
@@ -621,16 +697,22 @@ static int prolong_batch_impl(const void* nullvecs, int nvec, const void* coarse
     return QMG_SUCCESS;
   }
   for (int s0 = 0; s0 < bi.n; s0 += 8) {
-    const int left = bi.n - s0;
-    const int KB = left > 4 ? 8 : left > 2 ? 4 : 2;
-    const int SX = prolong_tile_sites(g, nvec, KB);
-    const size_t smem = (size_t)SX * (nvec * KB + 1) * sizeof(ct);
-    if (smem > 64 * 1024) return QMG_ERR_UNSUPPORTED;
+    const XferPlan pl = plan_for(XFER_OP_PROLONG, f32, 0, nvec, g, bi.n, bi.n - s0, true);
+    if (pl.family != XF_BPROLONG_TILE) return QMG_ERR_UNSUPPORTED;
+    const int SX = pl.SX;
+    const size_t smem = pl.smem;
     dim3 grid((unsigned)((2 * g.chr + SX - 1) / SX), g.cLy > 65535 ? 65535 : g.cLy);
-    if (KB == 8 && sizeof(T) == 4 && nvec >= 12) k_bprolong_tile<T, 8, 12><<<grid, BLOCK, smem, st>>>(nullvecs, nvec, coarse, fine, g, make_pass(bi, s0), (long)cstride, (long)fstride, SX);
-    else if (KB == 8) k_bprolong_tile<T, 8><<<grid, BLOCK, smem, st>>>(nullvecs, nvec, coarse, fine, g, make_pass(bi, s0), (long)cstride, (long)fstride, SX);
-    else if (KB == 4) k_bprolong_tile<T, 4><<<grid, BLOCK, smem, st>>>(nullvecs, nvec, coarse, fine, g, make_pass(bi, s0), (long)cstride, (long)fstride, SX);
-    else k_bprolong_tile<T, 2><<<grid, BLOCK, smem, st>>>(nullvecs, nvec, coarse, fine, g, make_pass(bi, s0), (long)cstride, (long)fstride, SX);
+    // (the condition and the instantiation of a launch share their literals: a plan that names no instantiated kernel launches nothing)
+    bool launched = false;
+#define QMG_BP(KBV, NVBV)                                                                                                                                     \
+  if (!launched && pl.KB == KBV && pl.NV == NVBV) {                                                                                                           \
+    k_bprolong_tile<T, KBV, NVBV><<<grid, BLOCK, smem, st>>>(nullvecs, nvec, coarse, fine, g, make_pass(bi, s0), (long)cstride, (long)fstride, SX);           \
+    launched = true;                                                                                                                                          \
+  }
+    if constexpr (f32) QMG_BP(8, BPROLONG_NVB_F32)
+    QMG_BP(8, 4) QMG_BP(4, 4) QMG_BP(2, 4)
+    if (!launched) return QMG_ERR_INVALID;
+#undef QMG_BP
     QMG_LAUNCH_CHECK();
   }
   return QMG_SUCCESS;
@@ -640,38 +722,55 @@ template <typename T>
 static int restrict_batch_impl(const void* nullvecs, int nvec, const void* fine, void* coarse, const XferGeom& g, const BatchIdx& bi, size_t fstride,
                                size_t cstride, hipStream_t st) {
   typedef typename CStore<T>::type ct;
-  if (bi.n == 1 || (g.bx & 1)) {
-    for (int s = 0; s < bi.n; s++) {
-      const int rc = launch_restrict<T>(nullvecs, nvec, (const ct*)fine + (size_t)bi.id[s] * fstride, (ct*)coarse + (size_t)bi.id[s] * cstride, g, st);
-      if (rc) return rc;
+  constexpr int f32 = sizeof(T) == sizeof(float);
+  {
+    const int fam = plan_for(XFER_OP_RESTRICT, f32, 0, nvec, g, bi.n, bi.n, true).family;
+    if (fam == XF_RESTRICT || fam == XF_RESTRICT_GENERIC) {   // system by system
+      for (int s = 0; s < bi.n; s++) {
+        const int rc = launch_restrict<T>(nullvecs, nvec, (const ct*)fine + (size_t)bi.id[s] * fstride, (ct*)coarse + (size_t)bi.id[s] * cstride, g, st);
+        if (rc) return rc;
+      }
+      return QMG_SUCCESS;
     }
-    return QMG_SUCCESS;
   }
   const long ncs = 2 * g.chalf_vol;
   const long nblk = (ncs + BLOCK / 32 - 1) / (BLOCK / 32);
   const unsigned gx = (unsigned)(nblk > 262144 ? 262144 : nblk);
-  const int nel = g.bx * g.by * g.fnc;
   for (int s0 = 0; s0 < bi.n; s0 += 8) {
-    const int left = bi.n - s0;
-    {
-      const PassIds pi = make_pass(bi, s0);
-      const int rc = restrict_batch_mfma(sizeof(T) == 4, nullvecs, nvec, fine, coarse, g.fhr, g.fLy, g.fnc, g.chr, g.cLy, g.cnc, g.bx, g.by, g.fhalf_vol, g.fsize, pi.id, pi.n,
-                                         (long)cstride, (long)fstride, st);
-      if (rc != SITE_DECLINED) { if (rc) return rc; continue; }
+    const XferPlan pl = plan_for(XFER_OP_RESTRICT, f32, 0, nvec, g, bi.n, bi.n - s0, true);
+    const PassIds pi = make_pass(bi, s0);
+    bool launched = false;
+#define QMG_RS(KBV, NVTV)                                                                                                                  \
+  if (!launched && pl.KB == KBV && pl.NV == NVTV) {                                                                                        \
+    k_brestrict_small<T, KBV, NVTV><<<gx, BLOCK, 0, st>>>(nullvecs, nvec, fine, coarse, g, pi, (long)cstride, (long)fstride);              \
+    launched = true;                                                                                                                       \
+  }
+#define QMG_RS_KB(KBV) QMG_RS(KBV, 8) QMG_RS(KBV, 16) QMG_RS(KBV, 24)
+#define QMG_RT(KBV)                                                                                                                        \
+  if (!launched && pl.KB == KBV) {                                                                                                         \
+    k_brestrict_tile<T, KBV><<<gx, BLOCK, 0, st>>>(nullvecs, nvec, fine, coarse, g, pi, (long)cstride, (long)fstride);                     \
+    launched = true;                                                                                                                       \
+  }
+    switch (pl.family) {
+      case XF_BRESTRICT_MFMA: {
+        const int rc = restrict_batch_mfma(pl, nullvecs, nvec, fine, coarse, g.fhr, g.fLy, g.fnc, g.chr, g.cLy, g.cnc, g.bx, g.by, g.fhalf_vol, g.fsize, pi.id, pi.n,
+                                           (long)cstride, (long)fstride, st);
+        if (rc) return rc;
+        continue;
+      }
+      case XF_BRESTRICT_SMALL:
+        QMG_RS_KB(8) QMG_RS_KB(4) QMG_RS_KB(2)
+        break;
+      case XF_BRESTRICT_TILE:
+        QMG_RT(8) QMG_RT(4) QMG_RT(2)
+        break;
+      default:
+        return QMG_ERR_UNSUPPORTED;
     }
-    const int KB = left > 4 ? 8 : left > 2 ? 4 : 2;
-    if (nel <= 32 && nvec <= 24) {   // one element per lane, every load of a site in flight at once
-#define QMG_RS(KBV, NVTV) k_brestrict_small<T, KBV, NVTV><<<gx, BLOCK, 0, st>>>(nullvecs, nvec, fine, coarse, g, make_pass(bi, s0), (long)cstride, (long)fstride)
-#define QMG_RS_KB(KBV) { if (nvec <= 8) QMG_RS(KBV, 8); else if (nvec <= 16) QMG_RS(KBV, 16); else QMG_RS(KBV, 24); }
-      if (KB == 8) QMG_RS_KB(8) else if (KB == 4) QMG_RS_KB(4) else QMG_RS_KB(2)
+    if (!launched) return QMG_ERR_INVALID;
+#undef QMG_RT
 #undef QMG_RS_KB
 #undef QMG_RS
-      QMG_LAUNCH_CHECK();
-      continue;
-    }
-    if (left > 4) k_brestrict_tile<T, 8><<<gx, BLOCK, 0, st>>>(nullvecs, nvec, fine, coarse, g, make_pass(bi, s0), (long)cstride, (long)fstride);
-    else if (left > 2) k_brestrict_tile<T, 4><<<gx, BLOCK, 0, st>>>(nullvecs, nvec, fine, coarse, g, make_pass(bi, s0), (long)cstride, (long)fstride);
-    else k_brestrict_tile<T, 2><<<gx, BLOCK, 0, st>>>(nullvecs, nvec, fine, coarse, g, make_pass(bi, s0), (long)cstride, (long)fstride);
     QMG_LAUNCH_CHECK();
   }
   return QMG_SUCCESS;
@@ -764,6 +863,26 @@ int qmg_restrict_batch_t(int dtype, const void* nullvecs, int nvec, const void* 
 int qmg_restrict_batch(const void* nullvecs, int nvec, const void* fine, void* coarse, int fLx, int fLy, int fnc, int cLx, int cLy, int cnc,
                        int nrhs, size_t fstride, size_t cstride, unsigned mask, void* stream) {
   return qmg_restrict_batch_t(QMG_C64, nullvecs, nvec, fine, coarse, fLx, fLy, fnc, cLx, cLy, cnc, nrhs, fstride, cstride, mask, stream);
+}
+
+// The plan of a request (qmg_transfer_plan.h): what transfer_plan, which every launch above switches on, answers.  No HIP call.
+int qmg_transfer_plan(int op, int dtype, int null32, int nvec, int fLx, int fLy, int fnc, int cLx, int cLy, int cnc, int n_active, int aligned16,
+                      int* plan_out, int plan_len) {
+  if ((op != XFER_OP_RESTRICT && op != XFER_OP_PROLONG) || !valid_dtype(dtype) || (null32 && dtype != QMG_C64) || !plan_out) return QMG_ERR_INVALID;
+  if (nvec < 1 || nvec > cnc || n_active < 1 || n_active > BATCH_MAX) return QMG_ERR_INVALID;
+  XferGeom g;
+  const int rc = make_geom(&g, fLx, fLy, fnc, cLx, cLy, cnc);
+  if (rc) return rc;
+  const XferPlan first = transfer_plan(op, dtype == QMG_C32, null32, nvec, fLx, fLy, fnc, cLx, cLy, n_active, n_active, aligned16 != 0);
+  const int npass = (first.KB == 1 || first.family == XF_UNSUPPORTED) ? 1 : (n_active + 7) / 8;
+  if (plan_len < npass * XFER_PLAN_INTS) return QMG_ERR_INVALID;
+  for (int i = 0; i < plan_len; i++) plan_out[i] = -1;
+  for (int p = 0; p < npass; p++) {
+    const XferPlan pl = p ? transfer_plan(op, dtype == QMG_C32, null32, nvec, fLx, fLy, fnc, cLx, cLy, n_active, n_active - 8 * p, aligned16 != 0) : first;
+    const int v[XFER_PLAN_INTS] = {pl.family, pl.KB, pl.NV, pl.MT, pl.CR, pl.nchunk, pl.small_pairs, pl.W};
+    for (int i = 0; i < XFER_PLAN_INTS; i++) plan_out[p * XFER_PLAN_INTS + i] = v[i];
+  }
+  return QMG_SUCCESS;
 }
 
 // block_orthonormalize (transfer.h:514-607): the reference's own formulation -- classical

@@ -21,6 +21,7 @@
 // Operand maps (as kernel C of qmg_stencil_mfma.hip): lane = 16 lq + lr; A (16 x 4): row lr, k lq; B (4 x 16): k lq, column lr;
 // C (16 x 16): column lr, row 4 i + lq in accumulator register i.
 #include "qmg_common.h"
+#include "qmg_transfer_plan.h"
 
 namespace qmg {
 
@@ -29,7 +30,6 @@ struct XferGeomM {      // (the geometry of qmg_transfer.hip, restated: the two 
   long fhalf_vol, fsize;
 };
 struct PassIdsM { int n; int id[8]; };
-struct MfmaTile { int SX, CR, nchunk, Dstride, Fstride, G, R; };
 
 __device__ __forceinline__ long m_coarse_site_index(const XferGeomM& g, int cx, int cy) {
   const int p = (cx + cy) & 1;
@@ -153,50 +153,29 @@ __global__ __launch_bounds__(BLOCK) void k_brestrict_mfma(const void* __restrict
   }
 }
 
-// tile shape for a geometry, or SX = 0 when the matrix-core kernel does not serve it
-static MfmaTile make_mfma_tile(const XferGeomM& g, int nvec, size_t esz) {
-  MfmaTile L;
-  L.SX = 0;
-  if ((g.bx & 1) || nvec > 32) return L;
-  L.G = (g.bx / 2) * g.fnc;
-  L.R = 2 * g.by;
-  int best = 0;
-  for (int cr = 1; cr <= L.R; cr++) {
-    if (L.R % cr || (cr * L.G) % 4) continue;            // elements of a site per chunk: a multiple of the MFMA's K extent
-    const size_t bytes = (size_t)(nvec + 8) * ((size_t)cr * 4 * L.G + 1) * esz;
-    if (bytes <= 60 * 1024) best = cr;
-  }
-  if (!best) return L;
-  L.SX = 4;
-  L.CR = best;
-  L.nchunk = L.R / best;
-  L.Dstride = L.CR * L.SX * L.G + 1;                     // odd in elements: operand columns spread over the LDS words
-  L.Fstride = L.CR * L.SX * L.G + 1;
-  return L;
-}
-
-// C-linkage-free entry point for qmg_transfer.hip: SITE_DECLINED when the shapes are not served.  The matrix cores serve where they are the
-// faster kernel AFTER the vector-FMA restricts stopped waiting for their loads one by one (qmg_common.h, RawC): complex<float>, 5-8 systems,
-// from the nc = 2 fine level to >= 16 null vectors (2048^2 -> 512^2 x 24: 1.09 against 1.33 ms).  Elsewhere the vector kernels are equal or
-// better (512^2 -> 128^2 x 24, 8 systems: 0.55 against 0.58 ms; 1024^2 -> 256^2 x 8: 0.29 against 0.34; every shape at <= 4 systems:
-// 0.17-0.72 against 0.33-1.03 ms; round-3 transfer profiles), and so are the fp64 restrict and both prolongs.
-int restrict_batch_mfma(int f32, const void* nullvecs, int nvec, const void* fine, void* coarse, int fhr, int fLy, int fnc, int chr, int cLy, int cnc, int bx, int by,
+// C-linkage-free launcher for qmg_transfer.hip, for a pass whose plan (transfer_plan, qmg_transfer_plan.h) is XF_BRESTRICT_MFMA.  The matrix
+// cores serve where they are the faster kernel AFTER the vector-FMA restricts stopped waiting for their loads one by one (qmg_common.h,
+// RawC): complex<float>, 5-8 systems, from the nc = 2 fine level to >= 16 null vectors (2048^2 -> 512^2 x 24: 1.09 against 1.33 ms).
+// Elsewhere the vector kernels are equal or better (512^2 -> 128^2 x 24, 8 systems: 0.55 against 0.58 ms; 1024^2 -> 256^2 x 8: 0.29 against
+// 0.34; every shape at <= 4 systems: 0.17-0.72 against 0.33-1.03 ms; round-3 transfer profiles), and so are the fp64 restrict and both prolongs.
+int restrict_batch_mfma(const XferPlan& pl, const void* nullvecs, int nvec, const void* fine, void* coarse, int fhr, int fLy, int fnc, int chr, int cLy, int cnc, int bx, int by,
                         long fhalf_vol, long fsize, const int* ids8, int n, long cstride, long fstride, hipStream_t st) {
-  if (!f32 || !(n >= 5 && fnc <= 2 && nvec >= 16)) return SITE_DECLINED;
+  if (pl.family != XF_BRESTRICT_MFMA) return QMG_ERR_INVALID;
   const XferGeomM g = {fhr, fLy, fnc, chr, cLy, cnc, bx, by, fhalf_vol, fsize};
   PassIdsM ids;
   ids.n = n;
   for (int q = 0; q < 8; q++) ids.id[q] = ids8[q];
-  const MfmaTile L = make_mfma_tile(g, nvec, sizeof(float2));
-  if (!L.SX) return SITE_DECLINED;
-  const size_t smem = ((size_t)nvec * L.Dstride + (size_t)8 * L.Fstride) * sizeof(float2);
+  const MfmaTile L = pl.tile;
+  const size_t smem = pl.smem;
   dim3 grid((unsigned)((2 * g.chr + L.SX - 1) / L.SX), g.cLy > 65535 ? 65535u : (unsigned)g.cLy);
-  if (nvec <= 16) {
+  if (pl.MT == 1) {
     if (smem > 64 * 1024) QMG_HIP_CHECK(hipFuncSetAttribute((const void*)k_brestrict_mfma<float, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
     k_brestrict_mfma<float, 1><<<grid, BLOCK, smem, st>>>(nullvecs, nvec, fine, coarse, g, ids, cstride, fstride, L);
-  } else {
+  } else if (pl.MT == 2) {
     if (smem > 64 * 1024) QMG_HIP_CHECK(hipFuncSetAttribute((const void*)k_brestrict_mfma<float, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
     k_brestrict_mfma<float, 2><<<grid, BLOCK, smem, st>>>(nullvecs, nvec, fine, coarse, g, ids, cstride, fstride, L);
+  } else {
+    return QMG_ERR_INVALID;
   }
   QMG_LAUNCH_CHECK();
   return QMG_SUCCESS;

@@ -158,8 +158,10 @@ def test_batch_blas_and_reductions_f32(n, stride_pad, nrhs, mask):
 @pytest.mark.parametrize("fd,cd,nrhs,mask", [((32, 32, 2), (8, 8, 8), 1, 1), ((32, 32, 2), (8, 8, 8), 8, 0xFF), ((32, 32, 2), (8, 8, 24), 5, 0b11011), ((16, 16, 8), (4, 4, 8), 3, 0b111),
                                             ((16, 8, 24), (4, 2, 24), 2, 0b11), ((24, 12, 2), (12, 6, 6), 4, 0b1111), ((12, 12, 2), (4, 4, 6), 2, 0b11)])
 def test_transfer_f32_single_and_tiled(fd, cd, nrhs, mask):
-    """restrict / prolong with complex<float> null vectors and vectors: the one-system kernels (nrhs = 1), the LDS-tiled
-    batch kernels (2, 4, 8 accumulators), 2x2 blocks, and the odd-block-width fallback (12 -> 4: bx = 3)."""
+    """restrict / prolong with complex<float> null vectors and vectors against the oracle, whole-vector: the one-system kernels (nrhs = 1), batch
+    kernels with 2, 4 and 8 systems (the 8-system row has nvec = 8: neither the matrix-core restrict nor the 12-wide prolong is reached here), 2x2
+    blocks, and the odd-block-width fallback (12 -> 4: bx = 3).  Which kernel a row runs is not asserted here: test_gpu_transfer_routes.py holds
+    one row per kernel plan, asserts the plan and compares elementwise with an independent reference."""
     fsize, csize = fd[0] * fd[1] * fd[2], cd[0] * cd[1] * cd[2]
     nvec = cd[2]
     nv = r32(cs.gaussian_cvec(nvec * fsize, 1))
