@@ -328,7 +328,8 @@ int qmg_restrict_batch(const void* nullvecs, int nvec, const void* fine, void* c
 /* Same operations as the entry points above with the storage type of EVERY array argument (vectors, matrices in the
  * descriptor, null vectors) given by `dtype` (qmg_dtype); host-side scalars and reduction results stay double.  With
  * QMG_C64 they ARE the entry points above.  With QMG_C32: the fine kernels (nc = 1, 2, 4) compute in fp32, the coarse
- * kernels widen to fp64 in registers (f64 FMA / f64 MFMA) and round once on store, reductions accumulate in fp64.
+ * vector-FMA kernels (B / B32) widen to fp64 in registers and round once on store, the coarse multi-rhs kernel (C: 4-5 systems up,
+ * nc in {8,12,16,24,32}) multiplies on the f32 matrix cores with fp32 accumulators, reductions accumulate in fp64.
  * Parity bar: relative L2 <= 5e-6 per apply against the fp64 oracle on the same (rounded) inputs.
  * fp32 arrays should be 16-byte aligned with even strides (anything qmg_malloc returns is); otherwise the kernels fall
  * back to 8-byte accesses.  nrhs <= 16, `mask` selects the active systems (nrhs = 1, mask = 1 for a single vector). */
@@ -441,6 +442,27 @@ int qmg_restrict_batch_nv32(const void* nullvecs_c32, int nvec, const void* fine
  * (a member the family does not use is 0).  QMG_ERR_INVALID: a request the entry points reject, or plan_len too short. */
 int qmg_transfer_plan(int op, int dtype, int null32, int nvec, int fLx, int fLy, int fnc, int cLx, int cLy, int cnc, int n_active,
                       int aligned16, int* plan_out, int plan_len);
+
+/* Which kernel serves a stencil apply: the answer of the one host function every stencil launch switches on, at the CURRENT values of the
+ * tuning knobs stencil_site, stencil_pair, stencil_mfma and pair_prefetch.  Host only, no HIP call.
+ * entry: the entry point (QMG_SE_*); mat: matrices 0 complex<double>, 1 complex<float>, 2 complex<half>; vec32: complex<float> vectors
+ * (QMG_SE_MASKED stands for qmg_stencil_apply_batch / _t / _mat32 / _mat16_t by these two); n_active: the active systems; holes: they are
+ * not systems 0 .. n_active-1 (QMG_SE_EPI: the system is not 0); inplace: lhs == rhs; has_clover / has_hopping: the descriptor's pointers
+ * are set; epilogue: 0, 1 (no dotv) or 2 (with the dots), QMG_SE_EPI only; slab_rows: `rows` of QMG_SE_SLAB.
+ * Writes 12 ints per pass (one pass, except kernel C: one per 16 systems) and -1 into the rest of plan_out:
+ *   family   0 unsupported (the call returns QMG_ERR_UNSUPPORTED), 1 k_stencil_elem (A), 2 k_stencil_pair (A2), 3 k_stencil_site (S),
+ *            4 k_stencil_gen (B), 5 k_stencil_gen32 (B32), 6 k_stencil_mfma (C), 7 the 1 x 1 lattice, 8 success with nothing launched,
+ *            9 invalid (the call returns QMG_ERR_INVALID)
+ *   storage  of the instantiation: 1 narrow matrices | 2 complex<float> vectors | 4 complex<half> matrices
+ *   NC       compile-time nc (A, A2, S, C; C's two-site form: 16); 0 where nc is a run-time argument
+ *   P        PT (B), PP (B32), MODE (C), SHAPE (S), ROWS (A2)
+ *   K        KR (B, B32), else the systems of the pass
+ *   flags    1 EPI | 2 with dots (grid.y capped) | 4 NORM | 8 PF | 16 ZERO | 32 BATCH | 64 VL | 128 PAIR | 256 shift term (1 x 1)
+ *   S, H     tile of B / B32;  smem: dynamic LDS bytes;  gx, gy: the grid;  nk: systems the pass serves
+ * QMG_ERR_INVALID: arguments no entry point can be called with, or plan_len too short. */
+enum { QMG_SE_APPLY = 0, QMG_SE_MASKED = 1, QMG_SE_H16 = 2, QMG_SE_NORM2 = 3, QMG_SE_EPI = 4, QMG_SE_SLAB = 5 };
+int qmg_stencil_plan(int entry, int mat, int vec32, int Lx, int Ly, int nc, unsigned pieces, int n_active, int holes, int inplace,
+                     int has_clover, int has_hopping, int epilogue, int slab_rows, int* plan_out, int plan_len);
 
 /* 16-bit storage of the fine operator (SURVEY 8f-4 "16-bit-storage smoother"; nc = 2 only): d->clover / d->hopping point to
  * complex<half> copies (qmg_convert_to_c16), vectors are complex<float>, arithmetic fp32: 112 B/site instead of 192.  The

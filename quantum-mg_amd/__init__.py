@@ -45,7 +45,7 @@ ABI_SYMBOLS = [
     "qmg_batch_blas", "qmg_batch_multi_caxpy", "qmg_batch_reduce", "qmg_batch_multidot", "qmg_prolong_batch", "qmg_restrict_batch",
     "qmg_comm_get_unique_id", "qmg_comm_init", "qmg_comm_init_env", "qmg_comm_rendezvous", "qmg_comm_all_ok", "qmg_comm_world", "qmg_allreduce_sum_f64", "qmg_comm_finalize",
     "qmg_convert", "qmg_stencil_apply_t", "qmg_batch_blas_t", "qmg_batch_multi_caxpy_t", "qmg_batch_gcr_update_t", "qmg_batch_cgm_update_t", "qmg_prolong_batch_nv32", "qmg_restrict_batch_nv32", "qmg_batch_reduce_t", "qmg_batch_multidot_t",
-    "qmg_prolong_batch_t", "qmg_restrict_batch_t", "qmg_transfer_plan",
+    "qmg_prolong_batch_t", "qmg_restrict_batch_t", "qmg_transfer_plan", "qmg_stencil_plan",
     "qmg_convert_to_c16", "qmg_convert_from_c16", "qmg_stencil_apply_h16", "qmg_stencil_apply_mat16_t", "qmg_stencil_apply_norm2",
     "qmg_wilson_apply_direct", "qmg_wilson_hops_direct", "qmg_halo_exchange", "qmg_halo_exchange_parity", "qmg_stencil_apply_slab", "qmg_wilson_fill_slab", "qmg_comm_set_distributed_reductions", "qmg_coarse_build_slab", "qmg_gaussian_slab", "qmg_rb_hopping_slab", "qmg_build_dagger_slab", "qmg_staggered_fill_slab", "qmg_laplace_fill_slab", "qmg_comm_emulate_begin", "qmg_comm_emulate_attach", "qmg_comm_emulate_end",
     "qmg_stencil_apply_epi_t", "qmg_wilson_apply_direct_epi", "qmg_wilson_hops_direct_epi", "qmg_batch_mr_dots_t", "qmg_batch_mr_update_t", "qmg_batch_mr_read_dots",
@@ -648,6 +648,24 @@ def transfer_plan(op, dtype, null32, nvec, fdims, cdims, n_active, aligned16=Tru
     out = (C.c_int * 16)()
     check(lib().qmg_transfer_plan(op, dtype, int(null32), nvec, *fdims, *cdims, n_active, int(aligned16), out, 16), "qmg_transfer_plan")
     return [tuple(out[8 * p:8 * p + 8]) for p in range(2) if out[8 * p] >= 0]
+
+
+# entry points, kernel families, storage bits and flags of qmg_stencil_plan (include/qmg_hip.h)
+SE_APPLY, SE_MASKED, SE_H16, SE_NORM2, SE_EPI, SE_SLAB = range(6)
+SF_UNSUPPORTED, SF_ELEM, SF_PAIR, SF_SITE, SF_GEN, SF_GEN32, SF_MFMA, SF_VOLUME1, SF_NOTHING, SF_INVALID = range(10)
+SST_M32, SST_V32, SST_M16 = 1, 2, 4
+SPF_EPI, SPF_DOTS, SPF_NORM, SPF_PF, SPF_ZERO, SPF_BATCH, SPF_VL, SPF_PAIR, SPF_SHIFT = 1, 2, 4, 8, 16, 32, 64, 128, 256
+STENCIL_PLAN_INTS = 12
+
+
+def stencil_plan(entry, mat, vec32, dims, pieces, n_active, holes=False, inplace=False, clover=True, hopping=True, epilogue=0, slab_rows=0, max_passes=4):
+    """The kernel plan of a stencil apply at the current tuning knobs (qmg_stencil_plan; host only): a list with one tuple
+    (family, storage, NC, P, K, flags, S, H, smem, gx, gy, nk) per pass."""
+    n = STENCIL_PLAN_INTS * max_passes
+    out = (C.c_int * n)()
+    check(lib().qmg_stencil_plan(entry, mat, int(vec32), *dims, C.c_uint(pieces), n_active, int(holes), int(inplace), int(clover), int(hopping), epilogue, slab_rows,
+                                 out, n), "qmg_stencil_plan")
+    return [tuple(out[STENCIL_PLAN_INTS * p:STENCIL_PLAN_INTS * (p + 1)]) for p in range(max_passes) if out[STENCIL_PLAN_INTS * p] >= 0]
 
 
 def prolong_batch_nv32(null32, nvec, coarse, fine, fdims, cdims, nrhs, cstride, fstride, mask):

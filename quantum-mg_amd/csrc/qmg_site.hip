@@ -26,6 +26,7 @@
 #include <hip/hip_fp16.h>
 
 #include "qmg_common.h"
+#include "qmg_stencil_plan.h"
 
 namespace qmg {
 
@@ -235,18 +236,16 @@ static void launch_site_b(const SiteArgs& a, int shape, bool zero, dim3 grid, hi
   else k_stencil_site<ST, 0, false, BATCH><<<grid, BLOCK, 0, st>>>(a);
 }
 template <int ST>
-static void launch_site(const SiteArgs& a, int shape, bool zero, dim3 grid, hipStream_t st) {
-  if (a.nrhs == 1) launch_site_b<ST, false>(a, shape, zero, grid, st);
-  else launch_site_b<ST, true>(a, shape, zero, grid, st);
+static void launch_site(const SiteArgs& a, const StencilPlan& pl, dim3 grid, hipStream_t st) {
+  if (pl.flags & SPF_BATCH) launch_site_b<ST, true>(a, pl.P, (pl.flags & SPF_ZERO) != 0, grid, st);
+  else launch_site_b<ST, false>(a, pl.P, (pl.flags & SPF_ZERO) != 0, grid, st);
 }
 
-// storage: 0 = complex<half> matrices + complex<float> vectors, 1 = complex<float>, 2 = complex<double>.  `ridx` = the slots
-// of the n right-hand sides (NULL: 0..n-1).  nc = 2 only.  `only_where_faster`: return SITE_DECLINED for the launches that
-// kernel A of qmg_stencil.hip does as well or better -- measured at 4096^2 (tools/h16_shapes.py): fp64 M 1.10 ms both,
-// fp64 batches of 8 0.63 ms (A) against 0.78 ms, fp64 D_eo 0.395 ms (site) against 0.425 ms.
-int site_kernel_apply(int storage, const qmg_stencil_desc* d, void* lhs, const void* rhs, unsigned pieces, int n, long vec_stride,
-                      const unsigned char* ridx, hipStream_t st, bool only_where_faster, const SlabHalo* slab) {
-  if (d->nc != 2 || n < 1 || n > 16 || storage < 0 || storage > 2) return QMG_ERR_UNSUPPORTED;
+// Kernel S on the plan of the launch (qmg_stencil_plan.h: site_plan; family SF_SITE): storage, shape, ZERO, BATCH and the grid are the plan's.
+// `ridx` = the slots of the n right-hand sides (NULL: 0..n-1).  nc = 2 only.
+int launch_stencil_site(const StencilPlan& pl, const qmg_stencil_desc* d, void* lhs, const void* rhs, unsigned pieces, int n, long vec_stride,
+                        const unsigned char* ridx, hipStream_t st, const SlabHalo* slab) {
+  if (pl.family != SF_SITE) return QMG_ERR_INVALID;
   SiteArgs a;
   a.clover = d->clover; a.hopping = d->hopping; a.lhs = lhs; a.rhs = rhs;
   a.hr = d->Lx / 2; a.Ly = d->Ly;
@@ -260,7 +259,6 @@ int site_kernel_apply(int storage, const qmg_stencil_desc* d, void* lhs, const v
   const unsigned even_bits = QMG_P_CLOVER_E | QMG_P_EO | QMG_P_SHIFT_E | QMG_P_ZERO_E;
   const unsigned odd_bits = QMG_P_CLOVER_O | QMG_P_OE | QMG_P_SHIFT_O | QMG_P_ZERO_O;
   const bool ev = pieces & even_bits, od = pieces & odd_bits;
-  if (!ev && !od) return QMG_SUCCESS;
   a.par_first = ev ? 0 : 1;
   a.par_count = (ev && od) ? 2 : 1;
   a.halo_lo = slab ? slab->lo : nullptr;
@@ -269,29 +267,24 @@ int site_kernel_apply(int storage, const qmg_stencil_desc* d, void* lhs, const v
   a.boundary_only = slab && slab->rows == 2;
   a.y_first = (slab && slab->rows == 1) ? 1 : 0;
   a.y_count = a.boundary_only ? 2 : (slab && slab->rows == 1) ? d->Ly - 2 : d->Ly;
-  if (a.y_count <= 0) return QMG_SUCCESS;
   a.nrows = a.y_count * a.par_count;
-  // the compile-time shape, if every processed parity asks for the same complete set
-  int sh[2] = {0, 0};
-  bool zero = true;
-  for (int q = 0; q < a.par_count; q++) {
-    const int p = (a.par_count == 2) ? q : a.par_first;
-    const bool cl = d->clover && ((pieces >> p) & 1u);
-    const unsigned hm = d->hopping ? ((pieces >> (2 + 4 * p)) & 0xFu) : 0u;
-    sh[q] = (hm == 0xFu) ? (cl ? 1 : 2) : 0;
-    if (!((pieces >> (12 + p)) & 1u)) zero = false;
-  }
-  int shape = (a.par_count == 2 && sh[0] != sh[1]) ? 0 : sh[0];
-  if (only_where_faster && storage == 2 && !(n == 1 && shape == 2)) return SITE_DECLINED;
-  const int lps = storage == 0 ? 1 : storage == 1 ? 2 : 4;
-  const long lanes = (long)a.hr * lps;
-  unsigned gy = a.nrows > 65535 ? 65535u : (unsigned)a.nrows;
-  dim3 grid((unsigned)((lanes + BLOCK - 1) / BLOCK), gy);
-  if (storage == 0) launch_site<0>(a, shape, zero, grid, st);
-  else if (storage == 1) launch_site<1>(a, shape, zero, grid, st);
-  else launch_site<2>(a, shape, zero, grid, st);
+  const dim3 grid((unsigned)pl.gx, (unsigned)pl.gy);
+  if (pl.storage & SST_M16) launch_site<0>(a, pl, grid, st);
+  else if (pl.storage & SST_V32) launch_site<1>(a, pl, grid, st);
+  else launch_site<2>(a, pl, grid, st);
   QMG_LAUNCH_CHECK();
   return QMG_SUCCESS;
+}
+
+// the entries of this file that go to kernel S themselves: the plan of a direct request in `storage` (0 = complex<half> matrices + complex<float>
+// vectors, 1 = complex<float>, 2 = complex<double>), then the launch
+static int site_entry_apply(int storage, const qmg_stencil_desc* d, void* lhs, const void* rhs, unsigned pieces, int n, long vec_stride,
+                            const unsigned char* ridx, hipStream_t st, const SlabHalo* slab) {
+  StencilPlanRequest r = plan_request(d, pieces, n, ridx != nullptr, lhs == rhs, storage == 0 ? 2 : storage == 1 ? 1 : 0, storage != 2, slab);
+  r.site_entry = 1;
+  const StencilPlan pl = stencil_plan(r);
+  if (pl.family != SF_SITE) return pl.status;
+  return launch_stencil_site(pl, d, lhs, rhs, pieces, n, vec_stride, ridx, st, slab);
 }
 
 }  // namespace qmg
@@ -323,7 +316,7 @@ int qmg_convert_from_c16(void* dst, int dst_dtype, const void* src_c16, size_t n
 // lhs (+)= pieces(M) rhs with d->clover / d->hopping stored as complex<half>, vectors complex<float>, fp32 arithmetic.
 // nc = 2 only (QMG_ERR_UNSUPPORTED otherwise); nrhs <= 16 with an active mask, as qmg_stencil_apply_t.
 int qmg_stencil_apply_h16(const qmg_stencil_desc* d, void* lhs, const void* rhs, unsigned pieces, int nrhs, size_t vec_stride, unsigned mask, void* stream) {
-  if (!d || !lhs || !rhs || nrhs < 1 || nrhs > 16) return QMG_ERR_INVALID;
+  if (!d || !lhs || !rhs || !entry_rules::batch_size_ok(nrhs)) return QMG_ERR_INVALID;
   if (!valid_lattice(d->Lx, d->Ly)) return QMG_ERR_INVALID;
   if (d->nc != 2) return QMG_ERR_UNSUPPORTED;
   if (nrhs > 1 && vec_stride < (size_t)d->Lx * d->Ly * 2) return QMG_ERR_INVALID;
@@ -332,7 +325,7 @@ int qmg_stencil_apply_h16(const qmg_stencil_desc* d, void* lhs, const void* rhs,
   for (int k = 0; k < nrhs; k++)
     if ((mask >> k) & 1u) ridx[n++] = (unsigned char)k;
   if (n == 0) return QMG_SUCCESS;
-  return site_kernel_apply(0, d, lhs, rhs, pieces, n, (long)vec_stride, ridx, as_stream(stream), false, nullptr);
+  return site_entry_apply(0, d, lhs, rhs, pieces, n, (long)vec_stride, ridx, as_stream(stream), nullptr);
 }
 
 // One y-slab of a lattice: lhs (+)= pieces(M) rhs on the slab's rows, the right-hand side's rows -1 / Ly taken from
@@ -342,11 +335,8 @@ int qmg_stencil_apply_h16(const qmg_stencil_desc* d, void* lhs, const void* rhs,
 // fp64 or fp32, rows = 0 (QMG_ERR_UNSUPPORTED otherwise).
 int qmg_stencil_apply_slab(int storage, const qmg_stencil_desc* d, void* lhs, const void* rhs, const void* halo_lo, const void* halo_hi,
                            unsigned pieces, int nrhs, size_t vec_stride, size_t halo_stride, unsigned mask, int rows, void* stream) {
-  if (!d || !lhs || !rhs || !halo_lo || !halo_hi || nrhs < 1 || nrhs > 16 || rows < 0 || rows > 2) return QMG_ERR_INVALID;
-  if (lhs == rhs) {   // in place only for the reference's aliased use (stencil_2d.h:1904): ONE parity written, from hops alone
-    const unsigned ev = pieces & (QMG_P_CLOVER_E | QMG_P_EO | QMG_P_SHIFT_E | QMG_P_ZERO_E), od = pieces & (QMG_P_CLOVER_O | QMG_P_OE | QMG_P_SHIFT_O | QMG_P_ZERO_O);
-    if ((ev && od) || (pieces & (QMG_P_CLOVER | QMG_P_SHIFT))) return QMG_ERR_INVALID;
-  }
+  if (!d || !lhs || !rhs || !halo_lo || !halo_hi || !entry_rules::batch_size_ok(nrhs) || rows < 0 || rows > 2) return QMG_ERR_INVALID;
+  if (lhs == rhs && !entry_rules::slab_inplace_ok(pieces)) return QMG_ERR_INVALID;   // in place only for the reference's aliased use (stencil_2d.h:1904)
   if (!valid_lattice(d->Lx, d->Ly)) return QMG_ERR_INVALID;
   const bool h16 = storage & QMG_SLAB_H16, m32 = storage & QMG_SLAB_M32, m16 = storage & QMG_SLAB_M16;
   const int dtype = storage & ~(QMG_SLAB_H16 | QMG_SLAB_M32 | QMG_SLAB_M16);
@@ -360,13 +350,12 @@ int qmg_stencil_apply_slab(int storage, const qmg_stencil_desc* d, void* lhs, co
   SlabHalo slab;
   slab.lo = halo_lo; slab.hi = halo_hi; slab.stride = (long)halo_stride; slab.rows = rows;
   if (d->nc != 2) {   // any other nc: kernels B / B32 / C (all rows in one launch); matrices in the vectors' precision or narrower
-    if (rows != 0) return QMG_ERR_UNSUPPORTED;
     const int vec32 = dtype == QMG_C32 ? 1 : 0;
     const int mat = (h16 || m16) ? 2 : (m32 || vec32) ? 1 : 0;
-    if ((mat == 2 && (d->nc & 3)) || ((mat == 2 || m32) && d->nc <= 4)) return QMG_ERR_UNSUPPORTED;   // (narrow storage: the Galerkin levels, nc > 4)
+    if (!entry_rules::slab_generic_served(mat, mat == 2 || m32, d->nc, rows)) return QMG_ERR_UNSUPPORTED;   // (all rows at once; narrow storage: the Galerkin levels, nc > 4)
     return generic_slab_apply(d, lhs, rhs, pieces, n, (long)vec_stride, ridx, as_stream(stream), &slab, mat, vec32);
   }
-  return site_kernel_apply(h16 ? 0 : (dtype == QMG_C32 ? 1 : 2), d, lhs, rhs, pieces, n, (long)vec_stride, ridx, as_stream(stream), false, &slab);
+  return site_entry_apply(h16 ? 0 : (dtype == QMG_C32 ? 1 : 2), d, lhs, rhs, pieces, n, (long)vec_stride, ridx, as_stream(stream), &slab);
 }
 
 }  // extern "C"

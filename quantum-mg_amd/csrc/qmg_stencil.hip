@@ -392,32 +392,26 @@ int norm_result_slot(double** res) {
   return QMG_SUCCESS;
 }
 
-// kernel A2 on its grid: lane groups over the half row, blocks over groups of ROWS rows (two where Ly is even)
-static int launch_pair_kernel(const StencilArgs& a, int nc, dim3 grid, size_t smem, hipStream_t st, bool norm, bool pf) {
-  return with_int<1, 2, 4>(nc, [&](auto nc_c) {
-    return with_int<1, 2>((int)(a.Ly % 2 == 0 ? 2 : 1), [&](auto rows_c) {
-      return with_bool(norm, [&](auto norm_c) {
-        return with_bool(pf, [&](auto pf_c) {
+// kernel A2, the instantiation and grid of the plan
+static int launch_pair_kernel(const StencilArgs& a, const StencilPlan& pl, hipStream_t st) {
+  const dim3 grid((unsigned)pl.gx, (unsigned)pl.gy);
+  return with_int<1, 2, 4>(pl.NC, [&](auto nc_c) {
+    return with_int<2>(pl.P, [&](auto rows_c) {   // (ROWS = 1 was odd Ly: no lattice has it, valid_lattice)
+      return with_bool((pl.flags & SPF_NORM) != 0, [&](auto norm_c) {
+        return with_bool((pl.flags & SPF_PF) != 0, [&](auto pf_c) {
           constexpr int NC = decltype(nc_c)::value, ROWS = decltype(rows_c)::value;
           constexpr bool NORM = decltype(norm_c)::value, PF = decltype(pf_c)::value;
           if constexpr ((PF && NC != 1) || (NORM && NC == 4)) return (int)QMG_ERR_UNSUPPORTED;   // not built: prefetch is nc = 1's, the norm nc = 1 and 2's
-          else return launch_kernel(k_stencil_pair<double, NC, ROWS, true, true, NORM, PF>, grid, smem, st, a);
+          else return launch_kernel(k_stencil_pair<double, NC, ROWS, true, true, NORM, PF>, grid, (size_t)pl.smem, st, a);
         });
       });
     });
   });
 }
-static dim3 pair_grid(const StencilArgs& a, int nc) {
-  const int E = nc * nc;   // lanes per site (KA<double, NC>::E)
-  const long ngroups = a.Ly / (a.Ly % 2 == 0 ? 2 : 1);
-  return dim3((unsigned)((a.hr + BLOCK / E - 1) / (BLOCK / E)), ngroups > 65535 ? 65535u : (unsigned)ngroups);
-}
 
 // apply + |lhs_k|^2 in one pass: kernel A2 with NORM, then the partials summed in a fixed order
-int launch_stencil_norm(StencilArgs& a, int nc, double* norms_dev, hipStream_t st) {
-  const dim3 grid = pair_grid(a, nc);
-  const long nparts = (long)grid.y * grid.x;            // one partial per block and system
-  const size_t smem = sizeof(double) * BLOCK * (size_t)a.nrhs;
+int launch_stencil_norm(StencilArgs& a, const StencilPlan& pl, double* norms_dev, hipStream_t st) {
+  const long nparts = (long)pl.gy * pl.gx;            // one partial per block and system
   int dev = 0;
   QMG_HIP_CHECK(hipGetDevice(&dev));
   NormWorkspace& ws = g_norm_ws;
@@ -432,27 +426,20 @@ int launch_stencil_norm(StencilArgs& a, int nc, double* norms_dev, hipStream_t s
   a.norm_part = ws.part;
   if (!ws.done) QMG_HIP_CHECK(hipEventCreateWithFlags(&ws.done, hipEventDisableTiming));
   if (ws.used && ws.last != st) QMG_HIP_CHECK(hipStreamWaitEvent(st, ws.done, 0));   // the previous call's partials are still being summed on another stream
-  const bool pf = nc == 1 && a.nrhs > 1 && g_pair_prefetch;   // (nc = 2: the prefetch costs 3 %, tools/apply_norm_ab.py)
-  if (const int rc = launch_pair_kernel(a, nc, grid, smem, st, true, pf)) return rc;
+  if (const int rc = launch_pair_kernel(a, pl, st)) return rc;
   if (const int rc = launch_kernel(k_apply_norm_final, dim3(a.nrhs), 0, st, ws.part, nparts, norms_dev)) return rc;
   QMG_HIP_CHECK(hipEventRecord(ws.done, st));
   ws.last = st; ws.used = true;
   return QMG_SUCCESS;
 }
 
-int launch_stencil_pair(const StencilArgs& a, int nc, hipStream_t st) {
-  // staggered-type batches (nc = 1): the variant that requests system k+1 ahead of system k's arithmetic -- 4096^2, 8 systems:
-  // 1.04 -> 0.90 ms; at nc = 2 it loses 3 % (tools/apply_norm_ab.py), so not there
-  const bool pf = nc == 1 && a.nrhs > 1 && g_pair_prefetch;
-  return launch_pair_kernel(a, nc, pair_grid(a, nc), 0, st, false, pf);
-}
+int launch_stencil_pair(const StencilArgs& a, const StencilPlan& pl, hipStream_t st) { return launch_pair_kernel(a, pl, st); }
 
-int launch_stencil_elem(const StencilArgs& a, int nc, hipStream_t st) {
-  const int E = (a.vec32 && nc % 2 == 0) ? nc * nc / 2 : nc * nc;   // lanes per site (KA<T, NC>::E)
-  const dim3 grid((unsigned)((a.hr + BLOCK / E - 1) / (BLOCK / E)), row_grid(a));
-  return with_int<1, 2, 4>(nc, [&](auto nc_c) {
+int launch_stencil_elem(const StencilArgs& a, const StencilPlan& pl, hipStream_t st) {
+  const dim3 grid((unsigned)pl.gx, (unsigned)pl.gy);
+  return with_int<1, 2, 4>(pl.NC, [&](auto nc_c) {
     constexpr int NC = decltype(nc_c)::value;
-    if (a.vec32) return launch_kernel(k_stencil_elem<float, NC, true, true>, grid, 0, st, a);
+    if (pl.storage & SST_V32) return launch_kernel(k_stencil_elem<float, NC, true, true>, grid, 0, st, a);
     return launch_kernel(k_stencil_elem<double, NC, true, true>, grid, 0, st, a);
   });
 }

@@ -42,46 +42,54 @@ static void fill_systems_and_shifts(StencilArgs& a, const StencilRequest& q) {
   for (int i = 0; i < 2; i++) { a.shift[i] = q.d->shift[i]; a.eo_shift[i] = q.d->eo_shift[i]; a.dof_shift[i] = q.d->dof_shift[i]; }
 }
 
-static int stencil_apply_volume1(const StencilRequest& q) {
+static int stencil_apply_volume1(const StencilRequest& q, const StencilPlan& pl) {
   const qmg_stencil_desc* d = q.d;
-  if (d->nc < 1 || q.nrhs > 16 || (q.nrhs > 1 && q.vec_stride < (size_t)d->nc)) return QMG_ERR_INVALID;
   StencilArgs a;
   memset(&a, 0, sizeof(a));
   fill_systems_and_shifts(a, q);
-  const int zero = (q.pieces & (QMG_P_ZERO_E | QMG_P_ZERO_O)) ? 1 : 0, shift_on = (q.pieces & QMG_P_SHIFT_E) ? 1 : 0;
-  if (!zero && !shift_on) return QMG_SUCCESS;
-  const int n = d->nc * q.nrhs;
-  if (q.vec32) k_stencil_volume1<float><<<(n + 63) / 64, 64, 0, as_stream(q.stream)>>>(q.lhs, q.rhs, d->nc, q.nrhs, (long)q.vec_stride, nullptr, a, zero, shift_on);
-  else k_stencil_volume1<double><<<(n + 63) / 64, 64, 0, as_stream(q.stream)>>>(q.lhs, q.rhs, d->nc, q.nrhs, (long)q.vec_stride, nullptr, a, zero, shift_on);
+  const int zero = (pl.flags & SPF_ZERO) ? 1 : 0, shift_on = (pl.flags & SPF_SHIFT) ? 1 : 0;
+  if (pl.storage & SST_V32) k_stencil_volume1<float><<<pl.gx, 64, 0, as_stream(q.stream)>>>(q.lhs, q.rhs, d->nc, q.nrhs, (long)q.vec_stride, nullptr, a, zero, shift_on);
+  else k_stencil_volume1<double><<<pl.gx, 64, 0, as_stream(q.stream)>>>(q.lhs, q.rhs, d->nc, q.nrhs, (long)q.vec_stride, nullptr, a, zero, shift_on);
   QMG_LAUNCH_CHECK();
   return QMG_SUCCESS;
 }
 
-// The dispatcher: validation, then the kernel families in route order -- the first one that serves the request takes it.
+// what stencil_plan reads of a request, with the knobs as they stand
+StencilPlanRequest qmg::plan_request(const qmg_stencil_desc* d, unsigned pieces, int nrhs, bool holes, bool inplace, int mat, bool vec32, const SlabHalo* slab) {
+  StencilPlanRequest r = {};
+  r.mat = mat; r.vec32 = vec32;
+  r.Lx = d->Lx; r.Ly = d->Ly; r.nc = d->nc;
+  r.pieces = pieces;
+  r.nrhs = nrhs; r.holes = holes; r.inplace = inplace;
+  r.clover = d->clover != nullptr; r.hopping = d->hopping != nullptr;
+  r.slab = slab != nullptr; r.rows = slab ? slab->rows : 0;
+  r.k_site = g_stencil_site; r.k_pair = g_stencil_pair; r.k_mfma = g_stencil_mfma; r.k_prefetch = g_pair_prefetch;
+  return r;
+}
+
+// The dispatcher: the request's own validation, then the plan (qmg_stencil_plan.h: the kernel families in route order -- the first one that serves
+// the request takes it) and the launch function of the plan's family.
 int qmg::stencil_apply(const StencilRequest& q) {
   const qmg_stencil_desc* d = q.d;
   const bool mat32 = q.mat != MatStorage::fp64, mat16 = q.mat == MatStorage::fp16, vec32 = q.vec32;   // (mat32: narrow-stored matrices, either width)
   const SlabHalo* slab = q.slab;
   const int nrhs = q.nrhs;
   if (!d || !q.lhs || !q.rhs || nrhs < 1) return QMG_ERR_INVALID;
-  if (d->Lx == 1 && d->Ly == 1) {
-    if (slab || q.norms_dev || q.epi) return QMG_ERR_UNSUPPORTED;
-    return stencil_apply_volume1(q);
-  }
-  if (!valid_lattice(d->Lx, d->Ly) || d->nc < 1) return QMG_ERR_INVALID;
-  const int nc = d->nc;
-  if (nrhs > 1 && q.vec_stride < (size_t)d->Lx * d->Ly * nc) return QMG_ERR_INVALID;
-
-  if (vec32 && !mat32) return QMG_ERR_UNSUPPORTED;   // fp32 vectors come with fp32 matrices (qmg_stencil_apply_t)
-  // nc = 2 in one storage precision: the site kernel (kernel S, qmg_site.hip)
-  const bool one_precision = !mat16 && mat32 == vec32;
-  if (slab && nc == 2 && !one_precision) return QMG_ERR_UNSUPPORTED;   // slabs at nc = 2: kernel S, matrices and vectors in ONE precision (or its own 16-bit form)
-  if (q.epi && (q.norms_dev || nrhs != 1)) return QMG_ERR_UNSUPPORTED;   // the epilogue is served for ONE system per launch, by kernels B / B32
+  StencilPlanRequest r = plan_request(d, q.pieces, nrhs, q.ridx != nullptr, q.lhs == q.rhs, mat16 ? 2 : mat32 ? 1 : 0, vec32, slab);
+  r.norm = q.norms_dev != nullptr;
+  r.epi = q.epi ? (q.epi->dotv ? 2 : 1) : 0;
+  const StencilPlan pl = stencil_plan(r);
+  if (pl.status == QMG_ERR_INVALID) return QMG_ERR_INVALID;
+  const bool volume1 = d->Lx == 1 && d->Ly == 1;
+  if (volume1 && pl.status) return pl.status;
+  if (nrhs > 1 && q.vec_stride < (volume1 ? (size_t)d->nc : (size_t)d->Lx * d->Ly * d->nc)) return QMG_ERR_INVALID;
+  if (pl.status) return pl.status;
+  if (q.epi && (q.epi->other == q.lhs || q.epi->dotv == q.lhs)) return QMG_ERR_INVALID;
+  if (pl.family == SF_NOTHING) return QMG_SUCCESS;
+  if (pl.family == SF_VOLUME1) return stencil_apply_volume1(q, pl);
   hipStream_t st = as_stream(q.stream);
-  if (nc == 2 && one_precision && nrhs <= 16 && !q.norms_dev && !q.epi && (slab || (vec32 ? (g_stencil_site & 2) : (g_stencil_site & 5)))) {
-    const int rc = site_kernel_apply(vec32 ? 1 : 2, d, q.lhs, q.rhs, q.pieces, nrhs, (long)q.vec_stride, q.ridx, st, !slab && !(g_stencil_site & 4), slab);
-    if (rc != SITE_DECLINED) return rc;
-  }
+  if (pl.family == SF_SITE) return launch_stencil_site(pl, d, q.lhs, q.rhs, q.pieces, nrhs, (long)q.vec_stride, q.ridx, st, slab);
+  const int nc = d->nc;
 
   StencilArgs a;
   a.clover = (const cplx*)d->clover;
@@ -109,51 +117,34 @@ int qmg::stencil_apply(const StencilRequest& q) {
   const unsigned even_bits = QMG_P_CLOVER_E | QMG_P_EO | QMG_P_SHIFT_E | QMG_P_ZERO_E;
   const unsigned odd_bits = QMG_P_CLOVER_O | QMG_P_OE | QMG_P_SHIFT_O | QMG_P_ZERO_O;
   const bool ev = q.pieces & even_bits, od = q.pieces & odd_bits;
-  if (!ev && !od) return QMG_SUCCESS;
   a.par_first = ev ? 0 : 1;
   a.par_count = (ev && od) ? 2 : 1;
   a.nrows = d->Ly * a.par_count;
-  const bool fine = nc == 1 || nc == 2 || nc == 4;   // kernels A / A2
-
-  if (q.norms_dev) {
-    // apply + |lhs_k|^2 in one pass: kernel A2 in fp64, nc = 1 or 2, every site written
-    if (vec32 || mat32 || slab || q.ridx || !(nc == 1 || nc == 2) || a.par_count != 2 || q.lhs == q.rhs || nrhs > 16) return QMG_ERR_UNSUPPORTED;
-    return launch_stencil_norm(a, nc, q.norms_dev, st);
-  }
 
   if (q.epi) {
-    // out = other_scale other + acc_scale acc and the MR dots, in kernels B / B32 (any nc the generic kernels serve); the processed
-    // parities must be overwritten (an accumulate into lhs and an `other` term at once has no single meaning)
-    if (fine) return QMG_ERR_UNSUPPORTED;   // kernels A / S / W: qmg_wilson_*_direct has its own epilogue, the rest falls back
-    if ((ev && !(q.pieces & QMG_P_ZERO_E)) || (od && !(q.pieces & QMG_P_ZERO_O))) return QMG_ERR_INVALID;
-    if (q.lhs == q.rhs || q.epi->other == q.lhs || q.epi->dotv == q.lhs) return QMG_ERR_INVALID;
+    // out = other_scale other + acc_scale acc and the MR dots, in kernels B / B32
     a.epi.on = 1;
     a.epi.other = q.epi->other; a.epi.other_scale = q.epi->other_scale; a.epi.acc_scale = q.epi->acc_scale;
     a.epi.dotv = q.epi->dotv;
-    // partials: one per wavefront of the launch; the launchers of kernels B / B32 fix the grid and ask for them
+    // partials: one per wavefront of the launch; the launchers of kernels B / B32 ask for them
   }
 
-  // fp32: the one-site-per-lane-group kernel is the faster one (4096^2 Wilson: 0.573 ms against 0.592 ms for the paired
-  // kernel, profiles/r02_kernel_rooflines.json: half the bytes per site leave the paired kernel's longer dependent chain
-  // exposed), so the paired kernel serves fp64 only
-  if (fine && a.par_count == 2 && g_stencil_pair && !vec32 && q.lhs != q.rhs && !slab) return launch_stencil_pair(a, nc, st);
-
-  if (fine && !slab) return launch_stencil_elem(a, nc, st);
-
-  // several right-hand sides against one matrix read: kernel C (f64 MFMA) from 4 systems up -- measured 512^2 nc = 24, 8 rhs:
-  // 2.84 ms against 4.84 ms for the vector-FMA kernel B, which tops out near 10 TFLOP/s on LDS traffic; with 2-3 systems
-  // kernel B's shared tile wins (nc = 8, 1024^2, 3 rhs: 1.06 vs 1.39 ms) and it serves every other nc
-  // (nc <= 16: kernel B with one 4-accumulator pass still wins at exactly 4 systems -- nc = 8, 1024^2: 1.21 vs 1.52 ms;
-  //  nc = 16, 512^2: 0.98 vs 1.08 ms -- so there the matrix cores take over from 5)
-  if (nrhs >= (nc <= 16 ? 5 : 4) && g_stencil_mfma && (nc == 8 || nc == 12 || nc == 16 || nc == 24 || nc == 32)) return launch_stencil_mfma(a, nc, !slab, st);
-
-  if (nc > BLOCK) return QMG_ERR_UNSUPPORTED;
-  if (mat32 && !(nc & 1) && !(slab && nc <= 4)) {   // (a slab's fp32 applies at nc = 4 keep kernel B's widening loads)
-    const int rc = launch_stencil_gen32(a, nc, st);
-    if (rc != ROUTE_DECLINED) return rc;
+  switch (pl.family) {
+    case SF_PAIR: return (pl.flags & SPF_NORM) ? launch_stencil_norm(a, pl, q.norms_dev, st) : launch_stencil_pair(a, pl, st);
+    case SF_ELEM: return launch_stencil_elem(a, pl, st);
+    case SF_GEN32: return launch_stencil_gen32(a, nc, pl, st);
+    case SF_GEN: return launch_stencil_gen(a, nc, pl, st);
+    case SF_MFMA:
+      // up to 16 right-hand sides per pass share one read of the matrices; the plan of each further pass from the same request
+      for (int k0 = 0;;) {
+        const StencilPlan pass = k0 ? stencil_plan(r, k0) : pl;
+        if (pass.family != SF_MFMA) return pass.status ? pass.status : QMG_ERR_INVALID;
+        if (const int rc = launch_stencil_mfma(a, pass, k0, st)) return rc;
+        k0 += pass.nk;
+        if (k0 >= nrhs) return QMG_SUCCESS;
+      }
+    default: return QMG_ERR_INVALID;
   }
-  if (mat16) return QMG_ERR_UNSUPPORTED;   // complex<half> matrices are served by kernels B32 / C only (nc a multiple of 4)
-  return launch_stencil_gen(a, nc, st);
 }
 
 // Generic-nc slab apply (csrc/qmg_site.hip holds the C entry qmg_stencil_apply_slab and serves nc = 2 itself): kernels B / B32 / C with the
@@ -168,7 +159,8 @@ int qmg::generic_slab_apply(const qmg_stencil_desc* d, void* lhs, const void* rh
 // A masked batch (only the right-hand sides whose bit is set in `mask` are read or written; at most 16 per call) in q's storage:
 // an empty mask is a success with nothing launched, a full mask runs without an index table (the kernels' direct path).
 static int stencil_apply_masked(StencilRequest q, unsigned mask) {
-  if (q.nrhs < 1 || q.nrhs > 16) return QMG_ERR_INVALID;
+  if (q.d && !entry_rules::narrow_storage_served(q.mat == MatStorage::fp16 ? 2 : q.mat == MatStorage::fp32 ? 1 : 0, q.vec32, q.d->nc)) return QMG_ERR_UNSUPPORTED;
+  if (!entry_rules::batch_size_ok(q.nrhs)) return QMG_ERR_INVALID;
   const BatchIdx b = expand_mask(mask, q.nrhs);
   if (b.n == 0) return QMG_SUCCESS;
   if (b.n < q.nrhs) { q.ridx = b.id; q.nrhs = b.n; }
@@ -193,8 +185,8 @@ extern "C" int qmg_stencil_apply_batch(const qmg_stencil_desc* d, void* lhs, con
 // only precondition (the K-cycle inside a flexible fp64 outer solver); nc = 1, 2, 4 are not served.
 extern "C" int qmg_stencil_apply_mat32(const qmg_stencil_desc* d, void* lhs, const void* rhs, unsigned pieces,
                                        int nrhs, size_t vec_stride, unsigned mask, void* stream) {
-  if (!d || d->nc == 1 || d->nc == 2 || d->nc == 4) return QMG_ERR_UNSUPPORTED;
-  return stencil_apply_masked({d, lhs, rhs, pieces, nrhs, vec_stride, nullptr, stream, MatStorage::fp32}, mask);
+  if (!d) return QMG_ERR_UNSUPPORTED;
+  return stencil_apply_masked({d, lhs, rhs, pieces, nrhs, vec_stride, nullptr, stream, MatStorage::fp32}, mask);   // (nc = 1, 2, 4: refused there)
 }
 
 // Matrices stored as complex<half> (d->clover / d->hopping point to __half2 pairs: qmg_convert_to_c16), vectors complex<double> (QMG_C64) or
@@ -204,13 +196,13 @@ extern "C" int qmg_stencil_apply_mat32(const qmg_stencil_desc* d, void* lhs, con
 extern "C" int qmg_stencil_apply_mat16_t(int vec_dtype, const qmg_stencil_desc* d, void* lhs, const void* rhs, unsigned pieces,
                                          int nrhs, size_t vec_stride, unsigned mask, void* stream) {
   if (vec_dtype != QMG_C64 && vec_dtype != QMG_C32) return QMG_ERR_INVALID;
-  if (!d || (d->nc & 3) || d->nc == 4) return QMG_ERR_UNSUPPORTED;
-  return stencil_apply_masked({d, lhs, rhs, pieces, nrhs, vec_stride, nullptr, stream, MatStorage::fp16, vec_dtype == QMG_C32}, mask);
+  if (!d) return QMG_ERR_UNSUPPORTED;
+  return stencil_apply_masked({d, lhs, rhs, pieces, nrhs, vec_stride, nullptr, stream, MatStorage::fp16, vec_dtype == QMG_C32}, mask);   // (nc: refused there)
 }
 
 // Either storage precision, masked batch semantics.  QMG_C64: qmg_stencil_apply_batch.  QMG_C32: matrices AND vectors are
-// complex<float>; nc in {1,2,4} run kernel A in fp32 arithmetic, every other nc the fp32-tile kernels B32 / B / C with
-// fp32 vector loads and stores around their fp64 accumulation.
+// complex<float>; nc in {1,2,4} run kernel A in fp32 arithmetic, every other nc the fp32-tile kernels B32 / B with
+// fp32 vector loads and stores around their fp64 accumulation, or kernel C on the f32 matrix cores (fp32 accumulators).
 extern "C" int qmg_stencil_apply_t(int dtype, const qmg_stencil_desc* d, void* lhs, const void* rhs, unsigned pieces,
                                    int nrhs, size_t vec_stride, unsigned mask, void* stream) {
   if (dtype == QMG_C64) return qmg_stencil_apply_batch(d, lhs, rhs, pieces, nrhs, vec_stride, mask, stream);
@@ -225,10 +217,9 @@ extern "C" int qmg_stencil_apply_t(int dtype, const qmg_stencil_desc* d, void* l
 extern "C" int qmg_stencil_apply_norm2(const qmg_stencil_desc* d, void* lhs, const void* rhs, unsigned pieces, int nrhs, size_t vec_stride,
                                        double* norms_dev, double* norms_host, void* stream) {
   if (!norms_dev && !norms_host) return QMG_ERR_INVALID;
-  if (nrhs < 1 || nrhs > 16) return QMG_ERR_INVALID;
+  if (!entry_rules::batch_size_ok(nrhs)) return QMG_ERR_INVALID;
   if (dist_reductions_on()) return QMG_ERR_UNSUPPORTED;
-  if (!(pieces & (QMG_P_CLOVER_E | QMG_P_EO | QMG_P_SHIFT_E | QMG_P_ZERO_E)) || !(pieces & (QMG_P_CLOVER_O | QMG_P_OE | QMG_P_SHIFT_O | QMG_P_ZERO_O)))
-    return QMG_ERR_UNSUPPORTED;   // a parity left untouched: its part of |lhs|^2 is not seen by the kernel
+  if (!entry_rules::both_parities(pieces)) return QMG_ERR_UNSUPPORTED;   // a parity left untouched: its part of |lhs|^2 is not seen by the kernel
   double* res = norms_dev;
   if (!res) { if (const int rc = norm_result_slot(&res)) return rc; }
   StencilRequest q = {d, lhs, rhs, pieces, nrhs, vec_stride, nullptr, stream};
@@ -249,11 +240,71 @@ extern "C" int qmg_stencil_apply_norm2(const qmg_stencil_desc* d, void* lhs, con
 extern "C" int qmg_stencil_apply_epi_t(int dtype, int mat32, const qmg_stencil_desc* d, void* lhs, const void* rhs, unsigned pieces, size_t vec_stride, int system,
                                        const qmg_apply_epilogue* epi, void* stream) {
   if (!epi || (dtype != QMG_C64 && dtype != QMG_C32) || system < 0 || system > 15) return QMG_ERR_INVALID;
-  if (dtype == QMG_C32 && !mat32) return QMG_ERR_INVALID;
-  if (mat32 && d && (d->nc == 1 || d->nc == 2 || d->nc == 4)) return QMG_ERR_UNSUPPORTED;
+  if (!entry_rules::epilogue_storage_valid(mat32, dtype == QMG_C32)) return QMG_ERR_INVALID;
+  if (d && !entry_rules::epilogue_storage_served(mat32, d->nc)) return QMG_ERR_UNSUPPORTED;
   unsigned char ridx[16];
   for (int k = 0; k < 16; k++) ridx[k] = (unsigned char)system;
   StencilRequest q = {d, lhs, rhs, pieces, 1, vec_stride, system ? ridx : nullptr, stream, storage_of(mat32), dtype == QMG_C32};
   q.epi = epi;
   return stencil_apply(q);
+}
+
+// Which kernel serves a stencil apply (include/qmg_hip.h): the entry's own checks, then the answer of stencil_plan -- the function the launches
+// above switch on -- for every pass.  Host only: no HIP call.
+extern "C" int qmg_stencil_plan(int entry, int mat, int vec32, int Lx, int Ly, int nc, unsigned pieces, int n_active, int holes, int inplace,
+                                int has_clover, int has_hopping, int epilogue, int slab_rows, int* plan_out, int plan_len) {
+  if (!plan_out || plan_len < STENCIL_PLAN_INTS || entry < QMG_SE_APPLY || entry > QMG_SE_SLAB || mat < 0 || mat > 2 || n_active < 1) return QMG_ERR_INVALID;
+  if ((epilogue != 0) != (entry == QMG_SE_EPI) || epilogue < 0 || epilogue > 2 || (slab_rows != 0 && entry != QMG_SE_SLAB)) return QMG_ERR_INVALID;
+  if (mat == 0 && vec32) return QMG_ERR_INVALID;   // no entry point takes complex<float> vectors with complex<double> matrices
+  using namespace entry_rules;
+  int status = QMG_SUCCESS, site_entry = 0;   // the entry's own refusal, if any
+  SlabHalo halo = {nullptr, nullptr, 0, slab_rows};
+  switch (entry) {
+    case QMG_SE_APPLY:   // qmg_stencil_apply: fp64, no mask, any number of systems
+      if (mat || holes) return QMG_ERR_INVALID;
+      break;
+    case QMG_SE_MASKED:  // qmg_stencil_apply_batch / _t / _mat32 / _mat16_t, by mat and vec32
+      if (!narrow_storage_served(mat, vec32, nc)) status = QMG_ERR_UNSUPPORTED;
+      else if (!batch_size_ok(n_active)) return QMG_ERR_INVALID;
+      break;
+    case QMG_SE_H16:     // qmg_stencil_apply_h16
+      if (mat != 2 || !vec32 || !batch_size_ok(n_active)) return QMG_ERR_INVALID;
+      site_entry = 1;
+      break;
+    case QMG_SE_NORM2:   // qmg_stencil_apply_norm2
+      if (mat || holes || !batch_size_ok(n_active)) return QMG_ERR_INVALID;
+      if (!both_parities(pieces)) status = QMG_ERR_UNSUPPORTED;
+      break;
+    case QMG_SE_EPI:     // qmg_stencil_apply_epi_t: one system (holes: it is not system 0)
+      if (n_active != 1 || !epilogue_storage_valid(mat, vec32)) return QMG_ERR_INVALID;
+      if (!epilogue_storage_served(mat, nc)) status = QMG_ERR_UNSUPPORTED;
+      break;
+    default:             // qmg_stencil_apply_slab
+      if (!batch_size_ok(n_active) || slab_rows < 0 || slab_rows > 2) return QMG_ERR_INVALID;
+      if (inplace && !slab_inplace_ok(pieces)) return QMG_ERR_INVALID;
+      if (!valid_lattice(Lx, Ly)) return QMG_ERR_INVALID;
+      if (nc == 2) {
+        if (mat != 0 && !vec32) return QMG_ERR_INVALID;   // narrow matrices under fp64 vectors are not a storage of kernel S
+        site_entry = 1;
+      } else if (!slab_generic_served(mat, mat == 2 || (mat == 1 && !vec32), nc, slab_rows)) status = QMG_ERR_UNSUPPORTED;
+      break;
+  }
+  for (int i = 0; i < plan_len; i++) plan_out[i] = -1;
+  static const char present = 0;   // a field that is there: stencil_plan reads the pointers' presence only
+  const qmg_stencil_desc d = {Lx, Ly, nc, has_clover ? &present : nullptr, has_hopping ? &present : nullptr, {0, 0}, {0, 0}, {0, 0}};
+  StencilPlanRequest r = plan_request(&d, pieces, n_active, holes != 0, inplace != 0, mat, vec32 != 0, entry == QMG_SE_SLAB ? &halo : nullptr);
+  r.site_entry = site_entry;
+  r.norm = entry == QMG_SE_NORM2;
+  r.epi = epilogue;
+  int at = 0;
+  for (int k0 = 0; k0 < n_active;) {
+    StencilPlan pl = status ? plan_detail::refused(status) : stencil_plan(r, k0);
+    if (at + STENCIL_PLAN_INTS > plan_len) return QMG_ERR_INVALID;
+    const int v[STENCIL_PLAN_INTS] = {pl.family, pl.storage, pl.NC, pl.P, pl.K, pl.flags, pl.S, pl.H, pl.smem, pl.gx, pl.gy, pl.nk};
+    for (int i = 0; i < STENCIL_PLAN_INTS; i++) plan_out[at + i] = v[i];
+    at += STENCIL_PLAN_INTS;
+    if (pl.family != SF_MFMA) break;
+    k0 += pl.nk;
+  }
+  return QMG_SUCCESS;
 }

@@ -10,6 +10,7 @@
 #include <type_traits>
 
 #include "qmg_common.h"
+#include "qmg_stencil_plan.h"
 
 namespace qmg {
 
@@ -183,15 +184,6 @@ __device__ __forceinline__ void st(cplx* p, cplx v) {
   }
 }
 
-// kernels B / B32: the tile of one block (qmg_stencil_gen.hip: make_gen_layout)
-struct GenLayout {
-  int S;        // sites per block
-  int H;        // c-slices per row
-  int rs;       // padded LDS row stride (complex elements)
-  int mat_elems;   // S * nc * nc
-  int per_thread;  // ceil(mat_elems / BLOCK)
-};
-
 // kernel C: a wavefront's write -> read hand-off through its own LDS slice (a wavefront fence, not a block barrier)
 __device__ __forceinline__ void wave_lds_handoff() {
   __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
@@ -219,27 +211,20 @@ struct StencilRequest {
 };
 int stencil_apply(const StencilRequest& q);
 
-constexpr int ROUTE_DECLINED = 1001;   // not an error: the family does not serve this launch, the next one in the route order does
-
-// The launch functions take the filled argument block.  Kernels A / A2 (qmg_stencil.hip):
-int launch_stencil_norm(StencilArgs& a, int nc, double* norms_dev, hipStream_t st);   // apply + |lhs_k|^2, fp64, nc = 1 or 2
-int launch_stencil_pair(const StencilArgs& a, int nc, hipStream_t st);                // fp64, both parities
-int launch_stencil_elem(const StencilArgs& a, int nc, hipStream_t st);
+// The launch functions take the filled argument block and the plan of the launch (qmg_stencil_plan.h: stencil_plan), and switch on the plan alone:
+// instantiation, tile, grid and LDS bytes are the plan's.  Kernels A / A2 (qmg_stencil.hip):
+int launch_stencil_norm(StencilArgs& a, const StencilPlan& pl, double* norms_dev, hipStream_t st);   // apply + |lhs_k|^2, fp64, nc = 1 or 2
+int launch_stencil_pair(const StencilArgs& a, const StencilPlan& pl, hipStream_t st);                // fp64, both parities
+int launch_stencil_elem(const StencilArgs& a, const StencilPlan& pl, hipStream_t st);
 int norm_result_slot(double** res);   // the calling thread's default device slot for 16 norms
-// kernel C (qmg_stencil_mfma.hip); whole_lattice: no slab halos
-int launch_stencil_mfma(const StencilArgs& a, int nc, bool whole_lattice, hipStream_t st);
-// kernels B32 (qmg_stencil_gen32.hip) and B (qmg_stencil_gen.hip); B32 answers ROUTE_DECLINED where its tile does not fit and kernel B takes the launch
-int launch_stencil_gen32(StencilArgs& a, int nc, hipStream_t st);
-int launch_stencil_gen(StencilArgs& a, int nc, hipStream_t st);
-// ... and what the two share (qmg_stencil_gen.hip): the tile, the right-hand sides per pass, the epilogue's partials around the launch
-constexpr int GEN_MAX_PER_THREAD = 12;   // register-staged matrix elements per thread per piece
-GenLayout make_gen_layout(int nc, int hr, bool mat32, int site_cap = 0);
-int gen_pass_width(int nrhs);
-int gen_epilogue_begin(StencilArgs& a, dim3& grid, long& npart);   // caps grid.y, asks for the partial buffer
+// kernel C (qmg_stencil_mfma.hip): the pass of the plan, a's vectors being those of the call
+int launch_stencil_mfma(const StencilArgs& a, const StencilPlan& pl, int k0, hipStream_t st);
+// kernels B32 (qmg_stencil_gen32.hip) and B (qmg_stencil_gen.hip)
+int launch_stencil_gen32(StencilArgs& a, int nc, const StencilPlan& pl, hipStream_t st);
+int launch_stencil_gen(StencilArgs& a, int nc, const StencilPlan& pl, hipStream_t st);
+// ... and what the two share (qmg_stencil_gen.hip): the epilogue's partials around the launch
+int gen_epilogue_begin(StencilArgs& a, const StencilPlan& pl, long& npart);   // asks for the partial buffer
 int gen_epilogue_finish(const StencilArgs& a, long npart, hipStream_t st);
-
-inline unsigned row_grid(const StencilArgs& a) { return a.nrows > 65535 ? 65535u : (unsigned)a.nrows; }   // grid.y: blocks walk the rows beyond it
-
 // Launch with dynamic LDS: above 64 KiB the kernel's limit is raised first.
 template <typename... KArgs, typename... Args>
 inline int launch_kernel(void (*kernel)(KArgs...), dim3 grid, size_t smem, hipStream_t st, const Args&... args) {
@@ -257,12 +242,13 @@ template <int... Vs, typename F> inline int with_int(int v, F&& f) {   // QMG_ER
   return rc;
 }
 // the storage forms the kernels are built for, as (M32, V32, M16): fp64; complex<float> or complex<half> matrices with either vectors
-template <typename F> inline int with_storage(const StencilArgs& a, F&& f) {
+template <typename F> inline int with_storage(const StencilPlan& pl, F&& f) {
   typedef std::true_type Y;
   typedef std::false_type N;
-  if (a.mat16) return a.vec32 ? f(Y(), Y(), Y()) : f(Y(), N(), Y());
-  if (a.vec32) return f(Y(), Y(), N());
-  if (a.mat32) return f(Y(), N(), N());
+  const bool v32 = pl.storage & SST_V32;
+  if (pl.storage & SST_M16) return v32 ? f(Y(), Y(), Y()) : f(Y(), N(), Y());
+  if (v32) return f(Y(), Y(), N());
+  if (pl.storage & SST_M32) return f(Y(), N(), N());
   return f(N(), N(), N());
 }
 

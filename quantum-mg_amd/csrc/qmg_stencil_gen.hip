@@ -213,35 +213,11 @@ __global__ __launch_bounds__(BLOCK) void k_stencil_gen(const StencilArgs a, cons
   if (EPI && a.epi.dotv) epilogue_store_partials(a.epi, edots);
 }
 
-GenLayout make_gen_layout(int nc, int hr, bool mat32, int site_cap) {
-  GenLayout L;
-  const int nc2 = nc * nc;
-  int S = (BLOCK * GEN_MAX_PER_THREAD) / nc2;       // registers: S*nc^2 <= 256*12
-  if (S > BLOCK / nc) S = BLOCK / nc;               // one (s,r) row per thread at least
-  if (S > hr) S = hr;
-  // fp32-stored matrices: the kernel is bound by bytes in flight per CU (one piece per resident block), not by HBM; with
-  // half the bytes per piece, smaller tiles (more resident blocks) pay: 512^2, nc = 24: S = 5 1.81 ms, S = 2 1.59 ms
-  if (mat32 && nc >= 16 && S > 2) S = 2;
-  if (site_cap > 0 && S > site_cap) S = site_cap;
-  if (S < 1) S = 1;
-  L.S = S;
-  int H = BLOCK / (S * nc);
-  if (H < 1) H = 1;
-  if (H > nc) H = nc;
-  L.H = H;
-  L.rs = nc + ((nc % 2 == 0) ? 1 : 0);
-  L.mat_elems = S * nc2;
-  L.per_thread = (L.mat_elems + BLOCK - 1) / BLOCK;
-  return L;
-}
-
 // the epilogue's dot partials: one slot per wavefront of the launch (system slot 0), summed by mr_epilogue_finish into the thread's MR slot
-int gen_epilogue_begin(StencilArgs& a, dim3& grid, long& npart) {
+int gen_epilogue_begin(StencilArgs& a, const StencilPlan& pl, long& npart) {
   npart = 0;
-  if (a.epi.on && a.epi.dotv) {
-    const unsigned cap = grid.x >= 2048u ? 1u : 2048u / grid.x;   // a few thousand partials for the one-block second stage: blocks walk rows
-    if (grid.y > cap) grid.y = cap;
-    npart = (long)grid.x * (long)grid.y * (BLOCK / WAVE);
+  if (pl.flags & SPF_DOTS) {
+    npart = (long)pl.gx * (long)pl.gy * (BLOCK / WAVE);
     a.epi.part = mr_epilogue_begin(1, npart);
     a.epi.npart = npart;
     if (!a.epi.part) return QMG_ERR_HIP;
@@ -254,33 +230,23 @@ int gen_epilogue_finish(const StencilArgs& a, long npart, hipStream_t st) {
   return mr_epilogue_finish(&id0, 1, npart, st);
 }
 
-// right-hand sides per pass: 8 accumulators from 5 systems, 4 for 2-4 systems, else 1
-int gen_pass_width(int nrhs) { return (nrhs >= 5) ? 8 : (nrhs >= 2) ? 4 : 1; }
-
 // kernel B: fp64 tile, matrices stored as complex<double> or complex<float>
-int launch_stencil_gen(StencilArgs& a, int nc, hipStream_t st) {
-  GenLayout L = make_gen_layout(nc, a.hr, a.mat32);
-  if (L.per_thread > GEN_MAX_PER_THREAD) return QMG_ERR_UNSUPPORTED;   // nc > 55: S = 1 still too large
-  // right-hand sides per pass of kernel B: 4 (2-4 systems) or 8 accumulators; if the tile plus the vectors of the pass do
-  // not fit 64 KB of LDS (>= 2 blocks per CU) the tile shrinks first (nc = 16: 12 -> 6 sites), the pass second
-  int kr = gen_pass_width(a.nrhs);
-  auto smem_of = [&](const GenLayout& l, int k) { return sizeof(cplx) * ((size_t)l.S * nc * l.rs + (size_t)k * l.S * nc + (size_t)l.H * l.S * nc); };
-  while (kr > 1 && smem_of(L, kr) > 64 * 1024 && L.S > 1) L = make_gen_layout(nc, a.hr, a.mat32, (L.S + 1) / 2);
-  while (kr > 1 && smem_of(L, kr) > 64 * 1024) kr = (kr == 8) ? 4 : 1;
-  const size_t smem = smem_of(L, kr);
-  if (smem > 160 * 1024) return QMG_ERR_UNSUPPORTED;
-  dim3 grid((unsigned)((a.hr + L.S - 1) / L.S), row_grid(a));
+int launch_stencil_gen(StencilArgs& a, int nc, const StencilPlan& pl, hipStream_t st) {
+  const GenLayout L = pl.L;
+  const int kr = pl.K;
+  const size_t smem = (size_t)pl.smem;
+  const dim3 grid((unsigned)pl.gx, (unsigned)pl.gy);
   long npart;
-  if (const int rc = gen_epilogue_begin(a, grid, npart)) return rc;
-  const int rc = with_int<1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12>(L.per_thread, [&](auto pt_c) {
-    return with_storage(a, [&](auto m32, auto v32, auto m16) {
+  if (const int rc = gen_epilogue_begin(a, pl, npart)) return rc;
+  const int rc = with_int<1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12>(pl.P, [&](auto pt_c) {
+    return with_storage(pl, [&](auto m32, auto v32, auto m16) {
       constexpr int PT = decltype(pt_c)::value;
       constexpr bool M32 = decltype(m32)::value, V32 = decltype(v32)::value;
       if constexpr (decltype(m16)::value) return (int)QMG_ERR_UNSUPPORTED;   // not built: complex<half> matrices are kernel B32's and C's
       else {
         if (kr == 8) return launch_kernel(k_stencil_gen<PT, M32, 8, V32>, grid, smem, st, a, nc, L);
         if (kr == 4) return launch_kernel(k_stencil_gen<PT, M32, 4, V32>, grid, smem, st, a, nc, L);
-        if (a.epi.on) return launch_kernel(k_stencil_gen<PT, M32, 1, V32, true>, grid, smem, st, a, nc, L);
+        if (pl.flags & SPF_EPI) return launch_kernel(k_stencil_gen<PT, M32, 1, V32, true>, grid, smem, st, a, nc, L);
         return launch_kernel(k_stencil_gen<PT, M32, 1, V32>, grid, smem, st, a, nc, L);
       }
     });

@@ -213,28 +213,22 @@ __global__ __launch_bounds__(BLOCK) void k_stencil_gen32(const StencilArgs a, co
 }
 
 // kernel B32: fp32 tile end to end (even nc); complex<half> matrices at nc a multiple of 4
-int launch_stencil_gen32(StencilArgs& a, int nc, hipStream_t st) {
-  const GenLayout L = make_gen_layout(nc, a.hr, false);
-  if (a.mat16 && (nc & 3)) return QMG_ERR_UNSUPPORTED;
-  const int pp = a.mat16 ? (L.mat_elems / 4 + BLOCK - 1) / BLOCK : (L.mat_elems / 2 + BLOCK - 1) / BLOCK;
-  if (pp < 1 || pp > (a.mat16 ? 3 : 6)) return ROUTE_DECLINED;
-  int kr = gen_pass_width(a.nrhs);
-  auto smem_of = [&](int k) { return (((size_t)L.S * nc * (nc + 2) * 8 + 15) & ~(size_t)15) + sizeof(cplx) * ((size_t)k * L.S * nc + (size_t)L.H * L.S * nc); };
-  while (kr > 1 && smem_of(kr) > 48 * 1024) kr = (kr == 8) ? 4 : 1;
-  const size_t smem = smem_of(kr);
-  if (smem > 64 * 1024) return ROUTE_DECLINED;
-  dim3 grid((unsigned)((a.hr + L.S - 1) / L.S), row_grid(a));
+int launch_stencil_gen32(StencilArgs& a, int nc, const StencilPlan& pl, hipStream_t st) {
+  const GenLayout L = pl.L;
+  const int kr = pl.K;
+  const size_t smem = (size_t)pl.smem;
+  const dim3 grid((unsigned)pl.gx, (unsigned)pl.gy);
   long npart;
-  if (const int rc = gen_epilogue_begin(a, grid, npart)) return rc;
-  const int rc = with_int<1, 2, 3, 4, 5, 6>(pp, [&](auto pp_c) {
-    return with_storage(a, [&](auto m32, auto v32, auto m16) {
+  if (const int rc = gen_epilogue_begin(a, pl, npart)) return rc;
+  const int rc = with_int<1, 2, 3, 4, 5, 6>(pl.P, [&](auto pp_c) {
+    return with_storage(pl, [&](auto m32, auto v32, auto m16) {
       constexpr int PP = decltype(pp_c)::value;
       constexpr bool V32 = decltype(v32)::value, M16 = decltype(m16)::value;
       if constexpr (!decltype(m32)::value || (M16 && PP > 3)) return (int)QMG_ERR_UNSUPPORTED;   // not built: fp64 matrices are kernel B's, quads stop at 3
       else {
         if (kr == 8) return launch_kernel(k_stencil_gen32<PP, 8, V32, false, M16>, grid, smem, st, a, nc, L);
         if (kr == 4) return launch_kernel(k_stencil_gen32<PP, 4, V32, false, M16>, grid, smem, st, a, nc, L);
-        if (a.epi.on) return launch_kernel(k_stencil_gen32<PP, 1, V32, true, M16>, grid, smem, st, a, nc, L);
+        if (pl.flags & SPF_EPI) return launch_kernel(k_stencil_gen32<PP, 1, V32, true, M16>, grid, smem, st, a, nc, L);
         return launch_kernel(k_stencil_gen32<PP, 1, V32, false, M16>, grid, smem, st, a, nc, L);
       }
     });

@@ -463,46 +463,30 @@ __global__ __launch_bounds__(BLOCK, (MODE == 1 && NC <= 24) ? 3 : 1) void k_sten
 
 int g_stencil_mfma = 1;   // tuning knob: 1 = multi-rhs applies with nc in {8,12,16,24,32} run on the f64 matrix cores (kernel C); 2 = same, plain 4-MFMA products; 0 = off
 
-// kernel C: up to 16 right-hand sides per pass share one read of the matrices
-int launch_stencil_mfma(const StencilArgs& a, int nc, bool whole_lattice, hipStream_t st) {
-  constexpr size_t WAVES = BLOCK / WAVE;
-  const dim3 grid((unsigned)((a.hr + WAVES - 1) / WAVES), row_grid(a));
-  for (int k0 = 0; k0 < a.nrhs; k0 += 16) {
-    StencilArgs b = a;
-    b.lhs = (char*)a.lhs + (size_t)k0 * a.vec_stride * (a.vec32 ? 8 : 16);
-    b.rhs = (const char*)a.rhs + (size_t)k0 * a.vec_stride * (a.vec32 ? 8 : 16);
-    const int nk = (a.nrhs - k0 < 16) ? a.nrhs - k0 : 16;
-    int mode = (g_stencil_mfma == 2 || nk > 8) ? 0 : 1;
-    // 9-16 systems in fp64: the real-form tiles where they save MFMAs (nc = 24: 36 instead of 48 per piece; nc = 8: 4 instead of 8)
-    if (mode == 0 && g_stencil_mfma == 1 && !a.mat32 && !a.vec32 && (nc == 24 || nc == 8)) mode = 2;
-    // LDS per wavefront: the matrix tile of T colours (raw complex<float> rows of T + 2, or complex<double> rows of T + 1) and,
-    // where the right-hand sides go through LDS (VL), a slice of 8 (MODE 1) or 16 vectors
-    auto smem_of = [&](int T, bool vl) {
-      return (a.mat32 ? sizeof(float2) * WAVES * T * (T + 2) : sizeof(cplx) * WAVES * T * (T + 1)) + (vl ? sizeof(cplx) * WAVES * (mode == 1 ? 8 : 16) * (T + 1) : 0);
-    };
-    int rc;
-    if (nc == 8 && mode == 1 && whole_lattice && (a.hr % 2 == 0)) {
-      // nc = 8, up to 8 systems, whole lattice: two sites per wavefront (PAIR)
-      const dim3 gridp((unsigned)((a.hr / 2 + WAVES - 1) / WAVES), grid.y);
-      rc = with_storage(b, [&](auto m32, auto v32, auto m16) {
-        return launch_kernel(k_stencil_mfma<16, 1, decltype(m32)::value, decltype(v32)::value, true, decltype(m16)::value, true>, gridp, smem_of(16, true), st, b, nk);
-      });
-    } else {
-      const bool vl = !(mode == 0 && a.mat32);   // (fp32- and 16-bit-stored matrices with plain products: B operands straight from global memory)
-      rc = with_int<8, 12, 16, 24, 32>(nc, [&](auto nc_c) {
-        return with_int<0, 1, 2>(mode, [&](auto mode_c) {
-          return with_storage(b, [&](auto m32, auto v32, auto m16) {
-            constexpr int NC = decltype(nc_c)::value, MODE = decltype(mode_c)::value;
-            constexpr bool M32 = decltype(m32)::value;
-            if constexpr (MODE == 2 && M32) return (int)QMG_ERR_UNSUPPORTED;   // not built: the real form is fp64 only (mode is 2 for fp64 storage only)
-            else return launch_kernel(k_stencil_mfma<NC, MODE, M32, decltype(v32)::value, !(MODE == 0 && M32), decltype(m16)::value>, grid, smem_of(nc, vl), st, b, nk);
-          });
-        });
-      });
-    }
-    if (rc) return rc;
+// kernel C: one pass of up to 16 right-hand sides, from system k0 of the call on, sharing one read of the matrices
+int launch_stencil_mfma(const StencilArgs& a, const StencilPlan& pl, int k0, hipStream_t st) {
+  const dim3 grid((unsigned)pl.gx, (unsigned)pl.gy);
+  const size_t smem = (size_t)pl.smem;
+  const int nk = pl.K;
+  StencilArgs b = a;
+  b.lhs = (char*)a.lhs + (size_t)k0 * a.vec_stride * (a.vec32 ? 8 : 16);
+  b.rhs = (const char*)a.rhs + (size_t)k0 * a.vec_stride * (a.vec32 ? 8 : 16);
+  if (pl.flags & SPF_PAIR) {
+    // nc = 8, up to 8 systems, whole lattice: two sites per wavefront (PAIR)
+    return with_storage(pl, [&](auto m32, auto v32, auto m16) {
+      return launch_kernel(k_stencil_mfma<16, 1, decltype(m32)::value, decltype(v32)::value, true, decltype(m16)::value, true>, grid, smem, st, b, nk);
+    });
   }
-  return QMG_SUCCESS;
+  return with_int<8, 12, 16, 24, 32>(pl.NC, [&](auto nc_c) {
+    return with_int<0, 1, 2>(pl.P, [&](auto mode_c) {
+      return with_storage(pl, [&](auto m32, auto v32, auto m16) {
+        constexpr int NC = decltype(nc_c)::value, MODE = decltype(mode_c)::value;
+        constexpr bool M32 = decltype(m32)::value;
+        if constexpr (MODE == 2 && M32) return (int)QMG_ERR_UNSUPPORTED;   // not built: the real form is fp64 only (mode is 2 for fp64 storage only)
+        else return launch_kernel(k_stencil_mfma<NC, MODE, M32, decltype(v32)::value, !(MODE == 0 && M32), decltype(m16)::value>, grid, smem, st, b, nk);
+      });
+    });
+  });
 }
 
 }  // namespace qmg

@@ -110,7 +110,12 @@ def test_batch_multidot_and_multi_caxpy(nj):
 @pytest.mark.parametrize("nc,nrhs,mask", [(2, 4, 0b1011), (1, 3, 0b101), (8, 6, 0b110101), (24, 16, 0xFFFF), (24, 12, 0b101010111011), (3, 4, 0b0110), (16, 2, 0b10),
                                           (8, 16, 0xFFFF), (8, 11, 0x7FF), (24, 9, 0x1FF), (12, 16, 0xFFFF), (32, 10, 0x3FF)])
 def test_stencil_apply_batch_masked(nc, nrhs, mask):
+    """Masked fp64 batches against the oracle per active system: kernel A2 / A (nc = 1, 2: batches are declined by kernel S), kernel B below the
+    hand-over ((8, 6) has 4 active systems, (3, 4) and (16, 2) fewer), kernel C from 5 active systems (4 at nc >= 24), nc = 32 included."""
     Lx, Ly = 12, 6
+    n_active = len(active(mask, nrhs))
+    family = {(2, 4): qmg.SF_PAIR, (1, 3): qmg.SF_PAIR, (8, 6): qmg.SF_GEN, (3, 4): qmg.SF_GEN, (16, 2): qmg.SF_GEN}.get((nc, nrhs), qmg.SF_MFMA)   # the row's kernel
+    assert qmg.stencil_plan(qmg.SE_MASKED, 0, 0, (Lx, Ly, nc), ol.P_ALL, n_active, n_active < nrhs)[0][0] == family
     vol = Lx * Ly
     size = vol * nc
     stride = size + 4
@@ -180,7 +185,8 @@ def test_transfer_batch_matches_single(fd, cd, nrhs, mask):
 def test_stencil_apply_with_f32_stored_matrices(nc, nrhs, mask):
     """qmg_stencil_apply_mat32 (opt-in storage format): the matrices are read as complex<float>, everything else is fp64.
     Parity is exact in the sense that matters: equal (1e-13) to the ORACLE's fp64 apply of the matrices rounded to
-    float -- kernels B (one rhs, or nc outside the MFMA set) and C (several rhs, f64 MFMA)."""
+    float -- kernels B32 (even nc: one rhs, (8, 6) with its 4 active systems, (12, 3), (32, 2), (6, 4)), B (nc = 3) and C ((24, 16): f64 MFMA);
+    which instantiation a request reaches: test_gpu_stencil_routes.py."""
     Lx, Ly = 12, 6
     vol = Lx * Ly
     size = vol * nc

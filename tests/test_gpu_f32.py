@@ -58,8 +58,10 @@ PIECE_SETS = [
 @pytest.mark.parametrize("Lx,Ly,nc", [(32, 32, 2), (6, 4, 2), (34, 10, 1), (16, 12, 4), (12, 8, 3), (16, 6, 8), (8, 8, 24)])
 def test_every_piece_mask_every_kernel_f32(name, pieces, Lx, Ly, nc):
     """The piece-mask matrix of test_gpu_parity.py::test_every_piece_mask_every_kernel in fp32: kernel A in fp32 arithmetic
-    (nc 1, 2, 4), kernels B / B32 with fp32 tiles and fp32 vectors (nc 3, 8, 24); accumulate vs overwrite, untouched
-    halves, ragged tiles, all three shifts."""
+    (nc 1, 4), kernel S in complex<float> (every nc = 2 apply at the default stencil_site), kernel B (nc 3) and B32 (nc 8, 24) with fp32
+    matrices and vectors around fp64 accumulation; accumulate vs overwrite, untouched halves, ragged tiles, all three shifts."""
+    if nc == 2:
+        assert qmg.stencil_plan(qmg.SE_MASKED, 1, 1, (Lx, Ly, nc), pieces, 1)[0][0] in (qmg.SF_SITE, qmg.SF_NOTHING)
     vol = Lx * Ly
     clover, hopping = r32(cs.gaussian_cvec(vol * nc * nc, 1)), r32(cs.gaussian_cvec(4 * vol * nc * nc, 2))
     rhs, lhs0 = r32(cs.gaussian_cvec(vol * nc, 3)), r32(cs.gaussian_cvec(vol * nc, 4))
@@ -76,8 +78,12 @@ def test_every_piece_mask_every_kernel_f32(name, pieces, Lx, Ly, nc):
 
 @pytest.mark.parametrize("nc,nrhs,mask", [(2, 3, 0b101), (1, 8, 0xFF), (8, 3, 0b110), (8, 7, 0x7F), (12, 6, 0b111011), (24, 5, 0b11111), (24, 16, 0xFFFF), (16, 9, 0x1FF), (7, 4, 0b1011)])
 def test_stencil_apply_f32_batches(nc, nrhs, mask):
-    """Masked lock-step batches in fp32: kernel A's rhs loop, kernel B32 with 4 / 8 accumulators, kernel C (f64 MFMA over
-    fp32 tiles and fp32 vectors, both the 2-MFMA and the 4-MFMA product).  Frozen systems are not written."""
+    """Masked lock-step batches in fp32: kernel S's (nc = 2) and kernel A's (nc = 1) rhs loop, kernels B32 (nc = 8, two systems) and B
+    (nc = 7) with 4 accumulators, kernel C from 5 systems (4 at nc = 24) on the f32 matrix cores (v_mfma_f32_16x16x4_f32 over fp32 tiles
+    and fp32 vectors, both the 2-MFMA and the 4-MFMA product).  Frozen systems are not written."""
+    n_active = bin(mask).count("1")
+    family = {(2, 3): qmg.SF_SITE, (1, 8): qmg.SF_ELEM, (8, 3): qmg.SF_GEN32, (7, 4): qmg.SF_GEN}.get((nc, nrhs), qmg.SF_MFMA)   # the row's kernel
+    assert qmg.stencil_plan(qmg.SE_MASKED, 1, 1, (16, 12, nc), ol.P_ALL | ol.P_ZERO, n_active, n_active < nrhs)[0][0] == family
     Lx, Ly = 16, 12
     vol = Lx * Ly
     size, stride = vol * nc, vol * nc + 6

@@ -169,8 +169,10 @@ PIECE_SETS = [
 @pytest.mark.parametrize("name,pieces", PIECE_SETS)
 @pytest.mark.parametrize("Lx,Ly,nc", [(32, 32, 2), (6, 4, 2), (34, 10, 1), (16, 12, 4), (12, 8, 3), (16, 6, 8), (8, 8, 24)])
 def test_every_piece_mask_every_kernel(name, pieces, Lx, Ly, nc):
-    """Random dense stencils: exercises kernel A (nc 1,2,4) and kernel B (nc 3,8,24), accumulate
-    vs overwrite, untouched halves, ragged tiles, all three shifts."""
+    """Random dense stencils through qmg_stencil_apply, one system: nc 1, 2, 4 as the dispatcher routes them at the default knobs (kernel A2
+    where both parities are written, kernel A for one parity, kernel S for nc = 2 with exactly the four hops of the processed parities) and
+    kernel B (nc 3, 8, 24); accumulate vs overwrite, untouched halves, ragged tiles, all three shifts.  Which kernel a request reaches is
+    asserted, kernel by kernel, in test_gpu_stencil_routes.py."""
     vol = Lx * Ly
     clover = cs.gaussian_cvec(vol * nc * nc, 1)
     hopping = cs.gaussian_cvec(4 * vol * nc * nc, 2)
@@ -281,8 +283,13 @@ def test_multi_rhs_shares_matrices(nc):
 @pytest.mark.parametrize("nc,nrhs", [(8, 2), (8, 16), (12, 5), (16, 16), (24, 8), (24, 19), (32, 3)])
 def test_multi_rhs_coarse_apply_on_matrix_cores(nc, nrhs):
     """Kernel C (v_mfma_f64_16x16x4_f64): every piece subset the facade launches, all three shifts, overwrite and
-    accumulate, ragged rhs counts (19 = one full pass of 16 + 3), against the oracle applied per right-hand side."""
+    accumulate, ragged rhs counts (19 = one full pass of 16 + 3), against the oracle applied per right-hand side.  The matrix cores take
+    over from 5 systems (nc <= 16) or 4: the rows (8, 2) and (32, 3) stay below that and hold kernel B's 4-accumulator pass to the same
+    checks; the plan assertion below says which kernel a row runs (nc = 32 on kernel C: test_gpu_stencil_routes.py)."""
     Lx, Ly = 12, 6
+    family = qmg.SF_GEN if (nc, nrhs) in ((8, 2), (32, 3)) else qmg.SF_MFMA   # the row's kernel
+    for pieces in (ol.P_ALL | ol.P_ZERO, ol.P_EO | ol.P_ZERO_E):
+        assert {p[0] for p in qmg.stencil_plan(qmg.SE_APPLY, 0, 0, (Lx, Ly, nc), pieces, nrhs)} == {family}
     vol = Lx * Ly
     clover = cs.gaussian_cvec(vol * nc * nc, 1)
     hopping = cs.gaussian_cvec(4 * vol * nc * nc, 2)
