@@ -555,6 +555,39 @@ int qmg_wilson_hops_direct(int dtype, const qmg_stencil_desc* d, const void* gau
                            const void* rhs, const void* halo_lo, const void* halo_hi, unsigned pieces, int nrhs, size_t vec_stride, size_t halo_stride,
                            unsigned mask, int rows, void* stream);
 
+/* ---------------- the Shamir domain-wall operator (operators/dwf.h; csrc/qmg_dwf.hip) ----------------
+ * nc = 2 Ls components per site, c = 2 s + sigma (s the fifth-dimension slice, sigma the spin); Ls = 2 .. 32.  D = clover + hopping + shift:
+ *   clover   3w on the diagonal;  out(s+1, 0) -= psi(s, 0) and out(s, 1) -= psi(s+1, 1) for s = 0 .. Ls-2;
+ *            out(0, 0) += m psi(Ls-1, 0) and out(Ls-1, 1) += m psi(0, 1)   (m = mass_re + i mass_im, the wall mass)
+ *   hopping  diagonal in s, the 2 x 2 spin blocks of qmg_wilson_fill on every slice
+ *   shift    the domain-wall height M5 goes into the stencil's identity shift (the reference's default is -1)
+ * qmg_dwf_fill writes the stored form -- the full nc x nc clover and hopping fields, zeros included -- that the dagger, right-block-Jacobi and
+ * Galerkin builds read; fp64, on the device. */
+int qmg_dwf_fill(void* clover, void* hopping, const void* gauge, int Lx, int Ly, int Ls, double mass_re, double mass_im, double wilson_coeff, void* stream);
+/* lhs (+)= pieces(D) rhs without stored matrices (kernels D / D2): 64 Ls + 32 B/site in fp64 (32 Ls + 16 in fp32) instead of the stored stencil's
+ * 5 (2 Ls)^2 complex numbers per site.  d: Lx, Ly, nc (= 2 Ls) and the three shifts with the stencil's semantics (its matrix pointers are
+ * ignored); gauge: the links in `dtype`; whole lattice only.  Piece sets served: those of qmg_wilson_apply_direct -- clover + every hop of the
+ * processed parities (shift pieces and QMG_P_ZERO optional), or every hop alone, where lhs == rhs is allowed for one parity;
+ * QMG_ERR_UNSUPPORTED otherwise (the stored stencil serves the rest).  QMG_ERR_INVALID, before anything is launched: a dtype other than
+ * QMG_C64 / QMG_C32, Ls outside 2 .. 32, d->nc != 2 Ls, nrhs outside 1 .. 16, a vec_stride shorter than a vector, pointers that are not
+ * 16-byte aligned.  mask as in qmg_stencil_apply_batch. */
+int qmg_dwf_apply_direct(int dtype, const qmg_stencil_desc* d, const void* gauge, int Ls, double mass_re, double mass_im, double wilson_coeff,
+                         void* lhs, const void* rhs, unsigned pieces, int nrhs, size_t vec_stride, unsigned mask, void* stream);
+/* What qmg_dwf_apply_direct does with a request: the answer of the one host function its launch switches on.  Host only, no HIP call.
+ * n_active: the systems whose mask bit is set (0 .. 16); inplace: lhs == rhs.  Writes 8 ints and -1 into the rest of plan_out:
+ *   family  0 unsupported (the call returns QMG_ERR_UNSUPPORTED), 1 k_dwf_direct (kernel D), 2 success with nothing launched, 3 invalid
+ *           (the call returns QMG_ERR_INVALID), 4 k_dwf_pair (kernel D2: the full operator -- shape 1 on both parities --, both parities of a
+ *           column per lane)
+ *   lps     lanes per site: Ls, a lane owns one (site, s) pair with its two spin components
+ *   block   threads per block
+ *   gx, gy  the grid: gx blocks cover the lps * Lx/2 lanes of a half row, gy = min(rows, 65535) blocks walk the rows: (parity, y) of the
+ *           processed parities for kernel D, y for kernel D2
+ *   flags   1 ZERO (every processed parity is overwritten) | 2 BATCH (more than one system) | 4 complex<float>
+ *   shape   1 clover + hops (+ shift), 2 hops alone
+ *   nk      the systems served
+ * (a member the family does not use is 0).  QMG_ERR_INVALID: plan_out missing or plan_len below 8. */
+int qmg_dwf_plan(int dtype, int Lx, int Ly, int Ls, unsigned pieces, int n_active, int inplace, int* plan_out, int plan_len);
+
 /* ---------------- tuning hooks (not part of the reference surface) ---------------- */
 /* Dispatch / codegen knobs, all with the defaults the measurements in profiles/ chose; results never depend on them
  * beyond summation order.  Unknown keys, and values a key does not take, return QMG_ERR_INVALID.

@@ -54,6 +54,7 @@ ABI_SYMBOLS = [
     "qmg_u1_hot_gauge", "qmg_u1_gauss_gauge", "qmg_u1_random_trans", "qmg_u1_gauge_transform", "qmg_u1_ape_smear", "qmg_u1_instanton", "qmg_u1_noncompact_instanton",
     "qmg_hmc_momentum_update", "qmg_hmc_momentum_update_poles", "qmg_hmc_momentum_update_staggered", "qmg_hmc_link_update", "qmg_hmc_momentum_refresh", "qmg_hmc_stream_seed",
     "qmg_u1_flow_stage", "qmg_u1_flow", "qmg_u1_wilson_loops", "qmg_u1_polyakov",
+    "qmg_dwf_fill", "qmg_dwf_apply_direct", "qmg_dwf_plan",
 ]
 
 
@@ -723,6 +724,37 @@ def wilson_hops_direct(dtype, desc, gauge, lhs, rhs, pieces, w, hop_scale, nrhs=
     check(lib().qmg_wilson_hops_direct(dtype, C.byref(desc), _vp(gauge), desc.Ly if gauge_Ly is None else gauge_Ly, y0, C.c_double(w), C.c_double(hop_scale),
                                        _vp(lhs), _vp(rhs), _vp(halo_lo), _vp(halo_hi), C.c_uint(pieces), nrhs, C.c_size_t(vec_stride), C.c_size_t(halo_stride),
                                        C.c_uint(mask), rows, stream), "qmg_wilson_hops_direct")
+
+
+def dwf_fill(clover, hopping, gauge, Lx, Ly, Ls, mass=0.0, w=1.0, stream=None):
+    """The stored nc = 2 Ls clover / hopping fields of the Shamir domain-wall operator (qmg_dwf_fill)."""
+    mass = complex(mass)
+    check(lib().qmg_dwf_fill(_vp(clover), _vp(hopping), _vp(gauge), Lx, Ly, Ls, C.c_double(mass.real), C.c_double(mass.imag), C.c_double(w), C.c_void_p(stream)),
+          "qmg_dwf_fill")
+
+
+def dwf_apply_direct_status(dtype, desc, gauge, Ls, mass, lhs, rhs, pieces, w=1.0, nrhs=1, vec_stride=0, mask=1, stream=None):
+    """qmg_dwf_apply_direct's status, unchecked (the refusals are part of its contract)."""
+    mass = complex(mass)
+    return lib().qmg_dwf_apply_direct(dtype, C.byref(desc), _vp(gauge), Ls, C.c_double(mass.real), C.c_double(mass.imag), C.c_double(w), _vp(lhs), _vp(rhs),
+                                      C.c_uint(pieces), nrhs, C.c_size_t(vec_stride), C.c_uint(mask), C.c_void_p(stream))
+
+
+def dwf_apply_direct(dtype, desc, gauge, Ls, mass, lhs, rhs, pieces, w=1.0, nrhs=1, vec_stride=0, mask=1, stream=None):
+    check(dwf_apply_direct_status(dtype, desc, gauge, Ls, mass, lhs, rhs, pieces, w, nrhs, vec_stride, mask, stream), "qmg_dwf_apply_direct")
+
+
+# families and flags of qmg_dwf_plan (include/qmg_hip.h)
+DF_UNSUPPORTED, DF_DIRECT, DF_NOTHING, DF_INVALID, DF_PAIR = range(5)
+DPF_ZERO, DPF_BATCH, DPF_F32 = 1, 2, 4
+DWF_PLAN_INTS = 8
+
+
+def dwf_plan(dtype, dims, Ls, pieces, n_active=1, inplace=False):
+    """What qmg_dwf_apply_direct does with a request (qmg_dwf_plan; host only): (family, lps, block, gx, gy, flags, shape, nk)."""
+    out = (C.c_int * DWF_PLAN_INTS)()
+    check(lib().qmg_dwf_plan(dtype, dims[0], dims[1], Ls, C.c_uint(pieces), n_active, int(inplace), out, DWF_PLAN_INTS), "qmg_dwf_plan")
+    return tuple(out)
 
 
 def comm_set_distributed_reductions(on):

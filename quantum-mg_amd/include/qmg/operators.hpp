@@ -1,6 +1,6 @@
 // operators.hpp -- the concrete stencils of the reference on device arrays:
 //   Wilson2D (operators/wilson.h), Staggered2D (operators/staggered.h), GaugedLaplace2D
-//   (operators/gaugedlaplace.h), FreeLaplace2D (tests/n02_free_laplace_test/free_laplace.h).
+//   (operators/gaugedlaplace.h), FreeLaplace2D (tests/n02_free_laplace_test/free_laplace.h), Dwf2D<Ls> / createDwfLs (operators/dwf.h).
 // CoarseOperator2D lives in coarse.hpp (it needs TransferMG).
 #ifndef QMG_OPERATORS_HPP
 #define QMG_OPERATORS_HPP
@@ -74,6 +74,88 @@ struct Wilson2D : public Stencil2D {
   virtual void sigma1(complex<double>* s1_vec, complex<double>* vec) { per_site(1.0, 1.0, 1, 0, s1_vec, vec); }          // :138-143
   virtual QMGDefaultChirality get_default_chirality() { return QMG_CHIRALITY_GAMMA_5; }
 };
+
+// ---------------- Shamir domain wall (operators/dwf.h; nc = 2 Ls: Ls copies of the Wilson spin blocks coupled along the fifth dimension) ----------------
+// Component c = 2 s + sigma.  The domain-wall height M5 is the stencil's identity shift, the wall mass couples slice Ls-1 to slice 0.  The
+// stored arrays (qmg_dwf_fill: the full nc x nc matrices, zeros included) serve the dagger / right-block-Jacobi / Galerkin builds and every
+// piece set the kernel from the links does not; the ORIGINAL-operator applies go straight from the links (qmg_dwf_apply_direct, csrc/qmg_dwf.hip).
+// Whole lattice only: y-slabs are not served.
+template <int Ls>
+struct Dwf2D : public Stencil2D {
+ protected:
+  Dwf2D(Dwf2D const&);
+  Dwf2D& operator=(Dwf2D const&);
+  complex<double> mass;
+  double M5;
+  complex<double>* scratch;   // for the in-place gamma5
+
+ public:
+  double a[2 * Ls];        // gamma5 as a scale / shuffle pattern (dwf.h:36-37, 62-67)
+  int shuffle[2 * Ls];
+
+  void update_links(complex<double>* gauge_links) {   // dwf.h:154-255; gauge_links: DEVICE nc=1 LatticeGauge
+    qmg::ok(qmg_dwf_fill(clover, hopping, gauge_links, lat->get_dim_mu(0), lat->get_dim_mu(1), Ls, mass.real(), mass.imag(), 1.0, qmg::current_stream()), "qmg_dwf_fill");
+    if (built_dagger) { deallocate_vector(&dagger_clover); deallocate_vector(&dagger_hopping); built_dagger = false; }
+    if (built_rbjacobi) { deallocate_vector(&rbjacobi_cinv); deallocate_vector(&rbjacobi_clover); deallocate_vector(&rbjacobi_hopping); built_rbjacobi = false; }
+    if (built_rbj_dagger) { deallocate_vector(&rbj_dagger_cinv); deallocate_vector(&rbj_dagger_clover); deallocate_vector(&rbj_dagger_hopping); built_rbj_dagger = false; }
+    set_direct_links(gauge_links, 1.0, QMG_DIRECT_DWF, Ls, mass);   // the ORIGINAL-operator applies go straight from the links
+    generated = true;
+  }
+
+  Dwf2D(Lattice2D* in_lat, complex<double> mass, complex<double>* gauge_links, double M5 = -1.0)
+      : Stencil2D(in_lat, QMG_PIECE_CLOVER_HOPPING, M5, 0.0, 0.0), mass(mass), M5(M5), scratch(0) {
+    for (int i = 0; i < Ls; i++) {
+      a[2 * i] = 1.0; a[2 * i + 1] = -1.0;
+      shuffle[2 * i] = 2 * (Ls - 1 - i); shuffle[2 * i + 1] = 2 * (Ls - 1 - i) + 1;
+    }
+    if (lat->get_nc() != 2 * Ls) { std::cout << "[QMG-ERROR]: Dwf2D only supports Nc = 2 Ls.\n"; return; }
+    if (qmg::slab().on) { std::cout << "[QMG-ERROR]: Dwf2D is not decomposed into y-slabs.\n"; return; }
+    update_links(gauge_links);
+  }
+  ~Dwf2D() { if (scratch) deallocate_vector(&scratch); }
+
+  static int get_dof(int i = 0) { return 2 * Ls; }
+  static chirality_state has_chirality() { return QMG_CHIRAL_YES; }
+
+  // (Gamma5 psi)(s, sigma) = (-1)^sigma psi(Ls-1-s, sigma)
+  virtual void gamma5(complex<double>* vec) {                                                                            // dwf.h:104-108
+    if (!scratch) scratch = allocate_vector<complex<double>>(lat->get_size_cv_l());
+    qmg::pattern(a, shuffle, 2 * Ls, vec, scratch, (size_t)lat->get_volume());
+    copy_vector(vec, scratch, lat->get_size_cv_l());
+  }
+  virtual void gamma5(complex<double>* g5_vec, complex<double>* vec) {                                                   // :110-114
+    if (g5_vec == vec) { gamma5(vec); return; }
+    qmg::pattern(a, shuffle, 2 * Ls, vec, g5_vec, (size_t)lat->get_volume());
+  }
+  virtual void chiral_projection(complex<double>*, bool) { return; }                                                     // empty in the reference (:117-146)
+  virtual void chiral_projection_copy(complex<double>*, complex<double>*, bool) { return; }
+  virtual void chiral_projection_both(complex<double>*, complex<double>*) { return; }
+  virtual QMGDefaultChirality get_default_chirality() { return QMG_CHIRALITY_GAMMA_5; }
+};
+
+// A domain-wall operator of run-time Ls (dwf.h:261-293): the reference's list of Ls values, of which those are served whose nc = 2 Ls the
+// stored-stencil apply serves (the variants and every piece set the links kernel declines go through it): qmg_stencil_plan is asked.
+inline Stencil2D* createDwfLs(Lattice2D* in_lat, complex<double> mass, complex<double>* gauge_links, int Ls, double M5 = -1.0) {
+  int plan[12];
+  const bool listed = Ls == 2 || Ls == 4 || Ls == 6 || Ls == 8 || Ls == 12 || Ls == 16 || Ls == 24 || Ls == 32;
+  const bool stored = listed && qmg_stencil_plan(QMG_SE_APPLY, 0, 0, in_lat->get_dim_mu(0), in_lat->get_dim_mu(1), 2 * Ls, QMG_P_ALL | QMG_P_ZERO, 1, 0, 0, 1, 1, 0, 0,
+                                                 plan, 12) == QMG_SUCCESS && plan[0] != 0 && plan[0] != 9;
+  if (stored) {
+    switch (Ls) {
+      case 2: return new Dwf2D<2>(in_lat, mass, gauge_links, M5);
+      case 4: return new Dwf2D<4>(in_lat, mass, gauge_links, M5);
+      case 6: return new Dwf2D<6>(in_lat, mass, gauge_links, M5);
+      case 8: return new Dwf2D<8>(in_lat, mass, gauge_links, M5);
+      case 12: return new Dwf2D<12>(in_lat, mass, gauge_links, M5);
+      case 16: return new Dwf2D<16>(in_lat, mass, gauge_links, M5);
+      case 24: return new Dwf2D<24>(in_lat, mass, gauge_links, M5);
+      case 32: return new Dwf2D<32>(in_lat, mass, gauge_links, M5);   // (nc = 64: not served by the stored-stencil apply today)
+      default: break;
+    }
+  }
+  std::cout << "[QMG-ERROR]: Unsupported Ls " << Ls << " for domain wall operator. Add a template to dwf.h.\n";
+  return nullptr;
+}
 
 // ---------------- shared by the two nc = 1 operators: hand-rolled even-odd normal operator ----------------
 struct EoPrecNc1 : public Stencil2D {

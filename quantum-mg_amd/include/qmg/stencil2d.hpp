@@ -79,9 +79,9 @@ struct Stencil2D {
       if (rc != QMG_ERR_UNSUPPORTED && rc != QMG_ERR_INVALID) { qmg::ok(rc, "qmg_wilson_hops_direct"); return; }
     }
     if (direct_usable(cl, ho)) {   // straight from the links where that serves the piece set
-      const int rc = qmg_wilson_apply_direct(QMG_C64, &d, direct.gauge, d.Ly, 0, direct.w, lhs, rhs, 0, 0, pieces, 1, 0, 0, 1u, 0, qmg::current_stream());
+      const int rc = direct_apply(QMG_C64, d, lhs, rhs, pieces, 1, 0, 1u);
       if (rc == QMG_SUCCESS) return;
-      if (rc != QMG_ERR_UNSUPPORTED && rc != QMG_ERR_INVALID) { qmg::ok(rc, "qmg_wilson_apply_direct"); return; }
+      if (rc != QMG_ERR_UNSUPPORTED && rc != QMG_ERR_INVALID) { qmg::ok(rc, direct_name()); return; }
     }
     const void *ncl = 0, *nho = 0;
     if (narrow_arrays_for(cl, ho, &ncl, &nho)) {   // fp32 / 16-bit storage of the ORIGINAL stencil or of the right-block-Jacobi hops / cinv (enable_f32_matrices)
@@ -138,8 +138,14 @@ struct Stencil2D {
   // site kernel).  The operator class keeps its own copy of the links here; the ORIGINAL-operator applies take this route for
   // the piece sets it serves while no variant is swapped in, everything else streams the stored matrices.
   // QMG_WILSON_DIRECT=0 in the environment turns it off.
+  // The same holds for the Shamir domain-wall operator (Dwf2D; qmg_dwf_apply_direct, csrc/qmg_dwf.hip: 64 Ls + 32 B/site instead of
+  // 5 (2 Ls)^2 complex numbers): `kind` says whose links these are, Ls and m are the domain-wall operator's.
+  enum QMGDirectKind { QMG_DIRECT_WILSON = 0, QMG_DIRECT_DWF = 1 };
   struct DirectLinks {
     complex<double>* gauge; void* gauge32; double w; bool on;
+    int kind;                // QMGDirectKind
+    int Ls;                  // domain wall: slices of the fifth dimension (nc = 2 Ls)
+    complex<double> m;       // domain wall: the wall mass
     // right-block-Jacobi hops from the links too (qmg_wilson_hops_direct): cinv = rbj_scale x identity at every site, 0 = not so
     double rbj_scale;
   } direct;
@@ -167,7 +173,7 @@ struct Stencil2D {
         if (rc == QMG_SUCCESS) return true;
         if (rc != QMG_ERR_UNSUPPORTED && rc != QMG_ERR_INVALID) return qmg::ok(rc, "qmg_wilson_hops_direct");
       }
-      if (original_arrays && direct.on) {   // Wilson straight from the (global, replicated) links
+      if (original_arrays && direct.on && direct.kind == QMG_DIRECT_WILSON) {   // Wilson straight from the (global, replicated) links
         const int rc = qmg_wilson_apply_direct(QMG_C64, &d, direct.gauge, d.Ly * qmg::slab().world, qmg::slab().rank * d.Ly, direct.w, lhs, rhs, slab_halo_lo,
                                                slab_halo_hi, pieces, 1, 0, hs, 1u, rows, st);
         if (rc == QMG_SUCCESS) return true;
@@ -206,6 +212,14 @@ struct Stencil2D {
     }
     return true;
   }
+  // the ORIGINAL operator from the links on the whole lattice, by the record's kind; the status is the entry point's
+  int direct_apply(int dt, const qmg_stencil_desc& d, void* lhs, const void* rhs, unsigned pieces, int nrhs, size_t stride, unsigned mask) const {
+    const void* g = dt == QMG_C32 ? direct.gauge32 : (const void*)direct.gauge;
+    if (direct.kind == QMG_DIRECT_DWF)
+      return qmg_dwf_apply_direct(dt, &d, g, direct.Ls, direct.m.real(), direct.m.imag(), direct.w, lhs, rhs, pieces, nrhs, stride, mask, qmg::current_stream());
+    return qmg_wilson_apply_direct(dt, &d, g, d.Ly, 0, direct.w, lhs, rhs, 0, 0, pieces, nrhs, stride, 0, mask, 0, qmg::current_stream());
+  }
+  const char* direct_name() const { return direct.kind == QMG_DIRECT_DWF ? "qmg_dwf_apply_direct" : "qmg_wilson_apply_direct"; }
   bool direct_usable(const complex<double>* cl, const complex<double>* ho) const {
     // (the link copy stands in for the stored arrays only while those ARE the filled operator: clear_stencils / prune_stencils
     // drop it, and a null pair -- 0 == 0 after a prune -- never qualifies)
@@ -216,16 +230,16 @@ struct Stencil2D {
     return direct.on && direct.rbj_scale != 0.0 && built_rbjacobi && cl == 0 && ho != 0 && ho == rbjacobi_hopping_in_use() && !swap_dagger && !swap_rbj_dagger &&
            !(pieces & (QMG_P_CLOVER | QMG_P_SHIFT));
   }
-  void set_direct_links(const complex<double>* gauge_links, double w) {   // copies the links (the caller's array may change)
+  void set_direct_links(const complex<double>* gauge_links, double w, int kind = QMG_DIRECT_WILSON, int Ls = 0, complex<double> m = 0.0) {   // copies the links (the caller's array may change)
     static const bool enabled = !(getenv("QMG_WILSON_DIRECT") && atoi(getenv("QMG_WILSON_DIRECT")) == 0);
     direct.rbj_scale = 0.0;   // (a right-block-Jacobi stencil of the old links is dropped by the caller)
     const size_t n = (size_t)2 * lat->get_volume() * (qmg::slab().on ? qmg::slab().world : 1);   // a slab keeps the links of the WHOLE lattice (32 B/site)
-    if (!enabled || lat->get_nc() != 2) { direct.on = false; return; }
+    if (!enabled || lat->get_nc() != (kind == QMG_DIRECT_DWF ? 2 * Ls : 2)) { direct.on = false; return; }
     if (!direct.gauge) direct.gauge = allocate_vector<complex<double>>(n);
     if (!direct.gauge) { direct.on = false; return; }
     qmg::ok(qmg_memcpy_d2d(direct.gauge, gauge_links, sizeof(complex<double>) * n, qmg::current_stream()), "qmg_memcpy_d2d");
     if (direct.gauge32) qmg::ok(qmg_convert(direct.gauge32, QMG_C32, direct.gauge, QMG_C64, n, qmg::current_stream()), "qmg_convert");
-    direct.w = w;
+    direct.w = w; direct.kind = kind; direct.Ls = Ls; direct.m = m;
     direct.on = true;
   }
   void drop_direct_links() {
@@ -266,6 +280,7 @@ struct Stencil2D {
     f32.clover = f32.hopping = f32.rbj_hopping = f32.rbj_cinv = 0; f32.on = false;
     f32.dagger_clover = f32.dagger_hopping = f32.rbj_dagger_hopping = 0;
     direct.gauge = 0; direct.gauge32 = 0; direct.w = 1.0; direct.on = false; direct.rbj_scale = 0.0;
+    direct.kind = QMG_DIRECT_WILSON; direct.Ls = 0; direct.m = 0.0;
     slab_halo_lo = slab_halo_hi = 0;
     slab_comm_stream = slab_ev_rhs = slab_ev_halo = 0;
     f32.clover16 = f32.hopping16 = f32.rbj_hopping16 = 0; f32.half_on = false;
@@ -563,7 +578,7 @@ struct Stencil2D {
       const size_t hs = (size_t)d.Lx * d.nc;
       void* st = qmg::current_stream();
       if (!qmg::ok(qmg_halo_exchange_parity(dt, rhs, d.Lx, d.Ly, d.nc, slab_halo_lo, slab_halo_hi, nrhs, stride, hs, halo_parities(pieces), st), "qmg_halo_exchange")) return;
-      if (set == QMG_ARR_ORIGINAL && direct_usable(clover, hopping) && (!f || direct.gauge32)) {
+      if (set == QMG_ARR_ORIGINAL && direct_usable(clover, hopping) && direct.kind == QMG_DIRECT_WILSON && (!f || direct.gauge32)) {
         const int rc = qmg_wilson_apply_direct(dt, &d, f ? direct.gauge32 : (void*)direct.gauge, d.Ly * qmg::slab().world, qmg::slab().rank * d.Ly, direct.w, lhs, rhs,
                                                slab_halo_lo, slab_halo_hi, pieces, nrhs, stride, hs, mask, 0, st);
         if (rc == QMG_SUCCESS) return;
@@ -595,10 +610,9 @@ struct Stencil2D {
       return;
     }
     if (set == QMG_ARR_ORIGINAL && direct_usable(clover, hopping) && (sizeof(T) == sizeof(double) || direct.gauge32)) {
-      const int rc = qmg_wilson_apply_direct(sizeof(T) == sizeof(float) ? QMG_C32 : QMG_C64, &d, sizeof(T) == sizeof(float) ? direct.gauge32 : (void*)direct.gauge,
-                                             d.Ly, 0, direct.w, lhs, rhs, 0, 0, pieces, nrhs, stride, 0, mask, 0, qmg::current_stream());
+      const int rc = direct_apply(sizeof(T) == sizeof(float) ? QMG_C32 : QMG_C64, d, lhs, rhs, pieces, nrhs, stride, mask);
       if (rc == QMG_SUCCESS) return;
-      if (rc != QMG_ERR_UNSUPPORTED && rc != QMG_ERR_INVALID) { qmg::ok(rc, "qmg_wilson_apply_direct"); return; }
+      if (rc != QMG_ERR_UNSUPPORTED && rc != QMG_ERR_INVALID) { qmg::ok(rc, direct_name()); return; }
     }
     if (set == QMG_ARR_RBJ_HOPPING && rbj_direct_usable(0, rbjacobi_hopping_in_use(), pieces) && (sizeof(T) == sizeof(double) || direct.gauge32)) {
       const int rc = qmg_wilson_hops_direct(sizeof(T) == sizeof(float) ? QMG_C32 : QMG_C64, &d, sizeof(T) == sizeof(float) ? direct.gauge32 : (void*)direct.gauge,
@@ -652,7 +666,7 @@ struct Stencil2D {
     const int nrhs = system + 1;
     const unsigned mask = 1u << system;
     auto served = [](int rc, const char* what) { if (rc == QMG_SUCCESS) return 1; if (rc == QMG_ERR_UNSUPPORTED) return 0; qmg::ok(rc, what); return -1; };
-    if (set == QMG_ARR_ORIGINAL && direct_usable(clover, hopping) && (!f || direct.gauge32)) {
+    if (set == QMG_ARR_ORIGINAL && direct_usable(clover, hopping) && direct.kind == QMG_DIRECT_WILSON && (!f || direct.gauge32)) {
       const int r = served(qmg_wilson_apply_direct_epi(dt, &d, f ? direct.gauge32 : (void*)direct.gauge, d.Ly, 0, direct.w, lhs, rhs, 0, 0, pieces, nrhs, stride, 0, mask,
                                                        &epi, qmg::current_stream()), "qmg_wilson_apply_direct_epi");
       if (r) return true;   // (an error has been reported; falling back would only repeat it)
