@@ -9,7 +9,10 @@
 //   n18  right-block-Jacobi and Schur solves reconstruct the ORIGINAL system   (tests/n18_rbjacobi_stencil_test:153-231)
 //   n21  rbj-dagger normal equations (CGNE / CGNR)           (tests/n21_rbj_dagger_stencil_test:138-209)
 //   storage / lattice / multigrid bookkeeping
+//   the route of an apply: in each live state the facade gives, bit for bit, what the entry point named by the policy table gives
 #include <cmath>
+#include <cstring>
+#include <functional>
 #include <iostream>
 #include <string>
 
@@ -33,6 +36,38 @@ static double rel_resid(Stencil2D* op, complex<double>* x, complex<double>* b, l
   deallocate_vector(&Ax);
   return r;
 }
+
+// The route of an apply (Stencil2D::resolve_route / run_route): the facade's result against the entry point that the policy table of DESIGN 6b names for
+// the state, called directly with desc() and the arrays the table names.  Both launch the same kernel with the same arguments, so the bytes must agree:
+// `got` and `want` start from the same contents (systems a mask leaves out and a parity no piece writes must stay as they were), three systems of n.
+struct RouteCheck {
+  size_t n;
+  complex<double>*in, *other, *init, *got, *want;
+  complex<float>* in32;
+  explicit RouteCheck(size_t n_) : n(n_) {
+    complex<double>** all[] = {&in, &other, &init, &got, &want};
+    for (auto p : all) *p = allocate_vector<complex<double>>(3 * n);
+    gaussian(in, 3 * n, 3100); gaussian(other, 3 * n, 3101); gaussian(init, 3 * n, 3102);
+    void* f = 0;
+    qmg::ok(qmg_malloc(&f, 3 * n * sizeof(complex<float>)), "qmg_malloc");
+    in32 = (complex<float>*)f;
+    qmg::ok(qmg_convert(in32, QMG_C32, in, QMG_C64, 3 * n, qmg::current_stream()), "qmg_convert");
+  }
+  ~RouteCheck() {
+    complex<double>** all[] = {&in, &other, &init, &got, &want};
+    for (auto p : all) deallocate_vector(p);
+    qmg_free(in32);
+  }
+  // state_ok: the operator is in the state the row is about; facade: false where it declined
+  void operator()(const string& what, bool state_ok, const std::function<bool(void*)>& facade, const std::function<int(void*)>& entry) {
+    copy_vector(got, init, 3 * n); copy_vector(want, init, 3 * n);
+    const bool served = facade(got);
+    const int rc = entry(want);
+    const std::vector<complex<double>> g = qmg::to_host(got, 3 * n), w = qmg::to_host(want, 3 * n), i0 = qmg::to_host(init, 3 * n);
+    const bool same = memcmp(g.data(), w.data(), 3 * n * sizeof(complex<double>)) == 0, wrote = memcmp(g.data(), i0.data(), 3 * n * sizeof(complex<double>)) != 0;
+    check(state_ok && served && rc == QMG_SUCCESS && same && wrote, "route: " + what, rc);
+  }
+};
 
 int main(int argc, char** argv) {
   qmg_driver::Guard guard;
@@ -322,6 +357,39 @@ int main(int argc, char** argv) {
       const double dsh = sqrt(diffnorm2sq(out.vec(1), ref.vec(1), (long)n) / norm2sq(ref.vec(1), (long)n));
       check(dsh < 1e-13, o == 0 ? "shifted normal operator (Wilson)" : "shifted normal operator (Galerkin nc = 8)", dsh);
     }
+    // the route of an apply on the Galerkin operator (nc = 8, no links): the stored arrays in fp64, their narrow copies, one epilogue
+    {
+      RouteCheck route((size_t)latc.get_size_cv_l());
+      const size_t n = route.n;
+      void* st = qmg::current_stream();
+      const unsigned M0 = QMG_P_ALL | QMG_P_ZERO, OE0 = QMG_P_OE | QMG_P_ZERO_O, C0 = QMG_P_CLOVER | QMG_P_ZERO;
+      const qmg_apply_epilogue e = {route.other, 1.0, -1.0, 0};
+      qmg_stencil_desc d = co.desc(), d0 = co.desc();   // d0: arrays by hand, no shifts (the right-block-Jacobi pieces)
+      for (int i = 0; i < 2; i++) d0.shift[i] = d0.eo_shift[i] = d0.dof_shift[i] = 0.0;
+      route("Galerkin nc = 8, fp64 == qmg_stencil_apply_batch", !co.f32_matrices, [&](void* o) { co.apply_M_overwrite((complex<double>*)o, route.in); return true; },
+            [&](void* o) { return qmg_stencil_apply_batch(&d, o, route.in, M0, 1, 0, 1u, st); });
+      route("Galerkin nc = 8, epilogue on system 1 of 2 == qmg_stencil_apply_epi_t", true,
+            [&](void* o) { return co.launch_set_epi<double>(M0, (complex<double>*)o, route.in, Stencil2D::QMG_ARR_ORIGINAL, co.shift, co.eo_shift, co.dof_shift, n, 1, e); },
+            [&](void* o) { return qmg_stencil_apply_epi_t(QMG_C64, 0, &d, o, route.in, M0, n, 1, &e, st); });
+      bool on = co.enable_f32_matrices(32);
+      d.clover = co.clover32; d.hopping = co.hopping32;
+      route("Galerkin nc = 8, enable_f32_matrices(32) == qmg_stencil_apply_mat32", on && co.f32_bits == 32 && co.clover32 && co.hopping32,
+            [&](void* o) { co.apply_M_overwrite((complex<double>*)o, route.in); return true; }, [&](void* o) { return qmg_stencil_apply_mat32(&d, o, route.in, M0, 1, 0, 1u, st); });
+      d0.clover = 0; d0.hopping = co.rbj_hopping32;
+      route("Galerkin nc = 8, rbj hops alone == qmg_stencil_apply_mat32 on rbj_hopping32", co.rbj_hopping32 != 0,
+            [&](void* o) { co.launch_set_batch<double>(OE0, (complex<double>*)o, route.in, Stencil2D::QMG_ARR_RBJ_HOPPING, 0.0, 0.0, 0.0, 2, n, 0b10u); return true; },
+            [&](void* o) { return qmg_stencil_apply_mat32(&d0, o, route.in, OE0, 2, n, 0b10u, st); });
+      d0.clover = co.rbj_cinv32; d0.hopping = 0;
+      route("Galerkin nc = 8, cinv alone == qmg_stencil_apply_mat32 on rbj_cinv32", co.rbj_cinv32 != 0,
+            [&](void* o) { co.launch_set_batch<double>(C0, (complex<double>*)o, route.in, Stencil2D::QMG_ARR_RBJ_CINV, 0.0, 0.0, 0.0, 2, n, 0b11u); return true; },
+            [&](void* o) { return qmg_stencil_apply_mat32(&d0, o, route.in, C0, 2, n, 0b11u, st); });
+      on = co.enable_f32_matrices(16);
+      d.clover = co.clover32; d.hopping = co.hopping32;
+      route("Galerkin nc = 8, enable_f32_matrices(16) == qmg_stencil_apply_mat16_t", on && co.f32_bits == 16 && co.clover32 && co.hopping32,
+            [&](void* o) { co.apply_M_overwrite((complex<double>*)o, route.in); return true; },
+            [&](void* o) { return qmg_stencil_apply_mat16_t(QMG_C64, &d, o, route.in, M0, 1, 0, 1u, st); });
+      co.disable_f32_matrices();
+    }
     for (int j = 0; j < nvec; j++) deallocate_vector(&nv[j]);
     delete[] nv;
   }
@@ -350,6 +418,54 @@ int main(int argc, char** argv) {
       check(diffnorm2sq(a, w, n2) <= 1e-28 * norm2sq(w, n2), "after pruning the hopping term apply_M is clover + shift", sqrt(diffnorm2sq(a, w, n2) / norm2sq(w, n2)));
     }
     for (complex<double>** p : {&v, &a, &w}) deallocate_vector(p);
+  }
+
+  // ---- the route of an apply on the Wilson operator (nc = 2): from the links, from the stored arrays, from the fp32 shadows
+  {
+    Wilson2D w(&lat2, complex<double>(0.05, 0.0), gauge);
+    RouteCheck route((size_t)n2);
+    const size_t n = route.n;
+    void* st = qmg::current_stream();
+    const unsigned M0 = QMG_P_ALL | QMG_P_ZERO, OE0 = QMG_P_OE | QMG_P_ZERO_O;
+    const qmg_apply_epilogue e = {route.other, 1.0, -1.0, 0};
+    const int Ly = lat2.get_dim_mu(1);
+    qmg_stencil_desc d = w.desc();
+    auto apply_M = [&](void* o) { w.apply_M_overwrite((complex<double>*)o, route.in); return true; };
+    auto batch32 = [&](void* o) {
+      w.launch_set_batch<float>(M0, (complex<float>*)o, route.in32, Stencil2D::QMG_ARR_ORIGINAL, w.shift, w.eo_shift, w.dof_shift, 3, n, 0b101u);
+      return true;
+    };
+    route("Wilson, plain == qmg_wilson_apply_direct", w.direct.on && w.direct.kind == Stencil2D::QMG_DIRECT_WILSON, apply_M,
+          [&](void* o) { return qmg_wilson_apply_direct(QMG_C64, &d, w.direct.gauge, Ly, 0, w.direct.w, o, route.in, 0, 0, M0, 1, 0, 0, 1u, 0, st); });
+    route("Wilson, epilogue on system 1 of 2 == qmg_wilson_apply_direct_epi", w.direct.on,
+          [&](void* o) { return w.launch_set_epi<double>(M0, (complex<double>*)o, route.in, Stencil2D::QMG_ARR_ORIGINAL, w.shift, w.eo_shift, w.dof_shift, n, 1, e); },
+          [&](void* o) { return qmg_wilson_apply_direct_epi(QMG_C64, &d, w.direct.gauge, Ly, 0, w.direct.w, o, route.in, 0, 0, M0, 2, n, 0, 0b10u, &e, st); });
+    w.build_rbjacobi_stencil();
+    qmg_stencil_desc dh = w.desc();
+    dh.clover = 0; dh.hopping = w.rbjacobi_hopping;
+    for (int i = 0; i < 2; i++) dh.shift[i] = dh.eo_shift[i] = dh.dof_shift[i] = 0.0;
+    route("Wilson, rbj hops == qmg_wilson_hops_direct", w.direct.on && w.direct.rbj_scale != 0.0,
+          [&](void* o) { w.launch_set_batch<double>(OE0, (complex<double>*)o, route.in, Stencil2D::QMG_ARR_RBJ_HOPPING, 0.0, 0.0, 0.0, 1, 0, 1u); return true; },
+          [&](void* o) { return qmg_wilson_hops_direct(QMG_C64, &dh, w.direct.gauge, Ly, 0, w.direct.w, w.direct.rbj_scale, o, route.in, 0, 0, OE0, 1, 0, 0, 1u, 0, st); });
+    bool on = w.enable_f32_shadow(false);
+    route("Wilson, fp32 batch of 3, mask 0b101, links == qmg_wilson_apply_direct on gauge32", on && w.direct.gauge32 != 0, batch32,
+          [&](void* o) { return qmg_wilson_apply_direct(QMG_C32, &d, w.direct.gauge32, Ly, 0, w.direct.w, o, route.in32, 0, 0, M0, 3, n, 0, 0b101u, 0, st); });
+    w.build_dagger_stencil();
+    w.perform_swap_dagger();
+    qmg_stencil_desc dd = w.desc();
+    route("Wilson, dagger swapped in == qmg_stencil_apply_batch on the swapped arrays", dd.clover != d.clover && dd.hopping != d.hopping, apply_M,
+          [&](void* o) { return qmg_stencil_apply_batch(&dd, o, route.in, M0, 1, 0, 1u, st); });
+    w.perform_swap_dagger();
+    w.drop_direct_links();
+    route("Wilson, links dropped == qmg_stencil_apply_batch", !w.direct.on, apply_M, [&](void* o) { return qmg_stencil_apply_batch(&d, o, route.in, M0, 1, 0, 1u, st); });
+    qmg_stencil_desc dn = d;
+    dn.clover = w.f32.clover; dn.hopping = w.f32.hopping;
+    route("Wilson, fp32 batch of 3, mask 0b101, shadow == qmg_stencil_apply_t", w.f32.on && !w.f32.half_on, batch32,
+          [&](void* o) { return qmg_stencil_apply_t(QMG_C32, &dn, o, route.in32, M0, 3, n, 0b101u, st); });
+    on = w.enable_f32_shadow(true);
+    dn.clover = w.f32.clover16; dn.hopping = w.f32.hopping16;
+    route("Wilson, fp32 batch of 3, mask 0b101, half shadow == qmg_stencil_apply_h16", on && w.f32.half_on, batch32,
+          [&](void* o) { return qmg_stencil_apply_h16(&dn, o, route.in32, M0, 3, n, 0b101u, st); });
   }
 
   deallocate_vector(&gauge);

@@ -42,10 +42,7 @@ struct Wilson2D : public Stencil2D {
                                    lat->get_dim_mu(1), wilson_coeff, qmg::current_stream()), "qmg_wilson_fill_slab");
     else
       qmg::ok(qmg_wilson_fill(clover, hopping, gauge_links, lat->get_dim_mu(0), lat->get_dim_mu(1), wilson_coeff, qmg::current_stream()), "qmg_wilson_fill");
-    if (built_dagger) { deallocate_vector(&dagger_clover); deallocate_vector(&dagger_hopping); built_dagger = false; }
-    if (built_rbjacobi) { deallocate_vector(&rbjacobi_cinv); deallocate_vector(&rbjacobi_clover); deallocate_vector(&rbjacobi_hopping); built_rbjacobi = false; }
-    // (the reference leaves a built rbj_dagger stencil dangling here, wilson.h:211-225; it is dropped too)
-    if (built_rbj_dagger) { deallocate_vector(&rbj_dagger_cinv); deallocate_vector(&rbj_dagger_clover); deallocate_vector(&rbj_dagger_hopping); built_rbj_dagger = false; }
+    drop_variant_stencils();   // (the reference leaves a built rbj_dagger stencil dangling here, wilson.h:211-225; it is dropped too)
     set_direct_links(gauge_links, wilson_coeff);   // the ORIGINAL-operator applies go straight from the links (qmg_wilson.hip)
     generated = true;
   }
@@ -95,9 +92,7 @@ struct Dwf2D : public Stencil2D {
 
   void update_links(complex<double>* gauge_links) {   // dwf.h:154-255; gauge_links: DEVICE nc=1 LatticeGauge
     qmg::ok(qmg_dwf_fill(clover, hopping, gauge_links, lat->get_dim_mu(0), lat->get_dim_mu(1), Ls, mass.real(), mass.imag(), 1.0, qmg::current_stream()), "qmg_dwf_fill");
-    if (built_dagger) { deallocate_vector(&dagger_clover); deallocate_vector(&dagger_hopping); built_dagger = false; }
-    if (built_rbjacobi) { deallocate_vector(&rbjacobi_cinv); deallocate_vector(&rbjacobi_clover); deallocate_vector(&rbjacobi_hopping); built_rbjacobi = false; }
-    if (built_rbj_dagger) { deallocate_vector(&rbj_dagger_cinv); deallocate_vector(&rbj_dagger_clover); deallocate_vector(&rbj_dagger_hopping); built_rbj_dagger = false; }
+    drop_variant_stencils();
     set_direct_links(gauge_links, 1.0, QMG_DIRECT_DWF, Ls, mass);   // the ORIGINAL-operator applies go straight from the links
     generated = true;
   }

@@ -54,6 +54,37 @@ inline bool slab_begin() {   // after qmg_comm_init_env (or qmg_comm_emulate_att
 }
 inline void slab_end() { slab() = {false, 1, 0}; qmg_comm_set_distributed_reductions(0); }
 
+// A slab apply with its halo exchange hidden behind the interior rows (Stencil2D::launch, SlabWilson2D::apply): the exchange on a second stream,
+// behind the producer of the right-hand side; the interior rows (1) meanwhile on the current stream; the boundary rows (2) after both.  Owns the
+// stream and the two events, made on first use.  exchange(stream) and rows(which) return false to stop.  The next exchange overwrites the halos:
+// it is ordered behind this boundary launch through ev_rhs of the next run.
+struct HaloOverlap {
+  void *comm_stream, *ev_rhs, *ev_halo;
+  HaloOverlap() : comm_stream(0), ev_rhs(0), ev_halo(0) {}
+  ~HaloOverlap() {
+    if (comm_stream) { qmg_stream_sync(comm_stream); qmg_event_destroy(ev_rhs); qmg_event_destroy(ev_halo); qmg_stream_destroy(comm_stream); }
+  }
+  bool ready() {
+    if (!comm_stream && (qmg_stream_create(&comm_stream) != QMG_SUCCESS || qmg_event_create(&ev_rhs) != QMG_SUCCESS || qmg_event_create(&ev_halo) != QMG_SUCCESS))
+      comm_stream = 0;
+    return comm_stream != 0;
+  }
+  template <typename Exchange, typename Rows>
+  void run(Exchange exchange, Rows rows) {
+    void* st = current_stream();
+    ok(qmg_event_record(ev_rhs, st), "qmg_event_record");
+    ok(qmg_stream_wait_event(comm_stream, ev_rhs), "qmg_stream_wait_event");
+    if (!exchange(comm_stream)) return;
+    ok(qmg_event_record(ev_halo, comm_stream), "qmg_event_record");
+    if (!rows(1)) return;
+    ok(qmg_stream_wait_event(st, ev_halo), "qmg_stream_wait_event");
+    rows(2);
+  }
+ private:
+  HaloOverlap(const HaloOverlap&);
+  HaloOverlap& operator=(const HaloOverlap&);
+};
+
 // ---- staging helpers (host <-> device); the reference has no such step, tests index arrays directly ----
 template <typename T> inline void upload(T* dev, const T* host, size_t n) { ok(qmg_memcpy_h2d(dev, host, n * sizeof(T), nullptr), "qmg_memcpy_h2d"); }
 template <typename T> inline void download(T* host, const T* dev, size_t n) {

@@ -48,7 +48,7 @@ class SlabWilson2D {
   complex<double>*clover = nullptr, *hopping = nullptr;
   complex<double>*halo_lo = nullptr, *halo_hi = nullptr;
   qmg_stencil_desc desc;
-  void *comm_stream = nullptr, *ev_rhs = nullptr, *ev_halo = nullptr;
+  HaloOverlap overlapped;            // the exchange behind the interior rows: its stream and events
   bool overlap = true;               // false: exchange, then one launch over all rows
   bool from_links = true;            // apply straight from the (replicated, global) links: qmg_wilson_apply_direct; false: the slab's stored stencil
   const complex<double>* gauge = nullptr;
@@ -72,48 +72,31 @@ class SlabWilson2D {
     desc.clover = clover; desc.hopping = hopping;
     desc.shift[0] = mass; desc.shift[1] = 0.0;
     desc.eo_shift[0] = desc.eo_shift[1] = desc.dof_shift[0] = desc.dof_shift[1] = 0.0;
-    ok(qmg_stream_create(&comm_stream), "qmg_stream_create");
-    ok(qmg_event_create(&ev_rhs), "qmg_event_create");
-    ok(qmg_event_create(&ev_halo), "qmg_event_create");
+    if (!overlapped.ready()) std::cout << "[QMG-ERROR]: no second stream for the halo exchange: it will not be overlapped\n";
   }
   ~SlabWilson2D() {
     qmg_stream_sync(current_stream());
-    qmg_stream_sync(comm_stream);
+    if (overlapped.comm_stream) qmg_stream_sync(overlapped.comm_stream);
     if (clover) deallocate_vector(&clover);
     if (hopping) deallocate_vector(&hopping);
     deallocate_vector(&halo_lo); deallocate_vector(&halo_hi);
-    qmg_event_destroy(ev_rhs); qmg_event_destroy(ev_halo); qmg_stream_destroy(comm_stream);
     delete lat;
   }
   size_t size_cv() const { return (size_t)lat->get_size_cv(); }
 
-  // one launch over the rows `rows` selects (0 all, 1 interior, 2 boundary)
-  void launch_rows(complex<double>* lhs, complex<double>* rhs, unsigned pieces, int rows, void* st) {
-    const size_t hs = 2 * (size_t)geo.Lx;
-    if (from_links)
-      ok(qmg_wilson_apply_direct(QMG_C64, &desc, gauge, geo.Ly_global, geo.y0, w, lhs, rhs, halo_lo, halo_hi, pieces, 1, 0, hs, 1u, rows, st), "qmg_wilson_apply_direct");
-    else
-      ok(qmg_stencil_apply_slab(QMG_C64, &desc, lhs, rhs, halo_lo, halo_hi, pieces, 1, 0, hs, 1u, rows, st), "qmg_stencil_apply_slab");
-  }
   // lhs = pieces(M) rhs on the slab; rhs must not alias lhs
   void apply(complex<double>* lhs, complex<double>* rhs, unsigned pieces) {
-    void* st = current_stream();
     const size_t hs = 2 * (size_t)geo.Lx;
     applies++;
-    if (!overlap) {
-      ok(qmg_halo_exchange(QMG_C64, rhs, geo.Lx, geo.Ly_local, 2, halo_lo, halo_hi, 1, 0, hs, st), "qmg_halo_exchange");
-      launch_rows(lhs, rhs, pieces, 0, st);
-      return;
-    }
-    // the exchange on its own stream, behind the producer of rhs; the interior rows meanwhile; the boundary rows after both
-    ok(qmg_event_record(ev_rhs, st), "qmg_event_record");
-    ok(qmg_stream_wait_event(comm_stream, ev_rhs), "qmg_stream_wait_event");
-    ok(qmg_halo_exchange(QMG_C64, rhs, geo.Lx, geo.Ly_local, 2, halo_lo, halo_hi, 1, 0, hs, comm_stream), "qmg_halo_exchange");
-    ok(qmg_event_record(ev_halo, comm_stream), "qmg_event_record");
-    launch_rows(lhs, rhs, pieces, 1, st);
-    ok(qmg_stream_wait_event(st, ev_halo), "qmg_stream_wait_event");
-    launch_rows(lhs, rhs, pieces, 2, st);
-    // the next exchange overwrites the halos: it is ordered behind this boundary launch through ev_rhs of the next apply
+    auto exchange = [&](void* st) { return ok(qmg_halo_exchange(QMG_C64, rhs, geo.Lx, geo.Ly_local, 2, halo_lo, halo_hi, 1, 0, hs, st), "qmg_halo_exchange"); };
+    auto rows = [&](int which) -> bool {   // one launch over the rows `which` selects (0 all, 1 interior, 2 boundary)
+      void* st = current_stream();
+      if (from_links)
+        return ok(qmg_wilson_apply_direct(QMG_C64, &desc, gauge, geo.Ly_global, geo.y0, w, lhs, rhs, halo_lo, halo_hi, pieces, 1, 0, hs, 1u, which, st), "qmg_wilson_apply_direct");
+      return ok(qmg_stencil_apply_slab(QMG_C64, &desc, lhs, rhs, halo_lo, halo_hi, pieces, 1, 0, hs, 1u, which, st), "qmg_stencil_apply_slab");
+    };
+    if (overlap && overlapped.ready()) overlapped.run(exchange, rows);
+    else if (exchange(current_stream())) rows(0);
   }
   void apply_M(complex<double>* lhs, complex<double>* rhs) { apply(lhs, rhs, QMG_P_ALL | QMG_P_ZERO); }
 };

@@ -62,35 +62,24 @@ struct Stencil2D {
   complex<double> shift_backup, eo_shift_backup, dof_shift_backup;
   bool swap_dagger, swap_rbjacobi, swap_rbj_dagger;
 
-  // ---- the one launch every apply method goes through ----
+  // ---- the one launch every single-vector apply method goes through: the route of (cl, ho), run on the whole lattice or on this rank's slab ----
   void launch(unsigned pieces, complex<double>* lhs, complex<double>* rhs, const complex<double>* cl, const complex<double>* ho,
               complex<double> s, complex<double> es, complex<double> ds) {
-    qmg_stencil_desc d;
-    d.Lx = lat->get_dim_mu(0); d.Ly = lat->get_dim_mu(1); d.nc = lat->get_nc();
-    d.clover = cl; d.hopping = ho;
-    d.shift[0] = s.real(); d.shift[1] = s.imag();
-    d.eo_shift[0] = es.real(); d.eo_shift[1] = es.imag();
-    d.dof_shift[0] = ds.real(); d.dof_shift[1] = ds.imag();
-    const double rbj_sc = rbj_direct_usable(cl, ho, pieces) ? direct.rbj_scale : 0.0;
-    if (qmg::slab().on) { launch_slab(d, pieces, lhs, rhs, direct_usable(cl, ho), rbj_sc); return; }
-    if (rbj_sc != 0.0) {           // D'_eo / D'_oe of the right-block-Jacobi Wilson stencil: the links times one number
-      const int rc = qmg_wilson_hops_direct(QMG_C64, &d, direct.gauge, d.Ly, 0, direct.w, rbj_sc, lhs, rhs, 0, 0, pieces, 1, 0, 0, 1u, 0, qmg::current_stream());
-      if (rc == QMG_SUCCESS) return;
-      if (rc != QMG_ERR_UNSUPPORTED && rc != QMG_ERR_INVALID) { qmg::ok(rc, "qmg_wilson_hops_direct"); return; }
-    }
-    if (direct_usable(cl, ho)) {   // straight from the links where that serves the piece set
-      const int rc = direct_apply(QMG_C64, d, lhs, rhs, pieces, 1, 0, 1u);
-      if (rc == QMG_SUCCESS) return;
-      if (rc != QMG_ERR_UNSUPPORTED && rc != QMG_ERR_INVALID) { qmg::ok(rc, direct_name()); return; }
-    }
-    const void *ncl = 0, *nho = 0;
-    if (narrow_arrays_for(cl, ho, &ncl, &nho)) {   // fp32 / 16-bit storage of the ORIGINAL stencil or of the right-block-Jacobi hops / cinv (enable_f32_matrices)
-      d.clover = ncl; d.hopping = nho;
-      if (f32_bits == 16) qmg::ok(qmg_stencil_apply_mat16_t(QMG_C64, &d, lhs, rhs, pieces, 1, 0, 1u, qmg::current_stream()), "qmg_stencil_apply_mat16_t");
-      else qmg::ok(qmg_stencil_apply_mat32(&d, lhs, rhs, pieces, 1, 0, 1u, qmg::current_stream()), "qmg_stencil_apply_mat32");
-      return;
-    }
-    qmg::ok(qmg_stencil_apply(&d, lhs, rhs, pieces, 1, 0, qmg::current_stream()), "qmg_stencil_apply");
+    const RouteState state = route_state();
+    const RouteRequest q = {cl, ho, false, QMG_ARR_ORIGINAL, pieces, QMG_C64, state.slab_on ? QMG_ROUTE_SLAB : QMG_ROUTE_WHOLE, true};
+    const Route r = resolve_route(state, q);
+    const qmg_stencil_desc d = desc(cl, ho, s, es, ds);
+    if (!state.slab_on) { run_route(r, q.mode, d, QMG_C64, lhs, rhs, pieces, 1, 0, 1u); return; }
+    // one system on a slab: exchange the halo rows of rhs with the neighbouring ranks, then apply with them
+    if (!slab_halos()) { std::cout << "[QMG-ERROR]: no memory for the halo rows\n"; return; }
+    const unsigned par = ho ? halo_parities(pieces) : 0u;   // (a route from the links has a hopping array too)
+    auto exchange = [&](void* st) {
+      return qmg::ok(qmg_halo_exchange_parity(QMG_C64, rhs, d.Lx, d.Ly, d.nc, slab_halo_lo, slab_halo_hi, 1, 0, (size_t)d.Lx * d.nc, par, st), "qmg_halo_exchange");
+    };
+    auto rows = [&](int which) { return run_route(r, q.mode, d, QMG_C64, lhs, rhs, pieces, 1, 0, 1u, which) > 0; };   // 0: all rows, 1: interior, 2: boundary
+    // with more than one rank the nc = 2 kernels run the interior rows WHILE the halo rows travel, then the two boundary rows (qmg::HaloOverlap)
+    if (par && qmg::slab().world > 1 && d.nc == 2 && d.Ly >= 4 && lhs != rhs && slab_overlap.ready()) slab_overlap.run(exchange, rows);
+    else if (exchange(qmg::current_stream())) rows(0);
   }
   void launch(unsigned pieces, complex<double>* lhs, complex<double>* rhs) { launch(pieces, lhs, rhs, clover, hopping, shift, eo_shift, dof_shift); }
 
@@ -105,8 +94,7 @@ struct Stencil2D {
   // opt-in: complex<float> copies of clover / hopping that the ORIGINAL-operator applies stream instead of the fp64 arrays
   bool f32_matrices;
   int f32_bits;   // 32: clover32 / hopping32 hold complex<float>; 16: complex<half> (enable_f32_matrices(16))
-  // the fp32 copies mirror the ORIGINAL arrays: while a variant (dagger, rbjacobi, rbj-dagger) is swapped into clover / hopping they do not apply
-  bool f32_in_use() const { return f32_matrices && !swap_dagger && !swap_rbjacobi && !swap_rbj_dagger; }
+  // (the fp32 copies mirror the ORIGINAL arrays: while a variant -- dagger, rbjacobi, rbj-dagger -- is swapped into clover / hopping they do not apply)
   void* clover32;
   void* hopping32;
   void* rbj_hopping32;   // the same narrow storage for the right-block-Jacobi hops and cinv (the Schur K-cycle's matrix stream), when that stencil is built
@@ -127,11 +115,6 @@ struct Stencil2D {
   // the conjugated shifts
   // QMG_ARR_RBJ_DAGGER: the hops of the right-block-Jacobi dagger stencil (build_rbj_dagger_stencil) by name; its clover is the identity (a unit shift)
   enum QMGArraySet { QMG_ARR_ORIGINAL = 0, QMG_ARR_RBJ_HOPPING = 1, QMG_ARR_RBJ_CINV = 2, QMG_ARR_DAGGER = 3, QMG_ARR_RBJ_DAGGER = 4 };
-  static bool set_has_16bit_copy(QMGArraySet set) { return set == QMG_ARR_ORIGINAL || set == QMG_ARR_RBJ_HOPPING; }
-  const void* clover_of(QMGArraySet set) const { return set == QMG_ARR_ORIGINAL ? clover : set == QMG_ARR_RBJ_CINV ? rbjacobi_cinv : set == QMG_ARR_DAGGER ? dagger_clover : 0; }
-  const void* hopping_of(QMGArraySet set) const { return set == QMG_ARR_ORIGINAL ? hopping : set == QMG_ARR_RBJ_HOPPING ? rbjacobi_hopping_in_use() : set == QMG_ARR_DAGGER ? dagger_hopping : set == QMG_ARR_RBJ_DAGGER ? (swap_rbj_dagger ? hopping : rbj_dagger_hopping) : 0; }
-  const void* f32_clover_of(QMGArraySet set) const { return set == QMG_ARR_ORIGINAL ? f32.clover : set == QMG_ARR_RBJ_CINV ? f32.rbj_cinv : set == QMG_ARR_DAGGER ? f32.dagger_clover : 0; }
-  const void* f32_hopping_of(QMGArraySet set) const { return set == QMG_ARR_ORIGINAL ? f32.hopping : set == QMG_ARR_RBJ_HOPPING ? f32.rbj_hopping : set == QMG_ARR_DAGGER ? f32.dagger_hopping : set == QMG_ARR_RBJ_DAGGER ? f32.rbj_dagger_hopping : 0; }
 
   // Operators whose stencil is a fixed spin pattern times the gauge links (Wilson2D) can be applied straight from the links
   // (qmg_wilson_apply_direct, csrc/qmg_wilson.hip: 96 B/site instead of 384, bit-identical to the stored stencil through the
@@ -158,78 +141,7 @@ struct Stencil2D {
   }
   // which parities of the right-hand side the hops of `pieces` read: D_eo (even sites written) reads odd rows, D_oe even rows
   static unsigned halo_parities(unsigned pieces) { return ((pieces & QMG_P_EO) ? 2u : 0u) | ((pieces & QMG_P_OE) ? 1u : 0u); }
-  // one system on a slab: exchange the halo rows of rhs with the neighbouring ranks, then apply with them
-  void launch_slab(const qmg_stencil_desc& d, unsigned pieces, complex<double>* lhs, complex<double>* rhs, bool original_arrays, double rbj_scale = 0.0) {
-    if (!slab_halos()) { std::cout << "[QMG-ERROR]: no memory for the halo rows\n"; return; }
-    const size_t hs = (size_t)d.Lx * d.nc;
-    void* st = qmg::current_stream();
-    const unsigned par = (d.hopping || original_arrays) ? halo_parities(pieces) : 0u;
-    // rows: 0 = all rows after the exchange; with more than one rank the nc = 2 kernels run the interior rows WHILE the halo rows travel
-    // (exchange on a second stream behind an event), then the two boundary rows -- what SlabWilson2D does (slab.hpp)
-    auto apply_rows = [&](int rows) -> bool {
-      if (rbj_scale != 0.0) {               // right-block-Jacobi hops from the links
-        const int rc = qmg_wilson_hops_direct(QMG_C64, &d, direct.gauge, d.Ly * qmg::slab().world, qmg::slab().rank * d.Ly, direct.w, rbj_scale, lhs, rhs, slab_halo_lo,
-                                              slab_halo_hi, pieces, 1, 0, hs, 1u, rows, st);
-        if (rc == QMG_SUCCESS) return true;
-        if (rc != QMG_ERR_UNSUPPORTED && rc != QMG_ERR_INVALID) return qmg::ok(rc, "qmg_wilson_hops_direct");
-      }
-      if (original_arrays && direct.on && direct.kind == QMG_DIRECT_WILSON) {   // Wilson straight from the (global, replicated) links
-        const int rc = qmg_wilson_apply_direct(QMG_C64, &d, direct.gauge, d.Ly * qmg::slab().world, qmg::slab().rank * d.Ly, direct.w, lhs, rhs, slab_halo_lo,
-                                               slab_halo_hi, pieces, 1, 0, hs, 1u, rows, st);
-        if (rc == QMG_SUCCESS) return true;
-        if (rc != QMG_ERR_UNSUPPORTED && rc != QMG_ERR_INVALID) return qmg::ok(rc, "qmg_wilson_apply_direct");
-      }
-      const void *ncl = 0, *nho = 0;
-      if (narrow_arrays_for(d.clover, d.hopping, &ncl, &nho)) {   // fp32 / 16-bit storage of a preconditioner level's matrices (enable_f32_matrices), fp64 vectors
-        qmg_stencil_desc dn = d;
-        dn.clover = ncl; dn.hopping = nho;
-        return qmg::ok(qmg_stencil_apply_slab(QMG_C64 | (f32_bits == 16 ? QMG_SLAB_M16 : QMG_SLAB_M32), &dn, lhs, rhs, slab_halo_lo, slab_halo_hi, pieces, 1, 0, hs, 1u, rows, st),
-                       "qmg_stencil_apply_slab");
-      }
-      return qmg::ok(qmg_stencil_apply_slab(QMG_C64, &d, lhs, rhs, slab_halo_lo, slab_halo_hi, pieces, 1, 0, hs, 1u, rows, st), "qmg_stencil_apply_slab");
-    };
-    const bool overlap = par && qmg::slab().world > 1 && d.nc == 2 && d.Ly >= 4 && lhs != rhs && slab_overlap_ready();
-    if (!overlap) {
-      if (!qmg::ok(qmg_halo_exchange_parity(QMG_C64, rhs, d.Lx, d.Ly, d.nc, slab_halo_lo, slab_halo_hi, 1, 0, hs, par, st), "qmg_halo_exchange")) return;
-      apply_rows(0);
-      return;
-    }
-    qmg::ok(qmg_event_record(slab_ev_rhs, st), "qmg_event_record");
-    qmg::ok(qmg_stream_wait_event(slab_comm_stream, slab_ev_rhs), "qmg_stream_wait_event");
-    if (!qmg::ok(qmg_halo_exchange_parity(QMG_C64, rhs, d.Lx, d.Ly, d.nc, slab_halo_lo, slab_halo_hi, 1, 0, hs, par, slab_comm_stream), "qmg_halo_exchange")) return;
-    qmg::ok(qmg_event_record(slab_ev_halo, slab_comm_stream), "qmg_event_record");
-    if (!apply_rows(1)) return;
-    qmg::ok(qmg_stream_wait_event(st, slab_ev_halo), "qmg_stream_wait_event");
-    apply_rows(2);
-  }
-  void *slab_comm_stream, *slab_ev_rhs, *slab_ev_halo;
-  bool slab_overlap_ready() {
-    if (!slab_comm_stream) {
-      if (qmg_stream_create(&slab_comm_stream) != QMG_SUCCESS || qmg_event_create(&slab_ev_rhs) != QMG_SUCCESS || qmg_event_create(&slab_ev_halo) != QMG_SUCCESS) {
-        slab_comm_stream = 0;
-        return false;
-      }
-    }
-    return true;
-  }
-  // the ORIGINAL operator from the links on the whole lattice, by the record's kind; the status is the entry point's
-  int direct_apply(int dt, const qmg_stencil_desc& d, void* lhs, const void* rhs, unsigned pieces, int nrhs, size_t stride, unsigned mask) const {
-    const void* g = dt == QMG_C32 ? direct.gauge32 : (const void*)direct.gauge;
-    if (direct.kind == QMG_DIRECT_DWF)
-      return qmg_dwf_apply_direct(dt, &d, g, direct.Ls, direct.m.real(), direct.m.imag(), direct.w, lhs, rhs, pieces, nrhs, stride, mask, qmg::current_stream());
-    return qmg_wilson_apply_direct(dt, &d, g, d.Ly, 0, direct.w, lhs, rhs, 0, 0, pieces, nrhs, stride, 0, mask, 0, qmg::current_stream());
-  }
-  const char* direct_name() const { return direct.kind == QMG_DIRECT_DWF ? "qmg_dwf_apply_direct" : "qmg_wilson_apply_direct"; }
-  bool direct_usable(const complex<double>* cl, const complex<double>* ho) const {
-    // (the link copy stands in for the stored arrays only while those ARE the filled operator: clear_stencils / prune_stencils
-    // drop it, and a null pair -- 0 == 0 after a prune -- never qualifies)
-    return direct.on && generated && cl != 0 && ho != 0 && cl == clover && ho == hopping && !swap_dagger && !swap_rbjacobi && !swap_rbj_dagger && !f32_matrices;
-  }
-  // the hops of the right-block-Jacobi stencil, alone, while that stencil is the built one (swapped in or not)
-  bool rbj_direct_usable(const complex<double>* cl, const complex<double>* ho, unsigned pieces) const {
-    return direct.on && direct.rbj_scale != 0.0 && built_rbjacobi && cl == 0 && ho != 0 && ho == rbjacobi_hopping_in_use() && !swap_dagger && !swap_rbj_dagger &&
-           !(pieces & (QMG_P_CLOVER | QMG_P_SHIFT));
-  }
+  qmg::HaloOverlap slab_overlap;   // the second stream and events of a single-vector slab apply, made on first use
   void set_direct_links(const complex<double>* gauge_links, double w, int kind = QMG_DIRECT_WILSON, int Ls = 0, complex<double> m = 0.0) {   // copies the links (the caller's array may change)
     static const bool enabled = !(getenv("QMG_WILSON_DIRECT") && atoi(getenv("QMG_WILSON_DIRECT")) == 0);
     direct.rbj_scale = 0.0;   // (a right-block-Jacobi stencil of the old links is dropped by the caller)
@@ -255,14 +167,166 @@ struct Stencil2D {
   bool built_rbj_dagger;
   complex<double>*rbj_dagger_clover, *rbj_dagger_hopping, *rbj_dagger_twolink, *rbj_dagger_corner, *rbj_dagger_cinv;
 
-  qmg_stencil_desc desc() const {   // for direct C-ABI users
+  // the descriptor of an apply: the lattice, the arrays and the three shifts
+  qmg_stencil_desc desc(const void* cl, const void* ho, complex<double> s, complex<double> es, complex<double> ds) const {
     qmg_stencil_desc d;
     d.Lx = lat->get_dim_mu(0); d.Ly = lat->get_dim_mu(1); d.nc = lat->get_nc();
-    d.clover = clover; d.hopping = hopping;
-    d.shift[0] = shift.real(); d.shift[1] = shift.imag();
-    d.eo_shift[0] = eo_shift.real(); d.eo_shift[1] = eo_shift.imag();
-    d.dof_shift[0] = dof_shift.real(); d.dof_shift[1] = dof_shift.imag();
+    d.clover = cl; d.hopping = ho;
+    d.shift[0] = s.real(); d.shift[1] = s.imag();
+    d.eo_shift[0] = es.real(); d.eo_shift[1] = es.imag();
+    d.dof_shift[0] = ds.real(); d.dof_shift[1] = ds.imag();
     return d;
+  }
+  qmg_stencil_desc desc() const { return desc(clover, hopping, shift, eo_shift, dof_shift); }   // for direct C-ABI users
+
+  // ================= the route of an apply =================
+  // "Which arrays and which C entry point serve this apply" is answered once: resolve_route is a pure function of a snapshot of the members the
+  // policy reads (RouteState, filled by route_state()) and of the request -- no library call, no allocation, no print; tests/host/stencil_route.cpp
+  // holds it to a table written out by hand -- and run_route is the only function that names the apply entry points.  launch (one fp64 vector, arrays
+  // by pointer), launch_set_batch and launch_set_epi (either precision, arrays by set) are front ends of the two.
+  enum RouteMode { QMG_ROUTE_WHOLE = 0, QMG_ROUTE_SLAB = 1, QMG_ROUTE_EPILOGUE = 2 };
+  enum RouteLinks { QMG_LINKS_NONE = 0, QMG_LINKS_WILSON = 1, QMG_LINKS_DWF = 2, QMG_LINKS_RBJ_HOPS = 3 };
+  enum RouteStorage { QMG_MAT_C64 = 0, QMG_MAT_C32 = 1, QMG_MAT_C16 = 2 };   // complex<double>, <float>, <half> matrices (the values are qmg_stencil_apply_epi_t's mat32)
+  struct RouteState {
+    const void *clover, *hopping, *dagger_clover, *dagger_hopping, *rbjacobi_hopping, *rbjacobi_cinv, *rbj_dagger_hopping;
+    bool built_rbjacobi, swap_dagger, swap_rbjacobi, swap_rbj_dagger, generated, f32_matrices;
+    int f32_bits;
+    const void *clover32, *hopping32, *rbj_hopping32, *rbj_cinv32;
+    F32Shadow f32;
+    DirectLinks direct;
+    int nc;
+    bool slab_on;   // qmg::slab().on
+    // the arrays of a set, in fp64 and in the fp32 shadow
+    const void* rbjacobi_hopping_in_use() const { return swap_rbjacobi ? hopping : rbjacobi_hopping; }
+    const void* clover_of(QMGArraySet set) const { return set == QMG_ARR_ORIGINAL ? clover : set == QMG_ARR_RBJ_CINV ? rbjacobi_cinv : set == QMG_ARR_DAGGER ? dagger_clover : 0; }
+    const void* hopping_of(QMGArraySet set) const { return set == QMG_ARR_ORIGINAL ? hopping : set == QMG_ARR_RBJ_HOPPING ? rbjacobi_hopping_in_use() : set == QMG_ARR_DAGGER ? dagger_hopping : set == QMG_ARR_RBJ_DAGGER ? (swap_rbj_dagger ? hopping : rbj_dagger_hopping) : 0; }
+    const void* f32_clover_of(QMGArraySet set) const { return set == QMG_ARR_ORIGINAL ? f32.clover : set == QMG_ARR_RBJ_CINV ? f32.rbj_cinv : set == QMG_ARR_DAGGER ? f32.dagger_clover : 0; }
+    const void* f32_hopping_of(QMGArraySet set) const { return set == QMG_ARR_ORIGINAL ? f32.hopping : set == QMG_ARR_RBJ_HOPPING ? f32.rbj_hopping : set == QMG_ARR_DAGGER ? f32.dagger_hopping : set == QMG_ARR_RBJ_DAGGER ? f32.rbj_dagger_hopping : 0; }
+  };
+  RouteState route_state() const {
+    const RouteState s = {clover, hopping, dagger_clover, dagger_hopping, rbjacobi_hopping, rbjacobi_cinv, rbj_dagger_hopping,
+                          built_rbjacobi, swap_dagger, swap_rbjacobi, swap_rbj_dagger, generated, f32_matrices, f32_bits,
+                          clover32, hopping32, rbj_hopping32, rbj_cinv32, f32, direct, lat->get_nc(), qmg::slab().on};
+    return s;
+  }
+  struct RouteRequest {
+    const void *cl, *ho;       // the fp64 arrays asked for (the single-vector path) ...
+    bool by_set;               // ... or an array set (the typed path; complex<float> vectors come this way only)
+    QMGArraySet set;
+    unsigned pieces;
+    int dtype;                 // of the vectors: QMG_C64 / QMG_C32
+    int mode;                  // RouteMode
+    bool epilogue_wanted;      // QMG_APPLY_EPILOGUE
+  };
+  // links != NONE: a first attempt straight from the links `gauge`; where that entry declines the request, and without one, the stored arrays
+  // `clover` / `hopping` in `storage` -- or, refused, nothing
+  struct Route { bool refused; int links; const void* gauge; const void *clover, *hopping; int storage; };
+
+  static Route resolve_route(const RouteState& s, const RouteRequest& q) {
+    Route r = {false, QMG_LINKS_NONE, 0, 0, 0, QMG_MAT_C64};
+    const bool f = q.dtype == QMG_C32, epi = q.mode == QMG_ROUTE_EPILOGUE;
+    // Refused before anything runs: an epilogue that is switched off or asked on a slab, and a complex<float> apply without the shadow on a slab (nothing
+    // travels for it).  On a whole lattice, and with an epilogue, the same apply is refused only after the links attempt: complex<float> applies from the
+    // links go on working after disable_f32_shadow(), which leaves gauge32 alone.  Both are the behaviour of old and stay.
+    if ((epi && (!q.epilogue_wanted || s.slab_on)) || (q.mode == QMG_ROUTE_SLAB && f && !s.f32.on)) { r.refused = true; return r; }
+    const void* cl = q.by_set ? s.clover_of(q.set) : q.cl;
+    const void* ho = q.by_set ? s.hopping_of(q.set) : q.ho;
+    const bool variant_in = s.swap_dagger || s.swap_rbjacobi || s.swap_rbj_dagger;
+    if (s.direct.on && (!f || s.direct.gauge32)) {
+      if (s.generated && cl != 0 && ho != 0 && cl == s.clover && ho == s.hopping && !variant_in && !s.f32_matrices) {
+        // the ORIGINAL operator (the link copy stands in for the stored arrays only while those ARE the filled operator: clear_stencils / prune_stencils
+        // drop it, and a null pair -- 0 == 0 after a prune -- never qualifies); slabs and epilogues are served from Wilson links only
+        if (s.direct.kind == QMG_DIRECT_WILSON) r.links = QMG_LINKS_WILSON;
+        else if (q.mode == QMG_ROUTE_WHOLE) r.links = QMG_LINKS_DWF;
+      } else if (s.direct.rbj_scale != 0.0 && s.built_rbjacobi && cl == 0 && ho != 0 && ho == s.rbjacobi_hopping_in_use() && !s.swap_dagger && !s.swap_rbj_dagger &&
+                 !(q.pieces & (QMG_P_CLOVER | QMG_P_SHIFT))) {
+        r.links = QMG_LINKS_RBJ_HOPS;   // the hops of the right-block-Jacobi stencil, alone, while that stencil is the built one (swapped in or not)
+      }
+      if (r.links != QMG_LINKS_NONE) r.gauge = f ? s.direct.gauge32 : (const void*)s.direct.gauge;
+    }
+    if (f) {   // the fp32 shadow of the set, or its 16-bit copies (only ORIGINAL has a clover16)
+      const bool half = s.f32.half_on && (q.set == QMG_ARR_ORIGINAL || q.set == QMG_ARR_RBJ_HOPPING);
+      if (!s.f32.on || (epi && half && s.nc == 2)) { r.refused = true; return r; }   // (kernel S, the 16-bit nc = 2 kernel, has no epilogue)
+      r.clover = half ? (q.set == QMG_ARR_ORIGINAL ? s.f32.clover16 : 0) : s.f32_clover_of(q.set);
+      r.hopping = half ? (q.set == QMG_ARR_ORIGINAL ? s.f32.hopping16 : s.f32.rbj_hopping16) : s.f32_hopping_of(q.set);
+      r.storage = half ? QMG_MAT_C16 : QMG_MAT_C32;
+      return r;
+    }
+    r.clover = cl; r.hopping = ho;
+    if (!s.f32_matrices || variant_in) return r;
+    // fp32 / 16-bit STORAGE under fp64 vectors (enable_f32_matrices): the narrow copy that serves (cl, ho), if any -- ORIGINAL, right-block-Jacobi hops, cinv.
+    // (No dagger set matches: its arrays are none of these three.)
+    if (cl == s.clover && ho == s.hopping && (s.clover32 || s.hopping32)) { r.clover = s.clover32; r.hopping = s.hopping32; }
+    else if (cl == 0 && ho != 0 && ho == s.rbjacobi_hopping && s.rbj_hopping32) r.hopping = s.rbj_hopping32;
+    else if (ho == 0 && cl != 0 && cl == s.rbjacobi_cinv && s.rbj_cinv32) r.clover = s.rbj_cinv32;
+    else return r;
+    r.storage = s.f32_bits == 16 ? QMG_MAT_C16 : QMG_MAT_C32;
+    return r;
+  }
+
+  // Runs a route: 1 = served, 0 = refused (nothing launched), -1 = an entry point failed and said so.  nrhs / stride / mask: the batch; an epilogue apply
+  // is system nrhs - 1 alone (mask = its bit); rows: of a slab, 0 = all, 1 = interior, 2 = boundary.
+  int run_route(const Route& r, int mode, qmg_stencil_desc d, int dt, void* lhs, const void* rhs, unsigned pieces, int nrhs, size_t stride, unsigned mask,
+                int rows = 0, const qmg_apply_epilogue* epi = 0) {
+    void* st = qmg::current_stream();
+    const bool slab = mode == QMG_ROUTE_SLAB, f = dt == QMG_C32;
+    // a slab reads the (global, replicated) links from its own row on and the halo rows of rhs; the whole lattice has neither
+    const int gauge_Ly = slab ? d.Ly * qmg::slab().world : d.Ly, y0 = slab ? qmg::slab().rank * d.Ly : 0;
+    const void *lo = slab ? slab_halo_lo : 0, *hi = slab ? slab_halo_hi : 0;
+    const size_t hs = slab ? (size_t)d.Lx * d.nc : 0;
+    if (r.links != QMG_LINKS_NONE) {
+      int rc;
+      const char* what;
+      if (r.links == QMG_LINKS_DWF) {
+        what = "qmg_dwf_apply_direct";
+        rc = qmg_dwf_apply_direct(dt, &d, r.gauge, direct.Ls, direct.m.real(), direct.m.imag(), direct.w, lhs, rhs, pieces, nrhs, stride, mask, st);
+      } else if (r.links == QMG_LINKS_WILSON) {
+        what = epi ? "qmg_wilson_apply_direct_epi" : "qmg_wilson_apply_direct";
+        rc = epi ? qmg_wilson_apply_direct_epi(dt, &d, r.gauge, gauge_Ly, y0, direct.w, lhs, rhs, lo, hi, pieces, nrhs, stride, hs, mask, epi, st)
+                 : qmg_wilson_apply_direct(dt, &d, r.gauge, gauge_Ly, y0, direct.w, lhs, rhs, lo, hi, pieces, nrhs, stride, hs, mask, rows, st);
+      } else {   // D'_eo / D'_oe of the right-block-Jacobi Wilson stencil: the links times one number
+        what = epi ? "qmg_wilson_hops_direct_epi" : "qmg_wilson_hops_direct";
+        rc = epi ? qmg_wilson_hops_direct_epi(dt, &d, r.gauge, gauge_Ly, y0, direct.w, direct.rbj_scale, lhs, rhs, lo, hi, pieces, nrhs, stride, hs, mask, epi, st)
+                 : qmg_wilson_hops_direct(dt, &d, r.gauge, gauge_Ly, y0, direct.w, direct.rbj_scale, lhs, rhs, lo, hi, pieces, nrhs, stride, hs, mask, rows, st);
+      }
+      if (rc == QMG_SUCCESS) return 1;
+      // an entry that does not serve the piece set leaves it to the stored arrays: QMG_ERR_UNSUPPORTED and, except with an epilogue, QMG_ERR_INVALID
+      // (with an epilogue falling back on an error would only repeat it)
+      if (rc != QMG_ERR_UNSUPPORTED && (epi || rc != QMG_ERR_INVALID)) { qmg::ok(rc, what); return -1; }
+    }
+    if (r.refused) {
+      if (!epi) std::cout << "[QMG-ERROR]: fp32 apply without an fp32 shadow (Stencil2D::enable_f32_shadow).\n";
+      return 0;
+    }
+    d.clover = r.clover; d.hopping = r.hopping;
+    const bool c16 = r.storage == QMG_MAT_C16;
+    int rc;
+    const char* what;
+    if (epi) {
+      what = "qmg_stencil_apply_epi_t";
+      rc = qmg_stencil_apply_epi_t(dt, r.storage, &d, lhs, rhs, pieces, stride, nrhs - 1, epi, st);
+      if (rc == QMG_ERR_UNSUPPORTED) return 0;   // a kernel without the epilogue: the caller runs the separate passes
+    } else if (slab) {
+      what = "qmg_stencil_apply_slab";
+      const int word = f ? (c16 ? QMG_C32 | QMG_SLAB_H16 : QMG_C32) : r.storage == QMG_MAT_C64 ? QMG_C64 : QMG_C64 | (c16 ? QMG_SLAB_M16 : QMG_SLAB_M32);
+      rc = qmg_stencil_apply_slab(word, &d, lhs, rhs, lo, hi, pieces, nrhs, stride, hs, mask, rows, st);
+    } else if (c16 && f && d.nc == 2) {
+      what = "qmg_stencil_apply_h16";
+      rc = qmg_stencil_apply_h16(&d, lhs, rhs, pieces, nrhs, stride, mask, st);
+    } else if (c16) {
+      what = "qmg_stencil_apply_mat16_t";
+      rc = qmg_stencil_apply_mat16_t(dt, &d, lhs, rhs, pieces, nrhs, stride, mask, st);
+    } else if (f) {
+      what = "qmg_stencil_apply_t";
+      rc = qmg_stencil_apply_t(QMG_C32, &d, lhs, rhs, pieces, nrhs, stride, mask, st);
+    } else if (r.storage == QMG_MAT_C32) {
+      what = "qmg_stencil_apply_mat32";
+      rc = qmg_stencil_apply_mat32(&d, lhs, rhs, pieces, nrhs, stride, mask, st);
+    } else {   // (one vector too: a batch of one with a full mask is the request qmg_stencil_apply builds)
+      what = "qmg_stencil_apply_batch";
+      rc = qmg_stencil_apply_batch(&d, lhs, rhs, pieces, nrhs, stride, mask, st);
+    }
+    return qmg::ok(rc, what) ? 1 : -1;
   }
 
   Stencil2D(Lattice2D* in_lat, int pieces, complex<double> in_shift = 0.0, complex<double> in_eo_shift = 0.0, complex<double> in_dof_shift = 0.0)
@@ -282,7 +346,6 @@ struct Stencil2D {
     direct.gauge = 0; direct.gauge32 = 0; direct.w = 1.0; direct.on = false; direct.rbj_scale = 0.0;
     direct.kind = QMG_DIRECT_WILSON; direct.Ls = 0; direct.m = 0.0;
     slab_halo_lo = slab_halo_hi = 0;
-    slab_comm_stream = slab_ev_rhs = slab_ev_halo = 0;
     f32.clover16 = f32.hopping16 = f32.rbj_hopping16 = 0; f32.half_on = false;
     built_dagger = false; dagger_clover = dagger_hopping = dagger_twolink = dagger_corner = 0;
     built_rbjacobi = false; rbjacobi_clover = rbjacobi_hopping = rbjacobi_twolink = rbjacobi_corner = rbjacobi_cinv = 0;
@@ -302,7 +365,6 @@ struct Stencil2D {
     drop_direct_links();
     if (slab_halo_lo) deallocate_vector(&slab_halo_lo);
     if (slab_halo_hi) deallocate_vector(&slab_halo_hi);
-    if (slab_comm_stream) { qmg_stream_sync(slab_comm_stream); qmg_event_destroy(slab_ev_rhs); qmg_event_destroy(slab_ev_halo); qmg_stream_destroy(slab_comm_stream); }
     built_dagger = built_rbjacobi = built_rbj_dagger = generated = false;
   }
 
@@ -412,14 +474,6 @@ struct Stencil2D {
     if (rbjacobi_hopping) narrow(&rbj_hopping32, rbjacobi_hopping, (size_t)lat->get_size_hopping_l());
     narrow(&rbj_cinv32, rbjacobi_cinv, (size_t)lat->get_size_cm_l());
   }
-  // the narrow copy that serves (cl, ho) of a launch, if any: ORIGINAL, right-block-Jacobi hops, cinv
-  bool narrow_arrays_for(const void* cl, const void* ho, const void** ncl, const void** nho) const {
-    if (!f32_in_use()) return false;
-    if (cl == clover && ho == hopping && (clover32 || hopping32)) { *ncl = clover32; *nho = hopping32; return true; }
-    if (cl == 0 && ho != 0 && ho == rbjacobi_hopping && rbj_hopping32) { *ncl = 0; *nho = rbj_hopping32; return true; }
-    if (ho == 0 && cl != 0 && cl == rbjacobi_cinv && rbj_cinv32) { *ncl = rbj_cinv32; *nho = 0; return true; }
-    return false;
-  }
   void disable_f32_matrices() {
     if (clover32) { qmg_free(clover32); clover32 = 0; }
     if (hopping32) { qmg_free(hopping32); hopping32 = 0; }
@@ -460,6 +514,13 @@ struct Stencil2D {
     if ((pieces & QMG_PIECE_CORNER) && corner != 0) deallocate_vector(&corner);
     if (clover == 0 || hopping == 0) drop_direct_links();   // the link copy describes clover + hopping together
     if (clover == 0 && hopping == 0 && twolink == 0 && corner == 0) generated = false;
+  }
+
+  // the variants built from the old matrices, when an operator refills clover / hopping (update_links of Wilson2D and Dwf2D)
+  void drop_variant_stencils() {
+    if (built_dagger) { deallocate_vector(&dagger_clover); deallocate_vector(&dagger_hopping); built_dagger = false; }
+    if (built_rbjacobi) { deallocate_vector(&rbjacobi_cinv); deallocate_vector(&rbjacobi_clover); deallocate_vector(&rbjacobi_hopping); built_rbjacobi = false; }
+    if (built_rbj_dagger) { deallocate_vector(&rbj_dagger_cinv); deallocate_vector(&rbj_dagger_clover); deallocate_vector(&rbj_dagger_hopping); built_rbj_dagger = false; }
   }
 
   void try_prune_stencils(int pieces, double tol) {   // :407-431
@@ -546,104 +607,23 @@ struct Stencil2D {
   }
   // lhs = A rhs without a separate zeroing pass (what the C wrappers do, :2571-2576)
   void apply_M_overwrite(complex<double>* lhs, complex<double>* rhs) { launch(QMG_P_ALL | QMG_P_ZERO, lhs, rhs); }
-  // The one launch of the batch layer (include/qmg/batch.hpp): `launch` for <= 16 vectors `stride` apart, active systems only.
-  void launch_batch(unsigned pieces, complex<double>* lhs, complex<double>* rhs, const complex<double>* cl, const complex<double>* ho,
-                    complex<double> s, complex<double> es, complex<double> ds, int nrhs, size_t stride, unsigned mask) {
-    qmg_stencil_desc d;
-    d.Lx = lat->get_dim_mu(0); d.Ly = lat->get_dim_mu(1); d.nc = lat->get_nc();
-    d.clover = cl; d.hopping = ho;
-    d.shift[0] = s.real(); d.shift[1] = s.imag();
-    d.eo_shift[0] = es.real(); d.eo_shift[1] = es.imag();
-    d.dof_shift[0] = ds.real(); d.dof_shift[1] = ds.imag();
-    qmg::ok(qmg_stencil_apply_batch(&d, lhs, rhs, pieces, nrhs, stride, mask, qmg::current_stream()), "qmg_stencil_apply_batch");
-  }
-  const complex<double>* rbjacobi_hopping_in_use() const { return swap_rbjacobi ? hopping : rbjacobi_hopping; }
-
   // The one launch of the batch layer in either storage precision: pieces of the operator built from array set `set`
   // (ORIGINAL: clover + hopping; RBJ_HOPPING: the right-block-Jacobi hopping alone; RBJ_CINV: cinv in the clover slot),
   // applied to the active systems of a batch of complex<T> vectors.  T = float streams the fp32 shadow.
   template <typename T>
   void launch_set_batch(unsigned pieces, complex<T>* lhs, complex<T>* rhs, QMGArraySet set, complex<double> s, complex<double> es, complex<double> ds,
                         int nrhs, size_t stride, unsigned mask) {
-    qmg_stencil_desc d;
-    d.Lx = lat->get_dim_mu(0); d.Ly = lat->get_dim_mu(1); d.nc = lat->get_nc();
-    d.shift[0] = s.real(); d.shift[1] = s.imag();
-    d.eo_shift[0] = es.real(); d.eo_shift[1] = es.imag();
-    d.dof_shift[0] = ds.real(); d.dof_shift[1] = ds.imag();
-    if (qmg::slab().on) {   // slabs: ONE exchange of the batch's halo rows, one launch with them (kernel W / S on nc = 2, kernel B otherwise)
-      const bool f = sizeof(T) == sizeof(float);
-      const int dt = f ? QMG_C32 : QMG_C64;
-      if (f && !f32.on) { std::cout << "[QMG-ERROR]: fp32 apply without an fp32 shadow (Stencil2D::enable_f32_shadow).\n"; return; }
+    const RouteState state = route_state();
+    const int dt = sizeof(T) == sizeof(float) ? QMG_C32 : QMG_C64;
+    const RouteRequest q = {0, 0, true, set, pieces, dt, state.slab_on ? QMG_ROUTE_SLAB : QMG_ROUTE_WHOLE, true};
+    const Route r = resolve_route(state, q);
+    const qmg_stencil_desc d = desc(0, 0, s, es, ds);
+    if (state.slab_on && !r.refused) {   // slabs: ONE exchange of the batch's halo rows, one launch with them (kernel W / S on nc = 2, kernel B otherwise)
       if (nrhs > 16 || !slab_halos()) { std::cout << "[QMG-ERROR]: a slab batch is at most 16 systems\n"; return; }
-      const size_t hs = (size_t)d.Lx * d.nc;
-      void* st = qmg::current_stream();
-      if (!qmg::ok(qmg_halo_exchange_parity(dt, rhs, d.Lx, d.Ly, d.nc, slab_halo_lo, slab_halo_hi, nrhs, stride, hs, halo_parities(pieces), st), "qmg_halo_exchange")) return;
-      if (set == QMG_ARR_ORIGINAL && direct_usable(clover, hopping) && direct.kind == QMG_DIRECT_WILSON && (!f || direct.gauge32)) {
-        const int rc = qmg_wilson_apply_direct(dt, &d, f ? direct.gauge32 : (void*)direct.gauge, d.Ly * qmg::slab().world, qmg::slab().rank * d.Ly, direct.w, lhs, rhs,
-                                               slab_halo_lo, slab_halo_hi, pieces, nrhs, stride, hs, mask, 0, st);
-        if (rc == QMG_SUCCESS) return;
-        if (rc != QMG_ERR_UNSUPPORTED && rc != QMG_ERR_INVALID) { qmg::ok(rc, "qmg_wilson_apply_direct"); return; }
-      }
-      if (set == QMG_ARR_RBJ_HOPPING && rbj_direct_usable(0, rbjacobi_hopping_in_use(), pieces) && (!f || direct.gauge32)) {
-        const int rc = qmg_wilson_hops_direct(dt, &d, f ? direct.gauge32 : (void*)direct.gauge, d.Ly * qmg::slab().world, qmg::slab().rank * d.Ly, direct.w, direct.rbj_scale,
-                                              lhs, rhs, slab_halo_lo, slab_halo_hi, pieces, nrhs, stride, hs, mask, 0, st);
-        if (rc == QMG_SUCCESS) return;
-        if (rc != QMG_ERR_UNSUPPORTED && rc != QMG_ERR_INVALID) { qmg::ok(rc, "qmg_wilson_hops_direct"); return; }
-      }
-      if (f && f32.half_on && set_has_16bit_copy(set)) {   // 16-bit stored matrices (nc = 2), fp32 vectors
-        d.clover = (set == QMG_ARR_ORIGINAL) ? f32.clover16 : 0;
-        d.hopping = (set == QMG_ARR_ORIGINAL) ? f32.hopping16 : f32.rbj_hopping16;
-        qmg::ok(qmg_stencil_apply_slab(QMG_C32 | QMG_SLAB_H16, &d, lhs, rhs, slab_halo_lo, slab_halo_hi, pieces, nrhs, stride, hs, mask, 0, st), "qmg_stencil_apply_slab");
-        return;
-      }
-      int storage = dt;
-      if (f) {
-        d.clover = f32_clover_of(set);
-        d.hopping = f32_hopping_of(set);
-      } else {
-        d.clover = clover_of(set);
-        d.hopping = hopping_of(set);
-        const void *ncl = 0, *nho = 0;
-        if (narrow_arrays_for(d.clover, d.hopping, &ncl, &nho)) { d.clover = ncl; d.hopping = nho; storage |= (f32_bits == 16) ? QMG_SLAB_M16 : QMG_SLAB_M32; }   // (enable_f32_matrices)
-      }
-      qmg::ok(qmg_stencil_apply_slab(storage, &d, lhs, rhs, slab_halo_lo, slab_halo_hi, pieces, nrhs, stride, hs, mask, 0, st), "qmg_stencil_apply_slab");
-      return;
+      if (!qmg::ok(qmg_halo_exchange_parity(dt, rhs, d.Lx, d.Ly, d.nc, slab_halo_lo, slab_halo_hi, nrhs, stride, (size_t)d.Lx * d.nc, halo_parities(pieces), qmg::current_stream()),
+                   "qmg_halo_exchange")) return;
     }
-    if (set == QMG_ARR_ORIGINAL && direct_usable(clover, hopping) && (sizeof(T) == sizeof(double) || direct.gauge32)) {
-      const int rc = direct_apply(sizeof(T) == sizeof(float) ? QMG_C32 : QMG_C64, d, lhs, rhs, pieces, nrhs, stride, mask);
-      if (rc == QMG_SUCCESS) return;
-      if (rc != QMG_ERR_UNSUPPORTED && rc != QMG_ERR_INVALID) { qmg::ok(rc, direct_name()); return; }
-    }
-    if (set == QMG_ARR_RBJ_HOPPING && rbj_direct_usable(0, rbjacobi_hopping_in_use(), pieces) && (sizeof(T) == sizeof(double) || direct.gauge32)) {
-      const int rc = qmg_wilson_hops_direct(sizeof(T) == sizeof(float) ? QMG_C32 : QMG_C64, &d, sizeof(T) == sizeof(float) ? direct.gauge32 : (void*)direct.gauge,
-                                            d.Ly, 0, direct.w, direct.rbj_scale, lhs, rhs, 0, 0, pieces, nrhs, stride, 0, mask, 0, qmg::current_stream());
-      if (rc == QMG_SUCCESS) return;
-      if (rc != QMG_ERR_UNSUPPORTED && rc != QMG_ERR_INVALID) { qmg::ok(rc, "qmg_wilson_hops_direct"); return; }
-    }
-    if (sizeof(T) == sizeof(float)) {
-      if (!f32.on) { std::cout << "[QMG-ERROR]: fp32 apply without an fp32 shadow (Stencil2D::enable_f32_shadow).\n"; return; }
-      if (f32.half_on && set_has_16bit_copy(set)) {   // 16-bit stored matrices, fp32 vectors
-        d.clover = (set == QMG_ARR_ORIGINAL) ? f32.clover16 : 0;
-        d.hopping = (set == QMG_ARR_ORIGINAL) ? f32.hopping16 : f32.rbj_hopping16;
-        if (d.nc == 2) qmg::ok(qmg_stencil_apply_h16(&d, lhs, rhs, pieces, nrhs, stride, mask, qmg::current_stream()), "qmg_stencil_apply_h16");
-        else qmg::ok(qmg_stencil_apply_mat16_t(QMG_C32, &d, lhs, rhs, pieces, nrhs, stride, mask, qmg::current_stream()), "qmg_stencil_apply_mat16_t");
-        return;
-      }
-      d.clover = f32_clover_of(set);
-      d.hopping = f32_hopping_of(set);
-      qmg::ok(qmg_stencil_apply_t(QMG_C32, &d, lhs, rhs, pieces, nrhs, stride, mask, qmg::current_stream()), "qmg_stencil_apply_t");
-      return;
-    }
-    d.clover = clover_of(set);
-    d.hopping = hopping_of(set);
-    const void *ncl = 0, *nho = 0;
-    if (set != QMG_ARR_DAGGER && narrow_arrays_for(d.clover, d.hopping, &ncl, &nho)) {   // fp32 / 16-bit STORAGE of the coarse matrices, fp64 vectors (enable_f32_matrices)
-      d.clover = ncl; d.hopping = nho;
-      if (f32_bits == 16) qmg::ok(qmg_stencil_apply_mat16_t(QMG_C64, &d, lhs, rhs, pieces, nrhs, stride, mask, qmg::current_stream()), "qmg_stencil_apply_mat16_t");
-      else qmg::ok(qmg_stencil_apply_mat32(&d, lhs, rhs, pieces, nrhs, stride, mask, qmg::current_stream()), "qmg_stencil_apply_mat32");
-      return;
-    }
-    qmg::ok(qmg_stencil_apply_batch(&d, lhs, rhs, pieces, nrhs, stride, mask, qmg::current_stream()), "qmg_stencil_apply_batch");
+    run_route(r, q.mode, d, dt, lhs, rhs, pieces, nrhs, stride, mask);
   }
 
   // ONE system (number `system` of a batch `stride` apart) with an apply epilogue (include/qmg_hip.h: qmg_apply_epilogue): the finished site
@@ -654,48 +634,9 @@ struct Stencil2D {
   bool launch_set_epi(unsigned pieces, complex<T>* lhs, complex<T>* rhs, QMGArraySet set, complex<double> s, complex<double> es, complex<double> ds,
                       size_t stride, int system, const qmg_apply_epilogue& epi) {
     static const bool wanted = !(getenv("QMG_APPLY_EPILOGUE") && atoi(getenv("QMG_APPLY_EPILOGUE")) == 0);
-    if (!wanted || qmg::slab().on) return false;
-    const bool f = sizeof(T) == sizeof(float);
-    const int dt = f ? QMG_C32 : QMG_C64;
-    qmg_stencil_desc d;
-    d.Lx = lat->get_dim_mu(0); d.Ly = lat->get_dim_mu(1); d.nc = lat->get_nc();
-    d.clover = 0; d.hopping = 0;
-    d.shift[0] = s.real(); d.shift[1] = s.imag();
-    d.eo_shift[0] = es.real(); d.eo_shift[1] = es.imag();
-    d.dof_shift[0] = ds.real(); d.dof_shift[1] = ds.imag();
-    const int nrhs = system + 1;
-    const unsigned mask = 1u << system;
-    auto served = [](int rc, const char* what) { if (rc == QMG_SUCCESS) return 1; if (rc == QMG_ERR_UNSUPPORTED) return 0; qmg::ok(rc, what); return -1; };
-    if (set == QMG_ARR_ORIGINAL && direct_usable(clover, hopping) && direct.kind == QMG_DIRECT_WILSON && (!f || direct.gauge32)) {
-      const int r = served(qmg_wilson_apply_direct_epi(dt, &d, f ? direct.gauge32 : (void*)direct.gauge, d.Ly, 0, direct.w, lhs, rhs, 0, 0, pieces, nrhs, stride, 0, mask,
-                                                       &epi, qmg::current_stream()), "qmg_wilson_apply_direct_epi");
-      if (r) return true;   // (an error has been reported; falling back would only repeat it)
-    }
-    if (set == QMG_ARR_RBJ_HOPPING && rbj_direct_usable(0, rbjacobi_hopping_in_use(), pieces) && (!f || direct.gauge32)) {
-      const int r = served(qmg_wilson_hops_direct_epi(dt, &d, f ? direct.gauge32 : (void*)direct.gauge, d.Ly, 0, direct.w, direct.rbj_scale, lhs, rhs, 0, 0, pieces, nrhs,
-                                                      stride, 0, mask, &epi, qmg::current_stream()), "qmg_wilson_hops_direct_epi");
-      if (r) return true;
-    }
-    int mat32 = 0;
-    if (f) {
-      const bool half = f32.half_on && set_has_16bit_copy(set);
-      if (!f32.on || (half && d.nc == 2)) return false;   // (kernel S, the 16-bit nc = 2 kernel, has no epilogue)
-      if (half) {
-        d.clover = (set == QMG_ARR_ORIGINAL) ? f32.clover16 : 0;
-        d.hopping = (set == QMG_ARR_ORIGINAL) ? f32.hopping16 : f32.rbj_hopping16;
-        mat32 = 2;
-      } else {
-        d.clover = f32_clover_of(set);
-        d.hopping = f32_hopping_of(set);
-        mat32 = 1;
-      }
-    } else {
-      d.clover = clover_of(set);
-      d.hopping = hopping_of(set);
-      const void *ncl = 0, *nho = 0;
-      if (set != QMG_ARR_DAGGER && narrow_arrays_for(d.clover, d.hopping, &ncl, &nho)) { d.clover = ncl; d.hopping = nho; mat32 = (f32_bits == 16) ? 2 : 1; }
-    }
-    return served(qmg_stencil_apply_epi_t(dt, mat32, &d, lhs, rhs, pieces, stride, system, &epi, qmg::current_stream()), "qmg_stencil_apply_epi_t") != 0;
+    const int dt = sizeof(T) == sizeof(float) ? QMG_C32 : QMG_C64;
+    const RouteRequest q = {0, 0, true, set, pieces, dt, QMG_ROUTE_EPILOGUE, wanted};
+    return run_route(resolve_route(route_state(), q), q.mode, desc(0, 0, s, es, ds), dt, lhs, rhs, pieces, system + 1, stride, 1u << system, 0, &epi) != 0;
   }
 
   // lhs_k = M rhs_k for the active systems of a lock-step batch (<= 16 vectors `stride` apart): one read of the matrices;
