@@ -464,6 +464,30 @@ enum { QMG_SE_APPLY = 0, QMG_SE_MASKED = 1, QMG_SE_H16 = 2, QMG_SE_NORM2 = 3, QM
 int qmg_stencil_plan(int entry, int mat, int vec32, int Lx, int Ly, int nc, unsigned pieces, int n_active, int holes, int inplace,
                      int has_clover, int has_hopping, int epilogue, int slab_rows, int* plan_out, int plan_len);
 
+/* Which kernel serves each pass of a batch vector call (qmg_batch_blas_t ... qmg_batch_mr_update_t): the answer of the one host function
+ * every launcher of those entry points switches on, at the CURRENT value of the tuning knob blas_nt_mb.  Host only, no HIP call.
+ * entry: the entry point (QMG_BE_*); op: the QMG_BOP_* of QMG_BE_BLAS, the QMG_BRED_* of QMG_BE_REDUCE, else 0; n, stride, nrhs, mask: as
+ * the entry point takes them; nj: the vector sets of QMG_BE_MULTI_CAXPY / _GCR_UPDATE / _MULTIDOT, the shifts of QMG_BE_CGM_UPDATE (with
+ * shift_masks[nj]), else 0; flags: QMG_BE_MR_UPDATE 1 x_set | 2 r_out given, QMG_BE_GCR_UPDATE 1 z_next given; aligned16: every pointer
+ * of the call is 16-byte aligned.  Writes 5 ints per pass, in launch order, and -1 into the rest of plan_out (5 * max_passes ints):
+ *   family   QMG_BF_*: 0 success with nothing launched (no active system, n = 0, no vector set; a multi-shift launch none of whose
+ *            shifts is iterated any more), 1 k_bblas, 2 k_bmulti_caxpy_small, 3 k_bmulti_caxpy (vectors of 16 MiB and more per system),
+ *            4 the single-vector qmg_multi_caxpy (ONE complex<double> system of 16 MiB and more), 5 k_bgcr_update, 6 k_bcgm_update,
+ *            7 k_breduce, 8 k_bmultidot, 9 k_bmultidot<2> + k_bmr_final, 10 k_bmr_update
+ *   W        elements per 16-byte access: 2 for complex<float> with aligned pointers, even n and (nrhs > 1) even stride, else 1
+ *   nt       read-only operands are read non-temporally (the active systems add up to blas_nt_mb MiB)
+ *   J        what the pass takes: vector sets (multi-axpy 1..8, GCR update 0..8), dots per pass over y (multidot 8 / 4 / 2 / 1; MR dots 2),
+ *            shifts (multi-shift update 1..8)
+ *   variant  the op (families 1, 7); the flags (families 5, 10); family 6: the largest number of shifts of the launch that one system
+ *            still iterates
+ * (a member the family does not use is 0).  QMG_ERR_INVALID: a request the entry point rejects, or more passes than max_passes. */
+enum { QMG_BE_BLAS = 0, QMG_BE_MULTI_CAXPY = 1, QMG_BE_GCR_UPDATE = 2, QMG_BE_CGM_UPDATE = 3, QMG_BE_REDUCE = 4, QMG_BE_MULTIDOT = 5,
+       QMG_BE_MR_DOTS = 6, QMG_BE_MR_UPDATE = 7 };
+enum { QMG_BF_NOTHING = 0, QMG_BF_BLAS = 1, QMG_BF_MAXPY_SMALL = 2, QMG_BF_MAXPY_LONG = 3, QMG_BF_MAXPY_SINGLE = 4, QMG_BF_GCR = 5,
+       QMG_BF_CGM = 6, QMG_BF_REDUCE = 7, QMG_BF_MULTIDOT = 8, QMG_BF_MR_DOTS = 9, QMG_BF_MR_UPDATE = 10 };
+int qmg_batch_plan(int entry, int dtype, int op, size_t n, size_t stride, int nrhs, unsigned mask, int nj, const unsigned* shift_masks,
+                   int flags, int aligned16, int* plan_out, int max_passes);
+
 /* 16-bit storage of the fine operator (SURVEY 8f-4 "16-bit-storage smoother"; nc = 2 only): d->clover / d->hopping point to
  * complex<half> copies (qmg_convert_to_c16), vectors are complex<float>, arithmetic fp32: 112 B/site instead of 192.  The
  * rounding (2^-11) perturbs the OPERATOR, so this is for applies inside a preconditioner only. */

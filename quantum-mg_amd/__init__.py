@@ -54,7 +54,7 @@ ABI_SYMBOLS = [
     "qmg_u1_hot_gauge", "qmg_u1_gauss_gauge", "qmg_u1_random_trans", "qmg_u1_gauge_transform", "qmg_u1_ape_smear", "qmg_u1_instanton", "qmg_u1_noncompact_instanton",
     "qmg_hmc_momentum_update", "qmg_hmc_momentum_update_poles", "qmg_hmc_momentum_update_staggered", "qmg_hmc_link_update", "qmg_hmc_momentum_refresh", "qmg_hmc_stream_seed",
     "qmg_u1_flow_stage", "qmg_u1_flow", "qmg_u1_wilson_loops", "qmg_u1_polyakov",
-    "qmg_dwf_fill", "qmg_dwf_apply_direct", "qmg_dwf_plan",
+    "qmg_dwf_fill", "qmg_dwf_apply_direct", "qmg_dwf_plan", "qmg_batch_plan",
 ]
 
 
@@ -667,6 +667,24 @@ def stencil_plan(entry, mat, vec32, dims, pieces, n_active, holes=False, inplace
     check(lib().qmg_stencil_plan(entry, mat, int(vec32), *dims, C.c_uint(pieces), n_active, int(holes), int(inplace), int(clover), int(hopping), epilogue, slab_rows,
                                  out, n), "qmg_stencil_plan")
     return [tuple(out[STENCIL_PLAN_INTS * p:STENCIL_PLAN_INTS * (p + 1)]) for p in range(max_passes) if out[STENCIL_PLAN_INTS * p] >= 0]
+
+
+# entry points, kernel families and variant bits of qmg_batch_plan (include/qmg_hip.h)
+BE_BLAS, BE_MULTI_CAXPY, BE_GCR_UPDATE, BE_CGM_UPDATE, BE_REDUCE, BE_MULTIDOT, BE_MR_DOTS, BE_MR_UPDATE = range(8)
+BF_NOTHING, BF_BLAS, BF_MAXPY_SMALL, BF_MAXPY_LONG, BF_MAXPY_SINGLE, BF_GCR, BF_CGM, BF_REDUCE, BF_MULTIDOT, BF_MR_DOTS, BF_MR_UPDATE = range(11)
+BPV_XSET, BPV_ROUT, BPV_ZNEXT = 1, 2, 1
+BATCH_PLAN_INTS = 5
+BATCH_LONG_BYTES = 16 << 20   # BATCH_LONG_BYTES of csrc/qmg_batch_plan.h: a vector of this many bytes per system is a long vector
+
+
+def batch_plan(entry, dtype, n, stride, nrhs, mask, op=0, nj=0, shift_masks=None, flags=0, aligned16=True, max_passes=8):
+    """The kernel plan of a batch vector call at the current blas_nt_mb (qmg_batch_plan; host only): a list with one tuple
+    (family, W, nt, J, variant) per pass, in launch order."""
+    out = (C.c_int * (BATCH_PLAN_INTS * max_passes))()
+    sm = (C.c_uint * max(len(shift_masks), 1))(*shift_masks) if shift_masks is not None else None
+    check(lib().qmg_batch_plan(entry, dtype, op, C.c_size_t(n), C.c_size_t(stride), nrhs, C.c_uint(mask), nj, sm, flags, int(aligned16), out, max_passes),
+          "qmg_batch_plan")
+    return [tuple(out[BATCH_PLAN_INTS * p:BATCH_PLAN_INTS * (p + 1)]) for p in range(max_passes) if out[BATCH_PLAN_INTS * p] >= 0]
 
 
 def prolong_batch_nv32(null32, nvec, coarse, fine, fdims, cdims, nrhs, cstride, fstride, mask):

@@ -16,13 +16,14 @@
 #include <time.h>
 
 #include <initializer_list>
+#include <vector>
 
+#include "qmg_batch_plan.h"
 #include "qmg_common.h"
 
 namespace qmg {
 
 constexpr int BRED_BLOCKS = 1024;    // partials per reduction per system (= RED_BLOCKS of qmg_blas.hip)
-constexpr int BDOT_MAX = 32;         // vectors per batched multidot / multi_caxpy call
 
 // ---------------- element-wise ----------------
 // T = storage scalar (double | float), W = elements per 16-byte access (1 for double; 2 for float when the arrays are
@@ -30,14 +31,11 @@ constexpr int BDOT_MAX = 32;         // vectors per batched multidot / multi_cax
 struct BatchCoef { cplx a[BATCH_MAX], b[BATCH_MAX]; };   // indexed by system id
 
 // read-only operands of a batch whose active systems add up to `blas_nt_mb` MiB or more are streamed non-temporally (as in qmg_blas.hip:
-// +8-10 % on vectors the caches cannot hold anyway); the in/out operand never is.  A run-time, launch-uniform choice.
+// +8-10 % on vectors the caches cannot hold anyway); the in/out operand never is.  A run-time, launch-uniform choice (the plan's `nt`).
 template <typename T, int W>
 __device__ __forceinline__ void ldb(const void* p, long i, cplx (&v)[W], bool nt) {
   if (nt) ldc_pack_nt<T, W>(p, i, v);
   else ldc_pack<T, W>(p, i, v);
-}
-static inline int batch_nt(const BatchIdx& bi, size_t n, int dtype) {
-  return g_blas_nt_bytes > 0 && (long)((size_t)bi.n * n * (dtype == QMG_C32 ? 8 : 16)) >= g_blas_nt_bytes;
 }
 
 template <int OP, typename T, int W>
@@ -68,8 +66,7 @@ __global__ __launch_bounds__(BLOCK) void k_bblas(void* __restrict__ z_, const vo
   }
 }
 
-// y_k += sum_j a[j][k] x_j,k for up to 8 vector sets per launch (coefficients travel as kernel arguments)
-constexpr int BMAXPY_J = 8;
+// y_k += sum_j a[j][k] x_j,k for up to BMAXPY_J = 8 vector sets per launch (coefficients travel as kernel arguments)
 struct BatchMultiAxpy { const void* x[BMAXPY_J]; cplx a[BMAXPY_J][BATCH_MAX]; };
 // The NJ vector sets' loads are all requested (in storage form) before the first is widened and used: with a loop over nj and a branch on the
 // coefficient around each load, every load waited for the one before it.  A zero coefficient means "this system does not use vector
@@ -186,8 +183,6 @@ __global__ __launch_bounds__(BLOCK) void k_bgcr_update(void* __restrict__ w_, co
 // part kept, because dropping it changes the sign of a zero result -- so the same bits; the kernel is bound by its loads (64 bytes per shift and
 // element against 12 FMAs).  A (system, shift) pair that has converged is not in the system's list: neither read nor written.  Shifts are
 // taken CGM_CHUNK at a time, all 2 CGM_CHUNK loads of a chunk requested in storage form before the first is used (as bmulti_caxpy_run: 8 loads in flight).
-constexpr int CGM_J = 8;        // shifts per launch (the coefficient tables travel as kernel arguments)
-constexpr int CGM_CHUNK = 4;    // shifts per staged chunk
 struct BatchCgm {
   void* x[CGM_J];
   void* p[CGM_J];
@@ -523,13 +518,27 @@ int mr_epilogue_finish(const unsigned char* ids, int n, long npart, hipStream_t 
   return QMG_SUCCESS;
 }
 
-// which access width the arrays of a call allow: 2 complex<float> per 16-byte access needs 16-byte aligned bases, even
-// element counts and even strides; complex<double> is always one element per access
-static int pack_width(int dtype, size_t n, size_t stride, int nrhs, std::initializer_list<const void*> ptrs) {
-  if (dtype != QMG_C32) return 1;
-  if ((n & 1) || (nrhs > 1 && (stride & 1))) return 1;
-  for (const void* p : ptrs) if (p && !aligned16(p)) return 1;
-  return 2;
+// What batch_plan (qmg_batch_plan.h) reads of a call, at the current "blas_nt_mb".  Every launcher below asks the plan and switches on its answer.
+static bool all_aligned16(std::initializer_list<const void*> ptrs) {
+  for (const void* p : ptrs) if (p && !aligned16(p)) return false;
+  return true;
+}
+static bool all_aligned16(const void* const* ptrs, int first, int count) {
+  for (int j = first; j < first + count; j++) if (ptrs[j] && !aligned16(ptrs[j])) return false;
+  return true;
+}
+static BatchPlanRequest batch_request(int entry, int dtype, size_t n, size_t stride, int nrhs, unsigned mask, bool aligned) {
+  BatchPlanRequest r = {};
+  r.entry = entry; r.dtype = dtype; r.n = n; r.stride = stride; r.nrhs = nrhs; r.mask = mask;
+  r.aligned = aligned;
+  r.nt_bytes = g_blas_nt_bytes;
+  return r;
+}
+// the systems of a launch and its non-temporal bit, as the kernels take them
+static BatchIdx batch_idx(const BatchPass& pl, int nrhs) {
+  BatchIdx bi = expand_mask(pl.systems, nrhs);
+  bi.nt = pl.nt;
+  return bi;
 }
 
 }  // namespace qmg
@@ -552,19 +561,21 @@ int qmg_batch_blas_t(int dtype, int op, const double* a, const double* b, const 
   if ((op == QMG_BOP_COPY || op == QMG_BOP_CAXPY || op == QMG_BOP_CXPY || op == QMG_BOP_CAXPBYZ) && !x && n) return QMG_ERR_INVALID;
   if (op == QMG_BOP_CAXPBYZ && ((!y && n) || !b)) return QMG_ERR_INVALID;
   if ((op == QMG_BOP_CAX || op == QMG_BOP_CAXPY || op == QMG_BOP_CAXPBYZ) && !a) return QMG_ERR_INVALID;
-  BatchIdx bi = expand_mask(mask, nrhs);
-  if (bi.n == 0 || n == 0) return QMG_SUCCESS;
-  bi.nt = batch_nt(bi, n, dtype);
+  BatchPlanRequest rq = batch_request(QMG_BE_BLAS, dtype, n, stride, nrhs, mask, all_aligned16({x, y, z}));
+  rq.op = op;
+  const BatchPass pl = batch_plan(rq);
+  if (pl.family == BF_NOTHING) return QMG_SUCCESS;
+  const BatchIdx bi = batch_idx(pl, nrhs);
   BatchCoef c;
   for (int k = 0; k < BATCH_MAX; k++) {
     c.a[k] = (a && k < nrhs) ? make_double2(a[2 * k], a[2 * k + 1]) : make_double2(0.0, 0.0);
     c.b[k] = (b && k < nrhs) ? make_double2(b[2 * k], b[2 * k + 1]) : make_double2(0.0, 0.0);
   }
-  const int W = pack_width(dtype, n, stride, nrhs, {x, y, z});
+  const int W = pl.W;
   dim3 grid(grid_1d(n / W), (unsigned)bi.n);
   hipStream_t st = as_stream(stream);
 #define QMG_K(T, WW)                                                                                                        \
-  switch (op) {                                                                                                             \
+  switch (pl.variant) {                                                                                                             \
     case QMG_BOP_ZERO: k_bblas<QMG_BOP_ZERO, T, WW><<<grid, BLOCK, 0, st>>>(z, nullptr, nullptr, c, bi, (long)n, (long)stride); break;   \
     case QMG_BOP_COPY: k_bblas<QMG_BOP_COPY, T, WW><<<grid, BLOCK, 0, st>>>(z, x, nullptr, c, bi, (long)n, (long)stride); break;        \
     case QMG_BOP_CAX: k_bblas<QMG_BOP_CAX, T, WW><<<grid, BLOCK, 0, st>>>(z, nullptr, nullptr, c, bi, (long)n, (long)stride); break;    \
@@ -586,17 +597,31 @@ int qmg_batch_blas(int op, const double* a, const double* b, const void* x, cons
 int qmg_batch_multi_caxpy_t(int dtype, const double* coeffs, const void* const* xs, int nj, void* y, size_t n, int nrhs, size_t stride, unsigned mask,
                             void* stream) {
   if (!valid_dtype(dtype) || nrhs < 1 || nrhs > BATCH_MAX || nj < 0 || (nj > 0 && (!coeffs || !xs)) || (!y && n)) return QMG_ERR_INVALID;
-  BatchIdx bi = expand_mask(mask, nrhs);
-  if (bi.n == 0 || n == 0 || nj == 0) return QMG_SUCCESS;
-  // one fp64 system of 16 MB and more (a single outer solve on the fine lattice): the single-vector kernel, which takes up to 32 vector sets per
+  BatchPlanRequest rq = batch_request(QMG_BE_MULTI_CAXPY, dtype, n, stride, nrhs, mask, all_aligned16({y}) && all_aligned16(xs, 0, nj));
+  rq.nj = nj;
+  BatchPass pl = batch_plan(rq);
+  if (pl.family == BF_NOTHING) return QMG_SUCCESS;
+  // one fp64 system on long vectors (a single outer solve on the fine lattice): the single-vector kernel, which takes up to 32 vector sets per
   // pass over y instead of 8 -- the same sums in the same order
-  if (dtype == QMG_C64 && nrhs == 1 && n * 16 >= ((size_t)16 << 20)) return qmg_multi_caxpy(coeffs, xs, nj, y, n, stream);
-  bi.nt = batch_nt(bi, n, dtype);
-  int W = pack_width(dtype, n, stride, nrhs, {y});
-  for (int j = 0; j < nj; j++) if (!xs[j]) return QMG_ERR_INVALID; else if (dtype == QMG_C32 && !aligned16(xs[j])) W = 1;
+  // -- on the vector sets whose coefficient is not zero, in their order: a zero coefficient means "not read" here as in the batch kernels, and
+  // the single-vector kernel multiplies whatever it is given (0 * nan = nan)
+  if (pl.family == BF_MAXPY_SINGLE) {
+    std::vector<double> cf;
+    std::vector<const void*> used;
+    for (int j = 0; j < nj; j++) {
+      if (!xs[j]) return QMG_ERR_INVALID;
+      if (coeffs[2 * j] == 0.0 && coeffs[2 * j + 1] == 0.0) continue;
+      cf.push_back(coeffs[2 * j]); cf.push_back(coeffs[2 * j + 1]);
+      used.push_back(xs[j]);
+    }
+    return qmg_multi_caxpy(cf.data(), used.data(), (int)used.size(), y, n, stream);
+  }
+  for (int j = 0; j < nj; j++) if (!xs[j]) return QMG_ERR_INVALID;
+  const BatchIdx bi = batch_idx(pl, nrhs);
+  const int W = pl.W;
   dim3 grid(grid_1d(n / W), (unsigned)bi.n);
-  for (int j0 = 0; j0 < nj; j0 += BMAXPY_J) {
-    const int jj = (nj - j0 < BMAXPY_J) ? nj - j0 : BMAXPY_J;
+  for (;; pl = batch_plan(rq, pl.next)) {
+    const int j0 = pl.at, jj = pl.J;
     BatchMultiAxpy m;
     for (int j = 0; j < BMAXPY_J; j++) {
       m.x[j] = (j < jj) ? xs[j0 + j] : nullptr;
@@ -604,14 +629,14 @@ int qmg_batch_multi_caxpy_t(int dtype, const double* coeffs, const void* const* 
         m.a[j][k] = (j < jj && k < nrhs) ? make_double2(coeffs[((size_t)(j0 + j) * nrhs + k) * 2], coeffs[((size_t)(j0 + j) * nrhs + k) * 2 + 1])
                                          : make_double2(0.0, 0.0);
     }
-    // vectors of 16 MB and more per system: all loads of a chunk in flight (same-box A/B, C5 shape: the outer flexible GCR's 4096^2 updates 4 % of the solve faster;
-    // the coarse levels' few-microsecond launches 1 % slower with it, hence the threshold)
-    const bool big = n * (dtype == QMG_C32 ? 8 : 16) >= ((size_t)16 << 20);
+    // long vectors: all loads of a chunk in flight (BATCH_LONG_BYTES, qmg_batch_plan.h)
+    const bool big = pl.family == BF_MAXPY_LONG;
 #define QMG_K(T, WW) if (big) k_bmulti_caxpy<T, WW><<<grid, BLOCK, 0, as_stream(stream)>>>(y, m, jj, bi, (long)n, (long)stride); \
                      else k_bmulti_caxpy_small<T, WW><<<grid, BLOCK, 0, as_stream(stream)>>>(y, m, jj, bi, (long)n, (long)stride)
     QMG_DISPATCH_TW(dtype, W, QMG_K);
 #undef QMG_K
     QMG_LAUNCH_CHECK();
+    if (pl.next < 0) break;
   }
   return QMG_SUCCESS;
 }
@@ -624,21 +649,23 @@ int qmg_batch_gcr_update_t(int dtype, const double* coeffs, const void* const* w
                            size_t stride, unsigned mask, void* stream) {
   if (!valid_dtype(dtype) || nrhs < 1 || nrhs > BATCH_MAX || nj < 0 || (nj > 0 && (!coeffs || !ws)) || !a || ((!w || !r) && n)) return QMG_ERR_INVALID;
   if (w == r || (z_next && (z_next == w || z_next == r))) return QMG_ERR_INVALID;
-  BatchIdx bi = expand_mask(mask, nrhs);
-  if (bi.n == 0 || n == 0) return QMG_SUCCESS;
-  // all but the last chunk of 8 vector sets: the plain multi-axpy.  Vectors of 16 MB and more per system (an outer solve on the fine lattice): every chunk
-  // through it -- its long-vector form keeps a chunk's loads in flight, which is worth more there than the saved launch (C5 shape: 2 % of the solve)
-  const bool big = n * (dtype == QMG_C32 ? 8 : 16) >= ((size_t)16 << 20);
-  const int lead = big ? nj : (nj > BMAXPY_J) ? ((nj - 1) / BMAXPY_J) * BMAXPY_J : 0;
+  BatchPlanRequest rq = batch_request(QMG_BE_GCR_UPDATE, dtype, n, stride, nrhs, mask, true);
+  rq.nj = nj;
+  rq.flags = z_next ? BPV_ZNEXT : 0;
+  if (batch_plan(rq).family == BF_NOTHING) return QMG_SUCCESS;
+  // all but the last chunk of 8 vector sets: the plain multi-axpy.  Long vectors (an outer solve on the fine lattice): every chunk through it -- its
+  // long-vector form keeps a chunk's loads in flight, which is worth more there than the saved launch (C5 shape: 2 % of the solve)
+  const int lead = batch_gcr_lead(rq);
   if (lead > 0) { const int rc = qmg_batch_multi_caxpy_t(dtype, coeffs, ws, lead, w, n, nrhs, stride, mask, stream); if (rc) return rc; }
-  bi.nt = batch_nt(bi, n, dtype);
-  int W = pack_width(dtype, n, stride, nrhs, {w, r, z_next});
   const int jj = nj - lead;
+  rq.aligned = all_aligned16({w, r, z_next}) && (jj == 0 || all_aligned16(ws, lead, jj));   // (the pointers this launch reads)
+  const BatchPass pl = batch_plan(rq, lead);
+  const BatchIdx bi = batch_idx(pl, nrhs);
+  const int W = pl.W;
   BatchMultiAxpy m;
   for (int j = 0; j < BMAXPY_J; j++) {
     m.x[j] = (j < jj) ? ws[lead + j] : nullptr;
     if (j < jj && !ws[lead + j]) return QMG_ERR_INVALID;
-    if (j < jj && dtype == QMG_C32 && !aligned16(ws[lead + j])) W = 1;
     for (int k = 0; k < BATCH_MAX; k++)
       m.a[j][k] = (j < jj && k < nrhs) ? make_double2(coeffs[((size_t)(lead + j) * nrhs + k) * 2], coeffs[((size_t)(lead + j) * nrhs + k) * 2 + 1]) : make_double2(0.0, 0.0);
   }
@@ -662,31 +689,33 @@ int qmg_batch_cgm_update_t(int dtype, const void* const* xs, const void* const* 
     for (int t = 0; t < s; t++) if (n && (xs[s] == xs[t] || ps[s] == ps[t] || xs[s] == ps[t] || ps[s] == xs[t])) return QMG_ERR_INVALID;
   }
   if (n == 0) return QMG_SUCCESS;
-  int W = pack_width(dtype, n, stride, nrhs, {r});
-  for (int s = 0; s < ns; s++) if (dtype == QMG_C32 && (!aligned16(xs[s]) || !aligned16(ps[s]))) W = 1;
-  for (int s0 = 0; s0 < ns; s0 += CGM_J) {
-    const int sj = (ns - s0 < CGM_J) ? ns - s0 : CGM_J;
+  BatchPlanRequest rq = batch_request(QMG_BE_CGM_UPDATE, dtype, n, stride, nrhs, mask, all_aligned16({r}) && all_aligned16(xs, 0, ns) && all_aligned16(ps, 0, ns));
+  rq.nj = ns;
+  rq.shift_masks = shift_masks;
+  for (BatchPass pl = batch_plan(rq);; pl = batch_plan(rq, pl.next)) {
+    if (pl.family == BF_NOTHING) {   // a launch none of whose shifts is iterated any more
+      if (pl.next < 0) break;
+      continue;
+    }
+    const int s0 = pl.at, sj = pl.J, W = pl.W;
     BatchCgm m;
     memset(&m, 0, sizeof(m));
-    unsigned any = 0;
     for (int j = 0; j < sj; j++) {
       m.x[j] = const_cast<void*>(xs[s0 + j]);
       m.p[j] = const_cast<void*>(ps[s0 + j]);
       const unsigned act = mask & shift_masks[s0 + j];
-      any |= act;
       for (int k = 0; k < nrhs; k++) {
         m.a[j][k] = a[(size_t)(s0 + j) * nrhs + k]; m.z[j][k] = z[(size_t)(s0 + j) * nrhs + k]; m.c[j][k] = c[(size_t)(s0 + j) * nrhs + k];
         if ((act >> k) & 1u) m.idx[k][m.na[k]++] = (unsigned char)j;
       }
     }
-    BatchIdx bi = expand_mask(any, nrhs);   // a system none of whose shifts is iterated any more launches no block
-    if (bi.n == 0) continue;
-    bi.nt = batch_nt(bi, n, dtype);
+    const BatchIdx bi = batch_idx(pl, nrhs);   // a system none of whose shifts is iterated any more launches no block
     dim3 grid(grid_1d(n / W), (unsigned)bi.n);
 #define QMG_K(T, WW) k_bcgm_update<T, WW><<<grid, BLOCK, 0, as_stream(stream)>>>(m, r, bi, (long)n, (long)stride)
     QMG_DISPATCH_TW(dtype, W, QMG_K);
 #undef QMG_K
     QMG_LAUNCH_CHECK();
+    if (pl.next < 0) break;
   }
   return QMG_SUCCESS;
 }
@@ -696,14 +725,16 @@ int qmg_batch_reduce_t(int dtype, int op, const void* x, const void* y, size_t n
   if (!valid_dtype(dtype) || nrhs < 1 || nrhs > BATCH_MAX || !x || !out_host) return QMG_ERR_INVALID;
   if (op < QMG_BRED_NORM2 || op > QMG_BRED_DIFFNORM2) return QMG_ERR_INVALID;
   if (op != QMG_BRED_NORM2 && !y) return QMG_ERR_INVALID;
-  BatchIdx bi = expand_mask(mask, nrhs);
-  if (bi.n == 0) return QMG_SUCCESS;
-  bi.nt = batch_nt(bi, n, dtype);
+  BatchPlanRequest rq = batch_request(QMG_BE_REDUCE, dtype, n, stride, nrhs, mask, all_aligned16({x, y}));
+  rq.op = op;
+  const BatchPass pl = batch_plan(rq);
+  if (pl.family == BF_NOTHING) return QMG_SUCCESS;
+  const BatchIdx bi = batch_idx(pl, nrhs);
   BatchWorkspace* ws;
   int rc = get_bws(&ws);
   if (rc) return rc;
   hipStream_t st = as_stream(stream);
-  const int W = pack_width(dtype, n, stride, nrhs, {x, y});
+  const int W = pl.W;
   const unsigned g = bred_grid((long)(n / W));
   dim3 grid(g, (unsigned)bi.n);
 #define QMG_K(T, WW)                                                                                                                      \
@@ -738,26 +769,25 @@ int qmg_batch_reduce(int op, const void* x, const void* y, size_t n, int nrhs, s
 int qmg_batch_multidot_t(int dtype, const void* const* xs, int nj, const void* y, size_t n, int nrhs, size_t stride, unsigned mask, double* out_host,
                          void* stream) {
   if (!valid_dtype(dtype) || nrhs < 1 || nrhs > BATCH_MAX || nj < 1 || nj > BDOT_MAX || !xs || !y || !out_host) return QMG_ERR_INVALID;
-  BatchIdx bi = expand_mask(mask, nrhs);
-  if (bi.n == 0) return QMG_SUCCESS;
-  bi.nt = batch_nt(bi, n, dtype);
+  BatchPlanRequest rq = batch_request(QMG_BE_MULTIDOT, dtype, n, stride, nrhs, mask, all_aligned16({y}) && all_aligned16(xs, 0, nj));
+  rq.nj = nj;
+  BatchPass pl = batch_plan(rq);
+  if (pl.family == BF_NOTHING) return QMG_SUCCESS;
+  const BatchIdx bi = batch_idx(pl, nrhs);
   BatchWorkspace* ws;
   int rc = get_bws(&ws);
   if (rc) return rc;
   hipStream_t st = as_stream(stream);
   BatchPtrs p;
-  int W = pack_width(dtype, n, stride, nrhs, {y});
+  const int W = pl.W;
   for (int j = 0; j < BDOT_MAX; j++) {
     p.x[j] = (j < nj) ? xs[j] : nullptr;
     if (j < nj && !xs[j]) return QMG_ERR_INVALID;
-    if (j < nj && dtype == QMG_C32 && !aligned16(xs[j])) W = 1;
   }
   const unsigned g = bred_grid((long)(n / W));
   dim3 grid(g, (unsigned)bi.n);
-  int j0 = 0;
-  while (j0 < nj) {   // same 8/4/2/1 chunking as qmg_multidot
-    const int left = nj - j0;
-    const int kt = left >= 8 ? 8 : left >= 4 ? 4 : left >= 2 ? 2 : 1;
+  for (;; pl = batch_plan(rq, pl.next)) {   // same 8/4/2/1 chunking as qmg_multidot
+    const int j0 = pl.at, kt = pl.J;
 #define QMG_K(T, WW)                                                                                                  \
     if (kt == 8) k_bmultidot<8, T, WW><<<grid, BLOCK, 0, st>>>(p, j0, y, (long)n, (long)stride, bi, ws->partials, nj);   \
     else if (kt == 4) k_bmultidot<4, T, WW><<<grid, BLOCK, 0, st>>>(p, j0, y, (long)n, (long)stride, bi, ws->partials, nj);   \
@@ -765,8 +795,8 @@ int qmg_batch_multidot_t(int dtype, const void* const* xs, int nj, const void* y
     else k_bmultidot<1, T, WW><<<grid, BLOCK, 0, st>>>(p, j0, y, (long)n, (long)stride, bi, ws->partials, nj)
     QMG_DISPATCH_TW(dtype, W, QMG_K);
 #undef QMG_K
-    j0 += kt;
     QMG_LAUNCH_CHECK();
+    if (pl.next < 0) break;
   }
   const bool dist = dist_reductions_on();
   const bool flagged = !dist && spin_results(ws);
@@ -795,9 +825,9 @@ int qmg_batch_multidot(const void* const* xs, int nj, const void* y, size_t n, i
 // reductions).  Nothing comes back to the host; nothing synchronises.
 int qmg_batch_mr_dots_t(int dtype, const void* r, const void* p, size_t n, int nrhs, size_t stride, unsigned mask, void* stream) {
   if (!valid_dtype(dtype) || nrhs < 1 || nrhs > BATCH_MAX || !r || !p) return QMG_ERR_INVALID;
-  BatchIdx bi = expand_mask(mask, nrhs);
-  if (bi.n == 0) return QMG_SUCCESS;
-  bi.nt = batch_nt(bi, n, dtype);
+  const BatchPass pl = batch_plan(batch_request(QMG_BE_MR_DOTS, dtype, n, stride, nrhs, mask, all_aligned16({r, p})));
+  if (pl.family == BF_NOTHING) return QMG_SUCCESS;
+  const BatchIdx bi = batch_idx(pl, nrhs);
   BatchWorkspace* ws;
   int rc = get_bws(&ws);
   if (rc) return rc;
@@ -805,7 +835,7 @@ int qmg_batch_mr_dots_t(int dtype, const void* r, const void* p, size_t n, int n
   BatchPtrs ptr;
   for (int j = 0; j < BDOT_MAX; j++) ptr.x[j] = nullptr;
   ptr.x[0] = r; ptr.x[1] = p;
-  int W = pack_width(dtype, n, stride, nrhs, {r, p});
+  const int W = pl.W;
   const unsigned g = bred_grid((long)(n / W));
   dim3 grid(g, (unsigned)bi.n);
 #define QMG_K(T, WW) k_bmultidot<2, T, WW><<<grid, BLOCK, 0, st>>>(ptr, 0, p, (long)n, (long)stride, bi, ws->partials, 2)
@@ -827,17 +857,19 @@ int qmg_batch_mr_dots_t(int dtype, const void* r, const void* p, size_t n, int n
 int qmg_batch_mr_update_t(int dtype, double omega, void* x, const void* r_in, void* r_out, const void* p, int x_set, size_t n, int nrhs, size_t stride,
                           unsigned mask, void* stream) {
   if (!valid_dtype(dtype) || nrhs < 1 || nrhs > BATCH_MAX || !x || !r_in || (r_out && !p)) return QMG_ERR_INVALID;
-  BatchIdx bi = expand_mask(mask, nrhs);
-  if (bi.n == 0 || n == 0) return QMG_SUCCESS;
-  bi.nt = batch_nt(bi, n, dtype);
+  BatchPlanRequest rq = batch_request(QMG_BE_MR_UPDATE, dtype, n, stride, nrhs, mask, all_aligned16({x, r_in, r_out, p}));
+  rq.flags = (x_set ? BPV_XSET : 0) | (r_out ? BPV_ROUT : 0);
+  const BatchPass pl = batch_plan(rq);
+  if (pl.family == BF_NOTHING) return QMG_SUCCESS;
+  const BatchIdx bi = batch_idx(pl, nrhs);
   BatchWorkspace* ws;
   int rc = get_bws(&ws);
   if (rc) return rc;
-  const int W = pack_width(dtype, n, stride, nrhs, {x, r_in, r_out, p});
+  const int W = pl.W;
   dim3 grid(grid_1d(n / W), (unsigned)bi.n);
   hipStream_t st = as_stream(stream);
 #define QMG_K(T, WW)                                                                                                               \
-  if (x_set) k_bmr_update<T, WW, true><<<grid, BLOCK, 0, st>>>(x, r_in, r_out, p, ws->mr, omega, bi, (long)n, (long)stride);        \
+  if (pl.variant & BPV_XSET) k_bmr_update<T, WW, true><<<grid, BLOCK, 0, st>>>(x, r_in, r_out, p, ws->mr, omega, bi, (long)n, (long)stride);        \
   else k_bmr_update<T, WW, false><<<grid, BLOCK, 0, st>>>(x, r_in, r_out, p, ws->mr, omega, bi, (long)n, (long)stride)
   QMG_DISPATCH_TW(dtype, W, QMG_K);
 #undef QMG_K
@@ -853,6 +885,36 @@ int qmg_batch_mr_read_dots(double* out_host, int nrhs, void* stream) {
   if (rc) return rc;
   QMG_HIP_CHECK(hipMemcpyAsync(out_host, ws->mr, sizeof(double) * 4 * nrhs, hipMemcpyDeviceToHost, as_stream(stream)));
   QMG_HIP_CHECK(hipStreamSynchronize(as_stream(stream)));
+  return QMG_SUCCESS;
+}
+
+// The plan of a call (include/qmg_hip.h): the entry point's own argument checks, then what batch_plan -- the function every launcher above switches
+// on -- answers pass by pass.  No HIP call.
+int qmg_batch_plan(int entry, int dtype, int op, size_t n, size_t stride, int nrhs, unsigned mask, int nj, const unsigned* shift_masks, int flags,
+                   int aligned16_, int* plan_out, int max_passes) {
+  if (!plan_out || max_passes < 1 || !valid_dtype(dtype) || nrhs < 1 || nrhs > BATCH_MAX) return QMG_ERR_INVALID;
+  switch (entry) {
+    case QMG_BE_BLAS: if (op < QMG_BOP_ZERO || op > QMG_BOP_CAXPBYZ || nj || flags) return QMG_ERR_INVALID; break;
+    case QMG_BE_MULTI_CAXPY: if (nj < 0 || op || flags) return QMG_ERR_INVALID; break;
+    case QMG_BE_GCR_UPDATE: if (nj < 0 || op || (flags & ~BPV_ZNEXT)) return QMG_ERR_INVALID; break;
+    case QMG_BE_CGM_UPDATE: if (nj < 1 || nj > BATCH_MAX || !shift_masks || op || flags) return QMG_ERR_INVALID; break;
+    case QMG_BE_REDUCE: if (op < QMG_BRED_NORM2 || op > QMG_BRED_DIFFNORM2 || nj || flags) return QMG_ERR_INVALID; break;
+    case QMG_BE_MULTIDOT: if (nj < 1 || nj > BDOT_MAX || op || flags) return QMG_ERR_INVALID; break;
+    case QMG_BE_MR_DOTS: if (nj || op || flags) return QMG_ERR_INVALID; break;
+    case QMG_BE_MR_UPDATE: if (nj || op || (flags & ~(BPV_XSET | BPV_ROUT))) return QMG_ERR_INVALID; break;
+    default: return QMG_ERR_INVALID;
+  }
+  BatchPlanRequest rq = batch_request(entry, dtype, n, stride, nrhs, mask, aligned16_ != 0);
+  rq.op = op; rq.nj = nj; rq.shift_masks = shift_masks; rq.flags = flags;
+  for (int i = 0; i < BATCH_PLAN_INTS * max_passes; i++) plan_out[i] = -1;
+  int passes = 0;
+  for (int at = 0; at >= 0; passes++) {
+    if (passes == max_passes) return QMG_ERR_INVALID;
+    const BatchPass pl = batch_plan(rq, at);
+    const int v[BATCH_PLAN_INTS] = {pl.family, pl.W, pl.nt, pl.J, pl.variant};
+    for (int i = 0; i < BATCH_PLAN_INTS; i++) plan_out[BATCH_PLAN_INTS * passes + i] = v[i];
+    at = pl.next;
+  }
   return QMG_SUCCESS;
 }
 

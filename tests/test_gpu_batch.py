@@ -36,6 +36,7 @@ MASKS = [(5, 0b11111), (5, 0b01101), (16, 0xFFFF), (16, 0x8421), (3, 0b010), (9,
 
 @pytest.mark.parametrize("nrhs,mask", MASKS)
 def test_batch_blas_bit_identical_and_masked(nrhs, mask):
+    """qmg_batch_blas bit for bit the single-vector kernels.  (The reference: test_gpu_batch_routes.py holds these kernels to a long-double reference, elementwise, one row per route of qmg_batch_plan.)"""
     n, pad = 1000, 7
     stride = n + pad
     x = cs.gaussian_cvec(stride * nrhs, 1)
@@ -62,6 +63,7 @@ def test_batch_blas_bit_identical_and_masked(nrhs, mask):
 @pytest.mark.parametrize("nrhs,mask", MASKS)
 @pytest.mark.parametrize("n", [1, 777, 300001])
 def test_batch_reductions_bit_identical(nrhs, mask, n):
+    """qmg_batch_reduce bit for bit the single-vector reductions.  (The reference: test_gpu_batch_routes.py holds these kernels to a long-double reference, elementwise, one row per route of qmg_batch_plan.)"""
     stride = n + 3
     x = cs.gaussian_cvec(stride * nrhs, 11)
     y = cs.gaussian_cvec(stride * nrhs, 12)
@@ -82,6 +84,7 @@ def test_batch_reductions_bit_identical(nrhs, mask, n):
 
 @pytest.mark.parametrize("nj", [1, 2, 5, 11, 32])
 def test_batch_multidot_and_multi_caxpy(nj):
+    """qmg_batch_multidot / qmg_batch_multi_caxpy bit for bit their single-vector forms.  (The reference: test_gpu_batch_routes.py holds these kernels to a long-double reference, elementwise, one row per route of qmg_batch_plan.)"""
     nrhs, mask, n = 6, 0b101101, 4099
     stride = n + 5
     xs = [cs.gaussian_cvec(stride * nrhs, 20 + j) for j in range(nj)]
@@ -268,7 +271,8 @@ def test_batch_entry_points_edge_cases():
 @pytest.mark.parametrize("dtype", ["c64", "c32"])
 def test_batch_non_temporal_reads_change_no_bit(dtype):
     """A batch whose active systems add up to `blas_nt_mb` MiB reads its read-only operands non-temporally (csrc/qmg_batch.hip): the same
-    bits with the threshold at 1 MiB (on: 5 systems x 100 001 elements) and at 0 (never), in both storage precisions, aliased z = a x + b z included."""
+    bits with the threshold at 1 MiB (on: 5 systems x 100 001 elements) and at 0 (never), in both storage precisions, aliased z = a x + b z included.
+    (Against a reference, with the non-temporal plan asserted: the nt rows of test_gpu_batch_routes.py.)"""
     n, nrhs, mask = 100001, 5, 0b10111
     stride = n + 3
     np_t = np.complex128 if dtype == "c64" else np.complex64
@@ -308,7 +312,8 @@ def test_mr_step_with_device_scalars_is_the_host_scalar_step(nrhs, mask, dtype):
     host-scalar step of bmr_core (krylov.hpp) built from the existing entry points: multidot of {r, p} against p, alpha =
     omega conj(<r,p>) / <p,p> on the host, two caxpy.  Same reduction order and the same (omega pr) / pp: x and r BIT FOR BIT, in both
     storage precisions; the dots in the device slot equal the multidot's; frozen systems untouched; the x_set form (x = alpha r) equals
-    the accumulate form on x = 0; <p,p> = 0 leaves a system as it is."""
+    the accumulate form on x = 0; <p,p> = 0 leaves a system as it is.  (Against the mathematics rather than the unfused passes: the mr rows of
+    test_gpu_batch_routes.py.)"""
     dt = qmg.C64 if dtype == "c64" else qmg.C32
     n, pad, omega = 3000, 8, 0.85
     stride = n + pad
@@ -363,7 +368,8 @@ def test_mr_step_with_device_scalars_is_the_host_scalar_step(nrhs, mask, dtype):
 def test_gcr_update_is_the_three_separate_passes_bit_for_bit(nj, f32, with_z):
     """qmg_batch_gcr_update_t (w += sum_j c_j W_j ; r += a w ; z_next = r in one launch: the vector updates of one flexible-GCR iteration, the
     caller of the K-cycle on both sides of the hot path) against qmg_batch_multi_caxpy_t, qmg_batch_blas_t(CAXPY), qmg_batch_blas_t(COPY) in that
-    order: identical bits in both storage precisions, frozen systems and the padding between systems untouched."""
+    order: identical bits in both storage precisions, frozen systems and the padding between systems untouched.  (Against the mathematics rather
+    than the unfused passes, long vectors included: the gcr rows of test_gpu_batch_routes.py.)"""
     nrhs, mask, n = 5, 0b10111, 4098
     stride = n + 6
     vt, dt = (np.complex64, qmg.C32) if f32 else (np.complex128, qmg.C64)

@@ -120,7 +120,8 @@ def test_wilson_fixture_apply_f32(golden_dir):
 @pytest.mark.parametrize("n,stride_pad,nrhs,mask", [(4096, 0, 1, 1), (1000, 2, 5, 0b10111), (4097, 1, 3, 0b101), (1 << 20, 0, 2, 0b11)])
 def test_batch_blas_and_reductions_f32(n, stride_pad, nrhs, mask):
     """Element-wise leaves round once (3e-7); reductions accumulate in fp64 (1e-12 on fp32-representable inputs).  Odd n /
-    odd stride exercise the 8-byte fallback of the 16-byte-per-lane kernels."""
+    odd stride exercise the 8-byte fallback of the 16-byte-per-lane kernels.  (Elementwise, with the access width asserted and misaligned
+    pointers: the c32 rows of test_gpu_batch_routes.py.)"""
     stride = n + stride_pad
     x, y, z = (r32(cs.gaussian_cvec(nrhs * stride, s)) for s in (1, 2, 3))
     a = np.array([0.3 - 0.2j + 0.1 * k for k in range(nrhs)])
