@@ -612,6 +612,45 @@ int qmg_dwf_apply_direct(int dtype, const qmg_stencil_desc* d, const void* gauge
  * (a member the family does not use is 0).  QMG_ERR_INVALID: plan_out missing or plan_len below 8. */
 int qmg_dwf_plan(int dtype, int Lx, int Ly, int Ls, unsigned pieces, int n_active, int inplace, int* plan_out, int plan_len);
 
+/* ---------------- the even-odd Schur complement of the domain-wall operator, from the links (csrc/qmg_dwf_eo.hip) ----------------
+ * D = A + H: A = clover + shift is site-local, H the hops.  With d_p = 3 w + shift +- eo_shift (+ even, - odd sites) A_p is, per spin, the
+ * Ls x Ls matrix  d_p - (lower shift along s) + m e_0 e_{Ls-1}^T  (sigma 0; sigma 1 mirrored under s -> Ls-1-s), inverted in the kernel by a
+ * geometric scan along s plus the rank-one wall correction; the powers of 1/d_p are formed on the host in fp64.
+ * Common to the three entries: d gives Lx, Ly, nc = 2 Ls and the shifts (matrix pointers ignored); qmg_dwf_apply_direct's validity rules
+ * (QMG_C64 / QMG_C32, Ls in 2 .. 32, nrhs in 1 .. 16, 16-byte alignment, vec_stride at least a vector); mask as in qmg_stencil_apply_batch.
+ * Refused before anything is launched:  dof_shift != 0 -- QMG_ERR_UNSUPPORTED (the diagonal is not constant along s);  |d_p| <= 1 for a
+ * processed or inverted parity -- QMG_ERR_UNSUPPORTED (outside the domain-wall regime the scan's powers grow);  1 + m d_p^-Ls == 0 or any
+ * coefficient (mass, wilson_coeff, shifts, alpha) not finite -- QMG_ERR_INVALID. */
+enum { QMG_DWF_G5_IN = 1, QMG_DWF_G5_OUT = 2 };   /* Gamma5 psi(s, sigma) = (-1)^sigma psi(Ls-1-s, sigma) on the load of the source / on the store */
+/* kernel I: lhs_p = alpha A_p^-1 rhs_p on the parities named by QMG_P_CLOVER_E / QMG_P_CLOVER_O (any other bit: QMG_ERR_UNSUPPORTED);
+ * overwrites; lhs == rhs is allowed. */
+int qmg_dwf_inv5(int dtype, const qmg_stencil_desc* d, int Ls, double mass_re, double mass_im, double wilson_coeff, void* lhs, const void* rhs,
+                 unsigned pieces, double alpha_re, double alpha_im, int nrhs, size_t vec_stride, unsigned mask, void* stream);
+/* kernel K: lhs_p = (QMG_P_ZERO_p ? 0 : lhs_p) + alpha A_p^-1 (H_{p,1-p} rhs_{1-p}).  pieces: all four hop bits of each processed parity plus
+ * optional QMG_P_ZERO_*; any clover or shift bit, or a partial hop set: QMG_ERR_UNSUPPORTED.  flags: QMG_DWF_G5_IN (the hop source is
+ * Gamma5 rhs) or 0.  lhs == rhs is allowed when exactly one parity is processed (QMG_ERR_INVALID otherwise). */
+int qmg_dwf_hops_inv5(int dtype, const qmg_stencil_desc* d, const void* gauge, int Ls, double mass_re, double mass_im, double wilson_coeff, void* lhs,
+                      const void* rhs, unsigned pieces, double alpha_re, double alpha_im, unsigned flags, int nrhs, size_t vec_stride, unsigned mask,
+                      void* stream);
+/* lhs_p = Gamma5^{out} M_p Gamma5^{in} rhs_p,  M_p = A_p - H_{p,1-p} A_{1-p}^-1 H_{1-p,p},  p = parity (0 even, 1 odd); flags: QMG_DWF_G5_IN |
+ * QMG_DWF_G5_OUT.  Two launches (kernel K into tmp, then the second stage), whatever the flags.  Only the 1-p half of tmp is written; the 1-p
+ * halves of lhs and rhs are not touched.  lhs, rhs and tmp are three different arrays (QMG_ERR_INVALID otherwise). */
+int qmg_dwf_schur_apply(int dtype, const qmg_stencil_desc* d, const void* gauge, int Ls, double mass_re, double mass_im, double wilson_coeff, void* lhs,
+                        const void* rhs, void* tmp, int parity, unsigned flags, int nrhs, size_t vec_stride, unsigned mask, void* stream);
+/* What the three entries launch: the answer of the one host function they switch on.  Host only, no HIP call.
+ * kernel: 0 kernel I (pieces as qmg_dwf_inv5), 1 kernel K (pieces as qmg_dwf_hops_inv5), 2 the second stage of M (pieces:
+ * QMG_P_CLOVER_p | the four hops of p | QMG_P_SHIFT_p | QMG_P_ZERO_p of exactly one parity).  Writes 8 ints and -1 into the rest of plan_out:
+ *   family  0 unsupported, 1 k_dwf_eo_inv5 with the hops (kernel K), 2 success with nothing launched, 3 invalid, 4 k_dwf_eo_inv5 on the own
+ *           chunk (kernel I), 5 k_dwf_eo_schur2 (the second stage)
+ *   lps     lanes per site: Ls
+ *   block   threads per block: Ls floor(256 / Ls) -- a multiple of Ls, so that the lanes of a site never straddle a block
+ *   gx, gy  the grid: gx blocks cover the Ls Lx/2 lanes of a half row, gy = min(rows, 65535) blocks walk the (parity, y) rows
+ *   flags   qmg_dwf_plan's: 1 every processed parity overwritten, 2 more than one system, 4 complex<float>
+ *   lds     bytes of LDS per block (the exchange along s; 0 for the second stage)
+ *   nk      the systems served
+ * QMG_ERR_INVALID: plan_out missing or plan_len below 8. */
+int qmg_dwf_eo_plan(int dtype, int Lx, int Ly, int Ls, int kernel, unsigned pieces, int n_active, int inplace, int* plan_out, int plan_len);
+
 /* ---------------- tuning hooks (not part of the reference surface) ---------------- */
 /* Dispatch / codegen knobs, all with the defaults the measurements in profiles/ chose; results never depend on them
  * beyond summation order.  Unknown keys, and values a key does not take, return QMG_ERR_INVALID.

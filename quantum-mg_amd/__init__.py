@@ -55,6 +55,7 @@ ABI_SYMBOLS = [
     "qmg_hmc_momentum_update", "qmg_hmc_momentum_update_poles", "qmg_hmc_momentum_update_staggered", "qmg_hmc_link_update", "qmg_hmc_momentum_refresh", "qmg_hmc_stream_seed",
     "qmg_u1_flow_stage", "qmg_u1_flow", "qmg_u1_wilson_loops", "qmg_u1_polyakov",
     "qmg_dwf_fill", "qmg_dwf_apply_direct", "qmg_dwf_plan", "qmg_batch_plan",
+    "qmg_dwf_inv5", "qmg_dwf_hops_inv5", "qmg_dwf_schur_apply", "qmg_dwf_eo_plan",
 ]
 
 
@@ -772,6 +773,55 @@ def dwf_plan(dtype, dims, Ls, pieces, n_active=1, inplace=False):
     """What qmg_dwf_apply_direct does with a request (qmg_dwf_plan; host only): (family, lps, block, gx, gy, flags, shape, nk)."""
     out = (C.c_int * DWF_PLAN_INTS)()
     check(lib().qmg_dwf_plan(dtype, dims[0], dims[1], Ls, C.c_uint(pieces), n_active, int(inplace), out, DWF_PLAN_INTS), "qmg_dwf_plan")
+    return tuple(out)
+
+
+# ---- the even-odd Schur complement of the domain-wall operator from the links (csrc/qmg_dwf_eo.hip)
+DWF_G5_IN, DWF_G5_OUT = 1, 2
+# the `kernel` argument and the families of qmg_dwf_eo_plan (include/qmg_hip.h)
+DEK_INV5, DEK_HOPS_INV5, DEK_SCHUR2 = range(3)
+DEF_UNSUPPORTED, DEF_HOPS_INV5, DEF_NOTHING, DEF_INVALID, DEF_INV5, DEF_SCHUR2 = range(6)
+DWF_EO_PLAN_INTS = 8
+
+
+def dwf_inv5_status(dtype, desc, Ls, mass, lhs, rhs, pieces, alpha=1.0, w=1.0, nrhs=1, vec_stride=0, mask=1, stream=None):
+    """qmg_dwf_inv5's status, unchecked: lhs_p = alpha A_p^-1 rhs_p on the parities P_CLOVER_E / P_CLOVER_O name."""
+    mass, alpha = complex(mass), complex(alpha)
+    return lib().qmg_dwf_inv5(dtype, C.byref(desc), Ls, C.c_double(mass.real), C.c_double(mass.imag), C.c_double(w), _vp(lhs), _vp(rhs), C.c_uint(pieces),
+                              C.c_double(alpha.real), C.c_double(alpha.imag), nrhs, C.c_size_t(vec_stride), C.c_uint(mask), C.c_void_p(stream))
+
+
+def dwf_inv5(*args, **kw):
+    check(dwf_inv5_status(*args, **kw), "qmg_dwf_inv5")
+
+
+def dwf_hops_inv5_status(dtype, desc, gauge, Ls, mass, lhs, rhs, pieces, alpha=1.0, flags=0, w=1.0, nrhs=1, vec_stride=0, mask=1, stream=None):
+    """qmg_dwf_hops_inv5's status, unchecked: lhs_p (+)= alpha A_p^-1 H_{p,1-p} [Gamma5] rhs_{1-p}."""
+    mass, alpha = complex(mass), complex(alpha)
+    return lib().qmg_dwf_hops_inv5(dtype, C.byref(desc), _vp(gauge), Ls, C.c_double(mass.real), C.c_double(mass.imag), C.c_double(w), _vp(lhs), _vp(rhs),
+                                   C.c_uint(pieces), C.c_double(alpha.real), C.c_double(alpha.imag), C.c_uint(flags), nrhs, C.c_size_t(vec_stride), C.c_uint(mask),
+                                   C.c_void_p(stream))
+
+
+def dwf_hops_inv5(*args, **kw):
+    check(dwf_hops_inv5_status(*args, **kw), "qmg_dwf_hops_inv5")
+
+
+def dwf_schur_apply_status(dtype, desc, gauge, Ls, mass, lhs, rhs, tmp, parity=0, flags=0, w=1.0, nrhs=1, vec_stride=0, mask=1, stream=None):
+    """qmg_dwf_schur_apply's status, unchecked: lhs_p = Gamma5^out M_p Gamma5^in rhs_p, two launches."""
+    mass = complex(mass)
+    return lib().qmg_dwf_schur_apply(dtype, C.byref(desc), _vp(gauge), Ls, C.c_double(mass.real), C.c_double(mass.imag), C.c_double(w), _vp(lhs), _vp(rhs), _vp(tmp),
+                                     parity, C.c_uint(flags), nrhs, C.c_size_t(vec_stride), C.c_uint(mask), C.c_void_p(stream))
+
+
+def dwf_schur_apply(*args, **kw):
+    check(dwf_schur_apply_status(*args, **kw), "qmg_dwf_schur_apply")
+
+
+def dwf_eo_plan(dtype, dims, Ls, kernel, pieces, n_active=1, inplace=False):
+    """What the even-odd entries launch (qmg_dwf_eo_plan; host only): (family, lps, block, gx, gy, flags, lds, nk)."""
+    out = (C.c_int * DWF_EO_PLAN_INTS)()
+    check(lib().qmg_dwf_eo_plan(dtype, dims[0], dims[1], Ls, kernel, C.c_uint(pieces), n_active, int(inplace), out, DWF_EO_PLAN_INTS), "qmg_dwf_eo_plan")
     return tuple(out)
 
 

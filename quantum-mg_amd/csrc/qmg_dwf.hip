@@ -19,6 +19,7 @@
 // 8 chunk loads per pair instead of 10, twice the bytes of a wavefront in flight -- 0.56 against 0.62 ms at 2048^2, Ls = 8 in fp64.
 // Piece sets served: the ones kernel W serves (qmg_wilson.hip) -- clover + every hop (+ shift) of the processed parities, or every hop
 // alone (then lhs == rhs is allowed for one parity); everything else returns QMG_ERR_UNSUPPORTED and the stored stencil serves it.
+#include "qmg_dwf_lane.h"   // dwf::uni, gld, fmac2
 #include "qmg_dwf_plan.h"
 
 namespace qmg {
@@ -37,23 +38,6 @@ struct DwfArgs {
   double shift[2], eo_shift[2], dof_shift[2];
   int ridx[16];
 };
-
-namespace dwf {
-typedef __attribute__((address_space(1))) char gchar;
-// a block-uniform pointer, told to the compiler: the accesses take the scalar-base + 32-bit-offset form (as in qmg_wilson.hip)
-__device__ __forceinline__ gchar* uni(const char* p) {
-  const unsigned long long v = reinterpret_cast<unsigned long long>(p);
-  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-  return (gchar*)(((unsigned long long)hi << 32) | lo);
-}
-template <typename V> __device__ __forceinline__ V gld(const gchar* base, unsigned off) { return *(const __attribute__((address_space(1))) V*)(base + off); }
-// acc += (mx + i my) (bx + i by)
-template <typename R>
-__device__ __forceinline__ void fmac2(R& ax, R& ay, R mx, R my, R bx, R by) {
-  ax = fma(mx, bx, ax); ax = fma(-my, by, ax);
-  ay = fma(mx, by, ay); ay = fma(my, bx, ay);
-}
-}  // namespace dwf
 
 // ---- the stored form: the full nc = 2 Ls clover and hopping fields, zeros included (layout of include/qmg_hip.h) ----
 // one thread per (site, row, column); the hopping entries are k_wilson_fill's single multiplications

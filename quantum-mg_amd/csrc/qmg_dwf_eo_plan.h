@@ -1,0 +1,146 @@
+// qmg_dwf_eo_plan.h -- which launch serves a request to the even-odd domain-wall entry points (qmg_dwf_inv5, qmg_dwf_hops_inv5,
+// qmg_dwf_schur_apply): ONE host function (dwf_eo_plan) that the launches switch on and that qmg_dwf_eo_plan() exports, after
+// qmg_dwf_plan.h; and the fifth-dimension coefficients those kernels take by value (dwf_eo_coef).  Host code only, no HIP call.
+#ifndef QMG_DWF_EO_PLAN_H
+#define QMG_DWF_EO_PLAN_H
+
+#include <cmath>
+#include <complex>
+
+#include "qmg_dwf_plan.h"
+
+namespace qmg {
+
+// the `kernel` argument of qmg_dwf_eo_plan()
+enum DwfEoKernel {
+  DEK_INV5 = 0,        // kernel I: lhs_p = alpha A_p^-1 rhs_p
+  DEK_HOPS_INV5 = 1,   // kernel K: lhs_p (+)= alpha A_p^-1 H_{p,1-p} rhs_{1-p}
+  DEK_SCHUR2 = 2       // second stage of M: lhs_p = A_p x_p + H_{p,1-p} t_{1-p}
+};
+// families (the values are part of qmg_dwf_eo_plan()'s output, include/qmg_hip.h)
+enum DwfEoFamily {
+  DEF_UNSUPPORTED = 0,   // the entry point returns QMG_ERR_UNSUPPORTED
+  DEF_HOPS_INV5 = 1,     // k_dwf_eo_inv5<T, true, ZERO, BATCH>
+  DEF_NOTHING = 2,       // success with nothing launched
+  DEF_INVALID = 3,       // the entry point returns QMG_ERR_INVALID
+  DEF_INV5 = 4,          // k_dwf_eo_inv5<T, false, true, BATCH>
+  DEF_SCHUR2 = 5         // k_dwf_eo_schur2<T, BATCH>
+};
+enum { DWF_EO_PLAN_INTS = 8, DWF_EO_BLOCK_MAX = 256 };
+
+// The first DWF_EO_PLAN_INTS members, in this order, are what qmg_dwf_eo_plan() writes.
+struct DwfEoPlan {
+  int family;   // DwfEoFamily
+  int lps;      // lanes per site: Ls
+  int block;    // threads per block: Ls * floor(256 / Ls), so that the Ls lanes of a site never straddle a block (the exchange is in LDS)
+  int gx, gy;   // gx blocks cover the lps * Lx/2 lanes of a half row; gy = min(rows, 65535) blocks walk the (parity, y) rows
+  int flags;    // DPF_ZERO / DPF_BATCH / DPF_F32 (qmg_dwf_plan.h)
+  int lds;      // bytes of LDS per block: two buffers of one chunk per lane for kernels K and I, 0 for the second stage
+  int nk;       // active systems served (all of them, in one launch)
+  // ----
+  int status;
+  int par_first, par_count;
+};
+
+namespace dwf_eo_detail {
+inline DwfEoPlan refused(int status) {
+  DwfEoPlan pl = {};
+  pl.family = status == QMG_ERR_INVALID ? DEF_INVALID : DEF_UNSUPPORTED;
+  pl.status = status;
+  return pl;
+}
+inline DwfEoPlan nothing() {
+  DwfEoPlan pl = {};
+  pl.family = DEF_NOTHING;
+  return pl;
+}
+}  // namespace dwf_eo_detail
+
+// pieces: kernel I   QMG_P_CLOVER_E / _O name the parities;
+//         kernel K   all four hop bits of each processed parity (+ QMG_P_ZERO_*);
+//         stage 2    QMG_P_CLOVER_p | the four hops of p | QMG_P_SHIFT_p | QMG_P_ZERO_p of exactly one parity p.
+// n_active: the systems whose mask bit is set (0 .. 16); inplace: lhs == rhs
+inline DwfEoPlan dwf_eo_plan(int dtype, int Lx, int Ly, int Ls, int kernel, unsigned pieces, int n_active, int inplace) {
+  using namespace dwf_eo_detail;
+  if (!valid_dtype(dtype) || !valid_lattice(Lx, Ly) || Ls < DWF_LS_MIN || Ls > DWF_LS_MAX || n_active < 0 || n_active > BATCH_MAX) return refused(QMG_ERR_INVALID);
+  if (kernel != DEK_INV5 && kernel != DEK_HOPS_INV5 && kernel != DEK_SCHUR2) return refused(QMG_ERR_INVALID);
+  const long lanes = (long)(Lx / 2) * Ls;
+  if (lanes * 32 > 0x7FFFFFFFl) return refused(QMG_ERR_INVALID);   // a half row of the vector is addressed with 32-bit byte offsets
+  if (n_active == 0 || pieces == 0) return nothing();
+  int par_first = 0, par_count = 0;
+  bool zero = true;
+  if (kernel == DEK_INV5) {
+    if (pieces & ~(unsigned)QMG_P_CLOVER) return refused(QMG_ERR_UNSUPPORTED);
+    const bool ev = pieces & QMG_P_CLOVER_E, od = pieces & QMG_P_CLOVER_O;
+    par_first = ev ? 0 : 1; par_count = (ev && od) ? 2 : 1;
+  } else if (kernel == DEK_HOPS_INV5) {
+    if (pieces & (QMG_P_CLOVER | QMG_P_SHIFT)) return refused(QMG_ERR_UNSUPPORTED);
+    const bool ev = pieces & (QMG_P_EO | QMG_P_ZERO_E), od = pieces & (QMG_P_OE | QMG_P_ZERO_O);
+    par_first = ev ? 0 : 1; par_count = (ev && od) ? 2 : 1;
+    for (int q = 0; q < par_count; q++) {
+      const int p = (par_count == 2) ? q : par_first;
+      if (((pieces >> (2 + 4 * p)) & 0xFu) != 0xFu) return refused(QMG_ERR_UNSUPPORTED);   // a partial hop set
+      if (!((pieces >> (12 + p)) & 1u)) zero = false;
+    }
+    if (inplace && par_count == 2) return refused(QMG_ERR_INVALID);   // in place: one parity written from the other
+  } else {
+    const unsigned even = QMG_P_CLOVER_E | QMG_P_EO | QMG_P_SHIFT_E | QMG_P_ZERO_E, odd = QMG_P_CLOVER_O | QMG_P_OE | QMG_P_SHIFT_O | QMG_P_ZERO_O;
+    if (pieces != even && pieces != odd) return refused(QMG_ERR_UNSUPPORTED);
+    if (inplace) return refused(QMG_ERR_INVALID);
+    par_first = pieces == even ? 0 : 1; par_count = 1;
+  }
+  const long nrows = (long)Ly * par_count;
+  const int f32 = dtype == QMG_C32;
+  DwfEoPlan pl = {};
+  pl.family = kernel == DEK_INV5 ? DEF_INV5 : kernel == DEK_HOPS_INV5 ? DEF_HOPS_INV5 : DEF_SCHUR2;
+  pl.lps = Ls;
+  pl.block = Ls * (DWF_EO_BLOCK_MAX / Ls);
+  pl.gx = (int)((lanes + pl.block - 1) / pl.block);
+  pl.gy = nrows > 65535 ? 65535 : (int)nrows;
+  pl.flags = (zero ? DPF_ZERO : 0) | (n_active > 1 ? DPF_BATCH : 0) | (f32 ? DPF_F32 : 0);
+  pl.lds = kernel == DEK_SCHUR2 ? 0 : 2 * DWF_EO_BLOCK_MAX * (f32 ? 16 : 32);
+  pl.nk = n_active;
+  pl.status = QMG_SUCCESS;
+  pl.par_first = par_first;
+  pl.par_count = par_count;
+  return pl;
+}
+
+// ---- the site-local block A_p = d_p - (shift along s) + m (wall), d_p = 3 w + shift +- eo_shift, and what its inverse needs ----
+//   sigma 0:  g_s = sum_{s' <= s} d^-(s-s'+1) h_s',   y_s = g_s - q d^-(s+1) g_{Ls-1},   q = m / (1 + m d^-Ls);   sigma 1: mirrored in s
+struct DwfEoCoef {
+  double d[2][2];                     // d_p (re, im)
+  double q[2][2];                     // m / (1 + m d_p^-Ls)
+  double pw[2][DWF_LS_MAX + 1][2];    // d_p^-k, k = 0 .. Ls
+};
+// need: bit p set when A_p is inverted or applied.  QMG_SUCCESS, or the refusal the entry points document.
+inline int dwf_eo_coef(const qmg_stencil_desc* d, int Ls, double mr, double mi, double w, unsigned need, DwfEoCoef* out) {
+  typedef std::complex<double> C;
+  const double all[] = {mr, mi, w, d->shift[0], d->shift[1], d->eo_shift[0], d->eo_shift[1], d->dof_shift[0], d->dof_shift[1]};
+  for (double v : all)
+    if (!std::isfinite(v)) return QMG_ERR_INVALID;
+  if (d->dof_shift[0] != 0.0 || d->dof_shift[1] != 0.0) return QMG_ERR_UNSUPPORTED;   // the diagonal is no longer constant along s
+  const C m(mr, mi);
+  DwfEoCoef c = {};
+  for (int p = 0; p < 2; p++) {
+    const double sg = p ? -1.0 : 1.0;
+    const C dp(3.0 * w + d->shift[0] + sg * d->eo_shift[0], d->shift[1] + sg * d->eo_shift[1]);
+    c.d[p][0] = dp.real(); c.d[p][1] = dp.imag();
+    if (!((need >> p) & 1u)) continue;
+    if (!(std::abs(dp) > 1.0)) return QMG_ERR_UNSUPPORTED;   // outside the domain-wall regime: the scan's powers would grow
+    const C inv = 1.0 / dp;
+    C pk(1.0, 0.0);
+    for (int k = 0; k <= Ls; k++) { c.pw[p][k][0] = pk.real(); c.pw[p][k][1] = pk.imag(); pk *= inv; }
+    const C den = 1.0 + m * C(c.pw[p][Ls][0], c.pw[p][Ls][1]);
+    if (den == C(0.0, 0.0)) return QMG_ERR_INVALID;
+    const C q = m / den;
+    if (!std::isfinite(q.real()) || !std::isfinite(q.imag())) return QMG_ERR_INVALID;
+    c.q[p][0] = q.real(); c.q[p][1] = q.imag();
+  }
+  *out = c;
+  return QMG_SUCCESS;
+}
+
+}  // namespace qmg
+
+#endif

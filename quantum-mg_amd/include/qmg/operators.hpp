@@ -1,6 +1,6 @@
 // operators.hpp -- the concrete stencils of the reference on device arrays:
 //   Wilson2D (operators/wilson.h), Staggered2D (operators/staggered.h), GaugedLaplace2D
-//   (operators/gaugedlaplace.h), FreeLaplace2D (tests/n02_free_laplace_test/free_laplace.h), Dwf2D<Ls> / createDwfLs (operators/dwf.h).
+//   (operators/gaugedlaplace.h), FreeLaplace2D (tests/n02_free_laplace_test/free_laplace.h), DwfBase / Dwf2D<Ls> / createDwfLs (operators/dwf.h).
 // CoarseOperator2D lives in coarse.hpp (it needs TransferMG).
 #ifndef QMG_OPERATORS_HPP
 #define QMG_OPERATORS_HPP
@@ -77,13 +77,87 @@ struct Wilson2D : public Stencil2D {
 // stored arrays (qmg_dwf_fill: the full nc x nc matrices, zeros included) serve the dagger / right-block-Jacobi / Galerkin builds and every
 // piece set the kernel from the links does not; the ORIGINAL-operator applies go straight from the links (qmg_dwf_apply_direct, csrc/qmg_dwf.hip).
 // Whole lattice only: y-slabs are not served.
+// DwfBase: what does not depend on the compile-time Ls -- the wall mass, M5, Ls, and the 4D even-odd Schur complement from the links
+// (qmg_dwf_inv5 / qmg_dwf_hops_inv5 / qmg_dwf_schur_apply, csrc/qmg_dwf_eo.hip).  D = A + H with A = clover + shift site-local and constant:
+//   M = A_ee - H_eo A_oo^-1 H_oe,   Gamma5 M Gamma5 = M^dagger for real m and shifts (no dagger stencil),
+// in the reference's Schur convention (stencil_2d.h:1886-1957): the arrays are addressed as full-length vectors of which the even half is
+// the system -- a solver hands over half-length arrays --, eo_cvector is the scratch.  These methods need the links route (direct.on, kind
+// domain wall, no variant swapped in); there is no stored fallback, so they also serve Ls = 32.
+struct DwfBase : public Stencil2D {
+ protected:
+  complex<double> mass;
+  double M5;
+  int dwf_Ls;
+  complex<double>* schur5_vector;   // M rhs inside apply_M_schur5_dagger_M, allocated on demand
+  DwfBase(Lattice2D* in_lat, complex<double> mass, double M5, int Ls)
+      : Stencil2D(in_lat, QMG_PIECE_CLOVER_HOPPING, M5, 0.0, 0.0), mass(mass), M5(M5), dwf_Ls(Ls), schur5_vector(0) {}
+
+  bool schur5(const char* who, complex<double>* lhs, complex<double>* rhs, unsigned flags) {
+    const qmg_stencil_desc d = desc();
+    return qmg::ok(qmg_dwf_schur_apply(QMG_C64, &d, direct.gauge, dwf_Ls, mass.real(), mass.imag(), direct.w, lhs, rhs, eo_cvector, 0, flags, 1, 0, 1u,
+                                       qmg::current_stream()), who);
+  }
+
+ public:
+  // whether the Schur methods can run (the links route is on; for the dagger forms: real wall mass and shifts); says why not, makes the scratch
+  bool schur5_ready(const char* who, bool dagger = false) {
+    if (!direct.on || direct.kind != QMG_DIRECT_DWF || swap_dagger || swap_rbjacobi || swap_rbj_dagger) {
+      std::cout << "[QMG-ERROR]: " << who << " needs the domain-wall links route (direct.on, no variant swapped in); there is no stored fallback.\n";
+      return false;
+    }
+    if (dagger && (mass.imag() != 0.0 || shift.imag() != 0.0 || eo_shift.imag() != 0.0)) {
+      std::cout << "[QMG-ERROR]: " << who << " uses Gamma5 M Gamma5 = M^dagger, which holds for a real wall mass and real shifts only.\n";
+      return false;
+    }
+    if (eo_cvector == 0) eo_cvector = allocate_vector<complex<double>>(lat->get_size_cv_l());
+    return eo_cvector != 0;
+  }
+  virtual ~DwfBase() { if (schur5_vector) deallocate_vector(&schur5_vector); }
+  int get_Ls() const { return dwf_Ls; }
+  complex<double> get_mass() const { return mass; }
+  double get_M5() const { return M5; }
+
+  // lhs_e = M rhs_e, overwriting; lhs != rhs
+  void apply_M_schur5(complex<double>* lhs, complex<double>* rhs) {
+    if (schur5_ready("apply_M_schur5")) schur5("apply_M_schur5", lhs, rhs, 0);
+  }
+  // lhs_e = M^dagger rhs_e = Gamma5 M Gamma5 rhs_e: the two launches and the bytes of M
+  void apply_M_schur5_dagger(complex<double>* lhs, complex<double>* rhs) {
+    if (schur5_ready("apply_M_schur5_dagger", true)) schur5("apply_M_schur5_dagger", lhs, rhs, QMG_DWF_G5_IN | QMG_DWF_G5_OUT);
+  }
+  void apply_M_schur5_dagger_M(complex<double>* lhs, complex<double>* rhs) {
+    if (!schur5_ready("apply_M_schur5_dagger_M", true)) return;
+    if (!schur5_vector) schur5_vector = allocate_vector<complex<double>>(lat->get_size_cv_l() / 2);
+    if (schur5("apply_M_schur5_dagger_M", schur5_vector, rhs, 0)) schur5("apply_M_schur5_dagger_M", lhs, schur5_vector, QMG_DWF_G5_IN | QMG_DWF_G5_OUT);
+  }
+  // b_r,e = b_e - H_eo A_oo^-1 b_o, odd half zero (full-length arrays)
+  void prepare_M_schur5(complex<double>* b_r, complex<double>* b) {
+    if (!schur5_ready("prepare_M_schur5")) return;
+    const qmg_stencil_desc d = desc();
+    const long half = lat->get_size_cv_l() / 2;
+    qmg::ok(qmg_dwf_inv5(QMG_C64, &d, dwf_Ls, mass.real(), mass.imag(), direct.w, eo_cvector, b, QMG_P_CLOVER_O, 1.0, 0.0, 1, 0, 1u, qmg::current_stream()), "qmg_dwf_inv5");
+    qmg::ok(qmg_dwf_apply_direct(QMG_C64, &d, direct.gauge, dwf_Ls, mass.real(), mass.imag(), direct.w, b_r, eo_cvector, QMG_P_EO | QMG_P_ZERO_E, 1, 0, 1u,
+                                 qmg::current_stream()), "qmg_dwf_apply_direct");
+    cxpay(b, -1.0, b_r, half);
+    zero_vector(b_r + half, half);
+  }
+  // x_e = y_e, x_o = A_oo^-1 (b_o - H_oe y_e)   (x and b full-length; of y_e the even half is read)
+  void reconstruct_M_schur5(complex<double>* x, complex<double>* y_e, complex<double>* b) {
+    if (!schur5_ready("reconstruct_M_schur5")) return;
+    const qmg_stencil_desc d = desc();
+    const long half = lat->get_size_cv_l() / 2;
+    if (x != y_e) copy_vector(x, y_e, half);
+    qmg::ok(qmg_dwf_inv5(QMG_C64, &d, dwf_Ls, mass.real(), mass.imag(), direct.w, x, b, QMG_P_CLOVER_O, 1.0, 0.0, 1, 0, 1u, qmg::current_stream()), "qmg_dwf_inv5");
+    qmg::ok(qmg_dwf_hops_inv5(QMG_C64, &d, direct.gauge, dwf_Ls, mass.real(), mass.imag(), direct.w, x, x, QMG_P_OE, -1.0, 0.0, 0, 1, 0, 1u, qmg::current_stream()),
+            "qmg_dwf_hops_inv5");
+  }
+};
+
 template <int Ls>
-struct Dwf2D : public Stencil2D {
+struct Dwf2D : public DwfBase {
  protected:
   Dwf2D(Dwf2D const&);
   Dwf2D& operator=(Dwf2D const&);
-  complex<double> mass;
-  double M5;
   complex<double>* scratch;   // for the in-place gamma5
 
  public:
@@ -98,7 +172,7 @@ struct Dwf2D : public Stencil2D {
   }
 
   Dwf2D(Lattice2D* in_lat, complex<double> mass, complex<double>* gauge_links, double M5 = -1.0)
-      : Stencil2D(in_lat, QMG_PIECE_CLOVER_HOPPING, M5, 0.0, 0.0), mass(mass), M5(M5), scratch(0) {
+      : DwfBase(in_lat, mass, M5, Ls), scratch(0) {
     for (int i = 0; i < Ls; i++) {
       a[2 * i] = 1.0; a[2 * i + 1] = -1.0;
       shuffle[2 * i] = 2 * (Ls - 1 - i); shuffle[2 * i + 1] = 2 * (Ls - 1 - i) + 1;
@@ -150,6 +224,30 @@ inline Stencil2D* createDwfLs(Lattice2D* in_lat, complex<double> mass, complex<d
   }
   std::cout << "[QMG-ERROR]: Unsupported Ls " << Ls << " for domain wall operator. Add a template to dwf.h.\n";
   return nullptr;
+}
+
+// The Schur complement with the matrix_op_cplx signature (extra_data: a DwfBase*), for the Krylov solvers on the even half.
+inline void apply_dwf_schur5_M(complex<double>* lhs, complex<double>* rhs, void* extra_data) { ((DwfBase*)extra_data)->apply_M_schur5(lhs, rhs); }
+inline void apply_dwf_schur5_Mdagger_M(complex<double>* lhs, complex<double>* rhs, void* extra_data) { ((DwfBase*)extra_data)->apply_M_schur5_dagger_M(lhs, rhs); }
+
+// D x = b by CG on the normal equations of the even-odd Schur complement: prepare, M^dagger b', minv_vector_cg over the half length from the
+// even half of x as the initial guess, reconstruct.  x and b are full-length; eps is the relative residual of M^dagger M y = M^dagger b'.
+// Where the Schur methods cannot run (schur5_ready) nothing is solved and success is false.
+inline inversion_info minv_dwf_eo_cg(complex<double>* x, complex<double>* b, int max_iter, double eps, DwfBase* dwf, inversion_verbose_struct* verb = 0) {
+  const size_t n = dwf->lat->get_size_cv_l(), half = n / 2;
+  if (!dwf->schur5_ready("minv_dwf_eo_cg", true)) {   // nothing to iterate on: no solve, x untouched
+    inversion_info none;
+    none.name = "CG (even-odd domain wall): not run";
+    return none;
+  }
+  complex<double>* b_r = allocate_vector<complex<double>>(n);
+  complex<double>* rhs = allocate_vector<complex<double>>(half);
+  dwf->prepare_M_schur5(b_r, b);
+  dwf->apply_M_schur5_dagger(rhs, b_r);
+  const inversion_info info = minv_vector_cg(x, rhs, (int)half, max_iter, eps, apply_dwf_schur5_Mdagger_M, (void*)dwf, verb);
+  dwf->reconstruct_M_schur5(x, x, b);
+  deallocate_vector(&b_r); deallocate_vector(&rhs);
+  return info;
 }
 
 // ---------------- shared by the two nc = 1 operators: hand-rolled even-odd normal operator ----------------
