@@ -578,6 +578,48 @@ int qmg_wilson_apply_direct(int dtype, const qmg_stencil_desc* d, const void* ga
 int qmg_wilson_hops_direct(int dtype, const qmg_stencil_desc* d, const void* gauge, int gauge_Ly, int y0, double wilson_coeff, double hop_scale, void* lhs,
                            const void* rhs, const void* halo_lo, const void* halo_hi, unsigned pieces, int nrhs, size_t vec_stride, size_t halo_stride,
                            unsigned mask, int rows, void* stream);
+/* What the four entries (these two and their _epi forms) do with a request: the answer of the one host function their launch switches on, at
+ * the current "wilson_pair".  Host only, no HIP call.  Lx, Ly, nc: the vectors' lattice (d); halos: both halo buffers are given; layout_ok:
+ * what only the entry point sees of the buffers -- the halos come as a pair, and with nrhs > 1 vec_stride holds a vector and halo_stride a halo
+ * row; scaled: the qmg_wilson_hops_direct entries; n_active: the systems whose mask bit is set (0 .. 16); inplace: lhs == rhs; rows as in
+ * qmg_stencil_apply_slab; epi: 0 without an epilogue, else 1 | 2 (other is set) | 4 (dotv is set) | 8 (dotv == other) | 16 (dotv == rhs) |
+ * 32 (other or dotv is lhs).  Writes 16 ints and -1 into the rest of plan_out:
+ *   family  0 unsupported (the call returns QMG_ERR_UNSUPPORTED), 1 k_wilson_direct (kernel W: one site per lane group), 2 success with nothing
+ *           launched, 3 invalid (the call returns QMG_ERR_INVALID), 4 k_wilson_pair (kernel W2: the full operator -- shape 1 on both parities --,
+ *           both parities of a column per lane group; "wilson_pair" >= 1), 5 k_wilson_pair2 (W2 on two rows per lane group: "wilson_pair" >= 2,
+ *           one system, an even run of consecutive rows, emode 0 or 1)
+ *   lps     lanes per site: 2 in fp64, 1 in fp32
+ *   block   threads per block
+ *   gx, gy  the grid: gx blocks cover the lps * Lx/2 lanes of a half row; gy blocks walk the rows -- (parity, y) for family 1, y for 4, row pairs
+ *           for 5 --: min(rows, 65535) of them, and with the dots at most max(1, 2048 / gx)
+ *   flags   1 ZERO (every processed parity is overwritten) | 2 BATCH (more than one system) | 4 complex<float> | 8 the launch leaves the MR dots
+ *   shape   1 clover + hops (+ shift), 2 hops alone, 3 hops alone times hop_scale (the hops entries)
+ *   emode   the epilogue as the kernel is compiled for it: 0 none, 1 dots against the right-hand side (shape 1: nothing extra is loaded),
+ *           2 out = other_scale other + acc_scale acc, 3 the same and dots against `other`, 4 dots against a separate vector
+ *   nk      the systems served
+ *   y_first, y_count, boundary_only   the rows of the launch: y_first .. y_first + y_count - 1, or rows 0 and Ly - 1
+ *   npart   partials of the MR dots: gx * gy * 4, one per wavefront; 0 without dots
+ *   status  what the call returns (pointer checks apart)
+ *   par_first, par_count   the processed parities
+ * (a member the family does not use is 0).  The status of a request, in this precedence -- Stencil2D falls back to the stored stencil on
+ * QMG_ERR_UNSUPPORTED alone, so the order is part of the contract:
+ *    1. the hops entries refuse QMG_P_CLOVER | QMG_P_SHIFT pieces: UNSUPPORTED   (then the entry's pointer checks: INVALID)
+ *    2. dtype, rows outside 0 .. 2, n_active outside 0 .. 16, a lattice (Lx x Ly, Lx x gauge_Ly) that is not even x even and >= 2 x 2, y0 negative or
+ *       odd or y0 + Ly > gauge_Ly: INVALID
+ *    3. nc != 2: UNSUPPORTED
+ *    4. !layout_ok, or no halos with gauge_Ly != Ly or rows != 0 (a slab needs its halos): INVALID
+ *    5. n_active == 0: nothing
+ *    6. an epilogue with n_active != 1: UNSUPPORTED
+ *    7. an epilogue vector that is lhs: INVALID
+ *    8. other and dotv both set and different: UNSUPPORTED
+ *    9. no piece names a parity: nothing
+ *   10. no row: rows == 1 on Ly == 2: nothing
+ *   11. a piece set that is not shape 1 or 2 on every processed parity alike, or a hops entry with a shape other than 2: UNSUPPORTED
+ *   12. inplace with shape 1 or both parities: INVALID
+ *   13. an epilogue without QMG_P_ZERO on every processed parity, or inplace: INVALID
+ * QMG_ERR_INVALID from qmg_wilson_plan itself: plan_out missing or plan_len below 16. */
+int qmg_wilson_plan(int dtype, int Lx, int Ly, int nc, int gauge_Ly, int y0, int halos, int layout_ok, int scaled, unsigned pieces, int n_active, int inplace,
+                    int rows, unsigned epi, int* plan_out, int plan_len);
 
 /* ---------------- the Shamir domain-wall operator (operators/dwf.h; csrc/qmg_dwf.hip) ----------------
  * nc = 2 Ls components per site, c = 2 s + sigma (s the fifth-dimension slice, sigma the spin); Ls = 2 .. 32.  D = clover + hopping + shift:

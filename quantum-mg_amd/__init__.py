@@ -54,7 +54,7 @@ ABI_SYMBOLS = [
     "qmg_u1_hot_gauge", "qmg_u1_gauss_gauge", "qmg_u1_random_trans", "qmg_u1_gauge_transform", "qmg_u1_ape_smear", "qmg_u1_instanton", "qmg_u1_noncompact_instanton",
     "qmg_hmc_momentum_update", "qmg_hmc_momentum_update_poles", "qmg_hmc_momentum_update_staggered", "qmg_hmc_link_update", "qmg_hmc_momentum_refresh", "qmg_hmc_stream_seed",
     "qmg_u1_flow_stage", "qmg_u1_flow", "qmg_u1_wilson_loops", "qmg_u1_polyakov",
-    "qmg_dwf_fill", "qmg_dwf_apply_direct", "qmg_dwf_plan", "qmg_batch_plan",
+    "qmg_dwf_fill", "qmg_dwf_apply_direct", "qmg_dwf_plan", "qmg_batch_plan", "qmg_wilson_plan",
     "qmg_dwf_inv5", "qmg_dwf_hops_inv5", "qmg_dwf_schur_apply", "qmg_dwf_eo_plan",
 ]
 
@@ -743,6 +743,22 @@ def wilson_hops_direct(dtype, desc, gauge, lhs, rhs, pieces, w, hop_scale, nrhs=
     check(lib().qmg_wilson_hops_direct(dtype, C.byref(desc), _vp(gauge), desc.Ly if gauge_Ly is None else gauge_Ly, y0, C.c_double(w), C.c_double(hop_scale),
                                        _vp(lhs), _vp(rhs), _vp(halo_lo), _vp(halo_hi), C.c_uint(pieces), nrhs, C.c_size_t(vec_stride), C.c_size_t(halo_stride),
                                        C.c_uint(mask), rows, stream), "qmg_wilson_hops_direct")
+
+
+# families, flags and the epilogue description of qmg_wilson_plan (include/qmg_hip.h)
+WF_UNSUPPORTED, WF_DIRECT, WF_NOTHING, WF_INVALID, WF_PAIR, WF_PAIR2 = range(6)
+WPF_ZERO, WPF_BATCH, WPF_F32, WPF_DOTS = 1, 2, 4, 8
+WPE_ON, WPE_OTHER, WPE_DOTV, WPE_DOTV_IS_OTHER, WPE_DOTV_IS_RHS, WPE_ALIASES_LHS = 1, 2, 4, 8, 16, 32
+WILSON_PLAN_INTS = 16
+
+
+def wilson_plan(dtype, dims, pieces, n_active=1, inplace=False, scaled=False, epi=0, gauge_Ly=None, y0=0, halos=False, rows=0, nc=2, layout_ok=True):
+    """What the Wilson applies from the links do with a request at the current "wilson_pair" (qmg_wilson_plan; host only): (family, lps, block,
+    gx, gy, flags, shape, emode, nk, y_first, y_count, boundary_only, npart, status, par_first, par_count)."""
+    out = (C.c_int * WILSON_PLAN_INTS)()
+    check(lib().qmg_wilson_plan(dtype, dims[0], dims[1], nc, dims[1] if gauge_Ly is None else gauge_Ly, y0, int(halos), int(layout_ok), int(scaled), C.c_uint(pieces),
+                                n_active, int(inplace), rows, C.c_uint(epi), out, WILSON_PLAN_INTS), "qmg_wilson_plan")
+    return tuple(out)
 
 
 def dwf_fill(clover, hopping, gauge, Lx, Ly, Ls, mass=0.0, w=1.0, stream=None):

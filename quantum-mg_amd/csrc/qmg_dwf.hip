@@ -19,7 +19,7 @@
 // 8 chunk loads per pair instead of 10, twice the bytes of a wavefront in flight -- 0.56 against 0.62 ms at 2048^2, Ls = 8 in fp64.
 // Piece sets served: the ones kernel W serves (qmg_wilson.hip) -- clover + every hop (+ shift) of the processed parities, or every hop
 // alone (then lhs == rhs is allowed for one parity); everything else returns QMG_ERR_UNSUPPORTED and the stored stencil serves it.
-#include "qmg_dwf_lane.h"   // dwf::uni, gld, fmac2
+#include "qmg_lane.h"   // uni, gld, fmac2
 #include "qmg_dwf_plan.h"
 
 namespace qmg {
@@ -107,8 +107,7 @@ __device__ __forceinline__ DwfCoef<R> dwf_coef(const DwfArgs& a, int s) {
 template <typename T, int SHAPE>
 __device__ __forceinline__ void dwf_site(const T __attribute__((ext_vector_type(4))) (&xr)[4], const T __attribute__((ext_vector_type(4))) & own,
                                          const T __attribute__((ext_vector_type(2))) & lo, const T __attribute__((ext_vector_type(2))) & hi, const T (&lx)[4],
-                                         const T (&ly)[4], const DwfCoef<T>& co, const DwfArgs& a, int p, bool do_shift, bool do_zero, dwf::gchar* dst_chunk) {
-  using namespace dwf;
+                                         const T (&ly)[4], const DwfCoef<T>& co, const DwfArgs& a, int p, bool do_shift, bool do_zero, gchar* dst_chunk) {
   typedef T R;
   typedef T v4 __attribute__((ext_vector_type(4)));
   const R h = (R)0.5;
@@ -150,7 +149,6 @@ __device__ __forceinline__ void dwf_site(const T __attribute__((ext_vector_type(
 // T: storage and arithmetic scalar.  SHAPE 1: clover + hops (+ shift); 2: hops alone.  ZERO: every processed parity is overwritten.
 template <typename T, int SHAPE, bool ZERO, bool BATCH>
 __global__ __launch_bounds__(BLOCK) void k_dwf_direct(const DwfArgs a) {
-  using namespace dwf;
   typedef T R;
   typedef T v4 __attribute__((ext_vector_type(4)));   // a lane's chunk: (sigma 0 re, im, sigma 1 re, im)
   typedef T v2 __attribute__((ext_vector_type(2)));   // half a chunk, a link
@@ -219,7 +217,6 @@ __global__ __launch_bounds__(BLOCK) void k_dwf_direct(const DwfArgs a) {
 // pair instead of 10, and twice the bytes of a wavefront in flight.  Per-slice arithmetic = dwf_site: kernel D's results bit for bit.
 template <typename T, bool ZERO, bool BATCH>
 __global__ __launch_bounds__(BLOCK) void k_dwf_pair(const DwfArgs a) {
-  using namespace dwf;
   typedef T R;
   typedef T v4 __attribute__((ext_vector_type(4)));
   typedef T v2 __attribute__((ext_vector_type(2)));

@@ -21,7 +21,7 @@
 // a half row stay for the barrier and skip their loads' result and the store.  Two LDS buffers alternate, so one barrier per (row, system)
 // suffices: 2 x 256 chunks = 16 KiB per block in fp64, 8 KiB in fp32.
 #include "qmg_dwf_eo_plan.h"
-#include "qmg_dwf_lane.h"   // dwf::uni, gld, fmac2, hop_acc
+#include "qmg_lane.h"   // uni, gld, fmac2, dwf::hop_acc
 
 namespace qmg {
 

@@ -75,13 +75,9 @@ inline DwfEoPlan dwf_eo_plan(int dtype, int Lx, int Ly, int Ls, int kernel, unsi
     par_first = ev ? 0 : 1; par_count = (ev && od) ? 2 : 1;
   } else if (kernel == DEK_HOPS_INV5) {
     if (pieces & (QMG_P_CLOVER | QMG_P_SHIFT)) return refused(QMG_ERR_UNSUPPORTED);
-    const bool ev = pieces & (QMG_P_EO | QMG_P_ZERO_E), od = pieces & (QMG_P_OE | QMG_P_ZERO_O);
-    par_first = ev ? 0 : 1; par_count = (ev && od) ? 2 : 1;
-    for (int q = 0; q < par_count; q++) {
-      const int p = (par_count == 2) ? q : par_first;
-      if (((pieces >> (2 + 4 * p)) & 0xFu) != 0xFu) return refused(QMG_ERR_UNSUPPORTED);   // a partial hop set
-      if (!((pieces >> (12 + p)) & 1u)) zero = false;
-    }
+    const PieceShape ps = links_piece_shape(pieces);   // no clover or shift bit is left: a parity is named by its hop or zero bits
+    if (ps.shape != 2) return refused(QMG_ERR_UNSUPPORTED);   // a partial hop set
+    par_first = ps.par_first; par_count = ps.par_count; zero = ps.zero;
     if (inplace && par_count == 2) return refused(QMG_ERR_INVALID);   // in place: one parity written from the other
   } else {
     const unsigned even = QMG_P_CLOVER_E | QMG_P_EO | QMG_P_SHIFT_E | QMG_P_ZERO_E, odd = QMG_P_CLOVER_O | QMG_P_OE | QMG_P_SHIFT_O | QMG_P_ZERO_O;

@@ -5,6 +5,7 @@
 #define QMG_DWF_PLAN_H
 
 #include "qmg_common.h"
+#include "qmg_wilson_plan.h"   // links_piece_shape
 
 namespace qmg {
 
@@ -60,22 +61,10 @@ inline DwfPlan dwf_plan(int dtype, int Lx, int Ly, int Ls, unsigned pieces, int 
   const long lanes = (long)(Lx / 2) * Ls;
   if (lanes * 32 > 0x7FFFFFFFl) return refused(QMG_ERR_INVALID);   // a half row of the vector is addressed with 32-bit byte offsets
   if (n_active == 0) return nothing();
-  const unsigned even_bits = QMG_P_CLOVER_E | QMG_P_EO | QMG_P_SHIFT_E | QMG_P_ZERO_E;
-  const unsigned odd_bits = QMG_P_CLOVER_O | QMG_P_OE | QMG_P_SHIFT_O | QMG_P_ZERO_O;
-  const bool ev = pieces & even_bits, od = pieces & odd_bits;
-  if (!ev && !od) return nothing();
-  const int par_first = ev ? 0 : 1, par_count = (ev && od) ? 2 : 1;
-  // the compile-time shape, if every processed parity asks for the same complete set (the sets kernel W serves, qmg_wilson.hip)
-  int sh[2] = {0, 0};
-  bool zero = true;
-  for (int q = 0; q < par_count; q++) {
-    const int p = (par_count == 2) ? q : par_first;
-    const bool cl = (pieces >> p) & 1u, shf = (pieces >> (10 + p)) & 1u;
-    const unsigned hm = (pieces >> (2 + 4 * p)) & 0xFu;
-    sh[q] = (hm == 0xFu) ? (cl ? 1 : (shf ? 0 : 2)) : 0;
-    if (!((pieces >> (12 + p)) & 1u)) zero = false;
-  }
-  const int shape = (par_count == 2 && sh[0] != sh[1]) ? 0 : sh[0];
+  const PieceShape ps = links_piece_shape(pieces);   // the sets kernel W serves (qmg_wilson_plan.h)
+  if (ps.par_count == 0) return nothing();
+  const int par_first = ps.par_first, par_count = ps.par_count, shape = ps.shape;
+  const bool zero = ps.zero;
   if (shape == 0) return refused(QMG_ERR_UNSUPPORTED);
   if (inplace && (shape == 1 || par_count == 2)) return refused(QMG_ERR_INVALID);   // in place: one parity written from the other by hops alone
   const bool pair = shape == 1 && par_count == 2;   // the full operator: kernel D2

@@ -1,26 +1,34 @@
-// qmg_dwf_lane.h -- what a lane of the domain-wall kernels uses to address and accumulate: shared by csrc/qmg_dwf.hip (kernels D / D2) and
-// csrc/qmg_dwf_eo.hip (the even-odd kernels): block-uniform addressing, the complex multiply-add and the hop sum of a site.  Device code only.
-#ifndef QMG_DWF_LANE_H
-#define QMG_DWF_LANE_H
+// qmg_lane.h -- what a lane of the kernels that work from the gauge links (and of the site kernel) uses to address and accumulate: the ONE copy
+// of the block-uniform addressing (gchar, uni, gld, gld_nt) and of the complex multiply-add (fmac2), shared by csrc/qmg_wilson.hip (kernels
+// W / W2), csrc/qmg_site.hip (kernel S), csrc/qmg_dwf.hip (kernels D / D2) and csrc/qmg_dwf_eo.hip (the even-odd kernels), and the hop sum of a
+// domain-wall site (dwf::hop_acc).  Device code only.
+#ifndef QMG_LANE_H
+#define QMG_LANE_H
 
 #include "qmg_common.h"
 
 namespace qmg {
-namespace dwf {
+
+// a block-uniform (row-uniform) pointer, told to the compiler: the loads then take the scalar-base + 32-bit-offset form
+// (the result is a GLOBAL-address-space pointer: an integer cast to a plain pointer would make the accesses flat_load / flat_store)
 typedef __attribute__((address_space(1))) char gchar;
-// a block-uniform pointer, told to the compiler: the accesses take the scalar-base + 32-bit-offset form (as in qmg_wilson.hip)
 __device__ __forceinline__ gchar* uni(const char* p) {
   const unsigned long long v = reinterpret_cast<unsigned long long>(p);
   const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
   return (gchar*)(((unsigned long long)hi << 32) | lo);
 }
 template <typename V> __device__ __forceinline__ V gld(const gchar* base, unsigned off) { return *(const __attribute__((address_space(1))) V*)(base + off); }
+template <typename V> __device__ __forceinline__ V gld_nt(const gchar* base, unsigned off) {
+  return __builtin_nontemporal_load((const __attribute__((address_space(1))) V*)(base + off));
+}
 // acc += (mx + i my) (bx + i by)
 template <typename R>
 __device__ __forceinline__ void fmac2(R& ax, R& ay, R mx, R my, R bx, R by) {
   ax = fma(mx, bx, ax); ax = fma(-my, by, ax);
   ay = fma(mx, by, ay); ay = fma(my, bx, ay);
 }
+
+namespace dwf {
 // the four hops of one (site, s) pair from its chunks xr = {+x, +y, -x, -y} and links (backward ones already conjugated), added to the two
 // spin rows a0 (sigma 0) and a1 (sigma 1): the 2 x 2 spin blocks of the Wilson operator; hw = -w/2.  The even-odd kernels call this;
 // dwf_site (qmg_dwf.hip) keeps its own copy of the loop: calling this one there gives the same instructions in another order and register

@@ -26,6 +26,7 @@
 #include <hip/hip_fp16.h>
 
 #include "qmg_common.h"
+#include "qmg_lane.h"   // fmac2
 #include "qmg_stencil_plan.h"
 
 namespace qmg {
@@ -63,11 +64,6 @@ template <> struct SiteT<2> { typedef double R; static constexpr int LPS = 4; };
 __device__ __forceinline__ v4f ld16(const void* p, long chunk) { return *(reinterpret_cast<const v4f*>(p) + chunk); }
 __device__ __forceinline__ v4f ld16_nt(const void* p, long chunk) { return __builtin_nontemporal_load(reinterpret_cast<const v4f*>(p) + chunk); }
 
-template <typename R>
-__device__ __forceinline__ void fmac2(R& ax, R& ay, R mx, R my, R bx, R by) {
-  ax = fma(mx, bx, ax); ax = fma(-my, by, ax);
-  ay = fma(mx, by, ay); ay = fma(my, bx, ay);
-}
 __device__ __forceinline__ v2d as_d(const v4f raw) { return __builtin_bit_cast(v2d, raw); }
 
 // One term: acc += (this lane's part of the 2x2 matrix) * (the right-hand-side chunk).  Accumulators:

@@ -23,9 +23,12 @@
 // 2x2 product leaves in memory, so the Schur-complement applies of the K-cycle stream 128 instead of 320 B per written site.
 // y-slabs: the links are indexed on the GLOBAL lattice (replicated, 32 B/site), only the right-hand side's rows
 // -1 / Ly come from halo buffers.
+// Which of the three kernels serves a request, on which grid and in which compile-time form, and every refusal: wilson_plan
+// (qmg_wilson_plan.h, host only); the entry point fills WilsonArgs from the plan and launch_wilson launches what it names.
 #include <type_traits>
 
-#include "qmg_common.h"
+#include "qmg_lane.h"          // gchar, uni, gld, gld_nt, fmac2
+#include "qmg_wilson_plan.h"
 
 namespace qmg {
 
@@ -56,25 +59,6 @@ struct WilsonArgs {
 typedef float w4f __attribute__((ext_vector_type(4)));
 typedef float w2f __attribute__((ext_vector_type(2)));
 typedef double w2d __attribute__((ext_vector_type(2)));
-
-template <typename R>
-__device__ __forceinline__ void fmac2w(R& ax, R& ay, R mx, R my, R bx, R by) {
-  ax = fma(mx, bx, ax); ax = fma(-my, by, ax);
-  ay = fma(mx, by, ay); ay = fma(my, bx, ay);
-}
-
-// a row-uniform pointer, told to the compiler: the loads then take the scalar-base + 32-bit-offset form
-// (the result is a GLOBAL-address-space pointer: an integer cast to a plain pointer would make the accesses flat_load / flat_store)
-typedef __attribute__((address_space(1))) char gchar;
-__device__ __forceinline__ gchar* uni(const char* p) {
-  const unsigned long long v = reinterpret_cast<unsigned long long>(p);
-  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-  return (gchar*)(((unsigned long long)hi << 32) | lo);
-}
-template <typename V> __device__ __forceinline__ V gld(const gchar* base, unsigned off) { return *(const __attribute__((address_space(1))) V*)(base + off); }
-template <typename V> __device__ __forceinline__ V gld_nt(const gchar* base, unsigned off) {
-  return __builtin_nontemporal_load((const __attribute__((address_space(1))) V*)(base + off));
-}
 
 // the four hop matrices' entries [row][col] for column c from the links (k_wilson_fill's multiplications, qmg_fill.hip)
 template <typename R>
@@ -138,20 +122,20 @@ __device__ __forceinline__ void wilson_site(const w4f (&xr)[5], const T (&lx)[4]
     R vx, vy;
     if (SHAPE == 1) {   // clover first: 2w on the diagonal (row == col)
       comp(xr[4], vx, vy);
-      fmac2w<R>(ax[cc][c], ay[cc][c], cw, (R)0, vx, vy);
+      fmac2<R>(ax[cc][c], ay[cc][c], cw, (R)0, vx, vy);
     }
 #pragma unroll
     for (int d = 0; d < 4; d++) {
       comp(xr[d], vx, vy);
       const HopCol<R> m = hop_col<R, SHAPE == 3>(d, c, lx[d], ly[d], hw, (R)a.hop_scale);
-      fmac2w<R>(ax[cc][0], ay[cc][0], m.m0x, m.m0y, vx, vy);
-      fmac2w<R>(ax[cc][1], ay[cc][1], m.m1x, m.m1y, vx, vy);
+      fmac2<R>(ax[cc][0], ay[cc][0], m.m0x, m.m0y, vx, vy);
+      fmac2<R>(ax[cc][1], ay[cc][1], m.m1x, m.m1y, vx, vy);
     }
     if (do_shift) {   // shift +- eo_shift +- dof_shift on the diagonal (stencil_2d.h:890-908)
       const double sg = p ? -1.0 : 1.0, dg = c ? -1.0 : 1.0;
       const R sx = (R)(a.shift[0] + sg * a.eo_shift[0] + dg * a.dof_shift[0]), sy = (R)(a.shift[1] + sg * a.eo_shift[1] + dg * a.dof_shift[1]);
       comp(xr[4], vx, vy);
-      fmac2w<R>(ax[cc][c], ay[cc][c], sx, sy, vx, vy);
+      fmac2<R>(ax[cc][c], ay[cc][c], sx, sy, vx, vy);
     }
   }
   if (F64) {
@@ -502,32 +486,46 @@ __global__ __launch_bounds__(BLOCK) void k_wilson_pair2(const WilsonArgs a) {
   if (EPI && EPI != 2) wilson_store_partials(a, ed);
 }
 
-// one system, overwrite, with the epilogue in mode `m` (1-4; mode 1 needs the own-site chunk: SHAPE 1)
+// THE launch of this unit: the instantiation wilson_plan names, and only those it can name (tests/test_host_wilson_plan.py counts them).
+// A launch with an epilogue is one system with overwrite (wilson_plan, steps 6 and 13): ZERO, not BATCH.
 template <typename T, int SHAPE>
-static void launch_wilson_epi_s(const WilsonArgs& a, int m, dim3 grid, hipStream_t st) {
-  if (m == 1) k_wilson_direct<T, SHAPE, true, false, (SHAPE == 1 ? 1 : 4)><<<grid, BLOCK, 0, st>>>(a);
-  else if (m == 2) k_wilson_direct<T, SHAPE, true, false, 2><<<grid, BLOCK, 0, st>>>(a);
-  else if (m == 3) k_wilson_direct<T, SHAPE, true, false, 3><<<grid, BLOCK, 0, st>>>(a);
-  else k_wilson_direct<T, SHAPE, true, false, 4><<<grid, BLOCK, 0, st>>>(a);
+static void launch_wilson_w(const WilsonPlan& pl, const WilsonArgs& a, dim3 grid, hipStream_t st) {
+  const bool zero = pl.flags & WPF_ZERO, batch = pl.flags & WPF_BATCH;
+  switch (pl.emode) {
+    case 0:
+      if (zero) { if (batch) k_wilson_direct<T, SHAPE, true, true><<<grid, BLOCK, 0, st>>>(a); else k_wilson_direct<T, SHAPE, true, false><<<grid, BLOCK, 0, st>>>(a); }
+      else { if (batch) k_wilson_direct<T, SHAPE, false, true><<<grid, BLOCK, 0, st>>>(a); else k_wilson_direct<T, SHAPE, false, false><<<grid, BLOCK, 0, st>>>(a); }
+      break;
+    case 1:   // dots against the own-site chunk: the plan gives this mode to shape 1 only
+      if constexpr (SHAPE == 1) k_wilson_direct<T, 1, true, false, 1><<<grid, BLOCK, 0, st>>>(a);
+      break;
+    case 2: k_wilson_direct<T, SHAPE, true, false, 2><<<grid, BLOCK, 0, st>>>(a); break;
+    case 3: k_wilson_direct<T, SHAPE, true, false, 3><<<grid, BLOCK, 0, st>>>(a); break;
+    default: k_wilson_direct<T, SHAPE, true, false, 4><<<grid, BLOCK, 0, st>>>(a);
+  }
 }
 template <typename T>
-static void launch_wilson_epi(const WilsonArgs& a, int shape, int m, dim3 grid, hipStream_t st) {
-  if (shape == 1) launch_wilson_epi_s<T, 1>(a, m, grid, st);
-  else if (shape == 3) launch_wilson_epi_s<T, 3>(a, m, grid, st);
-  else launch_wilson_epi_s<T, 2>(a, m, grid, st);
-}
-template <typename T>
-static void launch_wilson_pair_epi(const WilsonArgs& a, int m, bool two_rows, dim3 grid, hipStream_t st) {
-#define QMG_WP(M) { if (two_rows) k_wilson_pair2<T, true, M><<<grid, BLOCK, 0, st>>>(a); else k_wilson_pair<T, true, false, M><<<grid, BLOCK, 0, st>>>(a); }
-  if (m == 1) QMG_WP(1) else if (m == 2) QMG_WP(2) else if (m == 3) QMG_WP(3) else QMG_WP(4)
-#undef QMG_WP
-}
-
-template <typename T, bool BATCH>
-static void launch_wilson_b(const WilsonArgs& a, int shape, bool zero, dim3 grid, hipStream_t st) {
-  if (shape == 1) { if (zero) k_wilson_direct<T, 1, true, BATCH><<<grid, BLOCK, 0, st>>>(a); else k_wilson_direct<T, 1, false, BATCH><<<grid, BLOCK, 0, st>>>(a); }
-  else if (shape == 3) { if (zero) k_wilson_direct<T, 3, true, BATCH><<<grid, BLOCK, 0, st>>>(a); else k_wilson_direct<T, 3, false, BATCH><<<grid, BLOCK, 0, st>>>(a); }
-  else { if (zero) k_wilson_direct<T, 2, true, BATCH><<<grid, BLOCK, 0, st>>>(a); else k_wilson_direct<T, 2, false, BATCH><<<grid, BLOCK, 0, st>>>(a); }
+static void launch_wilson(const WilsonPlan& pl, const WilsonArgs& a, hipStream_t st) {
+  const dim3 grid((unsigned)pl.gx, (unsigned)pl.gy);
+  const bool zero = pl.flags & WPF_ZERO, batch = pl.flags & WPF_BATCH;
+  if (pl.family == WF_PAIR2) {   // modes 2-4 never come here (wilson_plan): they are not compiled
+    if (pl.emode == 1) k_wilson_pair2<T, true, 1><<<grid, BLOCK, 0, st>>>(a);
+    else if (zero) k_wilson_pair2<T, true><<<grid, BLOCK, 0, st>>>(a);
+    else k_wilson_pair2<T, false><<<grid, BLOCK, 0, st>>>(a);
+  } else if (pl.family == WF_PAIR) {
+    switch (pl.emode) {
+      case 0:
+        if (zero) { if (batch) k_wilson_pair<T, true, true><<<grid, BLOCK, 0, st>>>(a); else k_wilson_pair<T, true, false><<<grid, BLOCK, 0, st>>>(a); }
+        else { if (batch) k_wilson_pair<T, false, true><<<grid, BLOCK, 0, st>>>(a); else k_wilson_pair<T, false, false><<<grid, BLOCK, 0, st>>>(a); }
+        break;
+      case 1: k_wilson_pair<T, true, false, 1><<<grid, BLOCK, 0, st>>>(a); break;
+      case 2: k_wilson_pair<T, true, false, 2><<<grid, BLOCK, 0, st>>>(a); break;
+      case 3: k_wilson_pair<T, true, false, 3><<<grid, BLOCK, 0, st>>>(a); break;
+      default: k_wilson_pair<T, true, false, 4><<<grid, BLOCK, 0, st>>>(a);
+    }
+  } else if (pl.shape == 1) launch_wilson_w<T, 1>(pl, a, grid, st);
+  else if (pl.shape == 3) launch_wilson_w<T, 3>(pl, a, grid, st);
+  else launch_wilson_w<T, 2>(pl, a, grid, st);
 }
 
 }  // namespace qmg
@@ -548,7 +546,7 @@ extern "C" {
 int qmg_wilson_hops_direct(int dtype, const qmg_stencil_desc* d, const void* gauge, int gauge_Ly, int y0, double wilson_coeff, double hop_scale, void* lhs,
                            const void* rhs, const void* halo_lo, const void* halo_hi, unsigned pieces, int nrhs, size_t vec_stride, size_t halo_stride,
                            unsigned mask, int rows, void* stream) {
-  if (pieces & (QMG_P_CLOVER | QMG_P_SHIFT)) return QMG_ERR_UNSUPPORTED;
+  if (pieces & (QMG_P_CLOVER | QMG_P_SHIFT)) return QMG_ERR_UNSUPPORTED;   // before the pointer checks; wilson_plan states it again, as its step 1
   return wilson_direct_impl(dtype, d, gauge, gauge_Ly, y0, wilson_coeff, true, hop_scale, lhs, rhs, halo_lo, halo_hi, pieces, nrhs, vec_stride, halo_stride, mask,
                             rows, stream);
 }
@@ -584,125 +582,60 @@ int qmg_wilson_hops_direct_epi(int dtype, const qmg_stencil_desc* d, const void*
                             0, stream, epi);
 }
 
+// What the four entries above do with a request (include/qmg_hip.h), at the current "wilson_pair"
+int qmg_wilson_plan(int dtype, int Lx, int Ly, int nc, int gauge_Ly, int y0, int halos, int layout_ok, int scaled, unsigned pieces, int n_active, int inplace,
+                    int rows, unsigned epi, int* plan_out, int plan_len) {
+  if (!plan_out || plan_len < WILSON_PLAN_INTS) return QMG_ERR_INVALID;
+  WilsonRequest q = {};
+  q.dtype = dtype; q.Lx = Lx; q.Ly = Ly; q.nc = nc; q.gauge_Ly = gauge_Ly; q.y0 = y0; q.halos = halos; q.layout_ok = layout_ok; q.scaled = scaled;
+  q.pieces = pieces; q.n_active = n_active; q.inplace = inplace; q.rows = rows; q.pair = g_wilson_pair; q.epi = epi;
+  const WilsonPlan pl = wilson_plan(q);
+  const int v[WILSON_PLAN_INTS] = {pl.family, pl.lps, pl.block, pl.gx, pl.gy, pl.flags, pl.shape, pl.emode, pl.nk, pl.y_first, pl.y_count, pl.boundary_only,
+                                   pl.npart, pl.status, pl.par_first, pl.par_count};
+  for (int i = 0; i < plan_len; i++) plan_out[i] = i < WILSON_PLAN_INTS ? v[i] : -1;
+  return QMG_SUCCESS;
+}
+
 }  // extern "C"
 
 static int wilson_direct_impl(int dtype, const qmg_stencil_desc* d, const void* gauge, int gauge_Ly, int y0, double wilson_coeff, bool scaled, double hop_scale,
                               void* lhs, const void* rhs, const void* halo_lo, const void* halo_hi, unsigned pieces, int nrhs, size_t vec_stride,
                               size_t halo_stride, unsigned mask, int rows, void* stream, const qmg_apply_epilogue* epi) {
-  if (!valid_dtype(dtype) || !d || !gauge || !lhs || !rhs || nrhs < 1 || nrhs > 16 || rows < 0 || rows > 2) return QMG_ERR_INVALID;
-  if (!valid_lattice(d->Lx, d->Ly) || !valid_lattice(d->Lx, gauge_Ly) || y0 < 0 || (y0 & 1) || y0 + d->Ly > gauge_Ly) return QMG_ERR_INVALID;
-  if (d->nc != 2) return QMG_ERR_UNSUPPORTED;
-  if ((halo_lo == nullptr) != (halo_hi == nullptr)) return QMG_ERR_INVALID;
-  if (!halo_lo && (gauge_Ly != d->Ly || rows != 0)) return QMG_ERR_INVALID;   // a slab needs its halos
-  if (nrhs > 1 && (vec_stride < (size_t)d->Lx * d->Ly * 2 || (halo_lo && halo_stride < (size_t)d->Lx * 2))) return QMG_ERR_INVALID;
+  if (!d || !gauge || !lhs || !rhs || nrhs < 1 || nrhs > BATCH_MAX) return QMG_ERR_INVALID;
+  const BatchIdx b = expand_mask(mask, nrhs);
+  WilsonRequest q = {};   // the call as wilson_plan sees it
+  q.dtype = dtype; q.Lx = d->Lx; q.Ly = d->Ly; q.nc = d->nc; q.gauge_Ly = gauge_Ly; q.y0 = y0;
+  q.halos = halo_lo && halo_hi;
+  q.layout_ok = (halo_lo == nullptr) == (halo_hi == nullptr) &&
+                !(nrhs > 1 && (vec_stride < (size_t)d->Lx * d->Ly * 2 || (halo_lo && halo_stride < (size_t)d->Lx * 2)));
+  q.scaled = scaled; q.pieces = pieces; q.n_active = b.n; q.inplace = lhs == rhs; q.rows = rows; q.pair = g_wilson_pair;
+  if (epi)
+    q.epi = WPE_ON | (epi->other ? WPE_OTHER : 0) | (epi->dotv ? WPE_DOTV : 0) | (epi->dotv && epi->dotv == epi->other ? WPE_DOTV_IS_OTHER : 0) |
+            (epi->dotv == rhs ? WPE_DOTV_IS_RHS : 0) | (epi->other == lhs || epi->dotv == lhs ? WPE_ALIASES_LHS : 0);
+  const WilsonPlan pl = wilson_plan(q);
+  if (pl.family == WF_NOTHING) return QMG_SUCCESS;
+  if (pl.status != QMG_SUCCESS) return pl.status;
   WilsonArgs a;
   a.gauge = gauge; a.lhs = lhs; a.rhs = rhs;
   a.hr = d->Lx / 2; a.Ly = d->Ly; a.gLy = gauge_Ly; a.gy0 = y0;
   a.half_vol = (long)a.hr * d->Ly; a.ghalf_vol = (long)a.hr * gauge_Ly;
-  a.pieces = pieces; a.vec_stride = (long)vec_stride; a.w = wilson_coeff; a.hop_scale = hop_scale;
-  a.nrhs = 0;
-  for (int k = 0; k < 16; k++) a.ridx[k] = 0;
-  for (int k = 0; k < nrhs; k++)
-    if ((mask >> k) & 1u) a.ridx[a.nrhs++] = k;
-  if (a.nrhs == 0) return QMG_SUCCESS;
-  a.epi = no_epilogue();
-  if (epi) {
-    if (a.nrhs != 1) return QMG_ERR_UNSUPPORTED;      // one system per launch
-    if (epi->other == lhs || epi->dotv == lhs) return QMG_ERR_INVALID;
-    a.epi.on = 1;
-    a.epi.other = epi->other; a.epi.other_scale = epi->other_scale; a.epi.acc_scale = epi->acc_scale; a.epi.dotv = epi->dotv;
-    if (epi->other && epi->dotv && epi->other != epi->dotv) return QMG_ERR_UNSUPPORTED;   // two different extra vectors: the separate passes
-  }
+  a.pieces = pieces; a.nrhs = pl.nk; a.vec_stride = (long)vec_stride;
+  a.par_first = pl.par_first; a.par_count = pl.par_count; a.nrows = pl.y_count * pl.par_count;
+  a.w = wilson_coeff; a.hop_scale = hop_scale;
   for (int i = 0; i < 2; i++) { a.shift[i] = d->shift[i]; a.eo_shift[i] = d->eo_shift[i]; a.dof_shift[i] = d->dof_shift[i]; }
-  const unsigned even_bits = QMG_P_CLOVER_E | QMG_P_EO | QMG_P_SHIFT_E | QMG_P_ZERO_E;
-  const unsigned odd_bits = QMG_P_CLOVER_O | QMG_P_OE | QMG_P_SHIFT_O | QMG_P_ZERO_O;
-  const bool ev = pieces & even_bits, od = pieces & odd_bits;
-  if (!ev && !od) return QMG_SUCCESS;
-  a.par_first = ev ? 0 : 1;
-  a.par_count = (ev && od) ? 2 : 1;
+  for (int k = 0; k < 16; k++) a.ridx[k] = b.id[k];
   a.halo_lo = halo_lo; a.halo_hi = halo_hi; a.halo_stride = (long)halo_stride;
-  a.boundary_only = rows == 2;
-  a.y_first = rows == 1 ? 1 : 0;
-  a.y_count = rows == 2 ? 2 : rows == 1 ? d->Ly - 2 : d->Ly;
-  if (a.y_count <= 0) return QMG_SUCCESS;
-  a.nrows = a.y_count * a.par_count;
-  int sh[2] = {0, 0};
-  bool zero = true;
-  for (int q = 0; q < a.par_count; q++) {
-    const int p = (a.par_count == 2) ? q : a.par_first;
-    const bool cl = (pieces >> p) & 1u, shf = (pieces >> (10 + p)) & 1u;
-    const unsigned hm = (pieces >> (2 + 4 * p)) & 0xFu;
-    sh[q] = (hm == 0xFu) ? (cl ? 1 : (shf ? 0 : 2)) : 0;
-    if (!((pieces >> (12 + p)) & 1u)) zero = false;
+  a.y_first = pl.y_first; a.y_count = pl.y_count; a.boundary_only = pl.boundary_only;
+  a.epi = no_epilogue();
+  if (epi) { a.epi.on = 1; a.epi.other = epi->other; a.epi.other_scale = epi->other_scale; a.epi.acc_scale = epi->acc_scale; a.epi.dotv = epi->dotv; }
+  if (pl.npart) {   // the MR dots' partials: one per wavefront of the launch
+    a.epi.part = mr_epilogue_begin(1, pl.npart);
+    a.epi.npart = pl.npart;
+    if (!a.epi.part) return QMG_ERR_HIP;
   }
-  int shape = (a.par_count == 2 && sh[0] != sh[1]) ? 0 : sh[0];
-  if (shape == 0 || (scaled && shape != 2)) return QMG_ERR_UNSUPPORTED;
-  if (scaled) shape = 3;
-  if (lhs == rhs && (shape == 1 || a.par_count == 2)) return QMG_ERR_INVALID;
-  if (epi && (!zero || lhs == rhs)) return QMG_ERR_INVALID;   // an epilogue needs overwrite semantics and a separate output
-  const int lps = dtype == QMG_C64 ? 2 : 1;
-  const long lanes = (long)a.hr * lps;
-  dim3 grid((unsigned)((lanes + BLOCK - 1) / BLOCK), a.nrows > 65535 ? 65535u : (unsigned)a.nrows);
   hipStream_t st = as_stream(stream);
-  // the epilogue's dot partials: one per wavefront of the launch that is chosen below
-  long epi_npart = 0;
-  // epilogue mode (wilson_site): 1 dots against the right-hand side (own-site chunk; needs SHAPE 1, else the vector is loaded: mode 4),
-  // 2 combination only, 3 combination + dots against the same vector, 4 dots against a separate vector
-  int emode = 0;
-  if (a.epi.on) {
-    if (!a.epi.other && !a.epi.dotv) emode = 2;                       // a pure scaling of the result (other_scale is moot): served by mode 2 with no vector
-    else if (a.epi.other && !a.epi.dotv) emode = 2;
-    else if (a.epi.other) emode = 3;
-    else emode = (a.epi.dotv == rhs && shape == 1) ? 1 : 4;
-  }
-  // launches with the MR dots keep the number of partials (one per wavefront) small enough for the one-block second stage: the blocks
-  // walk several rows each (every kernel W form has the row loop; capping grid.y costs nothing)
-  auto epi_cap = [&](dim3& g) { if (a.epi.on && a.epi.dotv) { const unsigned cap = g.x >= 2048u ? 1u : 2048u / g.x; if (g.y > cap) g.y = cap; } };
-  auto epi_begin = [&](dim3 g) -> bool {
-    if (!(a.epi.on && a.epi.dotv)) return true;
-    epi_npart = (long)g.x * (long)g.y * (BLOCK / WAVE);
-    a.epi.part = mr_epilogue_begin(1, epi_npart);
-    a.epi.npart = epi_npart;
-    return a.epi.part != nullptr;
-  };
-  auto epi_finish = [&]() -> int {
-    if (!epi_npart) return QMG_SUCCESS;
-    const unsigned char id0 = (unsigned char)a.ridx[0];
-    return mr_epilogue_finish(&id0, 1, epi_npart, st);
-  };
-  // (an epilogue that loads a vector -- modes 2-4 -- would take the two-row form to 170-178 VGPRs, two wavefronts per SIMD: those go through the one-row form)
-  if (shape == 1 && a.par_count == 2 && g_wilson_pair >= 2 && a.nrhs == 1 && !a.boundary_only && a.y_count % 2 == 0 && emode <= 1) {
-    // one system, an even run of consecutive rows: kernel W2 on two rows per lane group
-    const int ny = a.y_count / 2;   // (capping grid.y -- a row-pair loop per block -- changes nothing: 0.29-0.31 ms at every cap)
-    dim3 gridp(grid.x, ny > 65535 ? 65535u : (unsigned)ny);
-    epi_cap(gridp);
-    if (!epi_begin(gridp)) return QMG_ERR_HIP;
-    if (a.epi.on) { if (dtype == QMG_C64) launch_wilson_pair_epi<double>(a, emode, true, gridp, st); else launch_wilson_pair_epi<float>(a, emode, true, gridp, st); }
-    else if (dtype == QMG_C64) { if (zero) k_wilson_pair2<double, true><<<gridp, BLOCK, 0, st>>>(a); else k_wilson_pair2<double, false><<<gridp, BLOCK, 0, st>>>(a); }
-    else { if (zero) k_wilson_pair2<float, true><<<gridp, BLOCK, 0, st>>>(a); else k_wilson_pair2<float, false><<<gridp, BLOCK, 0, st>>>(a); }
-    QMG_LAUNCH_CHECK();
-    return epi_finish();
-  }
-  if (shape == 1 && a.par_count == 2 && g_wilson_pair) {   // the full operator: both parities of a column per lane group (kernel W2)
-    dim3 gridp(grid.x, a.y_count > 65535 ? 65535u : (unsigned)a.y_count);
-    epi_cap(gridp);
-    if (!epi_begin(gridp)) return QMG_ERR_HIP;
-    if (a.epi.on) { if (dtype == QMG_C64) launch_wilson_pair_epi<double>(a, emode, false, gridp, st); else launch_wilson_pair_epi<float>(a, emode, false, gridp, st); }
-    else if (dtype == QMG_C64) {
-      if (a.nrhs == 1) { if (zero) k_wilson_pair<double, true, false><<<gridp, BLOCK, 0, st>>>(a); else k_wilson_pair<double, false, false><<<gridp, BLOCK, 0, st>>>(a); }
-      else { if (zero) k_wilson_pair<double, true, true><<<gridp, BLOCK, 0, st>>>(a); else k_wilson_pair<double, false, true><<<gridp, BLOCK, 0, st>>>(a); }
-    } else {
-      if (a.nrhs == 1) { if (zero) k_wilson_pair<float, true, false><<<gridp, BLOCK, 0, st>>>(a); else k_wilson_pair<float, false, false><<<gridp, BLOCK, 0, st>>>(a); }
-      else { if (zero) k_wilson_pair<float, true, true><<<gridp, BLOCK, 0, st>>>(a); else k_wilson_pair<float, false, true><<<gridp, BLOCK, 0, st>>>(a); }
-    }
-    QMG_LAUNCH_CHECK();
-    return epi_finish();
-  }
-  epi_cap(grid);
-  if (!epi_begin(grid)) return QMG_ERR_HIP;
-  if (a.epi.on) { if (dtype == QMG_C64) launch_wilson_epi<double>(a, shape, emode, grid, st); else launch_wilson_epi<float>(a, shape, emode, grid, st); }
-  else if (dtype == QMG_C64) { if (a.nrhs == 1) launch_wilson_b<double, false>(a, shape, zero, grid, st); else launch_wilson_b<double, true>(a, shape, zero, grid, st); }
-  else { if (a.nrhs == 1) launch_wilson_b<float, false>(a, shape, zero, grid, st); else launch_wilson_b<float, true>(a, shape, zero, grid, st); }
+  if (dtype == QMG_C64) launch_wilson<double>(pl, a, st); else launch_wilson<float>(pl, a, st);
   QMG_LAUNCH_CHECK();
-  return epi_finish();
+  if (!pl.npart) return QMG_SUCCESS;
+  return mr_epilogue_finish(&b.id[0], 1, pl.npart, st);
 }
