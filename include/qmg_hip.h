@@ -693,6 +693,35 @@ int qmg_dwf_schur_apply(int dtype, const qmg_stencil_desc* d, const void* gauge,
  * QMG_ERR_INVALID: plan_out missing or plan_len below 8. */
 int qmg_dwf_eo_plan(int dtype, int Lx, int Ly, int Ls, int kernel, unsigned pieces, int n_active, int inplace, int* plan_out, int plan_len);
 
+/* ---------------- domain-wall measurements: wall source, wall / midpoint projection, slice norms (csrc/qmg_dwf_meas.hip) ----------------
+ * A 5D vector has nc = 2 Ls components per site (c = 2 s + sigma), a 4D one nc = 2 (sigma); sigma = 0 is the P_+ component (the one that crosses
+ * the wall as out(0, 0) += m psi(Ls-1, 0)), sigma = 1 P_-.  Whole lattice only.  Common to the three entries: dtype QMG_C64 / QMG_C32, Ls in
+ * 2 .. 32, nsys in 1 .. 16 systems `stride` elements apart (ignored for nsys == 1; at least a vector, and even for QMG_C32), 16-byte aligned
+ * vectors; anything else is QMG_ERR_INVALID before a launch.  Input and output must not overlap.
+ * psi5 = the wall source of eta4, every element of psi5 overwritten:  psi5(x; 0, 0) = eta4(x, 0),  psi5(x; Ls-1, 1) = eta4(x, 1),  0 elsewhere. */
+int qmg_dwf_wall_source(int dtype, int Lx, int Ly, int Ls, void* psi5, const void* eta4, int nsys, size_t stride5, size_t stride4, void* stream);
+/* which = 0, the physical quark field:  q4(x, 0) = psi5(x; Ls-1, 0),  q4(x, 1) = psi5(x; 0, 1);
+ * which = 1, the midpoint field:        q4(x, 0) = psi5(x; Ls/2-1, 0),  q4(x, 1) = psi5(x; Ls/2, 1) -- odd Ls: QMG_ERR_UNSUPPORTED.
+ * Any other `which`: QMG_ERR_INVALID.  Only the two half chunks of a site that are needed are read. */
+int qmg_dwf_wall_project(int dtype, int Lx, int Ly, int Ls, void* q4, const void* psi5, int which, int nsys, size_t stride4, size_t stride5, void* stream);
+/* out[sys][y][s][sigma] = sum_x |psi5(x, y; s, sigma)|^2 -- 2 Ls Ly doubles per system, accumulated in fp64 for both dtypes, in one pass over the
+ * vector (32 Ls B/site in fp64) plus a small second launch that adds per-block partials in a fixed order: no atomics, the same bits on every
+ * run.  out_dev (device) and / or out_host (host; the stream is then synchronised) as in qmg_norm2sq_cv_timeslice: at least one.  The partials
+ * live in a device buffer of the calling thread that grows on demand and is held until qmg_shutdown. */
+int qmg_dwf_slice_norms(int dtype, int Lx, int Ly, int Ls, const void* psi5, int nsys, size_t stride5, double* out_dev, double* out_host, void* stream);
+/* What the three entries launch: the answer of the one host function they switch on.  Host only, no HIP call.
+ * kernel: 0 wall source, 1 wall projection, 2 midpoint projection, 3 slice norms.  Writes 8 ints and -1 into the rest of plan_out:
+ *   family  0 unsupported (midpoint with odd Ls), 1 k_dwf_wall_source, 2 k_dwf_wall_project, 3 invalid, 4 k_dwf_slice_norms + k_dwf_slice_sum
+ *   lps     lanes per site: Ls (source, norms: a lane owns one (site, s) pair with its two spin components), 2 (projections)
+ *   block   threads per block: 256; for the norms Ls floor(256 / Ls), so that a lane that strides by whole blocks keeps its s
+ *   gx, gy  the grid: gx blocks over the lps Lx/2 lanes of a half row (norms: gx = pbr), gy = min(2 Ly, 65535) blocks walk the (parity, y)
+ *           rows; the systems go over grid.z
+ *   pbr     norms: partial sums per (parity, y) row -- min(blocks that cover the half row, 4) blocks stride over it; else 0
+ *   lds     bytes of LDS per block (norms: two doubles per lane of the largest block; else 0)
+ *   nk      the systems served
+ * QMG_ERR_INVALID: plan_out missing or plan_len below 8. */
+int qmg_dwf_meas_plan(int dtype, int Lx, int Ly, int Ls, int kernel, int nsys, int* plan_out, int plan_len);
+
 /* ---------------- tuning hooks (not part of the reference surface) ---------------- */
 /* Dispatch / codegen knobs, all with the defaults the measurements in profiles/ chose; results never depend on them
  * beyond summation order.  Unknown keys, and values a key does not take, return QMG_ERR_INVALID.

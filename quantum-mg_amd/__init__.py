@@ -56,6 +56,7 @@ ABI_SYMBOLS = [
     "qmg_u1_flow_stage", "qmg_u1_flow", "qmg_u1_wilson_loops", "qmg_u1_polyakov",
     "qmg_dwf_fill", "qmg_dwf_apply_direct", "qmg_dwf_plan", "qmg_batch_plan", "qmg_wilson_plan",
     "qmg_dwf_inv5", "qmg_dwf_hops_inv5", "qmg_dwf_schur_apply", "qmg_dwf_eo_plan",
+    "qmg_dwf_wall_source", "qmg_dwf_wall_project", "qmg_dwf_slice_norms", "qmg_dwf_meas_plan",
 ]
 
 
@@ -838,6 +839,52 @@ def dwf_eo_plan(dtype, dims, Ls, kernel, pieces, n_active=1, inplace=False):
     """What the even-odd entries launch (qmg_dwf_eo_plan; host only): (family, lps, block, gx, gy, flags, lds, nk)."""
     out = (C.c_int * DWF_EO_PLAN_INTS)()
     check(lib().qmg_dwf_eo_plan(dtype, dims[0], dims[1], Ls, kernel, C.c_uint(pieces), n_active, int(inplace), out, DWF_EO_PLAN_INTS), "qmg_dwf_eo_plan")
+    return tuple(out)
+
+
+# ---- domain-wall measurements: wall source, wall / midpoint projection, slice norms (csrc/qmg_dwf_meas.hip)
+# the `kernel` argument and the families of qmg_dwf_meas_plan (include/qmg_hip.h)
+DMK_SOURCE, DMK_PROJECT_WALL, DMK_PROJECT_MID, DMK_NORMS = range(4)
+DMF_UNSUPPORTED, DMF_SOURCE, DMF_PROJECT, DMF_INVALID, DMF_NORMS = range(5)
+DWF_MEAS_PLAN_INTS = 8
+
+
+def dwf_wall_source_status(dtype, dims, Ls, psi5, eta4, nsys=1, stride5=0, stride4=0, stream=None):
+    """qmg_dwf_wall_source's status, unchecked: psi5(x; 0, 0) = eta4(x, 0), psi5(x; Ls-1, 1) = eta4(x, 1), zero elsewhere."""
+    return lib().qmg_dwf_wall_source(dtype, dims[0], dims[1], Ls, _vp(psi5), _vp(eta4), nsys, C.c_size_t(stride5), C.c_size_t(stride4), C.c_void_p(stream))
+
+
+def dwf_wall_source(*args, **kw):
+    check(dwf_wall_source_status(*args, **kw), "qmg_dwf_wall_source")
+
+
+def dwf_wall_project_status(dtype, dims, Ls, q4, psi5, which=0, nsys=1, stride4=0, stride5=0, stream=None):
+    """qmg_dwf_wall_project's status, unchecked: which = 0 the walls (Ls-1, 0), (0, 1); 1 the midpoint (Ls/2-1, 0), (Ls/2, 1)."""
+    return lib().qmg_dwf_wall_project(dtype, dims[0], dims[1], Ls, _vp(q4), _vp(psi5), which, nsys, C.c_size_t(stride4), C.c_size_t(stride5), C.c_void_p(stream))
+
+
+def dwf_wall_project(*args, **kw):
+    check(dwf_wall_project_status(*args, **kw), "qmg_dwf_wall_project")
+
+
+def dwf_slice_norms_status(dtype, dims, Ls, psi5, nsys=1, stride5=0, out_dev=None, out_host=None, stream=None):
+    """qmg_dwf_slice_norms's status, unchecked; out_host: a float64 array of nsys * Ly * 2 Ls numbers or None."""
+    host = None if out_host is None else out_host.ctypes.data_as(C.POINTER(C.c_double))
+    return lib().qmg_dwf_slice_norms(dtype, dims[0], dims[1], Ls, _vp(psi5), nsys, C.c_size_t(stride5), C.cast(_vp(out_dev), C.POINTER(C.c_double)), host,
+                                     C.c_void_p(stream))
+
+
+def dwf_slice_norms(dtype, dims, Ls, psi5, nsys=1, stride5=0, out_dev=None, stream=None):
+    """N[sys, y, s, sigma] = sum_x |psi5(x, y; s, sigma)|^2 on the host (and in out_dev where given)."""
+    out = np.empty((nsys, dims[1], Ls, 2), dtype=np.float64)
+    check(dwf_slice_norms_status(dtype, dims, Ls, psi5, nsys, stride5, out_dev, out, stream), "qmg_dwf_slice_norms")
+    return out
+
+
+def dwf_meas_plan(dtype, dims, Ls, kernel, nsys=1):
+    """What the measurement entries launch (qmg_dwf_meas_plan; host only): (family, lps, block, gx, gy, pbr, lds, nk)."""
+    out = (C.c_int * DWF_MEAS_PLAN_INTS)()
+    check(lib().qmg_dwf_meas_plan(dtype, dims[0], dims[1], Ls, kernel, nsys, out, DWF_MEAS_PLAN_INTS), "qmg_dwf_meas_plan")
     return tuple(out)
 
 

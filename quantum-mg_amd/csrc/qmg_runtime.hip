@@ -109,6 +109,7 @@ int qmg_shutdown(void) {
   release_deflate_workspace();
   release_u1_workspace();
   release_flow_workspace();
+  release_dwf_meas_workspace();
   QMG_HIP_CHECK(hipDeviceSynchronize());
   return QMG_SUCCESS;
 }

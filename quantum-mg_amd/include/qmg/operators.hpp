@@ -151,6 +151,22 @@ struct DwfBase : public Stencil2D {
     qmg::ok(qmg_dwf_hops_inv5(QMG_C64, &d, direct.gauge, dwf_Ls, mass.real(), mass.imag(), direct.w, x, x, QMG_P_OE, -1.0, 0.0, 0, 1, 0, 1u, qmg::current_stream()),
             "qmg_dwf_hops_inv5");
   }
+
+  // ---- measurements (csrc/qmg_dwf_meas.hip; include/qmg/dwf_measure.hpp builds the propagator and the correlators on these) ----
+  // psi5 = the wall source of the 4D (nc = 2) field eta4: eta4(x, 0) on (s, sigma) = (0, 0), eta4(x, 1) on (Ls-1, 1), zero elsewhere
+  bool wall_source(complex<double>* psi5, complex<double>* eta4) {
+    return qmg::ok(qmg_dwf_wall_source(QMG_C64, lat->get_dim_mu(0), lat->get_dim_mu(1), dwf_Ls, psi5, eta4, 1, 0, 0, qmg::current_stream()), "qmg_dwf_wall_source");
+  }
+  // q4 = the physical quark field (Ls-1, 0), (0, 1) of psi5, or its midpoint field (Ls/2-1, 0), (Ls/2, 1) (even Ls only: false otherwise)
+  bool wall_project(complex<double>* q4, complex<double>* psi5, bool midpoint) {
+    if (midpoint && (dwf_Ls & 1)) { std::cout << "[QMG-ERROR]: wall_project: an odd Ls has no midpoint between the walls.\n"; return false; }
+    return qmg::ok(qmg_dwf_wall_project(QMG_C64, lat->get_dim_mu(0), lat->get_dim_mu(1), dwf_Ls, q4, psi5, midpoint ? 1 : 0, 1, 0, 0, qmg::current_stream()),
+                   "qmg_dwf_wall_project");
+  }
+  // sum[(y Ls + s) 2 + sigma] = sum_x |psi5(x, y; s, sigma)|^2 on the host: 2 Ls Ly doubles
+  bool slice_norms(double* sum, complex<double>* psi5) {
+    return qmg::ok(qmg_dwf_slice_norms(QMG_C64, lat->get_dim_mu(0), lat->get_dim_mu(1), dwf_Ls, psi5, 1, 0, nullptr, sum, qmg::current_stream()), "qmg_dwf_slice_norms");
+  }
 };
 
 template <int Ls>

@@ -16,4 +16,5 @@
 #include "reductions.hpp"
 #include "hmc.hpp"
 #include "hmc_staggered.hpp"
+#include "dwf_measure.hpp"
 #endif
