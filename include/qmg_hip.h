@@ -299,6 +299,28 @@ int qmg_coarse_build(void* coarse_clover, void* coarse_hopping, const qmg_stenci
                      const void* nullvecs, const void* restrict_vecs /* or NULL */,
                      int cLx, int cLy, int cnc, void* stream);
 
+/* What the setup entry points do with a request: the answer of the one host function (csrc/qmg_setup_plan.h) that
+ * qmg_block_orthonormalize_n, qmg_coarse_build(_slab) and qmg_build_rbjacobi switch on.  Host only, no HIP call; reads the tuning knob
+ * "setup_fused".
+ *   op 0 ORTHO     (fLx, fLy, fnc) -> (cLx, cLy), ncv = nvec, a = passes
+ *   op 1 GALERKIN  (fLx, fLy, fnc) -> (cLx, cLy), ncv = cnc,  a = on a slab with halos (0 / 1)
+ *   op 2 CINV      (fLx, fLy, fnc) = the stencil's (Lx, Ly, nc), a = clover present, b = one of the six shift numbers is not zero;
+ *                  cLx, cLy, ncv are not looked at
+ * Writes 8 ints and -1 into the rest of plan_out:
+ *   family      0 unsupported (the call returns QMG_ERR_UNSUPPORTED: nc > 32 for CINV, a slab build that the probe passes would serve),
+ *               1 k_block_ortho (the block's tile in LDS), 2 the full-lattice orthonormalisation passes (odd block width, tile beyond
+ *               150 KB of LDS, "setup_fused" 0), 3 invalid (the call returns QMG_ERR_INVALID; any other op as well), 4 k_galerkin,
+ *               5 the probe passes (cnc > 32, more than 150 KB of LDS, "setup_fused" 0), 6 k_clover_inverse
+ *   tpb         k_block_ortho: threads per block of the null vectors, the power of two >= bx by fnc in 32 .. 256
+ *   groups      k_block_ortho: blocks per workgroup (1 .. 8; tiles up to 24 KB share a workgroup)
+ *   workgroups  the grid: min(ceil(blocks / groups), 262144), min(coarse sites, 262144), min(sites, 4096)
+ *   lds         dynamic LDS bytes per workgroup
+ *   flags       1 LDS opt-in (more than 64 KB) | 2 the last workgroup has groups without a block | 4 the grid-stride loop takes a second trip
+ *   outs        k_galerkin: output entries per thread in use, ceil(cnc^2 / 256) in 1 .. 4
+ *   threads     threads per workgroup
+ * (a member the family does not use is 0).  QMG_ERR_INVALID: plan_out missing or plan_len below 8. */
+int qmg_setup_plan(int op, int fLx, int fLy, int fnc, int cLx, int cLy, int ncv, int a, int b, int* plan_out, int plan_len);
+
 /* ---------------- lock-step batches of independent right-hand sides ---------------- */
 /* A batch vector is nrhs <= 16 vectors of n complex at a common `stride` (complex elements).  `mask` selects the
  * ACTIVE systems; a frozen system is neither read nor written.  Per-system arithmetic (including the reduction

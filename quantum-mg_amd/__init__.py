@@ -57,6 +57,7 @@ ABI_SYMBOLS = [
     "qmg_dwf_fill", "qmg_dwf_apply_direct", "qmg_dwf_plan", "qmg_batch_plan", "qmg_wilson_plan",
     "qmg_dwf_inv5", "qmg_dwf_hops_inv5", "qmg_dwf_schur_apply", "qmg_dwf_eo_plan",
     "qmg_dwf_wall_source", "qmg_dwf_wall_project", "qmg_dwf_slice_norms", "qmg_dwf_meas_plan",
+    "qmg_setup_plan",
 ]
 
 
@@ -389,6 +390,11 @@ def block_orthonormalize(nullvecs, nvec, fdims, cLx, cLy, cholesky=None):
     check(lib().qmg_block_orthonormalize(_vp(nullvecs), nvec, *fdims, cLx, cLy, _vp(cholesky), None), "qmg_block_orthonormalize")
 
 
+def block_orthonormalize_n(nullvecs, nvec, fdims, cLx, cLy, cholesky=None, passes=2):
+    """`passes` (1 or 2) passes in one call, the factor saved in the first (qmg_block_orthonormalize_n)"""
+    check(lib().qmg_block_orthonormalize_n(_vp(nullvecs), nvec, *fdims, cLx, cLy, _vp(cholesky), passes, None), "qmg_block_orthonormalize_n")
+
+
 def block_bi_orthonormalize(pvecs, rvecs, nvec, fdims, cLx, cLy, block_L=None, block_U=None):
     check(lib().qmg_block_bi_orthonormalize(_vp(pvecs), _vp(rvecs), nvec, *fdims, cLx, cLy, _vp(block_L), _vp(block_U), None), "qmg_block_bi_orthonormalize")
 
@@ -400,6 +406,21 @@ def coarse_build(cclover, chopping, fdesc, nullvecs, cdims, restrict_vecs=None):
 def coarse_build_slab(cclover, chopping, fdesc, nullvecs, cdims, halo_lo, halo_hi, halo_stride, restrict_vecs=None):
     check(lib().qmg_coarse_build_slab(_vp(cclover), _vp(chopping), C.byref(fdesc), _vp(nullvecs), _vp(restrict_vecs), *cdims, _vp(halo_lo), _vp(halo_hi),
                                       C.c_size_t(halo_stride), None), "qmg_coarse_build_slab")
+
+
+# the `op` argument, the families and the flags of qmg_setup_plan (include/qmg_hip.h)
+SETUP_OP_ORTHO, SETUP_OP_GALERKIN, SETUP_OP_CINV = range(3)
+SUF_UNSUPPORTED, SUF_ORTHO_LDS, SUF_ORTHO_PASSES, SUF_INVALID, SUF_GALERKIN, SUF_GALERKIN_PROBES, SUF_CINV = range(7)
+SUP_LDS_OPTIN, SUP_IDLE_GROUP, SUP_STRIDED = 1, 2, 4
+SETUP_PLAN_INTS = 8
+
+
+def setup_plan(op, fdims, cdims=(0, 0), ncv=0, a=0, b=0):
+    """What the setup entry points do with a request (qmg_setup_plan; host only): (family, tpb, groups, workgroups, lds, flags, outs, threads).
+    ORTHO: fdims -> cdims, ncv = nvec, a = passes; GALERKIN: ncv = cnc, a = slab; CINV: fdims = (Lx, Ly, nc), a = clover present, b = any shift."""
+    out = (C.c_int * SETUP_PLAN_INTS)()
+    check(lib().qmg_setup_plan(op, fdims[0], fdims[1], fdims[2], cdims[0], cdims[1], ncv, int(a), int(b), out, SETUP_PLAN_INTS), "qmg_setup_plan")
+    return tuple(out)
 
 
 class ApplyEpilogue(C.Structure):

@@ -4,6 +4,7 @@
 #include <string.h>
 
 #include "qmg_common.h"
+#include "qmg_setup_plan.h"   // qmg_build_rbjacobi switches on setup_plan(SETUP_OP_CINV, ...)
 
 namespace qmg {
 
@@ -440,17 +441,15 @@ int qmg_build_dagger_slab(void* dclover, void* dhopping, const void* clover, con
 }
 
 int qmg_build_rbjacobi(void* cinv, void* rb_clover, void* rb_hopping, const qmg_stencil_desc* d, void* stream) {
-  if (!d || !cinv || !valid_lattice(d->Lx, d->Ly) || d->nc < 1) return QMG_ERR_INVALID;
-  if (d->nc > 32) return QMG_ERR_UNSUPPORTED;
+  if (!d || !cinv) return QMG_ERR_INVALID;
   const bool no_shift = d->shift[0] == 0 && d->shift[1] == 0 && d->eo_shift[0] == 0 && d->eo_shift[1] == 0 &&
                         d->dof_shift[0] == 0 && d->dof_shift[1] == 0;
-  if (!d->clover && no_shift) return QMG_ERR_INVALID;   // stencil_2d.h:1471-1475
+  const SetupPlan pl = setup_plan(SETUP_OP_CINV, d->Lx, d->Ly, d->nc, 0, 0, 0, d->clover != nullptr, !no_shift);
+  if (pl.family != SUF_CINV) return pl.status;
   const int nc = d->nc;
   const long vol = (long)d->Lx * d->Ly;
   hipStream_t st = as_stream(stream);
-  const size_t smem = sizeof(cplx) * 2 * nc * nc;
-  unsigned gb = vol > 256 * 16 ? 256 * 16 : (unsigned)vol;
-  k_clover_inverse<<<gb, BLOCK, smem, st>>>((cplx*)cinv, (const cplx*)d->clover, vol, vol / 2, nc, d->shift[0], d->shift[1],
+  k_clover_inverse<<<(unsigned)pl.workgroups, BLOCK, (size_t)pl.lds, st>>>((cplx*)cinv, (const cplx*)d->clover, vol, vol / 2, nc, d->shift[0], d->shift[1],
                                             d->eo_shift[0], d->eo_shift[1], d->dof_shift[0], d->dof_shift[1]);
   QMG_LAUNCH_CHECK();
   if (rb_clover) {

@@ -19,6 +19,7 @@
 #include <string.h>
 
 #include "qmg_common.h"
+#include "qmg_setup_plan.h"
 
 namespace qmg {
 
@@ -136,7 +137,7 @@ __global__ __launch_bounds__(BLOCK) void k_block_ortho(cplx* __restrict__ nullv,
 // nc_c, in registers: thread k owns the output entries k, k + 256, ...).  A hop whose neighbour lies in the same block
 // goes to the coarse clover (coarse.h:222-224, 250-252), one that leaves it to the coarse hopping of that direction,
 // stored at the OUTPUT site X as in the fine layout.  The identity shift is NOT part of the build (coarse.h:131).
-constexpr int GAL_MAXOUT = 4;   // output entries per thread: nc_c^2 <= 4 * 256, i.e. nc_c <= 32
+// (GAL_MAXOUT output entries per thread, qmg_setup_plan.h: nc_c^2 <= 4 * 256, i.e. nc_c <= 32)
 // y-slab of a larger lattice: the prolongator's rows -1 / fLy (needed by the -y / +y hops that leave the slab) come from
 // P_lo / P_hi ([null vector][parity][fhr][nf], halo_stride elements between vectors; qmg_halo_exchange of the null vectors).
 __global__ __launch_bounds__(BLOCK) void k_galerkin(cplx* __restrict__ cclover, cplx* __restrict__ chopping, const cplx* __restrict__ fclover,
@@ -223,8 +224,7 @@ __global__ __launch_bounds__(BLOCK) void k_galerkin(cplx* __restrict__ cclover, 
 }
 
 static int make_sgeom(SetupGeom* g, int fLx, int fLy, int fnc, int cLx, int cLy, int cnc) {
-  if (!valid_lattice(fLx, fLy) || !valid_lattice(cLx, cLy) || fnc < 1 || cnc < 1) return QMG_ERR_INVALID;
-  if (fLx % cLx || fLy % cLy) return QMG_ERR_INVALID;
+  if (!setup_detail::valid_blocking(fLx, fLy, fnc, cLx, cLy, cnc)) return QMG_ERR_INVALID;
   g->fhr = fLx / 2; g->fLy = fLy; g->fnc = fnc;
   g->chr = cLx / 2; g->cLy = cLy; g->cnc = cnc;
   g->bx = fLx / cLx; g->by = fLy / cLy;
@@ -243,32 +243,26 @@ extern "C" {
 // the decomposition saved in the first: :160-174).  Falls back to the full-lattice passes for odd block widths or tiles
 // beyond LDS.  No allocation and no synchronisation here: asynchronous on `stream`.
 int qmg_block_orthonormalize_n(void* nullvecs, int nvec, int fLx, int fLy, int fnc, int cLx, int cLy, void* cholesky, int passes, void* stream) {
-  if (!nullvecs || nvec < 1 || passes < 1 || passes > 2) return QMG_ERR_INVALID;
-  SetupGeom g;
-  int rc = make_sgeom(&g, fLx, fLy, fnc, cLx, cLy, nvec);
-  if (rc) return rc;
-  const int nel = g.bx * g.by * fnc;
-  int TPB = 32;
-  while (TPB < nel && TPB < BLOCK) TPB <<= 1;
-  int groups = (TPB >= 64) ? 1 : 2;   // a workgroup is at least one wavefront
-  const size_t tile_bytes = sizeof(cplx) * (size_t)nvec * nel;
-  size_t smem = tile_bytes * groups + sizeof(double) * 2 * (BLOCK / WAVE);
-  if (!g_setup_fused || (g.bx & 1) || smem > 150 * 1024) {
+  if (!nullvecs) return QMG_ERR_INVALID;
+  const SetupPlan pl = setup_plan(SETUP_OP_ORTHO, fLx, fLy, fnc, cLx, cLy, nvec, passes, 0);
+  if (pl.family != SUF_ORTHO_LDS && pl.family != SUF_ORTHO_PASSES) return pl.status;
+  int rc = QMG_SUCCESS;
+  if (pl.family == SUF_ORTHO_PASSES) {
     for (int p = 0; p < passes && !rc; p++) rc = block_orthonormalize_passes(nullvecs, nvec, fLx, fLy, fnc, cLx, cLy, p == 0 ? cholesky : nullptr, stream);
     return rc;
   }
-  while (groups * 2 * TPB <= BLOCK && tile_bytes * groups * 2 <= 24 * 1024) groups *= 2;   // small tiles: several blocks per workgroup
-  smem = tile_bytes * groups + sizeof(double) * 2 * (BLOCK / WAVE);
-  const long ncs = (long)cLx * cLy;
-  long nwg = (ncs + groups - 1) / groups;
-  if (nwg > 262144) nwg = 262144;
+  SetupGeom g;
+  rc = make_sgeom(&g, fLx, fLy, fnc, cLx, cLy, nvec);
+  if (rc) return rc;
+  const int groups = pl.groups;
+  const size_t smem = (size_t)pl.lds;
   hipStream_t st = as_stream(stream);
 #define QMG_BO(TPBV)                                                                                                                        \
   {                                                                                                                                         \
-    if (smem > 64 * 1024) QMG_HIP_CHECK(hipFuncSetAttribute((const void*)k_block_ortho<TPBV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem)); \
-    k_block_ortho<TPBV><<<(unsigned)nwg, TPBV * groups, smem, st>>>((cplx*)nullvecs, nvec, (cplx*)cholesky, g, passes, groups);             \
+    if (pl.flags & SUP_LDS_OPTIN) QMG_HIP_CHECK(hipFuncSetAttribute((const void*)k_block_ortho<TPBV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem)); \
+    k_block_ortho<TPBV><<<(unsigned)pl.workgroups, TPBV * groups, smem, st>>>((cplx*)nullvecs, nvec, (cplx*)cholesky, g, passes, groups);   \
   }
-  if (TPB == 32) QMG_BO(32) else if (TPB == 64) QMG_BO(64) else if (TPB == 128) QMG_BO(128) else QMG_BO(256)
+  if (pl.tpb == 32) QMG_BO(32) else if (pl.tpb == 64) QMG_BO(64) else if (pl.tpb == 128) QMG_BO(128) else QMG_BO(256)
 #undef QMG_BO
   QMG_LAUNCH_CHECK();
   return QMG_SUCCESS;
@@ -290,22 +284,27 @@ int qmg_coarse_build_slab(void* cclover, void* chopping, const qmg_stencil_desc*
                           const void* P_halo_lo, const void* P_halo_hi, size_t halo_stride, void* stream) {
   if (!cclover || !chopping || !fine || !nullvecs) return QMG_ERR_INVALID;
   if ((P_halo_lo == nullptr) != (P_halo_hi == nullptr)) return QMG_ERR_INVALID;
+  const SetupPlan pl = setup_plan(SETUP_OP_GALERKIN, fine->Lx, fine->Ly, fine->nc, cLx, cLy, cnc, P_halo_lo != nullptr, 0);
+  if (pl.family == SUF_GALERKIN_PROBES) return coarse_build_probes(cclover, chopping, fine, nullvecs, restrict_vecs, cLx, cLy, cnc, stream);
+  if (pl.family != SUF_GALERKIN) return pl.status;
   SetupGeom g;
   int rc = make_sgeom(&g, fine->Lx, fine->Ly, fine->nc, cLx, cLy, cnc);
   if (rc) return rc;
-  const int nf = fine->nc;
-  const size_t smem = sizeof(cplx) * ((size_t)3 * nf * cnc + (size_t)nf * nf);
-  if (!g_setup_fused || cnc * cnc > GAL_MAXOUT * BLOCK || smem > 150 * 1024) {
-    if (P_halo_lo) return QMG_ERR_UNSUPPORTED;   // the full-lattice probe passes have no halo step
-    return coarse_build_probes(cclover, chopping, fine, nullvecs, restrict_vecs, cLx, cLy, cnc, stream);
-  }
-  long nwg = (long)cLx * cLy;
-  if (nwg > 262144) nwg = 262144;
-  if (smem > 64 * 1024) QMG_HIP_CHECK(hipFuncSetAttribute((const void*)k_galerkin, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-  k_galerkin<<<(unsigned)nwg, BLOCK, smem, as_stream(stream)>>>((cplx*)cclover, (cplx*)chopping, (const cplx*)fine->clover, (const cplx*)fine->hopping,
+  const size_t smem = (size_t)pl.lds;
+  if (pl.flags & SUP_LDS_OPTIN) QMG_HIP_CHECK(hipFuncSetAttribute((const void*)k_galerkin, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+  k_galerkin<<<(unsigned)pl.workgroups, BLOCK, smem, as_stream(stream)>>>((cplx*)cclover, (cplx*)chopping, (const cplx*)fine->clover, (const cplx*)fine->hopping,
                                                                (const cplx*)nullvecs, (const cplx*)(restrict_vecs ? restrict_vecs : nullvecs), g,
                                                                (const cplx*)P_halo_lo, (const cplx*)P_halo_hi, (long)halo_stride);
   QMG_LAUNCH_CHECK();
+  return QMG_SUCCESS;
+}
+
+// What the setup entry points do with a request (qmg_setup_plan.h): the answer of the one host function they switch on.  No HIP call.
+int qmg_setup_plan(int op, int fLx, int fLy, int fnc, int cLx, int cLy, int ncv, int a, int b, int* plan_out, int plan_len) {
+  if (!plan_out || plan_len < SETUP_PLAN_INTS) return QMG_ERR_INVALID;
+  const SetupPlan pl = setup_plan(op, fLx, fLy, fnc, cLx, cLy, ncv, a, b);
+  const int v[SETUP_PLAN_INTS] = {pl.family, pl.tpb, pl.groups, pl.workgroups, pl.lds, pl.flags, pl.outs, pl.threads};
+  for (int i = 0; i < plan_len; i++) plan_out[i] = i < SETUP_PLAN_INTS ? v[i] : -1;
   return QMG_SUCCESS;
 }
 

@@ -360,6 +360,7 @@ def test_apply_rejects_bad_arguments():
 # ------------------------------------------------------------------ stencil variants (a9-a11)
 @pytest.mark.parametrize("Lx,Ly,nc", [(32, 32, 2), (12, 8, 3), (8, 8, 8)])
 def test_dagger_and_rbjacobi_builds(Lx, Ly, nc):
+    """(per site and element, against an independent reference and on every launch shape: test_gpu_setup_routes.py, the jacobi and dagger rows)"""
     vol = Lx * Ly
     clover = cs.gaussian_cvec(vol * nc * nc, 1) + 4.0 * np.tile(np.eye(nc).reshape(-1), vol)
     hopping = cs.gaussian_cvec(4 * vol * nc * nc, 2)
@@ -394,7 +395,8 @@ def test_rbj_dagger_build_and_normal_operators(Lx, Ly, nc):
     clover, hopping daggered with the neighbour shift -- against the oracle's restatement, bit for bit (pure data movement); then the two
     normal operators the CGNE / CGNR smoothers apply, M_rbj^dag M_rbj (MDM, :2282-2299) and M_rbj M_rbj^dag (MMD, :2354-2371), as the
     facade launches them (identity clover as a unit shift, hops from the built arrays) against the oracle applying the stored matrices
-    pass by pass, and <y, M_rbj x> = <M_rbj^dag y, x> (n21)."""
+    pass by pass, and <y, M_rbj x> = <M_rbj^dag y, x> (n21).
+    (qmg_build_dagger and qmg_cmat_conjtrans bit for bit on further shapes: test_gpu_setup_routes.py, the dagger rows.)"""
     vol = Lx * Ly
     clover = cs.gaussian_cvec(vol * nc * nc, 11) + 4.0 * np.tile(np.eye(nc).reshape(-1), vol)
     hopping = cs.gaussian_cvec(4 * vol * nc * nc, 12)
@@ -548,6 +550,7 @@ def test_prolong_restrict(fdims, cdims):
 
 @pytest.mark.parametrize("fdims,cdims", XFER_CASES[:4])
 def test_block_orthonormalize_and_n05_identities(fdims, cdims):
+    """(per block and vector, every k_block_ortho instantiation and the fallback: test_gpu_setup_routes.py, the ortho rows)"""
     fsize, csize = fdims[0] * fdims[1] * fdims[2], cdims[0] * cdims[1] * cdims[2]
     nvec = cdims[2]
     nv = cs.gaussian_cvec(nvec * fsize, 1)
@@ -571,7 +574,8 @@ def test_block_local_setup_kernels_match_the_oracle_and_the_full_lattice_passes(
     """csrc/qmg_setup.hip: block orthonormalisation with the tile in LDS, BOTH passes of the TransferMG
     constructor in one launch (32-, 128- and 256-thread groups: nel = 32, 128, 384), and the Galerkin build as per-block
     products, with a separate restrictor -- against the oracle (1e-12) and against the first round's full-lattice passes
-    ("setup_fused" 0; also the fallback for the odd block width of the last case)."""
+    ("setup_fused" 0; also the fallback for the odd block width of the last case).
+    (One row per route of qmg_setup_plan, held per block and per entry to an independent reference: test_gpu_setup_routes.py.)"""
     fLx, fLy, fnc = fdims
     fvol, fsize = fLx * fLy, fLx * fLy * fnc
     nvec = cdims[2]
@@ -609,7 +613,8 @@ def test_block_local_setup_kernels_match_the_oracle_and_the_full_lattice_passes(
 @pytest.mark.parametrize("fdims,cdims", XFER_CASES[:4])
 def test_block_bi_orthonormalize_asymmetric_transfer(fdims, cdims):
     """transfer.h:610-769 (P != R^dag, tests/n05_prolong_restrict_test:105-139): after bi-orthonormalisation R^dag P = 1
-    on the coarse space; L and U reproduce the block Gram matrix R^dag P of the ORIGINAL vectors."""
+    on the coarse space; L and U reproduce the block Gram matrix R^dag P of the ORIGINAL vectors.
+    (Every block, an odd block width and nvec = 1: test_gpu_setup_routes.py, the biortho rows.)"""
     fsize, csize = fdims[0] * fdims[1] * fdims[2], cdims[0] * cdims[1] * cdims[2]
     nvec = cdims[2]
     pv = cs.gaussian_cvec(nvec * fsize, 1)
@@ -638,6 +643,8 @@ def test_block_bi_orthonormalize_asymmetric_transfer(fdims, cdims):
 
 @pytest.mark.parametrize("fdims,cdims", [((16, 16, 2), (4, 4, 4)), ((8, 8, 4), (4, 2, 6)), ((16, 8, 1), (4, 4, 2))])
 def test_coarse_build_matches_oracle_and_n08_galerkin(fdims, cdims):
+    """(every entry of every coarse block under the summation bound, every outputs-per-thread count of k_galerkin and the probe passes:
+    test_gpu_setup_routes.py, the galerkin rows)"""
     fLx, fLy, fnc = fdims
     fvol, fsize, csize = fLx * fLy, fLx * fLy * fnc, cdims[0] * cdims[1] * cdims[2]
     nvec = cdims[2]
