@@ -244,11 +244,8 @@ template <int NV>
 __device__ __forceinline__ void bblock_reduce_store(double* v, double* partial_out) {
   __shared__ double sm[NV][BLOCK / WAVE];
   const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
-#pragma unroll
-  for (int q = 0; q < NV; q++) {
-    const double w = wave_sum(v[q]);
-    if (lane == 0) sm[q][wv] = w;
-  }
+  const double w = wave_reduce_many<NV>(v);   // lane q: wave_sum(v[q]), bit for bit
+  if (lane < NV) sm[lane][wv] = w;
   __syncthreads();
   if (threadIdx.x < NV) {
     double t = sm[threadIdx.x][0];

@@ -131,11 +131,8 @@ template <int NV, bool MAX>
 __device__ __forceinline__ void block_reduce_store(double* v, double* partial_out) {
   __shared__ double sm[NV][BLOCK / WAVE];
   const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
-#pragma unroll
-  for (int q = 0; q < NV; q++) {
-    const double w = MAX ? wave_max(v[q]) : wave_sum(v[q]);
-    if (lane == 0) sm[q][wv] = w;
-  }
+  const double w = wave_reduce_many<NV, MAX>(v);   // lane q: wave_max(v[q]) / wave_sum(v[q]), bit for bit
+  if (lane < NV) sm[lane][wv] = w;
   __syncthreads();
   if (threadIdx.x < NV) {
     double t = sm[threadIdx.x][0];

@@ -104,6 +104,41 @@ __device__ __forceinline__ double wave_max(double v) {
   return v;
 }
 
+// NV (a power of two) sums or maxima at once, by recursive halving: lane q < NV returns what wave_sum(v[q]) / wave_max(v[q]) returns, bit
+// for bit; the other lanes return the same number for value (lane & (NV - 1)).  Level s pairs lane with lane ^ 2^s as the butterfly does, but
+// a lane sends only the half of its live values whose index has bit s unlike its own lane bit, and adds what it receives to the half it
+// keeps: a value's partial sums meet in the same pairs in the same level order, on the lanes whose low bits name the value, and a + b is
+// b + a.  Once one value per lane is left the plain butterfly finishes it.  16 values: 8 + 4 + 2 + 1 + 1 + 1 = 17 exchanges of a double
+// instead of 96, the first 12 of them DPP quad permutes.  Every lane of the wavefront must call it.
+__device__ __forceinline__ double lane_xor_level(double v, int s) {   // lane ^ 2^s (s is a constant after unrolling)
+  return s == 0 ? lane_xor1(v) : s == 1 ? lane_xor2(v) : __shfl_xor(v, 1 << s);
+}
+template <int NV, bool MAX = false>
+__device__ __forceinline__ double wave_reduce_many(const double* v) {
+  static_assert(NV >= 1 && NV <= WAVE && (NV & (NV - 1)) == 0, "wave_reduce_many: a power of two, at most one value per lane");
+  const int lane = threadIdx.x & (WAVE - 1);
+  double w[NV];
+#pragma unroll
+  for (int q = 0; q < NV; q++) w[q] = v[q];
+  constexpr int LV = __builtin_ctz((unsigned)NV);   // halving levels
+#pragma unroll
+  for (int s = 0; s < LV; s++) {   // w[j] at the start of level s is value (j << s) | (lane & (2^s - 1))
+    const bool up = (lane >> s) & 1;
+#pragma unroll
+    for (int j = 0; j < (NV >> (s + 1)); j++) {
+      const double keep = up ? w[2 * j + 1] : w[2 * j], send = up ? w[2 * j] : w[2 * j + 1];
+      const double got = lane_xor_level(send, s);
+      w[j] = MAX ? fmax(keep, got) : keep + got;
+    }
+  }
+#pragma unroll
+  for (int s = LV; s < 6; s++) {
+    const double got = lane_xor_level(w[0], s);
+    w[0] = MAX ? fmax(w[0], got) : w[0] + got;
+  }
+  return w[0];
+}
+
 // Two-stage sum of N numbers per thread in a FIXED order, so that the result is deterministic.  First stage, at the end of a kernel of BLOCK
 // threads: the block's N sums go to partials[blockIdx.x * N + q]; `sm` is the kernel's own __shared__ array.
 template <int N>

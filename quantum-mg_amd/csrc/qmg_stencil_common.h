@@ -105,11 +105,12 @@ __device__ __forceinline__ cplx epilogue_value(const Epilogue& e, cplx ov, cplx 
 // end of a kernel with an epilogue: one partial per wavefront of the launch, [slot][4] (system slot 0); every lane of the block calls it
 // (the launchers cap grid.y for these launches, so that the one-block second stage sums a few thousand partials, not one per row)
 __device__ __forceinline__ void epilogue_store_partials(const Epilogue& e, double (&d)[3]) {
-  const double s0 = wave_sum(d[0]), s1 = wave_sum(d[1]), s2 = wave_sum(d[2]);
-  if ((threadIdx.x & (WAVE - 1)) == 0) {
+  const double v[4] = {d[0], d[1], d[2], 0.0};
+  const double s = wave_reduce_many<4>(v);   // lane q: wave_sum(v[q]), bit for bit (the fourth is a sum of zeros: 0.0)
+  const int lane = threadIdx.x & (WAVE - 1);
+  if (lane < 4) {
     const long w = ((long)blockIdx.y * gridDim.x + blockIdx.x) * (BLOCK / WAVE) + threadIdx.x / WAVE;
-    double* p = e.part + w * 4;
-    p[0] = s0; p[1] = s1; p[2] = s2; p[3] = 0.0;
+    e.part[w * 4 + lane] = s;
   }
 }
 

@@ -59,6 +59,14 @@ __global__ __launch_bounds__(BLOCK, (MODE == 1 && NC <= 24) ? 3 : 1) void k_sten
   constexpr int MEL = PAIR ? 2 * SNC * SNC : NC * NC;   // stored matrix elements per piece per wavefront
   constexpr int RT = (MODE == 2) ? (2 * NC + 15) / 16 : (NC + 15) / 16, KS = (MODE == 2) ? NC / 2 : (NC + 3) / 4;
   constexpr int NACC = (MODE == 2) ? 1 : 2;
+  // PACK (MODE 1, NC % 16 == 8: nc = 24 and the one-site nc = 8; matrices stored narrow): the last row tile has eight rows, so its A operand
+  // carries Re M of them in tile rows 0-7 and Im M of the same rows in tile rows 8-15, and ONE MFMA into acc[0][RT - 1] yields P (C rows
+  // 0-7) and Q (C rows 8-15) instead of two MFMAs half of whose rows are zeros: 3 per k-step instead of 4 at nc = 24, 1 instead of 2 at
+  // nc = 8.  Every element of C still accumulates the same products in the same order, so the output bits do not change.
+  // Not with complex<double> matrices: that form sits at its register cap (163 of 168 VGPRs), the packed one spills 21 of them and was
+  // measured 12-16 % SLOWER (nc = 24, 8 systems, 512^2: 2.44 -> 2.73 ms; profiles/kernelc_pack_multidot.txt).
+  constexpr bool PACK = MODE == 1 && NC % 16 == 8 && !PAIR && M32;
+  static_assert(!PACK || VL, "PACK: the epilogue through the vector slice");
   // LDS row stride in tile elements: fp64 tile nc+1 complex (odd: conflict-free 16-B reads); fp32-stored matrices keep the
   // tile as raw complex<float> with stride nc+2 (even: 16-B aligned pair stores) -- half the LDS and half the staging
   // registers, widened to fp64 only as an MFMA operand
@@ -305,7 +313,9 @@ __global__ __launch_bounds__(BLOCK, (MODE == 1 && NC <= 24) ? 3 : 1) void k_sten
 #pragma unroll
         for (int t = 0; t < RT; t++) {
           const int r = 16 * t + lr, c = 4 * q + lq;
-          if (M32) {
+          if (PACK && t == RT - 1) {   // both halves of the tile read the row's element: tile rows 0-7 take its real part, rows 8-15 its imaginary part (into Af.x)
+            Af[t] = cmake((double)reinterpret_cast<const float*>(mlds32 + (r - (lr & 8)) * RS + c)[lr >> 3], 0.0);
+          } else if (M32) {
             const float2 mf = ((NC % 16 == 0 || r < NC) && (NC % 4 == 0 || c < NC)) ? mlds32[r * RS + c] : make_float2(0.0f, 0.0f);
             Af[t] = cmake((double)mf.x, (double)mf.y);
           } else
@@ -313,9 +323,12 @@ __global__ __launch_bounds__(BLOCK, (MODE == 1 && NC <= 24) ? 3 : 1) void k_sten
         }
         if constexpr (VL) {                       // B fragment of this k-step: X_{column}[4q + lq] from the wavefront's vector slice
           const int c = 4 * q + lq;
+          if constexpr (PACK) B[set][0] = reinterpret_cast<const double*>(xlds + kcol * XS + c)[lr >> 3];   // (NC % 4 == 0) the half this column carries, read alone
+          else {
           const cplx xv = (NC % 4 == 0 || c < NC) ? xlds[kcol * XS + c] : cmake(0.0, 0.0);
           if constexpr (MODE == 1) B[set][0] = (lr < 8) ? xv.x : xv.y;
           else B[set][0] = xv;
+          }
         }
         constexpr int qb = VL ? 0 : 1;            // VL: the fragment sits in slot 0; else slot q
         if constexpr (F32M && MODE == 0) {
@@ -332,8 +345,12 @@ __global__ __launch_bounds__(BLOCK, (MODE == 1 && NC <= 24) ? 3 : 1) void k_sten
         } else if constexpr (F32M) {
 #pragma unroll
           for (int t = 0; t < RT; t++) {
-            acc[0][t] = __builtin_amdgcn_mfma_f32_16x16x4f32((float)Af[t].x, (float)B[set][q * qb], acc[0][t], 0, 0, 0);
-            acc[1][t] = __builtin_amdgcn_mfma_f32_16x16x4f32((float)Af[t].y, (float)B[set][q * qb], acc[1][t], 0, 0, 0);
+            if (PACK && t == RT - 1) {
+              acc[0][t] = __builtin_amdgcn_mfma_f32_16x16x4f32((float)Af[t].x, (float)B[set][q * qb], acc[0][t], 0, 0, 0);
+            } else {
+              acc[0][t] = __builtin_amdgcn_mfma_f32_16x16x4f32((float)Af[t].x, (float)B[set][q * qb], acc[0][t], 0, 0, 0);
+              acc[1][t] = __builtin_amdgcn_mfma_f32_16x16x4f32((float)Af[t].y, (float)B[set][q * qb], acc[1][t], 0, 0, 0);
+            }
           }
         } else if constexpr (MODE == 0) {
 #pragma unroll
@@ -349,8 +366,12 @@ __global__ __launch_bounds__(BLOCK, (MODE == 1 && NC <= 24) ? 3 : 1) void k_sten
         } else {
 #pragma unroll
           for (int t = 0; t < RT; t++) {
-            acc[0][t] = __builtin_amdgcn_mfma_f64_16x16x4f64(Af[t].x, B[set][q * qb], acc[0][t], 0, 0, 0);
-            acc[1][t] = __builtin_amdgcn_mfma_f64_16x16x4f64(Af[t].y, B[set][q * qb], acc[1][t], 0, 0, 0);
+            if (PACK && t == RT - 1) {
+              acc[0][t] = __builtin_amdgcn_mfma_f64_16x16x4f64(Af[t].x, B[set][q * qb], acc[0][t], 0, 0, 0);
+            } else {
+              acc[0][t] = __builtin_amdgcn_mfma_f64_16x16x4f64(Af[t].x, B[set][q * qb], acc[0][t], 0, 0, 0);
+              acc[1][t] = __builtin_amdgcn_mfma_f64_16x16x4f64(Af[t].y, B[set][q * qb], acc[1][t], 0, 0, 0);
+            }
           }
         }
       }
@@ -402,6 +423,25 @@ __global__ __launch_bounds__(BLOCK, (MODE == 1 && NC <= 24) ? 3 : 1) void k_sten
       } else {
 #pragma unroll
       for (int t = 0; t < RT; t++) {
+        if constexpr (PACK) {
+          if (t == RT - 1) {   // the packed tile: P in C rows 0-7, Q of the same matrix rows in C rows 8-15 of ONE accumulator
+            if constexpr (F32M) {   // f32 C/D map: rows 4 lq + i; Q sits in lane ^ 32, the other column half in lane ^ 8, both in lane ^ 40
+#pragma unroll
+              for (int i = 0; i < 4; i++) {
+                const float own = acc[0][t][i];
+                const double pp = (double)__shfl_xor(own, 8), q0 = (double)__shfl_xor(own, 32), qp = (double)__shfl_xor(own, 40);
+                if (lq < 2 && lr < 8) xlds[kcol * XS + 16 * t + 4 * lq + i] = cmake((double)own - qp, pp + q0);
+              }
+            } else {                // f64 C/D map: rows 4 i + lq; P is register i, Q register i + 2
+#pragma unroll
+              for (int i = 0; i < 2; i++) {
+                const double pp = __shfl_xor(acc[0][t][i], 8), qp = __shfl_xor(acc[0][t][i + 2], 8);
+                if (lr < 8) xlds[kcol * XS + 16 * t + 4 * i + lq] = cmake(acc[0][t][i] - qp, pp + acc[0][t][i + 2]);
+              }
+            }
+            continue;
+          }
+        }
 #pragma unroll
         for (int i = 0; i < 4; i++) {
           const int r = F32M ? 16 * t + 4 * lq + i : 16 * t + 4 * i + lq;   // C/D row of accumulator register i: the f32 instruction puts rows 4 lq .. 4 lq + 3 in a lane, the f64 one rows lq, lq + 4, ...
