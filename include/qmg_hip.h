@@ -233,7 +233,8 @@ int qmg_build_rbjacobi(void* cinv, void* rb_clover, void* rb_hopping, const qmg_
 int qmg_cmat_conjtrans(void* out, const void* in, size_t nsite, int nc, void* stream);
 
 /* ---------------- BLAS-1 on device vectors (the quantum-linalg leaves the path calls) ---------------- */
-/* n = number of complex elements; scalars are (re,im) pairs passed by value. */
+/* n = number of complex elements; scalars are (re,im) pairs passed by value.  One system is the batch entry at nrhs = 1: these ten run
+ * qmg_batch_blas_t(QMG_C64, QMG_BOP_*, ...) with nrhs = 1, mask = 1 (same kernels, same operation order: DESIGN 4). */
 int qmg_zero_vector(void* x, size_t n, void* stream);
 int qmg_copy_vector(void* dst, const void* src, size_t n, void* stream);
 int qmg_cax(double ar, double ai, void* x, size_t n, void* stream);                                   /* x *= a            */
@@ -255,15 +256,17 @@ int qmg_gaussian(void* x, size_t n, unsigned long long seed, void* stream);
 /* ---------------- global reductions ---------------- */
 /* Two-stage (wavefront DPP + LDS block) deterministic reductions.  `out_dev` is a DEVICE buffer
  * (1 double for real results, 2 for dot) written asynchronously; `out_host`, if non-NULL, receives a
- * copy and makes the call synchronous.  Either may be NULL, not both. */
+ * copy and makes the call synchronous.  Either may be NULL, not both.  The sums (norm2sq, dot, diffnorm2sq, multidot) are the batch
+ * reductions below at nrhs = 1, mask = 1: the same kernels, the same summation order, and the same way to the host ("reduce_spin"). */
 int qmg_norm2sq(const void* x, size_t n, double* out_dev, double* out_host, void* stream);
 int qmg_dot(const void* x, const void* y, size_t n, double* out_dev, double* out_host, void* stream);   /* sum conj(x) y */
 int qmg_diffnorm2sq(const void* x, const void* y, size_t n, double* out_dev, double* out_host, void* stream);
 int qmg_norminf(const void* x, size_t n, double* out_dev, double* out_host, void* stream);
 /* k dot products <x_i, y>, i < k, in one pass over y (GCR orthogonalisation). xs: HOST array of k device pointers.
- * out: 2k doubles. k <= 64. */
+ * out: 2k doubles. k <= 64 (more than 32: two passes of 32 and the rest; every dot is its own sum). */
 int qmg_multidot(const void* const* xs, int k, const void* y, size_t n, double* out_dev, double* out_host, void* stream);
-/* reductions/reductions.h:24-87: per-timeslice (per-y) norm2sq / dot. out: Ly (or 2*Ly) doubles. */
+/* reductions/reductions.h:24-87: per-timeslice (per-y) norm2sq / dot. out: Ly (or 2*Ly) doubles.  (Results wanted on the host alone pass through
+ * the reduction workspace: Ly <= 2^19.) */
 int qmg_norm2sq_cv_timeslice(const void* cv, int Lx, int Ly, int nc, double* out_dev, double* out_host, void* stream);
 int qmg_dot_cv_timeslice(const void* a, const void* b, int Lx, int Ly, int nc, double* out_dev, double* out_host, void* stream);
 /* redot_cv_timeslice (reductions/reductions.h:47-66): sum[y] = Re sum_{x,c} conj(a) b, Ly doubles */
@@ -323,10 +326,13 @@ int qmg_setup_plan(int op, int fLx, int fLy, int fnc, int cLx, int cLy, int ncv,
 
 /* ---------------- lock-step batches of independent right-hand sides ---------------- */
 /* A batch vector is nrhs <= 16 vectors of n complex at a common `stride` (complex elements).  `mask` selects the
- * ACTIVE systems; a frozen system is neither read nor written.  Per-system arithmetic (including the reduction
- * order) is that of the single-vector entry points above.  Scalars are per system: a[2k], a[2k+1] = re, im. */
-typedef enum { QMG_BOP_ZERO = 0, QMG_BOP_COPY = 1, QMG_BOP_CAX = 2, QMG_BOP_CAXPY = 3, QMG_BOP_CXPY = 4, QMG_BOP_CAXPBYZ = 5 } qmg_batch_op;
-/* ZERO: z = 0; COPY: z = x; CAX: z *= a; CAXPY: z += a x; CXPY: z += x; CAXPBYZ: z = a x + b y */
+ * ACTIVE systems; a frozen system is neither read nor written.  A system's arithmetic (including the reduction
+ * order) does not depend on the batch it is in; the single-vector entry points above are these at nrhs = 1.  Scalars are per system:
+ * a[2k], a[2k+1] = re, im. */
+typedef enum { QMG_BOP_ZERO = 0, QMG_BOP_COPY = 1, QMG_BOP_CAX = 2, QMG_BOP_CAXPY = 3, QMG_BOP_CXPY = 4, QMG_BOP_CAXPBYZ = 5,
+               QMG_BOP_CAXY = 6, QMG_BOP_CXPAY = 7, QMG_BOP_CAXPBY = 8, QMG_BOP_CXPYZ = 9 } qmg_batch_op;
+/* ZERO: z = 0; COPY: z = x; CAX: z *= a; CAXPY: z += a x; CXPY: z += x; CAXPBYZ: z = a x + b y;
+ * CAXY: z = a x; CXPAY: z = x + a z; CAXPBY: z = a x + b z; CXPYZ: z = x + y.  z may alias x or y in CAXPBYZ and CXPYZ. */
 int qmg_batch_blas(int op, const double* a, const double* b, const void* x, const void* y, void* z, size_t n,
                    int nrhs, size_t stride, unsigned mask, void* stream);
 /* y_k += sum_j c[j][k] xs[j]_k ; coeffs[(j*nrhs + k)*2 + {0,1}]; xs: HOST array of nj batch base pointers */
@@ -494,7 +500,7 @@ int qmg_stencil_plan(int entry, int mat, int vec32, int Lx, int Ly, int nc, unsi
  * of the call is 16-byte aligned.  Writes 5 ints per pass, in launch order, and -1 into the rest of plan_out (5 * max_passes ints):
  *   family   QMG_BF_*: 0 success with nothing launched (no active system, n = 0, no vector set; a multi-shift launch none of whose
  *            shifts is iterated any more), 1 k_bblas, 2 k_bmulti_caxpy_small, 3 k_bmulti_caxpy (vectors of 16 MiB and more per system),
- *            4 the single-vector qmg_multi_caxpy (ONE complex<double> system of 16 MiB and more), 5 k_bgcr_update, 6 k_bcgm_update,
+ *            4 qmg_multi_caxpy (ONE complex<double> system of 16 MiB and more), 5 k_bgcr_update, 6 k_bcgm_update,
  *            7 k_breduce, 8 k_bmultidot, 9 k_bmultidot<2> + k_bmr_final, 10 k_bmr_update
  *   W        elements per 16-byte access: 2 for complex<float> with aligned pointers, even n and (nrhs > 1) even stride, else 1
  *   nt       read-only operands are read non-temporally (the active systems add up to blas_nt_mb MiB)

@@ -470,7 +470,7 @@ def gaussian_slab(x, Lx, Ly_global, y0, Ly_local, nc, seed):
 
 
 # ---------------- lock-step batches (qmg_batch.hip) ----------------
-BOP_ZERO, BOP_COPY, BOP_CAX, BOP_CAXPY, BOP_CXPY, BOP_CAXPBYZ = range(6)
+BOP_ZERO, BOP_COPY, BOP_CAX, BOP_CAXPY, BOP_CXPY, BOP_CAXPBYZ, BOP_CAXY, BOP_CXPAY, BOP_CAXPBY, BOP_CXPYZ = range(10)
 BRED_NORM2, BRED_DOT, BRED_DIFFNORM2 = range(3)
 
 

@@ -9,9 +9,10 @@
 // takes a bit mask of ACTIVE systems: a system that has converged inside an inner solve is frozen -- neither read nor
 // written -- while the others continue, so each system sees exactly the iteration it would see alone.
 //
-// Per-system arithmetic is the single-vector kernels' (qmg_blas.hip, qmg_transfer.hip): element-wise ops are identical,
-// reductions use the same block partition and the same fixed-order second stage, so a batched inner product is
-// bit-identical to the unbatched one.
+// ONE system is a batch of one: the single-vector BLAS-1 and sum reductions of the C ABI (qmg_caxpy, qmg_norm2sq, qmg_multidot, ...) are
+// entry points of this file too and run these kernels at nrhs = 1, mask = 1, complex<double> (the end of the file).  A system's arithmetic does
+// not depend on the batch it is in: the element-wise operation order is DESIGN 4's table, and a reduction's block partition and fixed-order
+// second stage are per system, so an inner product has the same bits alone and in any batch.
 #include <string.h>
 #include <time.h>
 
@@ -23,21 +24,69 @@
 
 namespace qmg {
 
-constexpr int BRED_BLOCKS = 1024;    // partials per reduction per system (= RED_BLOCKS of qmg_blas.hip)
-
 // ---------------- element-wise ----------------
 // T = storage scalar (double | float), W = elements per 16-byte access (1 for double; 2 for float when the arrays are
 // 16-byte aligned with even n and stride, else 1).  Arithmetic is fp64 in registers for both T.
 struct BatchCoef { cplx a[BATCH_MAX], b[BATCH_MAX]; };   // indexed by system id
 
-// read-only operands of a batch whose active systems add up to `blas_nt_mb` MiB or more are streamed non-temporally (as in qmg_blas.hip:
-// +8-10 % on vectors the caches cannot hold anyway); the in/out operand never is.  A run-time, launch-uniform choice (the plan's `nt`).
+// read-only operands of a batch whose active systems add up to `blas_nt_mb` MiB or more are streamed non-temporally (+8-10 % on vectors
+// the caches cannot hold anyway: a five-stream read of 12 GB runs at 6.96 TB/s with the hint and 6.37 without, tools/membw4.hip); the in/out
+// operand never is (a non-temporal read of a line about to be stored loses 3 %).  A run-time, launch-uniform choice (the plan's `nt`).
 template <typename T, int W>
 __device__ __forceinline__ void ldb(const void* p, long i, cplx (&v)[W], bool nt) {
   if (nt) ldc_pack_nt<T, W>(p, i, v);
   else ldc_pack<T, W>(p, i, v);
 }
+// The same choice at compile time, for the kernels that one system of 256 MiB and more runs through (k_bblas, k_breduce, k_bmultidot: their loops exist
+// twice and the kernel picks one by the plan's bit).  Under the run-time form the compiler merges the two loads of a complex<double> element -- same
+// type, same address -- into ONE plain load: none of the complex<double> kernels that use ldb has an `nt` on a load in its ISA, which costs
+// 9-12 % at 512 MiB per vector (profiles/blas_one_engine.txt; the complex<float> forms differ in type and keep theirs).
+template <typename T, int W, bool NT>
+__device__ __forceinline__ void ldp(const void* p, long i, cplx (&v)[W]) {
+  if (NT) ldc_pack_nt<T, W>(p, i, v);
+  else ldc_pack<T, W>(p, i, v);
+}
 
+// the non-temporal store of a result that is no operand of its own pass (+4 % on vectors the caches cannot hold; on an in/out operand it gains nothing)
+template <typename T, int W>
+__device__ __forceinline__ void stc_pack_nt(void* base, long ipack, const cplx (&v)[W]) {
+  if constexpr (sizeof(T) == 4 && W == 2) {
+    typedef float f4 __attribute__((ext_vector_type(4)));
+    const f4 r = {(float)v[0].x, (float)v[0].y, (float)v[W - 1].x, (float)v[W - 1].y};
+    __builtin_nontemporal_store(r, reinterpret_cast<f4*>(base) + ipack);
+  } else {
+    typename CStore<T>::type* p = reinterpret_cast<typename CStore<T>::type*>(base) + ipack;
+    __builtin_nontemporal_store((T)v[0].x, &p->x);
+    __builtin_nontemporal_store((T)v[0].y, &p->y);
+  }
+}
+// NT / YNT: x / y are read non-temporally; with both, z of the ops that do not read z is stored non-temporally
+template <int OP, typename T, int W, bool NT, bool YNT>
+__device__ __forceinline__ void bblas_run(typename CStore<T>::type* z, const typename CStore<T>::type* x, const typename CStore<T>::type* y, cplx a, cplx b, long np) {
+  for (long i = (long)blockIdx.x * BLOCK + threadIdx.x; i < np; i += (long)gridDim.x * BLOCK) {
+    cplx r[W], u[W], v[W];
+    if (OP == QMG_BOP_CAX || OP == QMG_BOP_CAXPY || OP == QMG_BOP_CXPY || OP == QMG_BOP_CXPAY || OP == QMG_BOP_CAXPBY) ldc_pack<T, W>(z, i, r);
+    if (OP != QMG_BOP_ZERO && OP != QMG_BOP_CAX) ldp<T, W, NT>(x, i, u);
+    if (OP == QMG_BOP_CAXPBYZ || OP == QMG_BOP_CXPYZ) ldp<T, W, YNT>(y, i, v);
+#pragma unroll
+    for (int w = 0; w < W; w++) {
+      if (OP == QMG_BOP_ZERO) r[w] = cmake(0.0, 0.0);
+      else if (OP == QMG_BOP_COPY) r[w] = u[w];
+      else if (OP == QMG_BOP_CAX) r[w] = cmul(a, r[w]);
+      else if (OP == QMG_BOP_CAXPY) cmac(r[w], a, u[w]);
+      else if (OP == QMG_BOP_CXPY) r[w] = cadd(r[w], u[w]);
+      else if (OP == QMG_BOP_CAXY) r[w] = cmul(a, u[w]);
+      else if (OP == QMG_BOP_CXPAY) { const cplx t = r[w]; r[w] = u[w]; cmac(r[w], a, t); }
+      else if (OP == QMG_BOP_CAXPBY) { r[w] = cmul(b, r[w]); cmac(r[w], a, u[w]); }
+      else if (OP == QMG_BOP_CXPYZ) r[w] = cadd(u[w], v[w]);
+      else { r[w] = cmul(a, u[w]); cmac(r[w], b, v[w]); }   // CAXPBYZ
+    }
+    constexpr bool reads_z = OP == QMG_BOP_CAX || OP == QMG_BOP_CAXPY || OP == QMG_BOP_CXPY || OP == QMG_BOP_CXPAY || OP == QMG_BOP_CAXPBY;
+    constexpr bool reads_y = OP == QMG_BOP_CAXPBYZ || OP == QMG_BOP_CXPYZ;
+    if (NT && !reads_z && (YNT || !reads_y)) stc_pack_nt<T, W>(z, i, r);
+    else stc_pack<T, W>(z, i, r);
+  }
+}
 template <int OP, typename T, int W>
 __global__ __launch_bounds__(BLOCK) void k_bblas(void* __restrict__ z_, const void* __restrict__ x_, const void* __restrict__ y_, const BatchCoef c,
                                                  const BatchIdx bi, long n, long stride) {
@@ -48,22 +97,10 @@ __global__ __launch_bounds__(BLOCK) void k_bblas(void* __restrict__ z_, const vo
   const ct* y = reinterpret_cast<const ct*>(y_) + (long)k * stride;
   const cplx a = c.a[k], b = c.b[k];
   const long np = n / W;
-  for (long i = (long)blockIdx.x * BLOCK + threadIdx.x; i < np; i += (long)gridDim.x * BLOCK) {
-    cplx r[W], u[W], v[W];
-    if (OP == QMG_BOP_CAX || OP == QMG_BOP_CAXPY || OP == QMG_BOP_CXPY) ldc_pack<T, W>(z, i, r);
-    if (OP == QMG_BOP_COPY || OP == QMG_BOP_CAXPY || OP == QMG_BOP_CXPY || OP == QMG_BOP_CAXPBYZ) ldb<T, W>(x, i, u, bi.nt);
-    if (OP == QMG_BOP_CAXPBYZ) ldb<T, W>(y, i, v, bi.nt && y_ != z_);   // (z = a x + b z is the common aliased use: then y is the in/out operand)
-#pragma unroll
-    for (int w = 0; w < W; w++) {
-      if (OP == QMG_BOP_ZERO) r[w] = cmake(0.0, 0.0);
-      else if (OP == QMG_BOP_COPY) r[w] = u[w];
-      else if (OP == QMG_BOP_CAX) r[w] = cmul(a, r[w]);
-      else if (OP == QMG_BOP_CAXPY) cmac(r[w], a, u[w]);
-      else if (OP == QMG_BOP_CXPY) r[w] = cadd(r[w], u[w]);
-      else { r[w] = cmul(a, u[w]); cmac(r[w], b, v[w]); }   // CAXPBYZ
-    }
-    stc_pack<T, W>(z, i, r);
-  }
+  constexpr bool reads_y = OP == QMG_BOP_CAXPBYZ || OP == QMG_BOP_CXPYZ;
+  if (!bi.nt) bblas_run<OP, T, W, false, false>(z, x, y, a, b, np);
+  else if (reads_y && y_ == z_) bblas_run<OP, T, W, true, false>(z, x, y, a, b, np);   // (z = a x + b z is the common aliased use: then y is the in/out operand)
+  else bblas_run<OP, T, W, true, reads_y>(z, x, y, a, b, np);
 }
 
 // y_k += sum_j a[j][k] x_j,k for up to BMAXPY_J = 8 vector sets per launch (coefficients travel as kernel arguments)
@@ -239,36 +276,16 @@ __global__ __launch_bounds__(BLOCK) void k_bcgm_update(const BatchCgm m, const v
   }
 }
 
-// ---------------- reductions (two-stage, deterministic; fp64: partition identical to qmg_blas.hip) ----------------
-template <int NV>
-__device__ __forceinline__ void bblock_reduce_store(double* v, double* partial_out) {
-  __shared__ double sm[NV][BLOCK / WAVE];
-  const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
-  const double w = wave_reduce_many<NV>(v);   // lane q: wave_sum(v[q]), bit for bit
-  if (lane < NV) sm[lane][wv] = w;
-  __syncthreads();
-  if (threadIdx.x < NV) {
-    double t = sm[threadIdx.x][0];
-#pragma unroll
-    for (int w = 1; w < BLOCK / WAVE; w++) t += sm[threadIdx.x][w];
-    partial_out[threadIdx.x] = t;
-  }
-}
-
-// partials layout: [system slot s][block][2*width]
-template <int OP, typename T, int W>
-__global__ __launch_bounds__(BLOCK) void k_breduce(const void* __restrict__ x_, const void* __restrict__ y_, long n, long stride, const BatchIdx bi,
-                                                   double* __restrict__ partials) {
-  typedef typename CStore<T>::type ct;
-  const long off = (long)bi.id[blockIdx.y] * stride;
-  const ct* x = reinterpret_cast<const ct*>(x_) + off;
-  const ct* y = reinterpret_cast<const ct*>(y_) + off;
-  double v[2] = {0.0, 0.0};
-  const long np = n / W;
+// ---------------- reductions ----------------
+// Two-stage and DETERMINISTIC: each lane accumulates a grid-strided slice in fp64, wave_reduce_many sums the wavefront, LDS the four
+// wavefronts of the block (block_reduce_store, qmg_common.h), the block writes one partial, and a second tiny launch sums the (fixed number
+// of) partials in a fixed order -- no float atomics, so two runs give bit-identical inner products.
+template <int OP, typename T, int W, bool NT>
+__device__ __forceinline__ void breduce_run(const typename CStore<T>::type* x, const typename CStore<T>::type* y, long np, double (&v)[2]) {
   for (long i = (long)blockIdx.x * BLOCK + threadIdx.x; i < np; i += (long)gridDim.x * BLOCK) {
     cplx av[W], bv[W];
-    ldb<T, W>(x, i, av, bi.nt);
-    if (OP != QMG_BRED_NORM2) ldb<T, W>(y, i, bv, bi.nt);
+    ldp<T, W, NT>(x, i, av);
+    if (OP != QMG_BRED_NORM2) ldp<T, W, NT>(y, i, bv);
 #pragma unroll
     for (int w = 0; w < W; w++) {
       const cplx a = av[w];
@@ -284,10 +301,40 @@ __global__ __launch_bounds__(BLOCK) void k_breduce(const void* __restrict__ x_, 
       }
     }
   }
-  bblock_reduce_store<2>(v, partials + ((long)blockIdx.y * gridDim.x + blockIdx.x) * 2);
 }
-
+// partials layout: [system slot s][block][2*width]
+template <int OP, typename T, int W>
+__global__ __launch_bounds__(BLOCK) void k_breduce(const void* __restrict__ x_, const void* __restrict__ y_, long n, long stride, const BatchIdx bi,
+                                                   double* __restrict__ partials) {
+  typedef typename CStore<T>::type ct;
+  const long off = (long)bi.id[blockIdx.y] * stride;
+  const ct* x = reinterpret_cast<const ct*>(x_) + off;
+  const ct* y = reinterpret_cast<const ct*>(y_) + off;
+  double v[2] = {0.0, 0.0};
+  if (bi.nt) breduce_run<OP, T, W, true>(x, y, n / W, v);
+  else breduce_run<OP, T, W, false>(x, y, n / W, v);
+  block_reduce_store<2>(v, partials + ((long)blockIdx.y * gridDim.x + blockIdx.x) * 2);
+}
 struct BatchPtrs { const void* x[BDOT_MAX]; };
+template <int KT, typename T, int W, bool NT>
+__device__ __forceinline__ void bmultidot_run(const BatchPtrs& xs, int j0, const typename CStore<T>::type* y, long off, long np, double (&v)[2 * KT]) {
+  typedef typename CStore<T>::type ct;
+  for (long i = (long)blockIdx.x * BLOCK + threadIdx.x; i < np; i += (long)gridDim.x * BLOCK) {
+    cplx bv[W];
+    ldp<T, W, NT>(y, i, bv);
+#pragma unroll
+    for (int q = 0; q < KT; q++) {
+      cplx av[W];
+      ldp<T, W, NT>(reinterpret_cast<const ct*>(xs.x[j0 + q]) + off, i, av);
+#pragma unroll
+      for (int w = 0; w < W; w++) {
+        const cplx a = av[w], b = bv[w];
+        v[2 * q] = fma(a.x, b.x, v[2 * q]); v[2 * q] = fma(a.y, b.y, v[2 * q]);
+        v[2 * q + 1] = fma(a.x, b.y, v[2 * q + 1]); v[2 * q + 1] = fma(-a.y, b.x, v[2 * q + 1]);
+      }
+    }
+  }
+}
 // KT dots <x_j,k , y_k> per system in one pass over y_k
 template <int KT, typename T, int W>
 __global__ __launch_bounds__(BLOCK) void k_bmultidot(const BatchPtrs xs, int j0, const void* __restrict__ y_, long n, long stride, const BatchIdx bi,
@@ -298,23 +345,9 @@ __global__ __launch_bounds__(BLOCK) void k_bmultidot(const BatchPtrs xs, int j0,
   double v[2 * KT];
 #pragma unroll
   for (int q = 0; q < 2 * KT; q++) v[q] = 0.0;
-  const long np = n / W;
-  for (long i = (long)blockIdx.x * BLOCK + threadIdx.x; i < np; i += (long)gridDim.x * BLOCK) {
-    cplx bv[W];
-    ldb<T, W>(y, i, bv, bi.nt);
-#pragma unroll
-    for (int q = 0; q < KT; q++) {
-      cplx av[W];
-      ldb<T, W>(reinterpret_cast<const ct*>(xs.x[j0 + q]) + off, i, av, bi.nt);
-#pragma unroll
-      for (int w = 0; w < W; w++) {
-        const cplx a = av[w], b = bv[w];
-        v[2 * q] = fma(a.x, b.x, v[2 * q]); v[2 * q] = fma(a.y, b.y, v[2 * q]);
-        v[2 * q + 1] = fma(a.x, b.y, v[2 * q + 1]); v[2 * q + 1] = fma(-a.y, b.x, v[2 * q + 1]);
-      }
-    }
-  }
-  bblock_reduce_store<2 * KT>(v, partials + ((long)blockIdx.y * gridDim.x + blockIdx.x) * 2 * jtot + 2 * j0);
+  if (bi.nt) bmultidot_run<KT, T, W, true>(xs, j0, y, off, n / W, v);
+  else bmultidot_run<KT, T, W, false>(xs, j0, y, off, n / W, v);
+  block_reduce_store<2 * KT>(v, partials + ((long)blockIdx.y * gridDim.x + blockIdx.x) * 2 * jtot + 2 * j0);
 }
 
 // stage 2: block (q, s) sums the nparts partials of output q of system slot s in a fixed order
@@ -406,33 +439,21 @@ __global__ __launch_bounds__(BLOCK) void k_bmr_final(const double* __restrict__ 
   }
 }
 
-struct BatchWorkspace {
-  double* partials = nullptr;   // BATCH_MAX * BRED_BLOCKS * 2 * BDOT_MAX doubles (8 MiB)
-  double* pinned = nullptr;     // host-pinned, device-visible results: BATCH_MAX * 2 * BDOT_MAX doubles
-  double* result = nullptr;     // the same in HBM: where the results go when they are summed over ranks first
-  double* mr = nullptr;         // device-resident scalars of the MR smoother: [system][4] = Re<p,r>, Im<p,r>, <p,p>, - (qmg_batch_mr_*)
-  double* epi_part = nullptr;   // partials of an apply's MR epilogue ([system slot][wavefront][4]), grown on demand
-  size_t epi_cap = 0;
-  unsigned* done = nullptr;              // blocks of the current final stage that have stored their result (device)
-  unsigned long long* flag = nullptr;    // host-pinned, coherent: sequence number of the last final stage whose results are in `pinned`
-  unsigned long long seq = 0;
-  int device = -1;
-};
 static thread_local BatchWorkspace g_bws;
 
-static int get_bws(BatchWorkspace** out) {
+int get_bws(BatchWorkspace** out) {
   int dev = 0;
   QMG_HIP_CHECK(hipGetDevice(&dev));
   if (g_bws.device != dev) {
-    QMG_HIP_CHECK(hipMalloc((void**)&g_bws.partials, sizeof(double) * BATCH_MAX * BRED_BLOCKS * 2 * BDOT_MAX));
-    QMG_HIP_CHECK(hipHostMalloc((void**)&g_bws.pinned, sizeof(double) * BATCH_MAX * 2 * BDOT_MAX, hipHostMallocCoherent));
+    QMG_HIP_CHECK(hipMalloc((void**)&g_bws.partials, sizeof(double) * WS_PARTIALS));
+    QMG_HIP_CHECK(hipHostMalloc((void**)&g_bws.pinned, sizeof(double) * WS_RESULTS, hipHostMallocCoherent));
     QMG_HIP_CHECK(hipHostMalloc((void**)&g_bws.flag, 64, hipHostMallocCoherent));
     *g_bws.flag = 0;
     g_bws.seq = 0;
     QMG_HIP_CHECK(hipMalloc((void**)&g_bws.done, sizeof(unsigned)));
     QMG_HIP_CHECK(hipMemset(g_bws.done, 0, sizeof(unsigned)));
-    QMG_HIP_CHECK(hipMalloc((void**)&g_bws.result, sizeof(double) * BATCH_MAX * 2 * BDOT_MAX));
-    QMG_HIP_CHECK(hipMemset(g_bws.result, 0, sizeof(double) * BATCH_MAX * 2 * BDOT_MAX));
+    QMG_HIP_CHECK(hipMalloc((void**)&g_bws.result, sizeof(double) * WS_RESULTS));
+    QMG_HIP_CHECK(hipMemset(g_bws.result, 0, sizeof(double) * WS_RESULTS));
     QMG_HIP_CHECK(hipMalloc((void**)&g_bws.mr, sizeof(double) * BATCH_MAX * 4));
     QMG_HIP_CHECK(hipMemset(g_bws.mr, 0, sizeof(double) * BATCH_MAX * 4));
     g_bws.device = dev;
@@ -479,6 +500,12 @@ static int wait_results(BatchWorkspace* ws, bool flagged, hipStream_t st) {
   return QMG_SUCCESS;
 }
 
+double* result_slot(BatchWorkspace* ws, double* out_dev) { return out_dev ? out_dev : (dist_reductions_on() ? ws->result : ws->pinned); }
+int results_to_host(BatchWorkspace* ws, const double* res, int count, bool flagged, hipStream_t st) {
+  if (res != ws->pinned) QMG_HIP_CHECK(hipMemcpyAsync(ws->pinned, res, sizeof(double) * count, hipMemcpyDeviceToHost, st));
+  return wait_results(ws, flagged, st);
+}
+
 double* mr_epilogue_begin(int nsys, long npart) {
   BatchWorkspace* ws;
   if (get_bws(&ws) != QMG_SUCCESS) return nullptr;
@@ -490,13 +517,6 @@ double* mr_epilogue_begin(int nsys, long npart) {
     ws->epi_cap = need;
   }
   return ws->epi_part;
-}
-
-static unsigned bred_grid(long n) {
-  long b = (n + BLOCK - 1) / BLOCK;
-  if (b > BRED_BLOCKS) b = BRED_BLOCKS;
-  if (b < 1) b = 1;
-  return (unsigned)b;
 }
 
 int mr_epilogue_finish(const unsigned char* ids, int n, long npart, hipStream_t st) {
@@ -554,10 +574,11 @@ extern "C" {
 int qmg_batch_blas_t(int dtype, int op, const double* a, const double* b, const void* x, const void* y, void* z, size_t n, int nrhs, size_t stride,
                      unsigned mask, void* stream) {
   if (!valid_dtype(dtype) || nrhs < 1 || nrhs > BATCH_MAX || (!z && n)) return QMG_ERR_INVALID;
-  if (op < QMG_BOP_ZERO || op > QMG_BOP_CAXPBYZ) return QMG_ERR_INVALID;
-  if ((op == QMG_BOP_COPY || op == QMG_BOP_CAXPY || op == QMG_BOP_CXPY || op == QMG_BOP_CAXPBYZ) && !x && n) return QMG_ERR_INVALID;
-  if (op == QMG_BOP_CAXPBYZ && ((!y && n) || !b)) return QMG_ERR_INVALID;
-  if ((op == QMG_BOP_CAX || op == QMG_BOP_CAXPY || op == QMG_BOP_CAXPBYZ) && !a) return QMG_ERR_INVALID;
+  if (op < QMG_BOP_ZERO || op > QMG_BOP_CXPYZ) return QMG_ERR_INVALID;
+  const bool reads_x = op != QMG_BOP_ZERO && op != QMG_BOP_CAX, reads_y = op == QMG_BOP_CAXPBYZ || op == QMG_BOP_CXPYZ;
+  const bool uses_b = op == QMG_BOP_CAXPBYZ || op == QMG_BOP_CAXPBY;
+  const bool uses_a = uses_b || op == QMG_BOP_CAX || op == QMG_BOP_CAXPY || op == QMG_BOP_CAXY || op == QMG_BOP_CXPAY;
+  if ((reads_x && !x && n) || (reads_y && !y && n) || (uses_a && !a) || (uses_b && !b)) return QMG_ERR_INVALID;
   BatchPlanRequest rq = batch_request(QMG_BE_BLAS, dtype, n, stride, nrhs, mask, all_aligned16({x, y, z}));
   rq.op = op;
   const BatchPass pl = batch_plan(rq);
@@ -571,17 +592,16 @@ int qmg_batch_blas_t(int dtype, int op, const double* a, const double* b, const 
   const int W = pl.W;
   dim3 grid(grid_1d(n / W), (unsigned)bi.n);
   hipStream_t st = as_stream(stream);
-#define QMG_K(T, WW)                                                                                                        \
-  switch (pl.variant) {                                                                                                             \
-    case QMG_BOP_ZERO: k_bblas<QMG_BOP_ZERO, T, WW><<<grid, BLOCK, 0, st>>>(z, nullptr, nullptr, c, bi, (long)n, (long)stride); break;   \
-    case QMG_BOP_COPY: k_bblas<QMG_BOP_COPY, T, WW><<<grid, BLOCK, 0, st>>>(z, x, nullptr, c, bi, (long)n, (long)stride); break;        \
-    case QMG_BOP_CAX: k_bblas<QMG_BOP_CAX, T, WW><<<grid, BLOCK, 0, st>>>(z, nullptr, nullptr, c, bi, (long)n, (long)stride); break;    \
-    case QMG_BOP_CAXPY: k_bblas<QMG_BOP_CAXPY, T, WW><<<grid, BLOCK, 0, st>>>(z, x, nullptr, c, bi, (long)n, (long)stride); break;      \
-    case QMG_BOP_CXPY: k_bblas<QMG_BOP_CXPY, T, WW><<<grid, BLOCK, 0, st>>>(z, x, nullptr, c, bi, (long)n, (long)stride); break;        \
-    default: k_bblas<QMG_BOP_CAXPBYZ, T, WW><<<grid, BLOCK, 0, st>>>(z, x, y, c, bi, (long)n, (long)stride); break;                   \
+#define QMG_OP(OP, T, WW) case OP: k_bblas<OP, T, WW><<<grid, BLOCK, 0, st>>>(z, x, y, c, bi, (long)n, (long)stride); break;
+#define QMG_K(T, WW)                                                                                                         \
+  switch (pl.variant) {                                                                                                      \
+    QMG_OP(QMG_BOP_ZERO, T, WW) QMG_OP(QMG_BOP_COPY, T, WW) QMG_OP(QMG_BOP_CAX, T, WW) QMG_OP(QMG_BOP_CAXPY, T, WW) QMG_OP(QMG_BOP_CXPY, T, WW) \
+    QMG_OP(QMG_BOP_CAXY, T, WW) QMG_OP(QMG_BOP_CXPAY, T, WW) QMG_OP(QMG_BOP_CAXPBY, T, WW) QMG_OP(QMG_BOP_CXPYZ, T, WW)      \
+    default: k_bblas<QMG_BOP_CAXPBYZ, T, WW><<<grid, BLOCK, 0, st>>>(z, x, y, c, bi, (long)n, (long)stride); break;          \
   }
   QMG_DISPATCH_TW(dtype, W, QMG_K);
 #undef QMG_K
+#undef QMG_OP
   QMG_LAUNCH_CHECK();
   return QMG_SUCCESS;
 }
@@ -598,10 +618,10 @@ int qmg_batch_multi_caxpy_t(int dtype, const double* coeffs, const void* const* 
   rq.nj = nj;
   BatchPass pl = batch_plan(rq);
   if (pl.family == BF_NOTHING) return QMG_SUCCESS;
-  // one fp64 system on long vectors (a single outer solve on the fine lattice): the single-vector kernel, which takes up to 32 vector sets per
-  // pass over y instead of 8 -- the same sums in the same order
+  // one fp64 system on long vectors (a single outer solve on the fine lattice): k_multi_caxpy (qmg_blas.hip), which takes up to 32 vector sets
+  // per pass over y instead of 8 -- the same sums in the same order
   // -- on the vector sets whose coefficient is not zero, in their order: a zero coefficient means "not read" here as in the batch kernels, and
-  // the single-vector kernel multiplies whatever it is given (0 * nan = nan)
+  // that kernel multiplies whatever it is given (0 * nan = nan)
   if (pl.family == BF_MAXPY_SINGLE) {
     std::vector<double> cf;
     std::vector<const void*> used;
@@ -717,11 +737,30 @@ int qmg_batch_cgm_update_t(int dtype, const void* const* xs, const void* const* 
   return QMG_SUCCESS;
 }
 
-// out_host[2*k + {0,1}] for every ACTIVE system k (inactive entries are left untouched); returns when they are on the host (wait_results)
-int qmg_batch_reduce_t(int dtype, int op, const void* x, const void* y, size_t n, int nrhs, size_t stride, unsigned mask, double* out_host, void* stream) {
-  if (!valid_dtype(dtype) || nrhs < 1 || nrhs > BATCH_MAX || !x || !out_host) return QMG_ERR_INVALID;
-  if (op < QMG_BRED_NORM2 || op > QMG_BRED_DIFFNORM2) return QMG_ERR_INVALID;
-  if (op != QMG_BRED_NORM2 && !y) return QMG_ERR_INVALID;
+// Stage 2 of a sum reduction and the way of its results, shared by every launcher below: block (q, system) of the final stage writes output q
+// (of `width`; the partials hold `pwidth` per block) of every active system k to res[k * width + q], res being the caller's device pointer
+// or the workspace's slot (result_slot).  Under distributed reductions the results are summed over the ranks where they are (every rank has
+// the same active mask: the lock-step decisions are taken on these very sums).  out_host == NULL: that is all, nothing waits.  Else the
+// active systems' results are on the host when this returns (wait_results); inactive entries of out_host are left untouched.
+static int reduce_finish(BatchWorkspace* ws, unsigned nparts, int pwidth, int width, const BatchIdx& bi, int nrhs, double* out_dev, double* out_host,
+                         hipStream_t st) {
+  double* res = result_slot(ws, out_dev);
+  const bool flagged = res == ws->pinned && spin_results(ws);
+  const dim3 grid(width, (unsigned)bi.n);
+  if (flagged) k_breduce_final<<<grid, BLOCK, 0, st>>>(ws->partials, (int)nparts, pwidth, bi, width, res, ws->done, ws->flag, ++ws->seq);
+  else k_breduce_final<<<grid, BLOCK, 0, st>>>(ws->partials, (int)nparts, pwidth, bi, width, res);
+  QMG_LAUNCH_CHECK();
+  if (dist_reductions_on()) { const int rc = dist_allreduce(res, width * nrhs, false, st); if (rc) return rc; }
+  if (!out_host) return QMG_SUCCESS;
+  const int rc = results_to_host(ws, res, width * nrhs, flagged, st);
+  if (rc) return rc;
+  for (int s = 0; s < bi.n; s++) memcpy(out_host + (size_t)bi.id[s] * width, ws->pinned + (size_t)bi.id[s] * width, sizeof(double) * width);
+  return QMG_SUCCESS;
+}
+
+// `width` doubles per system (2: re, im; 1: a real result alone) to out_dev and / or out_host (reduce_finish); the caller has checked the arguments
+static int reduce_run(int dtype, int op, const void* x, const void* y, size_t n, int nrhs, size_t stride, unsigned mask, int width, double* out_dev,
+                      double* out_host, void* stream) {
   BatchPlanRequest rq = batch_request(QMG_BE_REDUCE, dtype, n, stride, nrhs, mask, all_aligned16({x, y}));
   rq.op = op;
   const BatchPass pl = batch_plan(rq);
@@ -732,7 +771,7 @@ int qmg_batch_reduce_t(int dtype, int op, const void* x, const void* y, size_t n
   if (rc) return rc;
   hipStream_t st = as_stream(stream);
   const int W = pl.W;
-  const unsigned g = bred_grid((long)(n / W));
+  const unsigned g = red_grid((long)(n / W));
   dim3 grid(g, (unsigned)bi.n);
 #define QMG_K(T, WW)                                                                                                                      \
   if (op == QMG_BRED_NORM2) k_breduce<QMG_BRED_NORM2, T, WW><<<grid, BLOCK, 0, st>>>(x, nullptr, (long)n, (long)stride, bi, ws->partials); \
@@ -741,31 +780,23 @@ int qmg_batch_reduce_t(int dtype, int op, const void* x, const void* y, size_t n
   QMG_DISPATCH_TW(dtype, W, QMG_K);
 #undef QMG_K
   QMG_LAUNCH_CHECK();
-  // slabs of one lattice: the per-system results are summed over the ranks before they reach the host (every rank has
-  // the same active mask: the lock-step decisions are taken on these very sums)
-  const bool dist = dist_reductions_on();
-  const bool flagged = !dist && spin_results(ws);
-  if (flagged) k_breduce_final<<<dim3(2, (unsigned)bi.n), BLOCK, 0, st>>>(ws->partials, (int)g, 2, bi, 2, ws->pinned, ws->done, ws->flag, ++ws->seq);
-  else k_breduce_final<<<dim3(2, (unsigned)bi.n), BLOCK, 0, st>>>(ws->partials, (int)g, 2, bi, 2, dist ? ws->result : ws->pinned);
-  QMG_LAUNCH_CHECK();
-  if (dist) {
-    rc = dist_allreduce(ws->result, 2 * nrhs, false, st);
-    if (rc) return rc;
-    QMG_HIP_CHECK(hipMemcpyAsync(ws->pinned, ws->result, sizeof(double) * 2 * nrhs, hipMemcpyDeviceToHost, st));
-  }
-  rc = wait_results(ws, flagged, st);
-  if (rc) return rc;
-  for (int s = 0; s < bi.n; s++) { out_host[2 * bi.id[s]] = ws->pinned[2 * bi.id[s]]; out_host[2 * bi.id[s] + 1] = ws->pinned[2 * bi.id[s] + 1]; }
-  return QMG_SUCCESS;
+  return reduce_finish(ws, g, 2, width, bi, nrhs, out_dev, out_host, st);
+}
+
+// out_host[2*k + {0,1}] for every ACTIVE system k (inactive entries are left untouched); returns when they are on the host (wait_results)
+int qmg_batch_reduce_t(int dtype, int op, const void* x, const void* y, size_t n, int nrhs, size_t stride, unsigned mask, double* out_host, void* stream) {
+  if (!valid_dtype(dtype) || nrhs < 1 || nrhs > BATCH_MAX || !x || !out_host) return QMG_ERR_INVALID;
+  if (op < QMG_BRED_NORM2 || op > QMG_BRED_DIFFNORM2) return QMG_ERR_INVALID;
+  if (op != QMG_BRED_NORM2 && !y) return QMG_ERR_INVALID;
+  return reduce_run(dtype, op, x, y, n, nrhs, stride, mask, 2, nullptr, out_host, stream);
 }
 int qmg_batch_reduce(int op, const void* x, const void* y, size_t n, int nrhs, size_t stride, unsigned mask, double* out_host, void* stream) {
   return qmg_batch_reduce_t(QMG_C64, op, x, y, n, nrhs, stride, mask, out_host, stream);
 }
 
-// out_host[(k*nj + j)*2 + {0,1}] = <xs[j]_k , y_k> for every active system k; returns when they are on the host (wait_results)
-int qmg_batch_multidot_t(int dtype, const void* const* xs, int nj, const void* y, size_t n, int nrhs, size_t stride, unsigned mask, double* out_host,
-                         void* stream) {
-  if (!valid_dtype(dtype) || nrhs < 1 || nrhs > BATCH_MAX || nj < 1 || nj > BDOT_MAX || !xs || !y || !out_host) return QMG_ERR_INVALID;
+// <xs[j]_k , y_k> for 1 <= nj <= BDOT_MAX vector sets, 2 nj doubles per system, to out_dev and / or out_host (reduce_finish); the caller has checked the arguments
+static int multidot_run(int dtype, const void* const* xs, int nj, const void* y, size_t n, int nrhs, size_t stride, unsigned mask, double* out_dev,
+                        double* out_host, void* stream) {
   BatchPlanRequest rq = batch_request(QMG_BE_MULTIDOT, dtype, n, stride, nrhs, mask, all_aligned16({y}) && all_aligned16(xs, 0, nj));
   rq.nj = nj;
   BatchPass pl = batch_plan(rq);
@@ -781,9 +812,9 @@ int qmg_batch_multidot_t(int dtype, const void* const* xs, int nj, const void* y
     p.x[j] = (j < nj) ? xs[j] : nullptr;
     if (j < nj && !xs[j]) return QMG_ERR_INVALID;
   }
-  const unsigned g = bred_grid((long)(n / W));
+  const unsigned g = red_grid((long)(n / W));
   dim3 grid(g, (unsigned)bi.n);
-  for (;; pl = batch_plan(rq, pl.next)) {   // same 8/4/2/1 chunking as qmg_multidot
+  for (;; pl = batch_plan(rq, pl.next)) {   // chunks of 8 / 4 / 2 / 1 dots (batch_plan)
     const int j0 = pl.at, kt = pl.J;
 #define QMG_K(T, WW)                                                                                                  \
     if (kt == 8) k_bmultidot<8, T, WW><<<grid, BLOCK, 0, st>>>(p, j0, y, (long)n, (long)stride, bi, ws->partials, nj);   \
@@ -795,22 +826,14 @@ int qmg_batch_multidot_t(int dtype, const void* const* xs, int nj, const void* y
     QMG_LAUNCH_CHECK();
     if (pl.next < 0) break;
   }
-  const bool dist = dist_reductions_on();
-  const bool flagged = !dist && spin_results(ws);
-  if (flagged)
-    k_breduce_final<<<dim3(2 * nj, (unsigned)bi.n), BLOCK, 0, st>>>(ws->partials, (int)g, 2 * nj, bi, 2 * nj, ws->pinned, ws->done, ws->flag, ++ws->seq);
-  else k_breduce_final<<<dim3(2 * nj, (unsigned)bi.n), BLOCK, 0, st>>>(ws->partials, (int)g, 2 * nj, bi, 2 * nj, dist ? ws->result : ws->pinned);
-  QMG_LAUNCH_CHECK();
-  if (dist) {
-    rc = dist_allreduce(ws->result, 2 * nj * nrhs, false, st);
-    if (rc) return rc;
-    QMG_HIP_CHECK(hipMemcpyAsync(ws->pinned, ws->result, sizeof(double) * 2 * nj * nrhs, hipMemcpyDeviceToHost, st));
-  }
-  rc = wait_results(ws, flagged, st);
-  if (rc) return rc;
-  for (int s = 0; s < bi.n; s++)
-    memcpy(out_host + (size_t)bi.id[s] * 2 * nj, ws->pinned + (size_t)bi.id[s] * 2 * nj, sizeof(double) * 2 * nj);
-  return QMG_SUCCESS;
+  return reduce_finish(ws, g, 2 * nj, 2 * nj, bi, nrhs, out_dev, out_host, st);
+}
+
+// out_host[(k*nj + j)*2 + {0,1}] = <xs[j]_k , y_k> for every active system k; returns when they are on the host (wait_results)
+int qmg_batch_multidot_t(int dtype, const void* const* xs, int nj, const void* y, size_t n, int nrhs, size_t stride, unsigned mask, double* out_host,
+                         void* stream) {
+  if (!valid_dtype(dtype) || nrhs < 1 || nrhs > BATCH_MAX || nj < 1 || nj > BDOT_MAX || !xs || !y || !out_host) return QMG_ERR_INVALID;
+  return multidot_run(dtype, xs, nj, y, n, nrhs, stride, mask, nullptr, out_host, stream);
 }
 int qmg_batch_multidot(const void* const* xs, int nj, const void* y, size_t n, int nrhs, size_t stride, unsigned mask, double* out_host, void* stream) {
   return qmg_batch_multidot_t(QMG_C64, xs, nj, y, n, nrhs, stride, mask, out_host, stream);
@@ -833,7 +856,7 @@ int qmg_batch_mr_dots_t(int dtype, const void* r, const void* p, size_t n, int n
   for (int j = 0; j < BDOT_MAX; j++) ptr.x[j] = nullptr;
   ptr.x[0] = r; ptr.x[1] = p;
   const int W = pl.W;
-  const unsigned g = bred_grid((long)(n / W));
+  const unsigned g = red_grid((long)(n / W));
   dim3 grid(g, (unsigned)bi.n);
 #define QMG_K(T, WW) k_bmultidot<2, T, WW><<<grid, BLOCK, 0, st>>>(ptr, 0, p, (long)n, (long)stride, bi, ws->partials, 2)
   QMG_DISPATCH_TW(dtype, W, QMG_K);
@@ -891,7 +914,7 @@ int qmg_batch_plan(int entry, int dtype, int op, size_t n, size_t stride, int nr
                    int aligned16_, int* plan_out, int max_passes) {
   if (!plan_out || max_passes < 1 || !valid_dtype(dtype) || nrhs < 1 || nrhs > BATCH_MAX) return QMG_ERR_INVALID;
   switch (entry) {
-    case QMG_BE_BLAS: if (op < QMG_BOP_ZERO || op > QMG_BOP_CAXPBYZ || nj || flags) return QMG_ERR_INVALID; break;
+    case QMG_BE_BLAS: if (op < QMG_BOP_ZERO || op > QMG_BOP_CXPYZ || nj || flags) return QMG_ERR_INVALID; break;
     case QMG_BE_MULTI_CAXPY: if (nj < 0 || op || flags) return QMG_ERR_INVALID; break;
     case QMG_BE_GCR_UPDATE: if (nj < 0 || op || (flags & ~BPV_ZNEXT)) return QMG_ERR_INVALID; break;
     case QMG_BE_CGM_UPDATE: if (nj < 1 || nj > BATCH_MAX || !shift_masks || op || flags) return QMG_ERR_INVALID; break;
@@ -911,6 +934,48 @@ int qmg_batch_plan(int entry, int dtype, int op, size_t n, size_t stride, int nr
     const int v[BATCH_PLAN_INTS] = {pl.family, pl.W, pl.nt, pl.J, pl.variant};
     for (int i = 0; i < BATCH_PLAN_INTS; i++) plan_out[BATCH_PLAN_INTS * passes + i] = v[i];
     at = pl.next;
+  }
+  return QMG_SUCCESS;
+}
+
+// ---- ONE system: the single-vector BLAS-1 and sum reductions of the C ABI are the launchers above at nrhs = 1, mask = 1, complex<double>.
+// (qmg_multi_caxpy, qmg_norminf and the per-timeslice sums have no batch form: qmg_blas.hip.)
+static int blas1(int op, double ar, double ai, double br, double bi, const void* x, const void* y, void* z, size_t n, void* s) {
+  const double a[2] = {ar, ai}, b[2] = {br, bi};
+  return qmg_batch_blas_t(QMG_C64, op, a, b, x, y, z, n, 1, 0, 1u, s);   // (its argument checks are the single-vector ones: a NULL vector only with n = 0)
+}
+int qmg_zero_vector(void* x, size_t n, void* s) { return blas1(QMG_BOP_ZERO, 0, 0, 0, 0, nullptr, nullptr, x, n, s); }
+int qmg_copy_vector(void* dst, const void* src, size_t n, void* s) { return blas1(QMG_BOP_COPY, 0, 0, 0, 0, src, nullptr, dst, n, s); }
+int qmg_cax(double ar, double ai, void* x, size_t n, void* s) { return blas1(QMG_BOP_CAX, ar, ai, 0, 0, nullptr, nullptr, x, n, s); }
+int qmg_caxy(double ar, double ai, const void* x, void* y, size_t n, void* s) { return blas1(QMG_BOP_CAXY, ar, ai, 0, 0, x, nullptr, y, n, s); }
+int qmg_caxpy(double ar, double ai, const void* x, void* y, size_t n, void* s) { return blas1(QMG_BOP_CAXPY, ar, ai, 0, 0, x, nullptr, y, n, s); }
+int qmg_cxpy(const void* x, void* y, size_t n, void* s) { return blas1(QMG_BOP_CXPY, 0, 0, 0, 0, x, nullptr, y, n, s); }
+int qmg_cxpay(const void* x, double ar, double ai, void* y, size_t n, void* s) { return blas1(QMG_BOP_CXPAY, ar, ai, 0, 0, x, nullptr, y, n, s); }
+int qmg_caxpby(double ar, double ai, const void* x, double br, double bi, void* y, size_t n, void* s) {
+  return blas1(QMG_BOP_CAXPBY, ar, ai, br, bi, x, nullptr, y, n, s);
+}
+int qmg_cxpyz(const void* x, const void* y, void* z, size_t n, void* s) { return blas1(QMG_BOP_CXPYZ, 0, 0, 0, 0, x, y, z, n, s); }
+int qmg_caxpbyz(double ar, double ai, const void* x, double br, double bi, const void* y, void* z, size_t n, void* s) {
+  return blas1(QMG_BOP_CAXPBYZ, ar, ai, br, bi, x, y, z, n, s);
+}
+
+// out_dev: written by the final stage, nothing waits; out_host: makes the call synchronous (reduce_finish)
+static int reduce1(int op, int width, const void* x, const void* y, size_t n, double* od, double* oh, void* s) {
+  if (!x || (op != QMG_BRED_NORM2 && !y) || (!od && !oh)) return QMG_ERR_INVALID;
+  return reduce_run(QMG_C64, op, x, y, n, 1, 0, 1u, width, od, oh, s);
+}
+int qmg_norm2sq(const void* x, size_t n, double* od, double* oh, void* s) { return reduce1(QMG_BRED_NORM2, 1, x, nullptr, n, od, oh, s); }
+int qmg_dot(const void* x, const void* y, size_t n, double* od, double* oh, void* s) { return reduce1(QMG_BRED_DOT, 2, x, y, n, od, oh, s); }
+int qmg_diffnorm2sq(const void* x, const void* y, size_t n, double* od, double* oh, void* s) { return reduce1(QMG_BRED_DIFFNORM2, 1, x, y, n, od, oh, s); }
+
+// up to 64 vectors: BDOT_MAX per pass of the launcher (each dot is its own accumulation: the split changes no digit)
+int qmg_multidot(const void* const* xs, int k, const void* y, size_t n, double* out_dev, double* out_host, void* stream) {
+  if (!xs || !y || k < 1 || k > 2 * BDOT_MAX || (!out_dev && !out_host)) return QMG_ERR_INVALID;
+  for (int i = 0; i < k; i++) if (!xs[i]) return QMG_ERR_INVALID;
+  for (int k0 = 0; k0 < k; k0 += BDOT_MAX) {
+    const int rc = multidot_run(QMG_C64, xs + k0, k - k0 < BDOT_MAX ? k - k0 : BDOT_MAX, y, n, 1, 0, 1u, out_dev ? out_dev + 2 * k0 : nullptr,
+                                out_host ? out_host + 2 * k0 : nullptr, stream);
+    if (rc) return rc;
   }
   return QMG_SUCCESS;
 }

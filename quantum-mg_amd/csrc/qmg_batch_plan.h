@@ -15,7 +15,7 @@ enum BatchFamily {
   BF_BLAS = QMG_BF_BLAS,           // k_bblas<OP, T, W>
   BF_MAXPY_SMALL = QMG_BF_MAXPY_SMALL,    // k_bmulti_caxpy_small<T, W>
   BF_MAXPY_LONG = QMG_BF_MAXPY_LONG,     // k_bmulti_caxpy<T, W>: bmulti_caxpy_run<T, W, NJ, NT>
-  BF_MAXPY_SINGLE = QMG_BF_MAXPY_SINGLE,   // the single-vector qmg_multi_caxpy (qmg_blas.hip), on the vector sets whose coefficient is not zero
+  BF_MAXPY_SINGLE = QMG_BF_MAXPY_SINGLE,   // qmg_multi_caxpy (qmg_blas.hip: k_multi_caxpy, the one BLAS-1 kernel with no batch form), on the vector sets whose coefficient is not zero
   BF_GCR = QMG_BF_GCR,            // k_bgcr_update<T, W>
   BF_CGM = QMG_BF_CGM,            // k_bcgm_update<T, W>
   BF_REDUCE = QMG_BF_REDUCE,         // k_breduce<OP, T, W> + k_breduce_final
@@ -30,11 +30,10 @@ enum { BATCH_PLAN_INTS = 5 };
 // A vector of this many bytes and more per system is a LONG vector (an outer solve on the fine lattice).  There the multi-axpy keeps all loads of
 // a chunk of 8 vector sets in flight (k_bmulti_caxpy; same-box A/B, C5 shape: the outer flexible GCR's 4096^2 updates 4 % of the solve faster, the
 // coarse levels' few-microsecond launches 1 % slower with it, hence the threshold), the GCR update sends every chunk of its Gram-Schmidt sum
-// through the multi-axpy (2 % of the C5-shape solve), and ONE complex<double> system goes to the single-vector kernel, which takes up to 32
+// through the multi-axpy (2 % of the C5-shape solve), and ONE complex<double> system goes to k_multi_caxpy (qmg_blas.hip), which takes up to 32
 // vector sets per pass over y instead of 8 -- the same sums in the same order.
 constexpr size_t BATCH_LONG_BYTES = (size_t)16 << 20;
 
-constexpr int BDOT_MAX = 32;     // vectors per batched multidot call
 constexpr int BMAXPY_J = 8;      // vector sets per multi-axpy / GCR launch (the coefficients travel as kernel arguments)
 constexpr int CGM_J = 8;         // shifts per multi-shift CG launch (the coefficient tables travel as kernel arguments)
 constexpr int CGM_CHUNK = 4;     // shifts per staged chunk of k_bcgm_update
@@ -171,7 +170,7 @@ inline BatchPass batch_plan(const BatchPlanRequest& r, int at = 0) {
       return p;
     case QMG_BE_MULTIDOT: {
       if (!nact || r.nj <= at) return nothing(at);
-      const int left = r.nj - at;   // the 8 / 4 / 2 / 1 chunking of qmg_multidot
+      const int left = r.nj - at;   // chunks of 8 / 4 / 2 / 1 dots: y is re-read once per chunk (each dot is its own accumulation: the chunking changes no digit)
       p.family = BF_MULTIDOT;
       p.J = left >= 8 ? 8 : left >= 4 ? 4 : left >= 2 ? 2 : 1;
       if (at + p.J < r.nj) p.next = at + p.J;

@@ -139,6 +139,30 @@ __device__ __forceinline__ double wave_reduce_many(const double* v) {
   return w[0];
 }
 
+// First stage of the global reductions (qmg_batch.hip, qmg_blas.hip), at the end of a kernel of BLOCK threads: the block's NV sums (maxima)
+// go to partial_out[q] -- wavefronts by wave_reduce_many, then the block's wavefronts in index order.
+template <int NV, bool MAX = false>
+__device__ __forceinline__ void block_reduce_store(double* v, double* partial_out) {
+  __shared__ double sm[NV][BLOCK / WAVE];
+  const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
+  const double w = wave_reduce_many<NV, MAX>(v);   // lane q: wave_max(v[q]) / wave_sum(v[q]), bit for bit
+  if (lane < NV) sm[lane][wv] = w;
+  __syncthreads();
+  if (threadIdx.x < NV) {
+    double t = sm[threadIdx.x][0];
+#pragma unroll
+    for (int w = 1; w < BLOCK / WAVE; w++) t = MAX ? fmax(t, sm[threadIdx.x][w]) : t + sm[threadIdx.x][w];
+    partial_out[threadIdx.x] = t;
+  }
+}
+constexpr int RED_BLOCKS = 1024;    // partials per reduction per system (4 blocks per CU)
+inline unsigned red_grid(long n) {
+  long b = (n + BLOCK - 1) / BLOCK;
+  if (b > RED_BLOCKS) b = RED_BLOCKS;
+  if (b < 1) b = 1;
+  return (unsigned)b;
+}
+
 // Two-stage sum of N numbers per thread in a FIXED order, so that the result is deterministic.  First stage, at the end of a kernel of BLOCK
 // threads: the block's N sums go to partials[blockIdx.x * N + q]; `sm` is the kernel's own __shared__ array.
 template <int N>
@@ -317,10 +341,34 @@ inline Epilogue no_epilogue() { Epilogue e; e.other = nullptr; e.dotv = nullptr;
 double* mr_epilogue_begin(int nsys, long npart);
 int mr_epilogue_finish(const unsigned char* ids, int n, long npart, hipStream_t st);
 
+// qmg_batch.hip: the calling thread's reduction workspace.  Every reduction of the C ABI uses it -- the batch entry points, the single-vector
+// ones (the batch ones at nrhs = 1) and the two that have no batch form (qmg_blas.hip: the maximum norm, the per-timeslice sums).  Calls of one
+// host thread on different streams share it and must not overlap.
+constexpr int BDOT_MAX = 32;     // vectors per batched multidot call
+constexpr size_t WS_PARTIALS = (size_t)BATCH_MAX * RED_BLOCKS * 2 * BDOT_MAX;   // doubles
+constexpr size_t WS_RESULTS = (size_t)BATCH_MAX * 2 * BDOT_MAX;
+struct BatchWorkspace {
+  double* partials = nullptr;   // WS_PARTIALS doubles (8 MiB)
+  double* pinned = nullptr;     // host-pinned, device-visible results: WS_RESULTS doubles
+  double* result = nullptr;     // the same in HBM: where the results go when they are summed over ranks first
+  double* mr = nullptr;         // device-resident scalars of the MR smoother: [system][4] = Re<p,r>, Im<p,r>, <p,p>, - (qmg_batch_mr_*)
+  double* epi_part = nullptr;   // partials of an apply's MR epilogue ([system slot][wavefront][4]), grown on demand
+  size_t epi_cap = 0;
+  unsigned* done = nullptr;              // blocks of the current final stage that have stored their result (device)
+  unsigned long long* flag = nullptr;    // host-pinned, coherent: sequence number of the last final stage whose results are in `pinned`
+  unsigned long long seq = 0;
+  int device = -1;
+};
+int get_bws(BatchWorkspace** out);
+// where a final stage writes its results: the caller's device pointer if there is one, else the workspace's HBM slot when they are summed over
+// the ranks first (dist_reductions_on), else its pinned slot
+double* result_slot(BatchWorkspace* ws, double* out_dev);
+// `count` results at `res` (a result_slot) readable in ws->pinned when this returns; flagged: the final stage publishes ws->seq behind them
+int results_to_host(BatchWorkspace* ws, const double* res, int count, bool flagged, hipStream_t st);
+
 extern int g_reduce_spin;     // qmg_batch.hip; "reduce_spin"
 extern int g_malloc_poison;   // qmg_runtime.hip; "malloc_poison"
-// qmg_shutdown: the calling thread's reduction / norm workspaces (qmg_blas.hip, qmg_batch.hip, qmg_stencil.hip)
-void release_blas_workspace();
+// qmg_shutdown: the calling thread's reduction / norm workspaces (qmg_batch.hip, qmg_stencil.hip)
 void release_batch_workspace();
 void release_stencil_workspace();
 void release_deflate_workspace();   // qmg_deflate.hip

@@ -103,7 +103,6 @@ int qmg_shutdown(void) {
   int c = 0;
   if (hipGetDeviceCount(&c) != hipSuccess || c <= 0) return QMG_SUCCESS;   // nothing was ever initialised
   QMG_HIP_CHECK(hipDeviceSynchronize());
-  release_blas_workspace();
   release_batch_workspace();
   release_stencil_workspace();
   release_deflate_workspace();

@@ -3,7 +3,8 @@
 A batch is `nrhs` vectors of `n` elements at a common `stride`; every function here takes and returns the vectors of ONE system (the
 route tests of test_gpu_batch_routes.py cut the systems out of the batch themselves and hold everything outside the active systems to
 its initial bytes).  Inputs are complex128 arrays that already hold what the device holds: for complex<float> storage they have been
-rounded with r32 first.  Nothing here shares code with the kernels, the oracle or the single-vector BLAS.
+rounded with r32 first.  Nothing here shares code with the kernels or the oracle.  (The single-vector BLAS-1 and reductions of the C ABI are these
+same kernels at nrhs = 1.)
 
 Next to each elementwise result comes the term-magnitude sum S = |out0| + sum |c| |x| per element and the number of terms of the sum, the
 scale and length of the bound the kernels are held to (elementwise_bound: the form of transfer_numpy.elementwise_bound).
@@ -13,7 +14,7 @@ import numpy as np
 CLD = np.clongdouble
 LD = np.longdouble
 
-ZERO, COPY, CAX, CAXPY, CXPY, CAXPBYZ = range(6)      # qmg_batch_op
+ZERO, COPY, CAX, CAXPY, CXPY, CAXPBYZ, CAXY, CXPAY, CAXPBY, CXPYZ = range(10)      # qmg_batch_op
 NORM2, DOT, DIFFNORM2 = range(3)                      # qmg_batch_red
 
 
@@ -31,7 +32,7 @@ def _mag(v):
 
 
 def blas(op, a, b, x, y, z):
-    """(z', S, terms) of one qmg_batch_blas_t op: z' = 0 | x | a z | z + a x | z + x | a x + b y"""
+    """(z', S, terms) of one qmg_batch_blas_t op: z' = 0 | x | a z | z + a x | z + x | a x + b y | a x | x + a z | a x + b z | x + y"""
     a, b = CLD(a), CLD(b)
     if op == ZERO:
         return np.zeros(len(z), dtype=CLD), np.zeros(len(z), dtype=LD), 0
@@ -43,8 +44,16 @@ def blas(op, a, b, x, y, z):
         return _ld(z) + a * _ld(x), _mag(z) + abs(a) * _mag(x), 1
     if op == CXPY:
         return _ld(z) + _ld(x), _mag(z) + _mag(x), 1
-    assert op == CAXPBYZ
-    return a * _ld(x) + b * _ld(y), abs(a) * _mag(x) + abs(b) * _mag(y), 2
+    if op == CAXPBYZ:
+        return a * _ld(x) + b * _ld(y), abs(a) * _mag(x) + abs(b) * _mag(y), 2
+    if op == CAXY:
+        return a * _ld(x), abs(a) * _mag(x), 1
+    if op == CXPAY:
+        return _ld(x) + a * _ld(z), _mag(x) + abs(a) * _mag(z), 1
+    if op == CAXPBY:
+        return a * _ld(x) + b * _ld(z), abs(a) * _mag(x) + abs(b) * _mag(z), 2
+    assert op == CXPYZ
+    return _ld(x) + _ld(y), _mag(x) + _mag(y), 1
 
 
 PASS_SETS = 8    # vector sets per pass over y: the entry points take more in several passes, and y is STORED between them

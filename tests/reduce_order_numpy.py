@@ -1,4 +1,4 @@
-"""The summation order of the library's two-stage reductions (csrc/qmg_batch.hip, csrc/qmg_blas.hip), emulated in numpy, and inputs on which
+"""The summation order of the library's two-stage reductions (csrc/qmg_batch.hip: batches, and the single-vector entry points as a batch of one), emulated in numpy, and inputs on which
 numpy reproduces every device operation exactly, so that the emulation must match the device BIT FOR BIT.
 
 The documented order of one output value over n elements read W at a time (W = 2 for complex<float> at even n on aligned arrays, else 1):

@@ -36,7 +36,7 @@ MASKS = [(5, 0b11111), (5, 0b01101), (16, 0xFFFF), (16, 0x8421), (3, 0b010), (9,
 
 @pytest.mark.parametrize("nrhs,mask", MASKS)
 def test_batch_blas_bit_identical_and_masked(nrhs, mask):
-    """qmg_batch_blas bit for bit the single-vector kernels.  (The reference: test_gpu_batch_routes.py holds these kernels to a long-double reference, elementwise, one row per route of qmg_batch_plan.)"""
+    """qmg_batch_blas gives every active system the bits of the single-vector entry point -- the same kernel on a batch of one -- whatever batch, mask and stride it sits in, and leaves the systems that are masked out untouched.  (The reference: test_gpu_batch_routes.py holds these kernels to a long-double reference, elementwise, one row per route of qmg_batch_plan; test_gpu_blas_single.py holds the operation order bit for bit.)"""
     n, pad = 1000, 7
     stride = n + pad
     x = cs.gaussian_cvec(stride * nrhs, 1)
@@ -63,7 +63,7 @@ def test_batch_blas_bit_identical_and_masked(nrhs, mask):
 @pytest.mark.parametrize("nrhs,mask", MASKS)
 @pytest.mark.parametrize("n", [1, 777, 300001])
 def test_batch_reductions_bit_identical(nrhs, mask, n):
-    """qmg_batch_reduce bit for bit the single-vector reductions.  (The reference: test_gpu_batch_routes.py holds these kernels to a long-double reference, elementwise, one row per route of qmg_batch_plan.)"""
+    """qmg_batch_reduce gives every active system the bits of the single-vector reduction -- the same kernels on a batch of one -- whatever batch, mask and stride it sits in, and leaves the entries of masked-out systems untouched.  (The reference: test_gpu_batch_routes.py holds these kernels to a long-double reference, one row per route of qmg_batch_plan; test_gpu_reduce_order.py holds the summation order bit for bit.)"""
     stride = n + 3
     x = cs.gaussian_cvec(stride * nrhs, 11)
     y = cs.gaussian_cvec(stride * nrhs, 12)
@@ -84,7 +84,7 @@ def test_batch_reductions_bit_identical(nrhs, mask, n):
 
 @pytest.mark.parametrize("nj", [1, 2, 5, 11, 32])
 def test_batch_multidot_and_multi_caxpy(nj):
-    """qmg_batch_multidot / qmg_batch_multi_caxpy bit for bit their single-vector forms.  (The reference: test_gpu_batch_routes.py holds these kernels to a long-double reference, elementwise, one row per route of qmg_batch_plan.)"""
+    """qmg_batch_multidot gives every active system the bits of qmg_multidot -- the same kernels on a batch of one -- and qmg_batch_multi_caxpy those of qmg_multi_caxpy (k_multi_caxpy, a kernel of its own), and both leave masked-out systems untouched.  (The reference: test_gpu_batch_routes.py holds these kernels to a long-double reference, elementwise, one row per route of qmg_batch_plan.)"""
     nrhs, mask, n = 6, 0b101101, 4099
     stride = n + 5
     xs = [cs.gaussian_cvec(stride * nrhs, 20 + j) for j in range(nj)]

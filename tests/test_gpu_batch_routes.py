@@ -146,8 +146,8 @@ def flat(ns, nrhs, most):
 
 ROUTES = []
 
-# ======== qmg_batch_blas_t: the six ops on every shape, and past blas_nt_mb (CAXPBYZ there with y aliasing z -- then y is the in/out operand -- and distinct)
-for op in range(6):
+# ======== qmg_batch_blas_t: the ten ops on every shape, and past blas_nt_mb (CAXPBYZ there with y aliasing z -- then y is the in/out operand -- and distinct)
+for op in range(10):
     for sh in SHAPES:
         ROUTES.append(row("blas", sh, [BLAS(sh[5], 0, op)], op=op))
     for cls in CLASSES:

@@ -764,7 +764,7 @@ def test_transfer_at_4096_spot_checked():
 
 
 def test_blas_non_temporal_reads_change_no_bit():
-    """Vectors of `blas_nt_mb` MiB and more are streamed with non-temporal loads on their read-only operands (csrc/qmg_blas.hip): a cache hint,
+    """Vectors of `blas_nt_mb` MiB and more are streamed with non-temporal loads on their read-only operands (csrc/qmg_batch.hip, csrc/qmg_blas.hip): a cache hint,
     so every BLAS-1 result and every reduction must be the same bits with the threshold at 1 MiB (on for these 4.8 MB vectors) and at 0 (never)."""
     n = 300001
     x, y, z0 = cs.gaussian_cvec(n, 41), cs.gaussian_cvec(n, 42), cs.gaussian_cvec(n, 43)

@@ -8,9 +8,10 @@ reordered reduction cannot pass.  The cases are true of the butterfly-per-value 
 
 Shapes: n in {1, 63, 64, 65, 255, 256, 257, 1000, 262147} (below, at and above a wavefront and a block; a ragged last block; 1024 blocks
 with a second trip of the grid-stride loop); 1, 3 and 8 systems with masks with holes; nj in {1, 2, 3, 4, 7, 8, 9, 15, 32} (every chunking into
-kernels of 8 / 4 / 2 / 1 dots); complex<double>, and complex<float> read one and two elements per access.  Not the full product: every n
+kernels of 8 / 4 / 2 / 1 dots), and 33 and 64 for the single-vector multidot (more than one pass takes); complex<double>, and complex<float> read one and two elements per access.  Not the full product: every n
 meets every storage form and every nj, the batch shapes rotate, and n = 262147 goes with the widest shapes that stay small on the host.
 """
+import ctypes as C
 import importlib
 
 import numpy as np
@@ -133,9 +134,9 @@ def test_batch_reduce_bits(form, op):
         assert same_bits(got[act], want), (form, op, n, nrhs, hex(mask), W)
 
 
-@pytest.mark.parametrize("nj", NJS)
+@pytest.mark.parametrize("nj", NJS + (33, 64))      # (33, 64: more vectors than one pass of the multidot kernels takes)
 def test_multidot_bits(nj):
-    for n in SMALL_N + ((BIG_N,) if nj == 8 else ()):
+    for n in (1000,) if nj > 32 else SMALL_N + ((BIG_N,) if nj == 8 else ()):
         rng = np.random.default_rng(9000 + 100 * nj + n)
         xs, _ = ro.cvalues(rng, (nj, n), 25)
         y, _ = ro.cvalues(rng, (n,), 25)
@@ -163,3 +164,48 @@ def test_single_vector_reductions_bits():
         # a maximum has no order; |x|^2 is exact products and one rounding of their sum, the square root is held to one unit in the last place
         want = np.sqrt(np.max(x.real * x.real + x.imag * x.imag))
         assert abs(ninf - want) <= np.spacing(want), n
+
+
+def _through(call, width):
+    """the `width` doubles of one single-vector reduction three ways: out_host alone, out_dev alone (asynchronous: read after a
+    synchronise), and both at once"""
+    host, both = (C.c_double * width)(), (C.c_double * width)()
+    dev, dev2 = qmg.DeviceArray.from_host(np.full(width + 1, np.nan)), qmg.DeviceArray.from_host(np.full(width + 1, np.nan))
+    qmg.check(call(None, host))
+    qmg.check(call(C.cast(C.c_void_p(dev.ptr), C.POINTER(C.c_double)), None))
+    qmg.check(call(C.cast(C.c_void_p(dev2.ptr), C.POINTER(C.c_double)), both))
+    got = np.array(host[:]), dev.to_host(), np.array(both[:]), dev2.to_host()
+    free(dev, dev2)
+    return got
+
+
+@pytest.mark.parametrize("red", ("norm2sq", "dot", "diffnorm2sq", "norminf", "multidot"))
+def test_single_vector_reductions_through_out_dev(red):
+    """a result taken through the device pointer is the bytes of the one taken through the host pointer, and nothing is written behind it"""
+    L = qmg.lib()
+    for n in (257, 1000):
+        rng = np.random.default_rng(13000 + n)
+        nj = 33
+        xs, _ = ro.cvalues(rng, (nj, n), 25)
+        y, _ = ro.cvalues(rng, (n,), 25)
+        ro.make_cancelling(rng, xs, y, n)
+        dxs, dy = [qmg.DeviceArray.from_host(v) for v in xs], qmg.DeviceArray.from_host(y)
+        px, py, nn = C.c_void_p(dxs[0].ptr), C.c_void_p(dy.ptr), C.c_size_t(n)
+        ptrs = (C.c_void_p * nj)(*[d.ptr for d in dxs])
+        call, width = {
+            "norm2sq": (lambda od, oh: L.qmg_norm2sq(px, nn, od, oh, None), 1),
+            "dot": (lambda od, oh: L.qmg_dot(px, py, nn, od, oh, None), 2),
+            "diffnorm2sq": (lambda od, oh: L.qmg_diffnorm2sq(px, py, nn, od, oh, None), 1),
+            "norminf": (lambda od, oh: L.qmg_norminf(px, nn, od, oh, None), 1),
+            "multidot": (lambda od, oh: L.qmg_multidot(ptrs, nj, py, nn, od, oh, None), 2 * nj),
+        }[red]
+        host, dev, both, dev2 = _through(call, width)
+        free(*dxs, dy)
+        assert not np.any(np.isnan(host))
+        for d in (dev, dev2):
+            assert same_bits(d[:width], host) and np.isnan(d[width]), (red, n)
+        assert same_bits(both, host), (red, n)
+        if red == "dot":
+            assert same_bits(host.view(np.complex128), ro.complex_sum(*ro.dot_terms(xs[0], y), n)), n
+        if red == "multidot":
+            assert same_bits(host.view(np.complex128), ro.complex_sum(*ro.dot_terms(xs, y[None, :]), n)), n

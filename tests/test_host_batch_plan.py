@@ -49,7 +49,8 @@ def within(got, want, bound):
 def test_reference_elementwise_operations_match_plain_numpy(n, narrow):
     x, y, z, r, p = (vec(n, s, narrow) for s in range(1, 6))
     a, b = 0.3 - 0.2j, -0.7 + 0.05j
-    plain = {bn.ZERO: 0 * z, bn.COPY: x, bn.CAX: a * z, bn.CAXPY: z + a * x, bn.CXPY: z + x, bn.CAXPBYZ: a * x + b * y}
+    plain = {bn.ZERO: 0 * z, bn.COPY: x, bn.CAX: a * z, bn.CAXPY: z + a * x, bn.CXPY: z + x, bn.CAXPBYZ: a * x + b * y,
+             bn.CAXY: a * x, bn.CXPAY: x + a * z, bn.CAXPBY: a * x + b * z, bn.CXPYZ: x + y}
     for op, ref in plain.items():
         want, S, terms = bn.blas(op, a, b, x, y, z)
         assert within(ref, want, bn.elementwise_bound(terms, S)), op
@@ -138,7 +139,7 @@ def domain_n(st):
 def variants(entry, nrhs):
     """(op, nj, shift_masks, flags) of an entry point over the domain"""
     if entry == "blas":
-        return [(op, 0, None, 0) for op in range(6)]
+        return [(op, 0, None, 0) for op in range(10)]
     if entry == "reduce":
         return [(op, 0, None, 0) for op in range(3)]
     if entry == "maxpy":
@@ -193,7 +194,7 @@ def test_every_pass_in_the_domain_has_a_row():
                                 found.setdefault((st, p), (entry, n, pad, nrhs, mask, nj, sm, flags, al, mb))
     finally:
         qmg.set_tuning("blas_nt_mb", routes.NT_DEFAULT)
-    per_entry = {"blas": 6, "reduce": 3, "maxpy": 34, "gcr": 68, "multidot": 32, "cgm": 160, "mr_dots": 1, "mr_update": 4}
+    per_entry = {"blas": 10, "reduce": 3, "maxpy": 34, "gcr": 68, "multidot": 32, "cgm": 160, "mr_dots": 1, "mr_update": 4}
     assert asked == 3 * 2 * 2 * sum(per_entry.values()) * 8 * 2 * sum(k + 1 for k in NRHS)          # no case skipped
     assert not unlisted, unlisted[:5]
     assert not listed_but_launched, listed_but_launched[:5]
@@ -232,7 +233,7 @@ def test_plan_query_rejects_what_the_entry_points_reject():
                                                                                                   1, out, max_passes)
     assert ask(8, 0, 0, 8, 1, 1, 0, None, 0) == invalid                       # entry
     assert ask(qmg.BE_BLAS, 2, 0, 8, 1, 1, 0, None, 0) == invalid             # dtype
-    assert ask(qmg.BE_BLAS, 0, 6, 8, 1, 1, 0, None, 0) == invalid             # op
+    assert ask(qmg.BE_BLAS, 0, 10, 8, 1, 1, 0, None, 0) == invalid            # op
     assert ask(qmg.BE_REDUCE, 0, 3, 8, 1, 1, 0, None, 0) == invalid
     assert ask(qmg.BE_BLAS, 0, 0, 8, 17, 1, 0, None, 0) == invalid            # more than 16 systems
     assert ask(qmg.BE_MULTIDOT, 0, 0, 8, 1, 1, 33, None, 0) == invalid        # more than 32 dots
