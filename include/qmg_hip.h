@@ -201,6 +201,18 @@ int qmg_hmc_momentum_update_poles(double* pi, const void* gauge, const void* con
  * pure-gauge kick of qmg_hmc_momentum_update (W, weights may be null). */
 int qmg_hmc_momentum_update_staggered(double* pi, const void* gauge, const void* const* W, const double* weights, int n_poles, int Lx, int Ly, double beta, double dt,
                                       unsigned flags, void* stream);
+/* pi -= dt (dS_g/dtheta + sum_j weights[j] sum_s Ff(X[j](.; s), Y[j](.; s))) in one pass: the kick of two-flavour domain-wall pseudofermions
+ * (include/qmg/hmc_dwf.hpp), Ff the bilinear of the two-flavour Wilson force on the two spin components of slice s.  X, Y: HOST arrays of n_pairs
+ * DEVICE complex<double>[2 Ls Lx Ly] full-lattice vectors (nc = 2 Ls, c = 2 s + sigma, even-odd layout); weights: HOST double[n_pairs], any sign.
+ * QMG_HMC_DWF_G5_Y reads every Y[j] as Gamma5 Y[j] (slice Ls-1-s, the sign of sigma 1 flipped).  2 <= Ls <= 32; 4 pairs per launch, further
+ * pairs in further launches.  n_pairs = 0 or QMG_HMC_GAUGE_ONLY: the pure-gauge kick of qmg_hmc_momentum_update, its bits (X, Y, weights may be
+ * null).  No atomics: the sums over s and j run in a fixed order. */
+enum { QMG_HMC_DWF_G5_Y = 2u };
+int qmg_hmc_momentum_update_dwf(double* pi, const void* gauge, const void* const* X, const void* const* Y, const double* weights, int n_pairs, int Ls, int Lx, int Ly,
+                                double beta, double dt, unsigned flags, void* stream);
+/* What qmg_hmc_momentum_update_dwf launches (host only): plan_out = (family, lanes per site, block, gx, gy, LDS bytes, launches, pairs per
+ * launch).  family: 0 unsupported, 1 the fused kernel, 2 the pure-gauge kick, 3 invalid. */
+int qmg_hmc_dwf_plan(int Lx, int Ly, int Ls, int n_pairs, unsigned flags, int* plan_out, int plan_len);
 /* theta += dt pi ; gauge = exp(i theta) in one pass over n = 2 Lx Ly links */
 int qmg_hmc_link_update(double* theta, void* gauge, const double* pi, size_t n, double dt, void* stream);
 /* pi ~ N(0, 1) per link from the counter-based generator, a function of (seed, trajectory) alone; n even */

@@ -53,6 +53,7 @@ ABI_SYMBOLS = [
     "qmg_u1_heatbath_noncompact", "qmg_u1_phase_to_gauge", "qmg_u1_gauge_to_phase", "qmg_u1_plaquette", "qmg_u1_noncompact_action",
     "qmg_u1_hot_gauge", "qmg_u1_gauss_gauge", "qmg_u1_random_trans", "qmg_u1_gauge_transform", "qmg_u1_ape_smear", "qmg_u1_instanton", "qmg_u1_noncompact_instanton",
     "qmg_hmc_momentum_update", "qmg_hmc_momentum_update_poles", "qmg_hmc_momentum_update_staggered", "qmg_hmc_link_update", "qmg_hmc_momentum_refresh", "qmg_hmc_stream_seed",
+    "qmg_hmc_momentum_update_dwf", "qmg_hmc_dwf_plan",
     "qmg_u1_flow_stage", "qmg_u1_flow", "qmg_u1_wilson_loops", "qmg_u1_polyakov",
     "qmg_dwf_fill", "qmg_dwf_apply_direct", "qmg_dwf_plan", "qmg_batch_plan", "qmg_wilson_plan",
     "qmg_dwf_inv5", "qmg_dwf_hops_inv5", "qmg_dwf_schur_apply", "qmg_dwf_eo_plan",
@@ -998,6 +999,39 @@ def hmc_momentum_update_staggered(pi, gauge, W, weights, Lx, Ly, beta, dt, flags
     ws = (C.c_double * max(len(weights), 1))(*[float(w) for w in weights]) if weights is not None else None
     check(lib().qmg_hmc_momentum_update_staggered(_vp(pi), _vp(gauge), ws_, ws, n, Lx, Ly, C.c_double(beta), C.c_double(dt), C.c_uint(flags), C.c_void_p(stream)),
           "qmg_hmc_momentum_update_staggered")
+
+
+HMC_DWF_G5_Y = 2   # flag of hmc_momentum_update_dwf: every Y[j] is read as Gamma5 Y[j]
+# the families of qmg_hmc_dwf_plan (include/qmg_hip.h)
+HDF_UNSUPPORTED, HDF_FUSED, HDF_GAUGE, HDF_INVALID = range(4)
+HMC_DWF_PLAN_INTS = 8
+
+
+def hmc_momentum_update_dwf_status(pi, gauge, X, Y, weights, Ls, Lx, Ly, beta, dt, flags=0, stream=None, n_pairs=None):
+    """qmg_hmc_momentum_update_dwf's status, unchecked."""
+    n = n_pairs if n_pairs is not None else (len(weights) if weights is not None else 0)
+    xs = (C.c_void_p * max(len(X), 1))(*[_vp(x).value for x in X]) if X is not None else None
+    ys = (C.c_void_p * max(len(Y), 1))(*[_vp(y).value for y in Y]) if Y is not None else None
+    ws = (C.c_double * max(len(weights), 1))(*[float(w) for w in weights]) if weights is not None else None
+    return lib().qmg_hmc_momentum_update_dwf(_vp(pi), _vp(gauge), xs, ys, ws, n, Ls, Lx, Ly, C.c_double(beta), C.c_double(dt), C.c_uint(flags), C.c_void_p(stream))
+
+
+def hmc_momentum_update_dwf(*args, **kw):
+    """pi -= dt (gauge force + sum_j weights[j] sum_s Ff(X[j](.; s), Y[j](.; s))) in one pass; X, Y: sequences of device nc = 2 Ls vectors"""
+    check(hmc_momentum_update_dwf_status(*args, **kw), "qmg_hmc_momentum_update_dwf")
+
+
+def hmc_dwf_plan_status(dims, Ls, n_pairs, flags=0):
+    """(status, plan) of qmg_hmc_dwf_plan (host only): plan = (family, lps, block, gx, gy, lds, launches, pairs per launch)."""
+    out = (C.c_int * HMC_DWF_PLAN_INTS)()
+    rc = lib().qmg_hmc_dwf_plan(dims[0], dims[1], Ls, n_pairs, C.c_uint(flags), out, HMC_DWF_PLAN_INTS)
+    return rc, tuple(out)
+
+
+def hmc_dwf_plan(dims, Ls, n_pairs, flags=0):
+    rc, plan = hmc_dwf_plan_status(dims, Ls, n_pairs, flags)
+    check(rc, "qmg_hmc_dwf_plan")
+    return plan
 
 
 def hmc_link_update(theta, gauge, pi, n, dt, stream=None):

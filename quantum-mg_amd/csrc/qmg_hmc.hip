@@ -11,6 +11,8 @@
 //
 // Layouts (lattice.h:75-81): site (x, y) has index (y + p Ly) Lx/2 + x/2, p = (x + y) & 1; phases, momenta and links are [mu][site],
 // spinors [site][2].
+#include "qmg_hmc_dwf_plan.h"
+#include "qmg_lane.h"   // uni, gld
 #include "qmg_u1_pair.h"
 
 namespace qmg {
@@ -216,6 +218,117 @@ __global__ __launch_bounds__(BLOCK) void k_hmc_momentum_update_staggered(double*
   }
 }
 
+// ---- domain-wall fermions (include/qmg/hmc_dwf.hpp; the independent statement is tests/dwf_hmc_numpy.py) ----
+// The force of S_f = phi^dag P (M^dag M)^-1 P^dag phi is the Wilson bilinear Ff above summed over the Ls slices of pairs of FIVE-dimensional
+// full-lattice vectors (the hops of the domain-wall operator are diagonal in s and are the Wilson hops on every slice):
+//   pi -= dt (Fg + sum_j w_j sum_s Ff(X_j(.; s), Y_j(.; s)))
+// The vectors are nc = 2 Ls in the even-odd layout, c = 2 s + sigma: the chunk (sigma 0, sigma 1) of (site, s) is 32 bytes at (site Ls + s) 32.
+// G5Y reads Y_j as Gamma5 Y_j: the chunk of slice Ls-1-s with the sign of sigma 1 flipped.
+//
+// Lane mapping: kernels D and K's -- one lane per (site, s), rows (parity, y) over grid.y, block-uniform row bases, so every chunk load of a
+// wave is one contiguous run.  A site owns its two forward links: a lane loads X and Y at its site, at x + xhat (the other parity's row y) and
+// at x + yhat (the other parity's row y + 1) -- six chunks per pair, in front of that pair's arithmetic -- and forms its slice's share of the two
+// forces, pair by pair in the order given.  The shares go into LDS; after one barrier lane s = 0 adds the Ls shares of the x link in the order
+// s = 0 .. Ls-1, lane s = 1 those of the y link, each adds the gauge force of its link (from the ten links around the site, loaded in front of the
+// pair loop) and updates its momentum.  The order is fixed and there is no atomic: two runs give the same bits.  The block is
+// Ls floor(256 / Ls) lanes, so a site never straddles a block whatever Ls is; lanes past the end of a half row stay for the barrier, load what
+// lane (0, s) loads and store nothing.  Two LDS buffers alternate, so one barrier per row suffices: 2 x 256 x 16 B = 8 KiB per block.
+// GAUGE = false (the launches after the first when there are more than HMC_DWF_PAIRS pairs) loads the two own links alone.
+// Byte model: 64 + 64 Ls n B/site -- pi read and written (32), two links (32), per pair X_j and Y_j (2 x 32 Ls); the neighbours from cache.
+struct HmcDwfPairs {
+  const char* X[HMC_DWF_PAIRS];
+  const char* Y[HMC_DWF_PAIRS];
+  double w[HMC_DWF_PAIRS];
+};
+
+template <bool GAUGE>
+__global__ __launch_bounds__(HMC_DWF_BLOCK_MAX) void k_hmc_momentum_update_dwf(double* __restrict__ pi, const cplx* __restrict__ gauge, const HmcDwfPairs pr, int n_pairs,
+                                                                               int g5y, int hr, int Ly, int Ls, double beta, double dt) {
+  typedef double v4 __attribute__((ext_vector_type(4)));   // a lane's chunk: (sigma 0 re, im, sigma 1 re, im)
+  constexpr unsigned CH = 32u;
+  __shared__ double2 share[2][HMC_DWF_BLOCK_MAX];
+  const int tid = threadIdx.x;
+  const int t = blockIdx.x * blockDim.x + tid;
+  const bool live = t < hr * Ls;          // a site is live or not as a whole: the block and the half row are multiples of Ls lanes
+  const int jt = t / Ls, s = t - jt * Ls;
+  const int j = live ? jt : 0;
+  const int base = tid - s;               // the site's shares in LDS: base .. base + Ls - 1, all in this block
+  const int sy = g5y ? Ls - 1 - s : s;
+  const double g5 = g5y ? -1.0 : 1.0;
+  const long half_vol = (long)hr * Ly, V = 2 * half_vol;
+  const long row_bytes = (long)hr * Ls * CH;
+  const cplx* __restrict__ Ux = gauge;
+  const cplx* __restrict__ Uy = gauge + V;
+  const bool writer = live && s < 2;      // s = 0: the x link, s = 1: the y link
+  int buf = 0;
+  for (int row = blockIdx.y; row < 2 * Ly; row += gridDim.y) {
+    const int p = row & 1, y = row >> 1;
+    const int sx = (y + p) & 1;
+    int jp = j + sx;     if (jp == hr) jp = 0;
+    int jm = j + sx - 1; if (jm < 0) jm = hr - 1;
+    const int yp = (y + 1 == Ly) ? 0 : y + 1;
+    const int ym = (y == 0) ? Ly - 1 : y - 1;
+    const long r_own = (long)p * Ly + y, r_x = (long)(1 - p) * Ly + y, r_yp = (long)(1 - p) * Ly + yp;
+    const long site = r_own * hr + j;
+    const cplx ux = Ux[site], uy = Uy[site];
+    double p_old = 0.0, dg = 0.0;
+    double* dst = pi + (s == 1 ? V : 0) + site;
+    if (writer) {
+      p_old = *dst;
+      if (GAUGE) {
+        // sin P(x) and, for the x link, sin P(x - yhat); for the y link, sin P(x - xhat)
+        const long s_xp = r_x * hr + jp, s_yp = r_yp * hr + j;
+        const double sP = im_plaq(ux, Uy[s_xp], Ux[s_yp], uy);
+        if (s == 0) {
+          const long s_ym = ((long)(1 - p) * Ly + ym) * hr + j, s_ymxp = ((long)p * Ly + ym) * hr + jp;
+          dg = im_plaq(Ux[s_ym], Uy[s_ymxp], ux, Uy[s_ym]);
+          dg = sP - dg;
+        } else {
+          const long s_xm = r_x * hr + jm, s_xmyp = ((long)p * Ly + yp) * hr + jm;
+          dg = im_plaq(Ux[s_xm], uy, Ux[s_xmyp], Uy[s_xm]);
+          dg = dg - sP;
+        }
+        asm volatile("" : "+v"(dg));   // keep the links out of the pair loop, as in k_hmc_momentum_update_poles
+      }
+    }
+    const unsigned ox_own = (unsigned)(j * Ls + s) * CH, oy_own = (unsigned)(j * Ls + sy) * CH;
+    const unsigned ox_xp = (unsigned)(jp * Ls + s) * CH, oy_xp = (unsigned)(jp * Ls + sy) * CH;
+    // The pair sum starts from -0.0, the one number that fma(w, f, .) leaves every w f at, signed zeros included.
+    double fx = -0.0, fy = -0.0;
+    for (int k = 0; k < n_pairs; k++) {
+      const char* X = pr.X[k];
+      const char* Y = pr.Y[k];
+      const double w = pr.w[k];
+      const gchar* xo = uni(X + r_own * row_bytes);
+      const gchar* xx = uni(X + r_x * row_bytes);
+      const gchar* xy = uni(X + r_yp * row_bytes);
+      const gchar* yo = uni(Y + r_own * row_bytes);
+      const gchar* yx = uni(Y + r_x * row_bytes);
+      const gchar* yy = uni(Y + r_yp * row_bytes);
+      const v4 xa = gld<v4>(xo, ox_own), xb = gld<v4>(xx, ox_xp), xc = gld<v4>(xy, ox_own);
+      v4 ya = gld<v4>(yo, oy_own), yb = gld<v4>(yx, oy_xp), yc = gld<v4>(yy, oy_own);
+      __builtin_amdgcn_sched_barrier(0);
+      ya.z *= g5; ya.w *= g5; yb.z *= g5; yb.w *= g5; yc.z *= g5; yc.w *= g5;
+      const cplx xa0 = cmake(xa.x, xa.y), xa1 = cmake(xa.z, xa.w), xb0 = cmake(xb.x, xb.y), xb1 = cmake(xb.z, xb.w), xc0 = cmake(xc.x, xc.y), xc1 = cmake(xc.z, xc.w);
+      const cplx ya0 = cmake(ya.x, ya.y), ya1 = cmake(ya.z, ya.w), yb0 = cmake(yb.x, yb.y), yb1 = cmake(yb.z, yb.w), yc0 = cmake(yc.x, yc.y), yc1 = cmake(yc.z, yc.w);
+      fx = fma(w, link_force(ux, ydag_hx(ya0, ya1, xb0, xb1, 1.0), ydag_hx(yb0, yb1, xa0, xa1, -1.0)), fx);
+      fy = fma(w, link_force(uy, ydag_hy(ya0, ya1, xc0, xc1, 1.0), ydag_hy(yc0, yc1, xa0, xa1, -1.0)), fy);
+    }
+    share[buf][tid] = make_double2(fx, fy);
+    __syncthreads();
+    if (writer) {
+      double f = -0.0;
+      for (int k = 0; k < Ls; k++) {
+        const double2 v = share[buf][base + k];
+        f += s == 0 ? v.x : v.y;
+      }
+      if (GAUGE) f = fma(beta, dg, f);
+      *dst = fma(-dt, f, p_old);
+    }
+    buf ^= 1;
+  }
+}
+
 // theta += dt pi ; U = exp(i theta), one pass over the 2 V links.  One fma: the phases are within one rounding of a host `theta + dt * pi`.
 __global__ __launch_bounds__(BLOCK) void k_hmc_link_update(double* __restrict__ theta, cplx* __restrict__ gauge, const double* __restrict__ pi, long n, double dt) {
   for (long i = (long)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (long)gridDim.x * BLOCK) {
@@ -310,6 +423,47 @@ int qmg_hmc_momentum_update_staggered(double* pi, const void* gauge, const void*
     if (first) k_hmc_momentum_update_staggered<true><<<g, BLOCK, 0, as_stream(stream)>>>(pi, (const cplx*)gauge, p, nj, Lx, Ly, beta, dt);
     else k_hmc_momentum_update_staggered<false><<<g, BLOCK, 0, as_stream(stream)>>>(pi, (const cplx*)gauge, p, nj, Lx, Ly, beta, dt);
   });
+}
+
+// pi -= dt (Fg + sum_j weights[j] sum_s Ff(X[j](.; s), Y[j](.; s))) in one pass over the momenta and links: the kick of domain-wall pseudofermions.
+// X, Y: HOST arrays of n_pairs DEVICE complex<double>[2 Ls Lx Ly] vectors (nc = 2 Ls, c = 2 s + sigma, even-odd layout), 16-byte aligned;
+// weights: HOST double[n_pairs], any sign.  flags & QMG_HMC_DWF_G5_Y reads every Y[j] as Gamma5 Y[j].  Up to HMC_DWF_PAIRS pairs go in one
+// launch; further pairs take further launches without the gauge force.  n_pairs = 0 or flags & QMG_HMC_GAUGE_ONLY is the pure-gauge kick of
+// qmg_hmc_momentum_update (X, Y, weights are not read and may be null).  pi must not overlap the other fields.
+int qmg_hmc_momentum_update_dwf(double* pi, const void* gauge, const void* const* X, const void* const* Y, const double* weights, int n_pairs, int Ls, int Lx, int Ly,
+                                double beta, double dt, unsigned flags, void* stream) {
+  const HmcDwfPlan pl = hmc_dwf_plan(Lx, Ly, Ls, n_pairs, flags);
+  if (pl.family == HDF_INVALID || pl.family == HDF_UNSUPPORTED) return pl.status;
+  if (!pi || !gauge || beta != beta || dt != dt) return QMG_ERR_INVALID;
+  if (pl.family == HDF_GAUGE) return qmg_hmc_momentum_update(pi, gauge, nullptr, nullptr, Lx, Ly, beta, dt, QMG_HMC_GAUGE_ONLY, stream);
+  if (!pole_lists_valid(X, Y, weights, n_pairs)) return QMG_ERR_INVALID;
+  for (int j = 0; j < n_pairs; j++)
+    if (!aligned16(X[j]) || !aligned16(Y[j])) return QMG_ERR_INVALID;
+  const dim3 grid((unsigned)pl.gx, (unsigned)pl.gy);
+  const int g5y = (flags & QMG_HMC_DWF_G5_Y) ? 1 : 0;
+  for (int j0 = 0; j0 < n_pairs; j0 += HMC_DWF_PAIRS) {
+    const int nj = n_pairs - j0 < HMC_DWF_PAIRS ? n_pairs - j0 : HMC_DWF_PAIRS;
+    HmcDwfPairs p;
+    for (int j = 0; j < HMC_DWF_PAIRS; j++) {
+      p.X[j] = j < nj ? (const char*)X[j0 + j] : nullptr;
+      p.Y[j] = j < nj ? (const char*)Y[j0 + j] : nullptr;
+      p.w[j] = j < nj ? weights[j0 + j] : 0.0;
+    }
+    if (j0 == 0) k_hmc_momentum_update_dwf<true><<<grid, (unsigned)pl.block, 0, as_stream(stream)>>>(pi, (const cplx*)gauge, p, nj, g5y, Lx / 2, Ly, Ls, beta, dt);
+    else k_hmc_momentum_update_dwf<false><<<grid, (unsigned)pl.block, 0, as_stream(stream)>>>(pi, (const cplx*)gauge, p, nj, g5y, Lx / 2, Ly, Ls, beta, dt);
+    QMG_LAUNCH_CHECK();
+  }
+  return QMG_SUCCESS;
+}
+
+// What qmg_hmc_momentum_update_dwf launches for a request (host only): plan_out = (family, lanes per site, block, gx, gy, LDS bytes, launches,
+// pairs per launch); entries past the eighth are -1.
+int qmg_hmc_dwf_plan(int Lx, int Ly, int Ls, int n_pairs, unsigned flags, int* plan_out, int plan_len) {
+  if (!plan_out || plan_len < HMC_DWF_PLAN_INTS) return QMG_ERR_INVALID;
+  const HmcDwfPlan pl = hmc_dwf_plan(Lx, Ly, Ls, n_pairs, flags);
+  const int v[HMC_DWF_PLAN_INTS] = {pl.family, pl.lps, pl.block, pl.gx, pl.gy, pl.lds, pl.launches, pl.per_launch};
+  for (int i = 0; i < plan_len; i++) plan_out[i] = i < HMC_DWF_PLAN_INTS ? v[i] : -1;
+  return QMG_SUCCESS;
 }
 
 // theta += dt pi ; gauge = exp(i theta).  theta, pi: DEVICE double[n]; gauge: DEVICE complex<double>[n]; n = 2 Lx Ly links.

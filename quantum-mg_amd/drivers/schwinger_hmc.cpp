@@ -33,62 +33,15 @@
 
 #include "../include/qmg/qmg.hpp"
 #include "driver_common.hpp"
+#include "hmc_run_common.hpp"
 
 using namespace std;
 
-// SchwingerHMC proves with range_check that the spectrum is inside the caller's interval; the staggered interval [m^2, m^2 + 4] is exact
+// SchwingerHMC proves with range_check that the spectrum is inside the caller's interval; the staggered interval [m^2, m^2 + 4] is exact and takes no check
 static bool range_check_line(SchwingerHMC& hmc) {
   const RhmcRangeCheck c = hmc.range_check();
   cout << "[RHMC-CHECK] ratio " << c.ratio << " bound " << c.bound << " ok " << (c.ok ? 1 : 0) << "\n";
   return c.ok;
-}
-static bool range_check_line(StaggeredSchwingerHMC&) { return true; }
-
-// the trajectories, the final lines and the written configuration; returns the exit status
-template <class HMC> static int run(HMC& hmc, Lattice2D& lat_gauge, bool one_flavour, bool check_range, double rhmc_sites, int n_traj, int n_therm, const string& out_cfg) {
-  const size_t n_links = (size_t)lat_gauge.get_size_gauge();
-  int unconverged = 0, accepted = 0, range_failures = 0;
-  vector<double> w, plaq;
-  cout << setprecision(10);
-  auto rhmc_check = [&]() {
-    if (!range_check_line(hmc)) range_failures++;
-  };
-  if (one_flavour) {
-    const qmg::ZolotarevInvSqrt& z = hmc.rational();
-    cout << "[RHMC] n " << z.n << " ra " << z.ra << " rb " << z.rb << " delta " << z.delta << " det_bound " << expm1(rhmc_sites * log1p(z.delta)) << "\n";
-  }
-  for (int i = 0; i < n_therm + n_traj; i++) {
-    if (check_range && i == n_therm && n_therm > 0) rhmc_check();
-    const HmcResult r = hmc.trajectory();
-    cout << "[HMC] " << i << " dH " << r.dH << " acc " << (r.accepted ? 1 : 0) << " plaq " << r.plaquette << " Q " << r.topo << " cg " << r.cg_iterations << "\n";
-    if (!r.cg_converged) unconverged++;
-    if (i >= n_therm) { accepted += r.accepted ? 1 : 0; w.push_back(exp(-r.dH)); plaq.push_back(r.plaquette); }
-  }
-  // jackknife over single trajectories (for a plain mean: the standard error)
-  auto mean_err = [](const vector<double>& v, double& m, double& e) {
-    const size_t n = v.size();
-    m = 0.0; e = 0.0;
-    if (!n) return;
-    for (double x : v) m += x;
-    m /= (double)n;
-    if (n < 2) return;
-    double s = 0.0;
-    for (double x : v) { const double jk = (m * (double)n - x) / (double)(n - 1); s += (jk - m) * (jk - m); }
-    e = sqrt(s * (double)(n - 1) / (double)n);
-  };
-  double wm, we, pm, pe;
-  mean_err(w, wm, we);
-  mean_err(plaq, pm, pe);
-  cout << "[HMC-FINAL] trajectories " << n_traj << " acceptance " << (n_traj ? (double)accepted / n_traj : 0.0) << " exp_mdH " << wm << " +/- " << we << " plaq " << pm << " +/- " << pe
-       << " unconverged " << unconverged << "\n";
-  if (check_range) rhmc_check();
-  if (!out_cfg.empty()) {   // written, and read back the way the other drivers will read it
-    write_gauge_u1(hmc.links(), &lat_gauge, out_cfg);
-    complex<double>* check = allocate_vector<complex<double>>(n_links);
-    if (read_gauge_u1(check, &lat_gauge, out_cfg)) cout << "[HMC-READBACK] plaq " << std::real(get_plaquette_u1(check, &lat_gauge)) << " Q " << get_topo_u1(check, &lat_gauge) << "\n";
-    deallocate_vector(&check);
-  }
-  return unconverged == 0 && range_failures == 0 ? 0 : 1;
 }
 
 int main(int argc, char** argv) {
@@ -126,11 +79,11 @@ int main(int argc, char** argv) {
   if (staggered) {
     StaggeredSchwingerHMC hmc(phases, L, L, beta, mass, n_flavours, tau, n_steps, cg_eps, cg_max_iter, generator, rhmc_degree);
     if (!hmc.ok()) return qmg_driver::leave(3);
-    rc = run(hmc, lat_gauge, n_flavours == 1, false, 0.5 * L * L, n_traj, n_therm, out_cfg);
+    rc = hmc_run::run<StaggeredSchwingerHMC>(hmc, lat_gauge, n_flavours == 1, nullptr, 0.5 * L * L, n_traj, n_therm, out_cfg);
   } else {
     SchwingerHMC hmc(phases, L, L, beta, mass, n_flavours, tau, n_steps, cg_eps, cg_max_iter, generator, rhmc_degree, rhmc_lo, rhmc_hi);
     if (!hmc.ok()) return qmg_driver::leave(3);
-    rc = run(hmc, lat_gauge, n_flavours == 1, n_flavours == 1, 2.0 * L * L, n_traj, n_therm, out_cfg);
+    rc = hmc_run::run<SchwingerHMC>(hmc, lat_gauge, n_flavours == 1, n_flavours == 1 ? range_check_line : nullptr, 2.0 * L * L, n_traj, n_therm, out_cfg);
   }
   deallocate_vector(&phases);
   qmg::VecPool::release_all();

@@ -1,6 +1,7 @@
 // hmc_core.hpp -- the molecular dynamics that every HMC of the Schwinger model here shares: compact U(1) in two dimensions, leapfrog, Metropolis,
 // everything on the device (csrc/qmg_hmc.hip).  HmcCore knows the gauge field and nothing of fermions; SchwingerHMC (hmc.hpp, Wilson) and
-// StaggeredSchwingerHMC (hmc_staggered.hpp) derive from it and supply the pseudofermion action through five hooks.
+// StaggeredSchwingerHMC (hmc_staggered.hpp) and DomainWallSchwingerHMC (hmc_dwf.hpp) derive from it and supply the pseudofermion action through
+// five hooks.
 //
 //   H = 1/2 sum pi^2 + S_g + S_f,   S_g = beta sum_x (1 - cos P(x)),   S_f: the derived class's
 //

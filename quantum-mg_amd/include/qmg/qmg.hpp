@@ -16,5 +16,6 @@
 #include "reductions.hpp"
 #include "hmc.hpp"
 #include "hmc_staggered.hpp"
+#include "hmc_dwf.hpp"
 #include "dwf_measure.hpp"
 #endif
