@@ -95,6 +95,9 @@ const char* qmg_last_hip_error(void);
 const char* qmg_version(void);
 int qmg_malloc(void** dev_ptr, size_t bytes);   /* replaces allocate_vector<T> for device arrays */
 int qmg_free(void* dev_ptr);
+/* With the tuning key "malloc_poison" on: `bytes` bytes at dev_ptr are set to 0xFF on `stream` (asynchronous).  With the key off: nothing,
+ * no launch.  For a facade's pools: a recycled scratch block leaves the pool looking like a fresh qmg_malloc. */
+int qmg_poison_scratch(void* dev_ptr, size_t bytes, void* stream);
 int qmg_shutdown(void);                         /* ordered teardown for the calling host thread: device sync, then the library's per-thread workspaces are released */
 int qmg_mem_info(size_t* free_bytes, size_t* total_bytes);   /* HBM free / total on the current device: batch sizing */
 int qmg_memcpy_h2d(void* dst_dev, const void* src_host, size_t bytes, void* stream);  /* synchronous when stream == NULL */
@@ -132,7 +135,13 @@ int qmg_stencil_apply_norm2(const qmg_stencil_desc* d, void* lhs, const void* rh
                             double* norms_dev, double* norms_host, void* stream);
 /* Same, for a lock-step batch of at most 16 systems of which only those with their bit set in `mask` are read or
  * written.  With nc in {8,12,16,24,32} and two or more active systems the apply runs as an (nc x nc).(nc x k)
- * contraction on the f64 matrix cores (v_mfma_f64_16x16x4_f64), the matrices read once for all k. */
+ * contraction on the f64 matrix cores (v_mfma_f64_16x16x4_f64), the matrices read once for all k.
+ * Read set of every apply of this family, the Wilson and domain-wall applies from the links included (tests/test_gpu_isolation.py runs each
+ * route with everything else set to NaN): of rhs, the parity some selected piece takes as a source -- a clover or shift bit of parity p reads
+ * rhs_p, a hop bit of parity p reads rhs_{1-p}, a bit whose field is NULL selects nothing; of lhs, the halves a piece accumulates into -- a
+ * half that QMG_P_ZERO_E / QMG_P_ZERO_O clears is written without being read, a half no piece names is neither read nor written.  Never
+ * read: the elements between the systems (vec_stride beyond the vector's length), the halo rows of a parity no hop takes as a source, and
+ * any operand's segment of a system outside `mask` (entries without a mask serve every system). */
 int qmg_stencil_apply_batch(const qmg_stencil_desc* d, void* lhs, const void* rhs, unsigned pieces,
                             int nrhs, size_t vec_stride, unsigned mask, void* stream);
 
@@ -424,7 +433,9 @@ int qmg_batch_multidot_t(int dtype, const void* const* xs, int nj, const void* y
  * other / dotv: vectors with lhs's layout, precision and stride (element `system * vec_stride` onwards is used, like lhs and rhs).  Needs
  * overwrite semantics (QMG_P_ZERO on the processed parities); lhs must differ from rhs, other and dotv.  mat32: the matrices are complex<float>
  * (qmg_stencil_apply_mat32's storage) with dtype's vectors.  QMG_ERR_UNSUPPORTED: this operator is not served with an epilogue (nc = 1, 2, 4:
- * see qmg_wilson_apply_direct_epi) -- run the separate passes. */
+ * see qmg_wilson_apply_direct_epi) -- run the separate passes.
+ * Read set: system `system` alone, in all four vectors -- rhs by the parity rule of qmg_stencil_apply_batch, other and dotv on the processed
+ * parities only, lhs nowhere (it is overwritten); no other system, no element between the systems.  A refused call reads and writes nothing. */
 typedef struct { const void* other; double other_scale, acc_scale; const void* dotv; } qmg_apply_epilogue;
 int qmg_stencil_apply_epi_t(int dtype, int mat32, const qmg_stencil_desc* d, void* lhs, const void* rhs, unsigned pieces, size_t vec_stride, int system,
                             const qmg_apply_epilogue* epi, void* stream);
@@ -778,7 +789,13 @@ int qmg_dwf_meas_plan(int dtype, int Lx, int Ly, int Ls, int kernel, int nsys, i
  *   "setup_fused"   1: block-local setup kernels (block orthonormalisation in LDS, Galerkin build as per-block products);
  *                   0: the full-lattice restrict / prolong / probe passes of the reference's formulation (1)
  *   "malloc_poison" 1: qmg_malloc fills every allocation with 0xFF bytes (NaNs in every storage precision): a buffer read before
- *                   it is written then shows deterministically (0)
+ *                   it is written then shows deterministically.  The same holds for qmg_poison_scratch, through which the facade's
+ *                   pools (VecPool, ArrayStorageMG) poison every block they hand out, recycled ones included, and for these buffers of
+ *                   the library where they are created or grown: the reduction partials (batch reductions, the apply's fused norms, the
+ *                   plaquette sums), the epilogue partials, both buffers of the deflation workspace, and the per-thread scratch fields
+ *                   of the smearing, flow and dwf_meas entries.  Not filled: the result and MR slots of the reduction workspace (created
+ *                   as zeros, which the MR slot's contract is) and the temporaries of the pass-by-pass setup fallbacks
+ *                   (csrc/qmg_transfer.hip), which are zeroed or fully written before every use (0)
  *   "reduce_spin"   1: the host picks the results of the batch reductions (qmg_batch_reduce*, qmg_batch_multidot*) up by polling a sequence
  *                   number the final stage's last block publishes in coherent host memory behind them; the stream is NOT synchronised by
  *                   these calls then (later launches are ordered behind the kernel anyway).  0: hipStreamSynchronize, as before (1) */

@@ -446,6 +446,7 @@ int get_bws(BatchWorkspace** out) {
   QMG_HIP_CHECK(hipGetDevice(&dev));
   if (g_bws.device != dev) {
     QMG_HIP_CHECK(hipMalloc((void**)&g_bws.partials, sizeof(double) * WS_PARTIALS));
+    if (const int rc = poison_new_scratch(g_bws.partials, sizeof(double) * WS_PARTIALS)) return rc;
     QMG_HIP_CHECK(hipHostMalloc((void**)&g_bws.pinned, sizeof(double) * WS_RESULTS, hipHostMallocCoherent));
     QMG_HIP_CHECK(hipHostMalloc((void**)&g_bws.flag, 64, hipHostMallocCoherent));
     *g_bws.flag = 0;
@@ -514,6 +515,7 @@ double* mr_epilogue_begin(int nsys, long npart) {
     if (ws->epi_part) { if (hipFree(ws->epi_part) != hipSuccess) return nullptr; }   // (synchronises: nothing still writes the old buffer)
     ws->epi_part = nullptr; ws->epi_cap = 0;
     if (hipMalloc((void**)&ws->epi_part, sizeof(double) * need) != hipSuccess) return nullptr;
+    if (poison_new_scratch(ws->epi_part, sizeof(double) * need) != QMG_SUCCESS) return nullptr;
     ws->epi_cap = need;
   }
   return ws->epi_part;

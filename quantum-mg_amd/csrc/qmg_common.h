@@ -383,6 +383,16 @@ extern int g_pair_prefetch;    // qmg_stencil.hip; "pair_prefetch"
 extern int g_stencil_mfma;     // qmg_stencil_mfma.hip; "stencil_mfma"
 extern long g_blas_nt_bytes;   // qmg_blas.hip; "blas_nt_mb"
 
+// "malloc_poison": the library's own scratch is filled with 0xFF where it is created or grown, behind the allocation that has just
+// synchronised the device.  The key off: one host branch, no launch.
+inline int poison_new_scratch(void* p, size_t bytes) {
+  if (g_malloc_poison) {
+    QMG_HIP_CHECK(hipMemset(p, 0xFF, bytes));
+    QMG_HIP_CHECK(hipDeviceSynchronize());
+  }
+  return QMG_SUCCESS;
+}
+
 // A device scratch buffer of the calling thread (declare it thread_local), grown on demand -- the only synchronous step of its users, and only
 // when it grows -- and held until qmg_shutdown.  Calls of one host thread on different streams share it and must not overlap.
 struct ThreadScratch {
@@ -396,6 +406,7 @@ struct ThreadScratch {
       if (buf && device == dev) QMG_HIP_CHECK(hipFree(buf));   // waits for the device: nothing still reads it
       *this = ThreadScratch();
       QMG_HIP_CHECK(hipMalloc(&buf, need));
+      if (const int rc = poison_new_scratch(buf, need)) return rc;
       bytes = need;
       device = dev;
     }

@@ -159,6 +159,7 @@ static int get_dws(DeflateWorkspace** out, size_t partials_need) {
   QMG_HIP_CHECK(hipGetDevice(&dev));
   if (g_dws.device != dev) {
     QMG_HIP_CHECK(hipMalloc((void**)&g_dws.coef, sizeof(double) * BASIS_PAIRS * 2));
+    if (const int rc = poison_new_scratch(g_dws.coef, sizeof(double) * BASIS_PAIRS * 2)) return rc;
     QMG_HIP_CHECK(hipHostMalloc((void**)&g_dws.pinned, sizeof(double) * BASIS_PAIRS * 2, hipHostMallocCoherent));
     g_dws.device = dev;
   }
@@ -166,6 +167,7 @@ static int get_dws(DeflateWorkspace** out, size_t partials_need) {
     if (g_dws.partials) QMG_HIP_CHECK(hipFree(g_dws.partials));   // (synchronises: nothing still reads the old buffer)
     g_dws.partials = nullptr; g_dws.partials_cap = 0;
     QMG_HIP_CHECK(hipMalloc((void**)&g_dws.partials, sizeof(double) * partials_need));
+    if (const int rc = poison_new_scratch(g_dws.partials, sizeof(double) * partials_need)) return rc;
     g_dws.partials_cap = partials_need;
   }
   *out = &g_dws;

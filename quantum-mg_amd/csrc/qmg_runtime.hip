@@ -86,7 +86,15 @@ int qmg_malloc(void** p, size_t bytes) {
   QMG_HIP_CHECK(hipMalloc(p, bytes));
   // "malloc_poison": every byte 0xFF -- a complex<double> / complex<float> / complex<half> array then reads as NaNs, so a
   // vector that is read before it is written shows up deterministically (in residuals, not as box-dependent behaviour)
-  if (g_malloc_poison) QMG_HIP_CHECK(hipMemset(*p, 0xFF, bytes));
+  // The fill runs on the null stream, which is not ordered against the non-blocking streams of qmg_stream_create (the emulated ranks'
+  // streams): the device is synchronised behind it, so that no later write on such a stream can land under the fill.
+  if (g_malloc_poison) return poison_new_scratch(*p, bytes);
+  return QMG_SUCCESS;
+}
+
+int qmg_poison_scratch(void* p, size_t bytes, void* stream) {
+  if (!g_malloc_poison || !p || bytes == 0) return QMG_SUCCESS;
+  QMG_HIP_CHECK(hipMemsetAsync(p, 0xFF, bytes, (hipStream_t)stream));
   return QMG_SUCCESS;
 }
 

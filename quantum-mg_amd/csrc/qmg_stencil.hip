@@ -421,6 +421,7 @@ int launch_stencil_norm(StencilArgs& a, const StencilPlan& pl, double* norms_dev
     if (ws.device != dev && ws.done) { (void)hipEventDestroy(ws.done); ws.done = nullptr; }   // (an event belongs to the device it was created on)
     ws.used = false;
     QMG_HIP_CHECK(hipMalloc((void**)&ws.part, sizeof(double) * (size_t)nparts * a.nrhs));
+    if (const int rc = poison_new_scratch(ws.part, sizeof(double) * (size_t)nparts * a.nrhs)) return rc;
     ws.cap = (size_t)nparts * a.nrhs; ws.device = dev;
   }
   a.norm_part = ws.part;

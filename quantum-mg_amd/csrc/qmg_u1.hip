@@ -225,6 +225,7 @@ static int plaquette_sums(const void* gauge, const double* phase, int Lx, int Ly
   if (nb > 1024) nb = 1024;
   double* buf = nullptr;
   QMG_HIP_CHECK(hipMalloc((void**)&buf, sizeof(double) * (3 * nb + 3)));
+  if (const int rc = poison_new_scratch(buf, sizeof(double) * (3 * nb + 3))) { hipFree(buf); return rc; }
   if (mode == 0) k_plaquette<0><<<(unsigned)nb, BLOCK, 0, st>>>((const cplx*)gauge, nullptr, Lx, Ly, buf);
   else k_plaquette<1><<<(unsigned)nb, BLOCK, 0, st>>>(nullptr, phase, Lx, Ly, buf);
   k_sum_partials<3><<<1, 64, 0, st>>>(buf, (int)nb, 1.0, buf + 3 * nb);

@@ -90,6 +90,9 @@ struct VecPool {
     complex<double>* p = 0;
     for (auto it = sh.free_by_cap.lower_bound(n); it != sh.free_by_cap.end() && it->first <= 2 * n; ++it)
       if (!it->second.empty()) { p = it->second.back(); it->second.pop_back(); sh.cached_elems -= it->first; break; }
+    // "malloc_poison": a recycled block leaves the pool as a fresh one does, 0xFF in every byte, on the stream its user launches on (the key off:
+    // one branch inside the call, no launch) -- the previous solve's plausible numbers would hide a vector that is read before it is written
+    if (p) ok(qmg_poison_scratch(p, n * sizeof(complex<double>), current_stream()), "qmg_poison_scratch");
     if (!p) {
       // nothing cached serves the request.  If the HBM that is left cannot either, the cached blocks of OTHER capacities are given back first (a
       // batch of 3 systems after single-system solves found 36 GB of single-system scratch on the free list that no request of its own could

@@ -35,7 +35,12 @@ class ArrayStorageMG {
   ~ArrayStorageMG() { for (int i = 0; i < allocated_arrays; i++) deallocate_vector(&arrays[i]); }
   T* check_out() {
     for (int i = 0; i < allocated_arrays; i++)
-      if (!is_checked_out[i]) { is_checked_out[i] = true; n_checked++; return arrays[i]; }
+      if (!is_checked_out[i]) {
+        is_checked_out[i] = true; n_checked++;
+        // "malloc_poison": a vector that leaves the pool again holds 0xFF like a fresh one, not what its last user left (the key off: no launch)
+        qmg::ok(qmg_poison_scratch(arrays[i], (size_t)array_length * sizeof(T), qmg::current_stream()), "qmg_poison_scratch");
+        return arrays[i];
+      }
     arrays.push_back(allocate_vector<T>(array_length));
     is_checked_out.push_back(true);
     n_checked++;
