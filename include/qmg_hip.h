@@ -773,6 +773,48 @@ int qmg_dwf_slice_norms(int dtype, int Lx, int Ly, int Ls, const void* psi5, int
  * QMG_ERR_INVALID: plan_out missing or plan_len below 8. */
 int qmg_dwf_meas_plan(int dtype, int Lx, int Ly, int Ls, int kernel, int nsys, int* plan_out, int plan_len);
 
+/* ---------------- flavour-singlet loops from diluted Z4 noise on lock-step batches (csrc/qmg_singlet.hip) ----------------
+ * Element i = site * nc + c of a vector, site = (y + p Ly) Lx/2 + j (p the parity half).  The noise is a function of (seed, i) and is never
+ * stored:  eta_i = i^(h >> 62),  h = splitmix64(seed * 0xD1342543DE82EF95 + 2 i) -- the first hash qmg_gaussian takes for element i -- that is
+ * 1, i, -1, -i, of modulus one.  Dilution (nt, spin, eo): nt >= 1 divides Ly, spin and eo are 0 or 1, ncs = spin ? nc : 1, neo = eo ? 2 : 1; the
+ * class of an element is d(i) = ((y mod nt) ncs + (spin ? c : 0)) neo + (eo ? p : 0), D = nt ncs neo classes with disjoint supports.  System k
+ * of a batch (nrhs <= 16 vectors `stride` complex elements apart, bit k of mask: active) carries class first_class + k.  g(i), the sign of
+ * gamma5: g5_mode 0 (Wilson) +1 for c < nc/2 and -1 otherwise, even nc only; g5_mode 1 (staggered epsilon) -1 on the odd half.
+ * QMG_ERR_INVALID before any launch: an invalid lattice, nc < 1, nt that does not divide Ly, spin or eo outside {0, 1}, first_class < 0 or
+ * first_class + nrhs > D, nrhs outside 1 .. 16, dtype outside QMG_C64 / QMG_C32, a missing or misaligned (16 bytes) vector, nrhs > 1 with
+ * stride below Lx Ly nc; for the loops also g5_mode outside {0, 1}, odd nc with g5_mode 0, and both outputs NULL.  No active system: success,
+ * nothing launched.
+ * eta_i for all n elements (complex<double>). */
+int qmg_noise_z4(void* eta, size_t n, unsigned long long seed, void* stream);
+/* out_k = the diluted source of class first_class + k for the active systems, ONE launch: every element of an active system is written (the
+ * noise value or zero); a frozen system and the padding between Lx Ly nc and stride are neither read nor written. */
+int qmg_noise_dilute_batch(int dtype, void* out, int Lx, int Ly, int nc, int nt, int spin, int eo, int first_class, unsigned long long seed, int nrhs,
+                           size_t stride, unsigned mask, void* stream);
+/* For the active systems, in ONE pass over psi (16 nc B/site per system in fp64, 8 nc in fp32; the noise is regenerated inside the support and
+ * never read), with d = first_class + k and every sum accumulated in fp64:
+ *   S_k(y) = sum_{i in row y, d(i) = d} conj(eta_i) psi_k(i),   P_k(y) = the same sum of conj(eta_i) g(i) psi_k(i),   N_k(y) = sum_{i in row y} |psi_k(i)|^2
+ *   out[(k Ly + y) 5 + {0..4}] = Re S, Im S, Re P, Im P, N      (N over the WHOLE row; S = P = 0 on a row outside the class)
+ * Entries of frozen systems are not written; frozen systems and padding are not read.  No atomics, a fixed summation order: a system's five
+ * numbers are the same bits on every run, in every batch and under every mask.  out_dev (device) and / or out_host (host; the stream is then
+ * synchronised) as in qmg_norm2sq_cv_timeslice.  Without out_dev the results pass through a device buffer of the calling thread that grows on
+ * demand and is held until qmg_shutdown. */
+int qmg_loops_timeslice_batch(int dtype, const void* psi, int Lx, int Ly, int nc, int nt, int spin, int eo, int first_class, unsigned long long seed,
+                              int g5_mode, int nrhs, size_t stride, unsigned mask, double* out_dev, double* out_host, void* stream);
+/* What the two entries launch: the answer of the one host function they switch on.  Host only, no HIP call.  Writes 12 ints and -1 into the rest
+ * of out, and returns the status the entries return for these arguments:
+ *   family   0 invalid, 1 k_loops_timeslice / k_noise_dilute, 2 no active system (success, nothing launched)
+ *   block    threads per block of both kernels: 256, whatever the row length (a row of Lx = 2 keeps 2 nc lanes of a block busy)
+ *   gx, gy   the loops grid: gx = the active systems, gy = min(Ly, 65535) blocks over the timeslices
+ *   walk     timeslices walked per block, ceil(Ly / gy): block b takes y = b, b + gy, ...; 1 unless Ly > 65535
+ *   lds      bytes of LDS per block of the loops kernel
+ *   doubles  doubles the loops entry writes: 5 Ly per active system
+ *   dgx, dgy the dilution grid: dgx blocks of 256 lanes over the Lx Ly nc elements (at most 262144), dgy = the active systems
+ *   dwalk    elements walked per lane of the dilution kernel
+ *   nk       the active systems
+ *   classes  D
+ * QMG_ERR_INVALID also where out is missing or n_out below 12. */
+int qmg_singlet_plan(int Lx, int Ly, int nc, int nt, int spin, int eo, int first_class, int nrhs, unsigned mask, int* out, int n_out);
+
 /* ---------------- tuning hooks (not part of the reference surface) ---------------- */
 /* Dispatch / codegen knobs, all with the defaults the measurements in profiles/ chose; results never depend on them
  * beyond summation order.  Unknown keys, and values a key does not take, return QMG_ERR_INVALID.

@@ -59,6 +59,7 @@ ABI_SYMBOLS = [
     "qmg_dwf_inv5", "qmg_dwf_hops_inv5", "qmg_dwf_schur_apply", "qmg_dwf_eo_plan",
     "qmg_dwf_wall_source", "qmg_dwf_wall_project", "qmg_dwf_slice_norms", "qmg_dwf_meas_plan",
     "qmg_setup_plan",
+    "qmg_noise_z4", "qmg_noise_dilute_batch", "qmg_loops_timeslice_batch", "qmg_singlet_plan",
 ]
 
 
@@ -908,6 +909,56 @@ def dwf_meas_plan(dtype, dims, Ls, kernel, nsys=1):
     out = (C.c_int * DWF_MEAS_PLAN_INTS)()
     check(lib().qmg_dwf_meas_plan(dtype, dims[0], dims[1], Ls, kernel, nsys, out, DWF_MEAS_PLAN_INTS), "qmg_dwf_meas_plan")
     return tuple(out)
+
+
+# ---- flavour-singlet loops from diluted Z4 noise (csrc/qmg_singlet.hip)
+# the families of qmg_singlet_plan (include/qmg_hip.h); `dil` below is the dilution (nt, spin, eo)
+SGF_INVALID, SGF_ROWS, SGF_NONE = range(3)
+SINGLET_PLAN_INTS = 12
+
+
+def noise_z4(eta, n, seed, stream=None):
+    check(lib().qmg_noise_z4(_vp(eta), C.c_size_t(n), C.c_ulonglong(seed), C.c_void_p(stream)), "qmg_noise_z4")
+
+
+def noise_dilute_batch_status(dtype, out, dims, nc, dil, first_class, seed, nrhs=1, stride=0, mask=None, stream=None):
+    """qmg_noise_dilute_batch's status, unchecked: system k of the batch becomes the diluted source of class first_class + k."""
+    mask = (1 << min(max(nrhs, 0), 32)) - 1 if mask is None else mask
+    return lib().qmg_noise_dilute_batch(dtype, _vp(out), dims[0], dims[1], nc, dil[0], dil[1], dil[2], first_class, C.c_ulonglong(seed), nrhs,
+                                        C.c_size_t(stride), C.c_uint(mask), C.c_void_p(stream))
+
+
+def noise_dilute_batch(*args, **kw):
+    check(noise_dilute_batch_status(*args, **kw), "qmg_noise_dilute_batch")
+
+
+def loops_timeslice_batch_status(dtype, psi, dims, nc, dil, first_class, seed, g5_mode, nrhs=1, stride=0, mask=None, out_dev=None, out_host=None, stream=None):
+    """qmg_loops_timeslice_batch's status, unchecked; out_host: a float64 array of nrhs * Ly * 5 numbers or None."""
+    mask = (1 << min(max(nrhs, 0), 32)) - 1 if mask is None else mask
+    host = None if out_host is None else out_host.ctypes.data_as(C.POINTER(C.c_double))
+    return lib().qmg_loops_timeslice_batch(dtype, _vp(psi), dims[0], dims[1], nc, dil[0], dil[1], dil[2], first_class, C.c_ulonglong(seed), g5_mode, nrhs,
+                                           C.c_size_t(stride), C.c_uint(mask), C.cast(_vp(out_dev), C.POINTER(C.c_double)), host, C.c_void_p(stream))
+
+
+def loops_timeslice_batch(dtype, psi, dims, nc, dil, first_class, seed, g5_mode, nrhs=1, stride=0, mask=None, out_dev=None, fill=0.0, stream=None):
+    """out[k, y] = (Re S, Im S, Re P, Im P, N) of system k on the host (and in out_dev where given); entries of frozen systems keep `fill`."""
+    out = np.full((nrhs, dims[1], 5), fill, dtype=np.float64)
+    check(loops_timeslice_batch_status(dtype, psi, dims, nc, dil, first_class, seed, g5_mode, nrhs, stride, mask, out_dev, out, stream), "qmg_loops_timeslice_batch")
+    return out
+
+
+def singlet_plan_status(dims, nc, dil, first_class=0, nrhs=1, mask=None):
+    """(status, (family, block, gx, gy, walk, lds, doubles, dgx, dgy, dwalk, nk, classes)) of qmg_singlet_plan; host only."""
+    mask = (1 << min(max(nrhs, 0), 32)) - 1 if mask is None else mask
+    out = (C.c_int * SINGLET_PLAN_INTS)()
+    rc = lib().qmg_singlet_plan(dims[0], dims[1], nc, dil[0], dil[1], dil[2], first_class, nrhs, C.c_uint(mask), out, SINGLET_PLAN_INTS)
+    return rc, tuple(out)
+
+
+def singlet_plan(*args, **kw):
+    rc, plan = singlet_plan_status(*args, **kw)
+    check(rc, "qmg_singlet_plan")
+    return plan
 
 
 def comm_set_distributed_reductions(on):

@@ -375,6 +375,7 @@ void release_deflate_workspace();   // qmg_deflate.hip
 void release_u1_workspace();        // qmg_u1.hip
 void release_flow_workspace();      // qmg_flow.hip
 void release_dwf_meas_workspace();  // qmg_dwf_meas.hip
+void release_singlet_workspace();   // qmg_singlet.hip
 extern int g_setup_fused; // qmg_setup.hip; "setup_fused"
 extern int g_wilson_pair;      // qmg_wilson.hip; "wilson_pair"
 extern int g_stencil_site;     // qmg_stencil_apply.hip; "stencil_site"

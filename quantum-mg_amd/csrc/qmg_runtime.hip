@@ -117,6 +117,7 @@ int qmg_shutdown(void) {
   release_u1_workspace();
   release_flow_workspace();
   release_dwf_meas_workspace();
+  release_singlet_workspace();
   QMG_HIP_CHECK(hipDeviceSynchronize());
   return QMG_SUCCESS;
 }

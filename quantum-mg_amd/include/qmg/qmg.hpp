@@ -18,4 +18,5 @@
 #include "hmc_staggered.hpp"
 #include "hmc_dwf.hpp"
 #include "dwf_measure.hpp"
+#include "singlet.hpp"
 #endif
