@@ -153,6 +153,7 @@ int minres(MG& mg, int l, int type, cvec& x, const cvec& b, int max_iter, double
   const long n = mg.lv[l].solve_size(type);
   cvec r(mg.lv[l].size), p(mg.lv[l].size);
   const double bnorm = std::sqrt(norm2(b, n));
+  if (bnorm == 0.0) { std::fill(x.begin(), x.begin() + n, cplx(0.0)); return 0; }   // A x = 0: x = 0 whatever the guess
   apply(mg, l, type, p, x);
   for (long i = 0; i < n; i++) r[i] = b[i] - p[i];
   double rsq = norm2(r, n);
@@ -181,6 +182,7 @@ int gcr(MG& mg, int l, int type, cvec& x, const cvec& b, int max_iter, double ep
   std::vector<cvec> Z, W;
   std::vector<double> Wn;
   const double bnorm = std::sqrt(norm2(b, n));
+  if (bnorm == 0.0) { std::fill(x.begin(), x.begin() + n, cplx(0.0)); if (rsq_out) *rsq_out = 0.0; return 0; }   // A x = 0: x = 0 whatever the guess
   apply(mg, l, type, tmp, x);
   for (long i = 0; i < n; i++) r[i] = b[i] - tmp[i];
   double rsq = norm2(r, n);
@@ -232,6 +234,7 @@ int cg_restart(MG& mg, int l, int type, cplx shift, cvec& x, const cvec& b, int 
   const double bnorm = std::sqrt(norm2(b, n));
   int k = 0;
   bool conv = false;
+  if (bnorm == 0.0) { std::fill(x.begin(), x.begin() + n, cplx(0.0)); return 0; }   // A x = 0: x = 0 whatever the guess
   while (k < max_iter) {
     const int chunk = (restart > 0) ? std::min(restart, max_iter - k) : max_iter - k;
     apply(mg, l, type, Ap, x, shift);
@@ -459,6 +462,12 @@ int qo_krylov_solve(int kind, const qo_stencil_desc* d, const qo_stencil_desc* d
   int k = 0;
   double rsq = 0.0;
   bool conv = false;
+  if (bnorm == 0.0) {   // A x = 0: the solution is x = 0 whatever the initial guess was (no iteration, no apply, resSq 0)
+    std::memset(x_, 0, sizeof(cplx) * n);
+    if (iters) *iters = 0;
+    if (res_sq) *res_sq = 0.0;
+    return 1;
+  }
   auto note = [&](double r2) { if (hist && k - 1 < nhist && k >= 1) hist[k - 1] = std::sqrt(r2) / bnorm; };
   if (kind == 0) {   // CG
     cvec r(n), p(n), Ap(n);

@@ -306,6 +306,17 @@ inline std::vector<double> bresidual(BatchT<T> r, BatchT<T> x, BatchT<T> b, Batc
   return bnorm2sq(r, size, mask);
 }
 
+// The systems of `mask` whose right-hand side is identically zero.  A x = 0 has the solution x = 0 whatever the initial guess was, so every
+// core sets x_k = 0 for them (one bzero), reports success at iteration 0 with resSq 0, and keeps them out of every apply, the opening
+// residual included (ops_count 0).  (Before, such a system was reported converged with its initial guess left in x.)
+template <typename T>
+inline unsigned zero_rhs_systems(BatchT<T> phi, const std::vector<double>& bsq, size_t n, unsigned mask) {
+  unsigned zb = 0;
+  for (int k = 0; k < phi.nrhs; k++) if (is_active(mask, k) && bsq[k] == 0.0) zb |= 1u << k;
+  if (zb) bzero(phi, n, zb);
+  return zb;
+}
+
 // a single-vector operator / preconditioner (the reference's callback types) as the operator of a batch of one system
 struct MatrixOp1 { matrix_op_cplx f; void* data; };
 struct PrecondOp1 { precond_op_cplx f; void* data; };
@@ -333,8 +344,9 @@ inline std::vector<inversion_info> bmr_core(qmg::BatchT<T> phi, qmg::BatchT<T> p
   const std::vector<double> bsq = qmg::bnorm2sq(phi0, size, mask);
   std::vector<int> its(nrhs, 0), ops(nrhs, 0);
   std::vector<double> rsq = bsq;
-  if (zero_guess) qmg::bcopy(r, phi0, size, mask);
-  else rsq = qmg::bresidual(r, phi, phi0, p, size, matrix_vector, extra_info, mask, ops);
+  const unsigned run = mask & ~qmg::zero_rhs_systems(phi, bsq, size, mask);   // (a zero right-hand side: x = 0, done)
+  if (zero_guess) qmg::bcopy(r, phi0, size, run);
+  else rsq = qmg::bresidual(r, phi, phi0, p, size, matrix_vector, extra_info, run, ops);
   std::vector<double> rsq_ref = rsq, bnorm(nrhs);
   std::vector<bool> conv(nrhs, false);
   unsigned act = 0;
@@ -409,10 +421,11 @@ inline std::vector<inversion_info> bbicgstab_l_core(qmg::BatchT<T> phi, qmg::Bat
   const std::vector<double> bsq = qmg::bnorm2sq(phi0, size, mask);
   std::vector<int> its(nrhs, 0), ops(nrhs, 0);
   std::vector<double> rsq = bsq, bnorm(nrhs, 0.0);
-  if (zero_guess) qmg::bcopy(r[0], phi0, size, mask);
-  else rsq = qmg::bresidual(r[0], phi, phi0, u[0], size, matrix_vector, extra_info, mask, ops);
-  qmg::bcopy(rt, r[0], size, mask);
-  qmg::bzero(u[0], size, mask);
+  const unsigned run = mask & ~qmg::zero_rhs_systems(phi, bsq, size, mask);   // (a zero right-hand side: x = 0, done)
+  if (zero_guess) qmg::bcopy(r[0], phi0, size, run);
+  else rsq = qmg::bresidual(r[0], phi, phi0, u[0], size, matrix_vector, extra_info, run, ops);
+  qmg::bcopy(rt, r[0], size, run);
+  qmg::bzero(u[0], size, run);
   std::vector<bool> conv(nrhs, false);
   qmg::cvec rho0(nrhs, 1.0), alpha(nrhs, 0.0), omega(nrhs, 1.0);
   unsigned act = 0;
@@ -572,8 +585,9 @@ inline std::vector<inversion_info> bgcr_core(qmg::BatchT<T> phi, qmg::BatchT<T> 
   std::vector<double> rsq(nrhs, 0.0), rsq_ref(nrhs, 0.0), bnorm(nrhs, 0.0);
   std::vector<int> its(nrhs, 0), ops(nrhs, 0);
   std::vector<bool> conv(nrhs, false);
-  if (zero_guess) { qmg::bcopy(r, phi0, size, mask); rsq = bsq; }
-  else rsq = qmg::bresidual(r, phi, phi0, tmp, size, matrix_vector, extra_info, mask, ops);
+  const unsigned run = mask & ~qmg::zero_rhs_systems(phi, bsq, size, mask);   // (a zero right-hand side: x = 0, done)
+  if (zero_guess) { qmg::bcopy(r, phi0, size, run); rsq = bsq; }
+  else rsq = qmg::bresidual(r, phi, phi0, tmp, size, matrix_vector, extra_info, run, ops);
   unsigned act = 0;
   for (int k = 0; k < nrhs; k++) {
     bnorm[k] = std::sqrt(bsq[k]);
@@ -715,8 +729,10 @@ inline std::vector<inversion_info> bcg_core(qmg::BatchT<T> phi, qmg::BatchT<T> p
   for (int k = 0; k < nrhs; k++) bnorm[k] = std::sqrt(bsq[k]);
   const qmg::cvec one(nrhs, 1.0);
   std::vector<qmg::BatchT<T> > pv(1);
-  unsigned live = (r.p && p.p && Ap.p) ? mask : 0u;   // systems that may still start a cycle
-  if (!live && mask) std::cout << "[QMG-ERROR]: " << name << ": out of device memory for the CG work vectors\n";
+  const unsigned zero_b = qmg::zero_rhs_systems(phi, bsq, size, mask);   // (a zero right-hand side: x = 0, done)
+  for (int k = 0; k < nrhs; k++) if (qmg::is_active(zero_b, k)) conv[k] = true;
+  unsigned live = (r.p && p.p && Ap.p) ? (mask & ~zero_b) : 0u;   // systems that may still start a cycle
+  if (!live && (mask & ~zero_b)) std::cout << "[QMG-ERROR]: " << name << ": out of device memory for the CG work vectors\n";
   bool first = true;
   while (live) {
     // ---- one cycle: at most `chunk` iterations per system
@@ -994,6 +1010,12 @@ inline inversion_info minv_vector_richardson(complex<double>* phi, complex<doubl
   int ops = 0, k = 0;
   double rsq = 0.0;
   bool conv = false;
+  if (bnorm == 0.0) {   // A x = 0: x = 0 whatever the guess was, as in the batch cores (qmg::zero_rhs_systems)
+    zero_vector(phi, size);
+    invif.success = true;
+    qmg::summary(verb, "Richardson", 1, 0, true, 0, 0.0);
+    return invif;
+  }
   while (k < max_iter) {
     matrix_vector(Ax, phi, extra_info); ops++;
     caxpbyz(1.0, phi0, -1.0, Ax, r, size);

@@ -130,3 +130,49 @@ def test_cg_on_the_normal_operator(systems):
     bn = ol.stencil_apply(dd, b)   # M^dag b
     conv, it, x, rsq, _ = ol.krylov_solve(ol.KRYLOV_CG, d, bn, 3000, 1e-10, dagger_desc=dd, normal=True)
     assert conv and cs.rel_l2(ol.stencil_apply(d, x), b) < 1e-8
+
+
+# ---- the twins against the EQUATION, on the dense numpy matrices of tests/krylov_batch_numpy.py (quantum-linalg is absent: where its
+# convention is unknown, A x = b decides).  The GPU cores are held to the same two bars in tests/test_gpu_krylov_batch.py.
+EQUATION_KINDS = [  # id, oracle kind, operator of krylov_batch_numpy, param_i, param_d, max_iter
+    ("cg", ol.KRYLOV_CG, "laplace34x10", 0, 0.0, 400),
+    ("cg_normal", ol.KRYLOV_CG, "normal16", 0, 0.0, 400),
+    ("bicgstab2", ol.KRYLOV_BICGSTAB_L, "wilson16", 2, 0.0, 200),
+    ("richardson", ol.KRYLOV_RICHARDSON, "wilson16h", 5, 0.33, 400),
+    ("mr", ol.KRYLOV_MR, "wilson16h", 0, 0.85, 60),
+    ("gcr8", ol.KRYLOV_GCR, "wilson16", 8, 0.0, 200),
+]
+
+
+def solve_dense_twin(kind, name, b, x0, pi, pd, max_iter, tol=1e-9):
+    import krylov_batch_numpy as kb
+    import test_host_krylov_batch as host
+    op = kb.operators()[name]
+    d, dag = host.descs()[name]
+    normal = op.kind == "normal"
+    return op, ol.krylov_solve(kind, d, b, max_iter, tol, param_i=pi, param_d=pd, x0=x0, dagger_desc=dag if normal else None, normal=normal)[:4]
+
+
+@pytest.mark.parametrize("tag,kind,name,pi,pd,max_iter", EQUATION_KINDS, ids=[k[0] for k in EQUATION_KINDS])
+def test_a_zero_right_hand_side_has_the_solution_zero(tag, kind, name, pi, pd, max_iter):
+    """A x = 0 has the solution x = 0 and no other: converged, no iteration, resSq 0 -- from a non-zero initial guess too (the twins, like the
+    GPU cores, used to report success with the guess left in x)."""
+    import krylov_batch_numpy as kb
+    guess = kb.rhs_sets(kb.operators()[name])[2][1]
+    assert guess.any()
+    for x0 in (None, guess):
+        op, (conv, it, x, rsq) = solve_dense_twin(kind, name, np.zeros(guess.size, dtype=np.complex128), x0, pi, pd, max_iter)
+        assert conv and it == 0 and rsq == 0.0
+        assert not x.any() and np.linalg.norm(op.A @ x) == 0.0
+
+
+@pytest.mark.parametrize("tag,kind,name,pi,pd,max_iter", EQUATION_KINDS, ids=[k[0] for k in EQUATION_KINDS])
+def test_the_twins_solve_the_equation(tag, kind, name, pi, pd, max_iter):
+    import krylov_batch_numpy as kb
+    b0, bg, g = kb.rhs_sets(kb.operators()[name])
+    ref = None
+    for x0 in (None, g[0]):
+        op, (conv, it, x, rsq) = solve_dense_twin(kind, name, b0[0], x0, pi, pd, max_iter)
+        ref = kb.dense_solution(op.A, b0[0]) if ref is None else ref
+        assert conv and it > 0
+        kb.check_bars(op, x, b0[0], 1e-9, ref)
