@@ -48,6 +48,18 @@ def matrix_grids(Lx, Ly, nc, clover, hopping):
     return Cg, Hg
 
 
+_LAST = []   # the grids of the fields last applied and their magnitudes: a batch row applies the same fields once per system
+
+
+def _grids_and_magnitudes(Lx, Ly, nc, clover, hopping):
+    """(C, [H_mu], |C|, [|H_mu|]) of matrix_grids, kept while the next call passes the same two arrays"""
+    if _LAST and _LAST[0] is clover and _LAST[1] is hopping and _LAST[2] == (Lx, Ly, nc):
+        return _LAST[3]
+    Cg, Hg = matrix_grids(Lx, Ly, nc, clover, hopping)
+    _LAST[:] = [clover, hopping, (Lx, Ly, nc), (Cg, Hg, None if Cg is None else np.abs(Cg), None if Hg is None else [np.abs(h) for h in Hg])]
+    return _LAST[3]
+
+
 def apply(Lx, Ly, nc, clover, hopping, shift, eo_shift, dof_shift, pieces, rhs, lhs0):
     """(out, S, n) as flat (eo, y, x, c) arrays: complex long double, long double, int."""
     x = to_grid(rhs, Lx, Ly, nc)
@@ -65,7 +77,7 @@ def apply(Lx, Ly, nc, clover, hopping, shift, eo_shift, dof_shift, pieces, rhs, 
             S = S + (abs(shift) + abs(eo_shift) + dof_mag) * np.abs(x)
             n = n + 3
         return to_eo(out, 1, 1, nc), to_eo(S, 1, 1, nc), to_eo(n, 1, 1, nc)
-    Cg, Hg = matrix_grids(Lx, Ly, nc, clover, hopping)
+    Cg, Hg, Ca, Ha = _grids_and_magnitudes(Lx, Ly, nc, clover, hopping)
     xs, ys = np.meshgrid(np.arange(Lx), np.arange(Ly), indexing="ij")
     parity = (xs + ys) & 1
     for p in (0, 1):
@@ -77,13 +89,13 @@ def apply(Lx, Ly, nc, clover, hopping, shift, eo_shift, dof_shift, pieces, rhs, 
         on = (parity == p)[:, :, None]
         if Cg is not None and pieces & (P_CLOVER_E << p):
             out = out + on * np.einsum("xyrc,xyc->xyr", Cg, x)
-            S = S + on * np.einsum("xyrc,xyc->xyr", np.abs(Cg), ax)
+            S = S + on * np.einsum("xyrc,xyc->xyr", Ca, ax)
             n = n + on * nc
         for mu in range(4):
             if Hg is not None and pieces & ((P_OE_XP1 if p else P_EO_XP1) << mu):
                 axis, step = STEP[mu]
                 out = out + on * np.einsum("xyrc,xyc->xyr", Hg[mu], np.roll(x, step, axis=axis))
-                S = S + on * np.einsum("xyrc,xyc->xyr", np.abs(Hg[mu]), np.roll(ax, step, axis=axis))
+                S = S + on * np.einsum("xyrc,xyc->xyr", Ha[mu], np.roll(ax, step, axis=axis))
                 n = n + on * nc
         if pieces & (P_SHIFT_E << p):
             eo = eo_shift if p == 0 else -eo_shift

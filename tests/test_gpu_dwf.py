@@ -201,6 +201,116 @@ def test_hops_in_place(dims, Ls):
         assert ok, (hex(pieces), worst)
 
 
+# ---- past the cap of grid.y: 65540 rows on 65535 blocks, so five blocks take a second row
+# (name, family, lattice, pieces); kernel D walks (parity, y) rows, row = 2 y + parity on both parities and y on one; kernel D2 walks y
+TALL = [("D-hops-zero", P.DF_DIRECT, (2, 32770), P.P_HOPPING | P.P_ZERO),
+        ("D-hops", P.DF_DIRECT, (2, 32770), P.P_HOPPING),
+        ("D-even", P.DF_DIRECT, (2, 65540), P.P_CLOVER_E | P.P_EO | P.P_SHIFT_E | P.P_ZERO_E),
+        ("D2-zero", P.DF_PAIR, (2, 65540), P.P_ALL | P.P_ZERO),
+        ("D2", P.DF_PAIR, (2, 65540), P.P_ALL)]
+TALL_IDS = [c[0] for c in TALL]
+
+
+def walked_second(plan, dims, pieces, per_site):
+    """asserts from the plan that grid.y is capped below the row count, and returns the mask (over one vector of `per_site` numbers a site)
+    of the rows a block reaches on its second trip: rows gy .. nrows - 1 of the kernel's own numbering, as (parity, y)"""
+    Lx, Ly = dims
+    family, gy = plan[0], plan[4]
+    even, odd = bool(pieces & (P.P_CLOVER_E | P.P_EO)), bool(pieces & (P.P_CLOVER_O | P.P_OE))     # the parities written
+    both = even and odd
+    nrows = Ly if family == P.DF_PAIR or not both else 2 * Ly
+    assert gy == 65535 < nrows == 65540, (plan, nrows)
+    m = np.zeros((2, Ly, (Lx // 2) * per_site), dtype=bool)
+    for row in range(gy, nrows):
+        if family == P.DF_PAIR:
+            m[:, row] = True
+        elif both:
+            m[row & 1, row >> 1] = True
+        else:
+            m[0 if even else 1, row] = True
+    return m.ravel()
+
+
+def held_to_the_twin(h, want, S, cnt, f32, second, tag):
+    """the whole output and, on their own, the rows walked second: no NaN of the prefill left, and within the family's bound"""
+    assert np.all(np.isfinite(h)), (tag, "NaN prefill survived", int(np.count_nonzero(~np.isfinite(h[second]))), "of them on the second trip")
+    for name, sel in (("whole", slice(None)), ("second trip", second)):
+        ok, worst = within(h[sel], np.asarray(want)[sel], np.asarray(S)[sel], np.asarray(cnt)[sel], f32)
+        print("dwf tall %s %s: worst err/bound %.3f" % (tag, name, worst))
+        assert ok, (tag, name, worst)
+
+
+@pytest.mark.parametrize("f32", [False, True], ids=["c64", "c32"])
+@pytest.mark.parametrize("Ls", [2, 3])
+@pytest.mark.parametrize("name,family,dims,pieces", TALL, ids=TALL_IDS)
+def test_apply_walks_more_rows_than_the_grid_has_blocks(name, family, dims, pieces, Ls, f32):
+    Lx, Ly = dims
+    nc = 2 * Ls
+    dt, npt = (qmg.C32 if f32 else qmg.C64), np_dtype(f32)
+    plan = qmg.dwf_plan(dt, dims, Ls, pieces)
+    assert plan[0] == family, plan
+    second = walked_second(plan, dims, pieces, nc)
+    assert np.count_nonzero(second) == 5 * (Lx // 2) * nc * (2 if family == P.DF_PAIR else 1)
+    g, rhs, lhs0 = case(dims, Ls, f32)
+    want, S, cnt = reference(dims, Ls, f32, pieces)
+    start = lhs0.copy()
+    half = start.size // 2
+    for p in (0, 1):
+        if pieces & (P.P_ZERO_E << p):
+            start[p * half:(p + 1) * half] = np.nan
+    d = qmg.make_desc(Lx, Ly, nc, None, None, *SHIFTS)
+    dg, dx = D(g.astype(npt)), D(rhs.astype(npt))
+    runs = []
+    for _ in range(2):
+        got = D(start.astype(npt))
+        qmg.dwf_apply_direct(dt, d, dg, Ls, M, got, dx, pieces, W)
+        runs.append(got.to_host())
+    h = runs[0]
+    held_to_the_twin(h, want, S, cnt, f32, second, (name, Ls, "c32" if f32 else "c64"))
+    untouched = np.asarray(cnt == 0) & np.isfinite(start)
+    assert np.array_equal(h[untouched], lhs0.astype(npt)[untouched])
+    assert runs[1].tobytes() == h.tobytes()                # a second run on the same inputs: the same bytes
+
+
+@pytest.mark.parametrize("f32", [False, True], ids=["c64", "c32"])
+@pytest.mark.parametrize("name,family,dims,pieces", [TALL[1], TALL[3]], ids=[TALL_IDS[1], TALL_IDS[3]])
+def test_tall_batch_with_a_masked_system(name, family, dims, pieces, f32):
+    """three systems, the middle one masked out, Ls = 3: the system loop runs inside the row loop, so the second row starts it again"""
+    Lx, Ly = dims
+    Ls, nc = 3, 6
+    n = Lx * Ly * nc
+    stride = n + 4
+    nrhs, mask = 3, 0b101
+    dt, npt = (qmg.C32 if f32 else qmg.C64), np_dtype(f32)
+    plan = qmg.dwf_plan(dt, dims, Ls, pieces, 2)
+    assert plan[0] == family and plan[5] & P.DPF_BATCH and plan[7] == 2, plan
+    second = walked_second(plan, dims, pieces, nc)
+    g = case(dims, Ls, f32)[0]
+    xs, ls = rounded(cvec(nrhs * stride, 3), f32), rounded(cvec(nrhs * stride, 4), f32)
+    start = ls.copy()
+    if pieces & P.P_ZERO:
+        for k in range(nrhs):
+            if (mask >> k) & 1:
+                start[k * stride:k * stride + n] = np.nan
+    d = qmg.make_desc(Lx, Ly, nc, None, None, *SHIFTS)
+    dg, dx = D(g.astype(npt)), D(xs.astype(npt))
+    runs = []
+    for _ in range(2):
+        got = D(start.astype(npt))
+        qmg.dwf_apply_direct(dt, d, dg, Ls, M, got, dx, pieces, W, nrhs, stride, mask)
+        runs.append(got.to_host())
+    h = runs[0]
+    pad = np.ones(nrhs * stride, dtype=bool)
+    for k in range(nrhs):
+        sl = slice(k * stride, k * stride + n)
+        if (mask >> k) & 1:
+            pad[sl] = False
+            want, S, cnt = dn.apply(Lx, Ly, Ls, g, M, W, *SHIFTS, pieces, xs[sl], ls[sl])
+            held_to_the_twin(h[sl], want, S, cnt, f32, second, (name, "system", k, "c32" if f32 else "c64"))
+    assert h[pad].tobytes() == ls.astype(npt)[pad].tobytes()        # the masked system and the padding: byte-identical
+    assert runs[1].tobytes() == h.tobytes()
+
+
 def test_refusals_leave_lhs_untouched():
     Lx, Ly, Ls = 16, 8, 8
     nc = 2 * Ls

@@ -234,6 +234,160 @@ def test_batches_with_a_masked_system(dims, Ls, f32):
     check(tmp.to_host(), ts, lambda k: ref(k)[3:], "schur tmp")
 
 
+# ---- past the cap of grid.y: 65540 rows on 65535 blocks, so five blocks take a second row (kernels K and I through the other LDS buffer
+# when the number of active systems is odd)
+TALL2, TALL1 = (2, 32770), (2, 65540)          # rows = (parity, y), row = 2 y + parity; rows = y of one parity
+LS_TALL = [2, 3]                               # at Ls = 3 the block is 255 lanes
+
+
+def walked_second(plan, dims, Ls, parity=None):
+    """asserts from the plan that grid.y is capped below the row count, and returns the mask over one vector of the rows a block reaches on
+    its second trip: rows gy .. nrows - 1 of the kernel's own numbering, as (parity, y).  parity: the one processed, None for both"""
+    Lx, Ly = dims
+    gy, nrows = plan[4], Ly * (2 if parity is None else 1)
+    assert gy == 65535 < nrows == 65540, (plan, nrows)
+    m = np.zeros((2, Ly, (Lx // 2) * 2 * Ls), dtype=bool)
+    for row in range(gy, nrows):
+        if parity is None:
+            m[row & 1, row >> 1] = True
+        else:
+            m[parity, row] = True
+    return m.ravel()
+
+
+def held_to_the_twin(h, want, S, cnt, f32, second, tag):
+    """the whole output and, on their own, the rows walked second: no NaN of the prefill left, and within the family's bound"""
+    assert np.all(np.isfinite(h)), (tag, "NaN prefill survived", int(np.count_nonzero(~np.isfinite(h[second]))), "of them on the second trip")
+    for name, sel in (("whole", slice(None)), ("second trip", second)):
+        ok, worst = within(h[sel], np.asarray(want)[sel], np.asarray(S)[sel], np.asarray(cnt)[sel], f32)
+        print("dwf eo tall %s %s: worst err/bound %.3f" % (tag, name, worst))
+        assert ok, (tag, name, worst)
+
+
+def twice(launch, start, npt):
+    """the host copies of two runs from the same start"""
+    out = []
+    for _ in range(2):
+        got = D(start.astype(npt))
+        launch(got)
+        out.append(got.to_host())
+    return out
+
+
+@PREC
+@pytest.mark.parametrize("Ls", LS_TALL)
+@pytest.mark.parametrize("pieces", [P.P_HOPPING | P.P_ZERO, P.P_HOPPING], ids=["zero", "add"])
+def test_hops_inv5_walks_more_rows_than_the_grid_has_blocks(pieces, Ls, f32):
+    dims = TALL2
+    dt, npt = types(f32)
+    plan = qmg.dwf_eo_plan(dt, dims, Ls, qmg.DEK_HOPS_INV5, pieces)
+    assert plan[0] == qmg.DEF_HOPS_INV5 and plan[2] == Ls * (256 // Ls), plan
+    second = walked_second(plan, dims, Ls)
+    g, rhs, lhs0, _ = case(dims, Ls, f32)
+    d, dg, dx = desc(dims, Ls), D(g.astype(npt)), D(rhs.astype(npt))
+    want, S, n = de.hops_inv5(*dims, Ls, g, M, W, SHIFT, EO_SHIFT, pieces, ALPHA, qmg.DWF_G5_IN, rhs, lhs0)
+    start = prefill(lhs0, [0, 1] if pieces & P.P_ZERO else [])
+    h, again = twice(lambda got: qmg.dwf_hops_inv5(dt, d, dg, Ls, M, got, dx, pieces, ALPHA, qmg.DWF_G5_IN, W), start, npt)
+    held_to_the_twin(h, want, S, n, f32, second, ("K", hex(pieces), Ls, f32))
+    assert again.tobytes() == h.tobytes()                  # a second run on the same inputs: the same bytes
+
+
+@PREC
+@pytest.mark.parametrize("Ls", LS_TALL)
+def test_inv5_walks_more_rows_than_the_grid_has_blocks(Ls, f32):
+    dims = TALL2
+    dt, npt = types(f32)
+    plan = qmg.dwf_eo_plan(dt, dims, Ls, qmg.DEK_INV5, P.P_CLOVER)
+    assert plan[0] == qmg.DEF_INV5 and plan[2] == Ls * (256 // Ls), plan
+    second = walked_second(plan, dims, Ls)
+    g, rhs, lhs0, _ = case(dims, Ls, f32)
+    d, dx = desc(dims, Ls), D(rhs.astype(npt))
+    want, S, n = de.inv5(*dims, Ls, M, W, SHIFT, EO_SHIFT, P.P_CLOVER, ALPHA, rhs, lhs0)
+    h, again = twice(lambda got: qmg.dwf_inv5(dt, d, Ls, M, got, dx, P.P_CLOVER, ALPHA, W), prefill(lhs0, [0, 1]), npt)
+    held_to_the_twin(h, want, S, n, f32, second, ("I", Ls, f32))
+    assert again.tobytes() == h.tobytes()
+
+
+@PREC
+@pytest.mark.parametrize("Ls", LS_TALL)
+@pytest.mark.parametrize("flags", [0, qmg.DWF_G5_IN, qmg.DWF_G5_OUT, qmg.DWF_G5_IN | qmg.DWF_G5_OUT])
+def test_schur_apply_walks_more_rows_than_the_grid_has_blocks(flags, Ls, f32):
+    """one parity of 2 x 65540: kernel K writes tmp on the other parity and the second stage lhs on this one, each over 65540 rows"""
+    dims, parity = TALL1, 1
+    dt, npt = types(f32)
+    one = P.P_CLOVER_O | P.P_OE | P.P_SHIFT_O | P.P_ZERO_O
+    plan1, plan2 = qmg.dwf_eo_plan(dt, dims, Ls, qmg.DEK_HOPS_INV5, P.P_EO | P.P_ZERO_E), qmg.dwf_eo_plan(dt, dims, Ls, qmg.DEK_SCHUR2, one)
+    assert plan1[0] == qmg.DEF_HOPS_INV5 and plan2[0] == qmg.DEF_SCHUR2, (plan1, plan2)
+    second_t, second = walked_second(plan1, dims, Ls, 1 - parity), walked_second(plan2, dims, Ls, parity)
+    g, rhs, lhs0, tmp0 = case(dims, Ls, f32)
+    n = rhs.size
+    d, dg, dx = desc(dims, Ls), D(g.astype(npt)), D(rhs.astype(npt))
+    want, S, cnt, wt, St, nt = de.schur(*dims, Ls, g, M, W, SHIFT, EO_SHIFT, parity, flags, rhs, lhs0, tmp0)
+    runs = []
+    for _ in range(2):
+        got, tmp = D(prefill(lhs0, [parity]).astype(npt)), D(prefill(tmp0, [1 - parity]).astype(npt))
+        qmg.dwf_schur_apply(dt, d, dg, Ls, M, got, dx, tmp, parity, flags, W)
+        runs.append((got.to_host(), tmp.to_host()))
+    h, t = runs[0]
+    held_to_the_twin(t, wt, St, nt, f32, second_t, ("schur tmp", flags, Ls, f32))
+    held_to_the_twin(h, want, S, cnt, f32, second, ("schur lhs", flags, Ls, f32))
+    p_half, o_half = halves(n)[parity], halves(n)[1 - parity]
+    assert h[o_half].tobytes() == lhs0.astype(npt)[o_half].tobytes() and t[p_half].tobytes() == tmp0.astype(npt)[p_half].tobytes()
+    assert runs[1][0].tobytes() == h.tobytes() and runs[1][1].tobytes() == t.tobytes()
+
+
+TALL_STRIDE = TALL2[0] * TALL2[1] * 6 + 4
+
+
+@functools.lru_cache(maxsize=None)
+def tall_batch(f32):
+    """four systems of 2 x 32770 at Ls = 3, apart by more than a vector: links, rhs, lhs0"""
+    return (case(TALL2, 3, f32)[0],) + tuple(rounded(cvec(4 * TALL_STRIDE, s), f32) for s in (3, 4))
+
+
+@functools.lru_cache(maxsize=None)
+def tall_batch_reference(kernel, f32, k):
+    g, xs, ls = tall_batch(f32)
+    sl = slice(k * TALL_STRIDE, k * TALL_STRIDE + TALL_STRIDE - 4)
+    if kernel == "I":
+        return de.inv5(*TALL2, 3, M, W, SHIFT, EO_SHIFT, P.P_CLOVER, ALPHA, xs[sl], ls[sl])
+    return de.hops_inv5(*TALL2, 3, g, M, W, SHIFT, EO_SHIFT, P.P_HOPPING | P.P_ZERO, ALPHA, qmg.DWF_G5_IN, xs[sl], ls[sl])
+
+
+@PREC
+@pytest.mark.parametrize("nrhs,mask", [(4, 0b1101), (3, 0b101)], ids=["3of4", "2of3"])
+@pytest.mark.parametrize("kernel", ["K", "I"])
+def test_tall_batches_with_an_odd_and_an_even_number_of_active_systems(kernel, nrhs, mask, f32):
+    """the LDS buffer flips once per system: with three active systems a block starts its second row on the other buffer than its first,
+    with two on the same one"""
+    dims, Ls, stride = TALL2, 3, TALL_STRIDE
+    n = stride - 4
+    dt, npt = types(f32)
+    active = [k for k in range(nrhs) if (mask >> k) & 1]
+    pieces = P.P_CLOVER if kernel == "I" else P.P_HOPPING | P.P_ZERO
+    plan = qmg.dwf_eo_plan(dt, dims, Ls, qmg.DEK_INV5 if kernel == "I" else qmg.DEK_HOPS_INV5, pieces, len(active))
+    assert plan[0] == (qmg.DEF_INV5 if kernel == "I" else qmg.DEF_HOPS_INV5) and plan[7] == len(active) and plan[2] == 255, plan
+    second = walked_second(plan, dims, Ls)
+    g, xs, ls = tall_batch(f32)
+    xs, ls = xs[:nrhs * stride], ls[:nrhs * stride]
+    start = ls.copy()
+    pad = np.ones(nrhs * stride, dtype=bool)
+    for k in active:
+        start[k * stride:k * stride + n] = np.nan
+        pad[k * stride:k * stride + n] = False
+    d, dg, dx = desc(dims, Ls), D(g.astype(npt)), D(xs.astype(npt))
+    if kernel == "I":
+        launch = lambda got: qmg.dwf_inv5(dt, d, Ls, M, got, dx, pieces, ALPHA, W, nrhs, stride, mask)
+    else:
+        launch = lambda got: qmg.dwf_hops_inv5(dt, d, dg, Ls, M, got, dx, pieces, ALPHA, qmg.DWF_G5_IN, W, nrhs, stride, mask)
+    h, again = twice(launch, start, npt)
+    for k in active:
+        want, S, cnt = tall_batch_reference(kernel, f32, k)
+        held_to_the_twin(h[k * stride:k * stride + n], want, S, cnt, f32, second, (kernel, "system", k, "of", nrhs, f32))
+    assert h[pad].tobytes() == ls.astype(npt)[pad].tobytes()        # the masked system and the padding: byte-identical
+    assert again.tobytes() == h.tobytes()
+
+
 # ---- refusals
 def test_refusals_leave_lhs_untouched():
     dims, Ls = (16, 8), 8

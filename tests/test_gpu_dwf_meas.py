@@ -161,6 +161,114 @@ def test_slice_norms_within_the_fp64_bound_and_reproducible(dims, Ls, f32):
         assert dx.to_host().tobytes() == x.tobytes()
 
 
+# ---- past the cap of grid.y: the 65540 (parity, y) rows of 2 x 32770 on 65535 blocks, so five blocks take a second row.  The rows are walked
+# in storage order, row = parity Ly + y: the second trip is the odd rows y = 32765 .. 32769, the last five rows of a vector
+TALL = (2, 32770)
+TALL_Y0 = 32765
+
+
+def capped(dt, Ls, kernel, nsys):
+    plan = qmg.dwf_meas_plan(dt, TALL, Ls, kernel, nsys)
+    assert plan[4] == 65535 < 2 * TALL[1] == 65540 and plan[7] == nsys, plan
+    return plan
+
+
+@PREC
+@pytest.mark.parametrize("Ls", [2, 3])
+def test_source_and_projections_walk_more_rows_than_the_grid_has_blocks(Ls, f32):
+    Lx, Ly = TALL
+    dt, npt = types(f32)
+    for nsys, e5, e4 in BATCHES:
+        b5, b4 = Batch(Lx * Ly * 2 * Ls, nsys, e5), Batch(Lx * Ly * 2, nsys, e4)
+        tail5, tail4 = 5 * (Lx // 2) * 2 * Ls, 5 * (Lx // 2) * 2       # the elements of the five rows walked second
+        assert capped(dt, Ls, qmg.DMK_SOURCE, nsys)[0] == qmg.DMF_SOURCE
+        eta = cvec(b4.total, 1).astype(npt)
+        start5 = b5.start(2, npt)
+        runs = []
+        for _ in range(2):
+            psi = D(start5)
+            qmg.dwf_wall_source(dt, TALL, Ls, psi, D(eta), nsys, b5.arg, b4.arg)
+            runs.append(psi.to_host())
+        h = runs[0]
+        assert not np.any(np.isnan(h[~b5.pad])), "source: NaN prefill survived"
+        for k in range(nsys):
+            want = dm.wall_source(eta[b4.sl(k)], Lx, Ly, Ls)
+            assert h[b5.sl(k)].tobytes() == want.tobytes(), ("source", nsys, k)
+            assert h[b5.sl(k)][-tail5:].tobytes() == want[-tail5:].tobytes() and np.any(want[-tail5:]), ("source, second trip", nsys, k)
+        assert h[b5.pad].tobytes() == start5[b5.pad].tobytes(), "source wrote between the systems"
+        assert runs[1].tobytes() == h.tobytes()
+        x = cvec(b5.total, 3).astype(npt)
+        dx = D(x)
+        for which, name, kernel in ((0, "wall", qmg.DMK_PROJECT_WALL), (1, "mid", qmg.DMK_PROJECT_MID)):
+            if which == 1 and Ls % 2:
+                continue                                           # no midpoint between the walls: test_wall_source_and_projections_bit_for_bit holds the refusal
+            assert capped(dt, Ls, kernel, nsys)[0] == qmg.DMF_PROJECT
+            start4 = b4.start(4 + which, npt)
+            runs = []
+            for _ in range(2):
+                q = D(start4)
+                qmg.dwf_wall_project(dt, TALL, Ls, q, dx, which, nsys, b4.arg, b5.arg)
+                runs.append(q.to_host())
+            g = runs[0]
+            assert not np.any(np.isnan(g[~b4.pad])), (name, "NaN prefill survived")
+            for k in range(nsys):
+                want = dm.wall_project(x[b5.sl(k)], Lx, Ly, Ls, name)
+                assert g[b4.sl(k)].tobytes() == want.tobytes(), (name, nsys, k)
+                assert g[b4.sl(k)][-tail4:].tobytes() == want[-tail4:].tobytes(), (name, "second trip", nsys, k)
+            assert g[b4.pad].tobytes() == start4[b4.pad].tobytes(), "projection wrote between the systems"
+            assert runs[1].tobytes() == g.tobytes()
+
+
+def norms_held(dims, Ls, f32, nsys, e5, tail_from=None):
+    """qmg_dwf_slice_norms into a NaN-filled device result, twice, against the twin at the file's fp64 summation bound; tail_from: the
+    first y whose odd row is walked second, compared on its own too"""
+    Lx, Ly = dims
+    dt, npt = types(f32)
+    b5 = Batch(Lx * Ly * 2 * Ls, nsys, e5)
+    x = cvec(b5.total, 5).astype(npt)
+    dx = D(x)
+    runs = []
+    for _ in range(2):
+        out_dev = D(np.full(nsys * Ly * 2 * Ls, np.nan))
+        got = qmg.dwf_slice_norms(dt, dims, Ls, dx, nsys, b5.arg, out_dev)
+        assert out_dev.to_host().tobytes() == got.tobytes()
+        runs.append(got)
+    got = runs[0]
+    assert np.all(np.isfinite(got)), "NaN prefill survived"
+    assert runs[1].tobytes() == got.tobytes()                                     # two calls: the same bits
+    for k in range(nsys):
+        want = dm.slice_norms(x[b5.sl(k)].astype(np.complex128), Lx, Ly, Ls)
+        bound = sn.elementwise_bound(want, Lx + 2)
+        err = np.abs(got[k].astype(np.longdouble) - want)
+        print("dwf slice_norms %s Ls=%d %s nsys=%d k=%d worst err/bound %.4f" % (dims, Ls, "c32" if f32 else "c64", nsys, k, float(np.max(err / bound))))
+        assert np.all(err <= bound), (nsys, k, float(np.max(err / bound)))
+        if tail_from is not None:
+            assert np.all(err[tail_from:] <= bound[tail_from:]) and err[tail_from:].shape[0] == 5, (nsys, k, "second trip")
+    assert dx.to_host().tobytes() == x.tobytes()
+
+
+@PREC
+@pytest.mark.parametrize("Ls", [2, 3])
+def test_slice_norms_walk_more_rows_than_the_grid_has_blocks(Ls, f32):
+    for nsys, e5, _ in BATCHES:
+        assert capped(types(f32)[0], Ls, qmg.DMK_NORMS, nsys)[0] == qmg.DMF_NORMS
+        norms_held(TALL, Ls, f32, nsys, e5, TALL_Y0)
+
+
+@PREC
+@pytest.mark.parametrize("dims,Ls", [((520, 2), 32), ((4800, 2), 3)], ids=IDS)
+def test_slice_norms_through_the_unrolled_loop(dims, Ls, f32):
+    """wide half rows: lane 0 makes two trips of the loop that holds four chunks in flight, and only part of the lanes enter the remainder
+    loop after it.  (520, 2), Ls = 32: 8320 lanes, step 1024; (4800, 2), Ls = 3: 7200 lanes, step 1020 (only lanes below 60 take the second
+    unrolled trip)."""
+    for nsys, e5, _ in BATCHES:
+        family, _, block, gx, _, pbr, _, _ = qmg.dwf_meas_plan(types(f32)[0], dims, Ls, qmg.DMK_NORMS, nsys)
+        lanes, step = dims[0] // 2 * Ls, pbr * block
+        assert family == qmg.DMF_NORMS and gx == pbr
+        assert lanes > 7 * step and lanes % (4 * step) != 0, (lanes, step)
+        norms_held(dims, Ls, f32, nsys, e5)
+
+
 def test_invalid_arguments_are_refused_before_any_launch():
     dims, Ls = (16, 8), 8
     n5, n4 = 16 * 8 * 2 * Ls, 16 * 8 * 2

@@ -195,6 +195,27 @@ def test_wilson_and_polyakov_loops_match_numpy(golden_dir):
     assert np.abs(qmg.u1_wilson_loops(upload(th)[1], 34, 10, 3, 5) - fn.wilson_loops(*fn.links(th), 3, 5)).max() <= 1e-12
 
 
+@pytest.mark.parametrize("rows", ["all", "tail"])
+def test_loops_past_the_cap_of_the_partial_sum_grid(rows):
+    """516 x 512 = 264 192 sites against the 1024 blocks x 256 lanes = 262 144 of k_wilson_loop's grid: lanes 0 .. 2047 take a second site,
+    even-odd index >= 262 144, i.e. the odd sites from row 504 on.  "all": Gaussian beta = 6 phases on every link; "tail": on the links of the
+    rows y >= 509 alone, so that half of the loops that differ from 1 are summed on a second trip.  Loops up to (2, 2) and the Polyakov loops
+    against numpy at the 1e-12 of the test above; a second run returns the same bits."""
+    Lx, Ly = 516, 512
+    assert Lx * Ly > 1024 * 256
+    th = gaussian_phases(Lx, Ly, 6.0, 516)
+    if rows == "tail":
+        th = tuple(np.where(np.arange(Ly)[None, :] >= 509, t, 0.0) for t in th)
+    Ux, Uy = fn.links(th)
+    _, dg = upload(th)
+    W, want = qmg.u1_wilson_loops(dg, Lx, Ly, 2, 2), fn.wilson_loops(Ux, Uy, 2, 2)
+    (px, py), (wx, wy) = qmg.u1_polyakov(dg, Lx, Ly), fn.polyakov(Ux, Uy)
+    print("516 x 512 %s: loops %.2e, Polyakov %.2e %.2e" % (rows, np.abs(W - want).max(), abs(px - wx), abs(py - wy)))
+    assert np.abs(W - want).max() <= 1e-12 and abs(px - wx) <= 1e-12 and abs(py - wy) <= 1e-12
+    assert np.abs(want - 1.0).min() > 1e-4                                        # the rows of the tail alone move every loop far beyond the gate
+    assert np.array_equal(qmg.u1_wilson_loops(dg, Lx, Ly, 2, 2), W) and qmg.u1_polyakov(dg, Lx, Ly) == (px, py)
+
+
 def test_loops_of_uniform_instanton_and_cold_fields():
     """Uniform field strength F = 2 pi Q / V: W(R,T) = exp(i F R T) and a fixed point of the flow to rounding (test_host_flow.py).  The
     reference's create_instanton_u1 is not uniform (plaquette angles from -1.6 to 2.28 on the unit field), so for it numpy's own loops of the

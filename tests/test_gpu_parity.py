@@ -65,6 +65,45 @@ def test_cshift_bit_exact(Lx, Ly, dof):
     assert np.array_equal(out.to_host(), want)
 
 
+# past the caps of k_cshift's grid (csrc/qmg_fill.hip): grid.y = min(rows, 65535) blocks walk the rows of the written halves in storage order,
+# grid.x = min(blocks of a row, 1024) blocks of 256 lanes walk the hr * dof elements of a row
+#   2 x 32770 from both parities: 65540 rows, the second trip is rows 32765 .. 32769 of the odd half
+#   2 x 65540 from one parity:    65540 rows, the second trip is rows 65535 .. 65539 of the written half
+#   65540 x 2, dof = 9:           294 930 elements a row against 262 144 lanes, so the first 32 786 lanes take a second element
+CSHIFT_CAPPED = [(2, 32770, "evenodd", 1), (2, 32770, "evenodd", 3), (2, 65540, "even", 1), (2, 65540, "odd", 3), (65540, 2, "evenodd", 9)]
+
+
+@pytest.mark.parametrize("Lx,Ly,eo_name,dof", CSHIFT_CAPPED)
+def test_cshift_bit_exact_past_the_caps_of_the_grid(Lx, Ly, eo_name, dof):
+    eo = {"even": ol.EO_FROM_EVEN, "odd": ol.EO_FROM_ODD, "evenodd": ol.EO_FROM_EVENODD}[eo_name]
+    hr, half = Lx // 2, Lx * Ly * dof // 2
+    rows = Ly * (2 if eo_name == "evenodd" else 1)
+    # what is reached on a second trip: of the rows of the written halves taken together, in storage order
+    second = np.zeros((rows, hr * dof), dtype=bool)
+    if Lx == 2:
+        assert rows == 65540 and hr * dof <= 256
+        second[65535:] = True
+    else:
+        assert rows <= 65535 and hr * dof > 1024 * 256
+        second[:, 1024 * 256:] = True
+    v = cs.gaussian_cvec(Lx * Ly * dof, 100 + dof)
+    dv = D(v)
+    for cdir in (ol.CSHIFT_XP1, ol.CSHIFT_YP1, ol.CSHIFT_XM1, ol.CSHIFT_YM1):
+        sentinel = np.full(v.size, np.nan + 0j)
+        want = ol.cshift(v, cdir, eo, dof, Lx, Ly, lhs=sentinel.copy())
+        outs = []
+        for _ in range(2):
+            out = D(sentinel)
+            qmg.cshift(out, dv, cdir, eo, dof, Lx, Ly)
+            outs.append(out.to_host())
+        got = outs[0]
+        written = slice(None) if eo_name == "evenodd" else slice(half, None) if eo_name == "even" else slice(0, half)   # FROM_EVEN writes the odd half
+        assert np.all(np.isfinite(want[written])) and np.all(np.isfinite(got[written])), (cdir, "NaN prefill survived")
+        assert got.tobytes() == want.tobytes(), cdir                      # the half that is not written keeps the NaN's bits
+        assert np.any(second) and got[written][second.reshape(-1)].tobytes() == want[written][second.reshape(-1)].tobytes(), (cdir, "second trip")
+        assert outs[1].tobytes() == got.tobytes()
+
+
 def test_cshift_rejects_bad_arguments():
     v = D(np.zeros(64))
     L = qmg.lib()

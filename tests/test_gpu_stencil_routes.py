@@ -15,9 +15,11 @@ Frozen systems, all padding and a parity no piece touches must come back bit-ide
 bytes, norms and dots included (every kernel here has one writer per output and a fixed summation order).  Fused-norm rows hold the norms, epilogue rows `out` and the
 three dots, to long-double sums at the reductions' 1e-12.
 
-Left out: rows beyond grid.y for kernels B32 / C at nc = 8.  On a 2 x 32770 lattice at nc = 8 (21 M matrix elements) stencil_numpy takes 5.1 s
-per system and 1.2 GB of host memory, and kernel C needs five systems: neither fits the budget of a test here.  The row walk of those
-kernels is the loop of kernel B (`for (row = blockIdx.y; row < a.nrows; row += gridDim.y)`), which the nc = 3 row runs.
+Every kernel that caps grid.y has a `tall` row: 65 540 rows (kernel A2: row pairs) on 65 535 blocks, so that five blocks take a second row.
+Such a row asserts the cap from the plan, starts what the call overwrites as NaN and compares the rows walked second on their own as well.
+Kernels B32 and C are there at nc = 6 and nc = 8 on 2 x 32770 and 4 x 32770: stencil_numpy keeps the grids of the fields it applied last, so
+the five systems kernel C needs take 4 s on the narrow lattice and 9 s on the wide one, the two slowest rows of the table (260 MB on the device each).
+The `dotscap` row does the same for the epilogue's dots, whose partial sums cap grid.y at 2048 / gx.
 """
 import functools
 import importlib
@@ -585,6 +587,17 @@ ROUTES = [
     ('apply', 'c64', (2, 32770, 2), 1, 0b1, 'M0', 'tall', {'stencil_site': 7}, [S(0, 1, zero=True)]),
     ('h16', 'h16', (2, 32770, 2), 1, 0b1, 'M+', 'tall', {}, [S(H16BITS, 1)]),
     ('apply', 'c64', (2, 32770, 3), 1, 0b1, 'M0', 'tall', {}, [B(0, 1, 1, 1, 3)]),
+    # ---- ... kernel A2 with the fused norm: the LDS accumulator of a block lives across the row pairs it walks; two systems
+    ('norm2', 'c64', (2, 131080, 1), 2, 0b11, 'M0', 'tall', {}, [A2(1, norm=True, pf=True)]),
+    ('norm2', 'c64', (2, 131080, 2), 2, 0b11, 'M+', 'tall', {}, [A2(2, norm=True)]),
+    # ---- ... kernel B32 at nc = 6, the smallest even nc the plan sends there with complex<float> matrices
+    ('masked', 'm32', (2, 32770, 6), 1, 0b1, 'M0', 'tall', {}, [B32(M32, 1, 1, 1, 6)]),
+    # ---- ... kernel C (nc = 8, five systems), which restages its matrix tiles per row: the plain form where hr = 1 is odd with complex<float>
+    #      matrices (168 MB of them), the PAIR form at hr = 2 with complex<half> matrices and complex<float> vectors (168 MB + 84 MB)
+    ('masked', 'm32', (2, 32770, 8), 5, 0b11111, 'M0', 'tall', {}, [C(M32, 8, 1, 5)]),
+    ('masked', 'm16v32', (4, 32770, 8), 5, 0b11111, 'M0', 'tall', {}, [C(H16BITS, 8, 1, 5, pair=True)]),
+    # ---- the dots cap of kernel B's epilogue: gx = 1, so grid.y = 2048 blocks walk the 2060 (parity, y) rows
+    ('epi', 'c64', (2, 1030, 3), 2, 0b10, 'M0', 'other dots dotscap', {}, [B(0, 1, 1, 1, 3, epi=2)]),
 ]
 # ---- table end
 
@@ -694,6 +707,23 @@ def test_route_against_numpy_reference(row):
         set_knobs({})
 
 
+def walked_second(plan, dims, flags):
+    """asserts from the plan that grid.y is capped below the rows the blocks walk (at 65535, or at 2048 / gx by the dots), and returns the mask
+    over one vector of the rows reached on a second trip: rows gy .. of the kernel's own numbering -- kernel A2: the pair (2 row, 2 row + 1)
+    of both parities; every other kernel: row = 2 y + parity"""
+    Lx, Ly, nc = dims
+    family, gx, gy = plan[0], plan[9], plan[10]
+    walked = Ly // 2 if family == qmg.SF_PAIR else 2 * Ly
+    assert gy < walked and (gx * gy == 2048 if "dotscap" in flags else gy == 65535 and walked == 65540), plan
+    m = np.zeros((2, Ly, Lx // 2 * nc), dtype=bool)
+    for r in range(gy, walked):
+        if family == qmg.SF_PAIR:
+            m[:, 2 * r:2 * r + 2] = True
+        else:
+            m[r & 1, r >> 1] = True
+    return m.reshape(-1)
+
+
 def check_route(row):
     entry, storage, dims, nrhs, mask, pieces, flags, knobs, plans = row
     got_plans = planned(row)
@@ -702,8 +732,7 @@ def check_route(row):
     size, pc = Lx * Ly * nc, PIECES[pieces]
     act = active(mask, nrhs)
     assert sum(p[11] for p in got_plans) == len(act) or plans[0][0] in (qmg.SF_UNSUPPORTED, qmg.SF_INVALID)
-    if "tall" in flags:
-        assert all(p[10] == 65535 for p in got_plans)         # blocks walk the rows beyond grid.y
+    second = walked_second(got_plans[0], dims, flags) if "tall" in flags or "dotscap" in flags else None
     mdtype, vdtype, _, vec32 = STORAGE[storage]
     stride = size + PAD
     clover, hopping = operator(dims, mdtype)
@@ -719,6 +748,10 @@ def check_route(row):
     inplace = "inplace" in flags
     if inplace:
         lhs0 = rhs0
+    if second is not None and pc & P.P_ZERO == P.P_ZERO:      # what the call overwrites and never reads starts as NaN
+        assert not inplace
+        for k in act:
+            lhs0[k * stride:k * stride + size] = np.nan
     dcl = None if clover is None else to_device(clover, mdtype)
     dhop = None if hopping is None else to_device(hopping, mdtype)
     desc = qmg.make_desc(Lx, Ly, nc, dcl, dhop, *shifts)
@@ -780,6 +813,10 @@ def check_route(row):
         print("route %s system %d plan %s: max err/bound %.3f, rel L2 %.3e" % (route_id(row), k, plans[min(i // 16, len(plans) - 1)], ratio, l2))
         assert l2 < l2_limit, (k, l2)
         assert np.all(err <= bound), (k, int(np.argmax(err - bound)), ratio)
+        if second is not None:     # the rows walked second, on their own
+            assert np.all(np.isfinite(raw[seg])), (k, "NaN prefill survived", int(np.count_nonzero(~np.isfinite(raw[seg][second]))), "of them on the second trip")
+            l2 = float(np.linalg.norm(err[second]) / float(np.linalg.norm(want[second])))
+            assert np.any(second) and l2 < l2_limit and np.all(err[second] <= bound[second]), (k, "second trip", l2)
         if entry == "norm2":
             ref = float(np.sum(np.abs(want) ** 2))
             assert abs(extra["norms"][k] - ref) <= TOL_REDUCE * ref, (k, extra["norms"][k], ref)

@@ -162,7 +162,51 @@ ROUTES = [
     (P, "nv32", (8, 8, 3), (2, 2, 6), 1, 0b1, [REFUSED]),
     (R, "nv32", (8, 8, 2), (2, 2, 8), 1, 0b1, [REFUSED], "misaligned"),            # null vectors not 16-byte aligned
     (P, "nv32", (8, 8, 2), (2, 2, 8), 1, 0b1, [REFUSED], "misaligned"),
+    # ======== past the caps of the grid (qmg_transfer_plan exports no grid: the row counts are held against the launch code's caps here)
+    # ---- k_restrict: grid.y = min(cLy, 65535) blocks walk the coarse rows; cLy = 65538, so three blocks take a second row cy = 65535 .. 65537
+    (R, "c64", (4, 131076, 2), (2, 65538, 2), 1, 0b1, [ONE_R(1)]),
+    (R, "c32", (4, 131076, 2), (2, 65538, 2), 1, 0b1, [ONE_R(2)]),
+    (R, "nv32", (4, 131076, 2), (2, 65538, 2), 1, 0b1, [NV32_R]),
+    # ---- k_prolong: grid.y = min(2 fLy, 65535) blocks walk the fine rows row = parity fLy + y; 2 fLy = 65544, so nine blocks take a second
+    #      row 65535 .. 65543 (parity 1, y = 32763 .. 32771)
+    (P, "c64", (4, 32772, 2), (2, 16386, 4), 1, 0b1, [ONE_P(1)]),
+    (P, "c32", (4, 32772, 2), (2, 16386, 4), 1, 0b1, [ONE_P(2)]),
+    (P, "nv32", (4, 32772, 2), (2, 16386, 4), 1, 0b1, [NV32_P]),
+    # ---- k_bprolong_tile and k_brestrict_mfma: grid.y = min(cLy, 65535) blocks walk the coarse rows and restage their LDS tile per row;
+    #      cLy = 65538 again (the matrix-core restrict: 16 null vectors of 1 048 608 complex<float>, 134 MB)
+    (P, "c64", (4, 131076, 2), (2, 65538, 2), 2, 0b11, [PTILE(2, 4)]),
+    (R, "c32", (4, 131076, 2), (2, 65538, 16), 5, 0b11111, [MFMA(1, 4, 1, 1)]),
+    # ---- k_prolong: grid.x = min(blocks of a row, 1024) blocks of 256 lanes walk the fhr fnc / W = 10924 * 24 = 262 176 packs of a fine
+    #      row, so the first 32 lanes take a second pack 262 144 .. 262 175
+    (P, "c64", (21848, 2, 24), (10924, 2, 2), 1, 0b1, [ONE_P(1)]),
 ]
+GRID_Y_MAX, GRID_X_LANES = 65535, 1024 * 256      # the caps of the launch code (csrc/qmg_transfer.hip, csrc/qmg_transfer_mfma.hip)
+# which cap a geometry is about: "tall" coarse rows, "tallfine" fine (parity, y) rows, "wide" the packs of a fine row
+CAPPED = {((4, 131076, 2), (2, 65538, 2)): "tall", ((4, 131076, 2), (2, 65538, 16)): "tall", ((4, 32772, 2), (2, 16386, 4)): "tallfine",
+          ((21848, 2, 24), (10924, 2, 2)): "wide"}
+
+
+def walked_second(row):
+    """the mask over one output vector of what a block, or a lane, reaches on its second trip; None for a row that is not about a cap"""
+    op, _, fd, cd = row[:4]
+    tag = CAPPED.get((fd, cd), "")
+    if tag == "tall":             # coarse rows cy >= 65535: of the coarse vector (restrict), or the fine rows of their blocks (prolong)
+        assert cd[1] > GRID_Y_MAX
+        dims, y0 = (cd, GRID_Y_MAX) if op == R else (fd, GRID_Y_MAX * (fd[1] // cd[1]))
+        grid = np.zeros(dims, dtype=bool)
+        grid[:, y0:] = True
+        return tn._to_eo(grid, *dims)
+    if tag == "tallfine":         # fine rows in storage order, row = parity fLy + y >= 65535
+        assert 2 * fd[1] > GRID_Y_MAX
+        m = np.zeros((2 * fd[1], fd[0] // 2 * fd[2]), dtype=bool)
+        m[GRID_Y_MAX:] = True
+        return m.reshape(-1)
+    if tag == "wide":             # the packs (one element each in complex<double>) of every fine row beyond grid.x * block
+        assert fd[0] // 2 * fd[2] > GRID_X_LANES
+        m = np.zeros((2 * fd[1], fd[0] // 2 * fd[2]), dtype=bool)
+        m[:, GRID_X_LANES:] = True
+        return m.reshape(-1)
+    return None
 
 
 def route_id(row):
@@ -226,6 +270,7 @@ def test_route_against_numpy_reference(row):
     op, storage, fd, cd, nrhs, mask, plans = row[:7]
     mis = len(row) > 7
     assert planned(row) == plans
+    second = walked_second(row)
     nvec = cd[2]
     fsize, csize = fd[0] * fd[1] * fd[2], cd[0] * cd[1] * cd[2]
     fstride, cstride = fsize + FPAD, csize + CPAD
@@ -265,6 +310,10 @@ def test_route_against_numpy_reference(row):
         print("route %s system %d plan %s %s: max err/bound %.3f, rel L2 %.3e" % (route_id(row), k, storage, plans[i // 8 if len(plans) > 1 else 0], float(np.max(err / bound)), l2))
         assert l2 < (TOL32_ROUND if storage == "c32" else TOL64), (k, l2)
         assert np.all(err <= bound), (k, int(np.argmax(err / bound)), float(np.max(err / bound)))
+        if second is not None:      # what is reached on a second trip, on its own
+            l2 = float(np.linalg.norm(err[second]) / np.linalg.norm(want[second]))
+            assert np.any(second) and l2 < (TOL32_ROUND if storage == "c32" else TOL64), (k, "second trip", l2)
+            assert np.all(err[second] <= bound[second]), (k, "second trip", float(np.max(err[second] / bound[second])))
     # frozen systems and every padding element: the initial bytes
     assert np.array_equal(got[untouched], init[untouched])
     assert run().tobytes() == raw.tobytes()

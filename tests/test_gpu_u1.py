@@ -72,6 +72,40 @@ def test_noncompact_action_and_polar_round_trip():
     assert np.allclose(back.to_host(), phase_eo, atol=1e-14)    # |A| < pi here
 
 
+@pytest.mark.parametrize("rows", ["all", "tail"])
+def test_plaquette_sums_past_the_cap_of_the_partial_sum_grid(rows):
+    """516 x 512 = 264 192 sites against the 1024 blocks x 256 lanes = 262 144 of plaquette_sums' grid: lanes 0 .. 2047 take a second site,
+    t = y Lx + x >= 262 144, i.e. the sites from (16, 508) on.  "all": Gaussian phases on every link.  "tail": phases on the links of the
+    rows y >= 509 alone, so every plaquette that differs from 1 but those of row 508 is summed on a second trip, and a sum that leaves them
+    out is V to the last bit.  The gates are those of the tests above: 1e-13 on the mean plaquette, 1e-9 on the charge, 1e-10 on the action.
+    The last is absolute and was set at 24 x 24 with phases of width 0.4, an action of about 1.1e3; here the width is 0.4 sqrt(576 / V), which
+    gives an action of the same size, so the gate asks the same relative accuracy (9e-14) of a sum of 459 times as many terms."""
+    Lx, Ly = 516, 512
+    V = Lx * Ly
+    assert V > 1024 * 256 and 508 * Lx + 16 == 1024 * 256
+    rng = np.random.default_rng(516)
+    live = np.ones((1, Ly, 1)) if rows == "all" else (np.arange(Ly) >= 509).astype(np.float64).reshape(1, Ly, 1)
+    A = rng.normal(0.0, 0.4, size=(Lx, Ly, 2)) * live
+    Ux, Uy = np.exp(1j * A[:, :, 0]), np.exp(1j * A[:, :, 1])
+    dg = qmg.DeviceArray.from_host(cs.links_to_eo_gauge(Ux, Uy, Lx, Ly))
+    want_p, want_q = np_plaquette(Ux, Uy)
+    got_p, got_q = qmg.u1_plaquette(dg, Lx, Ly)
+    print("516 x 512 %s: plaquette %.3e, charge %.3e from numpy" % (rows, abs(got_p - want_p), abs(got_q - want_q)))
+    assert abs(got_p - want_p) < 1e-13 and abs(got_q - want_q) < 1e-9
+    assert abs(got_q - round(got_q)) < 1e-9
+    assert abs(want_p - 1.0) > 1e-4                              # the rows of the tail alone move the mean far beyond the gate
+    assert qmg.u1_plaquette(dg, Lx, Ly) == (got_p, got_q)        # a second run: the same bits
+    A = A * np.sqrt(576.0 / V)
+    Ax, Ay = A[:, :, 0], A[:, :, 1]
+    theta = Ax + cs.fwd(Ay, 0) - cs.fwd(Ax, 1) - Ay
+    phase_eo = np.concatenate([cs.grid_to_eo(Ax[:, :, None].astype(complex), Lx, Ly, 1).real, cs.grid_to_eo(Ay[:, :, None].astype(complex), Lx, Ly, 1).real])
+    dph = qmg.DeviceArray.from_host(phase_eo.astype(np.float64))
+    got_s, want_s = qmg.u1_noncompact_action(dph, Lx, Ly, 6.0), 3.0 * np.sum(theta ** 2)
+    print("516 x 512 %s: action %.6e, %.3e from numpy" % (rows, want_s, abs(got_s - want_s)))
+    assert abs(got_s - want_s) < 1e-10 and want_s > 1.0
+    assert qmg.u1_noncompact_action(dph, Lx, Ly, 6.0) == got_s
+
+
 @pytest.mark.parametrize("beta,stored", [(6.0, ["l32t32b60", "l64t64b60", "l128t128b60"]), (10.0, [])])
 def test_heatbath_ensemble_matches_free_field_theory_and_the_stored_configs(golden_dir, beta, stored):
     L, n_therm, n_meas, n_sep = 64, 400, 120, 10

@@ -16,8 +16,9 @@ writes nothing.
 
 Shapes: 130 x 6 (padding lanes in the last wavefront, a row count that is no power of two) unless a row is about an edge -- 2 x 2 (hr = 1:
 every x-neighbour is the site's own column, +y and -y are the same row), 516 x 2 (more than one block along x in both precisions, the last
-one partial), 2 x 4100 with the mode-1 epilogue (the dots cap makes each of the three forms walk several rows per block), 2 x 32770 (65 540
-(parity, y) rows: more than kernel W's grid.y can hold), the upper of two slabs of a 16 x 8 lattice with rows 0, 1, 2.
+one partial), 2 x 4100 with the mode-1 epilogue (the dots cap makes each of the three forms walk several rows per block), 2 x 32770, 2 x 65540 and 2 x 131080 (65 540
+(parity, y) rows, rows and row pairs: five more than the grid.y of kernel W, W2 and W2 on two rows can hold; such a `tall` row asserts the cap from the plan,
+starts what it overwrites as NaN and compares the rows walked second on their own as well), the upper of two slabs of a 16 x 8 lattice with rows 0, 1, 2.
 """
 import ctypes as C
 import functools
@@ -168,6 +169,12 @@ ROUTES = [
     ('apply_epi', 'c32', (2, 4100), 1, 0b1, 'M0', 'dotsrhs', 2, W22(zero=True, e=1)),
     # ---- rows beyond grid.y = 65535: 65 540 (parity, y) rows that the blocks of kernel W walk
     ('apply', 'c64', (2, 32770), 1, 0b1, 'M0', 'tall', 0, W(1, zero=True)),
+    # ---- ... 65 540 rows y that the blocks of kernel W2 walk (both parities of a row per block), alone and as a batch with a masked system
+    ('apply', 'c64', (2, 65540), 1, 0b1, 'M0', 'tall', 1, W2(zero=True)),
+    ('apply', 'c64', (2, 65540), 3, 0b101, 'M+', 'tall', 2, W2(batch=True)),
+    # ---- ... 65 540 row pairs (2 yi, 2 yi + 1) that the blocks of the two-row form walk
+    ('apply', 'c64', (2, 131080), 1, 0b1, 'M0', 'tall', 2, W22(zero=True)),
+    ('apply', 'c32', (2, 131080), 1, 0b1, 'M0', 'tall', 2, W22(zero=True)),
     # ---- y-slabs: rows 4 .. 7 of a 16 x 8 lattice, the links indexed on the whole lattice, rows -1 and Ly of the right-hand side from halos
     ('apply', 'c64', (16, 4), 1, 0b1, 'M0', 'slab0', 2, W22(zero=True)),
     ('apply', 'c64', (16, 4), 1, 0b1, 'M0', 'slab1', 2, W22(zero=True)),        # the interior: a row pair that starts at the odd row 1
@@ -303,6 +310,26 @@ def test_route_against_numpy_reference(row):
         qmg.set_tuning("wilson_pair", 2)
 
 
+def walked_second(plan, Lx, Ly):
+    """asserts from the plan that grid.y is capped below the rows the blocks walk, and returns the mask over one vector of the rows reached on
+    a second trip: rows gy .. of the kernel's own numbering -- kernel W: row = 2 y + parity on both parities; W2: y; W2 on two rows: the pair
+    (2 row, 2 row + 1)"""
+    family, gy, par_first, par_count = plan[0], plan[4], plan[14], plan[15]
+    walked = {qmg.WF_DIRECT: Ly * par_count, qmg.WF_PAIR: Ly, qmg.WF_PAIR2: Ly // 2}[family]
+    assert gy == 65535 < walked == 65540, plan
+    m = np.zeros((2, Ly, Lx), dtype=bool)
+    for r in range(gy, walked):
+        if family == qmg.WF_PAIR2:
+            m[:, 2 * r:2 * r + 2] = True
+        elif family == qmg.WF_PAIR:
+            m[:, r] = True
+        elif par_count == 2:
+            m[r & 1, r >> 1] = True
+        else:
+            m[par_first, r] = True
+    return m.reshape(-1)
+
+
 def check_route(row):
     entry, storage, dims, nrhs, mask, pieces, flags, pair, plan = row
     got_plan = planned(row)
@@ -318,8 +345,9 @@ def check_route(row):
     served = plan[0] in SERVED
     if served:
         assert got_plan[8] == len(act) and got_plan[13] == 0
-    if "tall" in fl:
-        assert got_plan[4] == 65535         # blocks walk the rows beyond grid.y
+    second = None
+    if "tall" in fl:                        # blocks walk the rows beyond grid.y
+        second = walked_second(got_plan, Lx, Ly)
     if served and got_plan[5] & qmg.WPF_DOTS and Ly > 4096:
         assert got_plan[3] * got_plan[4] == 2048     # the dots cap: fewer blocks than rows
     rnd = r32 if f32 else (lambda a: a)
@@ -350,9 +378,15 @@ def check_route(row):
         lo, hi = (qmg.DeviceArray.from_host(np.ascontiguousarray(halo(y), dtype=vdtype)) for y in (y0 - 1, y0 + Ly))
     dev = lambda a: qmg.DeviceArray.from_host(np.ascontiguousarray(a, dtype=vdtype))
     dots = {}
+    start = lhs0
+    if second is not None and plan[2]:      # ZERO: every processed parity is overwritten and never read, so it starts as NaN
+        start = lhs0.copy()
+        for k in act:
+            for p in range(got_plan[14], got_plan[14] + got_plan[15]):
+                start[k * stride + p * (size // 2):k * stride + (p + 1) * (size // 2)] = np.nan
 
     def run():
-        dl = dev(lhs0)
+        dl = dev(start)
         dr = dl if inplace else dev(rhs0)
         epi = None
         if entry.endswith("_epi"):
@@ -365,7 +399,7 @@ def check_route(row):
         return status, dl.to_host()
 
     status, raw = run()
-    init = np.ascontiguousarray(lhs0, dtype=vdtype)
+    init = np.ascontiguousarray(start, dtype=vdtype)
     if not served:
         assert status == STATUS[plan[0]] == got_plan[13]
         assert raw.tobytes() == init.tobytes()
@@ -395,6 +429,12 @@ def check_route(row):
         if not f32:
             bound = sn.elementwise_bound(S_, n)[done]
             assert np.all(err <= bound), (k, float(np.max(err / bound)))
+        if second is not None:      # the rows walked second, on their own
+            assert np.all(np.isfinite(raw[seg])), (k, "NaN prefill survived", int(np.count_nonzero(~np.isfinite(raw[seg][second]))), "of them on the second trip")
+            err2 = np.abs(got[seg].astype(sn.CLD) - want)[done & second]
+            l2 = float(np.linalg.norm(err2) / float(np.linalg.norm(want[done & second])))
+            assert np.count_nonzero(done & second) > 0 and l2 < (TOL32 if f32 else TOL64), (k, "second trip", l2)
+            assert f32 or np.all(err2 <= sn.elementwise_bound(S_, n)[done & second]), (k, "second trip")
         if "last" in dots:     # (Re <p, r>, Im <p, r>, <p, p>), p = out as stored, r = dotv, over the processed parities
             p_, r_ = got[seg].astype(sn.CLD)[done], dot_vec[seg].astype(sn.CLD)[done]
             pr, pp = np.vdot(p_, r_), np.vdot(p_, p_).real

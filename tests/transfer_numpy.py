@@ -29,10 +29,18 @@ def _to_eo(psi, Lx, Ly, nc):
     return psi.reshape(-1)[perm]
 
 
+_LAST = []   # the grids of the null vectors last asked for: a batch row asks once per system with the same array
+
+
 def _null_grid(nullvecs, nvec, fdims):
+    """(null, conj(null), |null|) as [d, x, y, c] grids"""
+    if _LAST and _LAST[0] is nullvecs and _LAST[1] == (nvec, fdims):
+        return _LAST[2]
     fLx, fLy, fnc = fdims
     fsize = fLx * fLy * fnc
-    return np.stack([_to_grid(nullvecs[d * fsize:(d + 1) * fsize], fLx, fLy, fnc) for d in range(nvec)])   # [d, x, y, c]
+    N = np.stack([_to_grid(nullvecs[d * fsize:(d + 1) * fsize], fLx, fLy, fnc) for d in range(nvec)])
+    _LAST[:] = [nullvecs, (nvec, fdims), (N, np.conj(N), np.abs(N))]
+    return _LAST[2]
 
 
 def restrict(nullvecs, fine, fdims, cdims, coarse0):
@@ -40,11 +48,11 @@ def restrict(nullvecs, fine, fdims, cdims, coarse0):
     fLx, fLy, fnc = fdims
     cLx, cLy, nvec = cdims
     bx, by = fLx // cLx, fLy // cLy
-    N = _null_grid(nullvecs, nvec, fdims).reshape(nvec, cLx, bx, cLy, by, fnc)
+    _, Nc, Na = (a.reshape(nvec, cLx, bx, cLy, by, fnc) for a in _null_grid(nullvecs, nvec, fdims))
     F = _to_grid(fine, fLx, fLy, fnc).reshape(cLx, bx, cLy, by, fnc)
     C0 = _to_grid(coarse0, cLx, cLy, nvec)
-    out = C0 + np.einsum("dxiyjc,xiyjc->xyd", np.conj(N), F)
-    S = np.abs(C0) + np.einsum("dxiyjc,xiyjc->xyd", np.abs(N), np.abs(F))
+    out = C0 + np.einsum("dxiyjc,xiyjc->xyd", Nc, F)
+    S = np.abs(C0) + np.einsum("dxiyjc,xiyjc->xyd", Na, np.abs(F))
     return _to_eo(out, cLx, cLy, nvec), _to_eo(S, cLx, cLy, nvec)
 
 
@@ -53,11 +61,11 @@ def prolong(nullvecs, coarse, fdims, cdims, fine0):
     fLx, fLy, fnc = fdims
     cLx, cLy, nvec = cdims
     bx, by = fLx // cLx, fLy // cLy
-    N = _null_grid(nullvecs, nvec, fdims)
+    N, _, Na = _null_grid(nullvecs, nvec, fdims)
     C = np.repeat(np.repeat(_to_grid(coarse, cLx, cLy, nvec), bx, axis=0), by, axis=1)   # coarse[x // bx, y // by, d] on the fine grid
     F0 = _to_grid(fine0, fLx, fLy, fnc)
     out = F0 + np.einsum("dxyc,xyd->xyc", N, C)
-    S = np.abs(F0) + np.einsum("dxyc,xyd->xyc", np.abs(N), np.abs(C))
+    S = np.abs(F0) + np.einsum("dxyc,xyd->xyc", Na, np.abs(C))
     return _to_eo(out, fLx, fLy, fnc), _to_eo(S, fLx, fLy, fnc)
 
 
