@@ -18,12 +18,90 @@
 // batch of one; only Richardson is single-vector code.  Every type and function of the batch layer is a template on the
 // storage scalar T of the vectors (double | float); all scalars, inner products and convergence decisions stay fp64.
 // The operators, the K-cycle and the mixed-precision preconditioner of a batch are in batch.hpp.
+//
+// THE PER-SYSTEM RULES are stated once, in qmg::SolveLedger (host arithmetic, below); a core holds its algorithm and asks the ledger.
+//   * |b_k| = 0: A x = 0 has the solution x = 0 whatever the guess was, so x_k is zeroed (one bzero), the system reports success at
+//     iter 0 with resSq 0 and ops_count 0, and it is in no mask that reaches an apply, the opening residual included.
+//   * Opening: r = b - A x costs one counted apply per system; under zero_guess the caller has zeroed phi, r0 = b and nothing is applied.
+//     A system whose opening |r| < eps_k |b| has converged at its guess and never becomes active; max_iter <= 0 makes none active.
+//   * ops_count: every apply handed to a mask counts once for each system of that mask.
+//   * The active mask: a bit leaves on convergence (sqrt(rsq) < eps_k |b|, success), on breakdown (a zero denominator: no success, iter as
+//     it stood) or at the cap (iter >= max_iter, no success), and never returns.  Frozen systems are neither read nor written.
+//   * MR and GCR carry |r|^2 as a recurrence, rsq -= delta, which loses absolute accuracy ~1e-16 rsq_ref: a true norm re-anchors it
+//     (rsq = rsq_ref = |r|^2) after every 8 orders of magnitude and whenever it announces sqrt(rsq) < c eps_k |b| (MR c = 4, GCR c = 1: a
+//     convergence is always confirmed by a true norm).  GCR restarts (a counted true residual) BEFORE it looks at the cap; CG opens every
+//     cycle like a solve, from the true residual of the current x; BiCGStab(L) takes a true norm at the end of each L-block.
+//   * eps_k is eps, or eps_per_system[k] where a core takes it (GCR, CG).  Closing: (success, iter, resSq, ops_count) per system; a
+//     system outside `mask` keeps inversion_info's defaults; the closing line's RelTol is sqrt(resSq) / |b|, 0 when |b| = 0.
 #ifndef QMG_KRYLOV_HPP
 #define QMG_KRYLOV_HPP
 
 #include <cmath>
+#include <complex>
+#include <string>
+#include <vector>
 
 namespace qmg {
+
+inline unsigned full_mask(int nrhs) { return (nrhs >= 32) ? 0xFFFFFFFFu : ((1u << nrhs) - 1u); }
+inline bool is_active(unsigned mask, int k) { return (mask >> k) & 1u; }
+
+// The book-keeping of one lock-step solve: which systems run, stop, re-anchor and report (the rules of the header comment).  Host arithmetic
+// only, like cgm_coefficients below: tests/host/krylov_ledger_host.cpp drives it with QMG_KRYLOV_HOST_ONLY and no device code.
+struct SolveLedger {
+  int nrhs, max_iter;
+  unsigned mask, zero_b, run, act;   // the caller's systems; those with b = 0; those that take an opening residual; those still iterating
+  std::vector<double> bsq, bnorm, rsq, rsq_ref, eps;
+  std::vector<int> its, ops;
+  std::vector<bool> conv;
+  struct Row { bool success; int iter; double resSq; int ops_count; };
+  SolveLedger(const std::vector<double>& bsq_, unsigned mask_, int max_iter_, double eps_, const std::vector<double>* eps_per_system = 0)
+      : nrhs((int)bsq_.size()), max_iter(max_iter_), mask(mask_), zero_b(0), act(0), bsq(bsq_), bnorm(nrhs, 0.0), eps(nrhs, eps_), its(nrhs, 0), ops(nrhs, 0),
+        conv(nrhs, false) {
+    if (eps_per_system) eps = *eps_per_system;
+    for (int k = 0; k < nrhs; k++) {
+      if (!is_active(mask, k)) bsq[k] = 0.0;
+      bnorm[k] = std::sqrt(bsq[k]);
+      if (is_active(mask, k) && bsq[k] == 0.0) { zero_b |= 1u << k; conv[k] = true; }
+    }
+    run = mask & ~zero_b;
+    rsq = rsq_ref = bsq;
+  }
+  bool below(int k, double c) const { return std::sqrt(rsq[k]) < c * eps[k] * bnorm[k]; }
+  // the systems of m open (a solve, or a CG cycle) with |r_k|^2 = r0[k]; returns the active mask
+  unsigned open(unsigned m, const std::vector<double>& r0) {
+    act = 0;
+    for (int k = 0; k < nrhs; k++) {
+      if (!is_active(m, k)) continue;
+      anchor(k, r0[k]);
+      conv[k] = below(k, 1.0);
+      if (!conv[k] && max_iter > 0) act |= 1u << k;
+    }
+    return act;
+  }
+  void count(unsigned m) { for (int k = 0; k < nrhs; k++) if (is_active(m, k)) ops[k]++; }
+  // rsq -= delta; true when the recurrence wants a true norm (anchor)
+  bool recur(int k, double delta, double c) { rsq[k] -= delta; return !(rsq[k] > 1e-8 * rsq_ref[k]) || below(k, c); }
+  void anchor(int k, double true_rsq) { rsq[k] = rsq_ref[k] = true_rsq; }
+  void breakdown(int k) { act &= ~(1u << k); }
+  bool settle(int k) {   // the convergence test on rsq: a converged system is frozen
+    if (below(k, 1.0)) { conv[k] = true; act &= ~(1u << k); }
+    return conv[k];
+  }
+  bool step(int k) { its[k]++; return settle(k); }
+  void cap() { for (int k = 0; k < nrhs; k++) if (is_active(act, k) && its[k] >= max_iter) act &= ~(1u << k); }
+  Row row(int k) const { Row o = {conv[k], its[k], rsq[k], ops[k]}; return o; }
+  double rel(int k) const { return bnorm[k] > 0 ? std::sqrt(rsq[k]) / bnorm[k] : 0.0; }
+};
+
+// GCR with raw search directions: y_j such that sum_k alpha_k z'_k = sum_j y_j z_j, z'_k = z_k + sum_{i<k} c[k][i] z'_i
+inline std::vector<std::complex<double> > gcr_direction_weights(const std::vector<std::complex<double> >& alpha,
+                                                                const std::vector<std::vector<std::complex<double> > >& c, int K) {
+  std::vector<std::complex<double> > beta(alpha.begin(), alpha.begin() + K);
+  for (int k = K - 1; k >= 0; k--)
+    for (int i = 0; i < k; i++) beta[i] += beta[k] * c[k][i];
+  return beta;
+}
 
 // ---------------------------------------------------------------------------------------------
 // The scalar recurrence of multi-shift CG (B. Jegerlehner, hep-lat/9612014), in CG's own notation.  CG on the base system
@@ -61,8 +139,6 @@ inline void cgm_coefficients(int ns, const double* dsigma, unsigned active, doub
 #include <algorithm>
 #include <iostream>
 #include <map>
-#include <string>
-#include <vector>
 
 #include "qmg_device.hpp"
 
@@ -161,14 +237,6 @@ inline void summary(inversion_verbose_struct* verb, const char* name, int nrhs, 
   std::cout << (ok_ ? " Success " : " Fail ") << "Iter " << iter << " RelTol " << rel << "\n";
 }
 
-// GCR with raw search directions: y_j such that sum_k alpha_k z'_k = sum_j y_j z_j, z'_k = z_k + sum_{i<k} c[k][i] z'_i
-inline std::vector<complex<double>> gcr_direction_weights(const std::vector<complex<double>>& alpha, const std::vector<std::vector<complex<double>>>& c, int K) {
-  std::vector<complex<double>> beta(alpha.begin(), alpha.begin() + K);
-  for (int k = K - 1; k >= 0; k--)
-    for (int i = 0; i < k; i++) beta[i] += beta[k] * c[k][i];
-  return beta;
-}
-
 template <typename T> struct dtype_of;
 template <> struct dtype_of<double> { enum { value = QMG_C64 }; };
 template <> struct dtype_of<float> { enum { value = QMG_C32 }; };
@@ -184,9 +252,6 @@ struct BatchT {
   complex<T>* vec(int k) const { return p + (size_t)k * stride; }
 };
 typedef BatchT<double> Batch;
-
-inline unsigned full_mask(int nrhs) { return (nrhs >= 32) ? 0xFFFFFFFFu : ((1u << nrhs) - 1u); }
-inline bool is_active(unsigned mask, int k) { return (mask >> k) & 1u; }
 
 // batch scratch, recycled like VecPool (whose unit is one complex<double>: an fp32 batch takes half as many units)
 template <typename T>
@@ -237,9 +302,9 @@ inline std::vector<double> bdiffnorm2sq(BatchT<T> x, BatchT<T> y, size_t n, unsi
   for (int k = 0; k < x.nrhs; k++) if (is_active(mask, k)) out[k] = raw[2 * k];
   return out;
 }
-// d[k][j] = <xs[j]_k, y_k>
+// d[k][j] = <xs[j]_k, y_k>; xs: nj batches, as an array (a core's fixed one or two: `&p`, `rp`) or a vector (a basis)
 template <typename T>
-inline std::vector<cvec> bmultidot(const std::vector<BatchT<T> >& xs, int nj, BatchT<T> y, size_t n, unsigned mask) {
+inline std::vector<cvec> bmultidot(const BatchT<T>* xs, int nj, BatchT<T> y, size_t n, unsigned mask) {
   std::vector<cvec> out(y.nrhs, cvec(nj, 0.0));
   int done = 0;
   while (done < nj) {   // the ABI takes up to 32 vector sets per call
@@ -255,9 +320,11 @@ inline std::vector<cvec> bmultidot(const std::vector<BatchT<T> >& xs, int nj, Ba
   }
   return out;
 }
+template <typename T>
+inline std::vector<cvec> bmultidot(const std::vector<BatchT<T> >& xs, int nj, BatchT<T> y, size_t n, unsigned mask) { return bmultidot(xs.data(), nj, y, n, mask); }
 // y_k += sum_j c[k][j] xs[j]_k
 template <typename T>
-inline void bmulti_caxpy(const std::vector<cvec>& c, const std::vector<BatchT<T> >& xs, int nj, BatchT<T> y, size_t n, unsigned mask) {
+inline void bmulti_caxpy(const std::vector<cvec>& c, const BatchT<T>* xs, int nj, BatchT<T> y, size_t n, unsigned mask) {
   if (nj <= 0) return;
   std::vector<double> cf((size_t)2 * nj * y.nrhs, 0.0);
   std::vector<const void*> ptrs(nj);
@@ -267,6 +334,8 @@ inline void bmulti_caxpy(const std::vector<cvec>& c, const std::vector<BatchT<T>
   }
   ok(qmg_batch_multi_caxpy_t(dtype_of<T>::value, cf.data(), ptrs.data(), nj, y.p, n, y.nrhs, y.stride, mask, current_stream()), "qmg_batch_multi_caxpy");
 }
+template <typename T>
+inline void bmulti_caxpy(const std::vector<cvec>& c, const std::vector<BatchT<T> >& xs, int nj, BatchT<T> y, size_t n, unsigned mask) { bmulti_caxpy(c, xs.data(), nj, y, n, mask); }
 // one flexible-GCR iteration's vector updates in one pass: w_k += sum_j c[k][j] Ws[j]_k ; r_k += a[k] w_k ; z_next_k = r_k (z_next.p != 0)
 template <typename T>
 inline void bgcr_update(const std::vector<cvec>& c, const std::vector<BatchT<T> >& Ws, int nj, BatchT<T> w, const cvec& a, BatchT<T> r, BatchT<T> z_next, size_t n, unsigned mask) {
@@ -299,22 +368,37 @@ namespace qmg {
 // r = b - A x for the active systems (tmp: scratch for A x), one counted operator application each; returns |r_k|^2
 template <typename T>
 inline std::vector<double> bresidual(BatchT<T> r, BatchT<T> x, BatchT<T> b, BatchT<T> tmp, int size, batch_matrix_op_t<T> matrix_vector, void* extra_info,
-                                     unsigned mask, std::vector<int>& ops) {
+                                     unsigned mask, SolveLedger& led) {
   matrix_vector(tmp, x, mask, extra_info);
-  for (int k = 0; k < x.nrhs; k++) if (is_active(mask, k)) ops[k]++;
+  led.count(mask);
   bxmyz(b, tmp, r, size, mask);
   return bnorm2sq(r, size, mask);
 }
 
-// The systems of `mask` whose right-hand side is identically zero.  A x = 0 has the solution x = 0 whatever the initial guess was, so every
-// core sets x_k = 0 for them (one bzero), reports success at iteration 0 with resSq 0, and keeps them out of every apply, the opening
-// residual included (ops_count 0).  (Before, such a system was reported converged with its initial guess left in x.)
+// the ledger of a solve of A phi = phi0 from its |b_k|^2, with x_k = 0 written for the systems whose right-hand side is zero
 template <typename T>
-inline unsigned zero_rhs_systems(BatchT<T> phi, const std::vector<double>& bsq, size_t n, unsigned mask) {
-  unsigned zb = 0;
-  for (int k = 0; k < phi.nrhs; k++) if (is_active(mask, k) && bsq[k] == 0.0) zb |= 1u << k;
-  if (zb) bzero(phi, n, zb);
-  return zb;
+inline SolveLedger open_ledger(BatchT<T> phi, BatchT<T> phi0, size_t n, unsigned mask, int max_iter, double eps, const std::vector<double>* eps_per_system = 0) {
+  const SolveLedger led(bnorm2sq(phi0, n, mask), mask, max_iter, eps, eps_per_system);
+  if (led.zero_b) bzero(phi, n, led.zero_b);
+  return led;
+}
+// the systems of m open a solve (or a CG cycle): r = b under zero_guess, else r = b - A x (tmp: scratch); returns the active mask
+template <typename T>
+inline unsigned bopen(SolveLedger& led, unsigned m, BatchT<T> r, BatchT<T> x, BatchT<T> b, BatchT<T> tmp, int size, batch_matrix_op_t<T> matrix_vector,
+                      void* extra_info, bool zero_guess) {
+  if (!zero_guess) return led.open(m, bresidual(r, x, b, tmp, size, matrix_vector, extra_info, m, led));
+  bcopy(r, b, size, m);
+  return led.open(m, led.bsq);
+}
+// the closing line of every system of the mask, and the ledger's rows as inversion_info
+inline std::vector<inversion_info> close_ledger(const SolveLedger& led, inversion_verbose_struct* verb, const char* name) {
+  std::vector<inversion_info> inv(led.nrhs);
+  for (int k = 0; k < led.nrhs; k++) {
+    const SolveLedger::Row o = led.row(k);
+    inv[k].success = o.success; inv[k].iter = o.iter; inv[k].resSq = o.resSq; inv[k].ops_count = o.ops_count; inv[k].name = name;
+    if (is_active(led.mask, k)) summary(verb, name, led.nrhs, k, o.success, o.iter, led.rel(k));
+  }
+  return inv;
 }
 
 // a single-vector operator / preconditioner (the reference's callback types) as the operator of a batch of one system
@@ -331,115 +415,78 @@ inline inversion_info renamed(inversion_info inv, const std::string& name) { inv
 
 // ---------------------------------------------------------------------------------------------
 // MR(omega) (minv_vector_minres):  r = b - A x ; repeat: p = A r ; alpha = omega <p,r>/<p,p> ; x += alpha r ; r -= alpha p.
-// zero_guess: the caller has zeroed phi, r0 = b (no apply).  `name` labels the printed lines (and inversion_info::name).
+// `name` labels the printed lines (and inversion_info::name).  The recurrence re-anchors below 4 eps |b|.
 // ---------------------------------------------------------------------------------------------
 template <typename T>
 inline std::vector<inversion_info> bmr_core(qmg::BatchT<T> phi, qmg::BatchT<T> phi0, int size, int max_iter, double eps, double omega,
                                             batch_matrix_op_t<T> matrix_vector, void* extra_info, unsigned mask, bool zero_guess,
                                             inversion_verbose_struct* verb = 0, const char* name = "MinRes") {
   const int nrhs = phi.nrhs;
-  std::vector<inversion_info> inv(nrhs);
   qmg::BatchPoolT<T> pool(phi.stride, nrhs);
   qmg::BatchT<T> r = pool.get(), p = pool.get();
-  const std::vector<double> bsq = qmg::bnorm2sq(phi0, size, mask);
-  std::vector<int> its(nrhs, 0), ops(nrhs, 0);
-  std::vector<double> rsq = bsq;
-  const unsigned run = mask & ~qmg::zero_rhs_systems(phi, bsq, size, mask);   // (a zero right-hand side: x = 0, done)
-  if (zero_guess) qmg::bcopy(r, phi0, size, run);
-  else rsq = qmg::bresidual(r, phi, phi0, p, size, matrix_vector, extra_info, run, ops);
-  std::vector<double> rsq_ref = rsq, bnorm(nrhs);
-  std::vector<bool> conv(nrhs, false);
-  unsigned act = 0;
-  for (int k = 0; k < nrhs; k++) {
-    bnorm[k] = std::sqrt(bsq[k]);
-    if (!qmg::is_active(mask, k)) continue;
-    conv[k] = (bnorm[k] == 0.0) || (std::sqrt(rsq[k]) < eps * bnorm[k]);
-    if (!conv[k] && max_iter > 0) act |= 1u << k;
-  }
-  std::vector<qmg::BatchT<T> > rp(2);
-  rp[0] = r; rp[1] = p;
-  while (act) {
-    matrix_vector(p, r, act, extra_info);
+  qmg::SolveLedger led = qmg::open_ledger(phi, phi0, size, mask, max_iter, eps);
+  qmg::bopen(led, led.run, r, phi, phi0, p, size, matrix_vector, extra_info, zero_guess);
+  const qmg::BatchT<T> rp[2] = {r, p};
+  while (led.act) {
+    matrix_vector(p, r, led.act, extra_info);
+    led.count(led.act);
     // <r,p> and <p,p> in one pass over p; the new residual norm follows analytically:
     // |r - a p|^2 = |r|^2 - (2 omega - omega^2) |<p,r>|^2 / <p,p>   for a = omega <p,r>/<p,p>
-    const std::vector<qmg::cvec> d2 = qmg::bmultidot(rp, 2, p, size, act);
+    const std::vector<qmg::cvec> d2 = qmg::bmultidot(rp, 2, p, size, led.act);
     qmg::cvec alpha(nrhs, 0.0), malpha(nrhs, 0.0);
     unsigned upd = 0, renorm = 0;
     for (int k = 0; k < nrhs; k++) {
-      if (!qmg::is_active(act, k)) continue;
-      ops[k]++;
+      if (!qmg::is_active(led.act, k)) continue;
       const complex<double> pr = std::conj(d2[k][0]);
       const double pp = d2[k][1].real();
-      if (pp == 0.0) { act &= ~(1u << k); continue; }   // breakdown: this system stops
+      if (pp == 0.0) { led.breakdown(k); continue; }
       alpha[k] = omega * pr / pp; malpha[k] = -alpha[k];
       upd |= 1u << k;
-      // (the subtraction loses absolute accuracy ~1e-16 * rsq_ref: re-anchor with a true norm after every 8 orders of magnitude)
-      rsq[k] = rsq[k] - (2.0 * omega - omega * omega) * std::norm(pr) / pp;
-      if (!(rsq[k] > 1e-8 * rsq_ref[k]) || std::sqrt(rsq[k]) < 4.0 * eps * bnorm[k]) renorm |= 1u << k;
+      if (led.recur(k, (2.0 * omega - omega * omega) * std::norm(pr) / pp, 4.0)) renorm |= 1u << k;
     }
     qmg::bcaxpy(alpha, r, phi, size, upd);
     // r is only needed by a further iteration or by a true-norm re-anchoring: the residual update of a system's LAST
     // iteration is skipped (callers that want the residual recompute b - A x, as the K-cycle does); x and the returned |r|^2 are unaffected
     unsigned need_r = renorm;
-    for (int k = 0; k < nrhs; k++) if (qmg::is_active(upd, k) && its[k] + 1 < max_iter) need_r |= 1u << k;
+    for (int k = 0; k < nrhs; k++) if (qmg::is_active(upd, k) && led.its[k] + 1 < max_iter) need_r |= 1u << k;
     qmg::bcaxpy(malpha, p, r, size, upd & need_r);
     if (renorm) {
       const std::vector<double> t = qmg::bnorm2sq(r, size, renorm);
-      for (int k = 0; k < nrhs; k++) if (qmg::is_active(renorm, k)) { rsq[k] = t[k]; rsq_ref[k] = t[k]; }
+      for (int k = 0; k < nrhs; k++) if (qmg::is_active(renorm, k)) led.anchor(k, t[k]);
     }
     for (int k = 0; k < nrhs; k++) {
       if (!qmg::is_active(upd, k)) continue;
-      its[k]++;
-      qmg::report(verb, name, nrhs, k, its[k], std::sqrt(rsq[k]) / bnorm[k]);
-      if (std::sqrt(rsq[k]) < eps * bnorm[k]) { conv[k] = true; act &= ~(1u << k); }
-      else if (its[k] >= max_iter) act &= ~(1u << k);
+      led.step(k);
+      qmg::report(verb, name, nrhs, k, led.its[k], led.rel(k));
     }
+    led.cap();
   }
-  for (int k = 0; k < nrhs; k++) {
-    inv[k].success = conv[k]; inv[k].iter = its[k]; inv[k].resSq = rsq[k]; inv[k].ops_count = ops[k]; inv[k].name = name;
-    if (qmg::is_active(mask, k)) qmg::summary(verb, name, nrhs, k, conv[k], its[k], bnorm[k] > 0 ? std::sqrt(rsq[k]) / bnorm[k] : 0.0);
-  }
-  return inv;
+  return qmg::close_ledger(led, verb, name);
 }
 
 // ---------------------------------------------------------------------------------------------
 // BiCGStab(L) (Sleijpen & Fokkema 1993; minv_vector_bicgstab_l): the null-vector relaxation of tests/n13_wilson_kcycle/wilson_kcycle.cpp:359
-// and the fine-level solver of the slab drivers.  `iter` counts BiCG steps per system; a system that converges, breaks down or
-// reaches max_iter is frozen at the end of its L-block.  The closing updates of a block go through one multi-vector pass each.
-// zero_guess: the caller has zeroed phi, r0 = b (no apply).
+// and the fine-level solver of the slab drivers.  `iter` counts BiCG steps per system; convergence and the cap are looked at
+// at the end of an L-block.  The closing updates of a block go through one multi-vector pass each.
 // ---------------------------------------------------------------------------------------------
 template <typename T>
 inline std::vector<inversion_info> bbicgstab_l_core(qmg::BatchT<T> phi, qmg::BatchT<T> phi0, int size, int max_iter, double eps, int L,
                                                     batch_matrix_op_t<T> matrix_vector, void* extra_info, unsigned mask, bool zero_guess,
                                                     inversion_verbose_struct* verb = 0, const char* name = "BiCGStab-L") {
   const int nrhs = phi.nrhs;
-  std::vector<inversion_info> inv(nrhs);
   qmg::BatchPoolT<T> pool(phi.stride, nrhs);
   std::vector<qmg::BatchT<T> > r(L + 1), u(L + 1);
   for (int i = 0; i <= L; i++) { r[i] = pool.get(); u[i] = pool.get(); }
   qmg::BatchT<T> rt = pool.get();
-  const std::vector<double> bsq = qmg::bnorm2sq(phi0, size, mask);
-  std::vector<int> its(nrhs, 0), ops(nrhs, 0);
-  std::vector<double> rsq = bsq, bnorm(nrhs, 0.0);
-  const unsigned run = mask & ~qmg::zero_rhs_systems(phi, bsq, size, mask);   // (a zero right-hand side: x = 0, done)
-  if (zero_guess) qmg::bcopy(r[0], phi0, size, run);
-  else rsq = qmg::bresidual(r[0], phi, phi0, u[0], size, matrix_vector, extra_info, run, ops);
-  qmg::bcopy(rt, r[0], size, run);
-  qmg::bzero(u[0], size, run);
-  std::vector<bool> conv(nrhs, false);
+  qmg::SolveLedger led = qmg::open_ledger(phi, phi0, size, mask, max_iter, eps);
+  const unsigned& act = led.act;
+  qmg::bopen(led, led.run, r[0], phi, phi0, u[0], size, matrix_vector, extra_info, zero_guess);
+  qmg::bcopy(rt, r[0], size, led.run);
+  qmg::bzero(u[0], size, led.run);
   qmg::cvec rho0(nrhs, 1.0), alpha(nrhs, 0.0), omega(nrhs, 1.0);
-  unsigned act = 0;
-  for (int k = 0; k < nrhs; k++) {
-    bnorm[k] = std::sqrt(bsq[k]);
-    if (!qmg::is_active(mask, k)) continue;
-    conv[k] = (bnorm[k] == 0.0) || (std::sqrt(rsq[k]) < eps * bnorm[k]);
-    if (!conv[k] && max_iter > 0) act |= 1u << k;
-  }
   const qmg::cvec one(nrhs, 1.0);
-  std::vector<qmg::BatchT<T> > single(1);
   auto bdot1 = [&](qmg::BatchT<T> a, qmg::BatchT<T> b, unsigned m) {   // <a_k, b_k> per system
-    single[0] = a;
-    const std::vector<qmg::cvec> d = qmg::bmultidot(single, 1, b, size, m);
+    const std::vector<qmg::cvec> d = qmg::bmultidot(&a, 1, b, size, m);
     qmg::cvec out(nrhs, 0.0);
     for (int k = 0; k < nrhs; k++) out[k] = d[k][0];
     return out;
@@ -454,27 +501,28 @@ inline std::vector<inversion_info> bbicgstab_l_core(qmg::BatchT<T> phi, qmg::Bat
       qmg::cvec mbeta(nrhs, 0.0);
       for (int k = 0; k < nrhs; k++) {
         if (!qmg::is_active(act, k)) continue;
-        if (rho0[k] == 0.0) { act &= ~(1u << k); continue; }                 // breakdown: this system stops
+        if (rho0[k] == 0.0) { led.breakdown(k); continue; }
         mbeta[k] = -(alpha[k] * rho1[k] / rho0[k]);
         rho0[k] = rho1[k];
       }
       if (!act) break;
       for (int i = 0; i <= j; i++) qmg::bcaxpbyz(one, r[i], mbeta, u[i], u[i], size, act);   // u_i = r_i - beta u_i
       matrix_vector(u[j + 1], u[j], act, extra_info);
+      led.count(act);
       const qmg::cvec gam = bdot1(rt, u[j + 1], act);
       qmg::cvec malpha(nrhs, 0.0);
       for (int k = 0; k < nrhs; k++) {
         if (!qmg::is_active(act, k)) continue;
-        ops[k]++;
-        if (gam[k] == 0.0) { act &= ~(1u << k); continue; }
+        if (gam[k] == 0.0) { led.breakdown(k); continue; }
         alpha[k] = rho0[k] / gam[k];
         malpha[k] = -alpha[k];
       }
       if (!act) break;
       for (int i = 0; i <= j; i++) qmg::bcaxpy(malpha, u[i + 1], r[i], size, act);
       matrix_vector(r[j + 1], r[j], act, extra_info);
+      led.count(act);
       qmg::bcaxpy(alpha, u[0], phi, size, act);
-      for (int k = 0; k < nrhs; k++) if (qmg::is_active(act, k)) { ops[k]++; its[k]++; }
+      for (int k = 0; k < nrhs; k++) if (qmg::is_active(act, k)) led.its[k]++;
     }
     if (!act) break;
     for (int j = 1; j <= L && act; j++) {   // MR part: modified Gram-Schmidt on r_1..r_L
@@ -484,14 +532,13 @@ inline std::vector<inversion_info> bbicgstab_l_core(qmg::BatchT<T> phi, qmg::Bat
         for (int k = 0; k < nrhs; k++) if (qmg::is_active(act, k)) { tau[k][i * (L + 1) + j] = d[k] / sigma[k][i]; mt[k] = -tau[k][i * (L + 1) + j]; }
         qmg::bcaxpy(mt, r[i], r[j], size, act);
       }
-      std::vector<qmg::BatchT<T> > two(2);
-      two[0] = r[j]; two[1] = r[0];
+      const qmg::BatchT<T> two[2] = {r[j], r[0]};
       // <r_j, r_j> and <r_j, r_0> in one pass over r_j: d[k][0] = <r_j, r_j>, d[k][1] = <r_0, r_j> = conj <r_j, r_0>
       const std::vector<qmg::cvec> d = qmg::bmultidot(two, 2, r[j], size, act);
       for (int k = 0; k < nrhs; k++) {
         if (!qmg::is_active(act, k)) continue;
         sigma[k][j] = d[k][0].real();
-        if (sigma[k][j] == 0.0) { act &= ~(1u << k); continue; }
+        if (sigma[k][j] == 0.0) { led.breakdown(k); continue; }
         gammap[k][j] = std::conj(d[k][1]) / sigma[k][j];
       }
     }
@@ -515,24 +562,19 @@ inline std::vector<inversion_info> bbicgstab_l_core(qmg::BatchT<T> phi, qmg::Bat
       for (int j = 1; j < L; j++) cx[k][j] = gpp[j];
       for (int j = 1; j <= L; j++) { cr[k][j - 1] = -gp[j]; cu[k][j - 1] = -g[j]; }
     }
-    std::vector<qmg::BatchT<T> > r0L(r.begin(), r.begin() + L), r1L(r.begin() + 1, r.end()), u1L(u.begin() + 1, u.end());
-    qmg::bmulti_caxpy(cx, r0L, L, phi, size, act);     // reads r_0 before it changes
-    qmg::bmulti_caxpy(cr, r1L, L, r[0], size, act);
-    qmg::bmulti_caxpy(cu, u1L, L, u[0], size, act);
+    qmg::bmulti_caxpy(cx, r.data(), L, phi, size, act);     // r_0..r_{L-1}; reads r_0 before it changes
+    qmg::bmulti_caxpy(cr, r.data() + 1, L, r[0], size, act);
+    qmg::bmulti_caxpy(cu, u.data() + 1, L, u[0], size, act);
     const std::vector<double> t2 = qmg::bnorm2sq(r[0], size, act);
     for (int k = 0; k < nrhs; k++) {
       if (!qmg::is_active(act, k)) continue;
-      rsq[k] = t2[k];
-      qmg::report(verb, name, nrhs, k, its[k], std::sqrt(rsq[k]) / bnorm[k]);
-      if (std::sqrt(rsq[k]) < eps * bnorm[k]) { conv[k] = true; act &= ~(1u << k); }
-      else if (its[k] >= max_iter) act &= ~(1u << k);
+      led.anchor(k, t2[k]);
+      qmg::report(verb, name, nrhs, k, led.its[k], led.rel(k));
+      led.settle(k);
     }
+    led.cap();
   }
-  for (int k = 0; k < nrhs; k++) {
-    inv[k].success = conv[k]; inv[k].iter = its[k]; inv[k].resSq = rsq[k]; inv[k].ops_count = ops[k]; inv[k].name = name;
-    if (qmg::is_active(mask, k)) qmg::summary(verb, name, nrhs, k, conv[k], its[k], bnorm[k] > 0 ? std::sqrt(rsq[k]) / bnorm[k] : 0.0);
-  }
-  return inv;
+  return qmg::close_ledger(led, verb, name);
 }
 
 
@@ -548,7 +590,6 @@ inline std::vector<inversion_info> bbicgstab_l_core(qmg::BatchT<T> phi, qmg::Bat
 // follows from alpha and c by a k x k back-substitution on the host (qmg::gcr_direction_weights): x is only brought
 // up to date at a restart and at exit, by ONE multi-axpy.  All systems of a batch start together, so the basis index kb
 // (and with it the restart points) is common; everything else is per system.
-// zero_guess: the caller has zeroed phi, r0 = b (no apply).
 // ---------------------------------------------------------------------------------------------
 template <typename T>
 inline std::vector<inversion_info> bgcr_core(qmg::BatchT<T> phi, qmg::BatchT<T> phi0, int size, int max_iter, double eps, int restart_freq,
@@ -556,9 +597,6 @@ inline std::vector<inversion_info> bgcr_core(qmg::BatchT<T> phi, qmg::BatchT<T> 
                                              unsigned mask, bool zero_guess, inversion_verbose_struct* verb, const char* name,
                                              const std::vector<double>* eps_per_system = 0) {
   const int nrhs = phi.nrhs;
-  std::vector<inversion_info> inv(nrhs);
-  std::vector<double> epsv(nrhs, eps);   // relative tolerance per system (the K-cycle's inner tolerance depends on the system)
-  if (eps_per_system) epsv = *eps_per_system;
   const int basis_max = (restart_freq > 0) ? restart_freq : max_iter;
   qmg::BatchPoolT<T> pool(phi.stride, nrhs);
   qmg::BatchT<T> r = pool.get(), tmp = pool.get();
@@ -581,26 +619,13 @@ inline std::vector<inversion_info> bgcr_core(qmg::BatchT<T> phi, qmg::BatchT<T> 
     }
     qmg::bmulti_caxpy(y, Z, K, phi, size, m);
   };
-  const std::vector<double> bsq = qmg::bnorm2sq(phi0, size, mask);
-  std::vector<double> rsq(nrhs, 0.0), rsq_ref(nrhs, 0.0), bnorm(nrhs, 0.0);
-  std::vector<int> its(nrhs, 0), ops(nrhs, 0);
-  std::vector<bool> conv(nrhs, false);
-  const unsigned run = mask & ~qmg::zero_rhs_systems(phi, bsq, size, mask);   // (a zero right-hand side: x = 0, done)
-  if (zero_guess) { qmg::bcopy(r, phi0, size, run); rsq = bsq; }
-  else rsq = qmg::bresidual(r, phi, phi0, tmp, size, matrix_vector, extra_info, run, ops);
-  unsigned act = 0;
-  for (int k = 0; k < nrhs; k++) {
-    bnorm[k] = std::sqrt(bsq[k]);
-    rsq_ref[k] = rsq[k];
-    if (!qmg::is_active(mask, k)) continue;
-    conv[k] = (bnorm[k] == 0.0) || (std::sqrt(rsq[k]) < epsv[k] * bnorm[k]);
-    if (!conv[k] && max_iter > 0) act |= 1u << k;
-  }
+  qmg::SolveLedger led = qmg::open_ledger(phi, phi0, size, mask, max_iter, eps, eps_per_system);   // (the K-cycle's inner tolerance depends on the system)
+  const unsigned& act = led.act;
+  qmg::bopen(led, led.run, r, phi, phi0, tmp, size, matrix_vector, extra_info, zero_guess);
   int kb = 0;
   bool z_ready = false;
   inversion_verbose_struct pverb(verb ? verb->precond_verbosity : VERB_NONE, verb ? verb->precond_verb_prefix : std::string(""));
   if (verb) { pverb.precond_verbosity = verb->precond_verbosity; pverb.precond_verb_prefix = verb->precond_verb_prefix; }
-  std::vector<qmg::BatchT<T> > rw(2);
   while (act) {
     if (kb == (int)Z.size()) { Z.push_back(pool.get()); W.push_back(pool.get()); Wnorm2.push_back(std::vector<double>(nrhs, 0.0)); }
     for (int k = 0; k < nrhs; k++) { if ((int)C[k].size() <= kb) { C[k].push_back(qmg::cvec()); alphas[k].push_back(0.0); } }
@@ -613,6 +638,7 @@ inline std::vector<inversion_info> bgcr_core(qmg::BatchT<T> phi, qmg::BatchT<T> 
     else if (!z_ready) qmg::bcopy(z, r, size, act);   // (z_ready: the previous iteration's update pass wrote z = r already)
     z_ready = false;
     matrix_vector(w, z, act, extra_info);
+    led.count(act);
     // ONE reduction pass and one host round trip per iteration: the Gram-Schmidt
     // coefficients c_i = <W_i, w>, <r, w> and <w, w> come from the same pass over the RAW w; for the orthogonalised w' = w - sum_i (c_i / N_i) W_i
     //   <w', w'> = <w, w> - sum_i |c_i|^2 / N_i          (the W_i are orthogonal)
@@ -638,7 +664,7 @@ inline std::vector<inversion_info> bgcr_core(qmg::BatchT<T> phi, qmg::BatchT<T> 
     const bool deferred = explicit_dots == 0;
     if (!deferred && kb > 0) qmg::bmulti_caxpy(c, W, kb, w, size, act);
     if (explicit_dots) {
-      rw[0] = r; rw[1] = w;
+      const qmg::BatchT<T> rw[2] = {r, w};
       const std::vector<qmg::cvec> e2 = qmg::bmultidot(rw, 2, w, size, explicit_dots);
       for (int k = 0; k < nrhs; k++) if (qmg::is_active(explicit_dots, k)) d2[k] = e2[k];
     }
@@ -647,17 +673,15 @@ inline std::vector<inversion_info> bgcr_core(qmg::BatchT<T> phi, qmg::BatchT<T> 
     // the true norm re-anchors the recurrence when it has lost digits and CONFIRMS a convergence the recurrence announces
     for (int k = 0; k < nrhs; k++) {
       if (!qmg::is_active(act, k)) continue;
-      ops[k]++;
       const double ww = d2[k][1].real();
-      if (ww == 0.0) { act &= ~(1u << k); continue; }
+      if (ww == 0.0) { led.breakdown(k); continue; }
       Wnorm2[kb][k] = ww;
       const complex<double> wr = std::conj(d2[k][0]);
       alpha[k] = wr / ww; malpha[k] = -alpha[k];
       alphas[k][kb] = alpha[k];
       used[k] = kb + 1;
       upd |= 1u << k;
-      rsq[k] = rsq[k] - std::norm(wr) / ww;
-      if (!(rsq[k] > 1e-8 * rsq_ref[k]) || std::sqrt(rsq[k]) < epsv[k] * bnorm[k]) renorm |= 1u << k;
+      if (led.recur(k, std::norm(wr) / ww, 1.0)) renorm |= 1u << k;
     }
     if (deferred) {
       qmg::BatchT<T> z_next;
@@ -670,103 +694,78 @@ inline std::vector<inversion_info> bgcr_core(qmg::BatchT<T> phi, qmg::BatchT<T> 
     } else qmg::bcaxpy(malpha, w, r, size, upd);
     if (renorm) {
       const std::vector<double> t = qmg::bnorm2sq(r, size, renorm);
-      for (int k = 0; k < nrhs; k++) if (qmg::is_active(renorm, k)) { rsq[k] = t[k]; rsq_ref[k] = t[k]; }
+      for (int k = 0; k < nrhs; k++) if (qmg::is_active(renorm, k)) led.anchor(k, t[k]);
     }
     kb++;
     for (int k = 0; k < nrhs; k++) {
       if (!qmg::is_active(upd, k)) continue;
-      its[k]++;
-      qmg::report(verb, name, nrhs, k, its[k], std::sqrt(rsq[k]) / bnorm[k]);
-      if (std::sqrt(rsq[k]) < epsv[k] * bnorm[k]) { conv[k] = true; act &= ~(1u << k); }
+      led.step(k);
+      qmg::report(verb, name, nrhs, k, led.its[k], led.rel(k));
     }
     if (kb == basis_max) flush_x();   // the basis is about to be reused: bring every pending x up to date (frozen systems too)
     if (act && kb == basis_max) {   // restart: true residual, drop the basis (before the iteration cap)
-      const std::vector<double> t = qmg::bresidual(r, phi, phi0, tmp, size, matrix_vector, extra_info, act, ops);
+      const std::vector<double> t = qmg::bresidual(r, phi, phi0, tmp, size, matrix_vector, extra_info, act, led);
       kb = 0;
       z_ready = false;
       for (int k = 0; k < nrhs; k++) {
         if (!qmg::is_active(act, k)) continue;
-        rsq[k] = t[k]; rsq_ref[k] = t[k];
+        led.anchor(k, t[k]);
         if (verb && verb->verbosity >= VERB_RESTART_DETAIL) {
           std::cout << verb->verb_prefix << name;
           if (nrhs > 1) std::cout << " rhs " << k;
-          std::cout << " restart at iter " << its[k] << " RelTol " << std::sqrt(rsq[k]) / bnorm[k] << "\n";
+          std::cout << " restart at iter " << led.its[k] << " RelTol " << led.rel(k) << "\n";
         }
-        if (std::sqrt(rsq[k]) < epsv[k] * bnorm[k]) { conv[k] = true; act &= ~(1u << k); }
+        led.settle(k);
       }
     }
-    for (int k = 0; k < nrhs; k++) if (qmg::is_active(act, k) && its[k] >= max_iter) act &= ~(1u << k);
+    led.cap();
   }
   flush_x();
-  for (int k = 0; k < nrhs; k++) {
-    inv[k].success = conv[k]; inv[k].iter = its[k]; inv[k].resSq = rsq[k]; inv[k].ops_count = ops[k]; inv[k].name = name;
-    if (qmg::is_active(mask, k)) qmg::summary(verb, name, nrhs, k, conv[k], its[k], bnorm[k] > 0 ? std::sqrt(rsq[k]) / bnorm[k] : 0.0);
-  }
-  return inv;
+  return qmg::close_ledger(led, verb, name);
 }
 
 // ---------------------------------------------------------------------------------------------
 // CG with restarts (minv_vector_cg, minv_vector_cg_restart; Hermitian positive definite operators: the coarsest solve on a
-// normal-equation operator, stateful_multigrid.h:930-960).  Each cycle starts from the true residual of the current x and runs
-// at most restart_freq iterations; every active system starts each cycle together; a system that converges, breaks down
-// (<p, A p> == 0), completes a cycle without an iteration or reaches max_iter is frozen.  restart_freq <= 0: one cycle of
-// max_iter iterations.  zero_guess: the caller has zeroed phi, the first cycle's r0 = b (no apply).
+// normal-equation operator, stateful_multigrid.h:930-960).  Each cycle opens like a solve and runs at most restart_freq iterations;
+// every live system starts each cycle together; a system that converges, completes a cycle without an iteration (a breakdown,
+// <p, A p> == 0, at its first step) or reaches max_iter starts no other.  restart_freq <= 0: one cycle of max_iter iterations.
+// zero_guess holds for the first cycle only.  The iteration lines carry the label "CG" whatever `name` is.
 // ---------------------------------------------------------------------------------------------
 template <typename T>
 inline std::vector<inversion_info> bcg_core(qmg::BatchT<T> phi, qmg::BatchT<T> phi0, int size, int max_iter, double eps, int restart_freq,
                                             batch_matrix_op_t<T> matrix_vector, void* extra_info, unsigned mask, bool zero_guess,
                                             inversion_verbose_struct* verb, const char* name, const std::vector<double>* eps_per_system = 0) {
   const int nrhs = phi.nrhs;
-  std::vector<inversion_info> inv(nrhs);
-  std::vector<double> epsv(nrhs, eps);
-  if (eps_per_system) epsv = *eps_per_system;
   qmg::BatchPoolT<T> pool(phi.stride, nrhs);
   qmg::BatchT<T> r = pool.get(), p = pool.get(), Ap = pool.get();
-  const std::vector<double> bsq = qmg::bnorm2sq(phi0, size, mask);
-  std::vector<double> rsq(nrhs, 0.0), bnorm(nrhs, 0.0);
-  std::vector<int> its(nrhs, 0), ops(nrhs, 0);
-  std::vector<bool> conv(nrhs, false);
-  for (int k = 0; k < nrhs; k++) bnorm[k] = std::sqrt(bsq[k]);
+  qmg::SolveLedger led = qmg::open_ledger(phi, phi0, size, mask, max_iter, eps, eps_per_system);
+  const unsigned& act = led.act;
   const qmg::cvec one(nrhs, 1.0);
-  std::vector<qmg::BatchT<T> > pv(1);
-  const unsigned zero_b = qmg::zero_rhs_systems(phi, bsq, size, mask);   // (a zero right-hand side: x = 0, done)
-  for (int k = 0; k < nrhs; k++) if (qmg::is_active(zero_b, k)) conv[k] = true;
-  unsigned live = (r.p && p.p && Ap.p) ? (mask & ~zero_b) : 0u;   // systems that may still start a cycle
-  if (!live && (mask & ~zero_b)) std::cout << "[QMG-ERROR]: " << name << ": out of device memory for the CG work vectors\n";
+  unsigned live = (r.p && p.p && Ap.p) ? led.run : 0u;   // systems that may still start a cycle
+  if (!live && led.run) std::cout << "[QMG-ERROR]: " << name << ": out of device memory for the CG work vectors\n";
   bool first = true;
   while (live) {
-    // ---- one cycle: at most `chunk` iterations per system
+    // ---- one cycle: at most `chunk` iterations per system (chunk > 0: a live system has iterations left, or max_iter <= 0 and none opens)
     std::vector<int> chunk(nrhs, 0), done_in_cycle(nrhs, 0);
-    unsigned act = 0;
     for (int k = 0; k < nrhs; k++) {
       if (!qmg::is_active(live, k)) continue;
-      const int left = max_iter - its[k];
+      const int left = max_iter - led.its[k];
       chunk[k] = (restart_freq > 0 && left > restart_freq) ? restart_freq : left;
     }
-    if (first && zero_guess) { qmg::bcopy(r, phi0, size, live); rsq = bsq; }
-    else {
-      const std::vector<double> t = qmg::bresidual(r, phi, phi0, Ap, size, matrix_vector, extra_info, live, ops);
-      for (int k = 0; k < nrhs; k++) if (qmg::is_active(live, k)) rsq[k] = t[k];
-    }
+    qmg::bopen(led, live, r, phi, phi0, Ap, size, matrix_vector, extra_info, first && zero_guess);
     first = false;
     qmg::bcopy(p, r, size, live);
-    for (int k = 0; k < nrhs; k++) {
-      if (!qmg::is_active(live, k)) continue;
-      conv[k] = (bnorm[k] == 0.0) || (std::sqrt(rsq[k]) < epsv[k] * bnorm[k]);
-      if (!conv[k] && chunk[k] > 0) act |= 1u << k;
-    }
     while (act) {
       matrix_vector(Ap, p, act, extra_info);
-      pv[0] = p;
-      const std::vector<qmg::cvec> d = qmg::bmultidot(pv, 1, Ap, size, act);   // <p, A p>
+      led.count(act);
+      const std::vector<qmg::cvec> d = qmg::bmultidot(&p, 1, Ap, size, act);   // <p, A p>
       qmg::cvec alpha(nrhs, 0.0), malpha(nrhs, 0.0);
       unsigned upd = 0;
       for (int k = 0; k < nrhs; k++) {
         if (!qmg::is_active(act, k)) continue;
-        ops[k]++;
         const double pAp = d[k][0].real();
-        if (pAp == 0.0) { act &= ~(1u << k); continue; }   // breakdown: this system's cycle ends
-        alpha[k] = rsq[k] / pAp; malpha[k] = -alpha[k];
+        if (pAp == 0.0) { led.breakdown(k); continue; }   // (this system's cycle ends; without an iteration in it, it starts no other)
+        alpha[k] = led.rsq[k] / pAp; malpha[k] = -alpha[k];
         upd |= 1u << k;
       }
       qmg::bcaxpy(alpha, p, phi, size, upd);
@@ -776,12 +775,14 @@ inline std::vector<inversion_info> bcg_core(qmg::BatchT<T> phi, qmg::BatchT<T> p
       unsigned go_on = 0;
       for (int k = 0; k < nrhs; k++) {
         if (!qmg::is_active(upd, k)) continue;
-        its[k]++; done_in_cycle[k]++;
-        qmg::report(verb, "CG", nrhs, k, its[k], std::sqrt(rn[k]) / bnorm[k]);
-        if (std::sqrt(rn[k]) < epsv[k] * bnorm[k]) { rsq[k] = rn[k]; conv[k] = true; act &= ~(1u << k); continue; }
-        beta[k] = rn[k] / rsq[k];
-        rsq[k] = rn[k];
-        if (done_in_cycle[k] >= chunk[k]) act &= ~(1u << k);
+        const double rsq_old = led.rsq[k];
+        led.anchor(k, rn[k]);
+        done_in_cycle[k]++;
+        const bool done = led.step(k);
+        qmg::report(verb, "CG", nrhs, k, led.its[k], led.rel(k));
+        if (done) continue;
+        beta[k] = rn[k] / rsq_old;
+        if (done_in_cycle[k] >= chunk[k]) led.act &= ~(1u << k);   // the cycle's end, not the system's
         else go_on |= 1u << k;
       }
       qmg::bcaxpbyz(one, r, beta, p, p, size, go_on);   // p = r + beta p
@@ -790,15 +791,11 @@ inline std::vector<inversion_info> bcg_core(qmg::BatchT<T> phi, qmg::BatchT<T> p
     unsigned next = 0;
     for (int k = 0; k < nrhs; k++) {
       if (!qmg::is_active(live, k)) continue;
-      if (restart_freq > 0 && !conv[k] && done_in_cycle[k] > 0 && its[k] < max_iter) next |= 1u << k;
+      if (restart_freq > 0 && !led.conv[k] && done_in_cycle[k] > 0 && led.its[k] < max_iter) next |= 1u << k;
     }
     live = next;
   }
-  for (int k = 0; k < nrhs; k++) {
-    inv[k].success = conv[k]; inv[k].iter = its[k]; inv[k].resSq = rsq[k]; inv[k].ops_count = ops[k]; inv[k].name = name;
-    if (qmg::is_active(mask, k)) qmg::summary(verb, name, nrhs, k, conv[k], its[k], bnorm[k] > 0 ? std::sqrt(rsq[k]) / bnorm[k] : 0.0);
-  }
-  return inv;
+  return qmg::close_ledger(led, verb, name);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -843,46 +840,45 @@ inline std::vector<inversion_info> bcg_m_core(const std::vector<qmg::BatchT<T> >
   std::vector<qmg::BatchT<T> > ps(S);
   bool have = r.p && Ap.p;
   for (int s = 0; s < S; s++) { ps[s] = pool.get(); have = have && ps[s].p; }
-  const std::vector<double> bsq = qmg::bnorm2sq(phi0, size, mask);
-  std::vector<double> rsq(bsq), bnorm(nrhs, 0.0), alpha_prev(nrhs, 1.0), beta_prev(nrhs, 0.0);
+  // the ledger's |b|, rsq, iter, ops and system-level mask; the shifts' freezing by zeta, and with it success and resSq, is this core's own
+  qmg::SolveLedger led(qmg::bnorm2sq(phi0, size, mask), mask, max_iter, eps);
+  const unsigned& act = led.act;
+  std::vector<double>&rsq = led.rsq, &bnorm = led.bnorm;
+  std::vector<double> alpha_prev(nrhs, 1.0), beta_prev(nrhs, 0.0);
   std::vector<std::vector<double> > zeta(nrhs, std::vector<double>(S, 1.0)), zeta_prev(zeta);
-  std::vector<int> its(nrhs, 0), ops(nrhs, 0);
   std::vector<unsigned> live(nrhs, 0u);            // per system: the shifts it still iterates
   std::vector<unsigned> shift_masks(S, 0u);        // per shift: the systems that still iterate it (the kernel's view of `live`)
-  unsigned act = 0;
   if (!have && mask) std::cout << "[QMG-ERROR]: " << name << ": out of device memory for the CG work vectors\n";
+  if (have && max_iter > 0) led.act = led.run;
   for (int k = 0; k < nrhs; k++) {
     if (!qmg::is_active(mask, k)) continue;
-    bnorm[k] = std::sqrt(bsq[k]);
-    for (int s = 0; s < S; s++) { inv[(size_t)k * S + s].success = (bnorm[k] == 0.0); inv[(size_t)k * S + s].resSq = bsq[k]; }
-    if (have && bnorm[k] > 0.0 && max_iter > 0) { act |= 1u << k; live[k] = qmg::full_mask(S); }
+    for (int s = 0; s < S; s++) { inv[(size_t)k * S + s].success = (bnorm[k] == 0.0); inv[(size_t)k * S + s].resSq = led.bsq[k]; }
+    if (qmg::is_active(act, k)) live[k] = qmg::full_mask(S);
   }
   if (act) {
     qmg::bcopy(r, phi0, size, act);
     for (int s = 0; s < S; s++) qmg::bcopy(ps[s], phi0, size, act);
   }
-  std::vector<qmg::BatchT<T> > dotv(2), axv(2);
+  const qmg::BatchT<T> Ap_p[2] = {Ap, ps[base]};
   std::vector<const void*> xtab(S), ptab(S);
   for (int s = 0; s < S; s++) { xtab[s] = phi[s].p; ptab[s] = ps[s].p; }
   std::vector<double> a((size_t)S * nrhs), z((size_t)S * nrhs), c((size_t)S * nrhs), as(S), zs(S), cs(S);
   while (act) {
     matrix_vector(Ap, ps[base], act, extra_info);
-    dotv[0] = Ap; dotv[1] = ps[base];
-    const std::vector<qmg::cvec> d = qmg::bmultidot(dotv, sigma0 != 0.0 ? 2 : 1, ps[base], size, act);   // <A p, p> (, <p, p>)
+    led.count(act);
+    const std::vector<qmg::cvec> d = qmg::bmultidot(Ap_p, sigma0 != 0.0 ? 2 : 1, ps[base], size, act);   // <A p, p> (, <p, p>)
     std::vector<double> alpha(nrhs, 0.0);
     std::vector<qmg::cvec> rc(nrhs, qmg::cvec(2, 0.0));
     unsigned upd = 0;
     for (int k = 0; k < nrhs; k++) {
       if (!qmg::is_active(act, k)) continue;
-      ops[k]++;
       const double pAp = d[k][0].real() + (sigma0 != 0.0 ? sigma0 * d[k][1].real() : 0.0);
-      if (pAp == 0.0) { act &= ~(1u << k); continue; }   // breakdown: the system stops where it is
+      if (pAp == 0.0) { led.breakdown(k); continue; }
       alpha[k] = rsq[k] / pAp;
       rc[k][0] = -alpha[k]; rc[k][1] = -alpha[k] * sigma0;
       upd |= 1u << k;
     }
-    axv[0] = Ap; axv[1] = ps[base];
-    qmg::bmulti_caxpy(rc, axv, sigma0 != 0.0 ? 2 : 1, r, size, upd);   // r -= alpha (A p + sigma_0 p)
+    qmg::bmulti_caxpy(rc, Ap_p, sigma0 != 0.0 ? 2 : 1, r, size, upd);   // r -= alpha (A p + sigma_0 p)
     const std::vector<double> rn = qmg::bnorm2sq(r, size, upd);
     std::fill(a.begin(), a.end(), 0.0); std::fill(z.begin(), z.end(), 0.0); std::fill(c.begin(), c.end(), 0.0);
     std::fill(shift_masks.begin(), shift_masks.end(), 0u);
@@ -902,23 +898,24 @@ inline std::vector<inversion_info> bcg_m_core(const std::vector<qmg::BatchT<T> >
                                      r.stride, upd, qmg::current_stream()), "qmg_batch_cgm_update");
     for (int k = 0; k < nrhs; k++) {
       if (!qmg::is_active(upd, k)) continue;
-      its[k]++;
+      led.its[k]++;
       const double rnorm = std::sqrt(rsq[k]);
-      qmg::report(verb, name, nrhs, k, its[k], rnorm / bnorm[k]);
+      qmg::report(verb, name, nrhs, k, led.its[k], rnorm / bnorm[k]);
       for (int s = 0; s < S; s++) {
         if (!((live[k] >> s) & 1u)) continue;
         inversion_info& o = inv[(size_t)k * S + s];
-        o.iter = its[k]; o.resSq = zeta[k][s] * zeta[k][s] * rsq[k];
+        o.iter = led.its[k]; o.resSq = zeta[k][s] * zeta[k][s] * rsq[k];
         if (std::fabs(zeta[k][s]) * rnorm < eps * bnorm[k]) { o.success = true; live[k] &= ~(1u << s); }
       }
-      if (!((live[k] >> base) & 1u) || its[k] >= max_iter) act &= ~(1u << k);
+      if (!((live[k] >> base) & 1u)) led.act &= ~(1u << k);   // the smallest shift has converged, the others before it (success is per shift)
     }
+    led.cap();
   }
   for (int k = 0; k < nrhs; k++) {
     if (!qmg::is_active(mask, k)) continue;
     for (int s = 0; s < S; s++) {
       inversion_info& o = inv[(size_t)k * S + s];
-      o.ops_count = ops[k];
+      o.ops_count = led.ops[k];
       if (verb && verb->verbosity != VERB_NONE) {
         std::cout << verb->verb_prefix << name;
         if (nrhs > 1) std::cout << " rhs " << k;
@@ -1010,7 +1007,7 @@ inline inversion_info minv_vector_richardson(complex<double>* phi, complex<doubl
   int ops = 0, k = 0;
   double rsq = 0.0;
   bool conv = false;
-  if (bnorm == 0.0) {   // A x = 0: x = 0 whatever the guess was, as in the batch cores (qmg::zero_rhs_systems)
+  if (bnorm == 0.0) {   // A x = 0: x = 0 whatever the guess was, as in the batch cores
     zero_vector(phi, size);
     invif.success = true;
     qmg::summary(verb, "Richardson", 1, 0, true, 0, 0.0);
