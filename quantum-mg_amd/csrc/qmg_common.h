@@ -432,6 +432,12 @@ inline unsigned grid_1d(size_t work_items, int per_block = BLOCK) {
   if (b == 0) b = 1;
   return (unsigned)b;
 }
+inline int rows_on_grid(long n) { return n > 65535 ? 65535 : (int)n; }   // grid.y: blocks walk the rows beyond it
+
+// What every qmg_*_plan export writes: the n numbers of the plan, then -1 in whatever the caller's array holds beyond them.
+inline void export_plan_ints(const int* v, int n, int* plan_out, int plan_len) {
+  for (int i = 0; i < plan_len; i++) plan_out[i] = i < n ? v[i] : -1;
+}
 
 }  // namespace qmg
 

@@ -86,6 +86,8 @@ __global__ __launch_bounds__(BLOCK) void k_dwf_fill(cplx* __restrict__ clover, c
 }
 
 // what a lane needs of its slice besides the data: the fifth-dimension coefficients and the diagonal shifts of both parities
+// (One struct for the partners s_lo / s_hi, their offsets and the four wall coefficients, shared with k_dwf_eo_schur2, moved a scalar load in
+// the four fp32 batch instantiations of kernels D / D2 and reordered all four of stage 2: not kept, profiles/dwf_lane_refactor.txt.)
 template <typename R>
 struct DwfCoef {
   R clx, cly, chx, chy;        // times psi(s_lo, sigma 0) and psi(s_hi, sigma 1): -1 inside, m across the wall
@@ -153,9 +155,9 @@ __global__ __launch_bounds__(BLOCK) void k_dwf_direct(const DwfArgs a) {
   typedef T v4 __attribute__((ext_vector_type(4)));   // a lane's chunk: (sigma 0 re, im, sigma 1 re, im)
   typedef T v2 __attribute__((ext_vector_type(2)));   // half a chunk, a link
   constexpr unsigned CH = 4u * sizeof(T), GB = 2u * sizeof(T);
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= a.hr * a.Ls) return;
-  const int j = t / a.Ls, s = t - j * a.Ls;
+  const dwf::Lane ln = dwf::lane_of<false>(a.hr, a.Ls);
+  if (!ln.live) return;
+  const int t = ln.t, j = ln.j, s = ln.s;
   // fifth dimension: sigma = 0 takes slice s - 1 (times -1; across the wall slice Ls - 1 times m), sigma = 1 slice s + 1 (the wall: slice 0)
   const int s_lo = s > 0 ? s - 1 : a.Ls - 1, s_hi = s + 1 < a.Ls ? s + 1 : 0;
   const DwfCoef<R> co = dwf_coef<R>(a, s);
@@ -165,10 +167,12 @@ __global__ __launch_bounds__(BLOCK) void k_dwf_direct(const DwfArgs a) {
   const long sys_bytes = a.vec_stride * (long)(2 * sizeof(T));
   const long row_bytes = (long)a.hr * a.Ls * CH;
   for (int row = blockIdx.y; row < a.nrows; row += gridDim.y) {
-    const int p = (a.par_count == 2) ? (row & 1) : a.par_first;
-    const int y = (a.par_count == 2) ? (row >> 1) : row;
+    int p, y;
+    dwf::row_py(a, row, p, y);
     const bool do_shift = (a.pieces >> (10 + p)) & 1u;
     const bool do_zero = ZERO || ((a.pieces >> (12 + p)) & 1u);
+    // dwf::row_of<T, true>, written out: through it all 16 instantiations keep their registers and, to within one, their instruction count
+    // but not their order (the helper forms the rows before off_xp / off_xm); held to the parent's text (profiles/dwf_lane_refactor.txt).
     const int sx = (y + p) & 1;
     int jp = j + sx;     if (jp == a.hr) jp = 0;
     int jm = j + sx - 1; if (jm < 0) jm = a.hr - 1;
@@ -221,9 +225,9 @@ __global__ __launch_bounds__(BLOCK) void k_dwf_pair(const DwfArgs a) {
   typedef T v4 __attribute__((ext_vector_type(4)));
   typedef T v2 __attribute__((ext_vector_type(2)));
   constexpr unsigned CH = 4u * sizeof(T), GB = 2u * sizeof(T);
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= a.hr * a.Ls) return;
-  const int j = t / a.Ls, s = t - j * a.Ls;
+  const dwf::Lane ln = dwf::lane_of<false>(a.hr, a.Ls);
+  if (!ln.live) return;
+  const int t = ln.t, j = ln.j, s = ln.s;
   const int s_lo = s > 0 ? s - 1 : a.Ls - 1, s_hi = s + 1 < a.Ls ? s + 1 : 0;
   const DwfCoef<R> co = dwf_coef<R>(a, s);
   const int jl = (j == 0) ? a.hr - 1 : j - 1, jr = (j + 1 == a.hr) ? 0 : j + 1;
@@ -320,29 +324,22 @@ int qmg_dwf_plan(int dtype, int Lx, int Ly, int Ls, unsigned pieces, int n_activ
   if (!plan_out || plan_len < DWF_PLAN_INTS) return QMG_ERR_INVALID;
   const DwfPlan pl = dwf_plan(dtype, Lx, Ly, Ls, pieces, n_active, inplace);
   const int v[DWF_PLAN_INTS] = {pl.family, pl.lps, pl.block, pl.gx, pl.gy, pl.flags, pl.shape, pl.nk};
-  for (int i = 0; i < plan_len; i++) plan_out[i] = i < DWF_PLAN_INTS ? v[i] : -1;
+  export_plan_ints(v, DWF_PLAN_INTS, plan_out, plan_len);
   return QMG_SUCCESS;
 }
 
 int qmg_dwf_apply_direct(int dtype, const qmg_stencil_desc* d, const void* gauge, int Ls, double mass_re, double mass_im, double wilson_coeff, void* lhs,
                          const void* rhs, unsigned pieces, int nrhs, size_t vec_stride, unsigned mask, void* stream) {
-  if (!d || !gauge || !lhs || !rhs || nrhs < 1 || nrhs > BATCH_MAX) return QMG_ERR_INVALID;
-  if (Ls < DWF_LS_MIN || Ls > DWF_LS_MAX || d->nc != 2 * Ls) return QMG_ERR_INVALID;
-  if (!aligned16(gauge) || !aligned16(lhs) || !aligned16(rhs)) return QMG_ERR_INVALID;
-  if (nrhs > 1 && (vec_stride < (size_t)d->Lx * d->Ly * d->nc || (dtype == QMG_C32 && (vec_stride & 1)))) return QMG_ERR_INVALID;
+  if (!d || !gauge || !lhs || !rhs || d->nc != 2 * Ls || !aligned16(gauge) || !aligned16(lhs) || !aligned16(rhs)) return QMG_ERR_INVALID;
+  if (int rc = dwf_entry_check(dtype, d->Lx, d->Ly, Ls, nrhs, vec_stride)) return rc;
   const BatchIdx b = expand_mask(mask, nrhs);
   const DwfPlan pl = dwf_plan(dtype, d->Lx, d->Ly, Ls, pieces, b.n, lhs == rhs);
   if (pl.family == DF_NOTHING) return QMG_SUCCESS;
   if (pl.family != DF_DIRECT && pl.family != DF_PAIR) return pl.status;
   DwfArgs a;
-  a.gauge = gauge; a.lhs = lhs; a.rhs = rhs;
-  a.hr = d->Lx / 2; a.Ly = d->Ly; a.Ls = Ls;
-  a.half_vol = (long)a.hr * d->Ly;
-  a.pieces = pieces; a.nrhs = b.n; a.vec_stride = (long)vec_stride;
-  a.par_first = pl.par_first; a.par_count = pl.par_count; a.nrows = d->Ly * pl.par_count;
+  dwf_fill_rows(a, gauge, lhs, rhs, d->Lx, d->Ly, Ls, pieces, b, vec_stride, pl.par_first, pl.par_count);
   a.w = wilson_coeff; a.mr = mass_re; a.mi = mass_im;
   for (int i = 0; i < 2; i++) { a.shift[i] = d->shift[i]; a.eo_shift[i] = d->eo_shift[i]; a.dof_shift[i] = d->dof_shift[i]; }
-  for (int k = 0; k < 16; k++) a.ridx[k] = b.id[k];
   hipStream_t st = as_stream(stream);
   if (dtype == QMG_C64) launch_dwf<double>(a, pl, st); else launch_dwf<float>(a, pl, st);
   QMG_LAUNCH_CHECK();

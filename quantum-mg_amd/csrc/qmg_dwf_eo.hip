@@ -46,56 +46,17 @@ struct DwfEoArgs {
   int ridx[16];
 };
 
-namespace dwf_eo {
-// the rows a site of (p, y) reaches and its four links, as kernel D forms them
-template <typename T>
-struct Row {
-  int p, jp, jm;
-  long row_own, row_x, row_yp, row_ym;
-  T lx[4], ly[4];
-};
-template <typename T, bool LINKS>
-__device__ __forceinline__ Row<T> row_of(const DwfEoArgs<T>& a, int p, int y, int j, long row_bytes) {
-  using namespace dwf;
-  typedef T v2 __attribute__((ext_vector_type(2)));
-  constexpr unsigned GB = 2u * sizeof(T);
-  Row<T> r;
-  r.p = p;
-  const int sx = (y + p) & 1;
-  r.jp = j + sx;     if (r.jp == a.hr) r.jp = 0;
-  r.jm = j + sx - 1; if (r.jm < 0) r.jm = a.hr - 1;
-  const int yp = (y + 1 == a.Ly) ? 0 : y + 1;
-  const int ym = (y == 0) ? a.Ly - 1 : y - 1;
-  r.row_own = ((long)p * a.Ly + y) * row_bytes;
-  r.row_x = ((long)(1 - p) * a.Ly + y) * row_bytes;
-  r.row_yp = ((long)(1 - p) * a.Ly + yp) * row_bytes;
-  r.row_ym = ((long)(1 - p) * a.Ly + ym) * row_bytes;
-  if (LINKS) {
-    // links: own Ux, Uy and the -x / -y neighbours' (opposite parity), conjugated for the backward directions
-    const long vol = 2 * a.half_vol;
-    const char* gc = reinterpret_cast<const char*>(a.gauge);
-    const gchar* g_own_x = uni(gc + ((long)p * a.half_vol + (long)y * a.hr) * GB);
-    const gchar* g_own_y = uni(gc + (vol + (long)p * a.half_vol + (long)y * a.hr) * GB);
-    const gchar* g_xm = uni(gc + ((long)(1 - p) * a.half_vol + (long)y * a.hr) * GB);
-    const gchar* g_ym = uni(gc + (vol + (long)(1 - p) * a.half_vol + (long)ym * a.hr) * GB);
-    const unsigned goff_j = (unsigned)j * GB;
-    const v2 u0 = gld<v2>(g_own_x, goff_j), u1 = gld<v2>(g_own_y, goff_j), u2 = gld<v2>(g_xm, (unsigned)r.jm * GB), u3 = gld<v2>(g_ym, goff_j);
-    r.lx[0] = u0.x; r.lx[1] = u1.x; r.lx[2] = u2.x; r.lx[3] = u3.x;
-    r.ly[0] = u0.y; r.ly[1] = u1.y; r.ly[2] = -u2.y; r.ly[3] = -u3.y;
-  }
-  return r;
-}
-}  // namespace dwf_eo
-
 // ---- kernels K (HOP) and I (!HOP): lhs_p (+)= alpha A_p^-1 h, h = H_{p,1-p} [Gamma5] rhs_{1-p} or rhs_p ----
 template <typename T, bool HOP, bool ZERO, bool BATCH>
-__global__ __launch_bounds__(DWF_EO_BLOCK_MAX) void k_dwf_eo_inv5(const DwfEoArgs<T> a) {
+__global__ __launch_bounds__(DWF_BLOCK_MAX) void k_dwf_eo_inv5(const DwfEoArgs<T> a) {
   using namespace dwf;
   typedef T R;
   typedef T v4 __attribute__((ext_vector_type(4)));   // a lane's chunk: (sigma 0 re, im, sigma 1 re, im)
   constexpr unsigned CH = 4u * sizeof(T);
-  __shared__ v4 xch[2][DWF_EO_BLOCK_MAX];
+  __shared__ v4 xch[2][DWF_BLOCK_MAX];
   const int tid = threadIdx.x;
+  // dwf::lane_of<true>, written out: through it the eight hop instantiations come out with the operands of one v_add_lshl_u32 exchanged,
+  // and the kernels are held to the parent's device code text (profiles/dwf_lane_refactor.txt).
   const int t = blockIdx.x * blockDim.x + tid;
   const bool live = t < a.hr * a.Ls;      // a site is live or not as a whole: the block and the half row are multiples of Ls lanes
   const int jt = t / a.Ls, s = t - jt * a.Ls;
@@ -110,10 +71,10 @@ __global__ __launch_bounds__(DWF_EO_BLOCK_MAX) void k_dwf_eo_inv5(const DwfEoArg
   const R hw = a.hw, alx = a.ar, aly = a.ai;
   int buf = 0;
   for (int row = blockIdx.y; row < a.nrows; row += gridDim.y) {
-    const int p = (a.par_count == 2) ? (row & 1) : a.par_first;
-    const int y = (a.par_count == 2) ? (row >> 1) : row;
+    int p, y;
+    row_py(a, row, p, y);
     const bool do_zero = ZERO || ((a.pieces >> (12 + p)) & 1u);
-    const dwf_eo::Row<T> r = dwf_eo::row_of<T, HOP>(a, p, y, j, row_bytes);
+    const Row<T> r = row_of<T, HOP>(a, p, y, j, row_bytes);
     const unsigned off_xp = (unsigned)(r.jp * a.Ls + sr) * CH, off_xm = (unsigned)(r.jm * a.Ls + sr) * CH;
     const R qx = a.q[p][0], qy = a.q[p][1];
     const int nsys = BATCH ? a.nrhs : 1;
@@ -176,15 +137,15 @@ __global__ __launch_bounds__(DWF_EO_BLOCK_MAX) void k_dwf_eo_inv5(const DwfEoArg
 
 // ---- the second stage of M: lhs_p = [Gamma5] (A_p [Gamma5] x_p + H_{p,1-p} t_{1-p}), overwriting; one parity ----
 template <typename T, bool BATCH>
-__global__ __launch_bounds__(DWF_EO_BLOCK_MAX) void k_dwf_eo_schur2(const DwfEoArgs<T> a) {
+__global__ __launch_bounds__(DWF_BLOCK_MAX) void k_dwf_eo_schur2(const DwfEoArgs<T> a) {
   using namespace dwf;
   typedef T R;
   typedef T v4 __attribute__((ext_vector_type(4)));
   typedef T v2 __attribute__((ext_vector_type(2)));
   constexpr unsigned CH = 4u * sizeof(T);
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= a.hr * a.Ls) return;
-  const int j = t / a.Ls, s = t - j * a.Ls;
+  const Lane ln = lane_of<false>(a.hr, a.Ls);
+  if (!ln.live) return;
+  const int t = ln.t, j = ln.j, s = ln.s;
   // fifth dimension: sigma = 0 takes slice s - 1 (times -1; across the wall slice Ls - 1 times m), sigma = 1 slice s + 1 (the wall: slice 0)
   const int s_lo = s > 0 ? s - 1 : a.Ls - 1, s_hi = s + 1 < a.Ls ? s + 1 : 0;
   const R clx = s > 0 ? (R)-1 : a.mr, cly = s > 0 ? (R)0 : a.mi;
@@ -202,7 +163,7 @@ __global__ __launch_bounds__(DWF_EO_BLOCK_MAX) void k_dwf_eo_schur2(const DwfEoA
   const int p = a.par_first;
   const R dx = a.d[p][0], dy = a.d[p][1];
   for (int y = blockIdx.y; y < a.Ly; y += gridDim.y) {
-    const dwf_eo::Row<T> r = dwf_eo::row_of<T, true>(a, p, y, j, row_bytes);
+    const Row<T> r = row_of<T, true>(a, p, y, j, row_bytes);
     const unsigned off_xp = (unsigned)(r.jp * a.Ls + s) * CH, off_xm = (unsigned)(r.jm * a.Ls + s) * CH;
     const int nsys = BATCH ? a.nrhs : 1;
     for (int k = 0; k < nsys; k++) {
@@ -248,12 +209,10 @@ static void launch_dwf_eo(const DwfEoArgs<T>& a, const DwfEoPlan& pl, hipStream_
   }
 }
 
-// what every entry checks before the plan is asked (qmg_dwf_apply_direct's rules)
+// what every entry checks before the plan is asked
 static int eo_valid(int dtype, const qmg_stencil_desc* d, int Ls, int nrhs, size_t vec_stride) {
-  if (!d || !valid_dtype(dtype) || nrhs < 1 || nrhs > BATCH_MAX) return QMG_ERR_INVALID;
-  if (Ls < DWF_LS_MIN || Ls > DWF_LS_MAX || d->nc != 2 * Ls) return QMG_ERR_INVALID;
-  if (nrhs > 1 && (vec_stride < (size_t)d->Lx * d->Ly * d->nc || (dtype == QMG_C32 && (vec_stride & 1)))) return QMG_ERR_INVALID;
-  return QMG_SUCCESS;
+  if (!d || d->nc != 2 * Ls) return QMG_ERR_INVALID;
+  return dwf_entry_check(dtype, d->Lx, d->Ly, Ls, nrhs, vec_stride);
 }
 
 // one launch of a planned request
@@ -261,11 +220,8 @@ template <typename T>
 static void eo_launch(const qmg_stencil_desc* d, const DwfEoPlan& pl, const DwfEoCoef& co, const void* gauge, int Ls, double mr, double mi, double w, void* lhs,
                       const void* rhs, const void* aux, unsigned pieces, double ar, double ai, unsigned flags, const BatchIdx& b, size_t vec_stride, hipStream_t st) {
   DwfEoArgs<T> a;
-  a.gauge = gauge; a.lhs = lhs; a.rhs = rhs; a.aux = aux;
-  a.hr = d->Lx / 2; a.Ly = d->Ly; a.Ls = Ls;
-  a.half_vol = (long)a.hr * d->Ly;
-  a.pieces = pieces; a.nrhs = b.n; a.vec_stride = (long)vec_stride;
-  a.par_first = pl.par_first; a.par_count = pl.par_count; a.nrows = d->Ly * pl.par_count;
+  dwf_fill_rows(a, gauge, lhs, rhs, d->Lx, d->Ly, Ls, pieces, b, vec_stride, pl.par_first, pl.par_count);
+  a.aux = aux;
   a.g5_in = (flags & QMG_DWF_G5_IN) ? 1 : 0; a.g5_out = (flags & QMG_DWF_G5_OUT) ? 1 : 0;
   a.hw = (T)(-0.5 * w); a.mr = (T)mr; a.mi = (T)mi; a.ar = (T)ar; a.ai = (T)ai;
   for (int p = 0; p < 2; p++)
@@ -273,7 +229,6 @@ static void eo_launch(const qmg_stencil_desc* d, const DwfEoPlan& pl, const DwfE
       a.d[p][c] = (T)co.d[p][c]; a.q[p][c] = (T)co.q[p][c];
       for (int k = 0; k <= DWF_LS_MAX; k++) a.pw[p][k][c] = (T)co.pw[p][k][c];
     }
-  for (int k = 0; k < 16; k++) a.ridx[k] = b.id[k];
   launch_dwf_eo<T>(a, pl, st);
 }
 static int eo_run(int dtype, const qmg_stencil_desc* d, const DwfEoPlan& pl, const DwfEoCoef& co, const void* gauge, int Ls, double mr, double mi, double w,
@@ -295,7 +250,7 @@ int qmg_dwf_eo_plan(int dtype, int Lx, int Ly, int Ls, int kernel, unsigned piec
   if (!plan_out || plan_len < DWF_EO_PLAN_INTS) return QMG_ERR_INVALID;
   const DwfEoPlan pl = dwf_eo_plan(dtype, Lx, Ly, Ls, kernel, pieces, n_active, inplace);
   const int v[DWF_EO_PLAN_INTS] = {pl.family, pl.lps, pl.block, pl.gx, pl.gy, pl.flags, pl.lds, pl.nk};
-  for (int i = 0; i < plan_len; i++) plan_out[i] = i < DWF_EO_PLAN_INTS ? v[i] : -1;
+  export_plan_ints(v, DWF_EO_PLAN_INTS, plan_out, plan_len);
   return QMG_SUCCESS;
 }
 

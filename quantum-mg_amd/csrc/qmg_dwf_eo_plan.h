@@ -26,7 +26,7 @@ enum DwfEoFamily {
   DEF_INV5 = 4,          // k_dwf_eo_inv5<T, false, true, BATCH>
   DEF_SCHUR2 = 5         // k_dwf_eo_schur2<T, BATCH>
 };
-enum { DWF_EO_PLAN_INTS = 8, DWF_EO_BLOCK_MAX = 256 };
+enum { DWF_EO_PLAN_INTS = 8 };
 
 // The first DWF_EO_PLAN_INTS members, in this order, are what qmg_dwf_eo_plan() writes.
 struct DwfEoPlan {
@@ -42,31 +42,15 @@ struct DwfEoPlan {
   int par_first, par_count;
 };
 
-namespace dwf_eo_detail {
-inline DwfEoPlan refused(int status) {
-  DwfEoPlan pl = {};
-  pl.family = status == QMG_ERR_INVALID ? DEF_INVALID : DEF_UNSUPPORTED;
-  pl.status = status;
-  return pl;
-}
-inline DwfEoPlan nothing() {
-  DwfEoPlan pl = {};
-  pl.family = DEF_NOTHING;
-  return pl;
-}
-}  // namespace dwf_eo_detail
-
 // pieces: kernel I   QMG_P_CLOVER_E / _O name the parities;
 //         kernel K   all four hop bits of each processed parity (+ QMG_P_ZERO_*);
 //         stage 2    QMG_P_CLOVER_p | the four hops of p | QMG_P_SHIFT_p | QMG_P_ZERO_p of exactly one parity p.
 // n_active: the systems whose mask bit is set (0 .. 16); inplace: lhs == rhs
 inline DwfEoPlan dwf_eo_plan(int dtype, int Lx, int Ly, int Ls, int kernel, unsigned pieces, int n_active, int inplace) {
-  using namespace dwf_eo_detail;
-  if (!valid_dtype(dtype) || !valid_lattice(Lx, Ly) || Ls < DWF_LS_MIN || Ls > DWF_LS_MAX || n_active < 0 || n_active > BATCH_MAX) return refused(QMG_ERR_INVALID);
+  const auto refused = [](int status) { return plan_refused<DwfEoPlan>(status, DEF_INVALID, DEF_UNSUPPORTED); };
+  if (!valid_dtype(dtype) || !dwf_dims_ok(Lx, Ly, Ls) || n_active < 0 || n_active > BATCH_MAX) return refused(QMG_ERR_INVALID);
   if (kernel != DEK_INV5 && kernel != DEK_HOPS_INV5 && kernel != DEK_SCHUR2) return refused(QMG_ERR_INVALID);
-  const long lanes = (long)(Lx / 2) * Ls;
-  if (lanes * 32 > 0x7FFFFFFFl) return refused(QMG_ERR_INVALID);   // a half row of the vector is addressed with 32-bit byte offsets
-  if (n_active == 0 || pieces == 0) return nothing();
+  if (n_active == 0 || pieces == 0) return plan_nothing<DwfEoPlan>(DEF_NOTHING);
   int par_first = 0, par_count = 0;
   bool zero = true;
   if (kernel == DEK_INV5) {
@@ -85,16 +69,14 @@ inline DwfEoPlan dwf_eo_plan(int dtype, int Lx, int Ly, int Ls, int kernel, unsi
     if (inplace) return refused(QMG_ERR_INVALID);
     par_first = pieces == even ? 0 : 1; par_count = 1;
   }
-  const long nrows = (long)Ly * par_count;
+  const HalfRowGrid g = half_row_grid(Lx, Ls, (long)Ly * par_count, true);
   const int f32 = dtype == QMG_C32;
   DwfEoPlan pl = {};
   pl.family = kernel == DEK_INV5 ? DEF_INV5 : kernel == DEK_HOPS_INV5 ? DEF_HOPS_INV5 : DEF_SCHUR2;
   pl.lps = Ls;
-  pl.block = Ls * (DWF_EO_BLOCK_MAX / Ls);
-  pl.gx = (int)((lanes + pl.block - 1) / pl.block);
-  pl.gy = nrows > 65535 ? 65535 : (int)nrows;
+  pl.block = g.block; pl.gx = g.gx; pl.gy = g.gy;
   pl.flags = (zero ? DPF_ZERO : 0) | (n_active > 1 ? DPF_BATCH : 0) | (f32 ? DPF_F32 : 0);
-  pl.lds = kernel == DEK_SCHUR2 ? 0 : 2 * DWF_EO_BLOCK_MAX * (f32 ? 16 : 32);
+  pl.lds = kernel == DEK_SCHUR2 ? 0 : 2 * DWF_BLOCK_MAX * (f32 ? 16 : 32);
   pl.nk = n_active;
   pl.status = QMG_SUCCESS;
   pl.par_first = par_first;

@@ -21,14 +21,14 @@
 namespace qmg {
 
 template <typename T>
-__global__ __launch_bounds__(DWF_MEAS_BLOCK_MAX) void k_dwf_wall_source(void* __restrict__ psi5, const void* __restrict__ eta4, int hr, int Ls, int nrows,
+__global__ __launch_bounds__(DWF_BLOCK_MAX) void k_dwf_wall_source(void* __restrict__ psi5, const void* __restrict__ eta4, int hr, int Ls, int nrows,
                                                                         long stride5_bytes, long stride4_bytes) {
   typedef T v4 __attribute__((ext_vector_type(4)));   // a lane's chunk: (sigma 0 re, im, sigma 1 re, im)
   typedef T v2 __attribute__((ext_vector_type(2)));
   constexpr unsigned CH = 4u * sizeof(T);
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= hr * Ls) return;
-  const int j = t / Ls, s = t - j * Ls;
+  const dwf::Lane ln = dwf::lane_of<false>(hr, Ls);
+  if (!ln.live) return;
+  const int t = ln.t, j = ln.j, s = ln.s;
   const long row5 = (long)hr * Ls * CH, row4 = (long)hr * CH;   // a 4D site is one chunk too
   char* out = reinterpret_cast<char*>(psi5) + blockIdx.z * stride5_bytes;
   const char* in = reinterpret_cast<const char*>(eta4) + blockIdx.z * stride4_bytes;
@@ -45,7 +45,7 @@ __global__ __launch_bounds__(DWF_MEAS_BLOCK_MAX) void k_dwf_wall_source(void* __
 
 // s0, s1: the slices sigma = 0 and sigma = 1 are taken from
 template <typename T>
-__global__ __launch_bounds__(DWF_MEAS_BLOCK_MAX) void k_dwf_wall_project(void* __restrict__ q4, const void* __restrict__ psi5, int hr, int Ls, int nrows, int s0, int s1,
+__global__ __launch_bounds__(DWF_BLOCK_MAX) void k_dwf_wall_project(void* __restrict__ q4, const void* __restrict__ psi5, int hr, int Ls, int nrows, int s0, int s1,
                                                                          long stride4_bytes, long stride5_bytes) {
   typedef T v2 __attribute__((ext_vector_type(2)));
   constexpr unsigned CH = 4u * sizeof(T);
@@ -64,11 +64,11 @@ __global__ __launch_bounds__(DWF_MEAS_BLOCK_MAX) void k_dwf_wall_project(void* _
 
 // part[((sys * nrows + row) * gridDim.x + blockIdx.x) * 2 Ls + c]
 template <typename T>
-__global__ __launch_bounds__(DWF_MEAS_BLOCK_MAX) void k_dwf_slice_norms(const void* __restrict__ psi5, int hr, int Ls, int nrows, long stride5_bytes,
+__global__ __launch_bounds__(DWF_BLOCK_MAX) void k_dwf_slice_norms(const void* __restrict__ psi5, int hr, int Ls, int nrows, long stride5_bytes,
                                                                         double* __restrict__ part) {
   typedef T v4 __attribute__((ext_vector_type(4)));
   constexpr unsigned CH = 4u * sizeof(T);
-  __shared__ double sm[DWF_MEAS_BLOCK_MAX][2];
+  __shared__ double sm[DWF_BLOCK_MAX][2];
   const int tid = threadIdx.x;
   const int lanes = hr * Ls;                         // of a half row
   const int step = gridDim.x * blockDim.x;           // a multiple of Ls: the lane keeps its s
@@ -129,15 +129,10 @@ __global__ __launch_bounds__(BLOCK) void k_dwf_slice_sum(const double* __restric
 static thread_local ThreadScratch g_meas;
 void release_dwf_meas_workspace() { g_meas.release(); }
 
-// what every entry checks before the plan is asked (qmg_dwf_apply_direct's rules); has4: the entry takes 4D vectors too
+// what every entry checks before the plan is asked; has4: the entry takes 4D vectors too
 static int meas_valid(int dtype, int Lx, int Ly, int Ls, int nsys, size_t stride5, size_t stride4, bool has4) {
-  if (!valid_dtype(dtype) || !valid_lattice(Lx, Ly) || Ls < DWF_LS_MIN || Ls > DWF_LS_MAX || nsys < 1 || nsys > BATCH_MAX) return QMG_ERR_INVALID;
-  if (nsys > 1) {
-    const size_t site = (size_t)Lx * Ly;
-    if (stride5 < site * 2 * Ls || (dtype == QMG_C32 && (stride5 & 1))) return QMG_ERR_INVALID;
-    if (has4 && (stride4 < site * 2 || (dtype == QMG_C32 && (stride4 & 1)))) return QMG_ERR_INVALID;
-  }
-  return QMG_SUCCESS;
+  if (!valid_lattice(Lx, Ly)) return QMG_ERR_INVALID;
+  return dwf_entry_check(dtype, Lx, Ly, Ls, nsys, stride5, stride4, has4);
 }
 
 }  // namespace qmg
@@ -150,7 +145,7 @@ int qmg_dwf_meas_plan(int dtype, int Lx, int Ly, int Ls, int kernel, int nsys, i
   if (!plan_out || plan_len < DWF_MEAS_PLAN_INTS) return QMG_ERR_INVALID;
   const DwfMeasPlan pl = dwf_meas_plan(dtype, Lx, Ly, Ls, kernel, nsys);
   const int v[DWF_MEAS_PLAN_INTS] = {pl.family, pl.lps, pl.block, pl.gx, pl.gy, pl.pbr, pl.lds, pl.nk};
-  for (int i = 0; i < plan_len; i++) plan_out[i] = i < DWF_MEAS_PLAN_INTS ? v[i] : -1;
+  export_plan_ints(v, DWF_MEAS_PLAN_INTS, plan_out, plan_len);
   return QMG_SUCCESS;
 }
 

@@ -23,7 +23,7 @@ enum DwfMeasFamily {
   DMF_INVALID = 3,       // the entry point returns QMG_ERR_INVALID
   DMF_NORMS = 4          // k_dwf_slice_norms<T>, then k_dwf_slice_sum
 };
-enum { DWF_MEAS_PLAN_INTS = 8, DWF_MEAS_BLOCK_MAX = 256, DWF_MEAS_PBR_MAX = 4 };
+enum { DWF_MEAS_PLAN_INTS = 8, DWF_MEAS_PBR_MAX = 4 };
 
 // The first DWF_MEAS_PLAN_INTS members, in this order, are what qmg_dwf_meas_plan() writes.
 struct DwfMeasPlan {
@@ -40,42 +40,23 @@ struct DwfMeasPlan {
   int status;
 };
 
-namespace dwf_meas_detail {
-inline DwfMeasPlan refused(int status) {
-  DwfMeasPlan pl = {};
-  pl.family = status == QMG_ERR_INVALID ? DMF_INVALID : DMF_UNSUPPORTED;
-  pl.status = status;
-  return pl;
-}
-}  // namespace dwf_meas_detail
-
 inline DwfMeasPlan dwf_meas_plan(int dtype, int Lx, int Ly, int Ls, int kernel, int nsys) {
-  using namespace dwf_meas_detail;
-  if (!valid_dtype(dtype) || !valid_lattice(Lx, Ly) || Ls < DWF_LS_MIN || Ls > DWF_LS_MAX || nsys < 1 || nsys > BATCH_MAX) return refused(QMG_ERR_INVALID);
+  const auto refused = [](int status) { return plan_refused<DwfMeasPlan>(status, DMF_INVALID, DMF_UNSUPPORTED); };
+  if (!valid_dtype(dtype) || !dwf_dims_ok(Lx, Ly, Ls) || nsys < 1 || nsys > BATCH_MAX) return refused(QMG_ERR_INVALID);
   if (kernel < DMK_SOURCE || kernel > DMK_NORMS) return refused(QMG_ERR_INVALID);
-  const long lanes5 = (long)(Lx / 2) * Ls;
-  if (lanes5 * 32 > 0x7FFFFFFFl) return refused(QMG_ERR_INVALID);   // a half row of the vector is addressed with 32-bit byte offsets
   if (kernel == DMK_PROJECT_MID && (Ls & 1)) return refused(QMG_ERR_UNSUPPORTED);   // no midpoint between the walls
-  const long nrows = 2l * Ly;
   DwfMeasPlan pl = {};
-  pl.gy = nrows > 65535 ? 65535 : (int)nrows;
+  pl.family = kernel == DMK_NORMS ? DMF_NORMS : kernel == DMK_SOURCE ? DMF_SOURCE : DMF_PROJECT;
+  pl.lps = pl.family == DMF_PROJECT ? 2 : Ls;
+  const HalfRowGrid g = half_row_grid(Lx, pl.lps, 2l * Ly, kernel == DMK_NORMS);
+  pl.block = g.block; pl.gx = g.gx; pl.gy = g.gy;
   pl.nk = nsys;
   pl.status = QMG_SUCCESS;
-  if (kernel == DMK_NORMS) {
-    pl.family = DMF_NORMS;
-    pl.lps = Ls;
-    pl.block = Ls * (DWF_MEAS_BLOCK_MAX / Ls);
-    const long cover = (lanes5 + pl.block - 1) / pl.block;
-    pl.pbr = cover > DWF_MEAS_PBR_MAX ? DWF_MEAS_PBR_MAX : (int)cover;
+  if (kernel == DMK_NORMS) {   // the blocks that would cover the half row, at most four, stride over it
+    pl.pbr = g.gx > DWF_MEAS_PBR_MAX ? DWF_MEAS_PBR_MAX : g.gx;
     pl.gx = pl.pbr;
-    pl.lds = DWF_MEAS_BLOCK_MAX * 16;
-    return pl;
+    pl.lds = DWF_BLOCK_MAX * 16;
   }
-  pl.family = kernel == DMK_SOURCE ? DMF_SOURCE : DMF_PROJECT;
-  pl.lps = kernel == DMK_SOURCE ? Ls : 2;
-  pl.block = DWF_MEAS_BLOCK_MAX;
-  const long lanes = (long)(Lx / 2) * pl.lps;
-  pl.gx = (int)((lanes + pl.block - 1) / pl.block);
   return pl;
 }
 

@@ -24,6 +24,59 @@ enum {
   DPF_F32 = 4      // complex<float> storage and arithmetic
 };
 enum { DWF_PLAN_INTS = 8, DWF_LS_MIN = 2, DWF_LS_MAX = 32 };
+constexpr int DWF_BLOCK_MAX = BLOCK;   // the largest block of a domain-wall kernel (launch bounds, LDS sized per lane)
+
+// ---- what the four domain-wall plans (this one, qmg_dwf_eo_plan.h, qmg_dwf_meas_plan.h, qmg_hmc_dwf_plan.h) and their entries share ----
+// the lattice, the Ls bounds, and a half row of a five-dimensional vector within reach of the kernels' 32-bit byte offsets
+inline bool dwf_dims_ok(int Lx, int Ly, int Ls) {
+  return valid_lattice(Lx, Ly) && Ls >= DWF_LS_MIN && Ls <= DWF_LS_MAX && (long)(Lx / 2) * Ls * 32 <= 0x7FFFFFFFl;
+}
+// The grid of the (site, s) lane mapping: gx blocks cover the lps * Lx/2 lanes of a half row, gy = min(rows, 65535) blocks walk
+// the rows.  whole_sites: the block is lps * floor(256 / lps) lanes, so that the lanes of a site never straddle a block (kernels that
+// exchange along s in LDS, or whose lanes stride by whole blocks and keep their s); else 256.
+struct HalfRowGrid { int block, gx, gy; };
+inline HalfRowGrid half_row_grid(int Lx, int lps, long rows, bool whole_sites) {
+  HalfRowGrid g;
+  g.block = whole_sites ? lps * (DWF_BLOCK_MAX / lps) : DWF_BLOCK_MAX;
+  g.gx = (int)(((long)(Lx / 2) * lps + g.block - 1) / g.block);
+  g.gy = rows_on_grid(rows);
+  return g;
+}
+// a plan that launches nothing: refused with a status (the INVALID or the UNSUPPORTED family of the plan), or success with nothing to do
+template <class Plan> inline Plan plan_refused(int status, int family_invalid, int family_unsupported) {
+  Plan pl = {};
+  pl.family = status == QMG_ERR_INVALID ? family_invalid : family_unsupported;
+  pl.status = status;
+  return pl;
+}
+template <class Plan> inline Plan plan_nothing(int family) {
+  Plan pl = {};
+  pl.family = family;
+  return pl;
+}
+// What every entry checks before its plan is asked: dtype, Ls, the systems of the call and, with more than one, the stride between them --
+// at least one five-dimensional vector (and, has4, one four-dimensional one), even in fp32 so that every system stays 16-byte aligned.
+// Entries with a descriptor check d->nc == 2 Ls beside it.
+inline int dwf_entry_check(int dtype, int Lx, int Ly, int Ls, int nsys, size_t stride5, size_t stride4 = 0, bool has4 = false) {
+  if (!valid_dtype(dtype) || Ls < DWF_LS_MIN || Ls > DWF_LS_MAX || nsys < 1 || nsys > BATCH_MAX) return QMG_ERR_INVALID;
+  if (nsys > 1) {
+    const size_t site = (size_t)Lx * Ly;
+    if (stride5 < site * 2 * Ls || (dtype == QMG_C32 && (stride5 & 1))) return QMG_ERR_INVALID;
+    if (has4 && (stride4 < site * 2 || (dtype == QMG_C32 && (stride4 & 1)))) return QMG_ERR_INVALID;
+  }
+  return QMG_SUCCESS;
+}
+// the row members DwfArgs and DwfEoArgs<T> share (their order and types are part of the kernels' device code and stay the structs' own)
+template <class Args>
+inline void dwf_fill_rows(Args& a, const void* gauge, void* lhs, const void* rhs, int Lx, int Ly, int Ls, unsigned pieces, const BatchIdx& b, size_t vec_stride,
+                          int par_first, int par_count) {
+  a.gauge = gauge; a.lhs = lhs; a.rhs = rhs;
+  a.hr = Lx / 2; a.Ly = Ly; a.Ls = Ls;
+  a.half_vol = (long)a.hr * Ly;
+  a.pieces = pieces; a.nrhs = b.n; a.vec_stride = (long)vec_stride;
+  a.par_first = par_first; a.par_count = par_count; a.nrows = Ly * par_count;
+  for (int k = 0; k < 16; k++) a.ridx[k] = b.id[k];
+}
 
 // The first DWF_PLAN_INTS members, in this order, are what qmg_dwf_plan() writes.
 struct DwfPlan {
@@ -40,26 +93,11 @@ struct DwfPlan {
   int par_first, par_count;
 };
 
-namespace dwf_detail {
-inline DwfPlan refused(int status) {
-  DwfPlan pl = {};
-  pl.family = status == QMG_ERR_INVALID ? DF_INVALID : DF_UNSUPPORTED;
-  pl.status = status;
-  return pl;
-}
-inline DwfPlan nothing() {
-  DwfPlan pl = {};
-  pl.family = DF_NOTHING;
-  return pl;
-}
-}  // namespace dwf_detail
-
 // n_active: the systems of the call whose mask bit is set (0 .. 16); inplace: lhs == rhs
 inline DwfPlan dwf_plan(int dtype, int Lx, int Ly, int Ls, unsigned pieces, int n_active, int inplace) {
-  using namespace dwf_detail;
-  if (!valid_dtype(dtype) || !valid_lattice(Lx, Ly) || Ls < DWF_LS_MIN || Ls > DWF_LS_MAX || n_active < 0 || n_active > BATCH_MAX) return refused(QMG_ERR_INVALID);
-  const long lanes = (long)(Lx / 2) * Ls;
-  if (lanes * 32 > 0x7FFFFFFFl) return refused(QMG_ERR_INVALID);   // a half row of the vector is addressed with 32-bit byte offsets
+  const auto refused = [](int status) { return plan_refused<DwfPlan>(status, DF_INVALID, DF_UNSUPPORTED); };
+  const auto nothing = [] { return plan_nothing<DwfPlan>(DF_NOTHING); };
+  if (!valid_dtype(dtype) || !dwf_dims_ok(Lx, Ly, Ls) || n_active < 0 || n_active > BATCH_MAX) return refused(QMG_ERR_INVALID);
   if (n_active == 0) return nothing();
   const PieceShape ps = links_piece_shape(pieces);   // the sets kernel W serves (qmg_wilson_plan.h)
   if (ps.par_count == 0) return nothing();
@@ -68,13 +106,11 @@ inline DwfPlan dwf_plan(int dtype, int Lx, int Ly, int Ls, unsigned pieces, int 
   if (shape == 0) return refused(QMG_ERR_UNSUPPORTED);
   if (inplace && (shape == 1 || par_count == 2)) return refused(QMG_ERR_INVALID);   // in place: one parity written from the other by hops alone
   const bool pair = shape == 1 && par_count == 2;   // the full operator: kernel D2
-  const long nrows = pair ? (long)Ly : (long)Ly * par_count;
+  const HalfRowGrid g = half_row_grid(Lx, Ls, pair ? (long)Ly : (long)Ly * par_count, false);
   DwfPlan pl = {};
   pl.family = pair ? DF_PAIR : DF_DIRECT;
   pl.lps = Ls;
-  pl.block = BLOCK;
-  pl.gx = (int)((lanes + BLOCK - 1) / BLOCK);
-  pl.gy = nrows > 65535 ? 65535 : (int)nrows;
+  pl.block = g.block; pl.gx = g.gx; pl.gy = g.gy;
   pl.flags = (zero ? DPF_ZERO : 0) | (n_active > 1 ? DPF_BATCH : 0) | (dtype == QMG_C32 ? DPF_F32 : 0);
   pl.shape = shape;
   pl.nk = n_active;

@@ -242,16 +242,15 @@ struct HmcDwfPairs {
 };
 
 template <bool GAUGE>
-__global__ __launch_bounds__(HMC_DWF_BLOCK_MAX) void k_hmc_momentum_update_dwf(double* __restrict__ pi, const cplx* __restrict__ gauge, const HmcDwfPairs pr, int n_pairs,
+__global__ __launch_bounds__(DWF_BLOCK_MAX) void k_hmc_momentum_update_dwf(double* __restrict__ pi, const cplx* __restrict__ gauge, const HmcDwfPairs pr, int n_pairs,
                                                                                int g5y, int hr, int Ly, int Ls, double beta, double dt) {
   typedef double v4 __attribute__((ext_vector_type(4)));   // a lane's chunk: (sigma 0 re, im, sigma 1 re, im)
   constexpr unsigned CH = 32u;
-  __shared__ double2 share[2][HMC_DWF_BLOCK_MAX];
+  __shared__ double2 share[2][DWF_BLOCK_MAX];
   const int tid = threadIdx.x;
-  const int t = blockIdx.x * blockDim.x + tid;
-  const bool live = t < hr * Ls;          // a site is live or not as a whole: the block and the half row are multiples of Ls lanes
-  const int jt = t / Ls, s = t - jt * Ls;
-  const int j = live ? jt : 0;
+  const dwf::Lane ln = dwf::lane_of<true>(hr, Ls);   // a site is live or not as a whole: the block and the half row are multiples of Ls lanes
+  const int j = ln.j, s = ln.s;
+  const bool live = ln.live;
   const int base = tid - s;               // the site's shares in LDS: base .. base + Ls - 1, all in this block
   const int sy = g5y ? Ls - 1 - s : s;
   const double g5 = g5y ? -1.0 : 1.0;
@@ -263,6 +262,8 @@ __global__ __launch_bounds__(HMC_DWF_BLOCK_MAX) void k_hmc_momentum_update_dwf(d
   int buf = 0;
   for (int row = blockIdx.y; row < 2 * Ly; row += gridDim.y) {
     const int p = row & 1, y = row >> 1;
+    // dwf::row_of<double, false>'s geometry, written out, in row indices (the links are indexed by site): through the helper both
+    // instantiations keep their 470 / 605 lines of device code but not their order (profiles/dwf_lane_refactor.txt).
     const int sx = (y + p) & 1;
     int jp = j + sx;     if (jp == hr) jp = 0;
     int jm = j + sx - 1; if (jm < 0) jm = hr - 1;
@@ -355,11 +356,11 @@ static bool pole_lists_valid(const void* const* A, const void* const* B, const d
     if (!A[j] || !B[j] || weights[j] != weights[j]) return false;
   return true;
 }
-// Poles in chunks of HMC_POLES_J: launch(j0, nj, first) fills the list of poles j0 .. j0 + nj - 1 and launches its kernel, with the gauge
-// force if `first` and without it after.
-template <class Launch> static int launch_pole_chunks(int n_poles, Launch launch) {
-  for (int j0 = 0; j0 < n_poles; j0 += HMC_POLES_J) {
-    launch(j0, n_poles - j0 < HMC_POLES_J ? n_poles - j0 : HMC_POLES_J, j0 == 0);
+// Poles in chunks of CHUNK (HMC_POLES_J; HMC_DWF_PAIRS for the domain-wall pairs): launch(j0, nj, first) fills the list of poles
+// j0 .. j0 + nj - 1 and launches its kernel, with the gauge force if `first` and without it after.
+template <int CHUNK, class Launch> static int launch_pole_chunks(int n_poles, Launch launch) {
+  for (int j0 = 0; j0 < n_poles; j0 += CHUNK) {
+    launch(j0, n_poles - j0 < CHUNK ? n_poles - j0 : CHUNK, j0 == 0);
     QMG_LAUNCH_CHECK();
   }
   return QMG_SUCCESS;
@@ -391,7 +392,7 @@ int qmg_hmc_momentum_update_poles(double* pi, const void* gauge, const void* con
   if ((flags & QMG_HMC_GAUGE_ONLY) || n_poles == 0) return qmg_hmc_momentum_update(pi, gauge, nullptr, nullptr, Lx, Ly, beta, dt, QMG_HMC_GAUGE_ONLY, stream);
   if (!pole_lists_valid(X, Y, weights, n_poles)) return QMG_ERR_INVALID;
   const unsigned g = grid_1d((size_t)Lx * Ly / 2);
-  return launch_pole_chunks(n_poles, [&](int j0, int nj, bool first) {
+  return launch_pole_chunks<HMC_POLES_J>(n_poles, [&](int j0, int nj, bool first) {
     HmcPoles p;
     for (int j = 0; j < HMC_POLES_J; j++) {
       p.X[j] = j < nj ? (const cplx*)X[j0 + j] : nullptr;
@@ -414,7 +415,7 @@ int qmg_hmc_momentum_update_staggered(double* pi, const void* gauge, const void*
   if ((flags & QMG_HMC_GAUGE_ONLY) || n_poles == 0) return qmg_hmc_momentum_update(pi, gauge, nullptr, nullptr, Lx, Ly, beta, dt, QMG_HMC_GAUGE_ONLY, stream);
   if (!pole_lists_valid(W, W, weights, n_poles)) return QMG_ERR_INVALID;
   const unsigned g = grid_1d((size_t)Lx * Ly / 2);
-  return launch_pole_chunks(n_poles, [&](int j0, int nj, bool first) {
+  return launch_pole_chunks<HMC_POLES_J>(n_poles, [&](int j0, int nj, bool first) {
     HmcStagPoles p;
     for (int j = 0; j < HMC_POLES_J; j++) {
       p.W[j] = j < nj ? (const cplx*)W[j0 + j] : nullptr;
@@ -441,19 +442,16 @@ int qmg_hmc_momentum_update_dwf(double* pi, const void* gauge, const void* const
     if (!aligned16(X[j]) || !aligned16(Y[j])) return QMG_ERR_INVALID;
   const dim3 grid((unsigned)pl.gx, (unsigned)pl.gy);
   const int g5y = (flags & QMG_HMC_DWF_G5_Y) ? 1 : 0;
-  for (int j0 = 0; j0 < n_pairs; j0 += HMC_DWF_PAIRS) {
-    const int nj = n_pairs - j0 < HMC_DWF_PAIRS ? n_pairs - j0 : HMC_DWF_PAIRS;
+  return launch_pole_chunks<HMC_DWF_PAIRS>(n_pairs, [&](int j0, int nj, bool first) {
     HmcDwfPairs p;
     for (int j = 0; j < HMC_DWF_PAIRS; j++) {
       p.X[j] = j < nj ? (const char*)X[j0 + j] : nullptr;
       p.Y[j] = j < nj ? (const char*)Y[j0 + j] : nullptr;
       p.w[j] = j < nj ? weights[j0 + j] : 0.0;
     }
-    if (j0 == 0) k_hmc_momentum_update_dwf<true><<<grid, (unsigned)pl.block, 0, as_stream(stream)>>>(pi, (const cplx*)gauge, p, nj, g5y, Lx / 2, Ly, Ls, beta, dt);
+    if (first) k_hmc_momentum_update_dwf<true><<<grid, (unsigned)pl.block, 0, as_stream(stream)>>>(pi, (const cplx*)gauge, p, nj, g5y, Lx / 2, Ly, Ls, beta, dt);
     else k_hmc_momentum_update_dwf<false><<<grid, (unsigned)pl.block, 0, as_stream(stream)>>>(pi, (const cplx*)gauge, p, nj, g5y, Lx / 2, Ly, Ls, beta, dt);
-    QMG_LAUNCH_CHECK();
-  }
-  return QMG_SUCCESS;
+  });
 }
 
 // What qmg_hmc_momentum_update_dwf launches for a request (host only): plan_out = (family, lanes per site, block, gx, gy, LDS bytes, launches,
@@ -462,7 +460,7 @@ int qmg_hmc_dwf_plan(int Lx, int Ly, int Ls, int n_pairs, unsigned flags, int* p
   if (!plan_out || plan_len < HMC_DWF_PLAN_INTS) return QMG_ERR_INVALID;
   const HmcDwfPlan pl = hmc_dwf_plan(Lx, Ly, Ls, n_pairs, flags);
   const int v[HMC_DWF_PLAN_INTS] = {pl.family, pl.lps, pl.block, pl.gx, pl.gy, pl.lds, pl.launches, pl.per_launch};
-  for (int i = 0; i < plan_len; i++) plan_out[i] = i < HMC_DWF_PLAN_INTS ? v[i] : -1;
+  export_plan_ints(v, HMC_DWF_PLAN_INTS, plan_out, plan_len);
   return QMG_SUCCESS;
 }
 

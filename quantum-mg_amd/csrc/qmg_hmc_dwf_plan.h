@@ -14,7 +14,7 @@ enum HmcDwfFamily {
   HDF_GAUGE = 2,         // the pure-gauge kick of qmg_hmc_momentum_update (its kernel, its bits)
   HDF_INVALID = 3        // the entry point returns QMG_ERR_INVALID
 };
-enum { HMC_DWF_PLAN_INTS = 8, HMC_DWF_BLOCK_MAX = 256, HMC_DWF_PAIRS = 4 };
+enum { HMC_DWF_PLAN_INTS = 8, HMC_DWF_PAIRS = 4 };
 
 // The first HMC_DWF_PLAN_INTS members, in this order, are what qmg_hmc_dwf_plan() writes.
 struct HmcDwfPlan {
@@ -30,12 +30,9 @@ struct HmcDwfPlan {
 };
 
 inline HmcDwfPlan hmc_dwf_plan(int Lx, int Ly, int Ls, int n_pairs, unsigned flags) {
+  if (!dwf_dims_ok(Lx, Ly, Ls) || n_pairs < 0 || (flags & ~(unsigned)(QMG_HMC_GAUGE_ONLY | QMG_HMC_DWF_G5_Y)))
+    return plan_refused<HmcDwfPlan>(QMG_ERR_INVALID, HDF_INVALID, HDF_UNSUPPORTED);
   HmcDwfPlan pl = {};
-  pl.family = HDF_INVALID;
-  pl.status = QMG_ERR_INVALID;
-  if (!valid_lattice(Lx, Ly) || Ls < DWF_LS_MIN || Ls > DWF_LS_MAX || n_pairs < 0 || (flags & ~(unsigned)(QMG_HMC_GAUGE_ONLY | QMG_HMC_DWF_G5_Y))) return pl;
-  const long lanes = (long)(Lx / 2) * Ls;
-  if (lanes * 32 > 0x7FFFFFFFl) return pl;   // a half row of a five-dimensional vector is addressed with 32-bit byte offsets
   pl.status = QMG_SUCCESS;
   if ((flags & QMG_HMC_GAUGE_ONLY) || n_pairs == 0) {
     pl.family = HDF_GAUGE;
@@ -47,10 +44,9 @@ inline HmcDwfPlan hmc_dwf_plan(int Lx, int Ly, int Ls, int n_pairs, unsigned fla
   }
   pl.family = HDF_FUSED;
   pl.lps = Ls;
-  pl.block = Ls * (HMC_DWF_BLOCK_MAX / Ls);
-  pl.gx = (int)((lanes + pl.block - 1) / pl.block);
-  pl.gy = 2l * Ly > 65535 ? 65535 : 2 * Ly;
-  pl.lds = 2 * HMC_DWF_BLOCK_MAX * 16;
+  const HalfRowGrid g = half_row_grid(Lx, Ls, 2l * Ly, true);
+  pl.block = g.block; pl.gx = g.gx; pl.gy = g.gy;
+  pl.lds = 2 * DWF_BLOCK_MAX * 16;
   pl.launches = (n_pairs + HMC_DWF_PAIRS - 1) / HMC_DWF_PAIRS;
   pl.per_launch = HMC_DWF_PAIRS;
   return pl;

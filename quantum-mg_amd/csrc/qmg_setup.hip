@@ -304,7 +304,7 @@ int qmg_setup_plan(int op, int fLx, int fLy, int fnc, int cLx, int cLy, int ncv,
   if (!plan_out || plan_len < SETUP_PLAN_INTS) return QMG_ERR_INVALID;
   const SetupPlan pl = setup_plan(op, fLx, fLy, fnc, cLx, cLy, ncv, a, b);
   const int v[SETUP_PLAN_INTS] = {pl.family, pl.tpb, pl.groups, pl.workgroups, pl.lds, pl.flags, pl.outs, pl.threads};
-  for (int i = 0; i < plan_len; i++) plan_out[i] = i < SETUP_PLAN_INTS ? v[i] : -1;
+  export_plan_ints(v, SETUP_PLAN_INTS, plan_out, plan_len);
   return QMG_SUCCESS;
 }
 

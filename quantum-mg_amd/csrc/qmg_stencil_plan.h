@@ -134,7 +134,6 @@ inline bool slab_generic_served(int mat, bool narrow_under, int nc, int rows) { 
 namespace plan_detail {
 constexpr unsigned EVEN_BITS = QMG_P_CLOVER_E | QMG_P_EO | QMG_P_SHIFT_E | QMG_P_ZERO_E;
 constexpr unsigned ODD_BITS = QMG_P_CLOVER_O | QMG_P_OE | QMG_P_SHIFT_O | QMG_P_ZERO_O;
-inline int rows_on_grid(long n) { return n > 65535 ? 65535 : (int)n; }   // grid.y: blocks walk the rows beyond it
 inline StencilPlan refused(int status) {
   StencilPlan pl = {};
   pl.family = status == QMG_ERR_INVALID ? SF_INVALID : SF_UNSUPPORTED;

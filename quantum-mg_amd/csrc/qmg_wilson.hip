@@ -592,7 +592,7 @@ int qmg_wilson_plan(int dtype, int Lx, int Ly, int nc, int gauge_Ly, int y0, int
   const WilsonPlan pl = wilson_plan(q);
   const int v[WILSON_PLAN_INTS] = {pl.family, pl.lps, pl.block, pl.gx, pl.gy, pl.flags, pl.shape, pl.emode, pl.nk, pl.y_first, pl.y_count, pl.boundary_only,
                                    pl.npart, pl.status, pl.par_first, pl.par_count};
-  for (int i = 0; i < plan_len; i++) plan_out[i] = i < WILSON_PLAN_INTS ? v[i] : -1;
+  export_plan_ints(v, WILSON_PLAN_INTS, plan_out, plan_len);
   return QMG_SUCCESS;
 }
 

@@ -162,7 +162,7 @@ inline WilsonPlan wilson_plan(const WilsonRequest& q) {
   if (full && q.pair >= 2 && q.n_active == 1 && !pl.boundary_only && y_count % 2 == 0 && pl.emode <= 1) { pl.family = WF_PAIR2; nrows = y_count / 2; }
   else if (full && q.pair) { pl.family = WF_PAIR; nrows = y_count; }
   else { pl.family = WF_DIRECT; nrows = (long)y_count * ps.par_count; }
-  pl.gy = nrows > 65535 ? 65535 : (int)nrows;
+  pl.gy = rows_on_grid(nrows);
   if (dotv) {
     // launches with the MR dots keep the number of partials (one per wavefront) small enough for the one-block second stage: the blocks
     // walk several rows each (every kernel W form has the row loop; capping grid.y costs nothing)
