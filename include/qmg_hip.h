@@ -229,6 +229,27 @@ int qmg_hmc_momentum_refresh(double* pi, size_t n, unsigned long long seed, unsi
 /* the generator seed of random field `field` (0 momenta, 1 pseudofermion noise, 2 Metropolis number) of a trajectory */
 unsigned long long qmg_hmc_stream_seed(unsigned long long seed, unsigned long long trajectory, int field);
 
+/* ---- stout-smeared links for the Wilson fermions of the HMC above, and the chain rule of their force (csrc/qmg_stout.hip; not in the
+ * reference); fp64 only ----
+ * One level: theta^(k+1) = theta^(k) - rho C^T sin P^(k), i.e. U^(k+1)_mu(x) = U^(k)_mu(x) exp(-i rho (dS_w/dtheta^(k))_mu(x)), S_w = sum_x (1 - cos P):
+ * an Euler step of the Wilson flow of length rho, gauge covariant.  With (C F)(x) = F_x(x) + F_y(x+xhat) - F_x(x+yhat) - F_y(x) the Jacobian of a
+ * level is the symmetric J_k = 1 - rho C^T diag(cos P^(k)) C.  Fermions on V = U^(n), gauge action on U = U^(0):
+ *   F^(n) = sum_j w_j Ff(X_j, Y_j) on V,   F^(k) = J_k F^(k+1),   pi -= dt (beta C^T sin P^(0) + F^(0)).
+ * Forces F: DEVICE double[2 Lx Ly] in the (mu, eo, y, x) order of the momenta.  Every entry refuses odd or non-positive extents, null
+ * pointers, negative counts and a non-finite rho with QMG_ERR_INVALID and leaves its outputs untouched. */
+/* levels[k] = level k + 1, k = 0 .. n_levels - 1: DEVICE complex<double>[n_levels][2 Lx Ly], each from the level before (level 0 is `gauge`,
+ * which is not copied); one launch per level.  n_levels == 0 does nothing (levels may be null).  levels must not overlap gauge. */
+int qmg_u1_stout_smear(void* levels, const void* gauge, int Lx, int Ly, double rho, int n_levels, void* stream);
+/* F = sum_j weights[j] Ff(X[j], Y[j]) with the links `gauge`, WRITTEN to F, Ff the bilinear of qmg_hmc_momentum_update.  X, Y, weights: the
+ * pole lists of qmg_hmc_momentum_update_poles (HOST arrays of DEVICE spinors, HOST weights); 16 poles per launch, further launches add.
+ * n_poles = 0 zeroes F (X, Y, weights may be null).  Two flavours is one pole of weight 1. */
+int qmg_hmc_fermion_force(double* F, const void* gauge, const void* const* X, const void* const* Y, const double* weights, int n_poles, int Lx, int Ly, void* stream);
+/* F_out = J_k F_in on the links gauge_k of level k, one pass; F_out is overwritten, F_out != F_in (refused otherwise) */
+int qmg_u1_stout_force_level(double* F_out, const double* F_in, const void* gauge_k, int Lx, int Ly, double rho, void* stream);
+/* pi -= dt (beta C^T sin P + J_0 F_in) in one pass over the thin links `gauge`: the gauge force and the last level of the chain rule from the
+ * same plaquettes.  dt = 0 returns the momenta bit for bit; rho = 0 is the gauge kick plus F_in.  pi must not overlap F_in. */
+int qmg_hmc_momentum_update_stout(double* pi, const void* gauge, const double* F_in, int Lx, int Ly, double beta, double rho, double dt, void* stream);
+
 /* ---- gradient (Wilson) flow and Wilson / Polyakov loops for compact U(1) (csrc/qmg_flow.hip; not in the reference); fp64, single domain ----
  * d theta / dt = -dS_w/dtheta, S_w = sum_x (1 - cos P(x)): the gauge force of qmg_hmc_momentum_update at beta = 1.  Luescher's third-order
  * Runge-Kutta step in two registers, Z = -eps dS_w/dtheta:  A = Z, theta += A/4;  A = 8/9 Z - 17/36 A, theta += A;  A = 3/4 Z - A, theta += A.

@@ -54,6 +54,7 @@ ABI_SYMBOLS = [
     "qmg_u1_hot_gauge", "qmg_u1_gauss_gauge", "qmg_u1_random_trans", "qmg_u1_gauge_transform", "qmg_u1_ape_smear", "qmg_u1_instanton", "qmg_u1_noncompact_instanton",
     "qmg_hmc_momentum_update", "qmg_hmc_momentum_update_poles", "qmg_hmc_momentum_update_staggered", "qmg_hmc_link_update", "qmg_hmc_momentum_refresh", "qmg_hmc_stream_seed",
     "qmg_hmc_momentum_update_dwf", "qmg_hmc_dwf_plan",
+    "qmg_u1_stout_smear", "qmg_hmc_fermion_force", "qmg_u1_stout_force_level", "qmg_hmc_momentum_update_stout",
     "qmg_u1_flow_stage", "qmg_u1_flow", "qmg_u1_wilson_loops", "qmg_u1_polyakov",
     "qmg_dwf_fill", "qmg_dwf_apply_direct", "qmg_dwf_plan", "qmg_batch_plan", "qmg_wilson_plan",
     "qmg_dwf_inv5", "qmg_dwf_hops_inv5", "qmg_dwf_schur_apply", "qmg_dwf_eo_plan",
@@ -1098,6 +1099,31 @@ def hmc_stream_seed(seed, trajectory, field):
     f = lib().qmg_hmc_stream_seed
     f.restype = C.c_ulonglong
     return f(C.c_ulonglong(seed), C.c_ulonglong(trajectory), field)
+
+
+def u1_stout_smear(levels, gauge, Lx, Ly, rho, n_levels, stream=None):
+    """levels[k] = stout level k + 1 of `gauge` (n_levels fields of 2 Lx Ly links, back to back); level 0 is `gauge`, which is not copied"""
+    check(lib().qmg_u1_stout_smear(_vp(levels), _vp(gauge), Lx, Ly, C.c_double(rho), n_levels, C.c_void_p(stream)), "qmg_u1_stout_smear")
+
+
+def hmc_fermion_force(F, gauge, X, Y, weights, Lx, Ly, stream=None, n_poles=None):
+    """F = sum_j weights[j] Ff(X[j], Y[j]) on the links `gauge`, written to the link field F; the pole lists of hmc_momentum_update_poles"""
+    n = n_poles if n_poles is not None else (len(weights) if weights is not None else 0)
+    xs = (C.c_void_p * max(len(X), 1))(*[_vp(x).value for x in X]) if X is not None else None
+    ys = (C.c_void_p * max(len(Y), 1))(*[_vp(y).value for y in Y]) if Y is not None else None
+    ws = (C.c_double * max(len(weights), 1))(*[float(w) for w in weights]) if weights is not None else None
+    check(lib().qmg_hmc_fermion_force(_vp(F), _vp(gauge), xs, ys, ws, n, Lx, Ly, C.c_void_p(stream)), "qmg_hmc_fermion_force")
+
+
+def u1_stout_force_level(F_out, F_in, gauge_k, Lx, Ly, rho, stream=None):
+    """F_out = J_k F_in = F_in - rho C^T [cos P . (C F_in)] on the links of level k; F_out is not F_in"""
+    check(lib().qmg_u1_stout_force_level(_vp(F_out), _vp(F_in), _vp(gauge_k), Lx, Ly, C.c_double(rho), C.c_void_p(stream)), "qmg_u1_stout_force_level")
+
+
+def hmc_momentum_update_stout(pi, gauge, F_in, Lx, Ly, beta, rho, dt, stream=None):
+    """pi -= dt (gauge force + J_0 F_in) in one pass over the thin links"""
+    check(lib().qmg_hmc_momentum_update_stout(_vp(pi), _vp(gauge), _vp(F_in), Lx, Ly, C.c_double(beta), C.c_double(rho), C.c_double(dt), C.c_void_p(stream)),
+          "qmg_hmc_momentum_update_stout")
 
 
 def u1_flow_stage(theta, acc, gauge_out, gauge_in, Lx, Ly, eps, stage, stream=None):

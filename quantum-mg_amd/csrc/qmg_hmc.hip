@@ -11,35 +11,12 @@
 //
 // Layouts (lattice.h:75-81): site (x, y) has index (y + p Ly) Lx/2 + x/2, p = (x + y) & 1; phases, momenta and links are [mu][site],
 // spinors [site][2].
+#include "qmg_hmc_bilinear.h"   // ydag_hx, ydag_hy, link_force, HmcPoles, launch_pole_chunks
 #include "qmg_hmc_dwf_plan.h"
 #include "qmg_lane.h"   // uni, gld
 #include "qmg_u1_pair.h"
 
 namespace qmg {
-
-// Y^dag Hp_x X etc. without the factor 1/2 of the projectors (it cancels the 2 of 2 Im[...]).
-//   Hp_x v = (-v0 + v1, v0 - v1)/2      Hm_x v = -(v0 + v1, v0 + v1)/2
-//   Hp_y v = (-v0 - i v1, i v0 - v1)/2  Hm_y v = (-v0 + i v1, -i v0 - v1)/2
-__device__ __forceinline__ cplx ydag_hx(cplx y0, cplx y1, cplx x0, cplx x1, double sgn) {   // sgn = +1: 2 Hp_x, -1: 2 Hm_x
-  const cplx d = cmake(fma(sgn, x1.x, -x0.x), fma(sgn, x1.y, -x0.y));    // -x0 + sgn x1
-  const cplx e = cmake(fma(sgn, x0.x, -x1.x), fma(sgn, x0.y, -x1.y));    // sgn x0 - x1
-  cplx acc = cmake(0.0, 0.0);
-  cmac_conj(acc, y0, d);
-  cmac_conj(acc, y1, e);
-  return acc;
-}
-__device__ __forceinline__ cplx ydag_hy(cplx y0, cplx y1, cplx x0, cplx x1, double sgn) {   // sgn = +1: 2 Hp_y, -1: 2 Hm_y
-  const cplx d = cmake(fma(sgn, x1.y, -x0.x), fma(-sgn, x1.x, -x0.y));   // -x0 - sgn i x1
-  const cplx e = cmake(fma(-sgn, x0.y, -x1.x), fma(sgn, x0.x, -x1.y));   // sgn i x0 - x1
-  cplx acc = cmake(0.0, 0.0);
-  cmac_conj(acc, y0, d);
-  cmac_conj(acc, y1, e);
-  return acc;
-}
-// Im[ U p - conj(U) m ]
-__device__ __forceinline__ double link_force(cplx u, cplx p, cplx m) {
-  return fma(u.x, p.y, u.y * p.x) - fma(u.x, m.y, -u.y * m.x);
-}
 
 // pi -= dt (Fg + Ff), every link in one pass, on the site pairs of qmg_u1_pair.h (its geometry; the loads are the kernel's own, see below): a
 // thread updates the four momenta of its pair from the pair's 15 links and, with fermions, X and Y at five sites (a, b, the site right of b and the two above), all loaded in front of the arithmetic.
@@ -94,15 +71,6 @@ __global__ __launch_bounds__(BLOCK) void k_hmc_momentum_update(double* __restric
     pi[V + sb] = fma(-dt, fby, pby);
   }
 }
-
-// The pole list of one launch of k_hmc_momentum_update_poles: device pointers and weights travel as kernel arguments (the way BatchCgm
-// of qmg_batch.hip carries its shift lists), so a launch needs no table in device memory.
-#define HMC_POLES_J 16
-struct HmcPoles {
-  const cplx* X[HMC_POLES_J];
-  const cplx* Y[HMC_POLES_J];
-  double w[HMC_POLES_J];
-};
 
 // pi -= dt (Fg + sum_j w_j Ff(X_j, Y_j)), every link in one pass: the kick of a rational pseudofermion action
 //   S = c0 phi^dag (1 + sum_j rho_j (D^dag D + mu_j^2)^-1) phi,   X_j = (D^dag D + mu_j^2)^-1 phi,  Y_j = D X_j,  w_j = c0 rho_j.
@@ -345,25 +313,10 @@ __global__ __launch_bounds__(BLOCK) void k_hmc_link_update(double* __restrict__ 
 
 using namespace qmg;
 
-// What the two pole kicks (qmg_hmc_momentum_update_poles, _staggered) check first, and the pole lists they check after the pure-gauge case has left: every vector present (B is the
-// second list of vectors, or A again) and no weight a NaN.
+// What the two pole kicks (qmg_hmc_momentum_update_poles, _staggered) check first; the pole lists they check after the pure-gauge case has
+// left are pole_lists_valid's (qmg_hmc_bilinear.h).
 static bool pole_kick_args_valid(const double* pi, const void* gauge, int Lx, int Ly, double beta, double dt, int n_poles, unsigned flags) {
   return pi && gauge && valid_lattice(Lx, Ly) && beta == beta && dt == dt && n_poles >= 0 && !(flags & ~(unsigned)QMG_HMC_GAUGE_ONLY);
-}
-static bool pole_lists_valid(const void* const* A, const void* const* B, const double* weights, int n_poles) {
-  if (!A || !B || !weights) return false;
-  for (int j = 0; j < n_poles; j++)
-    if (!A[j] || !B[j] || weights[j] != weights[j]) return false;
-  return true;
-}
-// Poles in chunks of CHUNK (HMC_POLES_J; HMC_DWF_PAIRS for the domain-wall pairs): launch(j0, nj, first) fills the list of poles
-// j0 .. j0 + nj - 1 and launches its kernel, with the gauge force if `first` and without it after.
-template <int CHUNK, class Launch> static int launch_pole_chunks(int n_poles, Launch launch) {
-  for (int j0 = 0; j0 < n_poles; j0 += CHUNK) {
-    launch(j0, n_poles - j0 < CHUNK ? n_poles - j0 : CHUNK, j0 == 0);
-    QMG_LAUNCH_CHECK();
-  }
-  return QMG_SUCCESS;
 }
 
 extern "C" {

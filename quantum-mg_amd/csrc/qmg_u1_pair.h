@@ -1,5 +1,5 @@
-// qmg_u1_pair.h -- the site-pair thread mapping of the U(1) link kernels: k_ape_smear (qmg_u1.hip), the three momentum kicks (qmg_hmc.hip) and
-// k_flow_stage (qmg_flow.hip).
+// qmg_u1_pair.h -- the site-pair thread mapping of the U(1) link kernels: k_ape_smear (qmg_u1.hip), the three momentum kicks (qmg_hmc.hip),
+// k_flow_stage (qmg_flow.hip) and the four stout kernels (qmg_stout.hip).
 //
 // Even-odd layout (lattice.h:75-81): site (x, y) has index (y + p Ly) Lx/2 + x/2, p = (x + y) & 1, so the sites of one parity of a row y are
 // Lx/2 consecutive elements.  Thread t owns the PAIR of sites a = (2 xh, y) and b = (2 xh + 1, y), xh = t % (Lx/2), y = t / (Lx/2): one of each
@@ -93,6 +93,38 @@ __device__ __forceinline__ PairForce pair_sin_diffs(const PairLinks& u) {
   PairForce d;
   d.ax = sPa - sPam; d.ay = sPl - sPa;
   d.bx = sPb - sPbm; d.by = sPa - sPb;
+  return d;
+}
+
+// ---- for the stout kernels (qmg_stout.hip): the real part of the plaquettes, and a real link field on the pair's 15 links ----
+__device__ __forceinline__ double re_plaq(cplx a, cplx b, cplx c, cplx d) {   // Re[ a b conj(c) conj(d) ]
+  const cplx ab = cmul(a, b), cd = cmul(c, d);
+  return fma(ab.x, cd.x, ab.y * cd.y);
+}
+
+// A real link field F (a force: [mu][site] doubles) at the 15 links of PairLinks, by the same indices.
+struct PairReals { double ax, ay, bx, by, apx, bpx, amx, amy, bmx, bmy, lx, ly, lpx, ry, rmy; };
+__device__ __forceinline__ PairReals pair_reals(const double* __restrict__ Fx, const double* __restrict__ Fy, const PairGeom& g) {
+  PairReals f;
+  f.ax = Fx[g.sa]; f.ay = Fy[g.sa]; f.bx = Fx[g.sb]; f.by = Fy[g.sb];
+  f.apx = Fx[g.rap + g.xh]; f.bpx = Fx[g.rbp + g.xh];
+  f.amx = Fx[g.ram + g.xh]; f.amy = Fy[g.ram + g.xh]; f.bmx = Fx[g.rbm + g.xh]; f.bmy = Fy[g.rbm + g.xh];
+  f.lx = Fx[g.rb + g.xl]; f.ly = Fy[g.rb + g.xl]; f.lpx = Fx[g.rbp + g.xl];
+  f.ry = Fy[g.ra + g.xr]; f.rmy = Fy[g.ram + g.xr];
+  return f;
+}
+
+// (C^T [cos P . (C F)]) at the pair's four links, C the lattice curl (C F)(x) = F_x(x) + F_y(x+xhat) - F_x(x+yhat) - F_y(x): the five
+// plaquettes of pair_sin_diffs with cos P = Re of the plaquette of the links and the curl of F on the same four links, and its differences.
+__device__ __forceinline__ PairForce pair_cos_curl_diffs(const PairLinks& u, const PairReals& f) {
+  const double ga = re_plaq(u.ax, u.by, u.apx, u.ay) * (f.ax + f.by - f.apx - f.ay);
+  const double gb = re_plaq(u.bx, u.ry, u.bpx, u.by) * (f.bx + f.ry - f.bpx - f.by);
+  const double gam = re_plaq(u.amx, u.bmy, u.ax, u.amy) * (f.amx + f.bmy - f.ax - f.amy);
+  const double gbm = re_plaq(u.bmx, u.rmy, u.bx, u.bmy) * (f.bmx + f.rmy - f.bx - f.bmy);
+  const double gl = re_plaq(u.lx, u.ay, u.lpx, u.ly) * (f.lx + f.ay - f.lpx - f.ly);
+  PairForce d;
+  d.ax = ga - gam; d.ay = gl - ga;
+  d.bx = gb - gbm; d.by = ga - gb;
   return d;
 }
 

@@ -1,8 +1,9 @@
 // rhmc_parity -- the deterministic parts of one-flavour SchwingerHMC (include/qmg/hmc.hpp) on fields the caller supplies, for
 // tests/test_gpu_rhmc.py:
-//   ./rhmc_parity mode L gauge_file dir beta mass tau n_steps cg_eps degree spectrum_lo spectrum_hi
+//   ./rhmc_parity mode L gauge_file dir beta mass tau n_steps cg_eps degree spectrum_lo spectrum_hi [stout_levels stout_rho]
 // gauge_file: phases in the reference's text format (read_phase_u1).  Files under dir are in the device layout, momenta as 2 L^2 doubles and
-// spinors as 2 L^2 complex<double>.  spectrum_hi = 0 takes the facade's default.  Every mode prints the coefficients' line
+// spinors as 2 L^2 complex<double>.  spectrum_hi = 0 takes the facade's default.  stout_levels and stout_rho (default 0 0: thin links) put
+// the fermions of every mode on stout-smeared links; the interval is then that of their operator.  Every mode prints the coefficients' line
 //   [RHMC] n <degree> ra <lo> rb <hi> c0 <c0> delta <delta>
 // mode md:        reads pi.bin and phi.bin; md_evolve forward (theta_fwd.bin, pi_fwd.bin), momenta negated, md_evolve again (theta_back.bin,
 //                 pi_back.bin);  [MD] forward|back dH <dH> cg <multi-shift iterations> converged <0|1> plaq <plaquette>
@@ -18,7 +19,7 @@ using namespace hmc_parity;
 
 int main(int argc, char** argv) {
   qmg_driver::Guard guard;
-  if (argc < 13) { cout << "usage: ./rhmc_parity md|heatbath|rational|action|check L gauge_file dir beta mass tau n_steps cg_eps degree spectrum_lo spectrum_hi\n"; return -1; }
+  if (argc < 13) { cout << "usage: ./rhmc_parity md|heatbath|rational|action|check L gauge_file dir beta mass tau n_steps cg_eps degree spectrum_lo spectrum_hi [stout_levels stout_rho]\n"; return -1; }
   if (!qmg::ok(qmg_init(0), "qmg_init")) return 2;
   const string mode = argv[1];
   const int L = stoi(argv[2]);
@@ -28,6 +29,8 @@ int main(int argc, char** argv) {
   const double cg_eps = stod(argv[9]);
   const int degree = stoi(argv[10]);
   const double lo = stod(argv[11]), hi = stod(argv[12]);
+  const int stout_levels = argc > 13 ? stoi(argv[13]) : 0;
+  const double stout_rho = argc > 14 ? stod(argv[14]) : 0.0;
 
   Lattice2D lat_gauge(L, L, 1);
   const size_t n_links = (size_t)lat_gauge.get_size_gauge(), cv = 2 * (size_t)L * L;
@@ -39,7 +42,7 @@ int main(int argc, char** argv) {
   if (!read_phase_u1(phases, &lat_gauge, gauge_file)) rc = 3;
   if (!rc) {
     HeatbathRng generator(1);
-    SchwingerHMC hmc(phases, L, L, beta, mass, 1, tau, n_steps, cg_eps, 20000, generator, degree, lo, hi);
+    SchwingerHMC hmc(phases, L, L, beta, mass, 1, tau, n_steps, cg_eps, 20000, generator, degree, lo, hi, stout_levels, stout_rho);
     cout << setprecision(17);
     if (!hmc.ok()) rc = 4;
     if (!rc) rhmc_line(hmc);

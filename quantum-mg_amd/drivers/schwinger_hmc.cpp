@@ -24,6 +24,13 @@
 // on the exact interval [mass^2, mass^2 + 4] -- it takes the degree alone, prints [RHMC] with det_bound (1 + delta)^(L^2 / 2) - 1 and no
 // [RHMC-CHECK]:
 //   ./schwinger_hmc L beta mass n_tastes n_traj n_therm n_steps seed out.dat cold|heatbath [degree] staggered
+// A trailing triple `stout <n_levels> <rho>`, behind everything else, puts the Wilson fermions on stout-smeared links (include/qmg/stout.hpp): it
+// is taken off before the wilson|staggered word is looked at and is refused with `staggered`.  The run then prints, before the trajectories,
+//   [STOUT] levels <n_levels> rho <rho>
+// and at the end the plaquette of the last configuration's thin links beside that of the links its fermions saw:
+//   [STOUT-READBACK] plaq <thin> fat <smeared>
+// (stout_smear_u1 on the written links); with an out.dat the smeared links go to out.dat.stout in the same format.
+//   ./schwinger_hmc L beta mass n_flavours n_traj n_therm n_steps seed out.dat cold|heatbath [degree lo [hi]] [wilson] stout <n_levels> <rho>
 #include <cstdlib>
 #include <cmath>
 #include <iomanip>
@@ -46,10 +53,15 @@ static bool range_check_line(SchwingerHMC& hmc) {
 
 int main(int argc, char** argv) {
   qmg_driver::Guard guard;
-  // the discretisation is the last argument, behind out.dat and cold|heatbath
+  // the smearing is the last triple, the discretisation the last argument in front of it, behind out.dat and cold|heatbath
+  int stout_levels = 0;
+  double stout_rho = 0.0;
+  const bool stout = argc > 3 && string(argv[argc - 3]) == "stout";
+  if (stout) { stout_levels = atoi(argv[argc - 2]); stout_rho = atof(argv[argc - 1]); argc -= 3; }
   bool staggered = false;
   if (argc > 11 && (string(argv[argc - 1]) == "staggered" || string(argv[argc - 1]) == "wilson")) { staggered = string(argv[argc - 1]) == "staggered"; argc--; }
   if (argc < 9) { cout << "usage: ./schwinger_hmc L beta mass n_flavours n_traj n_therm n_steps seed [out.dat [cold|heatbath]]\n"; return -1; }
+  if (stout && staggered) { cout << "[QMG-ERROR]: stout smearing is for the Wilson fermions; `staggered` does not take it.\n"; return -1; }
   if (!qmg::ok(qmg_init(0), "qmg_init")) return 2;
   const int L = stoi(argv[1]);
   const double beta = stod(argv[2]), mass = stod(argv[3]);
@@ -81,9 +93,17 @@ int main(int argc, char** argv) {
     if (!hmc.ok()) return qmg_driver::leave(3);
     rc = hmc_run::run<StaggeredSchwingerHMC>(hmc, lat_gauge, n_flavours == 1, nullptr, 0.5 * L * L, n_traj, n_therm, out_cfg);
   } else {
-    SchwingerHMC hmc(phases, L, L, beta, mass, n_flavours, tau, n_steps, cg_eps, cg_max_iter, generator, rhmc_degree, rhmc_lo, rhmc_hi);
+    SchwingerHMC hmc(phases, L, L, beta, mass, n_flavours, tau, n_steps, cg_eps, cg_max_iter, generator, rhmc_degree, rhmc_lo, rhmc_hi, stout_levels, stout_rho);
     if (!hmc.ok()) return qmg_driver::leave(3);
+    if (stout) cout << "[STOUT] levels " << stout_levels << " rho " << stout_rho << "\n";
     rc = hmc_run::run<SchwingerHMC>(hmc, lat_gauge, n_flavours == 1, n_flavours == 1 ? range_check_line : nullptr, 2.0 * L * L, n_traj, n_therm, out_cfg);
+    if (stout) {   // the links the fermions of the last configuration saw
+      complex<double>* fat = allocate_vector<complex<double>>(n_links);
+      stout_smear_u1(fat, hmc.links(), &lat_gauge, stout_rho, stout_levels);
+      cout << "[STOUT-READBACK] plaq " << std::real(get_plaquette_u1(hmc.links(), &lat_gauge)) << " fat " << std::real(get_plaquette_u1(fat, &lat_gauge)) << "\n";
+      if (!out_cfg.empty()) write_gauge_u1(fat, &lat_gauge, out_cfg + ".stout");
+      deallocate_vector(&fat);
+    }
   }
   deallocate_vector(&phases);
   qmg::VecPool::release_all();

@@ -17,6 +17,12 @@
 // one multi-shift CG for Z_j = (Q^2 + nu_j^2)^-1 eta, then phi = c0^(-1/2) [eta + Q (sum_j i s_j Z_j) + sum_j s_j nu_j Z_j].
 // The algorithm samples det r(Q^2)^-1 exactly (the Metropolis test uses the same r); while the spectrum of Q^2 stays inside the interval that
 // weight is within (1 +- delta)^(2 Lx Ly) of det D -- there is no reweighting factor here.  range_check() proves it when the spectrum has left.
+//
+// Stout-smeared fermions (stout_levels > 0; stout.hpp, csrc/qmg_stout.hip): D is D[V], V the stout_levels-fold stout smearing of the links with
+// step stout_rho, while S_g stays on the thin links.  Wherever this class hands links to its operator it hands fermion_links(): the thin links
+// themselves without levels, otherwise the freshly smeared top level.  The solves and both actions read the same on V; the kick becomes the force
+// bilinear on V as a link field, the chain rule down the levels and one fused kernel on the thin links (StoutLinks::kick).  With stout_levels == 0
+// none of that code runs.
 #ifndef QMG_HMC_HPP
 #define QMG_HMC_HPP
 
@@ -24,6 +30,7 @@
 
 #include "hmc_core.hpp"
 #include "operators.hpp"
+#include "stout.hpp"
 
 // SchwingerHMC::range_check: ratio = |xi^dag (r Q^2 r - 1) xi| / xi^dag xi for one Gaussian xi, bound = 2 delta + delta^2.  While the spectrum of
 // Q^2 lies in [spectrum_lo^2, spectrum_hi^2] the ratio cannot exceed the bound for ANY xi, so ok == false proves that it has left the interval.
@@ -36,6 +43,7 @@ class SchwingerHMC : public HmcCore {
   Lattice2D lat_fermion;
   complex<double>*phi, *X, *Y, *tmp1, *tmp2;
   Wilson2D* op;
+  StoutLinks stout;
   std::vector<complex<double>*> Ys;          // one flavour: Y_j per pole (the X_j are HmcCore's sols)
 
   static void apply_normal(complex<double>* lhs, complex<double>* rhs, void* self) {   // lhs = gamma5 D gamma5 D rhs = D^dag D rhs
@@ -46,11 +54,13 @@ class SchwingerHMC : public HmcCore {
     h->op->gamma5(lhs, h->tmp1);
   }
   bool has_fermions() const { return n_flavours != 0; }
-  void operator_takes_links() { op->update_links(gauge); }
+  // the links of the fermion operator on the current `gauge`: the thin links, or their freshly smeared top level
+  complex<double>* fermion_links() { return stout.smear(gauge); }
+  void operator_takes_links() { op->update_links(fermion_links()); }
   // the operator takes the current links; X = (D^dag D)^-1 phi, Y = D X; returns S_f = Re <phi, X>
   double solve_for_force(complex<double>* phi_in, HmcResult& r) {
     if (n_flavours == 1) return solve_poles(phi_in, r);
-    op->update_links(gauge);
+    op->update_links(fermion_links());
     zero_vector(X, cv);
     const inversion_info inv = solver(X, phi_in, (int)cv, cg_max_iter, cg_eps, apply_normal, (void*)this);
     r.cg_iterations += inv.iter;
@@ -60,7 +70,7 @@ class SchwingerHMC : public HmcCore {
   }
   // one flavour: the operator takes the current links; X_j = (D^dag D + mu_j^2)^-1 phi, Y_j = D X_j; returns S_pf
   double solve_poles(complex<double>* phi_in, HmcResult& r) {
-    op->update_links(gauge);
+    op->update_links(fermion_links());
     solve_shifts(phi_in, rat.mu2, r);
     double s = norm2sq(phi_in, cv);
     for (int j = 0; j < rat.n; j++) {
@@ -70,6 +80,12 @@ class SchwingerHMC : public HmcCore {
     return rat.c0 * s;
   }
   void kick(double* p, double dt) {
+    if (stout.on() && n_flavours) {   // the levels are those of the last solve_for_force
+      const double one = 1.0;
+      if (n_flavours == 1) stout.kick(p, gauge, (const void* const*)sols.data(), (const void* const*)Ys.data(), pole_weights.data(), rat.n, beta, dt);
+      else stout.kick(p, gauge, (const void* const*)&X, (const void* const*)&Y, &one, 1, beta, dt);
+      return;
+    }
     if (n_flavours == 1) {
       qmg::ok(qmg_hmc_momentum_update_poles(p, gauge, (const void* const*)sols.data(), (const void* const*)Ys.data(), pole_weights.data(), rat.n, lat_gauge.get_dim_mu(0),
                                             lat_gauge.get_dim_mu(1), beta, dt, 0u, qmg::current_stream()), "qmg_hmc_momentum_update_poles");
@@ -87,7 +103,7 @@ class SchwingerHMC : public HmcCore {
       hb = heatbath(phi, Ys[0]);
     } else {   // phi = D^dag eta = gamma5 D gamma5 eta on the current links: no solve, nothing to count
       polar_vector(theta, gauge, n_links);
-      op->update_links(gauge);
+      op->update_links(fermion_links());
       gaussian(tmp1, cv, qmg_hmc_stream_seed(rng.seed, traj, 1));
       cax(std::sqrt(0.5), tmp1, cv);
       op->gamma5(tmp2, tmp1);
@@ -105,14 +121,19 @@ class SchwingerHMC : public HmcCore {
   // degree of r (1 .. 16) and the interval [spectrum_lo, spectrum_hi] that holds the spectrum of |Q| = (D^dag D)^(1/2).  spectrum_lo is the
   // caller's; spectrum_hi = 0 takes |2 + mass| + 2, an upper bound since the hopping part of D has norm <= 2.  cg_eps is then the tolerance of
   // every shift of the multi-shift CG.  With degree 8 on eps = (lo/hi)^2 = 1e-3, delta = 1.2e-7: det r^-1 is within (1 +- delta)^(2 Lx Ly) of
-  // det D, 2.4e-4 at 32^2 and 6e-5 at 16^2.
+  // det D, 2.4e-4 at 32^2 and 6e-5 at 16^2.  stout_levels (0 .. 8) and stout_rho (>= 0) put the fermions, of either count, on stout-smeared links; the
+  // spectrum is then that of |Q[V]|.  Without fermions the levels are accepted and change nothing.
   SchwingerHMC(double* phase_field, int Lx, int Ly, double beta, double mass, int n_flavours, double tau, int n_steps, double cg_eps, int cg_max_iter, HeatbathRng& generator,
-               int rhmc_degree = 8, double spectrum_lo = 0.0, double spectrum_hi = 0.0)
+               int rhmc_degree = 8, double spectrum_lo = 0.0, double spectrum_hi = 0.0, int stout_levels = 0, double stout_rho = 0.0)
       : HmcCore("SchwingerHMC", "flavour", phase_field, Lx, Ly, beta, tau, n_steps, cg_eps, cg_max_iter, generator), lat_fermion(Lx, Ly, 2), phi(0), X(0), Y(0), tmp1(0),
-        tmp2(0), op(0), mass(mass), n_flavours(n_flavours) {
+        tmp2(0), op(0), stout(Lx, Ly, n_flavours ? stout_levels : 0, stout_rho), mass(mass), n_flavours(n_flavours) {
     cv = (size_t)lat_fermion.get_size_cv();
     rat_fn = apply_normal; rat_data = (void*)this; rat_size = cv;
     if (!admit(n_flavours == 0 || n_flavours == 1 || n_flavours == 2)) return;
+    if (!StoutLinks::valid(stout_levels, stout_rho)) {
+      std::cout << "[QMG-ERROR]: SchwingerHMC: stout smearing needs 0 <= stout_levels <= " << StoutLinks::max_levels << " and a finite stout_rho >= 0.\n";
+      return;
+    }
     if (n_flavours == 1) {
       rat = qmg::zolotarev_inv_sqrt(rhmc_degree, spectrum_lo, spectrum_hi != 0.0 ? spectrum_hi : std::fabs(2.0 + mass) + 2.0);
       if (!rat.ok) { std::cout << "[QMG-ERROR]: SchwingerHMC: one flavour needs 1 <= rhmc_degree <= 16 and 0 < spectrum_lo < spectrum_hi.\n"; return; }
@@ -121,14 +142,14 @@ class SchwingerHMC : public HmcCore {
     if (allocate_core() && n_flavours) {
       phi = allocate_vector<complex<double>>(cv); X = allocate_vector<complex<double>>(cv); Y = allocate_vector<complex<double>>(cv);
       tmp1 = allocate_vector<complex<double>>(cv); tmp2 = allocate_vector<complex<double>>(cv);
-      good = phi && X && Y && tmp1 && tmp2;
+      good = phi && X && Y && tmp1 && tmp2 && stout.ok();
       for (int j = 0; j < rat.n; j++) {
         sols.push_back(allocate_vector<complex<double>>(cv)); Ys.push_back(allocate_vector<complex<double>>(cv));
         good = good && sols.back() && Ys.back();
       }
       if (good) {
         polar_vector(theta, gauge, n_links);
-        op = new Wilson2D(&lat_fermion, mass, gauge);
+        op = new Wilson2D(&lat_fermion, mass, fermion_links());
       }
     }
     if (!good) std::cout << "[QMG-ERROR]: SchwingerHMC: out of device memory.\n";
@@ -145,7 +166,7 @@ class SchwingerHMC : public HmcCore {
     HmcResult r;
     if (refused(good && n_flavours == 1, "heatbath", one_flavour_object(), r)) return r;
     polar_vector(theta, gauge, n_links);
-    op->update_links(gauge);
+    op->update_links(fermion_links());
     solve_shifts(eta, rat.nu2, r);                          // Z_j
     zero_vector(Y, cv);                                      // sum_j i s_j Z_j
     copy_vector(phi_out, eta, cv);                           // eta + sum_j s_j nu_j Z_j
@@ -173,7 +194,7 @@ class SchwingerHMC : public HmcCore {
     if (!good || n_flavours != 1) { std::cout << "[QMG-ERROR]: SchwingerHMC::range_check needs a one-flavour object.\n"; return c; }
     HmcResult r;
     polar_vector(theta, gauge, n_links);
-    op->update_links(gauge);
+    op->update_links(fermion_links());
     gaussian(X, cv, seed);
     const double n2 = norm2sq(X, cv);
     rational_on_links(Y, X, r);

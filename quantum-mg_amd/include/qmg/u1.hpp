@@ -152,6 +152,23 @@ inline void apply_ape_smear_u1(complex<double>* smeared_field, complex<double>* 
   qmg::ok(qmg_u1_ape_smear(smeared_field, gauge_field, lat->get_dim_mu(0), lat->get_dim_mu(1), alpha, n_iter, qmg::current_stream()), "qmg_u1_ape_smear");
 }
 
+// Stout smearing (not in the reference; csrc/qmg_stout.hip): n_levels times U_mu(x) <- U_mu(x) exp(-i rho dS_w/dtheta_mu(x)), S_w = sum_x (1 - cos P(x)).
+// smeared_field receives the top level alone -- the links an ensemble generated by SchwingerHMC with (stout_levels, stout_rho) = (n_levels, rho)
+// has its fermions on.  smeared_field must not be gauge_field; n_levels == 0 copies.  The lower levels live in a buffer of the call's own.
+inline void stout_smear_u1(complex<double>* smeared_field, complex<double>* gauge_field, Lattice2D* lat, double rho, int n_levels) {
+  if (lat->get_nc() != 1) { std::cout << "[QMG-ERROR]: U1 gauge functions require Nc = 1 lattice.\n"; return; }
+  if (n_levels < 0 || smeared_field == gauge_field) { std::cout << "[QMG-ERROR]: stout_smear_u1 needs n_levels >= 0 and smeared_field != gauge_field.\n"; return; }
+  const int Lx = lat->get_dim_mu(0), Ly = lat->get_dim_mu(1);
+  const size_t n = (size_t)lat->get_size_gauge();
+  if (n_levels == 0) { copy_vector(smeared_field, gauge_field, n); return; }
+  if (n_levels == 1) { qmg::ok(qmg_u1_stout_smear(smeared_field, gauge_field, Lx, Ly, rho, 1, qmg::current_stream()), "qmg_u1_stout_smear"); return; }
+  complex<double>* lower = allocate_vector<complex<double>>(n * (size_t)(n_levels - 1));
+  if (!lower) { std::cout << "[QMG-ERROR]: stout_smear_u1: out of device memory.\n"; return; }
+  qmg::ok(qmg_u1_stout_smear(lower, gauge_field, Lx, Ly, rho, n_levels - 1, qmg::current_stream()), "qmg_u1_stout_smear");
+  qmg::ok(qmg_u1_stout_smear(smeared_field, lower + n * (size_t)(n_levels - 2), Lx, Ly, rho, 1, qmg::current_stream()), "qmg_u1_stout_smear");
+  deallocate_vector(&lower);
+}
+
 inline void create_instanton_u1(complex<double>* gauge_field, Lattice2D* lat, double Q, const int x0, const int y0) {   // :545-572
   if (lat->get_nc() != 1) { std::cout << "[QMG-ERROR]: U1 gauge functions require Nc = 1 lattice.\n"; return; }
   qmg::ok(qmg_u1_instanton(gauge_field, lat->get_dim_mu(0), lat->get_dim_mu(1), Q, x0, y0, qmg::current_stream()), "qmg_u1_instanton");
