@@ -224,6 +224,11 @@ int qmg_hmc_momentum_update_dwf(double* pi, const void* gauge, const void* const
 int qmg_hmc_dwf_plan(int Lx, int Ly, int Ls, int n_pairs, unsigned flags, int* plan_out, int plan_len);
 /* theta += dt pi ; gauge = exp(i theta) in one pass over n = 2 Lx Ly links */
 int qmg_hmc_link_update(double* theta, void* gauge, const double* pi, size_t n, double dt, void* stream);
+/* One step of a pure-gauge inner loop in one launch:  pi -= dt_kick beta C^T sin P(gauge_in) ;  theta += dt_drift pi ;  gauge_out = exp(i theta).
+ * The bits of qmg_hmc_momentum_update (QMG_HMC_GAUGE_ONLY, dt_kick) followed by qmg_hmc_link_update (dt_drift) in pi, theta and the links.
+ * gauge_out != gauge_in (neighbours are read from gauge_in); overlapping or null fields, bad extents and a NaN beta or dt are refused with
+ * QMG_ERR_INVALID and nothing is written. */
+int qmg_hmc_gauge_step(double* theta, void* gauge_out, const void* gauge_in, double* pi, int Lx, int Ly, double beta, double dt_kick, double dt_drift, void* stream);
 /* pi ~ N(0, 1) per link from the counter-based generator, a function of (seed, trajectory) alone; n even */
 int qmg_hmc_momentum_refresh(double* pi, size_t n, unsigned long long seed, unsigned long long trajectory, void* stream);
 /* the generator seed of random field `field` (0 momenta, 1 pseudofermion noise, 2 Metropolis number) of a trajectory */

@@ -53,7 +53,7 @@ ABI_SYMBOLS = [
     "qmg_u1_heatbath_noncompact", "qmg_u1_phase_to_gauge", "qmg_u1_gauge_to_phase", "qmg_u1_plaquette", "qmg_u1_noncompact_action",
     "qmg_u1_hot_gauge", "qmg_u1_gauss_gauge", "qmg_u1_random_trans", "qmg_u1_gauge_transform", "qmg_u1_ape_smear", "qmg_u1_instanton", "qmg_u1_noncompact_instanton",
     "qmg_hmc_momentum_update", "qmg_hmc_momentum_update_poles", "qmg_hmc_momentum_update_staggered", "qmg_hmc_link_update", "qmg_hmc_momentum_refresh", "qmg_hmc_stream_seed",
-    "qmg_hmc_momentum_update_dwf", "qmg_hmc_dwf_plan",
+    "qmg_hmc_momentum_update_dwf", "qmg_hmc_dwf_plan", "qmg_hmc_gauge_step",
     "qmg_u1_stout_smear", "qmg_hmc_fermion_force", "qmg_u1_stout_force_level", "qmg_hmc_momentum_update_stout",
     "qmg_u1_flow_stage", "qmg_u1_flow", "qmg_u1_wilson_loops", "qmg_u1_polyakov",
     "qmg_dwf_fill", "qmg_dwf_apply_direct", "qmg_dwf_plan", "qmg_batch_plan", "qmg_wilson_plan",
@@ -1089,6 +1089,12 @@ def hmc_dwf_plan(dims, Ls, n_pairs, flags=0):
 def hmc_link_update(theta, gauge, pi, n, dt, stream=None):
     """theta += dt pi ; gauge = exp(i theta)"""
     check(lib().qmg_hmc_link_update(_vp(theta), _vp(gauge), _vp(pi), C.c_size_t(n), C.c_double(dt), C.c_void_p(stream)), "qmg_hmc_link_update")
+
+
+def hmc_gauge_step(theta, gauge_out, gauge_in, pi, Lx, Ly, beta, dt_kick, dt_drift, stream=None):
+    """pi -= dt_kick (gauge force on gauge_in) ; theta += dt_drift pi ; gauge_out = exp(i theta), one launch; gauge_out is not gauge_in"""
+    check(lib().qmg_hmc_gauge_step(_vp(theta), _vp(gauge_out), _vp(gauge_in), _vp(pi), Lx, Ly, C.c_double(beta), C.c_double(dt_kick), C.c_double(dt_drift),
+                                   C.c_void_p(stream)), "qmg_hmc_gauge_step")
 
 
 def hmc_momentum_refresh(pi, n, seed, trajectory, stream=None):

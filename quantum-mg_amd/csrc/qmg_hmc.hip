@@ -309,6 +309,46 @@ __global__ __launch_bounds__(BLOCK) void k_hmc_link_update(double* __restrict__ 
   }
 }
 
+// One step of the pure-gauge inner loop of a two-scale integrator in one pass, on the site pairs of qmg_u1_pair.h:
+//   pi -= dt_kick beta C^T sin P(in) ;  theta += dt_drift pi ;  out = exp(i theta)
+// A thread owns the four links of its pair: four momenta, four phases and the pair's 15 links of `in`, all loaded in front of the arithmetic.
+// The kick is k_hmc_momentum_update<false>'s expression (beta times the difference of sin P, one fma onto the momentum), the drift and the
+// sincos are k_hmc_link_update's, so the three fields carry the bits of those two launches.  out != in: neighbours are read from `in`.
+// Byte model: 128 B/site -- pi read and written (32), theta read and written (32), two links read (32), two written (32).
+// Blocks of 128 threads (grid_1d with that block): at 2048^2 a step took 0.114 ms against 0.127 ms in blocks of 256 (profiles/hmc_gauge_step_bench.txt).
+constexpr int GAUGE_STEP_BLOCK = 128;
+__global__ __launch_bounds__(GAUGE_STEP_BLOCK) void k_hmc_gauge_step(double* __restrict__ theta, cplx* __restrict__ out, const cplx* __restrict__ in, double* __restrict__ pi,
+                                                          int Lx, int Ly, double beta, double dt_kick, double dt_drift) {
+  const long V = (long)Lx * Ly;
+  const int h = Lx >> 1;
+  const long npairs = V / 2;
+  const cplx* __restrict__ Ux = in;
+  const cplx* __restrict__ Uy = in + V;
+  for (long t = (long)blockIdx.x * GAUGE_STEP_BLOCK + threadIdx.x; t < npairs; t += (long)gridDim.x * GAUGE_STEP_BLOCK) {
+    const PairGeom g = pair_geom(t, h, Ly);
+    const long sa = g.sa, sb = g.sb;
+    const double pax = pi[sa], pay = pi[V + sa], pbx = pi[sb], pby = pi[V + sb];
+    const double tax = theta[sa], tay = theta[V + sa], tbx = theta[sb], tby = theta[V + sb];
+    const PairForce d = pair_sin_diffs(pair_links(Ux, Uy, g));
+
+    const double fax = beta * d.ax, fay = beta * d.ay, fbx = beta * d.bx, fby = beta * d.by;
+    const double nax = fma(-dt_kick, fax, pax), nay = fma(-dt_kick, fay, pay), nbx = fma(-dt_kick, fbx, pbx), nby = fma(-dt_kick, fby, pby);
+    const double hax = fma(dt_drift, nax, tax), hay = fma(dt_drift, nay, tay), hbx = fma(dt_drift, nbx, tbx), hby = fma(dt_drift, nby, tby);
+    // The eight real stores first, so that only the four new phases live on into the sincos calls, and those in a loop that stays rolled: 92
+    // VGPRs and 5 waves per SIMD, where the four calls written out between the stores took 138 and 3 (profiles/hmc_gauge_step_resource_usage.txt).
+    pi[sa] = nax; pi[V + sa] = nay; pi[sb] = nbx; pi[V + sb] = nby;
+    theta[sa] = hax; theta[V + sa] = hay; theta[sb] = hbx; theta[V + sb] = hby;
+    const double hs[4] = {hax, hay, hbx, hby};
+    const long is[4] = {sa, V + sa, sb, V + sb};
+#pragma unroll 1
+    for (int k = 0; k < 4; k++) {
+      double s, c;
+      sincos(hs[k], &s, &c);
+      out[is[k]] = cmake(c, s);
+    }
+  }
+}
+
 }  // namespace qmg
 
 using namespace qmg;
@@ -423,6 +463,20 @@ int qmg_hmc_link_update(double* theta, void* gauge, const double* pi, size_t n, 
   if (dt != dt) return QMG_ERR_INVALID;
   if (n == 0) return QMG_SUCCESS;
   k_hmc_link_update<<<grid_1d(n), BLOCK, 0, as_stream(stream)>>>(theta, (cplx*)gauge, pi, (long)n, dt);
+  QMG_LAUNCH_CHECK();
+  return QMG_SUCCESS;
+}
+
+// pi -= dt_kick beta C^T sin P(gauge_in) ; theta += dt_drift pi ; gauge_out = exp(i theta), one launch: the bits of qmg_hmc_momentum_update with
+// QMG_HMC_GAUGE_ONLY and dt_kick followed by qmg_hmc_link_update with dt_drift.  theta, pi: DEVICE double[2 Lx Ly]; gauge_in, gauge_out: DEVICE
+// complex<double>[2 Lx Ly], DIFFERENT buffers (neighbours are read from gauge_in); no two of the four fields may overlap.
+int qmg_hmc_gauge_step(double* theta, void* gauge_out, const void* gauge_in, double* pi, int Lx, int Ly, double beta, double dt_kick, double dt_drift, void* stream) {
+  if (!theta || !gauge_out || !gauge_in || !pi || !valid_lattice(Lx, Ly) || beta != beta || dt_kick != dt_kick || dt_drift != dt_drift) return QMG_ERR_INVALID;
+  const size_t n = 2 * (size_t)Lx * Ly, nr = sizeof(double) * n, nc = sizeof(cplx) * n;
+  if (fields_overlap(gauge_out, nc, gauge_in, nc) || fields_overlap(theta, nr, pi, nr) || fields_overlap(theta, nr, gauge_in, nc) || fields_overlap(theta, nr, gauge_out, nc) ||
+      fields_overlap(pi, nr, gauge_in, nc) || fields_overlap(pi, nr, gauge_out, nc))
+    return QMG_ERR_INVALID;
+  k_hmc_gauge_step<<<grid_1d((size_t)Lx * Ly / 2, GAUGE_STEP_BLOCK), GAUGE_STEP_BLOCK, 0, as_stream(stream)>>>(theta, (cplx*)gauge_out, (const cplx*)gauge_in, pi, Lx, Ly, beta, dt_kick, dt_drift);
   QMG_LAUNCH_CHECK();
   return QMG_SUCCESS;
 }

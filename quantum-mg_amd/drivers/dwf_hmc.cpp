@@ -8,6 +8,8 @@
 //   [HMC-FINAL] trajectories <n> acceptance <rate> exp_mdH <mean> +/- <error> plaq <mean> +/- <error> unconverged <count>
 // out.dat receives the last configuration through write_gauge_u1 (the format dwf_measure reads) and is read back through read_gauge_u1:
 //   [HMC-READBACK] plaq <plaquette> Q <charge>.
+// A trailing triple `integrator <leapfrog|omelyan> <n_gauge>` chooses the molecular dynamics (HmcCore::set_integrator) and is echoed before the
+// trajectories:  [INTEGRATOR] scheme <leapfrog|omelyan> n_gauge <n_gauge>.  Without it: leapfrog on one scale.
 // Exit status 1 if any CG did not converge, 3 if the object was refused.
 #include <iostream>
 #include <string>
@@ -20,6 +22,7 @@ using namespace std;
 
 int main(int argc, char** argv) {
   qmg_driver::Guard guard;
+  const hmc_run::Integrator integrator = hmc_run::Integrator::peel(argc, argv);   // the trailing `integrator <leapfrog|omelyan> <n_gauge>`, if any
   if (argc < 10) { cout << "usage: ./dwf_hmc L Ls beta mass n_flavours n_traj n_therm n_steps seed [out.dat [cold|heatbath]]\n"; return -1; }
   if (!qmg::ok(qmg_init(0), "qmg_init")) return 2;
   const int L = stoi(argv[1]), Ls = stoi(argv[2]);
@@ -40,7 +43,10 @@ int main(int argc, char** argv) {
   int rc = 3;
   {
     DomainWallSchwingerHMC hmc(phases, L, L, Ls, beta, mass, n_flavours, tau, n_steps, cg_eps, cg_max_iter, generator);
-    if (hmc.ok()) rc = hmc_run::run<DomainWallSchwingerHMC>(hmc, lat_gauge, false, nullptr, 0.0, n_traj, n_therm, out_cfg);
+    if (hmc.ok() && integrator.apply(hmc)) {
+      integrator.line();
+      rc = hmc_run::run<DomainWallSchwingerHMC>(hmc, lat_gauge, false, nullptr, 0.0, n_traj, n_therm, out_cfg);
+    }
   }
   deallocate_vector(&phases);
   qmg::VecPool::release_all();

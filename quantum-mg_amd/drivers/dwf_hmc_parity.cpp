@@ -6,6 +6,7 @@
 // mode md:        reads pi.bin and phi.bin; md_evolve forward (theta_fwd.bin, pi_fwd.bin), momenta negated, md_evolve again (theta_back.bin,
 //                 pi_back.bin);  [MD] forward|back dH <dH> cg <CG iterations> converged <0|1> plaq <plaquette>
 // mode heatbath:  reads eta.bin (even sites); phi to phi.bin;  [HB] eta2 <eta^dag eta> spf <S_f(phi)> cg <iterations> converged <0|1>
+// A trailing `integrator <leapfrog|omelyan> <n_gauge>`, behind everything else, sets HmcCore::set_integrator for mode md.
 // Exit status 1 if a solve did not converge.
 #include "hmc_parity_common.hpp"
 
@@ -14,6 +15,7 @@ using namespace hmc_parity;
 
 int main(int argc, char** argv) {
   qmg_driver::Guard guard;
+  const hmc_run::Integrator integrator = hmc_run::Integrator::peel(argc, argv);   // the trailing `integrator <leapfrog|omelyan> <n_gauge>`, if any
   if (argc < 12) { cout << "usage: ./dwf_hmc_parity md|heatbath L Ls gauge_file dir beta mass tau n_steps cg_eps n_flavours\n"; return -1; }
   if (!qmg::ok(qmg_init(0), "qmg_init")) return 2;
   const string mode = argv[1];
@@ -36,7 +38,7 @@ int main(int argc, char** argv) {
     HeatbathRng generator(1);
     DomainWallSchwingerHMC hmc(phases, L, L, Ls, beta, mass, n_flavours, tau, n_steps, cg_eps, 20000, generator);
     cout << setprecision(17);
-    if (!hmc.ok()) rc = 4;
+    if (!hmc.ok() || !integrator.apply(hmc)) rc = 4;
     if (rc) {   // refused
     } else if (mode == "md") {
       rc = load(dir + "/pi.bin", pi, n_links) && load(dir + "/phi.bin", a, half) ? md_legs(hmc, dir, phases, pi, a, n_links) : 3;

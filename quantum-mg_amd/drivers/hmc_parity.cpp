@@ -2,7 +2,7 @@
 //   ./hmc_parity L gauge_file dir beta mass n_flavours tau n_steps cg_eps [stout_levels stout_rho]
 // gauge_file: phases in the reference's text format (read_phase_u1).  dir/pi.bin: 2 L^2 doubles, dir/phi.bin: 2 L^2 complex<double>, both in
 // the device layout.  Runs md_evolve forward, dumps dir/theta_fwd.bin and dir/pi_fwd.bin, negates the momenta, runs md_evolve again and dumps
-// dir/theta_back.bin and dir/pi_back.bin.  stout_levels and stout_rho (default 0 0: thin links) put the fermions on stout-smeared links.  Prints
+// dir/theta_back.bin and dir/pi_back.bin.  A trailing `integrator <leapfrog|omelyan> <n_gauge>`, behind everything else, sets HmcCore::set_integrator.  stout_levels and stout_rho (default 0 0: thin links) put the fermions on stout-smeared links.  Prints
 //   [MD] forward dH <dH> cg <iterations> converged <0|1> plaq <plaquette>
 //   [MD] back    dH <dH> cg <iterations> converged <0|1> plaq <plaquette>
 #include "hmc_parity_common.hpp"
@@ -12,6 +12,7 @@ using namespace hmc_parity;
 
 int main(int argc, char** argv) {
   qmg_driver::Guard guard;
+  const hmc_run::Integrator integrator = hmc_run::Integrator::peel(argc, argv);   // the trailing `integrator <leapfrog|omelyan> <n_gauge>`, if any
   if (argc < 10) { cout << "usage: ./hmc_parity L gauge_file dir beta mass n_flavours tau n_steps cg_eps [stout_levels stout_rho]\n"; return -1; }
   if (!qmg::ok(qmg_init(0), "qmg_init")) return 2;
   const int L = stoi(argv[1]);
@@ -35,7 +36,7 @@ int main(int argc, char** argv) {
     HeatbathRng generator(1);
     SchwingerHMC hmc(phases, L, L, beta, mass, n_flavours, tau, n_steps, cg_eps, 20000, generator, 8, 0.0, 0.0, stout_levels, stout_rho);
     cout << setprecision(17);
-    rc = hmc.ok() ? md_legs(hmc, dir, phases, pi, phi, n_links) : 4;
+    rc = hmc.ok() && integrator.apply(hmc) ? md_legs(hmc, dir, phases, pi, phi, n_links) : 4;
   }
   deallocate_vector(&phases); deallocate_vector(&pi); deallocate_vector(&phi);
   qmg::VecPool::release_all();

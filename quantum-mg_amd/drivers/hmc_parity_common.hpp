@@ -12,6 +12,7 @@
 
 #include "../include/qmg/qmg.hpp"
 #include "driver_common.hpp"
+#include "hmc_run_common.hpp"   // the trailing `integrator <scheme> <n_gauge>` group
 
 namespace hmc_parity {
 

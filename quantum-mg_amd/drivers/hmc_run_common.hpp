@@ -4,6 +4,7 @@
 #define QMG_HMC_RUN_COMMON_HPP
 
 #include <cmath>
+#include <cstdlib>
 #include <iomanip>
 #include <iostream>
 #include <string>
@@ -12,6 +13,37 @@
 #include "../include/qmg/qmg.hpp"
 
 namespace hmc_run {
+
+// The trailing group `integrator <leapfrog|omelyan> <n_gauge>` of a command line (HmcCore::set_integrator), behind everything else: peel()
+// takes it off argc before anything else is looked at; apply() sets it on an HMC object.  Without the group nothing is set.
+struct Integrator {
+  bool given, known;
+  MdScheme scheme;
+  int n_gauge;
+  Integrator() : given(false), known(true), scheme(MD_LEAPFROG), n_gauge(0) {}
+  const char* scheme_name() const { return scheme == MD_OMELYAN ? "omelyan" : "leapfrog"; }
+  static Integrator peel(int& argc, char** argv) {
+    Integrator in;
+    if (argc > 3 && std::string(argv[argc - 3]) == "integrator") {
+      const std::string word = argv[argc - 2];
+      in.given = true;
+      in.known = word == "leapfrog" || word == "omelyan";
+      in.scheme = word == "omelyan" ? MD_OMELYAN : MD_LEAPFROG;
+      in.n_gauge = atoi(argv[argc - 1]);
+      argc -= 3;
+    }
+    return in;
+  }
+  // false (and a line) if the group names no scheme or the object refuses it
+  template <class HMC> bool apply(HMC& hmc) const {
+    if (!given) return true;
+    if (!known) { std::cout << "[QMG-ERROR]: integrator takes leapfrog or omelyan.\n"; return false; }
+    return hmc.set_integrator(scheme, n_gauge);
+  }
+  void line() const {
+    if (given) std::cout << "[INTEGRATOR] scheme " << scheme_name() << " n_gauge " << n_gauge << "\n";
+  }
+};
 
 // the trajectories, the final lines and the written configuration; returns the exit status.  one_flavour: a rational action, whose [RHMC] line
 // is printed first (rhmc_sites: the exponent of its determinant bound).  range_check: null, or what proves after the thermalisation and at

@@ -11,6 +11,7 @@
 // mode rational:  reads v.bin; r(Q^2) v to rv.bin and r(Q^2) r(Q^2) v to rrv.bin;  [RAT] cg <iterations> converged <0|1>
 // mode action:    reads phi.bin;  [SPF] <S_pf(phi)> cg <iterations> converged <0|1>
 // mode check:     [RHMC-CHECK] ratio <ratio> bound <bound> ok <0|1>
+// A trailing `integrator <leapfrog|omelyan> <n_gauge>`, behind everything else, sets HmcCore::set_integrator for mode md.
 // Exit status 1 if a solve did not converge.
 #include "hmc_parity_common.hpp"
 
@@ -19,6 +20,7 @@ using namespace hmc_parity;
 
 int main(int argc, char** argv) {
   qmg_driver::Guard guard;
+  const hmc_run::Integrator integrator = hmc_run::Integrator::peel(argc, argv);   // the trailing `integrator <leapfrog|omelyan> <n_gauge>`, if any
   if (argc < 13) { cout << "usage: ./rhmc_parity md|heatbath|rational|action|check L gauge_file dir beta mass tau n_steps cg_eps degree spectrum_lo spectrum_hi [stout_levels stout_rho]\n"; return -1; }
   if (!qmg::ok(qmg_init(0), "qmg_init")) return 2;
   const string mode = argv[1];
@@ -44,7 +46,7 @@ int main(int argc, char** argv) {
     HeatbathRng generator(1);
     SchwingerHMC hmc(phases, L, L, beta, mass, 1, tau, n_steps, cg_eps, 20000, generator, degree, lo, hi, stout_levels, stout_rho);
     cout << setprecision(17);
-    if (!hmc.ok()) rc = 4;
+    if (!hmc.ok() || !integrator.apply(hmc)) rc = 4;
     if (!rc) rhmc_line(hmc);
     if (rc) {   // refused
     } else if (mode == "md") {

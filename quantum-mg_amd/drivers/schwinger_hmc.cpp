@@ -31,6 +31,10 @@
 //   [STOUT-READBACK] plaq <thin> fat <smeared>
 // (stout_smear_u1 on the written links); with an out.dat the smeared links go to out.dat.stout in the same format.
 //   ./schwinger_hmc L beta mass n_flavours n_traj n_therm n_steps seed out.dat cold|heatbath [degree lo [hi]] [wilson] stout <n_levels> <rho>
+// A trailing triple `integrator <leapfrog|omelyan> <n_gauge>`, behind everything else (the stout triple included), chooses the molecular dynamics
+// (HmcCore::set_integrator): the scheme, and with n_gauge >= 1 that many gauge steps inside every drift of the fermion scale.  The run then prints
+//   [INTEGRATOR] scheme <leapfrog|omelyan> n_gauge <n_gauge>
+// before the trajectories.  Without it: leapfrog on one scale.
 #include <cstdlib>
 #include <cmath>
 #include <iomanip>
@@ -53,6 +57,7 @@ static bool range_check_line(SchwingerHMC& hmc) {
 
 int main(int argc, char** argv) {
   qmg_driver::Guard guard;
+  const hmc_run::Integrator integrator = hmc_run::Integrator::peel(argc, argv);   // the trailing `integrator <leapfrog|omelyan> <n_gauge>`, if any
   // the smearing is the last triple, the discretisation the last argument in front of it, behind out.dat and cold|heatbath
   int stout_levels = 0;
   double stout_rho = 0.0;
@@ -90,11 +95,13 @@ int main(int argc, char** argv) {
   int rc = 0;
   if (staggered) {
     StaggeredSchwingerHMC hmc(phases, L, L, beta, mass, n_flavours, tau, n_steps, cg_eps, cg_max_iter, generator, rhmc_degree);
-    if (!hmc.ok()) return qmg_driver::leave(3);
+    if (!hmc.ok() || !integrator.apply(hmc)) return qmg_driver::leave(3);
+    integrator.line();
     rc = hmc_run::run<StaggeredSchwingerHMC>(hmc, lat_gauge, n_flavours == 1, nullptr, 0.5 * L * L, n_traj, n_therm, out_cfg);
   } else {
     SchwingerHMC hmc(phases, L, L, beta, mass, n_flavours, tau, n_steps, cg_eps, cg_max_iter, generator, rhmc_degree, rhmc_lo, rhmc_hi, stout_levels, stout_rho);
-    if (!hmc.ok()) return qmg_driver::leave(3);
+    if (!hmc.ok() || !integrator.apply(hmc)) return qmg_driver::leave(3);
+    integrator.line();
     if (stout) cout << "[STOUT] levels " << stout_levels << " rho " << stout_rho << "\n";
     rc = hmc_run::run<SchwingerHMC>(hmc, lat_gauge, n_flavours == 1, n_flavours == 1 ? range_check_line : nullptr, 2.0 * L * L, n_traj, n_therm, out_cfg);
     if (stout) {   // the links the fermions of the last configuration saw

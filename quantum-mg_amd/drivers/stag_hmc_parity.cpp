@@ -8,6 +8,7 @@
 //                 pi_back.bin);  [MD] forward|back dH <dH> cg <CG iterations> converged <0|1> plaq <plaquette>
 // mode heatbath:  reads eta.bin (full lattice); phi_e to phi.bin;  [HB] eta2 <eta^dag eta> spf <S_pf(phi_e)> cg <iterations> converged <0|1>
 // mode rational:  one taste; reads v.bin; r(A_ee) v to rv.bin and r(A_ee) r(A_ee) v to rrv.bin;  [RAT] cg <iterations> converged <0|1>
+// A trailing `integrator <leapfrog|omelyan> <n_gauge>`, behind everything else, sets HmcCore::set_integrator for mode md.
 // Exit status 1 if a solve did not converge.
 #include "hmc_parity_common.hpp"
 
@@ -16,6 +17,7 @@ using namespace hmc_parity;
 
 int main(int argc, char** argv) {
   qmg_driver::Guard guard;
+  const hmc_run::Integrator integrator = hmc_run::Integrator::peel(argc, argv);   // the trailing `integrator <leapfrog|omelyan> <n_gauge>`, if any
   if (argc < 11) { cout << "usage: ./stag_hmc_parity md|heatbath|rational L gauge_file dir beta mass tau n_steps cg_eps n_tastes [degree]\n"; return -1; }
   if (!qmg::ok(qmg_init(0), "qmg_init")) return 2;
   const string mode = argv[1];
@@ -39,7 +41,7 @@ int main(int argc, char** argv) {
     HeatbathRng generator(1);
     StaggeredSchwingerHMC hmc(phases, L, L, beta, mass, n_tastes, tau, n_steps, cg_eps, 20000, generator, degree);
     cout << setprecision(17);
-    if (!hmc.ok()) rc = 4;
+    if (!hmc.ok() || !integrator.apply(hmc)) rc = 4;
     if (!rc && n_tastes == 1) rhmc_line(hmc);
     if (rc) {   // refused
     } else if (mode == "md") {

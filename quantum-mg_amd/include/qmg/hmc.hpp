@@ -79,19 +79,19 @@ class SchwingerHMC : public HmcCore {
     }
     return rat.c0 * s;
   }
-  void kick(double* p, double dt) {
+  void kick(double* p, double dt, double beta_g) {
     if (stout.on() && n_flavours) {   // the levels are those of the last solve_for_force
       const double one = 1.0;
-      if (n_flavours == 1) stout.kick(p, gauge, (const void* const*)sols.data(), (const void* const*)Ys.data(), pole_weights.data(), rat.n, beta, dt);
-      else stout.kick(p, gauge, (const void* const*)&X, (const void* const*)&Y, &one, 1, beta, dt);
+      if (n_flavours == 1) stout.kick(p, gauge, (const void* const*)sols.data(), (const void* const*)Ys.data(), pole_weights.data(), rat.n, beta_g, dt);
+      else stout.kick(p, gauge, (const void* const*)&X, (const void* const*)&Y, &one, 1, beta_g, dt);
       return;
     }
     if (n_flavours == 1) {
       qmg::ok(qmg_hmc_momentum_update_poles(p, gauge, (const void* const*)sols.data(), (const void* const*)Ys.data(), pole_weights.data(), rat.n, lat_gauge.get_dim_mu(0),
-                                            lat_gauge.get_dim_mu(1), beta, dt, 0u, qmg::current_stream()), "qmg_hmc_momentum_update_poles");
+                                            lat_gauge.get_dim_mu(1), beta_g, dt, 0u, qmg::current_stream()), "qmg_hmc_momentum_update_poles");
       return;
     }
-    qmg::ok(qmg_hmc_momentum_update(p, gauge, X, Y, lat_gauge.get_dim_mu(0), lat_gauge.get_dim_mu(1), beta, dt, n_flavours ? 0u : (unsigned)QMG_HMC_GAUGE_ONLY,
+    qmg::ok(qmg_hmc_momentum_update(p, gauge, X, Y, lat_gauge.get_dim_mu(0), lat_gauge.get_dim_mu(1), beta_g, dt, n_flavours ? 0u : (unsigned)QMG_HMC_GAUGE_ONLY,
                                     qmg::current_stream()), "qmg_hmc_momentum_update");
   }
   // eta: variance 1/2 per real component, from stream 1 of the trajectory

@@ -12,7 +12,9 @@
 //   * after every link update the operator takes the new links before anything is solved or applied (the first duty of solve_for_force);
 //   * random numbers are functions of (seed, trajectory number, field) alone (qmg_hmc_stream_seed: 0 momenta, 1 pseudofermion noise,
 //     2 Metropolis number), whatever was drawn before;
-//   * a rejected trajectory restores the phases AND the links, and reports the observables of the restored field.
+//   * a rejected trajectory restores the phases AND the links, and reports the observables of the restored field;
+//   * whenever a hook runs the links are in `gauge`, and that pointer never changes (DwfLinksSchur keeps a copy of it): the inner loop of a
+//     two-scale integrator (set_integrator) ping-pongs between `gauge` and a second buffer and always ends in `gauge`.
 // A rational pseudofermion action (one flavour, one taste) keeps r, its shifted solutions and the operator r acts on here as well, so that
 // the multi-shift solve and its accounting exist once.
 #ifndef QMG_HMC_CORE_HPP
@@ -37,6 +39,26 @@ inline inversion_info hmc_solve_cg(complex<double>* x, complex<double>* b, int s
   return minv_vector_cg(x, b, size, max_iter, eps, op, op_data);
 }
 
+// The molecular-dynamics schemes.  One step of length h, K a kick of the momenta and D a drift of the links:
+//   MD_LEAPFROG  K(h/2) D(h) K(h/2)
+//   MD_OMELYAN   K(lambda h) D(h/2) K((1 - 2 lambda) h) D(h/2) K(lambda h)      (second-order minimum norm; lambda = 0.1931833275037836)
+// Adjacent kicks of consecutive steps are one kick: n steps cost n + 1 force evaluations (leapfrog) or 2 n + 1 (Omelyan).
+enum MdScheme { MD_LEAPFROG = 0, MD_OMELYAN = 1 };
+
+// K(first kick) { D K }* of `n` steps of length h with the kicks of consecutive steps merged: calls K(dt) and D(dt) in order.
+template <class Kick, class Drift> void md_sequence(MdScheme scheme, double lambda, int n, double h, Kick K, Drift D) {
+  if (scheme == MD_LEAPFROG) {
+    K(0.5 * h);
+    for (int k = 0; k < n; k++) { D(h); K(k + 1 < n ? h : 0.5 * h); }
+    return;
+  }
+  K(lambda * h);
+  for (int k = 0; k < n; k++) {
+    D(0.5 * h); K((1.0 - 2.0 * lambda) * h);
+    D(0.5 * h); K(k + 1 < n ? 2.0 * lambda * h : lambda * h);
+  }
+}
+
 class HmcCore {
   HmcCore(HmcCore const&);
   HmcCore& operator=(HmcCore const&);
@@ -47,6 +69,7 @@ class HmcCore {
   double* theta;                     // the caller's
   double *theta_saved, *pi;
   complex<double>*gauge, *draw;
+  complex<double>* gauge_other;      // two scales only: the far end of the inner loop's ping-pong; the links are in `gauge` whenever a hook runs
   HeatbathRng& rng;
   bool good;
   size_t n_links, cv;                // cv: components of one of the derived class's fermion vectors
@@ -58,6 +81,10 @@ class HmcCore {
   matrix_op_cplx rat_fn;
   void* rat_data;
   size_t rat_size;
+  // the integrator (set_integrator): the scheme, the gauge steps inside one drift of the fermion scale (0: one scale) and Omelyan's lambda
+  MdScheme md_scheme;
+  int md_n_gauge;
+  double md_lambda;
 
   // ---- the hooks of a fermion action ----
   virtual bool has_fermions() const = 0;
@@ -65,18 +92,20 @@ class HmcCore {
   virtual void operator_takes_links() = 0;
   // the operator takes the current links, the solves run from zero; returns S_f(phi) and leaves the fields that kick() reads
   virtual double solve_for_force(complex<double>* phi, HmcResult& r) = 0;
-  // p -= dt (Fg + Ff), Ff from the fields of the last solve_for_force
-  virtual void kick(double* p, double dt) = 0;
+  // p -= dt (Fg(beta_g) + Ff), Ff from the fields of the last solve_for_force, Fg the gauge force at the coupling beta_g: `beta` on the fused
+  // single-scale path, 0.0 for the fermion force alone (every kick kernel multiplies its differences of sin P by the coupling it is given)
+  virtual void kick(double* p, double dt, double beta_g) = 0;
   // draws the pseudofermion of trajectory `traj` on the current phases from stream (rng.seed, traj, 1) and returns it; solver counts into hb
   virtual complex<double>* draw_pseudofermion(unsigned long long traj, HmcResult& hb) = 0;
 
   HmcCore(const char* name, const char* flavour, double* phase_field, int Lx, int Ly, double beta, double tau, int n_steps, double cg_eps, int cg_max_iter, HeatbathRng& generator)
-      : name(name), flavour(flavour), lat_gauge(Lx, Ly, 1), theta(phase_field), theta_saved(0), pi(0), gauge(0), draw(0), rng(generator), good(false), cv(0), rat_fn(0),
-        rat_data(0), rat_size(0), beta(beta), tau(tau), cg_eps(cg_eps), n_steps(n_steps), cg_max_iter(cg_max_iter), trajectories_done(0), solver(hmc_solve_cg) {
+      : name(name), flavour(flavour), lat_gauge(Lx, Ly, 1), theta(phase_field), theta_saved(0), pi(0), gauge(0), draw(0), gauge_other(0), rng(generator), good(false), cv(0), rat_fn(0),
+        rat_data(0), rat_size(0), md_scheme(MD_LEAPFROG), md_n_gauge(0), md_lambda(0.1931833275037836), beta(beta), tau(tau), cg_eps(cg_eps), n_steps(n_steps),
+        cg_max_iter(cg_max_iter), trajectories_done(0), solver(hmc_solve_cg) {
     n_links = (size_t)lat_gauge.get_size_gauge();
   }
   virtual ~HmcCore() {
-    deallocate_vector(&theta_saved); deallocate_vector(&pi); deallocate_vector(&gauge); deallocate_vector(&draw);
+    deallocate_vector(&theta_saved); deallocate_vector(&pi); deallocate_vector(&gauge); deallocate_vector(&draw); deallocate_vector(&gauge_other);
     for (size_t j = 0; j < sols.size(); j++) deallocate_vector(&sols[j]);
   }
   // the refusals every action shares, around the derived class's verdict on its flavour count; false (and a line) if the object is refused
@@ -106,6 +135,27 @@ class HmcCore {
   double plaquette() { return std::real(get_plaquette_u1(gauge, &lat_gauge)); }
   double gauge_action() { return beta * (double)lat_gauge.get_volume() * (1.0 - plaquette()); }
   void observe(HmcResult& r) { r.plaquette = plaquette(); r.topo = get_topo_u1(gauge, &lat_gauge); }
+
+  // A drift of length e on the fermion scale: md_n_gauge steps of the scheme, of length e / md_n_gauge, under the gauge force alone.  Written
+  // as pairs (kick, drift) and a last kick, the pairs go through qmg_hmc_gauge_step from `gauge` to gauge_other and back; an odd count sends its
+  // first pair through the two in-place entries, whose bits the fused step has, so that the block ends in `gauge`.  The last kick is the
+  // gauge-only kick.
+  void gauge_block(double* p, double e) {
+    const int Lx = lat_gauge.get_dim_mu(0), Ly = lat_gauge.get_dim_mu(1);
+    void* st = qmg::current_stream();
+    std::vector<double> kicks, drifts;
+    md_sequence(md_scheme, md_lambda, md_n_gauge, e / md_n_gauge, [&](double k) { kicks.push_back(k); }, [&](double d) { drifts.push_back(d); });
+    size_t j = 0;
+    if (drifts.size() & 1) {
+      qmg::ok(qmg_hmc_momentum_update(p, gauge, 0, 0, Lx, Ly, beta, kicks[0], QMG_HMC_GAUGE_ONLY, st), "qmg_hmc_momentum_update");
+      qmg::ok(qmg_hmc_link_update(theta, gauge, p, n_links, drifts[0], st), "qmg_hmc_link_update");
+      j = 1;
+    }
+    complex<double>* ends[2] = {gauge, gauge_other};
+    for (int src = 0; j < drifts.size(); j++, src ^= 1)
+      qmg::ok(qmg_hmc_gauge_step(theta, ends[1 - src], ends[src], p, Lx, Ly, beta, kicks[j], drifts[j], st), "qmg_hmc_gauge_step");
+    qmg::ok(qmg_hmc_momentum_update(p, gauge, 0, 0, Lx, Ly, beta, kicks.back(), QMG_HMC_GAUGE_ONLY, st), "qmg_hmc_momentum_update");
+  }
 
   // sols[j] = (A + shifts[j])^-1 b over `size` components by ONE multi-shift CG from zero, A the operator `fn`; counts into r
   void solve_shifts(complex<double>* b, std::vector<double>& shifts, size_t size, matrix_op_cplx fn, void* op_data, HmcResult& r) {
@@ -139,6 +189,23 @@ class HmcCore {
   complex<double>* links() { return gauge; }   // exp(i theta) as of the last call
   Lattice2D* gauge_lattice() { return &lat_gauge; }
 
+  // The integrator of md_evolve and trajectory(); the default is (MD_LEAPFROG, 0).  n_gauge = 0 is one scale: every kick is the fused kick of the
+  // gauge and the fermion force.  n_gauge >= 1 is two scales: the kicks of the scheme carry the fermion force alone (none without fermions) and
+  // every drift of length e is n_gauge steps of the same scheme, of length e / n_gauge, under the gauge force alone.  lambda is Omelyan's.
+  // Refuses n_gauge < 0 and lambda outside (0, 1/2) with a line and false, and leaves the object as it was.
+  bool set_integrator(MdScheme scheme, int n_gauge, double lambda = 0.1931833275037836) {
+    if ((scheme != MD_LEAPFROG && scheme != MD_OMELYAN) || n_gauge < 0 || !(lambda > 0.0 && lambda < 0.5)) {
+      std::cout << "[QMG-ERROR]: " << name << "::set_integrator needs a scheme, n_gauge >= 0 and 0 < lambda < 1/2.\n";
+      return false;
+    }
+    if (n_gauge > 0 && !gauge_other && !(gauge_other = allocate_vector<complex<double>>(n_links))) {
+      std::cout << "[QMG-ERROR]: " << name << "::set_integrator: out of device memory.\n";
+      return false;
+    }
+    md_scheme = scheme; md_n_gauge = n_gauge; md_lambda = lambda;
+    return true;
+  }
+
   // ---- a rational action only; takes the object's current phases ----
   const qmg::ZolotarevInvSqrt& rational() const { return rat; }
   // out = r(A) in (DEVICE vectors of the pseudofermion's length; out may be in).  Returns the multi-shift CG's count and convergence.
@@ -151,7 +218,7 @@ class HmcCore {
     return r;
   }
 
-  // The deterministic part alone: leapfrog over tau from the object's phases with the momenta `momenta` (DEVICE double[2 Lx Ly], evolved in place)
+  // The deterministic part alone: the integrator (set_integrator; by default leapfrog on one scale) over tau from the object's phases with the momenta `momenta` (DEVICE double[2 Lx Ly], evolved in place)
   // and the pseudofermion `pseudofermion` (DEVICE, the derived class's layout; ignored without fermions).  Fills dH, the CG counts and the
   // observables of the end point.
   HmcResult md_evolve(double* momenta, complex<double>* pseudofermion) {
@@ -162,11 +229,20 @@ class HmcCore {
     polar_vector(theta, gauge, n_links);
     double sf = fermions ? solve_for_force(pseudofermion, r) : 0.0;
     const double h0 = kinetic(momenta) + gauge_action() + sf;
-    kick(momenta, 0.5 * dt);
-    for (int k = 0; k < n_steps; k++) {
-      qmg::ok(qmg_hmc_link_update(theta, gauge, momenta, n_links, dt, qmg::current_stream()), "qmg_hmc_link_update");
-      if (fermions) sf = solve_for_force(pseudofermion, r);
-      kick(momenta, k + 1 < n_steps ? dt : 0.5 * dt);
+    if (md_n_gauge == 0) {   // one scale: the fused kick, and after every drift the solve that the next kick and the last H read
+      md_sequence(md_scheme, md_lambda, n_steps, dt,
+                  [&](double e) { kick(momenta, e, beta); },
+                  [&](double e) {
+                    qmg::ok(qmg_hmc_link_update(theta, gauge, momenta, n_links, e, qmg::current_stream()), "qmg_hmc_link_update");
+                    if (fermions) sf = solve_for_force(pseudofermion, r);
+                  });
+    } else {                 // two scales: the fermion force alone outside, every drift a block of gauge steps
+      md_sequence(md_scheme, md_lambda, n_steps, dt,
+                  [&](double e) { if (fermions) kick(momenta, e, 0.0); },
+                  [&](double e) {
+                    gauge_block(momenta, e);
+                    if (fermions) sf = solve_for_force(pseudofermion, r);
+                  });
     }
     r.dH = kinetic(momenta) + gauge_action() + sf - h0;
     observe(r);

@@ -76,12 +76,12 @@ class DomainWallSchwingerHMC : public HmcCore {
     op_pv.fill_odd(X5p); op_pv.fill_odd(Z5p);
     return sf;
   }
-  void kick(double* p, double dt) {
+  void kick(double* p, double dt, double beta_g) {
     const void* xs[2] = {X5, X5p};
     const void* ys[2] = {Z5, Z5p};
     const double w[2] = {1.0, -1.0};
     const unsigned flags = n_flavours ? (unsigned)QMG_HMC_DWF_G5_Y : (unsigned)QMG_HMC_GAUGE_ONLY;
-    qmg::ok(qmg_hmc_momentum_update_dwf(p, gauge, xs, ys, w, n_flavours ? 2 : 0, Ls, lat_gauge.get_dim_mu(0), lat_gauge.get_dim_mu(1), beta, dt, flags,
+    qmg::ok(qmg_hmc_momentum_update_dwf(p, gauge, xs, ys, w, n_flavours ? 2 : 0, Ls, lat_gauge.get_dim_mu(0), lat_gauge.get_dim_mu(1), beta_g, dt, flags,
                                         qmg::current_stream()), "qmg_hmc_momentum_update_dwf");
   }
   // eta on the even sites: variance 1/2 per real component, from stream 1 of the trajectory

@@ -59,12 +59,12 @@ class StaggeredSchwingerHMC : public HmcCore {
     }
     return rat.c0 * s;
   }
-  void kick(double* p, double dt) {
+  void kick(double* p, double dt, double beta_g) {
     const void* one[1] = {W};
     const double unit[1] = {1.0};
     const int n = n_tastes == 1 ? rat.n : (n_tastes ? 1 : 0);
     qmg::ok(qmg_hmc_momentum_update_staggered(p, gauge, n_tastes == 1 ? (const void* const*)sols.data() : one, n_tastes == 1 ? pole_weights.data() : unit, n,
-                                              lat_gauge.get_dim_mu(0), lat_gauge.get_dim_mu(1), beta, dt, n_tastes ? 0u : (unsigned)QMG_HMC_GAUGE_ONLY, qmg::current_stream()),
+                                              lat_gauge.get_dim_mu(0), lat_gauge.get_dim_mu(1), beta_g, dt, n_tastes ? 0u : (unsigned)QMG_HMC_GAUGE_ONLY, qmg::current_stream()),
             "qmg_hmc_momentum_update_staggered");
   }
 
