@@ -10,6 +10,7 @@ fallback: if the shared library is missing, importing `lib()` raises.
  `importlib.import_module("quantum-mg_amd")`.)
 """
 import ctypes as C
+import functools
 import os
 import subprocess
 
@@ -186,6 +187,60 @@ class DeviceArray:
             pass
 
 
+def _checked(status_fn, what):
+    """The raising form of a wrapper that returns its status: same parameters (stream= among them)."""
+    @functools.wraps(status_fn)
+    def call(*args, **kw):
+        check(status_fn(*args, **kw), what)
+    call.__name__ = call.__qualname__ = status_fn.__name__[:-len("_status")]
+    return call
+
+
+def memcpy_h2d(dst_dev, src_host, nbytes=None, stream=None):
+    """src_host: a contiguous numpy array; synchronous when stream is None"""
+    check(lib().qmg_memcpy_h2d(_vp(dst_dev), src_host.ctypes.data_as(C.c_void_p), C.c_size_t(src_host.nbytes if nbytes is None else nbytes), C.c_void_p(stream)), "qmg_memcpy_h2d")
+
+
+def memcpy_d2h(dst_host, src_dev, nbytes=None, stream=None):
+    check(lib().qmg_memcpy_d2h(dst_host.ctypes.data_as(C.c_void_p), _vp(src_dev), C.c_size_t(dst_host.nbytes if nbytes is None else nbytes), C.c_void_p(stream)), "qmg_memcpy_d2h")
+
+
+def memcpy_d2d(dst_dev, src_dev, nbytes, stream=None):
+    check(lib().qmg_memcpy_d2d(_vp(dst_dev), _vp(src_dev), C.c_size_t(nbytes), C.c_void_p(stream)), "qmg_memcpy_d2d")
+
+
+def memset_zero(dev, nbytes, stream=None):
+    check(lib().qmg_memset_zero(_vp(dev), C.c_size_t(nbytes), C.c_void_p(stream)), "qmg_memset_zero")
+
+
+def poison_scratch(dev, nbytes, stream=None):
+    check(lib().qmg_poison_scratch(_vp(dev), C.c_size_t(nbytes), C.c_void_p(stream)), "qmg_poison_scratch")
+
+
+def event_create():
+    ev = C.c_void_p()
+    check(lib().qmg_event_create(C.byref(ev)), "qmg_event_create")
+    return ev.value
+
+
+def event_destroy(ev):
+    check(lib().qmg_event_destroy(C.c_void_p(ev)), "qmg_event_destroy")
+
+
+def event_record(ev, stream=None):
+    check(lib().qmg_event_record(C.c_void_p(ev), C.c_void_p(stream)), "qmg_event_record")
+
+
+def event_elapsed_ms(ev_start, ev_stop):
+    ms = C.c_float()
+    check(lib().qmg_event_elapsed_ms(C.c_void_p(ev_start), C.c_void_p(ev_stop), C.byref(ms)), "qmg_event_elapsed_ms")
+    return ms.value
+
+
+def allreduce_sum_f64(buf_dev, n, stream=None):
+    check(lib().qmg_allreduce_sum_f64(C.cast(_vp(buf_dev), C.POINTER(C.c_double)), C.c_size_t(n), C.c_void_p(stream)), "qmg_allreduce_sum_f64")
+
+
 def _vp(x):
     if x is None:
         return C.c_void_p(None)
@@ -268,147 +323,147 @@ def _scalar(a):
     return C.c_double(a.real), C.c_double(a.imag)
 
 
-def zero_vector(x, n):
-    check(lib().qmg_zero_vector(_vp(x), C.c_size_t(n), None))
+def zero_vector(x, n, stream=None):
+    check(lib().qmg_zero_vector(_vp(x), C.c_size_t(n), C.c_void_p(stream)))
 
 
-def copy_vector(dst, src, n):
-    check(lib().qmg_copy_vector(_vp(dst), _vp(src), C.c_size_t(n), None))
+def copy_vector(dst, src, n, stream=None):
+    check(lib().qmg_copy_vector(_vp(dst), _vp(src), C.c_size_t(n), C.c_void_p(stream)))
 
 
-def cax(a, x, n):
-    check(lib().qmg_cax(*_scalar(a), _vp(x), C.c_size_t(n), None))
+def cax(a, x, n, stream=None):
+    check(lib().qmg_cax(*_scalar(a), _vp(x), C.c_size_t(n), C.c_void_p(stream)))
 
 
-def caxy(a, x, y, n):
-    check(lib().qmg_caxy(*_scalar(a), _vp(x), _vp(y), C.c_size_t(n), None))
+def caxy(a, x, y, n, stream=None):
+    check(lib().qmg_caxy(*_scalar(a), _vp(x), _vp(y), C.c_size_t(n), C.c_void_p(stream)))
 
 
-def caxpy(a, x, y, n):
-    check(lib().qmg_caxpy(*_scalar(a), _vp(x), _vp(y), C.c_size_t(n), None))
+def caxpy(a, x, y, n, stream=None):
+    check(lib().qmg_caxpy(*_scalar(a), _vp(x), _vp(y), C.c_size_t(n), C.c_void_p(stream)))
 
 
-def cxpy(x, y, n):
-    check(lib().qmg_cxpy(_vp(x), _vp(y), C.c_size_t(n), None))
+def cxpy(x, y, n, stream=None):
+    check(lib().qmg_cxpy(_vp(x), _vp(y), C.c_size_t(n), C.c_void_p(stream)))
 
 
-def cxpay(x, a, y, n):
-    check(lib().qmg_cxpay(_vp(x), *_scalar(a), _vp(y), C.c_size_t(n), None))
+def cxpay(x, a, y, n, stream=None):
+    check(lib().qmg_cxpay(_vp(x), *_scalar(a), _vp(y), C.c_size_t(n), C.c_void_p(stream)))
 
 
-def caxpby(a, x, b, y, n):
-    check(lib().qmg_caxpby(*_scalar(a), _vp(x), *_scalar(b), _vp(y), C.c_size_t(n), None))
+def caxpby(a, x, b, y, n, stream=None):
+    check(lib().qmg_caxpby(*_scalar(a), _vp(x), *_scalar(b), _vp(y), C.c_size_t(n), C.c_void_p(stream)))
 
 
-def cxpyz(x, y, z, n):
-    check(lib().qmg_cxpyz(_vp(x), _vp(y), _vp(z), C.c_size_t(n), None))
+def cxpyz(x, y, z, n, stream=None):
+    check(lib().qmg_cxpyz(_vp(x), _vp(y), _vp(z), C.c_size_t(n), C.c_void_p(stream)))
 
 
-def caxpbyz(a, x, b, y, z, n):
-    check(lib().qmg_caxpbyz(*_scalar(a), _vp(x), *_scalar(b), _vp(y), _vp(z), C.c_size_t(n), None))
+def caxpbyz(a, x, b, y, z, n, stream=None):
+    check(lib().qmg_caxpbyz(*_scalar(a), _vp(x), *_scalar(b), _vp(y), _vp(z), C.c_size_t(n), C.c_void_p(stream)))
 
 
-def multi_caxpy(coeffs, xs, y, n):
+def multi_caxpy(coeffs, xs, y, n, stream=None):
     k = len(xs)
     cf = (C.c_double * (2 * k))(*[v for a in coeffs for v in (complex(a).real, complex(a).imag)])
     ptrs = (C.c_void_p * k)(*[(x.ptr if isinstance(x, DeviceArray) else int(x)) for x in xs])
-    check(lib().qmg_multi_caxpy(cf, ptrs, k, _vp(y), C.c_size_t(n), None), "qmg_multi_caxpy")
+    check(lib().qmg_multi_caxpy(cf, ptrs, k, _vp(y), C.c_size_t(n), C.c_void_p(stream)), "qmg_multi_caxpy")
 
 
-def caxy_pattern(scale, shuffle, x, y, nsite):
+def caxy_pattern(scale, shuffle, x, y, nsite, stream=None):
     nc = len(scale)
     sc = (C.c_double * nc)(*scale)
     sh = (C.c_int * nc)(*shuffle)
-    check(lib().qmg_caxy_pattern(sc, sh, nc, _vp(x), _vp(y), C.c_size_t(nsite), None))
+    check(lib().qmg_caxy_pattern(sc, sh, nc, _vp(x), _vp(y), C.c_size_t(nsite), C.c_void_p(stream)))
 
 
-def gaussian(x, n, seed):
-    check(lib().qmg_gaussian(_vp(x), C.c_size_t(n), C.c_ulonglong(seed), None))
+def gaussian(x, n, seed, stream=None):
+    check(lib().qmg_gaussian(_vp(x), C.c_size_t(n), C.c_ulonglong(seed), C.c_void_p(stream)))
 
 
-def norm2sq(x, n):
+def norm2sq(x, n, stream=None):
     out = C.c_double()
-    check(lib().qmg_norm2sq(_vp(x), C.c_size_t(n), None, C.byref(out), None))
+    check(lib().qmg_norm2sq(_vp(x), C.c_size_t(n), None, C.byref(out), C.c_void_p(stream)))
     return out.value
 
 
-def dot(x, y, n):
+def dot(x, y, n, stream=None):
     out = (C.c_double * 2)()
-    check(lib().qmg_dot(_vp(x), _vp(y), C.c_size_t(n), None, out, None))
+    check(lib().qmg_dot(_vp(x), _vp(y), C.c_size_t(n), None, out, C.c_void_p(stream)))
     return complex(out[0], out[1])
 
 
-def diffnorm2sq(x, y, n):
+def diffnorm2sq(x, y, n, stream=None):
     out = C.c_double()
-    check(lib().qmg_diffnorm2sq(_vp(x), _vp(y), C.c_size_t(n), None, C.byref(out), None))
+    check(lib().qmg_diffnorm2sq(_vp(x), _vp(y), C.c_size_t(n), None, C.byref(out), C.c_void_p(stream)))
     return out.value
 
 
-def norminf(x, n):
+def norminf(x, n, stream=None):
     out = C.c_double()
-    check(lib().qmg_norminf(_vp(x), C.c_size_t(n), None, C.byref(out), None))
+    check(lib().qmg_norminf(_vp(x), C.c_size_t(n), None, C.byref(out), C.c_void_p(stream)))
     return out.value
 
 
-def multidot(xs, y, n):
+def multidot(xs, y, n, stream=None):
     k = len(xs)
     ptrs = (C.c_void_p * k)(*[(x.ptr if isinstance(x, DeviceArray) else int(x)) for x in xs])
     out = (C.c_double * (2 * k))()
-    check(lib().qmg_multidot(ptrs, k, _vp(y), C.c_size_t(n), None, out, None))
+    check(lib().qmg_multidot(ptrs, k, _vp(y), C.c_size_t(n), None, out, C.c_void_p(stream)))
     return np.array([complex(out[2 * i], out[2 * i + 1]) for i in range(k)])
 
 
-def norm2sq_cv_timeslice(cv, Lx, Ly, nc):
+def norm2sq_cv_timeslice(cv, Lx, Ly, nc, stream=None):
     out = np.zeros(Ly)
-    check(lib().qmg_norm2sq_cv_timeslice(_vp(cv), Lx, Ly, nc, None, out.ctypes.data_as(C.POINTER(C.c_double)), None))
+    check(lib().qmg_norm2sq_cv_timeslice(_vp(cv), Lx, Ly, nc, None, out.ctypes.data_as(C.POINTER(C.c_double)), C.c_void_p(stream)))
     return out
 
 
-def dot_cv_timeslice(a, b, Lx, Ly, nc):
+def dot_cv_timeslice(a, b, Lx, Ly, nc, stream=None):
     out = np.zeros(2 * Ly)
-    check(lib().qmg_dot_cv_timeslice(_vp(a), _vp(b), Lx, Ly, nc, None, out.ctypes.data_as(C.POINTER(C.c_double)), None))
+    check(lib().qmg_dot_cv_timeslice(_vp(a), _vp(b), Lx, Ly, nc, None, out.ctypes.data_as(C.POINTER(C.c_double)), C.c_void_p(stream)))
     return out[0::2] + 1j * out[1::2]
 
 
-def redot_cv_timeslice(a, b, Lx, Ly, nc):
+def redot_cv_timeslice(a, b, Lx, Ly, nc, stream=None):
     out = np.zeros(Ly)
-    check(lib().qmg_redot_cv_timeslice(_vp(a), _vp(b), Lx, Ly, nc, None, out.ctypes.data_as(C.POINTER(C.c_double)), None))
+    check(lib().qmg_redot_cv_timeslice(_vp(a), _vp(b), Lx, Ly, nc, None, out.ctypes.data_as(C.POINTER(C.c_double)), C.c_void_p(stream)))
     return out
 
 
-def gaussian_wall_source(cv, Lx, Ly, nc, timeslice, color, seed, deviation=1.0, mean=0.0):
+def gaussian_wall_source(cv, Lx, Ly, nc, timeslice, color, seed, deviation=1.0, mean=0.0, stream=None):
     """reductions/reductions.h:90-162; returns the status instead of raising for an out-of-range timeslice / color (the reference prints and returns)."""
-    return lib().qmg_gaussian_wall_source(_vp(cv), Lx, Ly, nc, timeslice, color, C.c_ulonglong(seed), C.c_double(deviation), C.c_double(mean), None)
+    return lib().qmg_gaussian_wall_source(_vp(cv), Lx, Ly, nc, timeslice, color, C.c_ulonglong(seed), C.c_double(deviation), C.c_double(mean), C.c_void_p(stream))
 
 
-def prolong(nullvecs, nvec, coarse, fine, fdims, cdims):
-    check(lib().qmg_prolong(_vp(nullvecs), nvec, _vp(coarse), _vp(fine), *fdims, *cdims, None), "qmg_prolong")
+def prolong(nullvecs, nvec, coarse, fine, fdims, cdims, stream=None):
+    check(lib().qmg_prolong(_vp(nullvecs), nvec, _vp(coarse), _vp(fine), *fdims, *cdims, C.c_void_p(stream)), "qmg_prolong")
 
 
-def restrict(nullvecs, nvec, fine, coarse, fdims, cdims):
-    check(lib().qmg_restrict(_vp(nullvecs), nvec, _vp(fine), _vp(coarse), *fdims, *cdims, None), "qmg_restrict")
+def restrict(nullvecs, nvec, fine, coarse, fdims, cdims, stream=None):
+    check(lib().qmg_restrict(_vp(nullvecs), nvec, _vp(fine), _vp(coarse), *fdims, *cdims, C.c_void_p(stream)), "qmg_restrict")
 
 
-def block_orthonormalize(nullvecs, nvec, fdims, cLx, cLy, cholesky=None):
-    check(lib().qmg_block_orthonormalize(_vp(nullvecs), nvec, *fdims, cLx, cLy, _vp(cholesky), None), "qmg_block_orthonormalize")
+def block_orthonormalize(nullvecs, nvec, fdims, cLx, cLy, cholesky=None, stream=None):
+    check(lib().qmg_block_orthonormalize(_vp(nullvecs), nvec, *fdims, cLx, cLy, _vp(cholesky), C.c_void_p(stream)), "qmg_block_orthonormalize")
 
 
-def block_orthonormalize_n(nullvecs, nvec, fdims, cLx, cLy, cholesky=None, passes=2):
+def block_orthonormalize_n(nullvecs, nvec, fdims, cLx, cLy, cholesky=None, passes=2, stream=None):
     """`passes` (1 or 2) passes in one call, the factor saved in the first (qmg_block_orthonormalize_n)"""
-    check(lib().qmg_block_orthonormalize_n(_vp(nullvecs), nvec, *fdims, cLx, cLy, _vp(cholesky), passes, None), "qmg_block_orthonormalize_n")
+    check(lib().qmg_block_orthonormalize_n(_vp(nullvecs), nvec, *fdims, cLx, cLy, _vp(cholesky), passes, C.c_void_p(stream)), "qmg_block_orthonormalize_n")
 
 
-def block_bi_orthonormalize(pvecs, rvecs, nvec, fdims, cLx, cLy, block_L=None, block_U=None):
-    check(lib().qmg_block_bi_orthonormalize(_vp(pvecs), _vp(rvecs), nvec, *fdims, cLx, cLy, _vp(block_L), _vp(block_U), None), "qmg_block_bi_orthonormalize")
+def block_bi_orthonormalize(pvecs, rvecs, nvec, fdims, cLx, cLy, block_L=None, block_U=None, stream=None):
+    check(lib().qmg_block_bi_orthonormalize(_vp(pvecs), _vp(rvecs), nvec, *fdims, cLx, cLy, _vp(block_L), _vp(block_U), C.c_void_p(stream)), "qmg_block_bi_orthonormalize")
 
 
-def coarse_build(cclover, chopping, fdesc, nullvecs, cdims, restrict_vecs=None):
-    check(lib().qmg_coarse_build(_vp(cclover), _vp(chopping), C.byref(fdesc), _vp(nullvecs), _vp(restrict_vecs), *cdims, None), "qmg_coarse_build")
+def coarse_build(cclover, chopping, fdesc, nullvecs, cdims, restrict_vecs=None, stream=None):
+    check(lib().qmg_coarse_build(_vp(cclover), _vp(chopping), C.byref(fdesc), _vp(nullvecs), _vp(restrict_vecs), *cdims, C.c_void_p(stream)), "qmg_coarse_build")
 
 
-def coarse_build_slab(cclover, chopping, fdesc, nullvecs, cdims, halo_lo, halo_hi, halo_stride, restrict_vecs=None):
+def coarse_build_slab(cclover, chopping, fdesc, nullvecs, cdims, halo_lo, halo_hi, halo_stride, restrict_vecs=None, stream=None):
     check(lib().qmg_coarse_build_slab(_vp(cclover), _vp(chopping), C.byref(fdesc), _vp(nullvecs), _vp(restrict_vecs), *cdims, _vp(halo_lo), _vp(halo_hi),
-                                      C.c_size_t(halo_stride), None), "qmg_coarse_build_slab")
+                                      C.c_size_t(halo_stride), C.c_void_p(stream)), "qmg_coarse_build_slab")
 
 
 # the `op` argument, the families and the flags of qmg_setup_plan (include/qmg_hip.h)
@@ -438,38 +493,38 @@ def make_epilogue(other=None, other_scale=1.0, acc_scale=-1.0, dotv=None):
     return e
 
 
-def stencil_apply_epi(dtype, mat32, desc, lhs, rhs, pieces, epi, vec_stride=0, system=0):
+def stencil_apply_epi(dtype, mat32, desc, lhs, rhs, pieces, epi, vec_stride=0, system=0, stream=None):
     """status (0 = done, 3 = this operator is not served with an epilogue) of qmg_stencil_apply_epi_t"""
-    return lib().qmg_stencil_apply_epi_t(dtype, int(mat32), C.byref(desc), _vp(lhs), _vp(rhs), C.c_uint(pieces), C.c_size_t(vec_stride), system, C.byref(epi), None)
+    return lib().qmg_stencil_apply_epi_t(dtype, int(mat32), C.byref(desc), _vp(lhs), _vp(rhs), C.c_uint(pieces), C.c_size_t(vec_stride), system, C.byref(epi), C.c_void_p(stream))
 
 
-def wilson_apply_direct_epi(dtype, desc, gauge, lhs, rhs, pieces, epi, nrhs=1, vec_stride=0, mask=1, wilson_coeff=1.0):
+def wilson_apply_direct_epi(dtype, desc, gauge, lhs, rhs, pieces, epi, nrhs=1, vec_stride=0, mask=1, wilson_coeff=1.0, stream=None):
     return lib().qmg_wilson_apply_direct_epi(dtype, C.byref(desc), _vp(gauge), desc.Ly, 0, C.c_double(wilson_coeff), _vp(lhs), _vp(rhs), None, None, C.c_uint(pieces), nrhs,
-                                             C.c_size_t(vec_stride), C.c_size_t(0), C.c_uint(mask), C.byref(epi), None)
+                                             C.c_size_t(vec_stride), C.c_size_t(0), C.c_uint(mask), C.byref(epi), C.c_void_p(stream))
 
 
-def wilson_hops_direct_epi(dtype, desc, gauge, hop_scale, lhs, rhs, pieces, epi, nrhs=1, vec_stride=0, mask=1, wilson_coeff=1.0):
+def wilson_hops_direct_epi(dtype, desc, gauge, hop_scale, lhs, rhs, pieces, epi, nrhs=1, vec_stride=0, mask=1, wilson_coeff=1.0, stream=None):
     return lib().qmg_wilson_hops_direct_epi(dtype, C.byref(desc), _vp(gauge), desc.Ly, 0, C.c_double(wilson_coeff), C.c_double(hop_scale), _vp(lhs), _vp(rhs), None, None,
-                                            C.c_uint(pieces), nrhs, C.c_size_t(vec_stride), C.c_size_t(0), C.c_uint(mask), C.byref(epi), None)
+                                            C.c_uint(pieces), nrhs, C.c_size_t(vec_stride), C.c_size_t(0), C.c_uint(mask), C.byref(epi), C.c_void_p(stream))
 
 
-def batch_mr_dots(dtype, r, p, n, nrhs, stride, mask):
-    check(lib().qmg_batch_mr_dots_t(dtype, _vp(r), _vp(p), C.c_size_t(n), nrhs, C.c_size_t(stride), C.c_uint(mask), None), "qmg_batch_mr_dots_t")
+def batch_mr_dots(dtype, r, p, n, nrhs, stride, mask, stream=None):
+    check(lib().qmg_batch_mr_dots_t(dtype, _vp(r), _vp(p), C.c_size_t(n), nrhs, C.c_size_t(stride), C.c_uint(mask), C.c_void_p(stream)), "qmg_batch_mr_dots_t")
 
 
-def batch_mr_update(dtype, omega, x, r_in, r_out, p, x_set, n, nrhs, stride, mask):
-    check(lib().qmg_batch_mr_update_t(dtype, C.c_double(omega), _vp(x), _vp(r_in), _vp(r_out), _vp(p), int(x_set), C.c_size_t(n), nrhs, C.c_size_t(stride), C.c_uint(mask), None),
+def batch_mr_update(dtype, omega, x, r_in, r_out, p, x_set, n, nrhs, stride, mask, stream=None):
+    check(lib().qmg_batch_mr_update_t(dtype, C.c_double(omega), _vp(x), _vp(r_in), _vp(r_out), _vp(p), int(x_set), C.c_size_t(n), nrhs, C.c_size_t(stride), C.c_uint(mask), C.c_void_p(stream)),
           "qmg_batch_mr_update_t")
 
 
-def batch_mr_read_dots(nrhs):
+def batch_mr_read_dots(nrhs, stream=None):
     out = (C.c_double * (4 * nrhs))()
-    check(lib().qmg_batch_mr_read_dots(out, nrhs, None), "qmg_batch_mr_read_dots")
+    check(lib().qmg_batch_mr_read_dots(out, nrhs, C.c_void_p(stream)), "qmg_batch_mr_read_dots")
     return np.array(out).reshape(nrhs, 4)
 
 
-def gaussian_slab(x, Lx, Ly_global, y0, Ly_local, nc, seed):
-    check(lib().qmg_gaussian_slab(_vp(x), Lx, Ly_global, y0, Ly_local, nc, C.c_ulonglong(seed), None), "qmg_gaussian_slab")
+def gaussian_slab(x, Lx, Ly_global, y0, Ly_local, nc, seed, stream=None):
+    check(lib().qmg_gaussian_slab(_vp(x), Lx, Ly_global, y0, Ly_local, nc, C.c_ulonglong(seed), C.c_void_p(stream)), "qmg_gaussian_slab")
 
 
 # ---------------- lock-step batches (qmg_batch.hip) ----------------
@@ -485,65 +540,65 @@ def _coef(a, nrhs):
 
 
 def stencil_apply_batch(desc, lhs, rhs, pieces, nrhs, vec_stride, mask, stream=None):
-    check(lib().qmg_stencil_apply_batch(C.byref(desc), _vp(lhs), _vp(rhs), C.c_uint(pieces), nrhs, C.c_size_t(vec_stride), C.c_uint(mask), stream),
+    check(lib().qmg_stencil_apply_batch(C.byref(desc), _vp(lhs), _vp(rhs), C.c_uint(pieces), nrhs, C.c_size_t(vec_stride), C.c_uint(mask), C.c_void_p(stream)),
           "qmg_stencil_apply_batch")
 
 
 def stencil_apply_mat32(desc, lhs, rhs, pieces, nrhs, vec_stride, mask, stream=None):
-    check(lib().qmg_stencil_apply_mat32(C.byref(desc), _vp(lhs), _vp(rhs), C.c_uint(pieces), nrhs, C.c_size_t(vec_stride), C.c_uint(mask), stream),
+    check(lib().qmg_stencil_apply_mat32(C.byref(desc), _vp(lhs), _vp(rhs), C.c_uint(pieces), nrhs, C.c_size_t(vec_stride), C.c_uint(mask), C.c_void_p(stream)),
           "qmg_stencil_apply_mat32")
 
 
 def stencil_apply_mat16(vec_dtype, desc, lhs, rhs, pieces, nrhs=1, vec_stride=0, mask=1, stream=None):
     """status of qmg_stencil_apply_mat16_t: complex<half> matrices (convert_to_c16), vectors of vec_dtype"""
-    return lib().qmg_stencil_apply_mat16_t(vec_dtype, C.byref(desc), _vp(lhs), _vp(rhs), C.c_uint(pieces), nrhs, C.c_size_t(vec_stride), C.c_uint(mask), stream)
+    return lib().qmg_stencil_apply_mat16_t(vec_dtype, C.byref(desc), _vp(lhs), _vp(rhs), C.c_uint(pieces), nrhs, C.c_size_t(vec_stride), C.c_uint(mask), C.c_void_p(stream))
 
 
-def convert_from_c16(dst, dst_dtype, src, n):
-    check(lib().qmg_convert_from_c16(_vp(dst), dst_dtype, _vp(src), C.c_size_t(n), None), "qmg_convert_from_c16")
+def convert_from_c16(dst, dst_dtype, src, n, stream=None):
+    check(lib().qmg_convert_from_c16(_vp(dst), dst_dtype, _vp(src), C.c_size_t(n), C.c_void_p(stream)), "qmg_convert_from_c16")
 
 
-def c64_to_c32(dst, src, n):
-    check(lib().qmg_c64_to_c32(_vp(dst), _vp(src), C.c_size_t(n), None), "qmg_c64_to_c32")
+def c64_to_c32(dst, src, n, stream=None):
+    check(lib().qmg_c64_to_c32(_vp(dst), _vp(src), C.c_size_t(n), C.c_void_p(stream)), "qmg_c64_to_c32")
 
 
-def batch_blas(op, z, n, nrhs, stride, mask, a=None, b=None, x=None, y=None):
+def batch_blas(op, z, n, nrhs, stride, mask, a=None, b=None, x=None, y=None, stream=None):
     ca, cb = _coef(a, nrhs), _coef(b, nrhs)
     check(lib().qmg_batch_blas(op, ca[0] if ca else None, cb[0] if cb else None, _vp(x), _vp(y), _vp(z), C.c_size_t(n), nrhs, C.c_size_t(stride),
-                               C.c_uint(mask), None), "qmg_batch_blas")
+                               C.c_uint(mask), C.c_void_p(stream)), "qmg_batch_blas")
 
 
-def batch_multi_caxpy(coeffs, xs, y, n, nrhs, stride, mask):
+def batch_multi_caxpy(coeffs, xs, y, n, nrhs, stride, mask, stream=None):
     nj = len(xs)
     cf = np.ascontiguousarray(np.asarray(coeffs, dtype=np.complex128).reshape(nj, nrhs)).view(np.float64)
     ptrs = (C.c_void_p * nj)(*[x.ptr for x in xs])
-    check(lib().qmg_batch_multi_caxpy(cf.ctypes.data_as(C.POINTER(C.c_double)), ptrs, nj, _vp(y), C.c_size_t(n), nrhs, C.c_size_t(stride), C.c_uint(mask), None),
+    check(lib().qmg_batch_multi_caxpy(cf.ctypes.data_as(C.POINTER(C.c_double)), ptrs, nj, _vp(y), C.c_size_t(n), nrhs, C.c_size_t(stride), C.c_uint(mask), C.c_void_p(stream)),
           "qmg_batch_multi_caxpy")
 
 
-def batch_reduce(op, x, y, n, nrhs, stride, mask):
+def batch_reduce(op, x, y, n, nrhs, stride, mask, stream=None):
     out = np.full(2 * nrhs, np.nan)
-    check(lib().qmg_batch_reduce(op, _vp(x), _vp(y), C.c_size_t(n), nrhs, C.c_size_t(stride), C.c_uint(mask), out.ctypes.data_as(C.POINTER(C.c_double)), None),
+    check(lib().qmg_batch_reduce(op, _vp(x), _vp(y), C.c_size_t(n), nrhs, C.c_size_t(stride), C.c_uint(mask), out.ctypes.data_as(C.POINTER(C.c_double)), C.c_void_p(stream)),
           "qmg_batch_reduce")
     return out[0::2] + 1j * out[1::2]
 
 
-def batch_multidot(xs, y, n, nrhs, stride, mask):
+def batch_multidot(xs, y, n, nrhs, stride, mask, stream=None):
     nj = len(xs)
     ptrs = (C.c_void_p * nj)(*[x.ptr for x in xs])
     out = np.full(2 * nrhs * nj, np.nan)
-    check(lib().qmg_batch_multidot(ptrs, nj, _vp(y), C.c_size_t(n), nrhs, C.c_size_t(stride), C.c_uint(mask), out.ctypes.data_as(C.POINTER(C.c_double)), None),
+    check(lib().qmg_batch_multidot(ptrs, nj, _vp(y), C.c_size_t(n), nrhs, C.c_size_t(stride), C.c_uint(mask), out.ctypes.data_as(C.POINTER(C.c_double)), C.c_void_p(stream)),
           "qmg_batch_multidot")
     return (out[0::2] + 1j * out[1::2]).reshape(nrhs, nj)
 
 
-def prolong_batch(nullvecs, nvec, coarse, fine, fdims, cdims, nrhs, cstride, fstride, mask):
-    check(lib().qmg_prolong_batch(_vp(nullvecs), nvec, _vp(coarse), _vp(fine), *fdims, *cdims, nrhs, C.c_size_t(cstride), C.c_size_t(fstride), C.c_uint(mask), None),
+def prolong_batch(nullvecs, nvec, coarse, fine, fdims, cdims, nrhs, cstride, fstride, mask, stream=None):
+    check(lib().qmg_prolong_batch(_vp(nullvecs), nvec, _vp(coarse), _vp(fine), *fdims, *cdims, nrhs, C.c_size_t(cstride), C.c_size_t(fstride), C.c_uint(mask), C.c_void_p(stream)),
           "qmg_prolong_batch")
 
 
-def restrict_batch(nullvecs, nvec, fine, coarse, fdims, cdims, nrhs, fstride, cstride, mask):
-    check(lib().qmg_restrict_batch(_vp(nullvecs), nvec, _vp(fine), _vp(coarse), *fdims, *cdims, nrhs, C.c_size_t(fstride), C.c_size_t(cstride), C.c_uint(mask), None),
+def restrict_batch(nullvecs, nvec, fine, coarse, fdims, cdims, nrhs, fstride, cstride, mask, stream=None):
+    check(lib().qmg_restrict_batch(_vp(nullvecs), nvec, _vp(fine), _vp(coarse), *fdims, *cdims, nrhs, C.c_size_t(fstride), C.c_size_t(cstride), C.c_uint(mask), C.c_void_p(stream)),
           "qmg_restrict_batch")
 
 
@@ -552,40 +607,40 @@ C64, C32 = 0, 1
 NP_DTYPE = {C64: np.complex128, C32: np.complex64}
 
 
-def convert(dst, dst_dtype, src, src_dtype, n):
-    check(lib().qmg_convert(_vp(dst), dst_dtype, _vp(src), src_dtype, C.c_size_t(n), None), "qmg_convert")
+def convert(dst, dst_dtype, src, src_dtype, n, stream=None):
+    check(lib().qmg_convert(_vp(dst), dst_dtype, _vp(src), src_dtype, C.c_size_t(n), C.c_void_p(stream)), "qmg_convert")
 
 
 def stencil_apply_t(dtype, desc, lhs, rhs, pieces, nrhs=1, vec_stride=0, mask=1, stream=None):
-    check(lib().qmg_stencil_apply_t(dtype, C.byref(desc), _vp(lhs), _vp(rhs), C.c_uint(pieces), nrhs, C.c_size_t(vec_stride), C.c_uint(mask), stream),
+    check(lib().qmg_stencil_apply_t(dtype, C.byref(desc), _vp(lhs), _vp(rhs), C.c_uint(pieces), nrhs, C.c_size_t(vec_stride), C.c_uint(mask), C.c_void_p(stream)),
           "qmg_stencil_apply_t")
 
 
-def batch_blas_t(dtype, op, z, n, nrhs, stride, mask, a=None, b=None, x=None, y=None):
+def batch_blas_t(dtype, op, z, n, nrhs, stride, mask, a=None, b=None, x=None, y=None, stream=None):
     ca, cb = _coef(a, nrhs), _coef(b, nrhs)
     check(lib().qmg_batch_blas_t(dtype, op, ca[0] if ca else None, cb[0] if cb else None, _vp(x), _vp(y), _vp(z), C.c_size_t(n), nrhs, C.c_size_t(stride),
-                                 C.c_uint(mask), None), "qmg_batch_blas_t")
+                                 C.c_uint(mask), C.c_void_p(stream)), "qmg_batch_blas_t")
 
 
-def batch_multi_caxpy_t(dtype, coeffs, xs, y, n, nrhs, stride, mask):
+def batch_multi_caxpy_t(dtype, coeffs, xs, y, n, nrhs, stride, mask, stream=None):
     nj = len(xs)
     cf = np.ascontiguousarray(np.asarray(coeffs, dtype=np.complex128).reshape(nj, nrhs)).view(np.float64)
     ptrs = (C.c_void_p * nj)(*[x.ptr for x in xs])
-    check(lib().qmg_batch_multi_caxpy_t(dtype, cf.ctypes.data_as(C.POINTER(C.c_double)), ptrs, nj, _vp(y), C.c_size_t(n), nrhs, C.c_size_t(stride), C.c_uint(mask), None),
+    check(lib().qmg_batch_multi_caxpy_t(dtype, cf.ctypes.data_as(C.POINTER(C.c_double)), ptrs, nj, _vp(y), C.c_size_t(n), nrhs, C.c_size_t(stride), C.c_uint(mask), C.c_void_p(stream)),
           "qmg_batch_multi_caxpy_t")
 
 
-def batch_gcr_update_t(dtype, coeffs, ws, w, a, r, z_next, n, nrhs, stride, mask):
+def batch_gcr_update_t(dtype, coeffs, ws, w, a, r, z_next, n, nrhs, stride, mask, stream=None):
     """w += sum_j c_j ws_j ; r += a w ; z_next = r (optional) in one pass (qmg_batch_gcr_update_t)"""
     nj = len(ws)
     cf = np.ascontiguousarray(np.asarray(coeffs, dtype=np.complex128).reshape(max(nj, 1), nrhs)).view(np.float64) if nj else None
     ptrs = (C.c_void_p * max(nj, 1))(*[x.ptr for x in ws]) if nj else None
     av = np.ascontiguousarray(np.asarray(a, dtype=np.complex128).reshape(nrhs)).view(np.float64)
     check(lib().qmg_batch_gcr_update_t(dtype, cf.ctypes.data_as(C.POINTER(C.c_double)) if nj else None, ptrs, nj, _vp(w), av.ctypes.data_as(C.POINTER(C.c_double)), _vp(r),
-                                       _vp(z_next), C.c_size_t(n), nrhs, C.c_size_t(stride), C.c_uint(mask), None), "qmg_batch_gcr_update_t")
+                                       _vp(z_next), C.c_size_t(n), nrhs, C.c_size_t(stride), C.c_uint(mask), C.c_void_p(stream)), "qmg_batch_gcr_update_t")
 
 
-def batch_cgm_update_status(dtype, xs, ps, a, z, c, shift_masks, r, n, nrhs, stride, mask, ns=None):
+def batch_cgm_update_status(dtype, xs, ps, a, z, c, shift_masks, r, n, nrhs, stride, mask, ns=None, stream=None):
     """qmg_batch_cgm_update_t's status code (xs / ps / a / z / c / shift_masks may be None: the argument checks are part of the ABI)"""
     ns = len(xs) if ns is None else ns
 
@@ -598,68 +653,68 @@ def batch_cgm_update_status(dtype, xs, ps, a, z, c, shift_masks, r, n, nrhs, str
     av, zv, cv = reals(a), reals(z), reals(c)
     dp = lambda v: v.ctypes.data_as(C.POINTER(C.c_double)) if v is not None else None
     sm = (C.c_uint * max(len(shift_masks), 1))(*shift_masks) if shift_masks is not None else None
-    return lib().qmg_batch_cgm_update_t(dtype, table(xs), table(ps), ns, dp(av), dp(zv), dp(cv), sm, _vp(r), C.c_size_t(n), nrhs, C.c_size_t(stride), C.c_uint(mask), None)
+    return lib().qmg_batch_cgm_update_t(dtype, table(xs), table(ps), ns, dp(av), dp(zv), dp(cv), sm, _vp(r), C.c_size_t(n), nrhs, C.c_size_t(stride), C.c_uint(mask), C.c_void_p(stream))
 
 
-def batch_cgm_update_t(dtype, xs, ps, a, z, c, shift_masks, r, n, nrhs, stride, mask):
+def batch_cgm_update_t(dtype, xs, ps, a, z, c, shift_masks, r, n, nrhs, stride, mask, stream=None):
     """x[s] += a[s] p[s] ; p[s] = z[s] r + c[s] p[s] for the systems of mask & shift_masks[s], every shift in one pass (qmg_batch_cgm_update_t);
     a, z, c: real, shape (ns, nrhs)"""
-    check(batch_cgm_update_status(dtype, xs, ps, a, z, c, shift_masks, r, n, nrhs, stride, mask), "qmg_batch_cgm_update_t")
+    check(batch_cgm_update_status(dtype, xs, ps, a, z, c, shift_masks, r, n, nrhs, stride, mask, stream=stream), "qmg_batch_cgm_update_t")
 
 
-def batch_reduce_t(dtype, op, x, y, n, nrhs, stride, mask):
+def batch_reduce_t(dtype, op, x, y, n, nrhs, stride, mask, stream=None):
     out = np.full(2 * nrhs, np.nan)
-    check(lib().qmg_batch_reduce_t(dtype, op, _vp(x), _vp(y), C.c_size_t(n), nrhs, C.c_size_t(stride), C.c_uint(mask), out.ctypes.data_as(C.POINTER(C.c_double)), None),
+    check(lib().qmg_batch_reduce_t(dtype, op, _vp(x), _vp(y), C.c_size_t(n), nrhs, C.c_size_t(stride), C.c_uint(mask), out.ctypes.data_as(C.POINTER(C.c_double)), C.c_void_p(stream)),
           "qmg_batch_reduce_t")
     return out[0::2] + 1j * out[1::2]
 
 
-def batch_multidot_t(dtype, xs, y, n, nrhs, stride, mask):
+def batch_multidot_t(dtype, xs, y, n, nrhs, stride, mask, stream=None):
     nj = len(xs)
     ptrs = (C.c_void_p * nj)(*[x.ptr for x in xs])
     out = np.full(2 * nrhs * nj, np.nan)
-    check(lib().qmg_batch_multidot_t(dtype, ptrs, nj, _vp(y), C.c_size_t(n), nrhs, C.c_size_t(stride), C.c_uint(mask), out.ctypes.data_as(C.POINTER(C.c_double)), None),
+    check(lib().qmg_batch_multidot_t(dtype, ptrs, nj, _vp(y), C.c_size_t(n), nrhs, C.c_size_t(stride), C.c_uint(mask), out.ctypes.data_as(C.POINTER(C.c_double)), C.c_void_p(stream)),
           "qmg_batch_multidot_t")
     return (out[0::2] + 1j * out[1::2]).reshape(nrhs, nj)
 
 
-def basis_dot_t(dtype, V, nv, ldv, B, n, nrhs, stride, mask, out_dev=None):
+def basis_dot_t(dtype, V, nv, ldv, B, n, nrhs, stride, mask, out_dev=None, stream=None):
     """C[k][j] = <v_j, b_k> for one basis V shared by the batch (qmg_basis_dot_t); (nrhs, nv) complex array, NaN for inactive systems.
     out_dev: a DeviceArray of nrhs * nv complex128 to receive them on the device instead (returns None)."""
     if out_dev is not None:
         check(lib().qmg_basis_dot_t(dtype, _vp(V), nv, C.c_size_t(ldv), _vp(B), C.c_size_t(n), nrhs, C.c_size_t(stride), C.c_uint(mask),
-                                    C.cast(C.c_void_p(out_dev.ptr), C.POINTER(C.c_double)), 1, None), "qmg_basis_dot_t")
+                                    C.cast(C.c_void_p(out_dev.ptr), C.POINTER(C.c_double)), 1, C.c_void_p(stream)), "qmg_basis_dot_t")
         return None
     out = np.full(2 * nrhs * nv, np.nan)
     check(lib().qmg_basis_dot_t(dtype, _vp(V), nv, C.c_size_t(ldv), _vp(B), C.c_size_t(n), nrhs, C.c_size_t(stride), C.c_uint(mask),
-                                out.ctypes.data_as(C.POINTER(C.c_double)), 0, None), "qmg_basis_dot_t")
+                                out.ctypes.data_as(C.POINTER(C.c_double)), 0, C.c_void_p(stream)), "qmg_basis_dot_t")
     return (out[0::2] + 1j * out[1::2]).reshape(nrhs, nv)
 
 
-def basis_update_t(dtype, coeffs, V, nv, ldv, B, n, nrhs, stride, mask):
+def basis_update_t(dtype, coeffs, V, nv, ldv, B, n, nrhs, stride, mask, stream=None):
     """b_k += sum_j C[k][j] v_j (qmg_basis_update_t); coeffs: (nrhs, nv) complex on the host, or a DeviceArray of them"""
     if isinstance(coeffs, DeviceArray):
         cp, dev = C.cast(C.c_void_p(coeffs.ptr), C.POINTER(C.c_double)), 1
     else:
         cf = np.ascontiguousarray(np.asarray(coeffs, dtype=np.complex128).reshape(nrhs, nv)).view(np.float64)
         cp, dev = cf.ctypes.data_as(C.POINTER(C.c_double)), 0
-    check(lib().qmg_basis_update_t(dtype, cp, dev, _vp(V), nv, C.c_size_t(ldv), _vp(B), C.c_size_t(n), nrhs, C.c_size_t(stride), C.c_uint(mask), None),
+    check(lib().qmg_basis_update_t(dtype, cp, dev, _vp(V), nv, C.c_size_t(ldv), _vp(B), C.c_size_t(n), nrhs, C.c_size_t(stride), C.c_uint(mask), C.c_void_p(stream)),
           "qmg_basis_update_t")
 
 
-def batch_deflate_t(dtype, V, nv, ldv, inv_lambda_dev, B, E, n, nrhs, stride, mask):
+def batch_deflate_t(dtype, V, nv, ldv, inv_lambda_dev, B, E, n, nrhs, stride, mask, stream=None):
     """e_k = sum_j v_j <v_j, b_k> inv_lambda[j] (qmg_batch_deflate_t); inv_lambda_dev: a DeviceArray of nv float64"""
     check(lib().qmg_batch_deflate_t(dtype, _vp(V), nv, C.c_size_t(ldv), C.cast(C.c_void_p(inv_lambda_dev.ptr), C.POINTER(C.c_double)), _vp(B), _vp(E),
-                                    C.c_size_t(n), nrhs, C.c_size_t(stride), C.c_uint(mask), None), "qmg_batch_deflate_t")
+                                    C.c_size_t(n), nrhs, C.c_size_t(stride), C.c_uint(mask), C.c_void_p(stream)), "qmg_batch_deflate_t")
 
 
-def prolong_batch_t(dtype, nullvecs, nvec, coarse, fine, fdims, cdims, nrhs, cstride, fstride, mask):
-    check(lib().qmg_prolong_batch_t(dtype, _vp(nullvecs), nvec, _vp(coarse), _vp(fine), *fdims, *cdims, nrhs, C.c_size_t(cstride), C.c_size_t(fstride), C.c_uint(mask), None),
+def prolong_batch_t(dtype, nullvecs, nvec, coarse, fine, fdims, cdims, nrhs, cstride, fstride, mask, stream=None):
+    check(lib().qmg_prolong_batch_t(dtype, _vp(nullvecs), nvec, _vp(coarse), _vp(fine), *fdims, *cdims, nrhs, C.c_size_t(cstride), C.c_size_t(fstride), C.c_uint(mask), C.c_void_p(stream)),
           "qmg_prolong_batch_t")
 
 
-def restrict_batch_t(dtype, nullvecs, nvec, fine, coarse, fdims, cdims, nrhs, fstride, cstride, mask):
-    check(lib().qmg_restrict_batch_t(dtype, _vp(nullvecs), nvec, _vp(fine), _vp(coarse), *fdims, *cdims, nrhs, C.c_size_t(fstride), C.c_size_t(cstride), C.c_uint(mask), None),
+def restrict_batch_t(dtype, nullvecs, nvec, fine, coarse, fdims, cdims, nrhs, fstride, cstride, mask, stream=None):
+    check(lib().qmg_restrict_batch_t(dtype, _vp(nullvecs), nvec, _vp(fine), _vp(coarse), *fdims, *cdims, nrhs, C.c_size_t(fstride), C.c_size_t(cstride), C.c_uint(mask), C.c_void_p(stream)),
           "qmg_restrict_batch_t")
 
 
@@ -713,23 +768,23 @@ def batch_plan(entry, dtype, n, stride, nrhs, mask, op=0, nj=0, shift_masks=None
     return [tuple(out[BATCH_PLAN_INTS * p:BATCH_PLAN_INTS * (p + 1)]) for p in range(max_passes) if out[BATCH_PLAN_INTS * p] >= 0]
 
 
-def prolong_batch_nv32(null32, nvec, coarse, fine, fdims, cdims, nrhs, cstride, fstride, mask):
+def prolong_batch_nv32(null32, nvec, coarse, fine, fdims, cdims, nrhs, cstride, fstride, mask, stream=None):
     """complex<double> vectors, complex<float> null vectors (qmg_prolong_batch_nv32)"""
-    check(lib().qmg_prolong_batch_nv32(_vp(null32), nvec, _vp(coarse), _vp(fine), *fdims, *cdims, nrhs, C.c_size_t(cstride), C.c_size_t(fstride), C.c_uint(mask), None),
+    check(lib().qmg_prolong_batch_nv32(_vp(null32), nvec, _vp(coarse), _vp(fine), *fdims, *cdims, nrhs, C.c_size_t(cstride), C.c_size_t(fstride), C.c_uint(mask), C.c_void_p(stream)),
           "qmg_prolong_batch_nv32")
 
 
-def restrict_batch_nv32(null32, nvec, fine, coarse, fdims, cdims, nrhs, fstride, cstride, mask):
-    check(lib().qmg_restrict_batch_nv32(_vp(null32), nvec, _vp(fine), _vp(coarse), *fdims, *cdims, nrhs, C.c_size_t(fstride), C.c_size_t(cstride), C.c_uint(mask), None),
+def restrict_batch_nv32(null32, nvec, fine, coarse, fdims, cdims, nrhs, fstride, cstride, mask, stream=None):
+    check(lib().qmg_restrict_batch_nv32(_vp(null32), nvec, _vp(fine), _vp(coarse), *fdims, *cdims, nrhs, C.c_size_t(fstride), C.c_size_t(cstride), C.c_uint(mask), C.c_void_p(stream)),
           "qmg_restrict_batch_nv32")
 
 
-def convert_to_c16(dst, src, src_dtype, n):
-    check(lib().qmg_convert_to_c16(_vp(dst), _vp(src), src_dtype, C.c_size_t(n), None), "qmg_convert_to_c16")
+def convert_to_c16(dst, src, src_dtype, n, stream=None):
+    check(lib().qmg_convert_to_c16(_vp(dst), _vp(src), src_dtype, C.c_size_t(n), C.c_void_p(stream)), "qmg_convert_to_c16")
 
 
 def stencil_apply_h16(desc, lhs, rhs, pieces, nrhs=1, vec_stride=0, mask=1, stream=None):
-    check(lib().qmg_stencil_apply_h16(C.byref(desc), _vp(lhs), _vp(rhs), C.c_uint(pieces), nrhs, C.c_size_t(vec_stride), C.c_uint(mask), stream),
+    check(lib().qmg_stencil_apply_h16(C.byref(desc), _vp(lhs), _vp(rhs), C.c_uint(pieces), nrhs, C.c_size_t(vec_stride), C.c_uint(mask), C.c_void_p(stream)),
           "qmg_stencil_apply_h16")
 
 
@@ -743,31 +798,40 @@ SLAB_M16 = 0x400   # nc != 2, a multiple of 4: complex<half> matrices
 
 
 def halo_exchange(dtype, vec, Lx, Ly_local, nc, halo_lo, halo_hi, nrhs=1, vec_stride=0, halo_stride=0, stream=None):
-    check(lib().qmg_halo_exchange(dtype, _vp(vec), Lx, Ly_local, nc, _vp(halo_lo), _vp(halo_hi), nrhs, C.c_size_t(vec_stride), C.c_size_t(halo_stride), stream),
+    check(lib().qmg_halo_exchange(dtype, _vp(vec), Lx, Ly_local, nc, _vp(halo_lo), _vp(halo_hi), nrhs, C.c_size_t(vec_stride), C.c_size_t(halo_stride), C.c_void_p(stream)),
           "qmg_halo_exchange")
+
+
+def halo_exchange_parity(dtype, vec, Lx, Ly_local, nc, halo_lo, halo_hi, parities, nrhs=1, vec_stride=0, halo_stride=0, stream=None):
+    check(lib().qmg_halo_exchange_parity(dtype, _vp(vec), Lx, Ly_local, nc, _vp(halo_lo), _vp(halo_hi), nrhs, C.c_size_t(vec_stride), C.c_size_t(halo_stride),
+                                         C.c_uint(parities), C.c_void_p(stream)), "qmg_halo_exchange_parity")
+
+
+def rb_hopping_slab(rb_hopping, desc, cinv, cinv_halo_lo, cinv_halo_hi, stream=None):
+    check(lib().qmg_rb_hopping_slab(_vp(rb_hopping), C.byref(desc), _vp(cinv), _vp(cinv_halo_lo), _vp(cinv_halo_hi), C.c_void_p(stream)), "qmg_rb_hopping_slab")
 
 
 def stencil_apply_slab(storage, desc, lhs, rhs, halo_lo, halo_hi, pieces, nrhs=1, vec_stride=0, halo_stride=0, mask=1, rows=0, stream=None):
     check(lib().qmg_stencil_apply_slab(storage, C.byref(desc), _vp(lhs), _vp(rhs), _vp(halo_lo), _vp(halo_hi), C.c_uint(pieces), nrhs, C.c_size_t(vec_stride),
-                                       C.c_size_t(halo_stride), C.c_uint(mask), rows, stream), "qmg_stencil_apply_slab")
+                                       C.c_size_t(halo_stride), C.c_uint(mask), rows, C.c_void_p(stream)), "qmg_stencil_apply_slab")
 
 
 def wilson_fill_slab(clover, hopping, gauge_global, Lx, Ly_global, y0, Ly_local, w=1.0, stream=None):
-    check(lib().qmg_wilson_fill_slab(_vp(clover), _vp(hopping), _vp(gauge_global), Lx, Ly_global, y0, Ly_local, C.c_double(w), stream), "qmg_wilson_fill_slab")
+    check(lib().qmg_wilson_fill_slab(_vp(clover), _vp(hopping), _vp(gauge_global), Lx, Ly_global, y0, Ly_local, C.c_double(w), C.c_void_p(stream)), "qmg_wilson_fill_slab")
 
 
 def wilson_apply_direct(dtype, desc, gauge, lhs, rhs, pieces, w=1.0, nrhs=1, vec_stride=0, mask=1, gauge_Ly=None, y0=0, halo_lo=None, halo_hi=None,
                         halo_stride=0, rows=0, stream=None):
     check(lib().qmg_wilson_apply_direct(dtype, C.byref(desc), _vp(gauge), desc.Ly if gauge_Ly is None else gauge_Ly, y0, C.c_double(w), _vp(lhs), _vp(rhs),
                                         _vp(halo_lo), _vp(halo_hi), C.c_uint(pieces), nrhs, C.c_size_t(vec_stride), C.c_size_t(halo_stride), C.c_uint(mask), rows,
-                                        stream), "qmg_wilson_apply_direct")
+                                        C.c_void_p(stream)), "qmg_wilson_apply_direct")
 
 
 def wilson_hops_direct(dtype, desc, gauge, lhs, rhs, pieces, w, hop_scale, nrhs=1, vec_stride=0, mask=1, gauge_Ly=None, y0=0, halo_lo=None, halo_hi=None,
                        halo_stride=0, rows=0, stream=None):
     check(lib().qmg_wilson_hops_direct(dtype, C.byref(desc), _vp(gauge), desc.Ly if gauge_Ly is None else gauge_Ly, y0, C.c_double(w), C.c_double(hop_scale),
                                        _vp(lhs), _vp(rhs), _vp(halo_lo), _vp(halo_hi), C.c_uint(pieces), nrhs, C.c_size_t(vec_stride), C.c_size_t(halo_stride),
-                                       C.c_uint(mask), rows, stream), "qmg_wilson_hops_direct")
+                                       C.c_uint(mask), rows, C.c_void_p(stream)), "qmg_wilson_hops_direct")
 
 
 # families, flags and the epilogue description of qmg_wilson_plan (include/qmg_hip.h)
@@ -832,8 +896,7 @@ def dwf_inv5_status(dtype, desc, Ls, mass, lhs, rhs, pieces, alpha=1.0, w=1.0, n
                               C.c_double(alpha.real), C.c_double(alpha.imag), nrhs, C.c_size_t(vec_stride), C.c_uint(mask), C.c_void_p(stream))
 
 
-def dwf_inv5(*args, **kw):
-    check(dwf_inv5_status(*args, **kw), "qmg_dwf_inv5")
+dwf_inv5 = _checked(dwf_inv5_status, "qmg_dwf_inv5")
 
 
 def dwf_hops_inv5_status(dtype, desc, gauge, Ls, mass, lhs, rhs, pieces, alpha=1.0, flags=0, w=1.0, nrhs=1, vec_stride=0, mask=1, stream=None):
@@ -844,8 +907,7 @@ def dwf_hops_inv5_status(dtype, desc, gauge, Ls, mass, lhs, rhs, pieces, alpha=1
                                    C.c_void_p(stream))
 
 
-def dwf_hops_inv5(*args, **kw):
-    check(dwf_hops_inv5_status(*args, **kw), "qmg_dwf_hops_inv5")
+dwf_hops_inv5 = _checked(dwf_hops_inv5_status, "qmg_dwf_hops_inv5")
 
 
 def dwf_schur_apply_status(dtype, desc, gauge, Ls, mass, lhs, rhs, tmp, parity=0, flags=0, w=1.0, nrhs=1, vec_stride=0, mask=1, stream=None):
@@ -855,8 +917,7 @@ def dwf_schur_apply_status(dtype, desc, gauge, Ls, mass, lhs, rhs, tmp, parity=0
                                      parity, C.c_uint(flags), nrhs, C.c_size_t(vec_stride), C.c_uint(mask), C.c_void_p(stream))
 
 
-def dwf_schur_apply(*args, **kw):
-    check(dwf_schur_apply_status(*args, **kw), "qmg_dwf_schur_apply")
+dwf_schur_apply = _checked(dwf_schur_apply_status, "qmg_dwf_schur_apply")
 
 
 def dwf_eo_plan(dtype, dims, Ls, kernel, pieces, n_active=1, inplace=False):
@@ -878,8 +939,7 @@ def dwf_wall_source_status(dtype, dims, Ls, psi5, eta4, nsys=1, stride5=0, strid
     return lib().qmg_dwf_wall_source(dtype, dims[0], dims[1], Ls, _vp(psi5), _vp(eta4), nsys, C.c_size_t(stride5), C.c_size_t(stride4), C.c_void_p(stream))
 
 
-def dwf_wall_source(*args, **kw):
-    check(dwf_wall_source_status(*args, **kw), "qmg_dwf_wall_source")
+dwf_wall_source = _checked(dwf_wall_source_status, "qmg_dwf_wall_source")
 
 
 def dwf_wall_project_status(dtype, dims, Ls, q4, psi5, which=0, nsys=1, stride4=0, stride5=0, stream=None):
@@ -887,8 +947,7 @@ def dwf_wall_project_status(dtype, dims, Ls, q4, psi5, which=0, nsys=1, stride4=
     return lib().qmg_dwf_wall_project(dtype, dims[0], dims[1], Ls, _vp(q4), _vp(psi5), which, nsys, C.c_size_t(stride4), C.c_size_t(stride5), C.c_void_p(stream))
 
 
-def dwf_wall_project(*args, **kw):
-    check(dwf_wall_project_status(*args, **kw), "qmg_dwf_wall_project")
+dwf_wall_project = _checked(dwf_wall_project_status, "qmg_dwf_wall_project")
 
 
 def dwf_slice_norms_status(dtype, dims, Ls, psi5, nsys=1, stride5=0, out_dev=None, out_host=None, stream=None):
@@ -929,8 +988,7 @@ def noise_dilute_batch_status(dtype, out, dims, nc, dil, first_class, seed, nrhs
                                         C.c_size_t(stride), C.c_uint(mask), C.c_void_p(stream))
 
 
-def noise_dilute_batch(*args, **kw):
-    check(noise_dilute_batch_status(*args, **kw), "qmg_noise_dilute_batch")
+noise_dilute_batch = _checked(noise_dilute_batch_status, "qmg_noise_dilute_batch")
 
 
 def loops_timeslice_batch_status(dtype, psi, dims, nc, dil, first_class, seed, g5_mode, nrhs=1, stride=0, mask=None, out_dev=None, out_host=None, stream=None):
@@ -972,28 +1030,28 @@ def comm_all_ok(ok):
     return bool(out.value)
 
 
-def u1_heatbath_noncompact(phase, Lx, Ly, beta, n_update, seed, first_sweep=0):
-    check(lib().qmg_u1_heatbath_noncompact(_vp(phase), Lx, Ly, C.c_double(beta), n_update, C.c_ulonglong(seed), C.c_ulonglong(first_sweep), None), "qmg_u1_heatbath_noncompact")
+def u1_heatbath_noncompact(phase, Lx, Ly, beta, n_update, seed, first_sweep=0, stream=None):
+    check(lib().qmg_u1_heatbath_noncompact(_vp(phase), Lx, Ly, C.c_double(beta), n_update, C.c_ulonglong(seed), C.c_ulonglong(first_sweep), C.c_void_p(stream)), "qmg_u1_heatbath_noncompact")
 
 
-def u1_phase_to_gauge(gauge, phase, n):
-    check(lib().qmg_u1_phase_to_gauge(_vp(gauge), _vp(phase), C.c_size_t(n), None), "qmg_u1_phase_to_gauge")
+def u1_phase_to_gauge(gauge, phase, n, stream=None):
+    check(lib().qmg_u1_phase_to_gauge(_vp(gauge), _vp(phase), C.c_size_t(n), C.c_void_p(stream)), "qmg_u1_phase_to_gauge")
 
 
-def u1_gauge_to_phase(phase, gauge, n):
-    check(lib().qmg_u1_gauge_to_phase(_vp(phase), _vp(gauge), C.c_size_t(n), None), "qmg_u1_gauge_to_phase")
+def u1_gauge_to_phase(phase, gauge, n, stream=None):
+    check(lib().qmg_u1_gauge_to_phase(_vp(phase), _vp(gauge), C.c_size_t(n), C.c_void_p(stream)), "qmg_u1_gauge_to_phase")
 
 
-def u1_plaquette(gauge, Lx, Ly):
+def u1_plaquette(gauge, Lx, Ly, stream=None):
     """(average plaquette, topological charge)"""
     out = (C.c_double * 3)()
-    check(lib().qmg_u1_plaquette(_vp(gauge), Lx, Ly, out, None), "qmg_u1_plaquette")
+    check(lib().qmg_u1_plaquette(_vp(gauge), Lx, Ly, out, C.c_void_p(stream)), "qmg_u1_plaquette")
     return complex(out[0], out[1]), out[2]
 
 
-def u1_noncompact_action(phase, Lx, Ly, beta):
+def u1_noncompact_action(phase, Lx, Ly, beta, stream=None):
     out = C.c_double()
-    check(lib().qmg_u1_noncompact_action(_vp(phase), Lx, Ly, C.c_double(beta), C.byref(out), None), "qmg_u1_noncompact_action")
+    check(lib().qmg_u1_noncompact_action(_vp(phase), Lx, Ly, C.c_double(beta), C.byref(out), C.c_void_p(stream)), "qmg_u1_noncompact_action")
     return out.value
 
 
@@ -1068,9 +1126,8 @@ def hmc_momentum_update_dwf_status(pi, gauge, X, Y, weights, Ls, Lx, Ly, beta, d
     return lib().qmg_hmc_momentum_update_dwf(_vp(pi), _vp(gauge), xs, ys, ws, n, Ls, Lx, Ly, C.c_double(beta), C.c_double(dt), C.c_uint(flags), C.c_void_p(stream))
 
 
-def hmc_momentum_update_dwf(*args, **kw):
-    """pi -= dt (gauge force + sum_j weights[j] sum_s Ff(X[j](.; s), Y[j](.; s))) in one pass; X, Y: sequences of device nc = 2 Ls vectors"""
-    check(hmc_momentum_update_dwf_status(*args, **kw), "qmg_hmc_momentum_update_dwf")
+# pi -= dt (gauge force + sum_j weights[j] sum_s Ff(X[j](.; s), Y[j](.; s))) in one pass; X, Y: sequences of device nc = 2 Ls vectors
+hmc_momentum_update_dwf = _checked(hmc_momentum_update_dwf_status, "qmg_hmc_momentum_update_dwf")
 
 
 def hmc_dwf_plan_status(dims, Ls, n_pairs, flags=0):

@@ -457,6 +457,9 @@ int get_bws(BatchWorkspace** out) {
     QMG_HIP_CHECK(hipMemset(g_bws.result, 0, sizeof(double) * WS_RESULTS));
     QMG_HIP_CHECK(hipMalloc((void**)&g_bws.mr, sizeof(double) * BATCH_MAX * 4));
     QMG_HIP_CHECK(hipMemset(g_bws.mr, 0, sizeof(double) * BATCH_MAX * 4));
+    // The three memsets are null-stream work, and the thread's first reduction may be on a non-blocking stream, which is not ordered behind
+    // them: `done` is that reduction's arrival counter.  Once per thread, as in poison_new_scratch.
+    QMG_HIP_CHECK(hipDeviceSynchronize());
     g_bws.device = dev;
   }
   *out = &g_bws;
