@@ -10,11 +10,16 @@
 //   n21  rbj-dagger normal equations (CGNE / CGNR)           (tests/n21_rbj_dagger_stencil_test:138-209)
 //   storage / lattice / multigrid bookkeeping
 //   the route of an apply: in each live state the facade gives, bit for bit, what the entry point named by the policy table gives
+//   the narrow copies of the matrices: which of them exist, and which uses are on, after each enable_* / disable_* / build_* / update_links call
 #include <cmath>
 #include <cstring>
 #include <functional>
+#include <initializer_list>
 #include <iostream>
+#include <sstream>
 #include <string>
+#include <utility>
+#include <vector>
 
 #include <unistd.h>
 
@@ -66,6 +71,47 @@ struct RouteCheck {
     const std::vector<complex<double>> g = qmg::to_host(got, 3 * n), w = qmg::to_host(want, 3 * n), i0 = qmg::to_host(init, 3 * n);
     const bool same = memcmp(g.data(), w.data(), 3 * n * sizeof(complex<double>)) == 0, wrote = memcmp(g.data(), i0.data(), 3 * n * sizeof(complex<double>)) != 0;
     check(state_ok && served && rc == QMG_SUCCESS && same && wrote, "route: " + what, rc);
+  }
+};
+
+// Which narrow matrix copies an operator holds, as "S<bits>:<copies> F<on>:<copies> H<on>:<copies> <g>".  S: the storage under fp64 vectors
+// (enable_f32_matrices), with its width 32 / 16 or - while off; F: the complex<float> shadow and H: its complex<half> copies (enable_f32_shadow), + on, - off.
+// One letter per copy that is there: c clover, h hopping, r right-block-Jacobi hops, i cinv, C / H the dagger stencil's clover / hops, R the rbj-dagger hops.
+// g: direct.gauge32 is there, -: it is not.
+typedef Stencil2D S;
+enum { STORAGE = S::QMG_NARROW_STORAGE, SHADOW = S::QMG_NARROW_SHADOW, HALF = S::QMG_NARROW_SHADOW_HALF };
+static void* clover_copy(const Stencil2D& s, int use, S::QMGArraySet set = S::QMG_ARR_ORIGINAL) { return s.narrow[use].copy[set][S::QMG_SLOT_CLOVER]; }
+static void* hopping_copy(const Stencil2D& s, int use, S::QMGArraySet set = S::QMG_ARR_ORIGINAL) { return s.narrow[use].copy[set][S::QMG_SLOT_HOPPING]; }
+static string narrow_census(const Stencil2D& s) {
+  auto there = [](std::initializer_list<std::pair<const void*, char>> copies) { string o; for (const auto& c : copies) if (c.first) o += c.second; return o; };
+  const S::NarrowCopies &st = s.narrow[STORAGE], &f = s.narrow[SHADOW], &h = s.narrow[HALF];
+  return "S" + (st.on ? to_string(st.bits) : string("-")) + ":" +
+         there({{clover_copy(s, STORAGE), 'c'}, {hopping_copy(s, STORAGE), 'h'}, {hopping_copy(s, STORAGE, S::QMG_ARR_RBJ_HOPPING), 'r'}, {clover_copy(s, STORAGE, S::QMG_ARR_RBJ_CINV), 'i'}}) +
+         " F" + (f.on ? "+:" : "-:") + there({{clover_copy(s, SHADOW), 'c'}, {hopping_copy(s, SHADOW), 'h'}, {hopping_copy(s, SHADOW, S::QMG_ARR_RBJ_HOPPING), 'r'}, {clover_copy(s, SHADOW, S::QMG_ARR_RBJ_CINV), 'i'},
+                                              {clover_copy(s, SHADOW, S::QMG_ARR_DAGGER), 'C'}, {hopping_copy(s, SHADOW, S::QMG_ARR_DAGGER), 'H'}, {hopping_copy(s, SHADOW, S::QMG_ARR_RBJ_DAGGER), 'R'}}) +
+         " H" + (h.on ? "+:" : "-:") + there({{clover_copy(s, HALF), 'c'}, {hopping_copy(s, HALF), 'h'}, {hopping_copy(s, HALF, S::QMG_ARR_RBJ_HOPPING), 'r'}}) + (s.direct.gauge32 ? " g" : " -");
+}
+// what a call prints is kept out of the program's output (the drivers' tests take a [QMG-WARNING] / [QMG-ERROR] line for a failure) and handed to the check
+struct Captured {
+  std::ostringstream text;
+  std::streambuf* old;
+  Captured() : old(cout.rdbuf(text.rdbuf())) {}
+  ~Captured() { cout.rdbuf(old); }
+};
+// a fresh Galerkin operator of `fine` on (L / 4)^2 with nc = nvec
+struct Galerkin {
+  Lattice2D lat;
+  std::vector<complex<double>*> nv;
+  TransferMG* transfer;
+  CoarseOperator2D* op;
+  Galerkin(Lattice2D* fine_lat, Stencil2D* fine, int L, int nvec, CoarseOperator2D::QMGCoarseBuildStencil extra) : lat(L / 4, L / 4, nvec), nv(nvec) {
+    for (int j = 0; j < nvec; j++) { nv[j] = allocate_vector<complex<double>>(fine_lat->get_size_cv_l()); gaussian(nv[j], fine_lat->get_size_cv_l(), 1300ull + j); }
+    transfer = new TransferMG(fine_lat, &lat, nv.data(), true, false, QMG_DOUBLE_NONE);
+    op = new CoarseOperator2D(&lat, fine, fine_lat, transfer, false, false, extra);
+  }
+  ~Galerkin() {
+    delete op; delete transfer;
+    for (auto& v : nv) deallocate_vector(&v);
   }
 };
 
@@ -277,7 +323,7 @@ int main(int argc, char** argv) {
     const bool f16on = co.enable_f32_matrices(16);
     zero_vector(a1, ncv); co.apply_M(a1, v);
     const double d16 = sqrt(diffnorm2sq(a1, a2, ncv) / norm2sq(a2, ncv));
-    check(f16on && co.f32_bits == 16 && d16 > 1e-6 && d16 < 2e-3, "apply_M with 16-bit-stored matrices is the fp64 apply to half rounding", d16);
+    check(f16on && co.narrow[STORAGE].bits == 16 && d16 > 1e-6 && d16 < 2e-3, "apply_M with 16-bit-stored matrices is the fp64 apply to half rounding", d16);
     co.disable_f32_matrices();
     for (complex<double>** p : {&v, &a1, &a2}) deallocate_vector(p);
     for (int j = 0; j < nvec; j++) deallocate_vector(&nv[j]);
@@ -344,26 +390,26 @@ int main(int argc, char** argv) {
       const qmg_apply_epilogue e = {route.other, 1.0, -1.0, 0};
       qmg_stencil_desc d = co.desc(), d0 = co.desc();   // d0: arrays by hand, no shifts (the right-block-Jacobi pieces)
       for (int i = 0; i < 2; i++) d0.shift[i] = d0.eo_shift[i] = d0.dof_shift[i] = 0.0;
-      route("Galerkin nc = 8, fp64 == qmg_stencil_apply_batch", !co.f32_matrices, [&](void* o) { co.apply_M_overwrite((complex<double>*)o, route.in); return true; },
+      route("Galerkin nc = 8, fp64 == qmg_stencil_apply_batch", !co.narrow[STORAGE].on, [&](void* o) { co.apply_M_overwrite((complex<double>*)o, route.in); return true; },
             [&](void* o) { return qmg_stencil_apply_batch(&d, o, route.in, M0, 1, 0, 1u, st); });
       route("Galerkin nc = 8, epilogue on system 1 of 2 == qmg_stencil_apply_epi_t", true,
             [&](void* o) { return co.launch_set_epi<double>(M0, (complex<double>*)o, route.in, Stencil2D::QMG_ARR_ORIGINAL, co.shift, co.eo_shift, co.dof_shift, n, 1, e); },
             [&](void* o) { return qmg_stencil_apply_epi_t(QMG_C64, 0, &d, o, route.in, M0, n, 1, &e, st); });
       bool on = co.enable_f32_matrices(32);
-      d.clover = co.clover32; d.hopping = co.hopping32;
-      route("Galerkin nc = 8, enable_f32_matrices(32) == qmg_stencil_apply_mat32", on && co.f32_bits == 32 && co.clover32 && co.hopping32,
+      d.clover = clover_copy(co, STORAGE); d.hopping = hopping_copy(co, STORAGE);
+      route("Galerkin nc = 8, enable_f32_matrices(32) == qmg_stencil_apply_mat32", on && co.narrow[STORAGE].bits == 32 && d.clover && d.hopping,
             [&](void* o) { co.apply_M_overwrite((complex<double>*)o, route.in); return true; }, [&](void* o) { return qmg_stencil_apply_mat32(&d, o, route.in, M0, 1, 0, 1u, st); });
-      d0.clover = 0; d0.hopping = co.rbj_hopping32;
-      route("Galerkin nc = 8, rbj hops alone == qmg_stencil_apply_mat32 on rbj_hopping32", co.rbj_hopping32 != 0,
+      d0.clover = 0; d0.hopping = hopping_copy(co, STORAGE, S::QMG_ARR_RBJ_HOPPING);
+      route("Galerkin nc = 8, rbj hops alone == qmg_stencil_apply_mat32 on rbj_hopping32", d0.hopping != 0,
             [&](void* o) { co.launch_set_batch<double>(OE0, (complex<double>*)o, route.in, Stencil2D::QMG_ARR_RBJ_HOPPING, 0.0, 0.0, 0.0, 2, n, 0b10u); return true; },
             [&](void* o) { return qmg_stencil_apply_mat32(&d0, o, route.in, OE0, 2, n, 0b10u, st); });
-      d0.clover = co.rbj_cinv32; d0.hopping = 0;
-      route("Galerkin nc = 8, cinv alone == qmg_stencil_apply_mat32 on rbj_cinv32", co.rbj_cinv32 != 0,
+      d0.clover = clover_copy(co, STORAGE, S::QMG_ARR_RBJ_CINV); d0.hopping = 0;
+      route("Galerkin nc = 8, cinv alone == qmg_stencil_apply_mat32 on rbj_cinv32", d0.clover != 0,
             [&](void* o) { co.launch_set_batch<double>(C0, (complex<double>*)o, route.in, Stencil2D::QMG_ARR_RBJ_CINV, 0.0, 0.0, 0.0, 2, n, 0b11u); return true; },
             [&](void* o) { return qmg_stencil_apply_mat32(&d0, o, route.in, C0, 2, n, 0b11u, st); });
       on = co.enable_f32_matrices(16);
-      d.clover = co.clover32; d.hopping = co.hopping32;
-      route("Galerkin nc = 8, enable_f32_matrices(16) == qmg_stencil_apply_mat16_t", on && co.f32_bits == 16 && co.clover32 && co.hopping32,
+      d.clover = clover_copy(co, STORAGE); d.hopping = hopping_copy(co, STORAGE);
+      route("Galerkin nc = 8, enable_f32_matrices(16) == qmg_stencil_apply_mat16_t", on && co.narrow[STORAGE].bits == 16 && d.clover && d.hopping,
             [&](void* o) { co.apply_M_overwrite((complex<double>*)o, route.in); return true; },
             [&](void* o) { return qmg_stencil_apply_mat16_t(QMG_C64, &d, o, route.in, M0, 1, 0, 1u, st); });
       co.disable_f32_matrices();
@@ -437,13 +483,124 @@ int main(int argc, char** argv) {
     w.drop_direct_links();
     route("Wilson, links dropped == qmg_stencil_apply_batch", !w.direct.on, apply_M, [&](void* o) { return qmg_stencil_apply_batch(&d, o, route.in, M0, 1, 0, 1u, st); });
     qmg_stencil_desc dn = d;
-    dn.clover = w.f32.clover; dn.hopping = w.f32.hopping;
-    route("Wilson, fp32 batch of 3, mask 0b101, shadow == qmg_stencil_apply_t", w.f32.on && !w.f32.half_on, batch32,
+    dn.clover = clover_copy(w, SHADOW); dn.hopping = hopping_copy(w, SHADOW);
+    route("Wilson, fp32 batch of 3, mask 0b101, shadow == qmg_stencil_apply_t", w.narrow[SHADOW].on && !w.narrow[HALF].on, batch32,
           [&](void* o) { return qmg_stencil_apply_t(QMG_C32, &dn, o, route.in32, M0, 3, n, 0b101u, st); });
     on = w.enable_f32_shadow(true);
-    dn.clover = w.f32.clover16; dn.hopping = w.f32.hopping16;
-    route("Wilson, fp32 batch of 3, mask 0b101, half shadow == qmg_stencil_apply_h16", on && w.f32.half_on, batch32,
+    dn.clover = clover_copy(w, HALF); dn.hopping = hopping_copy(w, HALF);
+    route("Wilson, fp32 batch of 3, mask 0b101, half shadow == qmg_stencil_apply_h16", on && w.narrow[HALF].on, batch32,
           [&](void* o) { return qmg_stencil_apply_h16(&dn, o, route.in32, M0, 3, n, 0b101u, st); });
+  }
+
+  // ---- which narrow copies of the matrices exist after which call (narrow_census): the answers are written out by hand from the rules of
+  // enable_f32_matrices / narrow_rbjacobi_copies / enable_f32_shadow and their disable_* (include/qmg/stencil2d.hpp)
+  {
+    typedef CoarseOperator2D C;
+    auto copies = [&](const string& what, Stencil2D& op, bool as_expected, const string& want) {
+      const string got = narrow_census(op);
+      check(as_expected && got == want, "copies: " + what + " -> " + want + (got == want ? "" : " (got " + got + ")"), 0);
+    };
+    auto said = [](const Captured& c, const char* line) { return c.text.str().find(line) != string::npos; };
+    {   // storage under fp64 vectors, Galerkin nc = 8, the right-block-Jacobi stencil built AFTER the copies
+      Galerkin g(&lat2, &wilson, L, 8, C::QMG_COARSE_BUILD_ORIGINAL);
+      Stencil2D& op = *g.op;
+      copies("Galerkin nc = 8, fresh", op, true, "S-: F-: H-: -");
+      bool on = op.enable_f32_matrices(32);
+      copies("enable_f32_matrices(32)", op, on, "S32:ch F-: H-: -");
+      on = op.enable_f32_matrices(16);
+      copies("enable_f32_matrices(16) over it", op, on, "S16:ch F-: H-: -");
+      op.build_rbjacobi_stencil();
+      copies("build_rbjacobi_stencil after it: its copies in the level's width", op, op.built_rbjacobi, "S16:chri F-: H-: -");
+      op.disable_f32_matrices();
+      copies("disable_f32_matrices", op, true, "S-: F-: H-: -");
+      on = op.enable_f32_matrices(32);
+      copies("enable_f32_matrices(32) after build_rbjacobi_stencil", op, on, "S32:chri F-: H-: -");
+      on = op.enable_f32_matrices(16);
+      copies("enable_f32_matrices(16) after build_rbjacobi_stencil", op, on, "S16:chri F-: H-: -");
+      on = op.enable_f32_shadow(true);
+      copies("enable_f32_shadow(true) beside the storage", op, on, "S16:chri F+:chri H+:chr -");
+      op.disable_f32_shadow();
+      copies("disable_f32_shadow leaves the storage", op, true, "S16:chri F-: H-: -");
+      on = op.enable_f32_shadow(false);
+      op.disable_f32_matrices();
+      copies("disable_f32_matrices leaves the shadow", op, on, "S-: F+:chri H-: -");
+    }
+    {   // the shadows of a Galerkin operator with every variant built; no links, so no gauge32
+      Galerkin g(&lat2, &wilson, L, 8, C::QMG_COARSE_BUILD_ALL);
+      Stencil2D& op = *g.op;
+      bool on = op.enable_f32_shadow(false);
+      copies("Galerkin nc = 8, every variant built, enable_f32_shadow(false)", op, on, "S-: F+:chriCHR H-: -");
+      on = op.enable_f32_shadow(true);
+      copies("... enable_f32_shadow(true)", op, on, "S-: F+:chriCHR H+:chr -");
+      op.disable_f32_shadow();
+      copies("... disable_f32_shadow", op, true, "S-: F-: H-: -");
+    }
+    {   // nc = 4: no storage, no half shadow
+      Galerkin g(&lat2, &wilson, L, 4, C::QMG_COARSE_BUILD_ORIGINAL);
+      Stencil2D& op = *g.op;
+      bool on;
+      { Captured c; on = op.enable_f32_matrices(32); on = on || !said(c, "fp32 matrix storage is not available for nc = 4."); }
+      copies("Galerkin nc = 4, enable_f32_matrices(32) refuses", op, !on, "S-: F-: H-: -");
+      on = op.enable_f32_shadow(true);
+      copies("Galerkin nc = 4, enable_f32_shadow(true): complex<float> only", op, on, "S-: F+:ch H-: -");
+    }
+    {   // the Wilson operator (nc = 2, applied from its links): no storage; the shadow with each variant built and not; gauge32 outlives the shadow
+      Wilson2D w(&lat2, complex<double>(0.05, 0.0), gauge);
+      copies("Wilson, fresh", w, w.direct.on, "S-: F-: H-: -");
+      bool on;
+      { Captured c; on = w.enable_f32_matrices(32); on = on || !said(c, "fp32 matrix storage is not available for nc = 2."); }
+      copies("Wilson, enable_f32_matrices(32) refuses", w, !on, "S-: F-: H-: -");
+      { Captured c; on = w.enable_f32_matrices(16); on = on || !said(c, "fp32 matrix storage is not available for nc = 2."); }
+      copies("Wilson, enable_f32_matrices(16) refuses", w, !on, "S-: F-: H-: -");
+      on = w.enable_f32_shadow(false);
+      copies("Wilson, no variant, enable_f32_shadow(false)", w, on, "S-: F+:ch H-: g");
+      on = w.enable_f32_shadow(true);
+      copies("Wilson, no variant, enable_f32_shadow(true)", w, on, "S-: F+:ch H+:ch g");
+      w.disable_f32_shadow();
+      copies("Wilson, disable_f32_shadow leaves gauge32", w, w.direct.gauge32 != 0, "S-: F-: H-: g");
+      w.build_rbjacobi_stencil();
+      on = w.enable_f32_shadow(false);
+      copies("Wilson, rbjacobi built, enable_f32_shadow(false)", w, on, "S-: F+:chri H-: g");
+      on = w.enable_f32_shadow(true);
+      copies("Wilson, rbjacobi built, enable_f32_shadow(true)", w, on, "S-: F+:chri H+:chr g");
+      w.build_rbj_dagger_stencil();
+      on = w.enable_f32_shadow(false);
+      copies("Wilson, rbjacobi and rbj-dagger built, enable_f32_shadow(false)", w, on, "S-: F+:chriR H-: g");
+      on = w.enable_f32_shadow(true);
+      copies("Wilson, rbjacobi and rbj-dagger built, enable_f32_shadow(true)", w, on, "S-: F+:chriR H+:chr g");
+      w.build_dagger_stencil();
+      on = w.enable_f32_shadow(false);
+      copies("Wilson, every variant built, enable_f32_shadow(false)", w, on, "S-: F+:chriCHR H-: g");
+      on = w.enable_f32_shadow(true);
+      copies("Wilson, every variant built, enable_f32_shadow(true)", w, on, "S-: F+:chriCHR H+:chr g");
+      // while a variant is swapped in: refused, and the shadow that was on is gone
+      bool (Stencil2D::*const swaps[3])() = {&Stencil2D::perform_swap_dagger, &Stencil2D::perform_swap_rbjacobi, &Stencil2D::perform_swap_rbj_dagger};
+      const char* const names[3] = {"the dagger stencil", "the rbjacobi stencil", "the rbj-dagger stencil"};
+      for (int v = 0; v < 3; v++) {
+        on = w.enable_f32_shadow(v == 1);
+        const bool in = (w.*swaps[v])();
+        bool refused;
+        { Captured c; refused = !w.enable_f32_shadow(v != 1) && said(c, "enable_f32_shadow called while a stencil variant is swapped in."); }
+        const bool out = !(w.*swaps[v])();
+        copies(string("Wilson, enable_f32_shadow with ") + names[v] + " swapped in refuses", w, on && in && refused && out, "S-: F-: H-: g");
+      }
+      // update_links with a shadow on: the variants go, the copies stay as they were (stale: "call again after changing the matrices")
+      on = w.enable_f32_shadow(true);
+      const void* const before = clover_copy(w, SHADOW);
+      w.update_links(gauge);
+      copies("Wilson, update_links under a shadow: variants dropped, copies kept", w,
+             on && !w.built_dagger && !w.built_rbjacobi && !w.built_rbj_dagger && before != 0 && clover_copy(w, SHADOW) == before, "S-: F+:chriCHR H+:chr g");
+      on = w.enable_f32_shadow(true);
+      copies("Wilson, enable_f32_shadow(true) again after update_links", w, on, "S-: F+:ch H+:ch g");
+    }
+    {   // the dagger stencil alone
+      Wilson2D w(&lat2, complex<double>(0.05, 0.0), gauge);
+      w.build_dagger_stencil();
+      bool on = w.enable_f32_shadow(false);
+      copies("Wilson, dagger built alone, enable_f32_shadow(false)", w, on, "S-: F+:chCH H-: g");
+      on = w.enable_f32_shadow(true);
+      copies("Wilson, dagger built alone, enable_f32_shadow(true)", w, on, "S-: F+:chCH H+:ch g");
+    }
   }
 
   deallocate_vector(&gauge);

@@ -119,7 +119,8 @@ inline bool apply_M_rbjacobi_batch(Stencil2D* st, qmg::BatchT<T> lhs, qmg::Batch
 template <typename T>
 inline bool apply_M_rbj_dagger_batch(Stencil2D* st, qmg::BatchT<T> lhs, qmg::BatchT<T> rhs, unsigned mask) {
   if (!st->built_rbj_dagger) { std::cout << "[QMG-WARNING]: Tried to call apply_M_rbj_dagger (batch), but the right jacobi dagger stencil has not been allocated.\n"; return false; }
-  if (sizeof(T) == sizeof(float) && (!st->f32.on || st->f32.rbj_dagger_hopping == 0)) {
+  const Stencil2D::NarrowCopies& shadow = st->narrow[Stencil2D::QMG_NARROW_SHADOW];
+  if (sizeof(T) == sizeof(float) && (!shadow.on || shadow.copy[Stencil2D::QMG_ARR_RBJ_DAGGER][Stencil2D::QMG_SLOT_HOPPING] == 0)) {
     std::cout << "[QMG-ERROR]: fp32 right-block-Jacobi dagger apply without its fp32 shadow (build_rbj_dagger_stencil before enable_f32_shadow).\n";
     return false;
   }

@@ -264,7 +264,7 @@ inline void StatefulMultigridMG::deflate_coarsest(int num_low, int num_high, boo
   for (int i = 0; i < nev; i++) { coarsest_evals[i] = complex<double>(ev[i], 0.0); coarsest_evecs[i] = evec_block + (size_t)i * N; inv[i] = 1.0 / ev[i]; }
   inv_lambda_dev = allocate_vector<double>((size_t)nev);
   if (inv_lambda_dev) qmg::upload(inv_lambda_dev, inv.data(), (size_t)nev);
-  if (st->f32.on) deflation_basis_f32();   // the fp32 K-cycle's shadow hierarchy already exists
+  if (st->narrow[Stencil2D::QMG_NARROW_SHADOW].on) deflation_basis_f32();   // the fp32 K-cycle's shadow hierarchy already exists
   if (print_evals)
     for (int i = 0; i < nev; i++) std::cout << "[QMG-COARSEST-EVALS]: " << i << " " << ev[i] << "\n";
 }

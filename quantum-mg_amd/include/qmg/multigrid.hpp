@@ -120,8 +120,15 @@ class MultigridMG {
     return f < 0 ? coarse_f32_default() : f != 0;
   }
   // true if any level of this hierarchy streams complex<float> Galerkin matrices (drivers print it)
-  bool any_coarse_f32() { for (int i = 1; i < num_levels; i++) if (stencil_list[i] && stencil_list[i]->f32_matrices) return true; return false; }
-  bool any_coarse_f16() { for (int i = 1; i < num_levels; i++) if (stencil_list[i] && stencil_list[i]->f32_matrices && stencil_list[i]->f32_bits == 16) return true; return false; }
+  bool any_coarse_f32(int bits = 0) {   // bits = 16: ... in that width
+    for (int i = 1; i < num_levels; i++) {
+      if (!stencil_list[i]) continue;
+      const Stencil2D::NarrowCopies& storage = stencil_list[i]->narrow[Stencil2D::QMG_NARROW_STORAGE];
+      if (storage.on && (bits == 0 || storage.bits == bits)) return true;
+    }
+    return false;
+  }
+  bool any_coarse_f16() { return any_coarse_f32(16); }
   // drivers: QMG_COARSE_F32=0 / 1 and QMG_COARSE_BITS=64 / 32 / 16 (the latter wins)
   static void coarse_storage_from_env() {
     if (getenv("QMG_COARSE_F32")) coarse_f32_storage() = atoi(getenv("QMG_COARSE_F32")) != 0 ? 1 : 0;

@@ -8,6 +8,7 @@
 #define QMG_STENCIL2D_HPP
 
 #include <algorithm>
+#include <initializer_list>
 #include <iostream>
 #include <string>
 
@@ -91,30 +92,25 @@ struct Stencil2D {
   complex<double>* corner;
   bool generated;
   complex<double> shift, eo_shift, dof_shift;
-  // opt-in: complex<float> copies of clover / hopping that the ORIGINAL-operator applies stream instead of the fp64 arrays
-  bool f32_matrices;
-  int f32_bits;   // 32: clover32 / hopping32 hold complex<float>; 16: complex<half> (enable_f32_matrices(16))
-  // (the fp32 copies mirror the ORIGINAL arrays: while a variant -- dagger, rbjacobi, rbj-dagger -- is swapped into clover / hopping they do not apply)
-  void* clover32;
-  void* hopping32;
-  void* rbj_hopping32;   // the same narrow storage for the right-block-Jacobi hops and cinv (the Schur K-cycle's matrix stream), when that stencil is built
-  void* rbj_cinv32;
-
-  // fp32 shadow (qmg_dtype QMG_C32; not in the reference, which is fp64 only): complex<float> copies of the arrays a
-  // K-cycle level streams -- the ORIGINAL clover / hopping and, when built, the right-block-Jacobi hopping and cinv.
-  // The fp64 arrays stay the master copy; enable_f32_shadow() (re)creates the copies from their current contents.
-  struct F32Shadow {
-    void* clover; void* hopping; void* rbj_hopping; void* rbj_cinv; bool on;
-    void* dagger_clover; void* dagger_hopping;   // when the dagger stencil is built (CGNE smoothers of the fp32 K-cycle)
-    void* rbj_dagger_hopping;                    // when the right-block-Jacobi dagger stencil is built (CGNE smoothers / normal-equation solves on RIGHT_JACOBI levels)
-    // optional (nc = 2): complex<half> copies of the matrices the smoother / residual applies of the fp32 K-cycle stream
-    // (qmg_stencil_apply_h16: 112 B/site); cinv stays fp32 (it is applied once per cycle)
-    void* clover16; void* hopping16; void* rbj_hopping16; bool half_on;
-  } f32;
   // QMG_ARR_DAGGER: the dagger stencil (build_dagger_stencil) by name, without perform_swap_dagger -- the batch engine's CGNE smoothers; the caller passes
   // the conjugated shifts
   // QMG_ARR_RBJ_DAGGER: the hops of the right-block-Jacobi dagger stencil (build_rbj_dagger_stencil) by name; its clover is the identity (a unit shift)
   enum QMGArraySet { QMG_ARR_ORIGINAL = 0, QMG_ARR_RBJ_HOPPING = 1, QMG_ARR_RBJ_CINV = 2, QMG_ARR_DAGGER = 3, QMG_ARR_RBJ_DAGGER = 4 };
+  enum { QMG_ARR_SETS = 5 };
+  // a set has a clover and a hopping slot: cinv sits in the clover slot of RBJ_CINV, the rbj and rbj-dagger hops in the hopping slot of RBJ_HOPPING and
+  // RBJ_DAGGER (as in RouteState::clover_of / hopping_of)
+  enum NarrowSlot { QMG_SLOT_CLOVER = 0, QMG_SLOT_HOPPING = 1 };
+
+  // The narrow copies of the matrices (not in the reference, which is fp64 only): ONE table by use, array set and slot.  The fp64 arrays stay the master
+  // copy; the copies of a use are made from their contents in the unswapped state when the use is enabled (narrow_source, narrow_copy) and are stale once
+  // the matrices change: call the enable_* again.
+  //   STORAGE      under complex<double> vectors (enable_f32_matrices): the ORIGINAL pair, the rbj hops and cinv, all in `bits` 32 or 16
+  //   SHADOW       complex<float> copies for complex<float> vectors (enable_f32_shadow): every slot of every set that is built
+  //   SHADOW_HALF  complex<half> copies for complex<float> vectors (enable_f32_shadow(true)): the slots of has_half_shadow; the rest stays complex<float>
+  enum NarrowUse { QMG_NARROW_STORAGE = 0, QMG_NARROW_SHADOW = 1, QMG_NARROW_SHADOW_HALF = 2, QMG_NARROW_USES = 3 };
+  struct NarrowCopies { bool on; int bits; void* copy[QMG_ARR_SETS][2]; } narrow[QMG_NARROW_USES];   // bits per real number, 32 / 16; copy[QMGArraySet][NarrowSlot]
+  // the slots the smoother / residual applies of the fp32 K-cycle stream in 16 bits (cinv is applied once per cycle, the dagger sets serve CGNE only)
+  static bool has_half_shadow(QMGArraySet set, NarrowSlot slot) { return set == QMG_ARR_ORIGINAL || (set == QMG_ARR_RBJ_HOPPING && slot == QMG_SLOT_HOPPING); }
 
   // Operators whose stencil is a fixed spin pattern times the gauge links (Wilson2D) can be applied straight from the links
   // (qmg_wilson_apply_direct, csrc/qmg_wilson.hip: 96 B/site instead of 384, bit-identical to the stored stencil through the
@@ -189,24 +185,20 @@ struct Stencil2D {
   enum RouteStorage { QMG_MAT_C64 = 0, QMG_MAT_C32 = 1, QMG_MAT_C16 = 2 };   // complex<double>, <float>, <half> matrices (the values are qmg_stencil_apply_epi_t's mat32)
   struct RouteState {
     const void *clover, *hopping, *dagger_clover, *dagger_hopping, *rbjacobi_hopping, *rbjacobi_cinv, *rbj_dagger_hopping;
-    bool built_rbjacobi, swap_dagger, swap_rbjacobi, swap_rbj_dagger, generated, f32_matrices;
-    int f32_bits;
-    const void *clover32, *hopping32, *rbj_hopping32, *rbj_cinv32;
-    F32Shadow f32;
+    bool built_rbjacobi, swap_dagger, swap_rbjacobi, swap_rbj_dagger, generated;
+    NarrowCopies narrow[QMG_NARROW_USES];
     DirectLinks direct;
     int nc;
     bool slab_on;   // qmg::slab().on
-    // the arrays of a set, in fp64 and in the fp32 shadow
+    // the fp64 arrays of a set
     const void* rbjacobi_hopping_in_use() const { return swap_rbjacobi ? hopping : rbjacobi_hopping; }
     const void* clover_of(QMGArraySet set) const { return set == QMG_ARR_ORIGINAL ? clover : set == QMG_ARR_RBJ_CINV ? rbjacobi_cinv : set == QMG_ARR_DAGGER ? dagger_clover : 0; }
     const void* hopping_of(QMGArraySet set) const { return set == QMG_ARR_ORIGINAL ? hopping : set == QMG_ARR_RBJ_HOPPING ? rbjacobi_hopping_in_use() : set == QMG_ARR_DAGGER ? dagger_hopping : set == QMG_ARR_RBJ_DAGGER ? (swap_rbj_dagger ? hopping : rbj_dagger_hopping) : 0; }
-    const void* f32_clover_of(QMGArraySet set) const { return set == QMG_ARR_ORIGINAL ? f32.clover : set == QMG_ARR_RBJ_CINV ? f32.rbj_cinv : set == QMG_ARR_DAGGER ? f32.dagger_clover : 0; }
-    const void* f32_hopping_of(QMGArraySet set) const { return set == QMG_ARR_ORIGINAL ? f32.hopping : set == QMG_ARR_RBJ_HOPPING ? f32.rbj_hopping : set == QMG_ARR_DAGGER ? f32.dagger_hopping : set == QMG_ARR_RBJ_DAGGER ? f32.rbj_dagger_hopping : 0; }
   };
   RouteState route_state() const {
     const RouteState s = {clover, hopping, dagger_clover, dagger_hopping, rbjacobi_hopping, rbjacobi_cinv, rbj_dagger_hopping,
-                          built_rbjacobi, swap_dagger, swap_rbjacobi, swap_rbj_dagger, generated, f32_matrices, f32_bits,
-                          clover32, hopping32, rbj_hopping32, rbj_cinv32, f32, direct, lat->get_nc(), qmg::slab().on};
+                          built_rbjacobi, swap_dagger, swap_rbjacobi, swap_rbj_dagger, generated,
+                          {narrow[QMG_NARROW_STORAGE], narrow[QMG_NARROW_SHADOW], narrow[QMG_NARROW_SHADOW_HALF]}, direct, lat->get_nc(), qmg::slab().on};
     return s;
   }
   struct RouteRequest {
@@ -225,15 +217,16 @@ struct Stencil2D {
   static Route resolve_route(const RouteState& s, const RouteRequest& q) {
     Route r = {false, QMG_LINKS_NONE, 0, 0, 0, QMG_MAT_C64};
     const bool f = q.dtype == QMG_C32, epi = q.mode == QMG_ROUTE_EPILOGUE;
+    const NarrowCopies &storage = s.narrow[QMG_NARROW_STORAGE], &shadow = s.narrow[QMG_NARROW_SHADOW], &half_shadow = s.narrow[QMG_NARROW_SHADOW_HALF];
     // Refused before anything runs: an epilogue that is switched off or asked on a slab, and a complex<float> apply without the shadow on a slab (nothing
     // travels for it).  On a whole lattice, and with an epilogue, the same apply is refused only after the links attempt: complex<float> applies from the
     // links go on working after disable_f32_shadow(), which leaves gauge32 alone.  Both are the behaviour of old and stay.
-    if ((epi && (!q.epilogue_wanted || s.slab_on)) || (q.mode == QMG_ROUTE_SLAB && f && !s.f32.on)) { r.refused = true; return r; }
+    if ((epi && (!q.epilogue_wanted || s.slab_on)) || (q.mode == QMG_ROUTE_SLAB && f && !shadow.on)) { r.refused = true; return r; }
     const void* cl = q.by_set ? s.clover_of(q.set) : q.cl;
     const void* ho = q.by_set ? s.hopping_of(q.set) : q.ho;
     const bool variant_in = s.swap_dagger || s.swap_rbjacobi || s.swap_rbj_dagger;
     if (s.direct.on && (!f || s.direct.gauge32)) {
-      if (s.generated && cl != 0 && ho != 0 && cl == s.clover && ho == s.hopping && !variant_in && !s.f32_matrices) {
+      if (s.generated && cl != 0 && ho != 0 && cl == s.clover && ho == s.hopping && !variant_in && !storage.on) {
         // the ORIGINAL operator (the link copy stands in for the stored arrays only while those ARE the filled operator: clear_stencils / prune_stencils
         // drop it, and a null pair -- 0 == 0 after a prune -- never qualifies); slabs and epilogues are served from Wilson links only
         if (s.direct.kind == QMG_DIRECT_WILSON) r.links = QMG_LINKS_WILSON;
@@ -244,23 +237,26 @@ struct Stencil2D {
       }
       if (r.links != QMG_LINKS_NONE) r.gauge = f ? s.direct.gauge32 : (const void*)s.direct.gauge;
     }
-    if (f) {   // the fp32 shadow of the set, or its 16-bit copies (only ORIGINAL has a clover16)
-      const bool half = s.f32.half_on && (q.set == QMG_ARR_ORIGINAL || q.set == QMG_ARR_RBJ_HOPPING);
-      if (!s.f32.on || (epi && half && s.nc == 2)) { r.refused = true; return r; }   // (kernel S, the 16-bit nc = 2 kernel, has no epilogue)
-      r.clover = half ? (q.set == QMG_ARR_ORIGINAL ? s.f32.clover16 : 0) : s.f32_clover_of(q.set);
-      r.hopping = half ? (q.set == QMG_ARR_ORIGINAL ? s.f32.hopping16 : s.f32.rbj_hopping16) : s.f32_hopping_of(q.set);
+    if (f) {   // the fp32 shadow of the set, or the 16-bit copies of the set's slots that have them (of RBJ_HOPPING the hops only)
+      const bool half = half_shadow.on && has_half_shadow(q.set, QMG_SLOT_HOPPING);
+      if (!shadow.on || (epi && half && s.nc == 2)) { r.refused = true; return r; }   // (kernel S, the 16-bit nc = 2 kernel, has no epilogue)
+      r.clover = !half ? shadow.copy[q.set][QMG_SLOT_CLOVER] : has_half_shadow(q.set, QMG_SLOT_CLOVER) ? half_shadow.copy[q.set][QMG_SLOT_CLOVER] : 0;
+      r.hopping = (half ? half_shadow : shadow).copy[q.set][QMG_SLOT_HOPPING];
       r.storage = half ? QMG_MAT_C16 : QMG_MAT_C32;
       return r;
     }
     r.clover = cl; r.hopping = ho;
-    if (!s.f32_matrices || variant_in) return r;
-    // fp32 / 16-bit STORAGE under fp64 vectors (enable_f32_matrices): the narrow copy that serves (cl, ho), if any -- ORIGINAL, right-block-Jacobi hops, cinv.
-    // (No dagger set matches: its arrays are none of these three.)
-    if (cl == s.clover && ho == s.hopping && (s.clover32 || s.hopping32)) { r.clover = s.clover32; r.hopping = s.hopping32; }
-    else if (cl == 0 && ho != 0 && ho == s.rbjacobi_hopping && s.rbj_hopping32) r.hopping = s.rbj_hopping32;
-    else if (ho == 0 && cl != 0 && cl == s.rbjacobi_cinv && s.rbj_cinv32) r.clover = s.rbj_cinv32;
+    if (!storage.on || variant_in) return r;
+    // fp32 / 16-bit STORAGE under fp64 vectors (enable_f32_matrices): the set whose fp64 arrays (cl, ho) are -- the ORIGINAL pair, the right-block-Jacobi hops
+    // alone or cinv alone -- and its narrow copy, if there is one.  (No dagger set matches: its arrays are none of these three.)
+    QMGArraySet set;
+    if (cl == s.clover && ho == s.hopping) set = QMG_ARR_ORIGINAL;
+    else if (cl == 0 && ho != 0 && ho == s.rbjacobi_hopping) set = QMG_ARR_RBJ_HOPPING;
+    else if (ho == 0 && cl != 0 && cl == s.rbjacobi_cinv) set = QMG_ARR_RBJ_CINV;
     else return r;
-    r.storage = s.f32_bits == 16 ? QMG_MAT_C16 : QMG_MAT_C32;
+    if (!storage.copy[set][QMG_SLOT_CLOVER] && !storage.copy[set][QMG_SLOT_HOPPING]) return r;
+    r.clover = storage.copy[set][QMG_SLOT_CLOVER]; r.hopping = storage.copy[set][QMG_SLOT_HOPPING];
+    r.storage = storage.bits == 16 ? QMG_MAT_C16 : QMG_MAT_C32;
     return r;
   }
 
@@ -340,13 +336,11 @@ struct Stencil2D {
     priv_cvector = 0;
     extra_cvector = allocate_vector<complex<double>>(lat->get_size_cv_l());
     eo_cvector = 0;
-    f32_matrices = false; f32_bits = 32; clover32 = hopping32 = 0; rbj_hopping32 = rbj_cinv32 = 0;
-    f32.clover = f32.hopping = f32.rbj_hopping = f32.rbj_cinv = 0; f32.on = false;
-    f32.dagger_clover = f32.dagger_hopping = f32.rbj_dagger_hopping = 0;
+    for (NarrowCopies& t : narrow) { t = NarrowCopies(); t.bits = 32; }
+    narrow[QMG_NARROW_SHADOW_HALF].bits = 16;
     direct.gauge = 0; direct.gauge32 = 0; direct.w = 1.0; direct.on = false; direct.rbj_scale = 0.0;
     direct.kind = QMG_DIRECT_WILSON; direct.Ls = 0; direct.m = 0.0;
     slab_halo_lo = slab_halo_hi = 0;
-    f32.clover16 = f32.hopping16 = f32.rbj_hopping16 = 0; f32.half_on = false;
     built_dagger = false; dagger_clover = dagger_hopping = dagger_twolink = dagger_corner = 0;
     built_rbjacobi = false; rbjacobi_clover = rbjacobi_hopping = rbjacobi_twolink = rbjacobi_corner = rbjacobi_cinv = 0;
     built_rbj_dagger = false; rbj_dagger_clover = rbj_dagger_hopping = rbj_dagger_twolink = rbj_dagger_corner = rbj_dagger_cinv = 0;
@@ -360,47 +354,79 @@ struct Stencil2D {
                                &rbjacobi_clover, &rbjacobi_hopping, &rbjacobi_twolink, &rbjacobi_corner, &rbjacobi_cinv,
                                &rbj_dagger_clover, &rbj_dagger_hopping, &rbj_dagger_twolink, &rbj_dagger_corner, &rbj_dagger_cinv};
     for (auto p : all) if (*p != 0) deallocate_vector(p);
-    disable_f32_matrices();
-    disable_f32_shadow();
+    for (int use = 0; use < QMG_NARROW_USES; use++) release_narrow((NarrowUse)use);
     drop_direct_links();
     if (slab_halo_lo) deallocate_vector(&slab_halo_lo);
     if (slab_halo_hi) deallocate_vector(&slab_halo_hi);
     built_dagger = built_rbjacobi = built_rbj_dagger = generated = false;
   }
 
+  // ---- the narrow copies: one source, one copy, one release, one range check
+  // The fp64 array the copy of (set, slot) is made from, in the unswapped state, and its length; null: the operator has no such array or the variant it
+  // belongs to is not built.  (The only place that says which member, of which length, a slot of a set is.)
+  const complex<double>* narrow_source(QMGArraySet set, NarrowSlot slot, size_t* n) const {
+    const bool cl = slot == QMG_SLOT_CLOVER;
+    *n = (size_t)(cl ? lat->get_size_cm_l() : lat->get_size_hopping_l());
+    switch (set) {
+      case QMG_ARR_ORIGINAL: return cl ? clover : hopping;
+      case QMG_ARR_RBJ_HOPPING: return built_rbjacobi && !cl ? rbjacobi_hopping : 0;
+      case QMG_ARR_RBJ_CINV: return built_rbjacobi && cl ? rbjacobi_cinv : 0;
+      case QMG_ARR_DAGGER: return !built_dagger ? 0 : cl ? dagger_clover : dagger_hopping;
+      case QMG_ARR_RBJ_DAGGER: return built_rbj_dagger && !cl ? rbj_dagger_hopping : 0;
+    }
+    return 0;
+  }
+  // Makes the copy of (set, slot) in the width of the use, n * bits / 4 bytes (the only caller of the conversion entries; the entry is null on the way in).
+  // true: made, or there is nothing to copy; false: no memory, or the conversion failed and said so -- the entry is null again.
+  bool narrow_copy(NarrowUse use, QMGArraySet set, NarrowSlot slot) {
+    size_t n;
+    const complex<double>* src = narrow_source(set, slot, &n);
+    if (src == 0) return true;
+    const int bits = narrow[use].bits;
+    void*& dst = narrow[use].copy[set][slot];
+    if (qmg_malloc(&dst, n * bits / 4) != QMG_SUCCESS) { dst = 0; return false; }
+    const bool good = bits == 16 ? qmg::ok(qmg_convert_to_c16(dst, src, QMG_C64, n, qmg::current_stream()), "qmg_convert_to_c16")
+                                 : qmg::ok(qmg_convert(dst, QMG_C32, src, QMG_C64, n, qmg::current_stream()), "qmg_convert");
+    if (!good) drop_narrow(use, set, slot);
+    return good;
+  }
+  void drop_narrow(NarrowUse use, QMGArraySet set, NarrowSlot slot) { void*& p = narrow[use].copy[set][slot]; if (p) { qmg_free(p); p = 0; } }
+  void release_narrow(NarrowUse use) {   // every copy of a use freed, the use off
+    for (int set = 0; set < QMG_ARR_SETS; set++) for (int slot = 0; slot < 2; slot++) drop_narrow(use, (QMGArraySet)set, (NarrowSlot)slot);
+    narrow[use].on = false;
+  }
+  // true unless every entry of the listed arrays is inside half range, |x| < 6e4; largest: the largest entry found
+  struct SetSlot { QMGArraySet set; NarrowSlot slot; };
+  bool out_of_half_range(std::initializer_list<SetSlot> arrays, double* largest = 0) const {
+    double big = 0.0;
+    for (const SetSlot& a : arrays) {
+      size_t n;
+      const complex<double>* src = narrow_source(a.set, a.slot, &n);
+      const double v = src ? norminf(src, n) : 0.0;
+      if (big < v || v != v) big = v;   // (a NaN stays: nothing is above it)
+    }
+    if (largest) *largest = big;
+    return !(big < 6.0e4);   // (a NaN is out of range)
+  }
+
+  // fp32 shadow (qmg_dtype QMG_C32): complex<float> copies of the arrays a K-cycle level streams -- the ORIGINAL pair and, when built, the right-block-Jacobi
+  // hops and cinv, the dagger stencil and the rbj-dagger hops (CGNE smoothers, normal-equation solves).  (Re)creates them from the current contents of the
+  // fp64 arrays; everything is released on any failure.  half_matrices: complex<half> copies of the slots of has_half_shadow as well -- nc = 2 (kernel S,
+  // qmg_stencil_apply_h16: 112 B/site) or a multiple of 4 beyond 4 (kernels B32 / C, qmg_stencil_apply_mat16_t) with every entry inside half range.
   bool enable_f32_shadow(bool half_matrices = false) {
     disable_f32_shadow();
-    // 16-bit matrices: nc = 2 (kernel S, qmg_stencil_apply_h16) or a multiple of 4 beyond 4 (kernels B32 / C, qmg_stencil_apply_mat16_t) with every entry
-    // inside half range
-    if (half_matrices) {
-      const int nc_ = lat->get_nc();
-      if (!(nc_ == 2 || (nc_ > 4 && (nc_ & 3) == 0))) half_matrices = false;
-      else if (nc_ != 2) {
-        double big = std::max(clover ? norminf(clover, (size_t)lat->get_size_cm_l()) : 0.0, hopping ? norminf(hopping, (size_t)lat->get_size_hopping_l()) : 0.0);
-        if (built_rbjacobi && rbjacobi_hopping) big = std::max(big, norminf(rbjacobi_hopping, (size_t)lat->get_size_hopping_l()));
-        if (!(big < 6.0e4)) half_matrices = false;
-      }
-    }
-    auto dup = [&](void** dst, const complex<double>* src, long n) -> bool {
-      if (src == 0) return true;
-      if (qmg_malloc(dst, (size_t)n * 8) != QMG_SUCCESS) { *dst = 0; return false; }
-      return qmg::ok(qmg_convert(*dst, QMG_C32, src, QMG_C64, (size_t)n, qmg::current_stream()), "qmg_convert");
-    };
+    const int nc_ = lat->get_nc();
+    if (half_matrices && !(nc_ == 2 || (nc_ > 4 && (nc_ & 3) == 0))) half_matrices = false;
+    if (half_matrices && nc_ != 2 &&
+        out_of_half_range({{QMG_ARR_ORIGINAL, QMG_SLOT_CLOVER}, {QMG_ARR_ORIGINAL, QMG_SLOT_HOPPING}, {QMG_ARR_RBJ_HOPPING, QMG_SLOT_HOPPING}})) half_matrices = false;
     // (a variant swapped in by perform_swap_* would be copied under the wrong name: shadows are taken in the unswapped state)
     if (swap_dagger || swap_rbjacobi || swap_rbj_dagger) { std::cout << "[QMG-ERROR]: enable_f32_shadow called while a stencil variant is swapped in.\n"; return false; }
-    bool good = dup(&f32.clover, clover, lat->get_size_cm_l()) && dup(&f32.hopping, hopping, lat->get_size_hopping_l());
-    if (good && built_rbjacobi) good = dup(&f32.rbj_hopping, rbjacobi_hopping, lat->get_size_hopping_l()) && dup(&f32.rbj_cinv, rbjacobi_cinv, lat->get_size_cm_l());
-    if (good && built_dagger) good = dup(&f32.dagger_clover, dagger_clover, lat->get_size_cm_l()) && dup(&f32.dagger_hopping, dagger_hopping, lat->get_size_hopping_l());
-    if (good && built_rbj_dagger) good = dup(&f32.rbj_dagger_hopping, rbj_dagger_hopping, lat->get_size_hopping_l());
+    bool good = true;   // set by set, clover before hopping
+    for (int set = 0; set < QMG_ARR_SETS; set++) for (int slot = 0; slot < 2; slot++) good = good && narrow_copy(QMG_NARROW_SHADOW, (QMGArraySet)set, (NarrowSlot)slot);
     if (good && half_matrices) {
-      auto dup16 = [&](void** dst, const complex<double>* src, long n) -> bool {
-        if (src == 0) return true;
-        if (qmg_malloc(dst, (size_t)n * 4) != QMG_SUCCESS) { *dst = 0; return false; }
-        return qmg::ok(qmg_convert_to_c16(*dst, src, QMG_C64, (size_t)n, qmg::current_stream()), "qmg_convert_to_c16");
-      };
-      good = dup16(&f32.clover16, clover, lat->get_size_cm_l()) && dup16(&f32.hopping16, hopping, lat->get_size_hopping_l());
-      if (good && built_rbjacobi) good = dup16(&f32.rbj_hopping16, rbjacobi_hopping, lat->get_size_hopping_l());
-      f32.half_on = good;
+      for (int set = 0; set < QMG_ARR_SETS; set++) for (int slot = 0; slot < 2; slot++)
+        if (has_half_shadow((QMGArraySet)set, (NarrowSlot)slot)) good = good && narrow_copy(QMG_NARROW_SHADOW_HALF, (QMGArraySet)set, (NarrowSlot)slot);
+      narrow[QMG_NARROW_SHADOW_HALF].on = good;
     }
     if (good && direct.on && !direct.gauge32) {   // the links of a direct-apply operator in fp32 as well (8 B/site; slab mode: of the whole lattice)
       const size_t n = (size_t)2 * lat->get_volume() * (qmg::slab().on ? qmg::slab().world : 1);
@@ -408,14 +434,10 @@ struct Stencil2D {
       else direct.gauge32 = 0;
     }
     if (!good) { disable_f32_shadow(); return false; }
-    f32.on = true;
+    narrow[QMG_NARROW_SHADOW].on = true;
     return true;
   }
-  void disable_f32_shadow() {
-    void** all[] = {&f32.clover, &f32.hopping, &f32.rbj_hopping, &f32.rbj_cinv, &f32.clover16, &f32.hopping16, &f32.rbj_hopping16, &f32.dagger_clover, &f32.dagger_hopping, &f32.rbj_dagger_hopping};
-    for (auto p : all) if (*p) { qmg_free(*p); *p = 0; }
-    f32.on = false; f32.half_on = false;
-  }
+  void disable_f32_shadow() { release_narrow(QMG_NARROW_SHADOW); release_narrow(QMG_NARROW_SHADOW_HALF); }   // (direct.gauge32 stays)
 
   // Opt-in storage format for operators that only PRECONDITION (a K-cycle inside a flexible fp64 outer solver): keep a
   // complex<float> copy of clover and hopping and let every ORIGINAL-operator apply stream that copy -- half the bytes of
@@ -424,63 +446,37 @@ struct Stencil2D {
   // Call again after changing the matrices.  Not available for nc = 1, 2, 4 (the fine operators).
   // bits = 16: the copy is complex<half> (a quarter of the fp64 stream; qmg_stencil_apply_mat16_t: nc a multiple of 4 and > 4) when every
   // entry is inside half range (|x| < 6e4; magnitudes below 6e-8 flush to zero) -- otherwise the complex<float> copy is kept, with a line
-  // saying so.  Measured on the n13 / n22 hierarchies: the same outer iteration counts as with fp32 storage.
+  // saying so.  Measured on the n13 / n22 hierarchies: the same outer iteration counts as with fp32 storage.  false: nothing is kept.
   bool enable_f32_matrices(int bits = 32) {
     const int nc = lat->get_nc();
     if (nc == 1 || nc == 2 || nc == 4) { std::cout << "[QMG-WARNING]: fp32 matrix storage is not available for nc = " << nc << ".\n"; return false; }
     disable_f32_matrices();
     if (bits == 16) {
-      const double big = std::max(clover ? norminf(clover, (size_t)lat->get_size_cm_l()) : 0.0, hopping ? norminf(hopping, (size_t)lat->get_size_hopping_l()) : 0.0);
-      if ((nc & 3) || !(big < 6.0e4)) {
+      double big;
+      const bool out = out_of_half_range({{QMG_ARR_ORIGINAL, QMG_SLOT_CLOVER}, {QMG_ARR_ORIGINAL, QMG_SLOT_HOPPING}}, &big);
+      if ((nc & 3) || out) {
         std::cout << "[QMG-INFO]: 16-bit matrix storage not used on this level (nc = " << nc << ", largest entry " << big << "): complex<float> instead.\n";
         bits = 32;
       }
     }
-    const size_t esz = (bits == 16) ? 4 : 8;
-    auto narrow = [&](void* dst, const complex<double>* src, size_t n) {
-      if (bits == 16) return qmg::ok(qmg_convert_to_c16(dst, src, QMG_C64, n, qmg::current_stream()), "qmg_convert_to_c16");
-      return qmg::ok(qmg_c64_to_c32(dst, src, n, qmg::current_stream()), "qmg_c64_to_c32");
-    };
-    if (clover != 0) {
-      if (qmg_malloc(&clover32, (size_t)lat->get_size_cm_l() * esz) != QMG_SUCCESS) { clover32 = 0; return false; }
-      narrow(clover32, clover, (size_t)lat->get_size_cm_l());
-    }
-    if (hopping != 0) {
-      if (qmg_malloc(&hopping32, (size_t)lat->get_size_hopping_l() * esz) != QMG_SUCCESS) { disable_f32_matrices(); return false; }
-      narrow(hopping32, hopping, (size_t)lat->get_size_hopping_l());
-    }
-    f32_matrices = true;
-    f32_bits = bits;
+    narrow[QMG_NARROW_STORAGE].bits = bits;
+    narrow[QMG_NARROW_STORAGE].on = narrow_copy(QMG_NARROW_STORAGE, QMG_ARR_ORIGINAL, QMG_SLOT_CLOVER) && narrow_copy(QMG_NARROW_STORAGE, QMG_ARR_ORIGINAL, QMG_SLOT_HOPPING);
+    if (!narrow[QMG_NARROW_STORAGE].on) { disable_f32_matrices(); return false; }
     narrow_rbjacobi_copies();
     return true;
   }
-  // narrow copies of the right-block-Jacobi hops and cinv (called by enable_f32_matrices and at the end of build_rbjacobi_stencil, whichever
-  // comes second); best effort: without them those applies stream the fp64 arrays
+  // the storage copies of the right-block-Jacobi hops and cinv, the Schur K-cycle's matrix stream (called by enable_f32_matrices and at the end of
+  // build_rbjacobi_stencil, whichever comes second); best effort: without them those applies stream the fp64 arrays
   void narrow_rbjacobi_copies() {
-    if (rbj_hopping32) { qmg_free(rbj_hopping32); rbj_hopping32 = 0; }
-    if (rbj_cinv32) { qmg_free(rbj_cinv32); rbj_cinv32 = 0; }
-    if (!f32_matrices || !built_rbjacobi || swap_rbjacobi || swap_dagger || swap_rbj_dagger) return;
-    int bits = f32_bits;
-    if (bits == 16) {
-      const double big = std::max(rbjacobi_hopping ? norminf(rbjacobi_hopping, (size_t)lat->get_size_hopping_l()) : 0.0, norminf(rbjacobi_cinv, (size_t)lat->get_size_cm_l()));
-      if (!(big < 6.0e4)) return;   // (one width for all copies of the level: keep fp64 for these)
-    }
-    const size_t esz = (bits == 16) ? 4 : 8;
-    auto narrow = [&](void** dst, const complex<double>* src, size_t n) {
-      if (qmg_malloc(dst, n * esz) != QMG_SUCCESS) { *dst = 0; return; }
-      if (bits == 16) qmg::ok(qmg_convert_to_c16(*dst, src, QMG_C64, n, qmg::current_stream()), "qmg_convert_to_c16");
-      else qmg::ok(qmg_c64_to_c32(*dst, src, n, qmg::current_stream()), "qmg_c64_to_c32");
-    };
-    if (rbjacobi_hopping) narrow(&rbj_hopping32, rbjacobi_hopping, (size_t)lat->get_size_hopping_l());
-    narrow(&rbj_cinv32, rbjacobi_cinv, (size_t)lat->get_size_cm_l());
+    drop_narrow(QMG_NARROW_STORAGE, QMG_ARR_RBJ_HOPPING, QMG_SLOT_HOPPING);
+    drop_narrow(QMG_NARROW_STORAGE, QMG_ARR_RBJ_CINV, QMG_SLOT_CLOVER);
+    if (!narrow[QMG_NARROW_STORAGE].on || !built_rbjacobi || swap_rbjacobi || swap_dagger || swap_rbj_dagger) return;
+    // (one width for all copies of the level: out of half range, these stay fp64)
+    if (narrow[QMG_NARROW_STORAGE].bits == 16 && out_of_half_range({{QMG_ARR_RBJ_HOPPING, QMG_SLOT_HOPPING}, {QMG_ARR_RBJ_CINV, QMG_SLOT_CLOVER}})) return;
+    narrow_copy(QMG_NARROW_STORAGE, QMG_ARR_RBJ_HOPPING, QMG_SLOT_HOPPING);
+    narrow_copy(QMG_NARROW_STORAGE, QMG_ARR_RBJ_CINV, QMG_SLOT_CLOVER);
   }
-  void disable_f32_matrices() {
-    if (clover32) { qmg_free(clover32); clover32 = 0; }
-    if (hopping32) { qmg_free(hopping32); hopping32 = 0; }
-    if (rbj_hopping32) { qmg_free(rbj_hopping32); rbj_hopping32 = 0; }
-    if (rbj_cinv32) { qmg_free(rbj_cinv32); rbj_cinv32 = 0; }
-    f32_matrices = false;
-  }
+  void disable_f32_matrices() { release_narrow(QMG_NARROW_STORAGE); }
 
   void clear_stencils() {   // stencil_2d.h:339-375
     if (clover != 0) zero_vector(clover, lat->get_size_cm_l());
@@ -649,7 +645,8 @@ struct Stencil2D {
   template <typename T>
   bool apply_M_dagger_overwrite_batch_t(complex<T>* lhs, complex<T>* rhs, int nrhs, size_t stride, unsigned mask) {
     if (!built_dagger || swap_dagger) { std::cout << "[QMG-WARNING]: Tried to call apply_M_dagger (batch), but the dagger stencil has not been allocated.\n"; return false; }
-    if (sizeof(T) == sizeof(float) && (!f32.on || (dagger_hopping != 0 && f32.dagger_hopping == 0))) {
+    const NarrowCopies& shadow = narrow[QMG_NARROW_SHADOW];
+    if (sizeof(T) == sizeof(float) && (!shadow.on || (dagger_hopping != 0 && shadow.copy[QMG_ARR_DAGGER][QMG_SLOT_HOPPING] == 0))) {
       std::cout << "[QMG-ERROR]: fp32 dagger apply without an fp32 shadow of the dagger stencil (build_dagger_stencil before enable_f32_shadow).\n";
       return false;
     }

@@ -25,26 +25,31 @@ static const char* fake_name(const void* p) {
 }
 
 // ---- states
+enum { STORAGE = S::QMG_NARROW_STORAGE, SHADOW = S::QMG_NARROW_SHADOW, HALF = S::QMG_NARROW_SHADOW_HALF };
+static void*& clover_copy(S::RouteState& s, int use, S::QMGArraySet set = S::QMG_ARR_ORIGINAL) { return s.narrow[use].copy[set][S::QMG_SLOT_CLOVER]; }
+static void*& hopping_copy(S::RouteState& s, int use, S::QMGArraySet set = S::QMG_ARR_ORIGINAL) { return s.narrow[use].copy[set][S::QMG_SLOT_HOPPING]; }
 static S::RouteState fine() {   // a Wilson operator (nc = 2) filled from its links, every variant built, nothing swapped in, no narrow copy of any kind
   S::RouteState s = S::RouteState();
   s.clover = P(CLOVER); s.hopping = P(HOPPING); s.dagger_clover = P(DAG_CL); s.dagger_hopping = P(DAG_HO);
   s.rbjacobi_hopping = P(RBJ_HO); s.rbjacobi_cinv = P(CINV); s.rbj_dagger_hopping = P(RBJD_HO);
-  s.built_rbjacobi = true; s.generated = true; s.f32_bits = 32; s.nc = 2;
+  s.built_rbjacobi = true; s.generated = true; s.narrow[STORAGE].bits = 32; s.nc = 2;
   s.direct.on = true; s.direct.gauge = (complex<double>*)P(GAUGE); s.direct.kind = S::QMG_DIRECT_WILSON; s.direct.w = 1.0; s.direct.rbj_scale = 0.25;
   return s;
 }
 static S::RouteState dwf() { S::RouteState s = fine(); s.nc = 8; s.direct.kind = S::QMG_DIRECT_DWF; s.direct.Ls = 4; s.direct.rbj_scale = 0.0; return s; }
 static S::RouteState coarse() { S::RouteState s = fine(); s.nc = 8; s.direct.on = false; s.direct.gauge = 0; s.direct.rbj_scale = 0.0; return s; }   // a Galerkin operator: no links
 static S::RouteState shadow(S::RouteState s, bool half = false) {   // enable_f32_shadow(half) on a direct-apply operator: gauge32 comes with it
-  s.f32.on = true; s.f32.clover = P(F_CL); s.f32.hopping = P(F_HO); s.f32.rbj_hopping = P(F_RBJ_HO); s.f32.rbj_cinv = P(F_CINV);
-  s.f32.dagger_clover = P(F_DAG_CL); s.f32.dagger_hopping = P(F_DAG_HO); s.f32.rbj_dagger_hopping = P(F_RBJD_HO);
-  if (half) { s.f32.half_on = true; s.f32.clover16 = P(H_CL); s.f32.hopping16 = P(H_HO); s.f32.rbj_hopping16 = P(H_RBJ_HO); }
+  s.narrow[SHADOW].on = true; clover_copy(s, SHADOW) = P(F_CL); hopping_copy(s, SHADOW) = P(F_HO);
+  hopping_copy(s, SHADOW, S::QMG_ARR_RBJ_HOPPING) = P(F_RBJ_HO); clover_copy(s, SHADOW, S::QMG_ARR_RBJ_CINV) = P(F_CINV);
+  clover_copy(s, SHADOW, S::QMG_ARR_DAGGER) = P(F_DAG_CL); hopping_copy(s, SHADOW, S::QMG_ARR_DAGGER) = P(F_DAG_HO); hopping_copy(s, SHADOW, S::QMG_ARR_RBJ_DAGGER) = P(F_RBJD_HO);
+  if (half) { s.narrow[HALF].on = true; clover_copy(s, HALF) = P(H_CL); hopping_copy(s, HALF) = P(H_HO); hopping_copy(s, HALF, S::QMG_ARR_RBJ_HOPPING) = P(H_RBJ_HO); }
   if (s.direct.on) s.direct.gauge32 = P(GAUGE32);
   return s;
 }
-static S::RouteState unshadowed(S::RouteState s) { s.f32 = S::F32Shadow(); return s; }   // disable_f32_shadow(): gauge32 survives it
+static S::RouteState unshadowed(S::RouteState s) { s.narrow[SHADOW] = s.narrow[HALF] = S::NarrowCopies(); return s; }   // disable_f32_shadow(): gauge32 survives it
 static S::RouteState narrow(S::RouteState s, int bits) {   // enable_f32_matrices(bits)
-  s.f32_matrices = true; s.f32_bits = bits; s.clover32 = P(CL32); s.hopping32 = P(HO32); s.rbj_hopping32 = P(RBJ_HO32); s.rbj_cinv32 = P(CINV32);
+  s.narrow[STORAGE].on = true; s.narrow[STORAGE].bits = bits; clover_copy(s, STORAGE) = P(CL32); hopping_copy(s, STORAGE) = P(HO32);
+  hopping_copy(s, STORAGE, S::QMG_ARR_RBJ_HOPPING) = P(RBJ_HO32); clover_copy(s, STORAGE, S::QMG_ARR_RBJ_CINV) = P(CINV32);
   return s;
 }
 static S::RouteState swapped_dagger(S::RouteState s) { s.swap_dagger = true; std::swap(s.clover, s.dagger_clover); std::swap(s.hopping, s.dagger_hopping); return s; }
@@ -57,8 +62,8 @@ static S::RouteState rbj_scale(S::RouteState s, double v) { s.direct.rbj_scale =
 static S::RouteState no_gauge32(S::RouteState s) { s.direct.gauge32 = 0; return s; }
 static S::RouteState links_off(S::RouteState s) { s.direct.on = false; return s; }
 static S::RouteState pruned(S::RouteState s, bool clover_too) { s.hopping = 0; if (clover_too) s.clover = 0; return s; }   // (as if the link copy had survived the prune)
-static S::RouteState no_clover(S::RouteState s) { s.clover = 0; s.dagger_clover = 0; s.clover32 = 0; return s; }
-static S::RouteState no_rbj_copies(S::RouteState s) { s.rbj_hopping32 = 0; s.rbj_cinv32 = 0; return s; }
+static S::RouteState no_clover(S::RouteState s) { s.clover = 0; s.dagger_clover = 0; clover_copy(s, STORAGE) = 0; return s; }
+static S::RouteState no_rbj_copies(S::RouteState s) { hopping_copy(s, STORAGE, S::QMG_ARR_RBJ_HOPPING) = 0; clover_copy(s, STORAGE, S::QMG_ARR_RBJ_CINV) = 0; return s; }
 static S::RouteState on_slab(S::RouteState s) { s.slab_on = true; return s; }
 
 // ---- requests

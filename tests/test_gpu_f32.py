@@ -356,3 +356,29 @@ def test_kcycle_with_16_bit_fine_matrices_still_reaches_fp64_tolerance(golden_di
         its[tag] = [int(r[1]) for r in rows]
     for tag in ("f16", "f16c", "f16fc"):
         assert all(b <= a + max(3, a // 8) for a, b in zip(its["f32"], its[tag])), its
+
+
+def test_the_two_complex_double_to_float_entries_give_the_same_bits():
+    """qmg_c64_to_c32 and qmg_convert(QMG_C32 <- QMG_C64) are two kernels of csrc/qmg_fill.hip; the facade makes every complex<float> copy of a
+    matrix (Stencil2D::narrow_copy) with the second.  Both are to round the same way: one array of 4096 complex numbers with the hard cases of
+    the rounding through both, the results compared as raw bytes."""
+    rng = np.random.default_rng(4096)
+    f = rng.standard_normal(2000).astype(np.float32) * np.float32(2.0) ** rng.integers(-120, 120, 2000).astype(np.float32)
+    ties = (f.astype(np.float64) + np.nextafter(f, np.float32(np.inf)).astype(np.float64)) / 2                      # exactly between two floats: to even
+    fmax, tiny = float(np.finfo(np.float32).max), 2.0 ** -149
+    special = np.array([1 + 2.0 ** -24, 1 + 3 * 2.0 ** -24, np.nextafter(1 + 2.0 ** -24, 2), np.nextafter(1 + 2.0 ** -24, 0),            # ties and their neighbours
+                        1e39, -1e39, 1e308, fmax, fmax + 2.0 ** 103, np.nextafter(fmax + 2.0 ** 103, 0), -(fmax + 2.0 ** 103),           # beyond float range, and the threshold
+                        1e-40, -1e-40, tiny, tiny / 2, np.nextafter(tiny / 2, 1), 1.5 * tiny, 2.0 ** -126, np.nextafter(2.0 ** -126, 0),  # float subnormals and what flushes
+                        5e-324, -5e-324, 2.2250738585072014e-308, 0.0, -0.0, np.inf, -np.inf, np.nan])
+    flat = np.concatenate([special, ties, -ties, ties * (1 + 2.0 ** -52), rng.standard_normal(8192)])[:8192]
+    assert flat.size == 8192 and np.isnan(flat).sum() == 1 and np.isinf(flat).sum() == 2
+    src = qmg.DeviceArray.from_host(np.ascontiguousarray(flat).view(np.complex128))
+    a, b = qmg.DeviceArray(4096, np.complex64), qmg.DeviceArray(4096, np.complex64)
+    qmg.c64_to_c32(a, src, 4096)
+    qmg.convert(b, qmg.C32, src, qmg.C64, 4096)
+    qmg.sync()
+    ha, hb = a.to_host().view(np.uint32), b.to_host().view(np.uint32)
+    differ = np.nonzero(ha != hb)[0]
+    assert differ.size == 0, [(float(flat[i]), hex(ha[i]), hex(hb[i])) for i in differ[:8]]
+    got = ha.view(np.float32)
+    assert np.isnan(got[26]) and got[24] == np.inf and got[25] == -np.inf and got[4] == np.inf and got[0] == 1.0        # the cases did reach the kernels

@@ -72,7 +72,7 @@ CASES = [
     ("multishift_parity", "multishift_parity", ["32", gauge(32), "TMP", "staggered", "0.04,0.06,0.08,0.1"], {}, 8, 300),
     # the gauged Laplace operator: the run that prints the [BATCH] / [BATCH0] rows of three systems by four shifts, and one refused non-zero guess
     ("multishift_parity_laplace", "multishift_parity", ["32", gauge(32), "TMP", "laplace", "0.001,0.01,0.1,1.0"], {}, 32, 300),
-    ("facade_selftest", "facade_selftest", [gauge(32)], {}, 18, 150),
+    ("facade_selftest", "facade_selftest", [gauge(32)], {}, 86, 150),
     ("dwf_selftest", "dwf_selftest", ["8", "6", "0.05", "7"], {}, 8, 300),
     ("dwf_eo_selftest", "dwf_eo_selftest", ["8", "6", "0.05", "7"], {}, 9, 300),
     ("dwf_measure", "dwf_measure", ["8", "CFG8", "0.05", "4", "-1", "1e-12"], {}, 10, 300),
