@@ -770,6 +770,39 @@ int qmg_dwf_schur_apply(int dtype, const qmg_stencil_desc* d, const void* gauge,
  * QMG_ERR_INVALID: plan_out missing or plan_len below 8. */
 int qmg_dwf_eo_plan(int dtype, int Lx, int Ly, int Ls, int kernel, unsigned pieces, int n_active, int inplace, int* plan_out, int plan_len);
 
+/* ---------------- the Moebius domain-wall operator, from the links (csrc/qmg_mobius.hip) ----------------
+ * The layout of the Shamir operator: nc = 2 Ls, c = 2 s + sigma, Ls = 2 .. 32.  With L the fifth-dimension hop
+ *   (L psi)(s, 0) = psi(s-1, 0) (s >= 1),  (L psi)(0, 0) = -m psi(Ls-1, 0);   (L psi)(s, 1) = psi(s+1, 1) (s <= Ls-2),  (L psi)(Ls-1, 1) = -m psi(0, 1)
+ * and H the hopping blocks of qmg_wilson_fill on every slice, d_w = 2 w + M5:
+ *   D = (d_w + H) (b5 + c5 L) + (1 - L) = A + H B,   A = alpha + kappa L,  alpha = b5 d_w + 1,  kappa = c5 d_w - 1,   B = b5 + c5 L.
+ * b5 = 1, c5 = 0 and w = 1 is the Shamir operator with shift = M5.  M5 is an argument here (B multiplies it); the three shifts of a descriptor
+ * keep the stencil's meaning and are added to the diagonal of D afterwards (conjugated for D^dagger).
+ * qmg_mobius_fill writes the stored form in fp64, zeros included: clover = A, hopping = H B (no longer diagonal in s); every entry is its
+ * exact value rounded once (formed in double-double). */
+int qmg_mobius_fill(void* clover, void* hopping, const void* gauge, int Lx, int Ly, int Ls, double mass_re, double mass_im, double wilson_coeff, double M5,
+                    double b5, double c5, void* stream);
+/* lhs (+)= op(D) rhs (+ shifts) without stored matrices: op 0 is D (the hop source b5 psi + c5 L psi is formed on the load: the lane reads the two
+ * fifth-dimension halves of each neighbour next to its chunk, from the cache lines the wavefront has just asked for), op 1 is D^dagger =
+ * Gamma5 (A' + B' H) Gamma5 with conj(m) in A', B' (the hop sum of a slice is exchanged along s in LDS; Gamma5 is a slice index and a sign on the
+ * load and on the store).  64 Ls + 32 B/site in fp64.  Served: the full operator on both parities -- clover + every hop of both, the shift
+ * pieces and QMG_P_ZERO_* optional per parity; every other piece set QMG_ERR_UNSUPPORTED (the stored stencil serves it).  QMG_ERR_INVALID,
+ * before anything is launched: what qmg_dwf_apply_direct refuses; op outside 0 / 1; lhs == rhs; a mass, wilson_coeff, M5, b5 or c5 that is
+ * not finite.  mask, batches and the stream as in qmg_dwf_apply_direct. */
+int qmg_mobius_apply_direct(int dtype, const qmg_stencil_desc* d, const void* gauge, int Ls, double mass_re, double mass_im, double wilson_coeff, double M5,
+                            double b5, double c5, int op, void* lhs, const void* rhs, unsigned pieces, int nrhs, size_t vec_stride, unsigned mask,
+                            void* stream);
+/* What qmg_mobius_apply_direct launches: the answer of the one host function it switches on.  Host only, no HIP call.  Writes 8 ints in the
+ * layout of qmg_dwf_eo_plan and -1 into the rest of plan_out:
+ *   family  0 unsupported, 1 k_mobius_load (op 0), 2 success with nothing launched, 3 invalid, 4 k_mobius_result (op 1)
+ *   lps     lanes per site: Ls
+ *   block   threads per block: 256 for op 0, Ls floor(256 / Ls) for op 1 (whole sites: the exchange is in LDS)
+ *   gx, gy  gx blocks cover the Ls Lx/2 lanes of a half row, gy = min(2 Ly, 65535) blocks walk the (parity, y) rows
+ *   flags   qmg_dwf_plan's: 1 both parities overwritten, 2 more than one system, 4 complex<float>
+ *   lds     bytes of LDS per block: 0 for op 0, two buffers of one chunk per lane for op 1
+ *   nk      the systems served
+ * QMG_ERR_INVALID: plan_out missing or plan_len below 8. */
+int qmg_mobius_plan(int dtype, int Lx, int Ly, int Ls, int op, unsigned pieces, int n_active, int inplace, int* plan_out, int plan_len);
+
 /* ---------------- domain-wall measurements: wall source, wall / midpoint projection, slice norms (csrc/qmg_dwf_meas.hip) ----------------
  * A 5D vector has nc = 2 Ls components per site (c = 2 s + sigma), a 4D one nc = 2 (sigma); sigma = 0 is the P_+ component (the one that crosses
  * the wall as out(0, 0) += m psi(Ls-1, 0)), sigma = 1 P_-.  Whole lattice only.  Common to the three entries: dtype QMG_C64 / QMG_C32, Ls in

@@ -60,6 +60,7 @@ ABI_SYMBOLS = [
     "qmg_dwf_fill", "qmg_dwf_apply_direct", "qmg_dwf_plan", "qmg_batch_plan", "qmg_wilson_plan",
     "qmg_dwf_inv5", "qmg_dwf_hops_inv5", "qmg_dwf_schur_apply", "qmg_dwf_eo_plan",
     "qmg_dwf_wall_source", "qmg_dwf_wall_project", "qmg_dwf_slice_norms", "qmg_dwf_meas_plan",
+    "qmg_mobius_fill", "qmg_mobius_apply_direct", "qmg_mobius_plan",
     "qmg_setup_plan",
     "qmg_noise_z4", "qmg_noise_dilute_batch", "qmg_loops_timeslice_batch", "qmg_singlet_plan",
 ]
@@ -924,6 +925,38 @@ def dwf_eo_plan(dtype, dims, Ls, kernel, pieces, n_active=1, inplace=False):
     """What the even-odd entries launch (qmg_dwf_eo_plan; host only): (family, lps, block, gx, gy, flags, lds, nk)."""
     out = (C.c_int * DWF_EO_PLAN_INTS)()
     check(lib().qmg_dwf_eo_plan(dtype, dims[0], dims[1], Ls, kernel, C.c_uint(pieces), n_active, int(inplace), out, DWF_EO_PLAN_INTS), "qmg_dwf_eo_plan")
+    return tuple(out)
+
+
+# ---- the Moebius domain-wall operator from the links (csrc/qmg_mobius.hip)
+# the `op` argument and the families of qmg_mobius_plan (include/qmg_hip.h)
+MOP_D, MOP_DAGGER = 0, 1
+MF_UNSUPPORTED, MF_LOAD, MF_NOTHING, MF_INVALID, MF_RESULT = range(5)
+MOBIUS_PLAN_INTS = 8
+
+
+def mobius_fill(clover, hopping, gauge, Lx, Ly, Ls, mass=0.0, w=1.0, M5=-1.0, b5=1.0, c5=0.0, stream=None):
+    """The stored nc = 2 Ls fields of the Moebius operator D = A + H B (qmg_mobius_fill): clover = A, hopping = H B."""
+    mass = complex(mass)
+    check(lib().qmg_mobius_fill(_vp(clover), _vp(hopping), _vp(gauge), Lx, Ly, Ls, C.c_double(mass.real), C.c_double(mass.imag), C.c_double(w), C.c_double(M5),
+                                C.c_double(b5), C.c_double(c5), C.c_void_p(stream)), "qmg_mobius_fill")
+
+
+def mobius_apply_direct_status(dtype, desc, gauge, Ls, mass, lhs, rhs, pieces, w=1.0, M5=-1.0, b5=1.0, c5=0.0, op=0, nrhs=1, vec_stride=0, mask=1, stream=None):
+    """qmg_mobius_apply_direct's status, unchecked: lhs (+)= D rhs (op 0) or D^dagger rhs (op 1) from the links."""
+    mass = complex(mass)
+    return lib().qmg_mobius_apply_direct(dtype, C.byref(desc), _vp(gauge), Ls, C.c_double(mass.real), C.c_double(mass.imag), C.c_double(w), C.c_double(M5),
+                                         C.c_double(b5), C.c_double(c5), int(op), _vp(lhs), _vp(rhs), C.c_uint(pieces), nrhs, C.c_size_t(vec_stride), C.c_uint(mask),
+                                         C.c_void_p(stream))
+
+
+mobius_apply_direct = _checked(mobius_apply_direct_status, "qmg_mobius_apply_direct")
+
+
+def mobius_plan(dtype, dims, Ls, op, pieces, n_active=1, inplace=False):
+    """What qmg_mobius_apply_direct launches (qmg_mobius_plan; host only): (family, lps, block, gx, gy, flags, lds, nk)."""
+    out = (C.c_int * MOBIUS_PLAN_INTS)()
+    check(lib().qmg_mobius_plan(dtype, dims[0], dims[1], Ls, int(op), C.c_uint(pieces), n_active, int(inplace), out, MOBIUS_PLAN_INTS), "qmg_mobius_plan")
     return tuple(out)
 
 

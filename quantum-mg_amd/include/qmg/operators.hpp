@@ -1,6 +1,7 @@
 // operators.hpp -- the concrete stencils of the reference on device arrays:
 //   Wilson2D (operators/wilson.h), Staggered2D (operators/staggered.h), GaugedLaplace2D
 //   (operators/gaugedlaplace.h), FreeLaplace2D (tests/n02_free_laplace_test/free_laplace.h), DwfBase / Dwf2D<Ls> / createDwfLs (operators/dwf.h).
+//   Not in the reference: MobiusBase / Mobius2D<Ls> / createMobiusLs, the Moebius domain-wall operator on the layout of Dwf2D.
 // CoarseOperator2D lives in coarse.hpp (it needs TransferMG).
 #ifndef QMG_OPERATORS_HPP
 #define QMG_OPERATORS_HPP
@@ -263,6 +264,126 @@ inline inversion_info minv_dwf_eo_cg(complex<double>* x, complex<double>* b, int
   const inversion_info info = minv_vector_cg(x, rhs, (int)half, max_iter, eps, apply_dwf_schur5_Mdagger_M, (void*)dwf, verb);
   dwf->reconstruct_M_schur5(x, x, b);
   deallocate_vector(&b_r); deallocate_vector(&rhs);
+  return info;
+}
+
+// ---------------- Moebius domain wall (nc = 2 Ls, the layout of Dwf2D) ----------------
+// D = D_W (b5 + c5 L) + (1 - L) = A + H B with D_W = 2 w + M5 + H (include/qmg_hip.h has L, A, B); b5 = 1, c5 = 0 is Dwf2D with shift = M5.  M5 sits
+// inside D_W and is multiplied by B, so it is a parameter of the operator and the stencil's three shifts are zero.  The stored arrays
+// (qmg_mobius_fill; the hopping blocks are no longer diagonal in s) serve the dagger / right-block-Jacobi / Galerkin builds and every piece set
+// the links entry declines; apply_M and apply_M_dagger on the whole lattice go straight from the links (qmg_mobius_apply_direct, op 0 / op 1,
+// csrc/qmg_mobius.hip).  Gamma5 D Gamma5 is NOT D^dagger here (B and H do not commute): the dagger is the entry's op 1, and it needs no stored
+// dagger stencil while the links route is on.  Whole lattice only.
+struct MobiusBase : public Stencil2D {
+ protected:
+  complex<double> mass;
+  double M5, b5, c5;
+  int mobius_Ls;
+  MobiusBase(Lattice2D* in_lat, complex<double> mass, double M5, double b5, double c5, int Ls)
+      : Stencil2D(in_lat, QMG_PIECE_CLOVER_HOPPING, 0, 0, 0), mass(mass), M5(M5), b5(b5), c5(c5), mobius_Ls(Ls) {}
+
+ public:
+  int get_Ls() const { return mobius_Ls; }
+  complex<double> get_mass() const { return mass; }
+  double get_M5() const { return M5; }
+  double get_b5() const { return b5; }
+  double get_c5() const { return c5; }
+  // whether both applies come from the links (the normal-equation solve below works on that: no stored fallback at Ls = 32)
+  bool links_ready() const { return direct.on && direct.kind == QMG_DIRECT_MOBIUS && !swap_dagger && !swap_rbjacobi && !swap_rbj_dagger; }
+  // lhs = D^dagger D rhs, both applies from the links; extra_cvector holds D rhs
+  void apply_M_dagger_M_links(complex<double>* lhs, complex<double>* rhs) {
+    apply_M_overwrite(extra_cvector, rhs);
+    zero_vector(lhs, lat->get_size_cv_l());
+    apply_M_dagger(lhs, extra_cvector);
+  }
+};
+
+template <int Ls>
+struct Mobius2D : public MobiusBase {
+ protected:
+  Mobius2D(Mobius2D const&);
+  Mobius2D& operator=(Mobius2D const&);
+  complex<double>* scratch;   // for the in-place gamma5
+
+ public:
+  double a[2 * Ls];        // gamma5 as a scale / shuffle pattern, as in Dwf2D
+  int shuffle[2 * Ls];
+
+  void update_links(complex<double>* gauge_links) {   // gauge_links: DEVICE nc=1 LatticeGauge
+    qmg::ok(qmg_mobius_fill(clover, hopping, gauge_links, lat->get_dim_mu(0), lat->get_dim_mu(1), Ls, mass.real(), mass.imag(), 1.0, M5, b5, c5, qmg::current_stream()),
+            "qmg_mobius_fill");
+    drop_variant_stencils();
+    set_direct_links(gauge_links, 1.0, QMG_DIRECT_MOBIUS, Ls, mass, M5, b5, c5);   // apply_M and apply_M_dagger go straight from the links
+    generated = true;
+  }
+
+  Mobius2D(Lattice2D* in_lat, complex<double> mass, complex<double>* gauge_links, double b5, double c5, double M5 = -1.0)
+      : MobiusBase(in_lat, mass, M5, b5, c5, Ls), scratch(0) {
+    for (int i = 0; i < Ls; i++) {
+      a[2 * i] = 1.0; a[2 * i + 1] = -1.0;
+      shuffle[2 * i] = 2 * (Ls - 1 - i); shuffle[2 * i + 1] = 2 * (Ls - 1 - i) + 1;
+    }
+    if (lat->get_nc() != 2 * Ls) { std::cout << "[QMG-ERROR]: Mobius2D only supports Nc = 2 Ls.\n"; return; }
+    if (qmg::slab().on) { std::cout << "[QMG-ERROR]: Mobius2D is not decomposed into y-slabs.\n"; return; }
+    update_links(gauge_links);
+  }
+  ~Mobius2D() { if (scratch) deallocate_vector(&scratch); }
+
+  static int get_dof(int i = 0) { return 2 * Ls; }
+  static chirality_state has_chirality() { return QMG_CHIRAL_YES; }
+
+  // (Gamma5 psi)(s, sigma) = (-1)^sigma psi(Ls-1-s, sigma)
+  virtual void gamma5(complex<double>* vec) {
+    if (!scratch) scratch = allocate_vector<complex<double>>(lat->get_size_cv_l());
+    qmg::pattern(a, shuffle, 2 * Ls, vec, scratch, (size_t)lat->get_volume());
+    copy_vector(vec, scratch, lat->get_size_cv_l());
+  }
+  virtual void gamma5(complex<double>* g5_vec, complex<double>* vec) {
+    if (g5_vec == vec) { gamma5(vec); return; }
+    qmg::pattern(a, shuffle, 2 * Ls, vec, g5_vec, (size_t)lat->get_volume());
+  }
+  virtual void chiral_projection(complex<double>*, bool) { return; }
+  virtual void chiral_projection_copy(complex<double>*, complex<double>*, bool) { return; }
+  virtual void chiral_projection_both(complex<double>*, complex<double>*) { return; }
+  virtual QMGDefaultChirality get_default_chirality() { return QMG_CHIRALITY_GAMMA_5; }
+};
+
+// A Moebius operator of run-time Ls: createDwfLs's list of Ls values.  Where the stored-stencil apply does not serve nc = 2 Ls (Ls = 32 today)
+// the operator is made all the same: both applies and the solve below come from the links, and only what needs the stored arrays is missing.
+inline MobiusBase* createMobiusLs(Lattice2D* in_lat, complex<double> mass, complex<double>* gauge_links, int Ls, double b5, double c5, double M5 = -1.0) {
+  switch (Ls) {
+    case 2: return new Mobius2D<2>(in_lat, mass, gauge_links, b5, c5, M5);
+    case 4: return new Mobius2D<4>(in_lat, mass, gauge_links, b5, c5, M5);
+    case 6: return new Mobius2D<6>(in_lat, mass, gauge_links, b5, c5, M5);
+    case 8: return new Mobius2D<8>(in_lat, mass, gauge_links, b5, c5, M5);
+    case 12: return new Mobius2D<12>(in_lat, mass, gauge_links, b5, c5, M5);
+    case 16: return new Mobius2D<16>(in_lat, mass, gauge_links, b5, c5, M5);
+    case 24: return new Mobius2D<24>(in_lat, mass, gauge_links, b5, c5, M5);
+    case 32: return new Mobius2D<32>(in_lat, mass, gauge_links, b5, c5, M5);
+    default: break;
+  }
+  std::cout << "[QMG-ERROR]: Unsupported Ls " << Ls << " for the Moebius domain wall operator.\n";
+  return nullptr;
+}
+
+inline void apply_mobius_Mdagger_M(complex<double>* lhs, complex<double>* rhs, void* extra_data) { ((MobiusBase*)extra_data)->apply_M_dagger_M_links(lhs, rhs); }
+
+// D x = b by CG on the normal equations: minv_vector_cg on D^dagger D with D^dagger b as the right-hand side, from x as the initial guess; eps is
+// the relative residual of D^dagger D x = D^dagger b.  Both applies come from the links, so this works at Ls = 32; where the links route is off
+// nothing is solved and success is false.
+inline inversion_info minv_mobius_cg(complex<double>* x, complex<double>* b, int max_iter, double eps, MobiusBase* mobius, inversion_verbose_struct* verb = 0) {
+  const size_t n = mobius->lat->get_size_cv_l();
+  if (!mobius->links_ready()) {
+    std::cout << "[QMG-ERROR]: minv_mobius_cg needs the Moebius links route (direct.on, no variant swapped in).\n";
+    inversion_info none;
+    none.name = "CG (Moebius domain wall): not run";
+    return none;
+  }
+  complex<double>* rhs = allocate_vector<complex<double>>(n);
+  zero_vector(rhs, n);
+  mobius->apply_M_dagger(rhs, b);
+  const inversion_info info = minv_vector_cg(x, rhs, (int)n, max_iter, eps, apply_mobius_Mdagger_M, (void*)mobius, verb);
+  deallocate_vector(&rhs);
   return info;
 }
 

@@ -67,7 +67,7 @@ struct Stencil2D {
   void launch(unsigned pieces, complex<double>* lhs, complex<double>* rhs, const complex<double>* cl, const complex<double>* ho,
               complex<double> s, complex<double> es, complex<double> ds) {
     const RouteState state = route_state();
-    const RouteRequest q = {cl, ho, false, QMG_ARR_ORIGINAL, pieces, QMG_C64, state.slab_on ? QMG_ROUTE_SLAB : QMG_ROUTE_WHOLE, true};
+    const RouteRequest q = {cl, ho, false, QMG_ARR_ORIGINAL, pieces, QMG_C64, state.slab_on ? QMG_ROUTE_SLAB : QMG_ROUTE_WHOLE, true, false};
     const Route r = resolve_route(state, q);
     const qmg_stencil_desc d = desc(cl, ho, s, es, ds);
     if (!state.slab_on) { run_route(r, q.mode, d, QMG_C64, lhs, rhs, pieces, 1, 0, 1u); return; }
@@ -119,7 +119,9 @@ struct Stencil2D {
   // QMG_WILSON_DIRECT=0 in the environment turns it off.
   // The same holds for the Shamir domain-wall operator (Dwf2D; qmg_dwf_apply_direct, csrc/qmg_dwf.hip: 64 Ls + 32 B/site instead of
   // 5 (2 Ls)^2 complex numbers): `kind` says whose links these are, Ls and m are the domain-wall operator's.
-  enum QMGDirectKind { QMG_DIRECT_WILSON = 0, QMG_DIRECT_DWF = 1 };
+  // And for the Moebius domain-wall operator (Mobius2D; qmg_mobius_apply_direct, csrc/qmg_mobius.hip), whose entry serves D^dagger as well
+  // (apply_M_dagger: no stored dagger stencil is needed while the links route is on): M5, b5, c5 are its parameters.
+  enum QMGDirectKind { QMG_DIRECT_WILSON = 0, QMG_DIRECT_DWF = 1, QMG_DIRECT_MOBIUS = 2 };
   struct DirectLinks {
     complex<double>* gauge; void* gauge32; double w; bool on;
     int kind;                // QMGDirectKind
@@ -127,6 +129,7 @@ struct Stencil2D {
     complex<double> m;       // domain wall: the wall mass
     // right-block-Jacobi hops from the links too (qmg_wilson_hops_direct): cinv = rbj_scale x identity at every site, 0 = not so
     double rbj_scale;
+    double M5, b5, c5;       // Moebius: the domain-wall height inside D_W and the two Moebius coefficients
   } direct;
   // y-slab mode (qmg::slab()): the halo rows of the right-hand side of an apply, [parity][Lx/2][nc] each
   complex<double>*slab_halo_lo, *slab_halo_hi;
@@ -138,16 +141,18 @@ struct Stencil2D {
   // which parities of the right-hand side the hops of `pieces` read: D_eo (even sites written) reads odd rows, D_oe even rows
   static unsigned halo_parities(unsigned pieces) { return ((pieces & QMG_P_EO) ? 2u : 0u) | ((pieces & QMG_P_OE) ? 1u : 0u); }
   qmg::HaloOverlap slab_overlap;   // the second stream and events of a single-vector slab apply, made on first use
-  void set_direct_links(const complex<double>* gauge_links, double w, int kind = QMG_DIRECT_WILSON, int Ls = 0, complex<double> m = 0.0) {   // copies the links (the caller's array may change)
+  void set_direct_links(const complex<double>* gauge_links, double w, int kind = QMG_DIRECT_WILSON, int Ls = 0, complex<double> m = 0.0, double M5 = 0.0,
+                        double b5 = 1.0, double c5 = 0.0) {   // copies the links (the caller's array may change)
     static const bool enabled = !(getenv("QMG_WILSON_DIRECT") && atoi(getenv("QMG_WILSON_DIRECT")) == 0);
     direct.rbj_scale = 0.0;   // (a right-block-Jacobi stencil of the old links is dropped by the caller)
     const size_t n = (size_t)2 * lat->get_volume() * (qmg::slab().on ? qmg::slab().world : 1);   // a slab keeps the links of the WHOLE lattice (32 B/site)
-    if (!enabled || lat->get_nc() != (kind == QMG_DIRECT_DWF ? 2 * Ls : 2)) { direct.on = false; return; }
+    if (!enabled || lat->get_nc() != (kind == QMG_DIRECT_WILSON ? 2 : 2 * Ls)) { direct.on = false; return; }
     if (!direct.gauge) direct.gauge = allocate_vector<complex<double>>(n);
     if (!direct.gauge) { direct.on = false; return; }
     qmg::ok(qmg_memcpy_d2d(direct.gauge, gauge_links, sizeof(complex<double>) * n, qmg::current_stream()), "qmg_memcpy_d2d");
     if (direct.gauge32) qmg::ok(qmg_convert(direct.gauge32, QMG_C32, direct.gauge, QMG_C64, n, qmg::current_stream()), "qmg_convert");
     direct.w = w; direct.kind = kind; direct.Ls = Ls; direct.m = m;
+    direct.M5 = M5; direct.b5 = b5; direct.c5 = c5;
     direct.on = true;
   }
   void drop_direct_links() {
@@ -181,7 +186,7 @@ struct Stencil2D {
   // holds it to a table written out by hand -- and run_route is the only function that names the apply entry points.  launch (one fp64 vector, arrays
   // by pointer), launch_set_batch and launch_set_epi (either precision, arrays by set) are front ends of the two.
   enum RouteMode { QMG_ROUTE_WHOLE = 0, QMG_ROUTE_SLAB = 1, QMG_ROUTE_EPILOGUE = 2 };
-  enum RouteLinks { QMG_LINKS_NONE = 0, QMG_LINKS_WILSON = 1, QMG_LINKS_DWF = 2, QMG_LINKS_RBJ_HOPS = 3 };
+  enum RouteLinks { QMG_LINKS_NONE = 0, QMG_LINKS_WILSON = 1, QMG_LINKS_DWF = 2, QMG_LINKS_RBJ_HOPS = 3, QMG_LINKS_MOBIUS = 4 };
   enum RouteStorage { QMG_MAT_C64 = 0, QMG_MAT_C32 = 1, QMG_MAT_C16 = 2 };   // complex<double>, <float>, <half> matrices (the values are qmg_stencil_apply_epi_t's mat32)
   struct RouteState {
     const void *clover, *hopping, *dagger_clover, *dagger_hopping, *rbjacobi_hopping, *rbjacobi_cinv, *rbj_dagger_hopping;
@@ -209,13 +214,15 @@ struct Stencil2D {
     int dtype;                 // of the vectors: QMG_C64 / QMG_C32
     int mode;                  // RouteMode
     bool epilogue_wanted;      // QMG_APPLY_EPILOGUE
+    bool dagger;               // the dagger of the ORIGINAL operator straight from the links (Moebius, op 1); such a request has no stored arrays
   };
   // links != NONE: a first attempt straight from the links `gauge`; where that entry declines the request, and without one, the stored arrays
   // `clover` / `hopping` in `storage` -- or, refused, nothing
-  struct Route { bool refused; int links; const void* gauge; const void *clover, *hopping; int storage; };
+  // op: 1 for a dagger request (its stored side is always refused: the dagger stencil is the caller's, apply_M_dagger)
+  struct Route { bool refused; int links; const void* gauge; const void *clover, *hopping; int storage; int op; };
 
   static Route resolve_route(const RouteState& s, const RouteRequest& q) {
-    Route r = {false, QMG_LINKS_NONE, 0, 0, 0, QMG_MAT_C64};
+    Route r = {false, QMG_LINKS_NONE, 0, 0, 0, QMG_MAT_C64, 0};
     const bool f = q.dtype == QMG_C32, epi = q.mode == QMG_ROUTE_EPILOGUE;
     const NarrowCopies &storage = s.narrow[QMG_NARROW_STORAGE], &shadow = s.narrow[QMG_NARROW_SHADOW], &half_shadow = s.narrow[QMG_NARROW_SHADOW_HALF];
     // Refused before anything runs: an epilogue that is switched off or asked on a slab, and a complex<float> apply without the shadow on a slab (nothing
@@ -229,14 +236,17 @@ struct Stencil2D {
       if (s.generated && cl != 0 && ho != 0 && cl == s.clover && ho == s.hopping && !variant_in && !storage.on) {
         // the ORIGINAL operator (the link copy stands in for the stored arrays only while those ARE the filled operator: clear_stencils / prune_stencils
         // drop it, and a null pair -- 0 == 0 after a prune -- never qualifies); slabs and epilogues are served from Wilson links only
-        if (s.direct.kind == QMG_DIRECT_WILSON) r.links = QMG_LINKS_WILSON;
-        else if (q.mode == QMG_ROUTE_WHOLE) r.links = QMG_LINKS_DWF;
-      } else if (s.direct.rbj_scale != 0.0 && s.built_rbjacobi && cl == 0 && ho != 0 && ho == s.rbjacobi_hopping_in_use() && !s.swap_dagger && !s.swap_rbj_dagger &&
+        // from the domain-wall links (Shamir, Moebius) on a whole lattice only; a dagger from Moebius links only
+        if (q.dagger) { if (s.direct.kind == QMG_DIRECT_MOBIUS && q.mode == QMG_ROUTE_WHOLE) r.links = QMG_LINKS_MOBIUS; }
+        else if (s.direct.kind == QMG_DIRECT_WILSON) r.links = QMG_LINKS_WILSON;
+        else if (q.mode == QMG_ROUTE_WHOLE) r.links = s.direct.kind == QMG_DIRECT_MOBIUS ? QMG_LINKS_MOBIUS : QMG_LINKS_DWF;
+      } else if (!q.dagger && s.direct.rbj_scale != 0.0 && s.built_rbjacobi && cl == 0 && ho != 0 && ho == s.rbjacobi_hopping_in_use() && !s.swap_dagger && !s.swap_rbj_dagger &&
                  !(q.pieces & (QMG_P_CLOVER | QMG_P_SHIFT))) {
         r.links = QMG_LINKS_RBJ_HOPS;   // the hops of the right-block-Jacobi stencil, alone, while that stencil is the built one (swapped in or not)
       }
       if (r.links != QMG_LINKS_NONE) r.gauge = f ? s.direct.gauge32 : (const void*)s.direct.gauge;
     }
+    if (q.dagger) { r.op = 1; r.refused = true; return r; }
     if (f) {   // the fp32 shadow of the set, or the 16-bit copies of the set's slots that have them (of RBJ_HOPPING the hops only)
       const bool half = half_shadow.on && has_half_shadow(q.set, QMG_SLOT_HOPPING);
       if (!shadow.on || (epi && half && s.nc == 2)) { r.refused = true; return r; }   // (kernel S, the 16-bit nc = 2 kernel, has no epilogue)
@@ -273,7 +283,11 @@ struct Stencil2D {
     if (r.links != QMG_LINKS_NONE) {
       int rc;
       const char* what;
-      if (r.links == QMG_LINKS_DWF) {
+      if (r.links == QMG_LINKS_MOBIUS) {
+        what = "qmg_mobius_apply_direct";
+        rc = qmg_mobius_apply_direct(dt, &d, r.gauge, direct.Ls, direct.m.real(), direct.m.imag(), direct.w, direct.M5, direct.b5, direct.c5, r.op, lhs, rhs, pieces, nrhs,
+                                     stride, mask, st);
+      } else if (r.links == QMG_LINKS_DWF) {
         what = "qmg_dwf_apply_direct";
         rc = qmg_dwf_apply_direct(dt, &d, r.gauge, direct.Ls, direct.m.real(), direct.m.imag(), direct.w, lhs, rhs, pieces, nrhs, stride, mask, st);
       } else if (r.links == QMG_LINKS_WILSON) {
@@ -291,7 +305,7 @@ struct Stencil2D {
       if (rc != QMG_ERR_UNSUPPORTED && (epi || rc != QMG_ERR_INVALID)) { qmg::ok(rc, what); return -1; }
     }
     if (r.refused) {
-      if (!epi) std::cout << "[QMG-ERROR]: fp32 apply without an fp32 shadow (Stencil2D::enable_f32_shadow).\n";
+      if (!epi && !r.op) std::cout << "[QMG-ERROR]: fp32 apply without an fp32 shadow (Stencil2D::enable_f32_shadow).\n";
       return 0;
     }
     d.clover = r.clover; d.hopping = r.hopping;
@@ -340,6 +354,7 @@ struct Stencil2D {
     narrow[QMG_NARROW_SHADOW_HALF].bits = 16;
     direct.gauge = 0; direct.gauge32 = 0; direct.w = 1.0; direct.on = false; direct.rbj_scale = 0.0;
     direct.kind = QMG_DIRECT_WILSON; direct.Ls = 0; direct.m = 0.0;
+    direct.M5 = 0.0; direct.b5 = 1.0; direct.c5 = 0.0;
     slab_halo_lo = slab_halo_hi = 0;
     built_dagger = false; dagger_clover = dagger_hopping = dagger_twolink = dagger_corner = 0;
     built_rbjacobi = false; rbjacobi_clover = rbjacobi_hopping = rbjacobi_twolink = rbjacobi_corner = rbjacobi_cinv = 0;
@@ -611,7 +626,7 @@ struct Stencil2D {
                         int nrhs, size_t stride, unsigned mask) {
     const RouteState state = route_state();
     const int dt = sizeof(T) == sizeof(float) ? QMG_C32 : QMG_C64;
-    const RouteRequest q = {0, 0, true, set, pieces, dt, state.slab_on ? QMG_ROUTE_SLAB : QMG_ROUTE_WHOLE, true};
+    const RouteRequest q = {0, 0, true, set, pieces, dt, state.slab_on ? QMG_ROUTE_SLAB : QMG_ROUTE_WHOLE, true, false};
     const Route r = resolve_route(state, q);
     const qmg_stencil_desc d = desc(0, 0, s, es, ds);
     if (state.slab_on && !r.refused) {   // slabs: ONE exchange of the batch's halo rows, one launch with them (kernel W / S on nc = 2, kernel B otherwise)
@@ -631,7 +646,7 @@ struct Stencil2D {
                       size_t stride, int system, const qmg_apply_epilogue& epi) {
     static const bool wanted = !(getenv("QMG_APPLY_EPILOGUE") && atoi(getenv("QMG_APPLY_EPILOGUE")) == 0);
     const int dt = sizeof(T) == sizeof(float) ? QMG_C32 : QMG_C64;
-    const RouteRequest q = {0, 0, true, set, pieces, dt, QMG_ROUTE_EPILOGUE, wanted};
+    const RouteRequest q = {0, 0, true, set, pieces, dt, QMG_ROUTE_EPILOGUE, wanted, false};
     return run_route(resolve_route(route_state(), q), q.mode, desc(0, 0, s, es, ds), dt, lhs, rhs, pieces, system + 1, stride, 1u << system, 0, &epi) != 0;
   }
 
@@ -773,7 +788,17 @@ struct Stencil2D {
     if (!built_dagger) { std::cout << "[QMG-WARNING]: Tried to call apply_M_dagger_shift, but the dagger stencil has not been allocated.\n"; return; }
     perform_swap_dagger(); apply_M_shift(lhs, rhs); perform_swap_dagger();
   }
+  // lhs += D^dagger rhs straight from the links, where the operator's entry has the dagger (Moebius: the other operator ordering, A + B H);
+  // false: not served this way, nothing launched
+  bool launch_dagger_from_links(unsigned pieces, complex<double>* lhs, complex<double>* rhs) {
+    if (!direct.on || direct.kind != QMG_DIRECT_MOBIUS) return false;
+    const RouteState state = route_state();
+    const RouteRequest q = {clover, hopping, false, QMG_ARR_ORIGINAL, pieces, QMG_C64, state.slab_on ? QMG_ROUTE_SLAB : QMG_ROUTE_WHOLE, true, true};
+    const Route r = resolve_route(state, q);
+    return r.links == QMG_LINKS_MOBIUS && run_route(r, q.mode, desc(), QMG_C64, lhs, rhs, pieces, 1, 0, 1u) == 1;
+  }
   void apply_M_dagger(complex<double>* lhs, complex<double>* rhs) {
+    if (launch_dagger_from_links(QMG_P_ALL, lhs, rhs)) return;
     if (!built_dagger) { std::cout << "[QMG-WARNING]: Tried to call apply_M_dagger, but the dagger stencil has not been allocated.\n"; return; }
     perform_swap_dagger(); apply_M(lhs, rhs); perform_swap_dagger();
   }
