@@ -803,6 +803,57 @@ int qmg_mobius_apply_direct(int dtype, const qmg_stencil_desc* d, const void* ga
  * QMG_ERR_INVALID: plan_out missing or plan_len below 8. */
 int qmg_mobius_plan(int dtype, int Lx, int Ly, int Ls, int op, unsigned pieces, int n_active, int inplace, int* plan_out, int plan_len);
 
+/* ---------------- the even-odd Schur complement of the Moebius operator and its dagger, from the links (csrc/qmg_mobius_eo.hip) ----------------
+ * D = A + H B with A, B site-local and the same at every site of a parity: alpha_p = alpha + shift +- eo_shift (+ even, - odd), A_p = alpha_p +
+ * kappa L.  With p the parity of the system:
+ *   M_p        = A_p - H_{p,1-p} B A_{1-p}^-1 H_{1-p,p} B
+ *   M_p^dagger = Gamma5 [A'_p - B' H_{p,1-p} A'_{1-p}^-1 B' H_{1-p,p}] Gamma5         ': conj(m) and conjugated shifts
+ *   prepare      b'_p    = b_p - H_{p,1-p} B A_{1-p}^-1 b_{1-p}
+ *   reconstruct  x_{1-p} = A_{1-p}^-1 (b_{1-p} - H_{1-p,p} B x_p)
+ * Gamma5 M Gamma5 is not M^dagger here (B does not commute with H).  L^Ls = -m on sigma 0, so every function of L is a twisted circulant of Ls
+ * coefficients: (L^k h)(s) = h(s-k) for s >= k, -m h(s-k+Ls) below; sigma 1 mirrored under s -> Ls-1-s.  The tables are formed on the host in
+ * long double, rounded once and passed by value:  A_p^-1: f_k = r^k / (alpha_p (1 + m r^Ls)), r = -kappa / alpha_p;  A_p^-1 B: g_k = b5 f_k +
+ * c5 f_{k-1}, g_0 = b5 f_0 - m c5 f_{Ls-1}.  The kernels exchange a site's chunks along s through LDS and apply a table in 2 Ls complex FMAs.
+ * Common to the three entries: d, M5, b5, c5 as in qmg_mobius_apply_direct and its validity rules; mask as in qmg_stencil_apply_batch.
+ * Refused before anything is launched:  dof_shift != 0 -- QMG_ERR_UNSUPPORTED;  |kappa| >= |alpha_p| for a parity whose A is inverted --
+ * QMG_ERR_UNSUPPORTED (the powers of r would not decay);  alpha_p == 0 or 1 + m r^Ls == 0 for such a parity, or any coefficient (mass,
+ * wilson_coeff, M5, b5, c5, shifts, scale, a table entry) not finite -- QMG_ERR_INVALID. */
+enum { QMG_MOBIUS_S_ONE = 0, QMG_MOBIUS_S_AINV = 1, QMG_MOBIUS_S_AINV_B = 2 };   /* `table`: the site matrix S applied through LDS */
+enum { QMG_MOBIUS_R_ONE = 0, QMG_MOBIUS_R_B = 1 };                               /* `source`: the site matrix R applied to the hop source on the load */
+/* lhs_p = scale S rhs_p on the parities named by QMG_P_CLOVER_E / QMG_P_CLOVER_O (any other bit: QMG_ERR_UNSUPPORTED); table: QMG_MOBIUS_S_AINV
+ * or QMG_MOBIUS_S_AINV_B (QMG_ERR_INVALID otherwise); overwrites; lhs == rhs is allowed. */
+int qmg_mobius_inv5(int dtype, const qmg_stencil_desc* d, int Ls, double mass_re, double mass_im, double wilson_coeff, double M5, double b5, double c5, void* lhs,
+                    const void* rhs, unsigned pieces, int table, double scale_re, double scale_im, int nrhs, size_t vec_stride, unsigned mask, void* stream);
+/* lhs_p = (QMG_P_ZERO_p ? 0 : lhs_p) + scale S H_{p,1-p} (R [Gamma5] rhs_{1-p}): stage 1 of M (S = A^-1, R = B) and of M^dagger (S = A^-1 B, R = 1,
+ * QMG_DWF_G5_IN, called with conj(m) and conjugated shifts), prepare (S = 1, R = B) and reconstruct (S = A^-1, R = B).  pieces, flags and the
+ * lhs == rhs rule are those of qmg_dwf_hops_inv5; a table or source outside the enums: QMG_ERR_INVALID. */
+int qmg_mobius_hops_inv5(int dtype, const qmg_stencil_desc* d, const void* gauge, int Ls, double mass_re, double mass_im, double wilson_coeff, double M5, double b5,
+                         double c5, void* lhs, const void* rhs, unsigned pieces, int table, int source, double scale_re, double scale_im, unsigned flags, int nrhs,
+                         size_t vec_stride, unsigned mask, void* stream);
+/* lhs_p = M_p rhs_p (op 0) or M_p^dagger rhs_p (op 1), p = parity (0 even, 1 odd).  Two launches either way; no Gamma5 pass and no copy.
+ *   op 0:  tmp_o = -A_o^-1 H (B rhs_p),  then  lhs_p = A_p rhs_p + H (B tmp_o)             (B on the load in both; no LDS in the second)
+ *   op 1:  tmp_o = -(A'_o^-1 B') H (Gamma5 rhs_p),  then  lhs_p = Gamma5 [A'_p Gamma5 rhs_p + B' (H tmp_o)]   (B' on the hop sum through LDS)
+ * Only the 1-p half of tmp is written; the 1-p halves of lhs and rhs are not touched.  lhs, rhs and tmp are three different arrays and op is
+ * 0 or 1 (QMG_ERR_INVALID otherwise). */
+int qmg_mobius_schur_apply(int dtype, const qmg_stencil_desc* d, const void* gauge, int Ls, double mass_re, double mass_im, double wilson_coeff, double M5,
+                           double b5, double c5, void* lhs, const void* rhs, void* tmp, int parity, int op, int nrhs, size_t vec_stride, unsigned mask,
+                           void* stream);
+/* What the three entries launch: the answer of the one host function they switch on.  Host only, no HIP call.
+ * kernel: 0 qmg_mobius_inv5, 1 qmg_mobius_hops_inv5, 2 the second stage of M, 3 the second stage of M^dagger (pieces of 2 and 3:
+ * QMG_P_CLOVER_p | the four hops of p | QMG_P_SHIFT_p | QMG_P_ZERO_p of exactly one parity; table and source as the entries take them, ignored
+ * by kernels 2 and 3).  Writes 8 ints in the layout of qmg_dwf_eo_plan and -1 into the rest of plan_out:
+ *   family  0 unsupported, 1 k_mobius_eo_mix with the hops, 2 success with nothing launched, 3 invalid, 4 k_mobius_eo_mix on the own chunk,
+ *           5 k_mobius_eo_schur2, 6 k_mobius_eo_schur2_dagger
+ *   lps     lanes per site: Ls
+ *   block   threads per block: Ls floor(256 / Ls) (whole sites: the exchange is in LDS); 256 for family 5
+ *   gx, gy  gx blocks cover the Ls Lx/2 lanes of a half row, gy = min(rows, 65535) blocks walk the (parity, y) rows
+ *   flags   qmg_dwf_plan's (1 every processed parity overwritten, 2 more than one system, 4 complex<float>) | 8 the hop source is mixed by B
+ *   lds     bytes of LDS per block: two buffers of one chunk per lane; 0 for family 5
+ *   nk      the systems served
+ * QMG_ERR_INVALID: plan_out missing or plan_len below 8. */
+int qmg_mobius_eo_plan(int dtype, int Lx, int Ly, int Ls, int kernel, unsigned pieces, int table, int source, int n_active, int inplace, int* plan_out,
+                       int plan_len);
+
 /* ---------------- domain-wall measurements: wall source, wall / midpoint projection, slice norms (csrc/qmg_dwf_meas.hip) ----------------
  * A 5D vector has nc = 2 Ls components per site (c = 2 s + sigma), a 4D one nc = 2 (sigma); sigma = 0 is the P_+ component (the one that crosses
  * the wall as out(0, 0) += m psi(Ls-1, 0)), sigma = 1 P_-.  Whole lattice only.  Common to the three entries: dtype QMG_C64 / QMG_C32, Ls in

@@ -61,6 +61,7 @@ ABI_SYMBOLS = [
     "qmg_dwf_inv5", "qmg_dwf_hops_inv5", "qmg_dwf_schur_apply", "qmg_dwf_eo_plan",
     "qmg_dwf_wall_source", "qmg_dwf_wall_project", "qmg_dwf_slice_norms", "qmg_dwf_meas_plan",
     "qmg_mobius_fill", "qmg_mobius_apply_direct", "qmg_mobius_plan",
+    "qmg_mobius_inv5", "qmg_mobius_hops_inv5", "qmg_mobius_schur_apply", "qmg_mobius_eo_plan",
     "qmg_setup_plan",
     "qmg_noise_z4", "qmg_noise_dilute_batch", "qmg_loops_timeslice_batch", "qmg_singlet_plan",
 ]
@@ -957,6 +958,60 @@ def mobius_plan(dtype, dims, Ls, op, pieces, n_active=1, inplace=False):
     """What qmg_mobius_apply_direct launches (qmg_mobius_plan; host only): (family, lps, block, gx, gy, flags, lds, nk)."""
     out = (C.c_int * MOBIUS_PLAN_INTS)()
     check(lib().qmg_mobius_plan(dtype, dims[0], dims[1], Ls, int(op), C.c_uint(pieces), n_active, int(inplace), out, MOBIUS_PLAN_INTS), "qmg_mobius_plan")
+    return tuple(out)
+
+
+# ---- the even-odd Schur complement of the Moebius operator and its dagger from the links (csrc/qmg_mobius_eo.hip)
+# the `kernel`, `table` and `source` arguments and the families of qmg_mobius_eo_plan (include/qmg_hip.h)
+MEK_INV5, MEK_HOPS_INV5, MEK_SCHUR2, MEK_SCHUR2_DAGGER = range(4)
+MOBIUS_S_ONE, MOBIUS_S_AINV, MOBIUS_S_AINV_B = range(3)
+MOBIUS_R_ONE, MOBIUS_R_B = range(2)
+MEF_UNSUPPORTED, MEF_HOPS_MIX, MEF_NOTHING, MEF_INVALID, MEF_MIX, MEF_SCHUR2, MEF_SCHUR2_DAGGER = range(7)
+MEPF_RMIX = 8
+MOBIUS_EO_PLAN_INTS = 8
+
+
+def mobius_inv5_status(dtype, desc, Ls, mass, lhs, rhs, pieces, table=MOBIUS_S_AINV, scale=1.0, w=1.0, M5=-1.0, b5=1.0, c5=0.0, nrhs=1, vec_stride=0, mask=1,
+                       stream=None):
+    """qmg_mobius_inv5's status, unchecked: lhs_p = scale S rhs_p on the parities P_CLOVER_E / P_CLOVER_O name; S = A^-1 or A^-1 B."""
+    mass, scale = complex(mass), complex(scale)
+    return lib().qmg_mobius_inv5(dtype, C.byref(desc), Ls, C.c_double(mass.real), C.c_double(mass.imag), C.c_double(w), C.c_double(M5), C.c_double(b5),
+                                 C.c_double(c5), _vp(lhs), _vp(rhs), C.c_uint(pieces), int(table), C.c_double(scale.real), C.c_double(scale.imag), nrhs,
+                                 C.c_size_t(vec_stride), C.c_uint(mask), C.c_void_p(stream))
+
+
+mobius_inv5 = _checked(mobius_inv5_status, "qmg_mobius_inv5")
+
+
+def mobius_hops_inv5_status(dtype, desc, gauge, Ls, mass, lhs, rhs, pieces, table=MOBIUS_S_AINV, source=MOBIUS_R_B, scale=1.0, flags=0, w=1.0, M5=-1.0, b5=1.0,
+                            c5=0.0, nrhs=1, vec_stride=0, mask=1, stream=None):
+    """qmg_mobius_hops_inv5's status, unchecked: lhs_p (+)= scale S H_{p,1-p} (R [Gamma5] rhs_{1-p})."""
+    mass, scale = complex(mass), complex(scale)
+    return lib().qmg_mobius_hops_inv5(dtype, C.byref(desc), _vp(gauge), Ls, C.c_double(mass.real), C.c_double(mass.imag), C.c_double(w), C.c_double(M5),
+                                      C.c_double(b5), C.c_double(c5), _vp(lhs), _vp(rhs), C.c_uint(pieces), int(table), int(source), C.c_double(scale.real),
+                                      C.c_double(scale.imag), C.c_uint(flags), nrhs, C.c_size_t(vec_stride), C.c_uint(mask), C.c_void_p(stream))
+
+
+mobius_hops_inv5 = _checked(mobius_hops_inv5_status, "qmg_mobius_hops_inv5")
+
+
+def mobius_schur_apply_status(dtype, desc, gauge, Ls, mass, lhs, rhs, tmp, parity=0, op=0, w=1.0, M5=-1.0, b5=1.0, c5=0.0, nrhs=1, vec_stride=0, mask=1,
+                              stream=None):
+    """qmg_mobius_schur_apply's status, unchecked: lhs_p = M_p rhs_p (op 0) or M_p^dagger rhs_p (op 1), two launches."""
+    mass = complex(mass)
+    return lib().qmg_mobius_schur_apply(dtype, C.byref(desc), _vp(gauge), Ls, C.c_double(mass.real), C.c_double(mass.imag), C.c_double(w), C.c_double(M5),
+                                        C.c_double(b5), C.c_double(c5), _vp(lhs), _vp(rhs), _vp(tmp), int(parity), int(op), nrhs, C.c_size_t(vec_stride),
+                                        C.c_uint(mask), C.c_void_p(stream))
+
+
+mobius_schur_apply = _checked(mobius_schur_apply_status, "qmg_mobius_schur_apply")
+
+
+def mobius_eo_plan(dtype, dims, Ls, kernel, pieces, table=MOBIUS_S_AINV, source=MOBIUS_R_ONE, n_active=1, inplace=False):
+    """What the even-odd Moebius entries launch (qmg_mobius_eo_plan; host only): (family, lps, block, gx, gy, flags, lds, nk)."""
+    out = (C.c_int * MOBIUS_EO_PLAN_INTS)()
+    check(lib().qmg_mobius_eo_plan(dtype, dims[0], dims[1], Ls, int(kernel), C.c_uint(pieces), int(table), int(source), n_active, int(inplace), out,
+                                   MOBIUS_EO_PLAN_INTS), "qmg_mobius_eo_plan")
     return tuple(out)
 
 

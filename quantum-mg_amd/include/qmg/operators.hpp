@@ -279,10 +279,18 @@ struct MobiusBase : public Stencil2D {
   complex<double> mass;
   double M5, b5, c5;
   int mobius_Ls;
+  complex<double>* schur5_vector;   // M rhs inside apply_M_schur5_dagger_M, allocated on demand
   MobiusBase(Lattice2D* in_lat, complex<double> mass, double M5, double b5, double c5, int Ls)
-      : Stencil2D(in_lat, QMG_PIECE_CLOVER_HOPPING, 0, 0, 0), mass(mass), M5(M5), b5(b5), c5(c5), mobius_Ls(Ls) {}
+      : Stencil2D(in_lat, QMG_PIECE_CLOVER_HOPPING, 0, 0, 0), mass(mass), M5(M5), b5(b5), c5(c5), mobius_Ls(Ls), schur5_vector(0) {}
+
+  bool schur5(const char* who, complex<double>* lhs, complex<double>* rhs, int op) {
+    const qmg_stencil_desc d = desc();
+    return qmg::ok(qmg_mobius_schur_apply(QMG_C64, &d, direct.gauge, mobius_Ls, mass.real(), mass.imag(), direct.w, M5, b5, c5, lhs, rhs, eo_cvector, 0, op, 1, 0,
+                                          1u, qmg::current_stream()), who);
+  }
 
  public:
+  virtual ~MobiusBase() { if (schur5_vector) deallocate_vector(&schur5_vector); }
   int get_Ls() const { return mobius_Ls; }
   complex<double> get_mass() const { return mass; }
   double get_M5() const { return M5; }
@@ -295,6 +303,59 @@ struct MobiusBase : public Stencil2D {
     apply_M_overwrite(extra_cvector, rhs);
     zero_vector(lhs, lat->get_size_cv_l());
     apply_M_dagger(lhs, extra_cvector);
+  }
+
+  // ---- the 4D even-odd Schur complement from the links (qmg_mobius_inv5 / qmg_mobius_hops_inv5 / qmg_mobius_schur_apply, csrc/qmg_mobius_eo.hip) ----
+  //   M = A_e - H_eo B A_o^-1 H_oe B,   M^dagger = Gamma5 [A'_e - B' H_eo A'_o^-1 B' H_oe] Gamma5   (the entry's op 1: Gamma5 M Gamma5 is not M^dagger)
+  // in the reference's Schur convention, as DwfBase has it: the arrays are addressed as full-length vectors of which the even half is the
+  // system -- a solver hands over half-length arrays --, eo_cvector is the scratch.  These methods need the links route; there is no stored
+  // fallback, so they also serve Ls = 32.  Any complex wall mass and shifts are served (the dagger has kernels of its own).
+  // whether the Schur methods can run (the links route is on); says why not, makes the scratch
+  bool schur5_ready(const char* who) {
+    if (!links_ready()) {
+      std::cout << "[QMG-ERROR]: " << who << " needs the Moebius links route (direct.on, no variant swapped in); there is no stored fallback.\n";
+      return false;
+    }
+    if (eo_cvector == 0) eo_cvector = allocate_vector<complex<double>>(lat->get_size_cv_l());
+    return eo_cvector != 0;
+  }
+  // lhs_e = M rhs_e, overwriting; lhs != rhs
+  void apply_M_schur5(complex<double>* lhs, complex<double>* rhs) {
+    if (schur5_ready("apply_M_schur5")) schur5("apply_M_schur5", lhs, rhs, 0);
+  }
+  // lhs_e = M^dagger rhs_e: two launches, as M
+  void apply_M_schur5_dagger(complex<double>* lhs, complex<double>* rhs) {
+    if (schur5_ready("apply_M_schur5_dagger")) schur5("apply_M_schur5_dagger", lhs, rhs, 1);
+  }
+  void apply_M_schur5_dagger_M(complex<double>* lhs, complex<double>* rhs) {
+    if (!schur5_ready("apply_M_schur5_dagger_M")) return;
+    if (!schur5_vector) schur5_vector = allocate_vector<complex<double>>(lat->get_size_cv_l() / 2);
+    if (schur5("apply_M_schur5_dagger_M", schur5_vector, rhs, 0)) schur5("apply_M_schur5_dagger_M", lhs, schur5_vector, 1);
+  }
+  // b_r,e = b_e - H_eo B A_o^-1 b_o, odd half zero (full-length arrays; b_r != b)
+  void prepare_M_schur5(complex<double>* b_r, complex<double>* b) {
+    if (!schur5_ready("prepare_M_schur5")) return;
+    const qmg_stencil_desc d = desc();
+    const long half = lat->get_size_cv_l() / 2;
+    const double mr = mass.real(), mi = mass.imag();
+    qmg::ok(qmg_mobius_inv5(QMG_C64, &d, mobius_Ls, mr, mi, direct.w, M5, b5, c5, eo_cvector, b, QMG_P_CLOVER_O, QMG_MOBIUS_S_AINV, 1.0, 0.0, 1, 0, 1u,
+                            qmg::current_stream()), "qmg_mobius_inv5");
+    copy_vector(b_r, b, half);
+    qmg::ok(qmg_mobius_hops_inv5(QMG_C64, &d, direct.gauge, mobius_Ls, mr, mi, direct.w, M5, b5, c5, b_r, eo_cvector, QMG_P_EO, QMG_MOBIUS_S_ONE, QMG_MOBIUS_R_B,
+                                 -1.0, 0.0, 0, 1, 0, 1u, qmg::current_stream()), "qmg_mobius_hops_inv5");
+    zero_vector(b_r + half, half);
+  }
+  // x_e = y_e, x_o = A_o^-1 (b_o - H_oe B y_e)   (x and b full-length; of y_e the even half is read)
+  void reconstruct_M_schur5(complex<double>* x, complex<double>* y_e, complex<double>* b) {
+    if (!schur5_ready("reconstruct_M_schur5")) return;
+    const qmg_stencil_desc d = desc();
+    const long half = lat->get_size_cv_l() / 2;
+    const double mr = mass.real(), mi = mass.imag();
+    if (x != y_e) copy_vector(x, y_e, half);
+    qmg::ok(qmg_mobius_inv5(QMG_C64, &d, mobius_Ls, mr, mi, direct.w, M5, b5, c5, x, b, QMG_P_CLOVER_O, QMG_MOBIUS_S_AINV, 1.0, 0.0, 1, 0, 1u,
+                            qmg::current_stream()), "qmg_mobius_inv5");
+    qmg::ok(qmg_mobius_hops_inv5(QMG_C64, &d, direct.gauge, mobius_Ls, mr, mi, direct.w, M5, b5, c5, x, x, QMG_P_OE, QMG_MOBIUS_S_AINV, QMG_MOBIUS_R_B, -1.0, 0.0,
+                                 0, 1, 0, 1u, qmg::current_stream()), "qmg_mobius_hops_inv5");
   }
 };
 
@@ -384,6 +445,32 @@ inline inversion_info minv_mobius_cg(complex<double>* x, complex<double>* b, int
   mobius->apply_M_dagger(rhs, b);
   const inversion_info info = minv_vector_cg(x, rhs, (int)n, max_iter, eps, apply_mobius_Mdagger_M, (void*)mobius, verb);
   deallocate_vector(&rhs);
+  return info;
+}
+
+// The Schur complement with the matrix_op_cplx signature (extra_data: a MobiusBase*), for the Krylov solvers on the even half.
+inline void apply_mobius_schur5_M(complex<double>* lhs, complex<double>* rhs, void* extra_data) { ((MobiusBase*)extra_data)->apply_M_schur5(lhs, rhs); }
+inline void apply_mobius_schur5_Mdagger_M(complex<double>* lhs, complex<double>* rhs, void* extra_data) {
+  ((MobiusBase*)extra_data)->apply_M_schur5_dagger_M(lhs, rhs);
+}
+
+// D x = b by CG on the normal equations of the even-odd Schur complement: prepare, M^dagger b', minv_vector_cg over the half length from the
+// even half of x as the initial guess, reconstruct.  x and b are full-length; eps is the relative residual of M^dagger M y = M^dagger b'.
+// Everything comes from the links, so this works at Ls = 32; where the links route is off nothing is solved and success is false.
+inline inversion_info minv_mobius_eo_cg(complex<double>* x, complex<double>* b, int max_iter, double eps, MobiusBase* mobius, inversion_verbose_struct* verb = 0) {
+  const size_t n = mobius->lat->get_size_cv_l(), half = n / 2;
+  if (!mobius->schur5_ready("minv_mobius_eo_cg")) {   // nothing to iterate on: no solve, x untouched
+    inversion_info none;
+    none.name = "CG (even-odd Moebius domain wall): not run";
+    return none;
+  }
+  complex<double>* b_r = allocate_vector<complex<double>>(n);
+  complex<double>* rhs = allocate_vector<complex<double>>(half);
+  mobius->prepare_M_schur5(b_r, b);
+  mobius->apply_M_schur5_dagger(rhs, b_r);
+  const inversion_info info = minv_vector_cg(x, rhs, (int)half, max_iter, eps, apply_mobius_schur5_Mdagger_M, (void*)mobius, verb);
+  mobius->reconstruct_M_schur5(x, x, b);
+  deallocate_vector(&b_r); deallocate_vector(&rhs);
   return info;
 }
 
