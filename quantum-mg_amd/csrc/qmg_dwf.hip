@@ -321,11 +321,8 @@ int qmg_dwf_fill(void* clover, void* hopping, const void* gauge, int Lx, int Ly,
 }
 
 int qmg_dwf_plan(int dtype, int Lx, int Ly, int Ls, unsigned pieces, int n_active, int inplace, int* plan_out, int plan_len) {
-  if (!plan_out || plan_len < DWF_PLAN_INTS) return QMG_ERR_INVALID;
   const DwfPlan pl = dwf_plan(dtype, Lx, Ly, Ls, pieces, n_active, inplace);
-  const int v[DWF_PLAN_INTS] = {pl.family, pl.lps, pl.block, pl.gx, pl.gy, pl.flags, pl.shape, pl.nk};
-  export_plan_ints(v, DWF_PLAN_INTS, plan_out, plan_len);
-  return QMG_SUCCESS;
+  return export_dw_plan(pl, pl.shape, plan_out, plan_len);
 }
 
 int qmg_dwf_apply_direct(int dtype, const qmg_stencil_desc* d, const void* gauge, int Ls, double mass_re, double mass_im, double wilson_coeff, void* lhs,

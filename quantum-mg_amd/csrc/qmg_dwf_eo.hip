@@ -209,12 +209,6 @@ static void launch_dwf_eo(const DwfEoArgs<T>& a, const DwfEoPlan& pl, hipStream_
   }
 }
 
-// what every entry checks before the plan is asked
-static int eo_valid(int dtype, const qmg_stencil_desc* d, int Ls, int nrhs, size_t vec_stride) {
-  if (!d || d->nc != 2 * Ls) return QMG_ERR_INVALID;
-  return dwf_entry_check(dtype, d->Lx, d->Ly, Ls, nrhs, vec_stride);
-}
-
 // one launch of a planned request
 template <typename T>
 static void eo_launch(const qmg_stencil_desc* d, const DwfEoPlan& pl, const DwfEoCoef& co, const void* gauge, int Ls, double mr, double mi, double w, void* lhs,
@@ -247,23 +241,19 @@ using namespace qmg;
 extern "C" {
 
 int qmg_dwf_eo_plan(int dtype, int Lx, int Ly, int Ls, int kernel, unsigned pieces, int n_active, int inplace, int* plan_out, int plan_len) {
-  if (!plan_out || plan_len < DWF_EO_PLAN_INTS) return QMG_ERR_INVALID;
   const DwfEoPlan pl = dwf_eo_plan(dtype, Lx, Ly, Ls, kernel, pieces, n_active, inplace);
-  const int v[DWF_EO_PLAN_INTS] = {pl.family, pl.lps, pl.block, pl.gx, pl.gy, pl.flags, pl.lds, pl.nk};
-  export_plan_ints(v, DWF_EO_PLAN_INTS, plan_out, plan_len);
-  return QMG_SUCCESS;
+  return export_dw_plan(pl, pl.lds, plan_out, plan_len);
 }
 
 int qmg_dwf_inv5(int dtype, const qmg_stencil_desc* d, int Ls, double mass_re, double mass_im, double wilson_coeff, void* lhs, const void* rhs, unsigned pieces,
                  double alpha_re, double alpha_im, int nrhs, size_t vec_stride, unsigned mask, void* stream) {
   if (!lhs || !rhs || !aligned16(lhs) || !aligned16(rhs) || !std::isfinite(alpha_re) || !std::isfinite(alpha_im)) return QMG_ERR_INVALID;
-  if (int rc = eo_valid(dtype, d, Ls, nrhs, vec_stride)) return rc;
+  if (int rc = dw_eo_valid(dtype, d, Ls, nrhs, vec_stride)) return rc;
   const BatchIdx b = expand_mask(mask, nrhs);
   const DwfEoPlan pl = dwf_eo_plan(dtype, d->Lx, d->Ly, Ls, DEK_INV5, pieces, b.n, lhs == rhs);
-  if (pl.family == DEF_UNSUPPORTED || pl.family == DEF_INVALID) return pl.status;
+  if (dw_eo_refused(pl)) return pl.status;
   DwfEoCoef co;
-  const unsigned need = pl.family == DEF_NOTHING ? 0u : (pieces & 3u);
-  if (int rc = dwf_eo_coef(d, Ls, mass_re, mass_im, wilson_coeff, need, &co)) return rc;
+  if (int rc = dwf_eo_coef(d, Ls, mass_re, mass_im, wilson_coeff, dw_eo_need(pl), &co)) return rc;
   if (pl.family == DEF_NOTHING) return QMG_SUCCESS;
   return eo_run(dtype, d, pl, co, 0, Ls, mass_re, mass_im, wilson_coeff, lhs, rhs, 0, pieces, alpha_re, alpha_im, 0, b, vec_stride, as_stream(stream));
 }
@@ -272,13 +262,12 @@ int qmg_dwf_hops_inv5(int dtype, const qmg_stencil_desc* d, const void* gauge, i
                       const void* rhs, unsigned pieces, double alpha_re, double alpha_im, unsigned flags, int nrhs, size_t vec_stride, unsigned mask, void* stream) {
   if (!gauge || !lhs || !rhs || !aligned16(gauge) || !aligned16(lhs) || !aligned16(rhs)) return QMG_ERR_INVALID;
   if (!std::isfinite(alpha_re) || !std::isfinite(alpha_im) || (flags & ~(unsigned)QMG_DWF_G5_IN)) return QMG_ERR_INVALID;
-  if (int rc = eo_valid(dtype, d, Ls, nrhs, vec_stride)) return rc;
+  if (int rc = dw_eo_valid(dtype, d, Ls, nrhs, vec_stride)) return rc;
   const BatchIdx b = expand_mask(mask, nrhs);
   const DwfEoPlan pl = dwf_eo_plan(dtype, d->Lx, d->Ly, Ls, DEK_HOPS_INV5, pieces, b.n, lhs == rhs);
-  if (pl.family == DEF_UNSUPPORTED || pl.family == DEF_INVALID) return pl.status;
+  if (dw_eo_refused(pl)) return pl.status;
   DwfEoCoef co;
-  const unsigned need = pl.family == DEF_NOTHING ? 0u : (pl.par_count == 2 ? 3u : 1u << pl.par_first);
-  if (int rc = dwf_eo_coef(d, Ls, mass_re, mass_im, wilson_coeff, need, &co)) return rc;
+  if (int rc = dwf_eo_coef(d, Ls, mass_re, mass_im, wilson_coeff, dw_eo_need(pl), &co)) return rc;
   if (pl.family == DEF_NOTHING) return QMG_SUCCESS;
   return eo_run(dtype, d, pl, co, gauge, Ls, mass_re, mass_im, wilson_coeff, lhs, rhs, 0, pieces, alpha_re, alpha_im, flags, b, vec_stride, as_stream(stream));
 }
@@ -287,22 +276,20 @@ int qmg_dwf_schur_apply(int dtype, const qmg_stencil_desc* d, const void* gauge,
                         const void* rhs, void* tmp, int parity, unsigned flags, int nrhs, size_t vec_stride, unsigned mask, void* stream) {
   if (!gauge || !lhs || !rhs || !tmp || !aligned16(gauge) || !aligned16(lhs) || !aligned16(rhs) || !aligned16(tmp)) return QMG_ERR_INVALID;
   if ((parity != 0 && parity != 1) || (flags & ~(unsigned)(QMG_DWF_G5_IN | QMG_DWF_G5_OUT)) || lhs == rhs || tmp == rhs || tmp == lhs) return QMG_ERR_INVALID;
-  if (int rc = eo_valid(dtype, d, Ls, nrhs, vec_stride)) return rc;
+  if (int rc = dw_eo_valid(dtype, d, Ls, nrhs, vec_stride)) return rc;
   const BatchIdx b = expand_mask(mask, nrhs);
-  const int p = parity, o = 1 - parity;
   // stage 1 (kernel K): tmp_o = -A_o^-1 H_{o,p} [Gamma5] rhs_p;  stage 2: lhs_p = [Gamma5] (A_p [Gamma5] rhs_p + H_{p,o} tmp_o)
-  const unsigned pieces1 = (o ? QMG_P_OE | QMG_P_ZERO_O : QMG_P_EO | QMG_P_ZERO_E);
-  const unsigned pieces2 = p ? (QMG_P_CLOVER_O | QMG_P_OE | QMG_P_SHIFT_O | QMG_P_ZERO_O) : (QMG_P_CLOVER_E | QMG_P_EO | QMG_P_SHIFT_E | QMG_P_ZERO_E);
-  const DwfEoPlan pl1 = dwf_eo_plan(dtype, d->Lx, d->Ly, Ls, DEK_HOPS_INV5, pieces1, b.n, 0);
-  const DwfEoPlan pl2 = dwf_eo_plan(dtype, d->Lx, d->Ly, Ls, DEK_SCHUR2, pieces2, b.n, 0);
-  if (pl1.family == DEF_UNSUPPORTED || pl1.family == DEF_INVALID) return pl1.status;
-  if (pl2.family == DEF_UNSUPPORTED || pl2.family == DEF_INVALID) return pl2.status;
+  const DwEoStages s = dw_eo_stages(parity);
+  const DwfEoPlan pl1 = dwf_eo_plan(dtype, d->Lx, d->Ly, Ls, DEK_HOPS_INV5, s.pieces1, b.n, 0);
+  const DwfEoPlan pl2 = dwf_eo_plan(dtype, d->Lx, d->Ly, Ls, DEK_SCHUR2, s.pieces2, b.n, 0);
+  if (dw_eo_refused(pl1)) return pl1.status;
+  if (dw_eo_refused(pl2)) return pl2.status;
   DwfEoCoef co;
   if (int rc = dwf_eo_coef(d, Ls, mass_re, mass_im, wilson_coeff, 3u, &co)) return rc;
   if (pl1.family == DEF_NOTHING || pl2.family == DEF_NOTHING) return QMG_SUCCESS;
   hipStream_t st = as_stream(stream);
-  if (int rc = eo_run(dtype, d, pl1, co, gauge, Ls, mass_re, mass_im, wilson_coeff, tmp, rhs, 0, pieces1, -1.0, 0.0, flags & QMG_DWF_G5_IN, b, vec_stride, st)) return rc;
-  return eo_run(dtype, d, pl2, co, gauge, Ls, mass_re, mass_im, wilson_coeff, lhs, rhs, tmp, pieces2, 1.0, 0.0, flags, b, vec_stride, st);
+  if (int rc = eo_run(dtype, d, pl1, co, gauge, Ls, mass_re, mass_im, wilson_coeff, tmp, rhs, 0, s.pieces1, -1.0, 0.0, flags & QMG_DWF_G5_IN, b, vec_stride, st)) return rc;
+  return eo_run(dtype, d, pl2, co, gauge, Ls, mass_re, mass_im, wilson_coeff, lhs, rhs, tmp, s.pieces2, 1.0, 0.0, flags, b, vec_stride, st);
 }
 
 }  // extern "C"

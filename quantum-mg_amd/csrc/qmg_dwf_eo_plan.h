@@ -1,6 +1,7 @@
 // qmg_dwf_eo_plan.h -- which launch serves a request to the even-odd domain-wall entry points (qmg_dwf_inv5, qmg_dwf_hops_inv5,
-// qmg_dwf_schur_apply): ONE host function (dwf_eo_plan) that the launches switch on and that qmg_dwf_eo_plan() exports, after
-// qmg_dwf_plan.h; and the fifth-dimension coefficients those kernels take by value (dwf_eo_coef).  Host code only, no HIP call.
+// qmg_dwf_schur_apply, and their Moebius namesakes through qmg_mobius_eo_plan.h): ONE host function (dw_eo_plan) that the launches of both
+// operators switch on and that qmg_dwf_eo_plan() / qmg_mobius_eo_plan() export, after qmg_dwf_plan.h; what the entries of both do around it;
+// and the fifth-dimension coefficients the Shamir kernels take by value (dwf_eo_coef).  Host code only, no HIP call.
 #ifndef QMG_DWF_EO_PLAN_H
 #define QMG_DWF_EO_PLAN_H
 
@@ -11,46 +12,64 @@
 
 namespace qmg {
 
-// the `kernel` argument of qmg_dwf_eo_plan()
+// the `kernel` argument of qmg_dwf_eo_plan(); qmg_mobius_eo_plan() has the same three and a fourth (MobiusEoKernel)
 enum DwfEoKernel {
   DEK_INV5 = 0,        // kernel I: lhs_p = alpha A_p^-1 rhs_p
   DEK_HOPS_INV5 = 1,   // kernel K: lhs_p (+)= alpha A_p^-1 H_{p,1-p} rhs_{1-p}
   DEK_SCHUR2 = 2       // second stage of M: lhs_p = A_p x_p + H_{p,1-p} t_{1-p}
 };
-// families (the values are part of qmg_dwf_eo_plan()'s output, include/qmg_hip.h)
-enum DwfEoFamily {
-  DEF_UNSUPPORTED = 0,   // the entry point returns QMG_ERR_UNSUPPORTED
-  DEF_HOPS_INV5 = 1,     // k_dwf_eo_inv5<T, true, ZERO, BATCH>
-  DEF_NOTHING = 2,       // success with nothing launched
-  DEF_INVALID = 3,       // the entry point returns QMG_ERR_INVALID
-  DEF_INV5 = 4,          // k_dwf_eo_inv5<T, false, true, BATCH>
-  DEF_SCHUR2 = 5         // k_dwf_eo_schur2<T, BATCH>
+// families (the values are part of qmg_dwf_eo_plan()'s and qmg_mobius_eo_plan()'s output, include/qmg_hip.h), under either operator's names
+enum DwEoFamily {
+  DEF_UNSUPPORTED = 0, MEF_UNSUPPORTED = 0,   // the entry point returns QMG_ERR_UNSUPPORTED
+  DEF_HOPS_INV5 = 1, MEF_HOPS_MIX = 1,        // k_dwf_eo_inv5<T, true, ZERO, BATCH>; k_mobius_eo_mix<T, true, RMIX, ZERO, BATCH>
+  DEF_NOTHING = 2, MEF_NOTHING = 2,           // success with nothing launched
+  DEF_INVALID = 3, MEF_INVALID = 3,           // the entry point returns QMG_ERR_INVALID
+  DEF_INV5 = 4, MEF_MIX = 4,                  // k_dwf_eo_inv5<T, false, true, BATCH>; k_mobius_eo_mix<T, false, false, true, BATCH>
+  DEF_SCHUR2 = 5, MEF_SCHUR2 = 5,             // k_dwf_eo_schur2<T, BATCH>; k_mobius_eo_schur2<T, BATCH>
+  MEF_SCHUR2_DAGGER = 6                       // k_mobius_eo_schur2_dagger<T, BATCH>
 };
-enum { DWF_EO_PLAN_INTS = 8 };
+// MEPF_RMIX: a flag next to DPF_ZERO / DPF_BATCH / DPF_F32 -- the hop source is mixed on the load (Moebius only)
+enum { DWF_EO_PLAN_INTS = DW_PLAN_INTS, MOBIUS_EO_PLAN_INTS = DW_PLAN_INTS, MEPF_RMIX = 8 };
 
-// The first DWF_EO_PLAN_INTS members, in this order, are what qmg_dwf_eo_plan() writes.
-struct DwfEoPlan {
-  int family;   // DwfEoFamily
+// The first DW_PLAN_INTS members, in this order, are what the two exports write (export_dw_plan).
+struct DwEoPlan {
+  int family;   // DwEoFamily
   int lps;      // lanes per site: Ls
-  int block;    // threads per block: Ls * floor(256 / Ls), so that the Ls lanes of a site never straddle a block (the exchange is in LDS)
+  int block;    // Ls * floor(256 / Ls) where the lanes of a site must not straddle a block (the exchange along s is in LDS), else 256
   int gx, gy;   // gx blocks cover the lps * Lx/2 lanes of a half row; gy = min(rows, 65535) blocks walk the (parity, y) rows
-  int flags;    // DPF_ZERO / DPF_BATCH / DPF_F32 (qmg_dwf_plan.h)
-  int lds;      // bytes of LDS per block: two buffers of one chunk per lane for kernels K and I, 0 for the second stage
+  int flags;    // DPF_ZERO / DPF_BATCH / DPF_F32 (qmg_dwf_plan.h) / MEPF_RMIX
+  int lds;      // bytes of LDS per block: two buffers of one chunk per lane, 0 for the second stage of M
   int nk;       // active systems served (all of them, in one launch)
   // ----
   int status;
   int par_first, par_count;
 };
+typedef DwEoPlan DwfEoPlan;
+typedef DwEoPlan MobiusEoPlan;
 
-// pieces: kernel I   QMG_P_CLOVER_E / _O name the parities;
-//         kernel K   all four hop bits of each processed parity (+ QMG_P_ZERO_*);
-//         stage 2    QMG_P_CLOVER_p | the four hops of p | QMG_P_SHIFT_p | QMG_P_ZERO_p of exactly one parity p.
-// n_active: the systems whose mask bit is set (0 .. 16); inplace: lhs == rhs
-inline DwfEoPlan dwf_eo_plan(int dtype, int Lx, int Ly, int Ls, int kernel, unsigned pieces, int n_active, int inplace) {
-  const auto refused = [](int status) { return plan_refused<DwfEoPlan>(status, DEF_INVALID, DEF_UNSUPPORTED); };
+// the pieces of the two launches of a Schur apply of parity p (o = 1 - p): kernel 1 writes tmp_o from rhs_p, the second stage writes lhs_p
+struct DwEoStages { unsigned pieces1, pieces2; };
+inline DwEoStages dw_eo_stages(int p) {
+  DwEoStages s;
+  s.pieces1 = p ? QMG_P_EO | QMG_P_ZERO_E : QMG_P_OE | QMG_P_ZERO_O;
+  s.pieces2 = p ? QMG_P_CLOVER_O | QMG_P_OE | QMG_P_SHIFT_O | QMG_P_ZERO_O : QMG_P_CLOVER_E | QMG_P_EO | QMG_P_SHIFT_E | QMG_P_ZERO_E;
+  return s;
+}
+
+// pieces: kernel 0   QMG_P_CLOVER_E / _O name the parities;
+//         kernel 1   all four hop bits of each processed parity (+ QMG_P_ZERO_*);
+//         kernel 2   QMG_P_CLOVER_p | the four hops of p | QMG_P_SHIFT_p | QMG_P_ZERO_p of exactly one parity p; kernel 3 (the second stage of
+//                    M^dagger, Moebius) takes kernel 2's.
+// n_active: the systems whose mask bit is set (0 .. 16); inplace: lhs == rhs.  What the operator brings: kernel_max, its highest kernel number;
+// rmix, whether a kernel-1 launch carries MEPF_RMIX; stage2_whole_sites, the block of kernel 2 -- Shamir's stage 2 runs whole-site blocks
+// (Ls floor(256 / Ls)) although it exchanges nothing in LDS, Moebius's runs 256.  That is the launch geometry the two kernels were written
+// and measured with: kept, not chosen here.
+inline DwEoPlan dw_eo_plan(int dtype, int Lx, int Ly, int Ls, int kernel, int kernel_max, unsigned pieces, int n_active, int inplace, bool rmix,
+                           bool stage2_whole_sites) {
+  const auto refused = [](int status) { return plan_refused<DwEoPlan>(status, DEF_INVALID, DEF_UNSUPPORTED); };
   if (!valid_dtype(dtype) || !dwf_dims_ok(Lx, Ly, Ls) || n_active < 0 || n_active > BATCH_MAX) return refused(QMG_ERR_INVALID);
-  if (kernel != DEK_INV5 && kernel != DEK_HOPS_INV5 && kernel != DEK_SCHUR2) return refused(QMG_ERR_INVALID);
-  if (n_active == 0 || pieces == 0) return plan_nothing<DwfEoPlan>(DEF_NOTHING);
+  if (kernel < DEK_INV5 || kernel > kernel_max) return refused(QMG_ERR_INVALID);
+  if (n_active == 0 || pieces == 0) return plan_nothing<DwEoPlan>(DEF_NOTHING);
   int par_first = 0, par_count = 0;
   bool zero = true;
   if (kernel == DEK_INV5) {
@@ -64,18 +83,18 @@ inline DwfEoPlan dwf_eo_plan(int dtype, int Lx, int Ly, int Ls, int kernel, unsi
     par_first = ps.par_first; par_count = ps.par_count; zero = ps.zero;
     if (inplace && par_count == 2) return refused(QMG_ERR_INVALID);   // in place: one parity written from the other
   } else {
-    const unsigned even = QMG_P_CLOVER_E | QMG_P_EO | QMG_P_SHIFT_E | QMG_P_ZERO_E, odd = QMG_P_CLOVER_O | QMG_P_OE | QMG_P_SHIFT_O | QMG_P_ZERO_O;
+    const unsigned even = dw_eo_stages(0).pieces2, odd = dw_eo_stages(1).pieces2;
     if (pieces != even && pieces != odd) return refused(QMG_ERR_UNSUPPORTED);
     if (inplace) return refused(QMG_ERR_INVALID);
     par_first = pieces == even ? 0 : 1; par_count = 1;
   }
-  const HalfRowGrid g = half_row_grid(Lx, Ls, (long)Ly * par_count, true);
+  const HalfRowGrid g = half_row_grid(Lx, Ls, (long)Ly * par_count, kernel != DEK_SCHUR2 || stage2_whole_sites);
   const int f32 = dtype == QMG_C32;
-  DwfEoPlan pl = {};
-  pl.family = kernel == DEK_INV5 ? DEF_INV5 : kernel == DEK_HOPS_INV5 ? DEF_HOPS_INV5 : DEF_SCHUR2;
+  DwEoPlan pl = {};
+  pl.family = kernel == DEK_INV5 ? DEF_INV5 : kernel == DEK_HOPS_INV5 ? DEF_HOPS_INV5 : kernel == DEK_SCHUR2 ? DEF_SCHUR2 : MEF_SCHUR2_DAGGER;
   pl.lps = Ls;
   pl.block = g.block; pl.gx = g.gx; pl.gy = g.gy;
-  pl.flags = (zero ? DPF_ZERO : 0) | (n_active > 1 ? DPF_BATCH : 0) | (f32 ? DPF_F32 : 0);
+  pl.flags = (zero ? DPF_ZERO : 0) | (n_active > 1 ? DPF_BATCH : 0) | (f32 ? DPF_F32 : 0) | (kernel == DEK_HOPS_INV5 && rmix ? MEPF_RMIX : 0);
   pl.lds = kernel == DEK_SCHUR2 ? 0 : 2 * DWF_BLOCK_MAX * (f32 ? 16 : 32);
   pl.nk = n_active;
   pl.status = QMG_SUCCESS;
@@ -83,6 +102,20 @@ inline DwfEoPlan dwf_eo_plan(int dtype, int Lx, int Ly, int Ls, int kernel, unsi
   pl.par_count = par_count;
   return pl;
 }
+inline DwfEoPlan dwf_eo_plan(int dtype, int Lx, int Ly, int Ls, int kernel, unsigned pieces, int n_active, int inplace) {
+  return dw_eo_plan(dtype, Lx, Ly, Ls, kernel, DEK_SCHUR2, pieces, n_active, inplace, false, true);
+}
+
+// ---- what the entries of both operators do around the plan ----
+// what every entry checks before the plan is asked
+inline int dw_eo_valid(int dtype, const qmg_stencil_desc* d, int Ls, int nrhs, size_t vec_stride) {
+  if (!d || d->nc != 2 * Ls) return QMG_ERR_INVALID;
+  return dwf_entry_check(dtype, d->Lx, d->Ly, Ls, nrhs, vec_stride);
+}
+// a plan that launches nothing and ends the entry with its status
+inline bool dw_eo_refused(const DwEoPlan& pl) { return pl.family == DEF_UNSUPPORTED || pl.family == DEF_INVALID; }
+// the `need` mask of a kernel-0 or kernel-1 request for the coefficients: bit p set when the site-local block of parity p is inverted
+inline unsigned dw_eo_need(const DwEoPlan& pl) { return pl.family == DEF_NOTHING ? 0u : (pl.par_count == 2 ? 3u : 1u << pl.par_first); }
 
 // ---- the site-local block A_p = d_p - (shift along s) + m (wall), d_p = 3 w + shift +- eo_shift, and what its inverse needs ----
 //   sigma 0:  g_s = sum_{s' <= s} d^-(s-s'+1) h_s',   y_s = g_s - q d^-(s+1) g_{Ls-1},   q = m / (1 + m d^-Ls);   sigma 1: mirrored in s

@@ -23,7 +23,7 @@ enum {
   DPF_BATCH = 2,   // more than one active system: the links stay in registers across the systems
   DPF_F32 = 4      // complex<float> storage and arithmetic
 };
-enum { DWF_PLAN_INTS = 8, DWF_LS_MIN = 2, DWF_LS_MAX = 32 };
+enum { DW_PLAN_INTS = 8, DWF_PLAN_INTS = DW_PLAN_INTS, DWF_LS_MIN = 2, DWF_LS_MAX = 32 };
 constexpr int DWF_BLOCK_MAX = BLOCK;   // the largest block of a domain-wall kernel (launch bounds, LDS sized per lane)
 
 // ---- what the four domain-wall plans (this one, qmg_dwf_eo_plan.h, qmg_dwf_meas_plan.h, qmg_hmc_dwf_plan.h) and their entries share ----
@@ -53,6 +53,14 @@ template <class Plan> inline Plan plan_nothing(int family) {
   Plan pl = {};
   pl.family = family;
   return pl;
+}
+// What qmg_dwf_plan(), qmg_dwf_eo_plan(), qmg_mobius_plan() and qmg_mobius_eo_plan() write: {family, lps, block, gx, gy, flags, slot6, nk}, where
+// slot6 is the plan's lds (its shape for qmg_dwf_plan()), then -1 beyond them.
+template <class Plan> inline int export_dw_plan(const Plan& pl, int slot6, int* plan_out, int plan_len) {
+  if (!plan_out || plan_len < DW_PLAN_INTS) return QMG_ERR_INVALID;
+  const int v[DW_PLAN_INTS] = {pl.family, pl.lps, pl.block, pl.gx, pl.gy, pl.flags, slot6, pl.nk};
+  export_plan_ints(v, DW_PLAN_INTS, plan_out, plan_len);
+  return QMG_SUCCESS;
 }
 // What every entry checks before its plan is asked: dtype, Ls, the systems of the call and, with more than one, the stride between them --
 // at least one five-dimensional vector (and, has4, one four-dimensional one), even in fp32 so that every system stays 16-byte aligned.

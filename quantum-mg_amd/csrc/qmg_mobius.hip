@@ -320,11 +320,8 @@ int qmg_mobius_fill(void* clover, void* hopping, const void* gauge, int Lx, int 
 }
 
 int qmg_mobius_plan(int dtype, int Lx, int Ly, int Ls, int op, unsigned pieces, int n_active, int inplace, int* plan_out, int plan_len) {
-  if (!plan_out || plan_len < MOBIUS_PLAN_INTS) return QMG_ERR_INVALID;
   const MobiusPlan pl = mobius_plan(dtype, Lx, Ly, Ls, op, pieces, n_active, inplace);
-  const int v[MOBIUS_PLAN_INTS] = {pl.family, pl.lps, pl.block, pl.gx, pl.gy, pl.flags, pl.lds, pl.nk};
-  export_plan_ints(v, MOBIUS_PLAN_INTS, plan_out, plan_len);
-  return QMG_SUCCESS;
+  return export_dw_plan(pl, pl.lds, plan_out, plan_len);
 }
 
 int qmg_mobius_apply_direct(int dtype, const qmg_stencil_desc* d, const void* gauge, int Ls, double mass_re, double mass_im, double wilson_coeff, double M5,

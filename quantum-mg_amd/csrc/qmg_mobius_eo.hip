@@ -300,12 +300,6 @@ static void launch_mobius_eo(const MobiusEoArgs<T>& a, const MobiusEoPlan& pl, h
   }
 }
 
-// what every entry checks before the plan is asked
-static int meo_valid(int dtype, const qmg_stencil_desc* d, int Ls, int nrhs, size_t vec_stride) {
-  if (!d || d->nc != 2 * Ls) return QMG_ERR_INVALID;
-  return dwf_entry_check(dtype, d->Lx, d->Ly, Ls, nrhs, vec_stride);
-}
-
 // one launch of a planned request
 template <typename T>
 static void meo_launch(const qmg_stencil_desc* d, const MobiusEoPlan& pl, const MobiusEoCoef& co, const void* gauge, int Ls, double w, void* lhs, const void* rhs,
@@ -340,23 +334,19 @@ extern "C" {
 
 int qmg_mobius_eo_plan(int dtype, int Lx, int Ly, int Ls, int kernel, unsigned pieces, int table, int source, int n_active, int inplace, int* plan_out,
                        int plan_len) {
-  if (!plan_out || plan_len < MOBIUS_EO_PLAN_INTS) return QMG_ERR_INVALID;
   const MobiusEoPlan pl = mobius_eo_plan(dtype, Lx, Ly, Ls, kernel, pieces, table, source, n_active, inplace);
-  const int v[MOBIUS_EO_PLAN_INTS] = {pl.family, pl.lps, pl.block, pl.gx, pl.gy, pl.flags, pl.lds, pl.nk};
-  export_plan_ints(v, MOBIUS_EO_PLAN_INTS, plan_out, plan_len);
-  return QMG_SUCCESS;
+  return export_dw_plan(pl, pl.lds, plan_out, plan_len);
 }
 
 int qmg_mobius_inv5(int dtype, const qmg_stencil_desc* d, int Ls, double mass_re, double mass_im, double wilson_coeff, double M5, double b5, double c5, void* lhs,
                     const void* rhs, unsigned pieces, int table, double scale_re, double scale_im, int nrhs, size_t vec_stride, unsigned mask, void* stream) {
   if (!lhs || !rhs || !aligned16(lhs) || !aligned16(rhs) || !std::isfinite(scale_re) || !std::isfinite(scale_im)) return QMG_ERR_INVALID;
-  if (int rc = meo_valid(dtype, d, Ls, nrhs, vec_stride)) return rc;
+  if (int rc = dw_eo_valid(dtype, d, Ls, nrhs, vec_stride)) return rc;
   const BatchIdx b = expand_mask(mask, nrhs);
   const MobiusEoPlan pl = mobius_eo_plan(dtype, d->Lx, d->Ly, Ls, MEK_INV5, pieces, table, MES_ONE, b.n, lhs == rhs);
-  if (pl.family == MEF_UNSUPPORTED || pl.family == MEF_INVALID) return pl.status;
+  if (dw_eo_refused(pl)) return pl.status;
   MobiusEoCoef co;
-  const unsigned need = pl.family == MEF_NOTHING ? 0u : (pieces & 3u);
-  if (int rc = mobius_eo_coef(d, Ls, mass_re, mass_im, wilson_coeff, M5, b5, c5, false, table, need, &co)) return rc;
+  if (int rc = mobius_eo_coef(d, Ls, mass_re, mass_im, wilson_coeff, M5, b5, c5, false, table, dw_eo_need(pl), &co)) return rc;
   if (pl.family == MEF_NOTHING) return QMG_SUCCESS;
   return meo_run(dtype, d, pl, co, 0, Ls, wilson_coeff, lhs, rhs, 0, pieces, scale_re, scale_im, 0, b, vec_stride, as_stream(stream));
 }
@@ -366,13 +356,12 @@ int qmg_mobius_hops_inv5(int dtype, const qmg_stencil_desc* d, const void* gauge
                          size_t vec_stride, unsigned mask, void* stream) {
   if (!gauge || !lhs || !rhs || !aligned16(gauge) || !aligned16(lhs) || !aligned16(rhs)) return QMG_ERR_INVALID;
   if (!std::isfinite(scale_re) || !std::isfinite(scale_im) || (flags & ~(unsigned)QMG_DWF_G5_IN)) return QMG_ERR_INVALID;
-  if (int rc = meo_valid(dtype, d, Ls, nrhs, vec_stride)) return rc;
+  if (int rc = dw_eo_valid(dtype, d, Ls, nrhs, vec_stride)) return rc;
   const BatchIdx b = expand_mask(mask, nrhs);
   const MobiusEoPlan pl = mobius_eo_plan(dtype, d->Lx, d->Ly, Ls, MEK_HOPS_INV5, pieces, table, source, b.n, lhs == rhs);
-  if (pl.family == MEF_UNSUPPORTED || pl.family == MEF_INVALID) return pl.status;
+  if (dw_eo_refused(pl)) return pl.status;
   MobiusEoCoef co;
-  const unsigned need = pl.family == MEF_NOTHING ? 0u : (pl.par_count == 2 ? 3u : 1u << pl.par_first);
-  if (int rc = mobius_eo_coef(d, Ls, mass_re, mass_im, wilson_coeff, M5, b5, c5, false, table, need, &co)) return rc;
+  if (int rc = mobius_eo_coef(d, Ls, mass_re, mass_im, wilson_coeff, M5, b5, c5, false, table, dw_eo_need(pl), &co)) return rc;
   if (pl.family == MEF_NOTHING) return QMG_SUCCESS;
   return meo_run(dtype, d, pl, co, gauge, Ls, wilson_coeff, lhs, rhs, 0, pieces, scale_re, scale_im, flags, b, vec_stride, as_stream(stream));
 }
@@ -382,25 +371,23 @@ int qmg_mobius_schur_apply(int dtype, const qmg_stencil_desc* d, const void* gau
                            void* stream) {
   if (!gauge || !lhs || !rhs || !tmp || !aligned16(gauge) || !aligned16(lhs) || !aligned16(rhs) || !aligned16(tmp)) return QMG_ERR_INVALID;
   if ((parity != 0 && parity != 1) || (op != MOP_D && op != MOP_DAGGER) || lhs == rhs || tmp == rhs || tmp == lhs) return QMG_ERR_INVALID;
-  if (int rc = meo_valid(dtype, d, Ls, nrhs, vec_stride)) return rc;
+  if (int rc = dw_eo_valid(dtype, d, Ls, nrhs, vec_stride)) return rc;
   const BatchIdx b = expand_mask(mask, nrhs);
-  const int p = parity, o = 1 - parity;
   const bool dag = op == MOP_DAGGER;
   // M:        stage 1  tmp_o = -A_o^-1 H_{o,p} (B rhs_p);               stage 2  lhs_p = A_p rhs_p + H_{p,o} (B tmp_o)
   // M^dagger: stage 1  tmp_o = -(A'_o^-1 B') H_{o,p} (Gamma5 rhs_p);    stage 2  lhs_p = Gamma5 [A'_p Gamma5 rhs_p + B' (H_{p,o} tmp_o)]
-  const unsigned pieces1 = (o ? QMG_P_OE | QMG_P_ZERO_O : QMG_P_EO | QMG_P_ZERO_E);
-  const unsigned pieces2 = p ? (QMG_P_CLOVER_O | QMG_P_OE | QMG_P_SHIFT_O | QMG_P_ZERO_O) : (QMG_P_CLOVER_E | QMG_P_EO | QMG_P_SHIFT_E | QMG_P_ZERO_E);
+  const DwEoStages s = dw_eo_stages(parity);
   const int table = dag ? MET_AINV_B : MET_AINV;
-  const MobiusEoPlan pl1 = mobius_eo_plan(dtype, d->Lx, d->Ly, Ls, MEK_HOPS_INV5, pieces1, table, dag ? MES_ONE : MES_B, b.n, 0);
-  const MobiusEoPlan pl2 = mobius_eo_plan(dtype, d->Lx, d->Ly, Ls, dag ? MEK_SCHUR2_DAGGER : MEK_SCHUR2, pieces2, MET_ONE, MES_ONE, b.n, 0);
-  if (pl1.family == MEF_UNSUPPORTED || pl1.family == MEF_INVALID) return pl1.status;
-  if (pl2.family == MEF_UNSUPPORTED || pl2.family == MEF_INVALID) return pl2.status;
+  const MobiusEoPlan pl1 = mobius_eo_plan(dtype, d->Lx, d->Ly, Ls, MEK_HOPS_INV5, s.pieces1, table, dag ? MES_ONE : MES_B, b.n, 0);
+  const MobiusEoPlan pl2 = mobius_eo_plan(dtype, d->Lx, d->Ly, Ls, dag ? MEK_SCHUR2_DAGGER : MEK_SCHUR2, s.pieces2, MET_ONE, MES_ONE, b.n, 0);
+  if (dw_eo_refused(pl1)) return pl1.status;
+  if (dw_eo_refused(pl2)) return pl2.status;
   MobiusEoCoef co;
-  if (int rc = mobius_eo_coef(d, Ls, mass_re, mass_im, wilson_coeff, M5, b5, c5, dag, table, 1u << o, &co)) return rc;
+  if (int rc = mobius_eo_coef(d, Ls, mass_re, mass_im, wilson_coeff, M5, b5, c5, dag, table, 1u << (1 - parity), &co)) return rc;
   if (pl1.family == MEF_NOTHING || pl2.family == MEF_NOTHING) return QMG_SUCCESS;
   hipStream_t st = as_stream(stream);
-  if (int rc = meo_run(dtype, d, pl1, co, gauge, Ls, wilson_coeff, tmp, rhs, 0, pieces1, -1.0, 0.0, dag ? QMG_DWF_G5_IN : 0u, b, vec_stride, st)) return rc;
-  return meo_run(dtype, d, pl2, co, gauge, Ls, wilson_coeff, lhs, rhs, tmp, pieces2, 1.0, 0.0, 0u, b, vec_stride, st);
+  if (int rc = meo_run(dtype, d, pl1, co, gauge, Ls, wilson_coeff, tmp, rhs, 0, s.pieces1, -1.0, 0.0, dag ? QMG_DWF_G5_IN : 0u, b, vec_stride, st)) return rc;
+  return meo_run(dtype, d, pl2, co, gauge, Ls, wilson_coeff, lhs, rhs, tmp, s.pieces2, 1.0, 0.0, 0u, b, vec_stride, st);
 }
 
 }  // extern "C"

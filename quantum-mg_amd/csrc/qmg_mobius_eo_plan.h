@@ -1,12 +1,14 @@
 // qmg_mobius_eo_plan.h -- which launch serves a request to the even-odd Moebius entry points (qmg_mobius_inv5, qmg_mobius_hops_inv5,
-// qmg_mobius_schur_apply): ONE host function (mobius_eo_plan) that the launches switch on and that qmg_mobius_eo_plan() exports, after
-// qmg_dwf_eo_plan.h; and the twisted-circulant tables those kernels take by value (mobius_eo_coef).  Host code only, no HIP call.
+// qmg_mobius_schur_apply): mobius_eo_plan, which the launches switch on and qmg_mobius_eo_plan() exports, is dw_eo_plan (qmg_dwf_eo_plan.h, with the
+// plan, its families and flags) with a fourth kernel and the table / source arguments; and the twisted-circulant tables those kernels take by
+// value (mobius_eo_coef).  Host code only, no HIP call.
 #ifndef QMG_MOBIUS_EO_PLAN_H
 #define QMG_MOBIUS_EO_PLAN_H
 
 #include <cmath>
 #include <complex>
 
+#include "qmg_dwf_eo_plan.h"
 #include "qmg_mobius_plan.h"
 
 namespace qmg {
@@ -21,73 +23,14 @@ enum MobiusEoKernel {
 // the site matrix S applied to the hop sum (or to the own chunk) through LDS, and the matrix R applied to the hop source on the load
 enum MobiusEoTable { MET_ONE = 0, MET_AINV = 1, MET_AINV_B = 2 };
 enum MobiusEoSource { MES_ONE = 0, MES_B = 1 };
-// families (the values are part of qmg_mobius_eo_plan()'s output, include/qmg_hip.h)
-enum MobiusEoFamily {
-  MEF_UNSUPPORTED = 0,     // the entry point returns QMG_ERR_UNSUPPORTED
-  MEF_HOPS_MIX = 1,        // k_mobius_eo_mix<T, true, RMIX, ZERO, BATCH>
-  MEF_NOTHING = 2,         // success with nothing launched
-  MEF_INVALID = 3,         // the entry point returns QMG_ERR_INVALID
-  MEF_MIX = 4,             // k_mobius_eo_mix<T, false, false, true, BATCH>
-  MEF_SCHUR2 = 5,          // k_mobius_eo_schur2<T, BATCH>
-  MEF_SCHUR2_DAGGER = 6    // k_mobius_eo_schur2_dagger<T, BATCH>
-};
-enum { MOBIUS_EO_PLAN_INTS = 8, MEPF_RMIX = 8 };   // MEPF_RMIX: a flag next to DPF_ZERO / DPF_BATCH / DPF_F32 -- the hop source is mixed on the load
 
-// The first MOBIUS_EO_PLAN_INTS members, in this order, are what qmg_mobius_eo_plan() writes (the layout of DwfEoPlan).
-struct MobiusEoPlan {
-  int family;   // MobiusEoFamily
-  int lps;      // lanes per site: Ls
-  int block;    // Ls * floor(256 / Ls) where the kernel exchanges along s in LDS (whole sites), 256 for the second stage of M
-  int gx, gy;   // gx blocks cover the lps * Lx/2 lanes of a half row; gy = min(rows, 65535) blocks walk the (parity, y) rows
-  int flags;    // DPF_ZERO / DPF_BATCH / DPF_F32 (qmg_dwf_plan.h) / MEPF_RMIX
-  int lds;      // bytes of LDS per block: two buffers of one chunk per lane, 0 for the second stage of M
-  int nk;       // active systems served (all of them, in one launch)
-  // ----
-  int status;
-  int par_first, par_count;
-};
-
-// pieces: as dwf_eo_plan's for kernels 0, 1 and 2; kernel 3 takes kernel 2's.  table: MobiusEoTable (kernel 0: not MET_ONE; kernels 2, 3: ignored);
-// source: MobiusEoSource (kernel 1 only).  n_active: the systems whose mask bit is set (0 .. 16); inplace: lhs == rhs
+// pieces, n_active, inplace: dw_eo_plan's.  table: MobiusEoTable (kernel 0: not MET_ONE; kernels 2, 3: ignored); source: MobiusEoSource (kernel 1
+// only).  A table or source out of range is INVALID like every refusal dw_eo_plan makes before it looks at the pieces, so it is made here.
 inline MobiusEoPlan mobius_eo_plan(int dtype, int Lx, int Ly, int Ls, int kernel, unsigned pieces, int table, int source, int n_active, int inplace) {
-  const auto refused = [](int status) { return plan_refused<MobiusEoPlan>(status, MEF_INVALID, MEF_UNSUPPORTED); };
-  if (!valid_dtype(dtype) || !dwf_dims_ok(Lx, Ly, Ls) || n_active < 0 || n_active > BATCH_MAX) return refused(QMG_ERR_INVALID);
-  if (kernel < MEK_INV5 || kernel > MEK_SCHUR2_DAGGER) return refused(QMG_ERR_INVALID);
-  if (kernel == MEK_INV5 && table != MET_AINV && table != MET_AINV_B) return refused(QMG_ERR_INVALID);
-  if (kernel == MEK_HOPS_INV5 && (table < MET_ONE || table > MET_AINV_B || (source != MES_ONE && source != MES_B))) return refused(QMG_ERR_INVALID);
-  if (n_active == 0 || pieces == 0) return plan_nothing<MobiusEoPlan>(MEF_NOTHING);
-  int par_first = 0, par_count = 0;
-  bool zero = true;
-  if (kernel == MEK_INV5) {
-    if (pieces & ~(unsigned)QMG_P_CLOVER) return refused(QMG_ERR_UNSUPPORTED);
-    const bool ev = pieces & QMG_P_CLOVER_E, od = pieces & QMG_P_CLOVER_O;
-    par_first = ev ? 0 : 1; par_count = (ev && od) ? 2 : 1;
-  } else if (kernel == MEK_HOPS_INV5) {
-    if (pieces & (QMG_P_CLOVER | QMG_P_SHIFT)) return refused(QMG_ERR_UNSUPPORTED);
-    const PieceShape ps = links_piece_shape(pieces);   // no clover or shift bit is left: a parity is named by its hop or zero bits
-    if (ps.shape != 2) return refused(QMG_ERR_UNSUPPORTED);   // a partial hop set
-    par_first = ps.par_first; par_count = ps.par_count; zero = ps.zero;
-    if (inplace && par_count == 2) return refused(QMG_ERR_INVALID);   // in place: one parity written from the other
-  } else {
-    const unsigned even = QMG_P_CLOVER_E | QMG_P_EO | QMG_P_SHIFT_E | QMG_P_ZERO_E, odd = QMG_P_CLOVER_O | QMG_P_OE | QMG_P_SHIFT_O | QMG_P_ZERO_O;
-    if (pieces != even && pieces != odd) return refused(QMG_ERR_UNSUPPORTED);
-    if (inplace) return refused(QMG_ERR_INVALID);
-    par_first = pieces == even ? 0 : 1; par_count = 1;
-  }
-  const bool lds = kernel != MEK_SCHUR2;
-  const HalfRowGrid g = half_row_grid(Lx, Ls, (long)Ly * par_count, lds);
-  const int f32 = dtype == QMG_C32;
-  MobiusEoPlan pl = {};
-  pl.family = kernel == MEK_INV5 ? MEF_MIX : kernel == MEK_HOPS_INV5 ? MEF_HOPS_MIX : kernel == MEK_SCHUR2 ? MEF_SCHUR2 : MEF_SCHUR2_DAGGER;
-  pl.lps = Ls;
-  pl.block = g.block; pl.gx = g.gx; pl.gy = g.gy;
-  pl.flags = (zero ? DPF_ZERO : 0) | (n_active > 1 ? DPF_BATCH : 0) | (f32 ? DPF_F32 : 0) | (kernel == MEK_HOPS_INV5 && source == MES_B ? MEPF_RMIX : 0);
-  pl.lds = lds ? 2 * DWF_BLOCK_MAX * (f32 ? 16 : 32) : 0;
-  pl.nk = n_active;
-  pl.status = QMG_SUCCESS;
-  pl.par_first = par_first;
-  pl.par_count = par_count;
-  return pl;
+  const bool bad = (kernel == MEK_INV5 && table != MET_AINV && table != MET_AINV_B) ||
+                   (kernel == MEK_HOPS_INV5 && (table < MET_ONE || table > MET_AINV_B || (source != MES_ONE && source != MES_B)));
+  if (bad) return plan_refused<MobiusEoPlan>(QMG_ERR_INVALID, MEF_INVALID, MEF_UNSUPPORTED);
+  return dw_eo_plan(dtype, Lx, Ly, Ls, kernel, MEK_SCHUR2_DAGGER, pieces, n_active, inplace, source == MES_B, false);
 }
 
 // ---- the site-local blocks as twisted circulants ----

@@ -20,9 +20,9 @@ enum MobiusFamily {
   MF_INVALID = 3,       // the entry point returns QMG_ERR_INVALID
   MF_RESULT = 4         // k_mobius_result<T, ZERO, BATCH>: D^dagger, the hop sum mixed along s in LDS
 };
-enum { MOBIUS_PLAN_INTS = 8 };
+enum { MOBIUS_PLAN_INTS = DW_PLAN_INTS };
 
-// The first MOBIUS_PLAN_INTS members, in this order, are what qmg_mobius_plan() writes (the layout of DwfEoPlan).
+// The first MOBIUS_PLAN_INTS members, in this order, are what qmg_mobius_plan() writes (export_dw_plan; the layout of DwEoPlan).
 struct MobiusPlan {
   int family;   // MobiusFamily
   int lps;      // lanes per site: Ls

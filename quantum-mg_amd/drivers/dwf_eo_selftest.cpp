@@ -17,22 +17,14 @@
 //                          and (d) is not printed.
 // With `rounds` the two solves of (c) and (d) are then timed alternately, wall clock around each (tools/dwf_eo_bench.py): one line
 // `[QMG-DWF-EO-BENCH] round r eo_ms t full_ms t` per round.  The dagger stencil and D^dagger b are made before the clock starts.
-#include <chrono>
-#include <cmath>
 #include <iomanip>
-#include <iostream>
 #include <string>
 
-#include "../include/qmg/qmg.hpp"
-#include "driver_common.hpp"
+#include "dw_selftest_common.hpp"
 
 using namespace std;
 
-static bool all_pass = true;
-static void line(const char* name, double value, bool pass) {
-  cout << "[QMG-DWF-EO] " << name << " " << value << " " << (pass ? "PASS" : "FAIL") << "\n";
-  if (!pass) all_pass = false;
-}
+static dw_selftest::Lines line("[QMG-DWF-EO]");
 
 int main(int argc, char** argv) {
   qmg_driver::Guard guard;
@@ -44,7 +36,8 @@ int main(int argc, char** argv) {
   const double mass = stod(argv[3]);
   const unsigned long long seed = stoull(argv[4]);
   Lattice2D lat_g(L, L, 1), lat(L, L, 2 * Ls);
-  complex<double>* gauge = allocate_vector<complex<double>>(lat_g.get_size_gauge());
+  dw_selftest::Vectors vec;
+  complex<double>* gauge = vec.make(lat_g.get_size_gauge());
   // link phases N(0, 0.4^2)
   if (!qmg::ok(qmg_u1_gauss_gauge(gauge, L, L, 1.0 / (0.4 * 0.4), seed, qmg::current_stream()), "qmg_u1_gauss_gauge")) return 3;
   // Ls = 32 (nc = 64) is beyond the stored-stencil apply, so createDwfLs declines it; the links route and the Schur methods do not need it
@@ -53,14 +46,7 @@ int main(int argc, char** argv) {
   DwfBase* dwf = dynamic_cast<DwfBase*>(made);
   if (!dwf || !dwf->generated) { cout << "[QMG-DWF-EO] create 0 FAIL\n"; return 4; }
   const int n = (int)lat.get_size_cv_l(), half = n / 2;
-  complex<double>* x = allocate_vector<complex<double>>(n);
-  complex<double>* y = allocate_vector<complex<double>>(n);
-  complex<double>* v = allocate_vector<complex<double>>(n);
-  complex<double>* t1 = allocate_vector<complex<double>>(n);
-  complex<double>* t2 = allocate_vector<complex<double>>(n);
-  complex<double>* b = allocate_vector<complex<double>>(n);
-  complex<double>* xe = allocate_vector<complex<double>>(n);
-  complex<double>* xf = allocate_vector<complex<double>>(n);
+  complex<double>*x = vec.make(n), *y = vec.make(n), *v = vec.make(n), *t1 = vec.make(n), *t2 = vec.make(n), *b = vec.make(n), *xe = vec.make(n), *xf = vec.make(n);
   gaussian(x, n, seed + 101);
   gaussian(y, n, seed + 102);
   gaussian(b, n, seed + 200);
@@ -91,25 +77,18 @@ int main(int argc, char** argv) {
   const double eps = 1e-10;
   zero_vector(xe, n);
   const inversion_info eo = minv_dwf_eo_cg(xe, b, max_iter, eps, dwf);
-  dwf->apply_M_overwrite(t1, xe);
   const double bnorm = norm2sq(b, n);
-  const double eo_res = sqrt(diffnorm2sq(t1, b, n) / bnorm);
+  const double eo_res = dw_selftest::true_residual(dwf, t1, xe, b, n, bnorm);
 
   inversion_info full = eo;
   double full_res = 0.0, sol_diff = 0.0, eps_full = eps;
+  const auto full_solve = [&](complex<double>* sol, double tol) { return minv_vector_cg(sol, t2, n, max_iter, tol, apply_stencil_2D_M_dagger_M, (void*)dwf); };
   if (stored) {
     qmg_driver::phase("full cg");
     dwf->build_dagger_stencil();
     zero_vector(t2, n);
     dwf->apply_M_dagger(t2, b);                                      // the right-hand side of the normal equations
-    for (int attempt = 0; attempt < 10; attempt++) {
-      zero_vector(xf, n);
-      full = minv_vector_cg(xf, t2, n, max_iter, eps_full, apply_stencil_2D_M_dagger_M, (void*)dwf);
-      dwf->apply_M_overwrite(t1, xf);
-      full_res = sqrt(diffnorm2sq(t1, b, n) / bnorm);
-      if (full_res <= eo_res && full_res >= 0.5 * eo_res) break;
-      eps_full *= 0.75 * eo_res / full_res;
-    }
+    full = dw_selftest::tightened_solve(dwf, xf, t1, b, n, bnorm, eo_res, eps_full, full_res, full_solve);
     sol_diff = sqrt(diffnorm2sq(xe, xf, n) / norm2sq(xf, n));
   }
 
@@ -125,25 +104,12 @@ int main(int argc, char** argv) {
     line("eo_vs_full_solution", sol_diff, sol_diff <= 1e-7);
   }
 
-  if (stored && rounds > 0) {
-    qmg_driver::phase("timing");
-    auto wall_ms = [&](complex<double>* sol, bool even_odd) -> double {
-      zero_vector(sol, n);
-      qmg_stream_sync(qmg::current_stream());
-      const auto t0 = chrono::steady_clock::now();
-      if (even_odd) minv_dwf_eo_cg(sol, b, max_iter, eps, dwf);
-      else minv_vector_cg(sol, t2, n, max_iter, eps_full, apply_stencil_2D_M_dagger_M, (void*)dwf);
-      qmg_stream_sync(qmg::current_stream());
-      return chrono::duration<double, milli>(chrono::steady_clock::now() - t0).count();
-    };
-    for (int r = 0; r < rounds; r++) {
-      const double te = wall_ms(xe, true), tf = wall_ms(xf, false);
-      cout << "[QMG-DWF-EO-BENCH] round " << r << " eo_ms " << te << " full_ms " << tf << "\n";
-    }
-  }
+  if (stored && rounds > 0)
+    dw_selftest::timing_rounds("[QMG-DWF-EO-BENCH]", rounds, n, xe, xf, [&](complex<double>* sol) { minv_dwf_eo_cg(sol, b, max_iter, eps, dwf); },
+                               [&](complex<double>* sol) { full_solve(sol, eps_full); });
 
   delete made;
-  for (complex<double>** p : {&x, &y, &v, &t1, &t2, &b, &xe, &xf, &gauge}) deallocate_vector(p);
+  vec.release();
   qmg::VecPool::release_all();
-  return qmg_driver::leave(all_pass ? 0 : 1);
+  return qmg_driver::leave(line.all_pass ? 0 : 1);
 }

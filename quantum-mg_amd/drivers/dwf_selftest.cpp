@@ -10,22 +10,14 @@
 //   (d) cg_iterations, cg_true_residual   CG on M^dagger M (apply_stencil_2D_M_dagger_M) to 1e-10; the recomputed |b - D^dag D x| / |b| <= 1e-9.
 //   (e) batch_iterations, batch_residual  the same solve as a batch of 3 through the batch engine: every system takes the iterations and
 //                          reaches the residual of its single solve (the batch kernels' per-system arithmetic is the single-vector one).
-#include <cmath>
 #include <iomanip>
-#include <iostream>
 #include <string>
-#include <vector>
 
-#include "../include/qmg/qmg.hpp"
-#include "driver_common.hpp"
+#include "dw_selftest_common.hpp"
 
 using namespace std;
 
-static bool all_pass = true;
-static void line(const char* name, double value, bool pass) {
-  cout << "[QMG-DWF] " << name << " " << value << " " << (pass ? "PASS" : "FAIL") << "\n";
-  if (!pass) all_pass = false;
-}
+static dw_selftest::Lines line("[QMG-DWF]");
 
 int main(int argc, char** argv) {
   qmg_driver::Guard guard;
@@ -36,22 +28,16 @@ int main(int argc, char** argv) {
   const double mass = stod(argv[3]);
   const unsigned long long seed = stoull(argv[4]);
   Lattice2D lat_g(L, L, 1), lat(L, L, 2 * Ls);
-  complex<double>* gauge = allocate_vector<complex<double>>(lat_g.get_size_gauge());
+  dw_selftest::Vectors vec;
+  complex<double>* gauge = vec.make(lat_g.get_size_gauge());
   // link phases N(0, 0.4^2)
   if (!qmg::ok(qmg_u1_gauss_gauge(gauge, L, L, 1.0 / (0.4 * 0.4), seed, qmg::current_stream()), "qmg_u1_gauss_gauge")) return 3;
   Stencil2D* dwf = createDwfLs(&lat, mass, gauge, Ls);
   if (!dwf || !dwf->generated) { cout << "[QMG-DWF] create 0 FAIL\n"; return 4; }
   const int n = (int)lat.get_size_cv_l();
   const int nsys = 3;
-  complex<double>* x = allocate_vector<complex<double>>(n);
-  complex<double>* y = allocate_vector<complex<double>>(n);
-  complex<double>* t1 = allocate_vector<complex<double>>(n);
-  complex<double>* t2 = allocate_vector<complex<double>>(n);
-  complex<double>* g5dg5x = allocate_vector<complex<double>>(n);
-  complex<double>* Dx_direct = allocate_vector<complex<double>>(n);
-  complex<double>* B = allocate_vector<complex<double>>((size_t)nsys * n);
-  complex<double>* X = allocate_vector<complex<double>>((size_t)nsys * n);
-  complex<double>* X1 = allocate_vector<complex<double>>(n);
+  complex<double>*x = vec.make(n), *y = vec.make(n), *t1 = vec.make(n), *t2 = vec.make(n), *g5dg5x = vec.make(n), *Dx_direct = vec.make(n);
+  complex<double>*B = vec.make((size_t)nsys * n), *X = vec.make((size_t)nsys * n), *X1 = vec.make(n);
   gaussian(x, n, seed + 101);
   gaussian(y, n, seed + 102);
 
@@ -121,8 +107,7 @@ int main(int argc, char** argv) {
   line("batch_residual", res_diff, res_diff == 0.0 && batch_true <= 1e-9);
 
   delete dwf;
-  deallocate_vector(&x); deallocate_vector(&y); deallocate_vector(&t1); deallocate_vector(&t2); deallocate_vector(&g5dg5x); deallocate_vector(&Dx_direct);
-  deallocate_vector(&B); deallocate_vector(&X); deallocate_vector(&X1); deallocate_vector(&gauge);
+  vec.release();
   qmg::VecPool::release_all();
-  return qmg_driver::leave(all_pass ? 0 : 1);
+  return qmg_driver::leave(line.all_pass ? 0 : 1);
 }

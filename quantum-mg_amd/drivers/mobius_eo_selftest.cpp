@@ -16,24 +16,14 @@
 // With `rounds` > 0 the two solves of (c) and (d) are then timed alternately, wall clock around each (tools/mobius_eo_bench.py): one line
 // `[QMG-MOBIUS-EO-BENCH] round r eo_ms t full_ms t` per round.  With a solution_file the links, b and the even-odd solution are written there
 // as raw complex<double> (2 L^2, then twice 2 Ls L^2 numbers in the device layout), for a dense solve elsewhere.
-#include <chrono>
-#include <cmath>
-#include <cstdio>
 #include <iomanip>
-#include <iostream>
 #include <string>
-#include <vector>
 
-#include "../include/qmg/qmg.hpp"
-#include "driver_common.hpp"
+#include "dw_selftest_common.hpp"
 
 using namespace std;
 
-static bool all_pass = true;
-static void line(const char* name, double value, bool pass) {
-  cout << "[QMG-MOBIUS-EO] " << name << " " << value << " " << (pass ? "PASS" : "FAIL") << "\n";
-  if (!pass) all_pass = false;
-}
+static dw_selftest::Lines line("[QMG-MOBIUS-EO]");
 
 int main(int argc, char** argv) {
   qmg_driver::Guard guard;
@@ -45,20 +35,14 @@ int main(int argc, char** argv) {
   const double mass = stod(argv[3]), b5 = 1.5, c5 = 0.5;
   const unsigned long long seed = stoull(argv[4]);
   Lattice2D lat_g(L, L, 1), lat(L, L, 2 * Ls);
-  complex<double>* gauge = allocate_vector<complex<double>>(lat_g.get_size_gauge());
+  dw_selftest::Vectors vec;
+  complex<double>* gauge = vec.make(lat_g.get_size_gauge());
   // link phases N(0, 0.4^2)
   if (!qmg::ok(qmg_u1_gauss_gauge(gauge, L, L, 1.0 / (0.4 * 0.4), seed, qmg::current_stream()), "qmg_u1_gauss_gauge")) return 3;
   MobiusBase* mob = createMobiusLs(&lat, mass, gauge, Ls, b5, c5);
   if (!mob || !mob->generated) { cout << "[QMG-MOBIUS-EO] create 0 FAIL\n"; return 4; }
   const int n = (int)lat.get_size_cv_l(), half = n / 2;
-  complex<double>* x = allocate_vector<complex<double>>(n);
-  complex<double>* y = allocate_vector<complex<double>>(n);
-  complex<double>* v = allocate_vector<complex<double>>(n);
-  complex<double>* t1 = allocate_vector<complex<double>>(n);
-  complex<double>* t2 = allocate_vector<complex<double>>(n);
-  complex<double>* b = allocate_vector<complex<double>>(n);
-  complex<double>* xe = allocate_vector<complex<double>>(n);
-  complex<double>* xf = allocate_vector<complex<double>>(n);
+  complex<double>*x = vec.make(n), *y = vec.make(n), *v = vec.make(n), *t1 = vec.make(n), *t2 = vec.make(n), *b = vec.make(n), *xe = vec.make(n), *xf = vec.make(n);
   gaussian(x, n, seed + 101);
   gaussian(y, n, seed + 102);
   gaussian(b, n, seed + 200);
@@ -84,34 +68,18 @@ int main(int argc, char** argv) {
   const double eps = 1e-10;
   zero_vector(xe, n);
   const inversion_info eo = minv_mobius_eo_cg(xe, b, max_iter, eps, mob);
-  mob->apply_M_overwrite(t1, xe);
   const double bnorm = norm2sq(b, n);
-  const double eo_res = sqrt(diffnorm2sq(t1, b, n) / bnorm);
+  const double eo_res = dw_selftest::true_residual(mob, t1, xe, b, n, bnorm);
   if (argc > 6) {
-    FILE* f = fopen(argv[6], "wb");
-    bool written = f != nullptr;
-    const size_t ng = lat_g.get_size_gauge();
     const complex<double>* parts[3] = {gauge, b, xe};
-    const size_t lens[3] = {ng, (size_t)n, (size_t)n};
-    for (int i = 0; written && i < 3; i++) {
-      const vector<complex<double>> h = qmg::to_host(parts[i], lens[i]);
-      written = fwrite(h.data(), sizeof(complex<double>), lens[i], f) == lens[i];
-    }
-    if (f) fclose(f);
-    if (!written) { cout << "[QMG-MOBIUS-EO] solution_file 0 FAIL\n"; all_pass = false; }
+    const size_t lens[3] = {(size_t)lat_g.get_size_gauge(), (size_t)n, (size_t)n};
+    if (!dw_selftest::write_raw(argv[6], parts, lens, 3)) line("solution_file", 0.0, false);
   }
 
   qmg_driver::phase("full cg");
-  inversion_info full = eo;
   double full_res = 0.0, eps_full = eps;
-  for (int attempt = 0; attempt < 10; attempt++) {
-    zero_vector(xf, n);
-    full = minv_mobius_cg(xf, b, max_iter, eps_full, mob);
-    mob->apply_M_overwrite(t1, xf);
-    full_res = sqrt(diffnorm2sq(t1, b, n) / bnorm);
-    if (full_res <= eo_res && full_res >= 0.5 * eo_res) break;
-    eps_full *= 0.75 * eo_res / full_res;
-  }
+  const auto full_solve = [&](complex<double>* sol, double tol) { return minv_mobius_cg(sol, b, max_iter, tol, mob); };
+  const inversion_info full = dw_selftest::tightened_solve(mob, xf, t1, b, n, bnorm, eo_res, eps_full, full_res, full_solve);
   const double sol_diff = sqrt(diffnorm2sq(xe, xf, n) / norm2sq(xf, n));
 
   line("links_route_on", links_on ? 1.0 : 0.0, links_on);
@@ -123,25 +91,12 @@ int main(int argc, char** argv) {
   line("full_true_residual", full_res, true);   // a figure: how closely the comparison solve was matched to (c)
   line("eo_vs_full_solution", sol_diff, sol_diff <= 1e-7);
 
-  if (rounds > 0) {
-    qmg_driver::phase("timing");
-    auto wall_ms = [&](complex<double>* sol, bool even_odd) -> double {
-      zero_vector(sol, n);
-      qmg_stream_sync(qmg::current_stream());
-      const auto t0 = chrono::steady_clock::now();
-      if (even_odd) minv_mobius_eo_cg(sol, b, max_iter, eps, mob);
-      else minv_mobius_cg(sol, b, max_iter, eps_full, mob);
-      qmg_stream_sync(qmg::current_stream());
-      return chrono::duration<double, milli>(chrono::steady_clock::now() - t0).count();
-    };
-    for (int r = 0; r < rounds; r++) {
-      const double te = wall_ms(xe, true), tf = wall_ms(xf, false);
-      cout << "[QMG-MOBIUS-EO-BENCH] round " << r << " eo_ms " << te << " full_ms " << tf << "\n";
-    }
-  }
+  if (rounds > 0)
+    dw_selftest::timing_rounds("[QMG-MOBIUS-EO-BENCH]", rounds, n, xe, xf, [&](complex<double>* sol) { minv_mobius_eo_cg(sol, b, max_iter, eps, mob); },
+                               [&](complex<double>* sol) { full_solve(sol, eps_full); });
 
   delete mob;
-  for (complex<double>** p : {&x, &y, &v, &t1, &t2, &b, &xe, &xf, &gauge}) deallocate_vector(p);
+  vec.release();
   qmg::VecPool::release_all();
-  return qmg_driver::leave(all_pass ? 0 : 1);
+  return qmg_driver::leave(line.all_pass ? 0 : 1);
 }

@@ -10,23 +10,14 @@
 //   (d) shamir_limit         a second operator with b5 = 1, c5 = 0 against Dwf2D<Ls> with shift = M5: relative l2 difference < 1e-13.
 //   (e) cg_iterations, cg_true_residual   minv_mobius_cg to 1e-10; the recomputed |b - D x| / |b| <= 1e-8.  With a solution_file the links, b and
 //       x of this solve are written there as raw complex<double> (2 L^2, then twice 2 Ls L^2 numbers in the device layout), for a dense solve elsewhere.
-#include <cmath>
-#include <cstdio>
 #include <iomanip>
-#include <iostream>
 #include <string>
-#include <vector>
 
-#include "../include/qmg/qmg.hpp"
-#include "driver_common.hpp"
+#include "dw_selftest_common.hpp"
 
 using namespace std;
 
-static bool all_pass = true;
-static void line(const char* name, double value, bool pass) {
-  cout << "[QMG-MOBIUS] " << name << " " << value << " " << (pass ? "PASS" : "FAIL") << "\n";
-  if (!pass) all_pass = false;
-}
+static dw_selftest::Lines line("[QMG-MOBIUS]");
 
 // Dwf2D of run-time Ls for the Shamir limit: createDwfLs, and at Ls = 32 (which it declines: no stored apply at nc = 64) the class itself
 static Stencil2D* shamir(Lattice2D* lat, double mass, complex<double>* gauge, int Ls, bool stored) {
@@ -43,7 +34,8 @@ int main(int argc, char** argv) {
   const double mass = stod(argv[3]), b5 = stod(argv[4]), c5 = stod(argv[5]);
   const unsigned long long seed = argc > 6 ? stoull(argv[6]) : 7ull;
   Lattice2D lat_g(L, L, 1), lat(L, L, 2 * Ls);
-  complex<double>* gauge = allocate_vector<complex<double>>(lat_g.get_size_gauge());
+  dw_selftest::Vectors vec;
+  complex<double>* gauge = vec.make(lat_g.get_size_gauge());
   // link phases N(0, 0.4^2)
   if (!qmg::ok(qmg_u1_gauss_gauge(gauge, L, L, 1.0 / (0.4 * 0.4), seed, qmg::current_stream()), "qmg_u1_gauss_gauge")) return 3;
   int plan[12];
@@ -51,14 +43,7 @@ int main(int argc, char** argv) {
   MobiusBase* mob = createMobiusLs(&lat, mass, gauge, Ls, b5, c5);
   if (!mob || !mob->generated) { cout << "[QMG-MOBIUS] create 0 FAIL\n[MOBIUS-SELFTEST] FAIL\n"; return 4; }
   const int n = (int)lat.get_size_cv_l();
-  complex<double>* x = allocate_vector<complex<double>>(n);
-  complex<double>* y = allocate_vector<complex<double>>(n);
-  complex<double>* Dx = allocate_vector<complex<double>>(n);
-  complex<double>* Ddy = allocate_vector<complex<double>>(n);
-  complex<double>* Ddx = allocate_vector<complex<double>>(n);
-  complex<double>* t1 = allocate_vector<complex<double>>(n);
-  complex<double>* t2 = allocate_vector<complex<double>>(n);
-  complex<double>* b = allocate_vector<complex<double>>(n);
+  complex<double>*x = vec.make(n), *y = vec.make(n), *Dx = vec.make(n), *Ddy = vec.make(n), *Ddx = vec.make(n), *t1 = vec.make(n), *t2 = vec.make(n), *b = vec.make(n);
   gaussian(x, n, seed + 101);
   gaussian(y, n, seed + 102);
   gaussian(b, n, seed + 200);
@@ -95,20 +80,11 @@ int main(int argc, char** argv) {
   const double eps = 1e-10;
   zero_vector(t1, n);
   const inversion_info info = minv_mobius_cg(t1, b, max_iter, eps, mob);
-  mob->apply_M_overwrite(t2, t1);
-  const double true_res = sqrt(diffnorm2sq(t2, b, n) / norm2sq(b, n));
+  const double true_res = dw_selftest::true_residual(mob, t2, t1, b, n, norm2sq(b, n));
   if (argc > 7) {
-    FILE* f = fopen(argv[7], "wb");
-    bool written = f != nullptr;
-    const size_t ng = lat_g.get_size_gauge();
     const complex<double>* parts[3] = {gauge, b, t1};
-    const size_t lens[3] = {ng, (size_t)n, (size_t)n};
-    for (int i = 0; written && i < 3; i++) {
-      const vector<complex<double>> h = qmg::to_host(parts[i], lens[i]);
-      written = fwrite(h.data(), sizeof(complex<double>), lens[i], f) == lens[i];
-    }
-    if (f) fclose(f);
-    if (!written) { cout << "[QMG-MOBIUS] solution_file 0 FAIL\n"; all_pass = false; }
+    const size_t lens[3] = {(size_t)lat_g.get_size_gauge(), (size_t)n, (size_t)n};
+    if (!dw_selftest::write_raw(argv[7], parts, lens, 3)) line("solution_file", 0.0, false);
   }
 
   double dvs = -1.0, ddvs = -1.0;
@@ -132,11 +108,10 @@ int main(int argc, char** argv) {
   line("shamir_limit", sham, sham >= 0.0 && sham < 1e-13);
   line("cg_iterations", (double)info.iter, info.success && info.iter < max_iter);
   line("cg_true_residual", true_res, true_res <= 1e-8);
-  cout << "[MOBIUS-SELFTEST] " << (all_pass ? "PASS" : "FAIL") << "\n";
+  cout << "[MOBIUS-SELFTEST] " << (line.all_pass ? "PASS" : "FAIL") << "\n";
 
   delete mob;
-  deallocate_vector(&x); deallocate_vector(&y); deallocate_vector(&Dx); deallocate_vector(&Ddy); deallocate_vector(&Ddx);
-  deallocate_vector(&t1); deallocate_vector(&t2); deallocate_vector(&b); deallocate_vector(&gauge);
+  vec.release();
   qmg::VecPool::release_all();
-  return qmg_driver::leave(all_pass ? 0 : 1);
+  return qmg_driver::leave(line.all_pass ? 0 : 1);
 }

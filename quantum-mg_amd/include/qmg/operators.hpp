@@ -1,7 +1,8 @@
 // operators.hpp -- the concrete stencils of the reference on device arrays:
 //   Wilson2D (operators/wilson.h), Staggered2D (operators/staggered.h), GaugedLaplace2D
 //   (operators/gaugedlaplace.h), FreeLaplace2D (tests/n02_free_laplace_test/free_laplace.h), DwfBase / Dwf2D<Ls> / createDwfLs (operators/dwf.h).
-//   Not in the reference: MobiusBase / Mobius2D<Ls> / createMobiusLs, the Moebius domain-wall operator on the layout of Dwf2D.
+//   Not in the reference: MobiusBase / Mobius2D<Ls> / createMobiusLs, the Moebius domain-wall operator on the layout of Dwf2D, and
+//   DomainWallBase, the host layer DwfBase and MobiusBase share.
 // CoarseOperator2D lives in coarse.hpp (it needs TransferMG).
 #ifndef QMG_OPERATORS_HPP
 #define QMG_OPERATORS_HPP
@@ -73,36 +74,156 @@ struct Wilson2D : public Stencil2D {
   virtual QMGDefaultChirality get_default_chirality() { return QMG_CHIRALITY_GAMMA_5; }
 };
 
-// ---------------- Shamir domain wall (operators/dwf.h; nc = 2 Ls: Ls copies of the Wilson spin blocks coupled along the fifth dimension) ----------------
-// Component c = 2 s + sigma.  The domain-wall height M5 is the stencil's identity shift, the wall mass couples slice Ls-1 to slice 0.  The
-// stored arrays (qmg_dwf_fill: the full nc x nc matrices, zeros included) serve the dagger / right-block-Jacobi / Galerkin builds and every
-// piece set the kernel from the links does not; the ORIGINAL-operator applies go straight from the links (qmg_dwf_apply_direct, csrc/qmg_dwf.hip).
-// Whole lattice only: y-slabs are not served.
-// DwfBase: what does not depend on the compile-time Ls -- the wall mass, M5, Ls, and the 4D even-odd Schur complement from the links
-// (qmg_dwf_inv5 / qmg_dwf_hops_inv5 / qmg_dwf_schur_apply, csrc/qmg_dwf_eo.hip).  D = A + H with A = clover + shift site-local and constant:
-//   M = A_ee - H_eo A_oo^-1 H_oe,   Gamma5 M Gamma5 = M^dagger for real m and shifts (no dagger stencil),
-// in the reference's Schur convention (stencil_2d.h:1886-1957): the arrays are addressed as full-length vectors of which the even half is
-// the system -- a solver hands over half-length arrays --, eo_cvector is the scratch.  These methods need the links route (direct.on, kind
-// domain wall, no variant swapped in); there is no stored fallback, so they also serve Ls = 32.
-struct DwfBase : public Stencil2D {
+// ---------------- domain wall: what the Shamir and the Moebius operator share (nc = 2 Ls) ----------------
+// Component c = 2 s + sigma: Ls copies of the Wilson spin blocks coupled along the fifth dimension.  The stored arrays (the full nc x nc
+// matrices) serve the dagger / right-block-Jacobi / Galerkin builds and every piece set the links entries decline; the ORIGINAL-operator
+// applies go straight from the links.  Whole lattice only: y-slabs are not served.
+// DomainWallBase holds what does not depend on which operator it is: the wall mass, M5, Ls, Gamma5, the measurements on a five-dimensional
+// field, and the skeleton of the 4D even-odd Schur complement M from the links, in the reference's Schur convention (stencil_2d.h:1886-1957):
+// the arrays are addressed as full-length vectors of which the even half is the system -- a solver hands over half-length arrays --,
+// eo_cvector is the scratch.  There is no stored fallback, so the Schur methods also serve Ls = 32.  An operator fills in
+//   schur5_ready    whether the Schur methods can run, saying why not;
+//   schur5_stages   the two launches of M or M^dagger;
+//   prepare_M_schur5 / reconstruct_M_schur5   its own launch sequence around A_o^-1.
+enum { QMG_DW_LS_MAX = 32 };
+#define QMG_DW_LS_LIST(X) X(2) X(4) X(6) X(8) X(12) X(16) X(24) X(32)   // the reference's list of Ls values (dwf.h:261-293), for both factories
+
+struct DomainWallBase : public Stencil2D {
  protected:
   complex<double> mass;
   double M5;
-  int dwf_Ls;
+  int dw_Ls;
+  double g5_scale[2 * QMG_DW_LS_MAX];   // gamma5 as a scale / shuffle pattern (dwf.h:36-37, 62-67), filled for Ls
+  int g5_shuffle[2 * QMG_DW_LS_MAX];
+  complex<double>* scratch;         // for the in-place gamma5
   complex<double>* schur5_vector;   // M rhs inside apply_M_schur5_dagger_M, allocated on demand
-  DwfBase(Lattice2D* in_lat, complex<double> mass, double M5, int Ls)
-      : Stencil2D(in_lat, QMG_PIECE_CLOVER_HOPPING, M5, 0.0, 0.0), mass(mass), M5(M5), dwf_Ls(Ls), schur5_vector(0) {}
 
-  bool schur5(const char* who, complex<double>* lhs, complex<double>* rhs, unsigned flags) {
+  DomainWallBase(Lattice2D* in_lat, complex<double> shift, complex<double> mass, double M5, int Ls)
+      : Stencil2D(in_lat, QMG_PIECE_CLOVER_HOPPING, shift, 0.0, 0.0), mass(mass), M5(M5), dw_Ls(Ls), scratch(0), schur5_vector(0) {
+    for (int i = 0; i < Ls && i < QMG_DW_LS_MAX; i++) {
+      g5_scale[2 * i] = 1.0; g5_scale[2 * i + 1] = -1.0;
+      g5_shuffle[2 * i] = 2 * (Ls - 1 - i); g5_shuffle[2 * i + 1] = 2 * (Ls - 1 - i) + 1;
+    }
+  }
+  // what a constructor refuses, by the name of its class: a lattice that is not nc = 2 Ls, and y-slabs
+  bool served(const char* cls) const {
+    if (lat->get_nc() != 2 * dw_Ls) { std::cout << "[QMG-ERROR]: " << cls << " only supports Nc = 2 Ls.\n"; return false; }
+    if (qmg::slab().on) { std::cout << "[QMG-ERROR]: " << cls << " is not decomposed into y-slabs.\n"; return false; }
+    return true;
+  }
+  // whether the ORIGINAL-operator applies come from the links of `kind`
+  bool links_route(int kind) const { return direct.on && direct.kind == kind && !swap_dagger && !swap_rbjacobi && !swap_rbj_dagger; }
+  bool schur5_scratch() {
+    if (eo_cvector == 0) eo_cvector = allocate_vector<complex<double>>(lat->get_size_cv_l());
+    return eo_cvector != 0;
+  }
+  // lhs_e = M rhs_e or M^dagger rhs_e: the operator's two launches
+  virtual bool schur5_stages(const char* who, complex<double>* lhs, complex<double>* rhs, bool dagger) = 0;
+
+ public:
+  virtual ~DomainWallBase() {
+    if (scratch) deallocate_vector(&scratch);
+    if (schur5_vector) deallocate_vector(&schur5_vector);
+  }
+  int get_Ls() const { return dw_Ls; }
+  complex<double> get_mass() const { return mass; }
+  double get_M5() const { return M5; }
+
+  // (Gamma5 psi)(s, sigma) = (-1)^sigma psi(Ls-1-s, sigma)
+  virtual void gamma5(complex<double>* vec) {                                                                            // dwf.h:104-108
+    if (!scratch) scratch = allocate_vector<complex<double>>(lat->get_size_cv_l());
+    qmg::pattern(g5_scale, g5_shuffle, 2 * dw_Ls, vec, scratch, (size_t)lat->get_volume());
+    copy_vector(vec, scratch, lat->get_size_cv_l());
+  }
+  virtual void gamma5(complex<double>* g5_vec, complex<double>* vec) {                                                   // :110-114
+    if (g5_vec == vec) { gamma5(vec); return; }
+    qmg::pattern(g5_scale, g5_shuffle, 2 * dw_Ls, vec, g5_vec, (size_t)lat->get_volume());
+  }
+  virtual void chiral_projection(complex<double>*, bool) { return; }                                                     // empty in the reference (:117-146)
+  virtual void chiral_projection_copy(complex<double>*, complex<double>*, bool) { return; }
+  virtual void chiral_projection_both(complex<double>*, complex<double>*) { return; }
+  virtual QMGDefaultChirality get_default_chirality() { return QMG_CHIRALITY_GAMMA_5; }
+
+  // whether the Schur methods can run (the links route is on, and what the operator's dagger form asks); says why not, makes the scratch
+  virtual bool schur5_ready(const char* who, bool dagger = false) = 0;
+  // lhs_e = M rhs_e, overwriting; lhs != rhs
+  void apply_M_schur5(complex<double>* lhs, complex<double>* rhs) {
+    if (schur5_ready("apply_M_schur5")) schur5_stages("apply_M_schur5", lhs, rhs, false);
+  }
+  // lhs_e = M^dagger rhs_e: two launches, as M
+  void apply_M_schur5_dagger(complex<double>* lhs, complex<double>* rhs) {
+    if (schur5_ready("apply_M_schur5_dagger", true)) schur5_stages("apply_M_schur5_dagger", lhs, rhs, true);
+  }
+  void apply_M_schur5_dagger_M(complex<double>* lhs, complex<double>* rhs) {
+    if (!schur5_ready("apply_M_schur5_dagger_M", true)) return;
+    if (!schur5_vector) schur5_vector = allocate_vector<complex<double>>(lat->get_size_cv_l() / 2);
+    if (schur5_stages("apply_M_schur5_dagger_M", schur5_vector, rhs, false)) schur5_stages("apply_M_schur5_dagger_M", lhs, schur5_vector, true);
+  }
+  // b_r,e = b_e - (hops A_o^-1 b)_e, odd half zero (full-length arrays; b_r != b)
+  virtual void prepare_M_schur5(complex<double>* b_r, complex<double>* b) = 0;
+  // x_e = y_e, x_o = A_o^-1 (b_o - (hops y)_o)   (x and b full-length; of y_e the even half is read)
+  virtual void reconstruct_M_schur5(complex<double>* x, complex<double>* y_e, complex<double>* b) = 0;
+
+  // ---- measurements (csrc/qmg_dwf_meas.hip; include/qmg/dwf_measure.hpp builds the propagator and the correlators on these) ----
+  // psi5 = the wall source of the 4D (nc = 2) field eta4: eta4(x, 0) on (s, sigma) = (0, 0), eta4(x, 1) on (Ls-1, 1), zero elsewhere
+  bool wall_source(complex<double>* psi5, complex<double>* eta4) {
+    return qmg::ok(qmg_dwf_wall_source(QMG_C64, lat->get_dim_mu(0), lat->get_dim_mu(1), dw_Ls, psi5, eta4, 1, 0, 0, qmg::current_stream()), "qmg_dwf_wall_source");
+  }
+  // q4 = the physical quark field (Ls-1, 0), (0, 1) of psi5, or its midpoint field (Ls/2-1, 0), (Ls/2, 1) (even Ls only: false otherwise)
+  bool wall_project(complex<double>* q4, complex<double>* psi5, bool midpoint) {
+    if (midpoint && (dw_Ls & 1)) { std::cout << "[QMG-ERROR]: wall_project: an odd Ls has no midpoint between the walls.\n"; return false; }
+    return qmg::ok(qmg_dwf_wall_project(QMG_C64, lat->get_dim_mu(0), lat->get_dim_mu(1), dw_Ls, q4, psi5, midpoint ? 1 : 0, 1, 0, 0, qmg::current_stream()),
+                   "qmg_dwf_wall_project");
+  }
+  // sum[(y Ls + s) 2 + sigma] = sum_x |psi5(x, y; s, sigma)|^2 on the host: 2 Ls Ly doubles
+  bool slice_norms(double* sum, complex<double>* psi5) {
+    return qmg::ok(qmg_dwf_slice_norms(QMG_C64, lat->get_dim_mu(0), lat->get_dim_mu(1), dw_Ls, psi5, 1, 0, nullptr, sum, qmg::current_stream()), "qmg_dwf_slice_norms");
+  }
+};
+
+// The Schur complement with the matrix_op_cplx signature (extra_data: a DomainWallBase*), for the Krylov solvers on the even half.
+inline void apply_domain_wall_schur5_Mdagger_M(complex<double>* lhs, complex<double>* rhs, void* extra_data) {
+  ((DomainWallBase*)extra_data)->apply_M_schur5_dagger_M(lhs, rhs);
+}
+// D x = b by CG on the normal equations of the even-odd Schur complement: prepare, M^dagger b', minv_vector_cg over the half length from the
+// even half of x as the initial guess, reconstruct.  x and b are full-length; eps is the relative residual of M^dagger M y = M^dagger b'.
+// Where the Schur methods cannot run (schur5_ready) nothing is solved, x is untouched, success is false and the name is `not_run`.
+inline inversion_info minv_domain_wall_eo_cg(complex<double>* x, complex<double>* b, int max_iter, double eps, DomainWallBase* op, const char* who, const char* not_run,
+                                             inversion_verbose_struct* verb) {
+  const size_t n = op->lat->get_size_cv_l(), half = n / 2;
+  if (!op->schur5_ready(who, true)) {
+    inversion_info none;
+    none.name = not_run;
+    return none;
+  }
+  complex<double>* b_r = allocate_vector<complex<double>>(n);
+  complex<double>* rhs = allocate_vector<complex<double>>(half);
+  op->prepare_M_schur5(b_r, b);
+  op->apply_M_schur5_dagger(rhs, b_r);
+  const inversion_info info = minv_vector_cg(x, rhs, (int)half, max_iter, eps, apply_domain_wall_schur5_Mdagger_M, (void*)op, verb);
+  op->reconstruct_M_schur5(x, x, b);
+  deallocate_vector(&b_r); deallocate_vector(&rhs);
+  return info;
+}
+
+// ---------------- Shamir domain wall (operators/dwf.h) ----------------
+// The domain-wall height M5 is the stencil's identity shift, the wall mass couples slice Ls-1 to slice 0.  D = A + H with A = clover + shift
+// site-local and constant (qmg_dwf_fill / qmg_dwf_apply_direct, csrc/qmg_dwf.hip; qmg_dwf_inv5 / qmg_dwf_hops_inv5 / qmg_dwf_schur_apply,
+// csrc/qmg_dwf_eo.hip):
+//   M = A_ee - H_eo A_oo^-1 H_oe,   Gamma5 M Gamma5 = M^dagger for real m and shifts (no dagger stencil, the launches and bytes of M).
+struct DwfBase : public DomainWallBase {
+ protected:
+  DwfBase(Lattice2D* in_lat, complex<double> mass, double M5, int Ls) : DomainWallBase(in_lat, M5, mass, M5, Ls) {}
+
+  virtual bool schur5_stages(const char* who, complex<double>* lhs, complex<double>* rhs, bool dagger) {
     const qmg_stencil_desc d = desc();
-    return qmg::ok(qmg_dwf_schur_apply(QMG_C64, &d, direct.gauge, dwf_Ls, mass.real(), mass.imag(), direct.w, lhs, rhs, eo_cvector, 0, flags, 1, 0, 1u,
-                                       qmg::current_stream()), who);
+    return qmg::ok(qmg_dwf_schur_apply(QMG_C64, &d, direct.gauge, dw_Ls, mass.real(), mass.imag(), direct.w, lhs, rhs, eo_cvector, 0,
+                                       dagger ? QMG_DWF_G5_IN | QMG_DWF_G5_OUT : 0u, 1, 0, 1u, qmg::current_stream()), who);
   }
 
  public:
-  // whether the Schur methods can run (the links route is on; for the dagger forms: real wall mass and shifts); says why not, makes the scratch
-  bool schur5_ready(const char* who, bool dagger = false) {
-    if (!direct.on || direct.kind != QMG_DIRECT_DWF || swap_dagger || swap_rbjacobi || swap_rbj_dagger) {
+  virtual bool schur5_ready(const char* who, bool dagger = false) {
+    if (!links_route(QMG_DIRECT_DWF)) {
       std::cout << "[QMG-ERROR]: " << who << " needs the domain-wall links route (direct.on, no variant swapped in); there is no stored fallback.\n";
       return false;
     }
@@ -110,63 +231,28 @@ struct DwfBase : public Stencil2D {
       std::cout << "[QMG-ERROR]: " << who << " uses Gamma5 M Gamma5 = M^dagger, which holds for a real wall mass and real shifts only.\n";
       return false;
     }
-    if (eo_cvector == 0) eo_cvector = allocate_vector<complex<double>>(lat->get_size_cv_l());
-    return eo_cvector != 0;
+    return schur5_scratch();
   }
-  virtual ~DwfBase() { if (schur5_vector) deallocate_vector(&schur5_vector); }
-  int get_Ls() const { return dwf_Ls; }
-  complex<double> get_mass() const { return mass; }
-  double get_M5() const { return M5; }
-
-  // lhs_e = M rhs_e, overwriting; lhs != rhs
-  void apply_M_schur5(complex<double>* lhs, complex<double>* rhs) {
-    if (schur5_ready("apply_M_schur5")) schur5("apply_M_schur5", lhs, rhs, 0);
-  }
-  // lhs_e = M^dagger rhs_e = Gamma5 M Gamma5 rhs_e: the two launches and the bytes of M
-  void apply_M_schur5_dagger(complex<double>* lhs, complex<double>* rhs) {
-    if (schur5_ready("apply_M_schur5_dagger", true)) schur5("apply_M_schur5_dagger", lhs, rhs, QMG_DWF_G5_IN | QMG_DWF_G5_OUT);
-  }
-  void apply_M_schur5_dagger_M(complex<double>* lhs, complex<double>* rhs) {
-    if (!schur5_ready("apply_M_schur5_dagger_M", true)) return;
-    if (!schur5_vector) schur5_vector = allocate_vector<complex<double>>(lat->get_size_cv_l() / 2);
-    if (schur5("apply_M_schur5_dagger_M", schur5_vector, rhs, 0)) schur5("apply_M_schur5_dagger_M", lhs, schur5_vector, QMG_DWF_G5_IN | QMG_DWF_G5_OUT);
-  }
-  // b_r,e = b_e - H_eo A_oo^-1 b_o, odd half zero (full-length arrays)
-  void prepare_M_schur5(complex<double>* b_r, complex<double>* b) {
+  // b_r,e = b_e - H_eo A_oo^-1 b_o
+  virtual void prepare_M_schur5(complex<double>* b_r, complex<double>* b) {
     if (!schur5_ready("prepare_M_schur5")) return;
     const qmg_stencil_desc d = desc();
     const long half = lat->get_size_cv_l() / 2;
-    qmg::ok(qmg_dwf_inv5(QMG_C64, &d, dwf_Ls, mass.real(), mass.imag(), direct.w, eo_cvector, b, QMG_P_CLOVER_O, 1.0, 0.0, 1, 0, 1u, qmg::current_stream()), "qmg_dwf_inv5");
-    qmg::ok(qmg_dwf_apply_direct(QMG_C64, &d, direct.gauge, dwf_Ls, mass.real(), mass.imag(), direct.w, b_r, eo_cvector, QMG_P_EO | QMG_P_ZERO_E, 1, 0, 1u,
+    qmg::ok(qmg_dwf_inv5(QMG_C64, &d, dw_Ls, mass.real(), mass.imag(), direct.w, eo_cvector, b, QMG_P_CLOVER_O, 1.0, 0.0, 1, 0, 1u, qmg::current_stream()), "qmg_dwf_inv5");
+    qmg::ok(qmg_dwf_apply_direct(QMG_C64, &d, direct.gauge, dw_Ls, mass.real(), mass.imag(), direct.w, b_r, eo_cvector, QMG_P_EO | QMG_P_ZERO_E, 1, 0, 1u,
                                  qmg::current_stream()), "qmg_dwf_apply_direct");
     cxpay(b, -1.0, b_r, half);
     zero_vector(b_r + half, half);
   }
-  // x_e = y_e, x_o = A_oo^-1 (b_o - H_oe y_e)   (x and b full-length; of y_e the even half is read)
-  void reconstruct_M_schur5(complex<double>* x, complex<double>* y_e, complex<double>* b) {
+  // x_o = A_oo^-1 (b_o - H_oe y_e)
+  virtual void reconstruct_M_schur5(complex<double>* x, complex<double>* y_e, complex<double>* b) {
     if (!schur5_ready("reconstruct_M_schur5")) return;
     const qmg_stencil_desc d = desc();
     const long half = lat->get_size_cv_l() / 2;
     if (x != y_e) copy_vector(x, y_e, half);
-    qmg::ok(qmg_dwf_inv5(QMG_C64, &d, dwf_Ls, mass.real(), mass.imag(), direct.w, x, b, QMG_P_CLOVER_O, 1.0, 0.0, 1, 0, 1u, qmg::current_stream()), "qmg_dwf_inv5");
-    qmg::ok(qmg_dwf_hops_inv5(QMG_C64, &d, direct.gauge, dwf_Ls, mass.real(), mass.imag(), direct.w, x, x, QMG_P_OE, -1.0, 0.0, 0, 1, 0, 1u, qmg::current_stream()),
+    qmg::ok(qmg_dwf_inv5(QMG_C64, &d, dw_Ls, mass.real(), mass.imag(), direct.w, x, b, QMG_P_CLOVER_O, 1.0, 0.0, 1, 0, 1u, qmg::current_stream()), "qmg_dwf_inv5");
+    qmg::ok(qmg_dwf_hops_inv5(QMG_C64, &d, direct.gauge, dw_Ls, mass.real(), mass.imag(), direct.w, x, x, QMG_P_OE, -1.0, 0.0, 0, 1, 0, 1u, qmg::current_stream()),
             "qmg_dwf_hops_inv5");
-  }
-
-  // ---- measurements (csrc/qmg_dwf_meas.hip; include/qmg/dwf_measure.hpp builds the propagator and the correlators on these) ----
-  // psi5 = the wall source of the 4D (nc = 2) field eta4: eta4(x, 0) on (s, sigma) = (0, 0), eta4(x, 1) on (Ls-1, 1), zero elsewhere
-  bool wall_source(complex<double>* psi5, complex<double>* eta4) {
-    return qmg::ok(qmg_dwf_wall_source(QMG_C64, lat->get_dim_mu(0), lat->get_dim_mu(1), dwf_Ls, psi5, eta4, 1, 0, 0, qmg::current_stream()), "qmg_dwf_wall_source");
-  }
-  // q4 = the physical quark field (Ls-1, 0), (0, 1) of psi5, or its midpoint field (Ls/2-1, 0), (Ls/2, 1) (even Ls only: false otherwise)
-  bool wall_project(complex<double>* q4, complex<double>* psi5, bool midpoint) {
-    if (midpoint && (dwf_Ls & 1)) { std::cout << "[QMG-ERROR]: wall_project: an odd Ls has no midpoint between the walls.\n"; return false; }
-    return qmg::ok(qmg_dwf_wall_project(QMG_C64, lat->get_dim_mu(0), lat->get_dim_mu(1), dwf_Ls, q4, psi5, midpoint ? 1 : 0, 1, 0, 0, qmg::current_stream()),
-                   "qmg_dwf_wall_project");
-  }
-  // sum[(y Ls + s) 2 + sigma] = sum_x |psi5(x, y; s, sigma)|^2 on the host: 2 Ls Ly doubles
-  bool slice_norms(double* sum, complex<double>* psi5) {
-    return qmg::ok(qmg_dwf_slice_norms(QMG_C64, lat->get_dim_mu(0), lat->get_dim_mu(1), dwf_Ls, psi5, 1, 0, nullptr, sum, qmg::current_stream()), "qmg_dwf_slice_norms");
   }
 };
 
@@ -175,12 +261,8 @@ struct Dwf2D : public DwfBase {
  protected:
   Dwf2D(Dwf2D const&);
   Dwf2D& operator=(Dwf2D const&);
-  complex<double>* scratch;   // for the in-place gamma5
 
  public:
-  double a[2 * Ls];        // gamma5 as a scale / shuffle pattern (dwf.h:36-37, 62-67)
-  int shuffle[2 * Ls];
-
   void update_links(complex<double>* gauge_links) {   // dwf.h:154-255; gauge_links: DEVICE nc=1 LatticeGauge
     qmg::ok(qmg_dwf_fill(clover, hopping, gauge_links, lat->get_dim_mu(0), lat->get_dim_mu(1), Ls, mass.real(), mass.imag(), 1.0, qmg::current_stream()), "qmg_dwf_fill");
     drop_variant_stencils();
@@ -188,54 +270,28 @@ struct Dwf2D : public DwfBase {
     generated = true;
   }
 
-  Dwf2D(Lattice2D* in_lat, complex<double> mass, complex<double>* gauge_links, double M5 = -1.0)
-      : DwfBase(in_lat, mass, M5, Ls), scratch(0) {
-    for (int i = 0; i < Ls; i++) {
-      a[2 * i] = 1.0; a[2 * i + 1] = -1.0;
-      shuffle[2 * i] = 2 * (Ls - 1 - i); shuffle[2 * i + 1] = 2 * (Ls - 1 - i) + 1;
-    }
-    if (lat->get_nc() != 2 * Ls) { std::cout << "[QMG-ERROR]: Dwf2D only supports Nc = 2 Ls.\n"; return; }
-    if (qmg::slab().on) { std::cout << "[QMG-ERROR]: Dwf2D is not decomposed into y-slabs.\n"; return; }
-    update_links(gauge_links);
+  Dwf2D(Lattice2D* in_lat, complex<double> mass, complex<double>* gauge_links, double M5 = -1.0) : DwfBase(in_lat, mass, M5, Ls) {
+    if (served("Dwf2D")) update_links(gauge_links);
   }
-  ~Dwf2D() { if (scratch) deallocate_vector(&scratch); }
 
   static int get_dof(int i = 0) { return 2 * Ls; }
   static chirality_state has_chirality() { return QMG_CHIRAL_YES; }
-
-  // (Gamma5 psi)(s, sigma) = (-1)^sigma psi(Ls-1-s, sigma)
-  virtual void gamma5(complex<double>* vec) {                                                                            // dwf.h:104-108
-    if (!scratch) scratch = allocate_vector<complex<double>>(lat->get_size_cv_l());
-    qmg::pattern(a, shuffle, 2 * Ls, vec, scratch, (size_t)lat->get_volume());
-    copy_vector(vec, scratch, lat->get_size_cv_l());
-  }
-  virtual void gamma5(complex<double>* g5_vec, complex<double>* vec) {                                                   // :110-114
-    if (g5_vec == vec) { gamma5(vec); return; }
-    qmg::pattern(a, shuffle, 2 * Ls, vec, g5_vec, (size_t)lat->get_volume());
-  }
-  virtual void chiral_projection(complex<double>*, bool) { return; }                                                     // empty in the reference (:117-146)
-  virtual void chiral_projection_copy(complex<double>*, complex<double>*, bool) { return; }
-  virtual void chiral_projection_both(complex<double>*, complex<double>*) { return; }
-  virtual QMGDefaultChirality get_default_chirality() { return QMG_CHIRALITY_GAMMA_5; }
 };
 
 // A domain-wall operator of run-time Ls (dwf.h:261-293): the reference's list of Ls values, of which those are served whose nc = 2 Ls the
 // stored-stencil apply serves (the variants and every piece set the links kernel declines go through it): qmg_stencil_plan is asked.
 inline Stencil2D* createDwfLs(Lattice2D* in_lat, complex<double> mass, complex<double>* gauge_links, int Ls, double M5 = -1.0) {
   int plan[12];
-  const bool listed = Ls == 2 || Ls == 4 || Ls == 6 || Ls == 8 || Ls == 12 || Ls == 16 || Ls == 24 || Ls == 32;
+#define QMG_DW_LS_IS(N) || Ls == N
+  const bool listed = false QMG_DW_LS_LIST(QMG_DW_LS_IS);
+#undef QMG_DW_LS_IS
   const bool stored = listed && qmg_stencil_plan(QMG_SE_APPLY, 0, 0, in_lat->get_dim_mu(0), in_lat->get_dim_mu(1), 2 * Ls, QMG_P_ALL | QMG_P_ZERO, 1, 0, 0, 1, 1, 0, 0,
                                                  plan, 12) == QMG_SUCCESS && plan[0] != 0 && plan[0] != 9;
-  if (stored) {
+  if (stored) {   // (Ls = 32, nc = 64: not served by the stored-stencil apply today)
     switch (Ls) {
-      case 2: return new Dwf2D<2>(in_lat, mass, gauge_links, M5);
-      case 4: return new Dwf2D<4>(in_lat, mass, gauge_links, M5);
-      case 6: return new Dwf2D<6>(in_lat, mass, gauge_links, M5);
-      case 8: return new Dwf2D<8>(in_lat, mass, gauge_links, M5);
-      case 12: return new Dwf2D<12>(in_lat, mass, gauge_links, M5);
-      case 16: return new Dwf2D<16>(in_lat, mass, gauge_links, M5);
-      case 24: return new Dwf2D<24>(in_lat, mass, gauge_links, M5);
-      case 32: return new Dwf2D<32>(in_lat, mass, gauge_links, M5);   // (nc = 64: not served by the stored-stencil apply today)
+#define QMG_DW_LS_CASE(N) case N: return new Dwf2D<N>(in_lat, mass, gauge_links, M5);
+      QMG_DW_LS_LIST(QMG_DW_LS_CASE)
+#undef QMG_DW_LS_CASE
       default: break;
     }
   }
@@ -247,57 +303,36 @@ inline Stencil2D* createDwfLs(Lattice2D* in_lat, complex<double> mass, complex<d
 inline void apply_dwf_schur5_M(complex<double>* lhs, complex<double>* rhs, void* extra_data) { ((DwfBase*)extra_data)->apply_M_schur5(lhs, rhs); }
 inline void apply_dwf_schur5_Mdagger_M(complex<double>* lhs, complex<double>* rhs, void* extra_data) { ((DwfBase*)extra_data)->apply_M_schur5_dagger_M(lhs, rhs); }
 
-// D x = b by CG on the normal equations of the even-odd Schur complement: prepare, M^dagger b', minv_vector_cg over the half length from the
-// even half of x as the initial guess, reconstruct.  x and b are full-length; eps is the relative residual of M^dagger M y = M^dagger b'.
-// Where the Schur methods cannot run (schur5_ready) nothing is solved and success is false.
+// minv_domain_wall_eo_cg on the Shamir operator
 inline inversion_info minv_dwf_eo_cg(complex<double>* x, complex<double>* b, int max_iter, double eps, DwfBase* dwf, inversion_verbose_struct* verb = 0) {
-  const size_t n = dwf->lat->get_size_cv_l(), half = n / 2;
-  if (!dwf->schur5_ready("minv_dwf_eo_cg", true)) {   // nothing to iterate on: no solve, x untouched
-    inversion_info none;
-    none.name = "CG (even-odd domain wall): not run";
-    return none;
-  }
-  complex<double>* b_r = allocate_vector<complex<double>>(n);
-  complex<double>* rhs = allocate_vector<complex<double>>(half);
-  dwf->prepare_M_schur5(b_r, b);
-  dwf->apply_M_schur5_dagger(rhs, b_r);
-  const inversion_info info = minv_vector_cg(x, rhs, (int)half, max_iter, eps, apply_dwf_schur5_Mdagger_M, (void*)dwf, verb);
-  dwf->reconstruct_M_schur5(x, x, b);
-  deallocate_vector(&b_r); deallocate_vector(&rhs);
-  return info;
+  return minv_domain_wall_eo_cg(x, b, max_iter, eps, dwf, "minv_dwf_eo_cg", "CG (even-odd domain wall): not run", verb);
 }
 
-// ---------------- Moebius domain wall (nc = 2 Ls, the layout of Dwf2D) ----------------
+// ---------------- Moebius domain wall (nc = 2 Ls, the layout of Dwf2D; not in the reference) ----------------
 // D = D_W (b5 + c5 L) + (1 - L) = A + H B with D_W = 2 w + M5 + H (include/qmg_hip.h has L, A, B); b5 = 1, c5 = 0 is Dwf2D with shift = M5.  M5 sits
-// inside D_W and is multiplied by B, so it is a parameter of the operator and the stencil's three shifts are zero.  The stored arrays
-// (qmg_mobius_fill; the hopping blocks are no longer diagonal in s) serve the dagger / right-block-Jacobi / Galerkin builds and every piece set
-// the links entry declines; apply_M and apply_M_dagger on the whole lattice go straight from the links (qmg_mobius_apply_direct, op 0 / op 1,
-// csrc/qmg_mobius.hip).  Gamma5 D Gamma5 is NOT D^dagger here (B and H do not commute): the dagger is the entry's op 1, and it needs no stored
-// dagger stencil while the links route is on.  Whole lattice only.
-struct MobiusBase : public Stencil2D {
+// inside D_W and is multiplied by B, so it is a parameter of the operator and the stencil's three shifts are zero.  In the stored arrays
+// (qmg_mobius_fill) the hopping blocks are no longer diagonal in s; apply_M and apply_M_dagger on the whole lattice go straight from the links
+// (qmg_mobius_apply_direct, op 0 / op 1, csrc/qmg_mobius.hip).  Gamma5 D Gamma5 is NOT D^dagger here (B and H do not commute): the dagger is the
+// entry's op 1, and it needs no stored dagger stencil while the links route is on.  The Schur complement (qmg_mobius_inv5 /
+// qmg_mobius_hops_inv5 / qmg_mobius_schur_apply, csrc/qmg_mobius_eo.hip):
+//   M = A_e - H_eo B A_o^-1 H_oe B,   M^dagger = Gamma5 [A'_e - B' H_eo A'_o^-1 B' H_oe] Gamma5   (the entry's op 1)
+// serves any complex wall mass and shifts: the dagger has kernels of its own.
+struct MobiusBase : public DomainWallBase {
  protected:
-  complex<double> mass;
-  double M5, b5, c5;
-  int mobius_Ls;
-  complex<double>* schur5_vector;   // M rhs inside apply_M_schur5_dagger_M, allocated on demand
-  MobiusBase(Lattice2D* in_lat, complex<double> mass, double M5, double b5, double c5, int Ls)
-      : Stencil2D(in_lat, QMG_PIECE_CLOVER_HOPPING, 0, 0, 0), mass(mass), M5(M5), b5(b5), c5(c5), mobius_Ls(Ls), schur5_vector(0) {}
+  double b5, c5;
+  MobiusBase(Lattice2D* in_lat, complex<double> mass, double M5, double b5, double c5, int Ls) : DomainWallBase(in_lat, 0, mass, M5, Ls), b5(b5), c5(c5) {}
 
-  bool schur5(const char* who, complex<double>* lhs, complex<double>* rhs, int op) {
+  virtual bool schur5_stages(const char* who, complex<double>* lhs, complex<double>* rhs, bool dagger) {
     const qmg_stencil_desc d = desc();
-    return qmg::ok(qmg_mobius_schur_apply(QMG_C64, &d, direct.gauge, mobius_Ls, mass.real(), mass.imag(), direct.w, M5, b5, c5, lhs, rhs, eo_cvector, 0, op, 1, 0,
+    return qmg::ok(qmg_mobius_schur_apply(QMG_C64, &d, direct.gauge, dw_Ls, mass.real(), mass.imag(), direct.w, M5, b5, c5, lhs, rhs, eo_cvector, 0, dagger ? 1 : 0, 1, 0,
                                           1u, qmg::current_stream()), who);
   }
 
  public:
-  virtual ~MobiusBase() { if (schur5_vector) deallocate_vector(&schur5_vector); }
-  int get_Ls() const { return mobius_Ls; }
-  complex<double> get_mass() const { return mass; }
-  double get_M5() const { return M5; }
   double get_b5() const { return b5; }
   double get_c5() const { return c5; }
   // whether both applies come from the links (the normal-equation solve below works on that: no stored fallback at Ls = 32)
-  bool links_ready() const { return direct.on && direct.kind == QMG_DIRECT_MOBIUS && !swap_dagger && !swap_rbjacobi && !swap_rbj_dagger; }
+  bool links_ready() const { return links_route(QMG_DIRECT_MOBIUS); }
   // lhs = D^dagger D rhs, both applies from the links; extra_cvector holds D rhs
   void apply_M_dagger_M_links(complex<double>* lhs, complex<double>* rhs) {
     apply_M_overwrite(extra_cvector, rhs);
@@ -305,56 +340,36 @@ struct MobiusBase : public Stencil2D {
     apply_M_dagger(lhs, extra_cvector);
   }
 
-  // ---- the 4D even-odd Schur complement from the links (qmg_mobius_inv5 / qmg_mobius_hops_inv5 / qmg_mobius_schur_apply, csrc/qmg_mobius_eo.hip) ----
-  //   M = A_e - H_eo B A_o^-1 H_oe B,   M^dagger = Gamma5 [A'_e - B' H_eo A'_o^-1 B' H_oe] Gamma5   (the entry's op 1: Gamma5 M Gamma5 is not M^dagger)
-  // in the reference's Schur convention, as DwfBase has it: the arrays are addressed as full-length vectors of which the even half is the
-  // system -- a solver hands over half-length arrays --, eo_cvector is the scratch.  These methods need the links route; there is no stored
-  // fallback, so they also serve Ls = 32.  Any complex wall mass and shifts are served (the dagger has kernels of its own).
-  // whether the Schur methods can run (the links route is on); says why not, makes the scratch
-  bool schur5_ready(const char* who) {
+  virtual bool schur5_ready(const char* who, bool dagger = false) {
     if (!links_ready()) {
       std::cout << "[QMG-ERROR]: " << who << " needs the Moebius links route (direct.on, no variant swapped in); there is no stored fallback.\n";
       return false;
     }
-    if (eo_cvector == 0) eo_cvector = allocate_vector<complex<double>>(lat->get_size_cv_l());
-    return eo_cvector != 0;
+    return schur5_scratch();
   }
-  // lhs_e = M rhs_e, overwriting; lhs != rhs
-  void apply_M_schur5(complex<double>* lhs, complex<double>* rhs) {
-    if (schur5_ready("apply_M_schur5")) schur5("apply_M_schur5", lhs, rhs, 0);
-  }
-  // lhs_e = M^dagger rhs_e: two launches, as M
-  void apply_M_schur5_dagger(complex<double>* lhs, complex<double>* rhs) {
-    if (schur5_ready("apply_M_schur5_dagger")) schur5("apply_M_schur5_dagger", lhs, rhs, 1);
-  }
-  void apply_M_schur5_dagger_M(complex<double>* lhs, complex<double>* rhs) {
-    if (!schur5_ready("apply_M_schur5_dagger_M")) return;
-    if (!schur5_vector) schur5_vector = allocate_vector<complex<double>>(lat->get_size_cv_l() / 2);
-    if (schur5("apply_M_schur5_dagger_M", schur5_vector, rhs, 0)) schur5("apply_M_schur5_dagger_M", lhs, schur5_vector, 1);
-  }
-  // b_r,e = b_e - H_eo B A_o^-1 b_o, odd half zero (full-length arrays; b_r != b)
-  void prepare_M_schur5(complex<double>* b_r, complex<double>* b) {
+  // b_r,e = b_e - H_eo B A_o^-1 b_o
+  virtual void prepare_M_schur5(complex<double>* b_r, complex<double>* b) {
     if (!schur5_ready("prepare_M_schur5")) return;
     const qmg_stencil_desc d = desc();
     const long half = lat->get_size_cv_l() / 2;
     const double mr = mass.real(), mi = mass.imag();
-    qmg::ok(qmg_mobius_inv5(QMG_C64, &d, mobius_Ls, mr, mi, direct.w, M5, b5, c5, eo_cvector, b, QMG_P_CLOVER_O, QMG_MOBIUS_S_AINV, 1.0, 0.0, 1, 0, 1u,
+    qmg::ok(qmg_mobius_inv5(QMG_C64, &d, dw_Ls, mr, mi, direct.w, M5, b5, c5, eo_cvector, b, QMG_P_CLOVER_O, QMG_MOBIUS_S_AINV, 1.0, 0.0, 1, 0, 1u,
                             qmg::current_stream()), "qmg_mobius_inv5");
     copy_vector(b_r, b, half);
-    qmg::ok(qmg_mobius_hops_inv5(QMG_C64, &d, direct.gauge, mobius_Ls, mr, mi, direct.w, M5, b5, c5, b_r, eo_cvector, QMG_P_EO, QMG_MOBIUS_S_ONE, QMG_MOBIUS_R_B,
+    qmg::ok(qmg_mobius_hops_inv5(QMG_C64, &d, direct.gauge, dw_Ls, mr, mi, direct.w, M5, b5, c5, b_r, eo_cvector, QMG_P_EO, QMG_MOBIUS_S_ONE, QMG_MOBIUS_R_B,
                                  -1.0, 0.0, 0, 1, 0, 1u, qmg::current_stream()), "qmg_mobius_hops_inv5");
     zero_vector(b_r + half, half);
   }
-  // x_e = y_e, x_o = A_o^-1 (b_o - H_oe B y_e)   (x and b full-length; of y_e the even half is read)
-  void reconstruct_M_schur5(complex<double>* x, complex<double>* y_e, complex<double>* b) {
+  // x_o = A_o^-1 (b_o - H_oe B y_e)
+  virtual void reconstruct_M_schur5(complex<double>* x, complex<double>* y_e, complex<double>* b) {
     if (!schur5_ready("reconstruct_M_schur5")) return;
     const qmg_stencil_desc d = desc();
     const long half = lat->get_size_cv_l() / 2;
     const double mr = mass.real(), mi = mass.imag();
     if (x != y_e) copy_vector(x, y_e, half);
-    qmg::ok(qmg_mobius_inv5(QMG_C64, &d, mobius_Ls, mr, mi, direct.w, M5, b5, c5, x, b, QMG_P_CLOVER_O, QMG_MOBIUS_S_AINV, 1.0, 0.0, 1, 0, 1u,
+    qmg::ok(qmg_mobius_inv5(QMG_C64, &d, dw_Ls, mr, mi, direct.w, M5, b5, c5, x, b, QMG_P_CLOVER_O, QMG_MOBIUS_S_AINV, 1.0, 0.0, 1, 0, 1u,
                             qmg::current_stream()), "qmg_mobius_inv5");
-    qmg::ok(qmg_mobius_hops_inv5(QMG_C64, &d, direct.gauge, mobius_Ls, mr, mi, direct.w, M5, b5, c5, x, x, QMG_P_OE, QMG_MOBIUS_S_AINV, QMG_MOBIUS_R_B, -1.0, 0.0,
+    qmg::ok(qmg_mobius_hops_inv5(QMG_C64, &d, direct.gauge, dw_Ls, mr, mi, direct.w, M5, b5, c5, x, x, QMG_P_OE, QMG_MOBIUS_S_AINV, QMG_MOBIUS_R_B, -1.0, 0.0,
                                  0, 1, 0, 1u, qmg::current_stream()), "qmg_mobius_hops_inv5");
   }
 };
@@ -364,12 +379,8 @@ struct Mobius2D : public MobiusBase {
  protected:
   Mobius2D(Mobius2D const&);
   Mobius2D& operator=(Mobius2D const&);
-  complex<double>* scratch;   // for the in-place gamma5
 
  public:
-  double a[2 * Ls];        // gamma5 as a scale / shuffle pattern, as in Dwf2D
-  int shuffle[2 * Ls];
-
   void update_links(complex<double>* gauge_links) {   // gauge_links: DEVICE nc=1 LatticeGauge
     qmg::ok(qmg_mobius_fill(clover, hopping, gauge_links, lat->get_dim_mu(0), lat->get_dim_mu(1), Ls, mass.real(), mass.imag(), 1.0, M5, b5, c5, qmg::current_stream()),
             "qmg_mobius_fill");
@@ -379,48 +390,21 @@ struct Mobius2D : public MobiusBase {
   }
 
   Mobius2D(Lattice2D* in_lat, complex<double> mass, complex<double>* gauge_links, double b5, double c5, double M5 = -1.0)
-      : MobiusBase(in_lat, mass, M5, b5, c5, Ls), scratch(0) {
-    for (int i = 0; i < Ls; i++) {
-      a[2 * i] = 1.0; a[2 * i + 1] = -1.0;
-      shuffle[2 * i] = 2 * (Ls - 1 - i); shuffle[2 * i + 1] = 2 * (Ls - 1 - i) + 1;
-    }
-    if (lat->get_nc() != 2 * Ls) { std::cout << "[QMG-ERROR]: Mobius2D only supports Nc = 2 Ls.\n"; return; }
-    if (qmg::slab().on) { std::cout << "[QMG-ERROR]: Mobius2D is not decomposed into y-slabs.\n"; return; }
-    update_links(gauge_links);
+      : MobiusBase(in_lat, mass, M5, b5, c5, Ls) {
+    if (served("Mobius2D")) update_links(gauge_links);
   }
-  ~Mobius2D() { if (scratch) deallocate_vector(&scratch); }
 
   static int get_dof(int i = 0) { return 2 * Ls; }
   static chirality_state has_chirality() { return QMG_CHIRAL_YES; }
-
-  // (Gamma5 psi)(s, sigma) = (-1)^sigma psi(Ls-1-s, sigma)
-  virtual void gamma5(complex<double>* vec) {
-    if (!scratch) scratch = allocate_vector<complex<double>>(lat->get_size_cv_l());
-    qmg::pattern(a, shuffle, 2 * Ls, vec, scratch, (size_t)lat->get_volume());
-    copy_vector(vec, scratch, lat->get_size_cv_l());
-  }
-  virtual void gamma5(complex<double>* g5_vec, complex<double>* vec) {
-    if (g5_vec == vec) { gamma5(vec); return; }
-    qmg::pattern(a, shuffle, 2 * Ls, vec, g5_vec, (size_t)lat->get_volume());
-  }
-  virtual void chiral_projection(complex<double>*, bool) { return; }
-  virtual void chiral_projection_copy(complex<double>*, complex<double>*, bool) { return; }
-  virtual void chiral_projection_both(complex<double>*, complex<double>*) { return; }
-  virtual QMGDefaultChirality get_default_chirality() { return QMG_CHIRALITY_GAMMA_5; }
 };
 
 // A Moebius operator of run-time Ls: createDwfLs's list of Ls values.  Where the stored-stencil apply does not serve nc = 2 Ls (Ls = 32 today)
-// the operator is made all the same: both applies and the solve below come from the links, and only what needs the stored arrays is missing.
+// the operator is made all the same: both applies and the solves below come from the links, and only what needs the stored arrays is missing.
 inline MobiusBase* createMobiusLs(Lattice2D* in_lat, complex<double> mass, complex<double>* gauge_links, int Ls, double b5, double c5, double M5 = -1.0) {
   switch (Ls) {
-    case 2: return new Mobius2D<2>(in_lat, mass, gauge_links, b5, c5, M5);
-    case 4: return new Mobius2D<4>(in_lat, mass, gauge_links, b5, c5, M5);
-    case 6: return new Mobius2D<6>(in_lat, mass, gauge_links, b5, c5, M5);
-    case 8: return new Mobius2D<8>(in_lat, mass, gauge_links, b5, c5, M5);
-    case 12: return new Mobius2D<12>(in_lat, mass, gauge_links, b5, c5, M5);
-    case 16: return new Mobius2D<16>(in_lat, mass, gauge_links, b5, c5, M5);
-    case 24: return new Mobius2D<24>(in_lat, mass, gauge_links, b5, c5, M5);
-    case 32: return new Mobius2D<32>(in_lat, mass, gauge_links, b5, c5, M5);
+#define QMG_DW_LS_CASE(N) case N: return new Mobius2D<N>(in_lat, mass, gauge_links, b5, c5, M5);
+    QMG_DW_LS_LIST(QMG_DW_LS_CASE)
+#undef QMG_DW_LS_CASE
     default: break;
   }
   std::cout << "[QMG-ERROR]: Unsupported Ls " << Ls << " for the Moebius domain wall operator.\n";
@@ -454,24 +438,9 @@ inline void apply_mobius_schur5_Mdagger_M(complex<double>* lhs, complex<double>*
   ((MobiusBase*)extra_data)->apply_M_schur5_dagger_M(lhs, rhs);
 }
 
-// D x = b by CG on the normal equations of the even-odd Schur complement: prepare, M^dagger b', minv_vector_cg over the half length from the
-// even half of x as the initial guess, reconstruct.  x and b are full-length; eps is the relative residual of M^dagger M y = M^dagger b'.
-// Everything comes from the links, so this works at Ls = 32; where the links route is off nothing is solved and success is false.
+// minv_domain_wall_eo_cg on the Moebius operator (everything comes from the links, so this works at Ls = 32)
 inline inversion_info minv_mobius_eo_cg(complex<double>* x, complex<double>* b, int max_iter, double eps, MobiusBase* mobius, inversion_verbose_struct* verb = 0) {
-  const size_t n = mobius->lat->get_size_cv_l(), half = n / 2;
-  if (!mobius->schur5_ready("minv_mobius_eo_cg")) {   // nothing to iterate on: no solve, x untouched
-    inversion_info none;
-    none.name = "CG (even-odd Moebius domain wall): not run";
-    return none;
-  }
-  complex<double>* b_r = allocate_vector<complex<double>>(n);
-  complex<double>* rhs = allocate_vector<complex<double>>(half);
-  mobius->prepare_M_schur5(b_r, b);
-  mobius->apply_M_schur5_dagger(rhs, b_r);
-  const inversion_info info = minv_vector_cg(x, rhs, (int)half, max_iter, eps, apply_mobius_schur5_Mdagger_M, (void*)mobius, verb);
-  mobius->reconstruct_M_schur5(x, x, b);
-  deallocate_vector(&b_r); deallocate_vector(&rhs);
-  return info;
+  return minv_domain_wall_eo_cg(x, b, max_iter, eps, mobius, "minv_mobius_eo_cg", "CG (even-odd Moebius domain wall): not run", verb);
 }
 
 // ---------------- shared by the two nc = 1 operators: hand-rolled even-odd normal operator ----------------
